@@ -11,12 +11,20 @@ The LAST line rank 0 prints is ONE compact JSON object (< 4 KB; tests/test_api_h
   value        SURVEY.md 8(d)'s metric as written: N / median over the K timed steps of the per-call DEVICE-SYNCHRONISED wall-clock time of
                one forward + backward (max over ranks), measured with the context's pose table OFF -- every forward is a first visit of its
                camera pose, the number that transfers to SaRO-GS's time-varying scenes (`config.pose_table` says so)
+  ms_per_step  the median of the K timed steps in milliseconds (1e3 * N / value)
+A plain run does only that: set up, warm up, time the K steps (and write --dump-outputs).  Everything below needs `--full`:
   value_warm   the same protocol with the pose table on (every pose seen before: a fixed rig over an unchanged scene)
   pipelined    K steps enqueued back to back, one synchronisation at the end (rounds 1-5's headline): throughput, not the stated metric
   roofline     the dominant kernel (per-tile backward blend) against the HBM roof: algorithmic bytes per launch (SURVEY.md 8(d) formula with
                the MEASURED R_eff) / its mean duration measured with HIP events on the launch stream inside the timed region; the binding
                resource (VALU issue) beside it;  roofline_fwd: the same for the forward blend
   cpu_baseline the CPU oracle (a port, OpenMP on the host cores) timed on a bounded sample of the same workload
+  (and value_no_list_cut, stage_ms, host, sweep_1080p_cold, the R / R_eff / Q / visible counts in `config`)
+
+--dump-outputs DIR: what the last timed step handed its caller (image, radii, depth, the leaves' gradients) as float32 .npy files (sample
+indices float64), at most 64 MB in all (dump_outputs); the inputs, camera of that step included, are the same from run to run for the
+same arguments.
+
 Everything else rounds 1-5 printed in that line (per-stage tables, training-like / eval legs, the SURVEY 8f rows, a second scene) is
 `--extras`: tools/bench_extras.py, written to gpurun_out/bench_report.json or the path given and printed as an EARLIER line.
 """
@@ -60,9 +68,14 @@ def parse(argv=None):
     ap.add_argument("--sweep", type=str, default="100000,300000,1000000",
                     help="extra #Gaussians points of the metric's 'vs #Gaussians' (N=1 only; same protocol, table off); '' disables")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline objects, per-stage times, the pose-table-on and no-list-cut legs, pipelined throughput, "
+                         "the #Gaussians sweep and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (image, radii, depth, leaf gradients) to DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--extras", nargs="?", const=os.path.join(ROOT, "gpurun_out", "bench_report.json"), default=None, metavar="PATH",
                     help="also run the side legs of tools/bench_extras.py (per-stage tables at 1 M, shell scene, BASELINE cfg2 / cfg3 shapes, two views in "
-                         "flight, eval FPS, training-like iterations, SURVEY 8f rows): written to PATH and printed as an earlier line")
+                         "flight, eval FPS, training-like iterations, SURVEY 8f rows): written to PATH and printed as an earlier line; implies --full")
     ap.add_argument("--ablate", type=int, default=0, help="kernel ablation experiments (not a valid bench)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="library option for A/B experiments (repeatable)")
     ap.add_argument("--ppl", type=int, default=0, help="force pixels per lane of both blend kernels (0 = auto)")
@@ -116,6 +129,8 @@ class Workload:
         self.g = t(scenes.upstream_grad(H, W, 1))
         self.raster = self.rasters[0]
         self.dev = dev
+        self.capture_step = -1       # step() whose step_no reaches this keeps what it handed its caller in self.captured (--dump-outputs)
+        self.captured = None
         import view_parallel
         self.vp = view_parallel
 
@@ -131,6 +146,10 @@ class Workload:
         color, radii, depth = raster(means3D=L["means3D"], means2D=self.means2D, opacities=L["opacities"],
                                      shs=L["shs"], scales=L["scales"], rotations=L["rotations"])
         color.backward(self.g)
+        if self.step_no == self.capture_step:
+            # references only (no copy inside the step); a bucket's gradient views are final once the exchange below has run
+            self.captured = dict(color=color.detach(), radii=radii, depth=depth.detach(),
+                                 **{"grad_" + k: p.grad for k, p in L.items()}, grad_means2D=self.means2D.grad)
         if bucket is None and not self.keep_grads:
             # optimizer.zero_grad(set_to_none=True) where the reference's loop has it: at the END of the iteration (train.py:221), behind the backward's
             # launches -- the host does it while the GPU works, not in front of the next forward's first launch
@@ -503,6 +522,47 @@ def compact_line(result: dict) -> str:
     return line
 
 
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
+DUMP_IMAGE_LIMIT = 40 << 20    # images up to this size are written whole, larger ones at a fixed sample of pixels
+DUMP_ROWS = 65536              # per-Gaussian arrays: a fixed sample of this many Gaussians (all of them below it)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, captured, P, H, W):
+    """--dump-outputs: the arrays the last timed step handed its caller -- color [3, H, W], depth [1, H, W] and radii [P] of the forward,
+    the gradients of means3D, opacities, shs, scales, rotations and means2D of the backward -- as DIR/<name>.npy, float32 (the sample indices float64).  The images
+    are written whole up to DUMP_IMAGE_LIMIT bytes (beyond it: the pixels of `pixels.npy`, a seeded sample of flat indices y * W + x);
+    per-Gaussian arrays at the Gaussians of `rows.npy` (a seeded sample of DUMP_ROWS indices, sorted; every Gaussian when P is smaller).
+    The samples depend on P, H and W only, so two builds run with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(P) if P <= DUMP_ROWS else np.sort(rng.choice(P, size=DUMP_ROWS, replace=False))
+    pixels = None
+    if (3 + 1) * H * W * 4 > DUMP_IMAGE_LIMIT:
+        pixels = np.sort(rng.choice(H * W, size=DUMP_IMAGE_LIMIT // (4 * 4 + 8), replace=False))     # 4 float32 channels + its float64 index
+    arrays = {"rows": rows.astype(np.float64)}
+    if pixels is not None:
+        arrays["pixels"] = pixels.astype(np.float64)
+    for name, t in captured.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if name in ("color", "depth"):
+            t = t.reshape(t.shape[0], H * W)
+            if pixels is not None:
+                t = t[:, torch.as_tensor(pixels, device=t.device)]
+            t = t.reshape((t.shape[0], H, W) if pixels is None else t.shape)
+        elif len(rows) < P:
+            t = t[torch.as_tensor(rows, device=t.device)]
+        arrays[name] = t.to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (> {DUMP_LIMIT})")
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return total
+
+
 def main():
     a = parse()
     if a.gpus < 1:
@@ -569,14 +629,16 @@ def main():
         if a.exchange == "factors":
             vp.overlap_factor_exchange(True)     # the all-gather starts between the two phases of the backward
 
-    names = [_C.lib().gsrast_profile_kernel_name(k).decode() for k in range(_C.lib().gsrast_profile_kernel_count())]
-    kid = {n: i for i, n in enumerate(names)}
+    full = a.full or bool(a.extras)
 
     # ---- headline leg: pose table OFF (every forward a first visit), per-call synchronised ----
     _C.set_option("no_order_hint", 1)
-    _C.profile_reset()
-    # only the roofline kernel is bracketed with events inside the timed region (2 records/step, ~5 us of GPU idle each)
-    _C.set_option("profile", 1 << kid["blend_bwd"])
+    if full:
+        names = [_C.lib().gsrast_profile_kernel_name(k).decode() for k in range(_C.lib().gsrast_profile_kernel_count())]
+        kid = {n: i for i, n in enumerate(names)}
+        _C.profile_reset()
+        # only the roofline kernel is bracketed with events inside the timed region (2 records/step, ~5 us of GPU idle each)
+        _C.set_option("profile", 1 << kid["blend_bwd"])
     n_pre = 0
     if a.preroll_ms > 0:        # settle the device first (see --preroll-ms); reported as preroll_steps
         t_pre = time.perf_counter()
@@ -588,37 +650,48 @@ def main():
             # the same elapsed time on every rank, so every rank runs the same number of rounds (and collectives)
             if vp.max_over_ranks(time.perf_counter() - t_pre, dev) * 1e3 >= a.preroll_ms:
                 break
+    # the preroll's length follows the wall clock: the warm-up and timed steps start at the first pose of the ring whatever it was, so
+    # that every step after it (the last timed one, whose outputs --dump-outputs writes, among them) renders the same camera every run
+    wl.step_no = 0
     for _ in range(a.warmup):
         wl.step(bucket, world)
     torch.cuda.synchronize(dev)
-    _C.profile_reset()
+    if full:
+        _C.profile_reset()
+    if a.dump_outputs:
+        wl.capture_step = wl.step_no + a.steps
     med, mean, per_step = timed_sync(wl, a.steps, bucket, world, vp, dev)
-    prof = _C.profile_read()
-    _C.set_option("profile", 0)
     late_cold = _query(_C, "last_late")
-    d_pipe_cold = timed(wl, a.steps, 0, bucket, world, vp, dev)
-    host_cold = dict(HOST_STEPS)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, wl.captured, P, H, W)
+    wl.captured, wl.capture_step = None, -1
 
-    st, per_kernel, pk = None, None, None
-    if world == 1 and not exchanging:
-        st = wl.stats()             # (measured under the headline's options: table off)
-        per_kernel, pk = stage_table(_C, wl, st, P, deg, H)
-    elif rank == 0:
-        st = wl.stats()
+    st, per_kernel, pk, prof, host_cold, d_pipe_cold = None, None, None, None, {}, None
+    if full:
+        prof = _C.profile_read()
+        _C.set_option("profile", 0)
+        d_pipe_cold = timed(wl, a.steps, 0, bucket, world, vp, dev)
+        host_cold = dict(HOST_STEPS)
+        if world == 1 and not exchanging:
+            st = wl.stats()             # (measured under the headline's options: table off)
+            per_kernel, pk = stage_table(_C, wl, st, P, deg, H)
+        elif rank == 0:
+            st = wl.stats()
     _C.set_option("no_order_hint", 0)
 
     # ---- the same protocol with the pose table ON: every pose seen before (an unchanged scene over a fixed rig) ----
-    warm_warmup = max(a.warmup, 3 * n_poses)
-    for _ in range(warm_warmup):
-        wl.step(bucket, world)
-    torch.cuda.synchronize(dev)
-    med_w, mean_w, _ = timed_sync(wl, a.steps, bucket, world, vp, dev)
-    late_warm = _query(_C, "last_late")
-    d_pipe_warm = timed(wl, a.steps, 0, bucket, world, vp, dev)
+    if full:
+        warm_warmup = max(a.warmup, 3 * n_poses)
+        for _ in range(warm_warmup):
+            wl.step(bucket, world)
+        torch.cuda.synchronize(dev)
+        med_w, mean_w, _ = timed_sync(wl, a.steps, bucket, world, vp, dev)
+        late_warm = _query(_C, "last_late")
+        d_pipe_warm = timed(wl, a.steps, 0, bucket, world, vp, dev)
 
     # ---- ... and with the LIST CUT switched off altogether (the floor for a scene no prediction can cut) ----
     med_nc = None
-    if world == 1 and not exchanging:
+    if full and world == 1 and not exchanging:
         _C.set_option("no_list_cut", 1)
         try:
             for _ in range(a.warmup):
@@ -635,8 +708,6 @@ def main():
         ranks_info = [None] * torch.distributed.get_world_size()
         torch.distributed.all_gather_object(ranks_info, mine)
     if rank == 0:
-        bwd_ms = prof["blend_bwd"][0] / max(prof["blend_bwd"][1], 1)
-        fwd_ms = pk["blend_fwd"][0] / max(pk["blend_fwd"][1], 1) if per_kernel else 0.0   # (the event-bracketed all-stages pass behind the timed region)
         try:
             nccl_version = ".".join(str(x) for x in torch.cuda.nccl.version())
         except Exception:       # noqa: BLE001
@@ -649,24 +720,30 @@ def main():
             "preroll_steps": n_pre,
             # the K-step region as a whole (barrier + synchronize on both sides, every step synchronised inside): wall time / K
             "mean_ms_per_step": round(mean * 1e3, 4),
-            "value_warm": round(world / med_w, 3), "ms_per_step_warm": round(med_w * 1e3, 4), "warmup_warm": warm_warmup,
-            "value_no_list_cut": round(1.0 / med_nc, 3) if med_nc else None,
-            "pipelined": {"views_per_s_cold": round(world * a.steps / d_pipe_cold, 1), "views_per_s_warm": round(world * a.steps / d_pipe_warm, 1),
-                          "note": "K steps back to back, one sync (rounds 1-5's headline): throughput, not the metric"},
             "config": {"workload": f"BASELINE configs[4] stress-1080p: {scene_fn}(P={P}, seed 0) SH{deg}, {W}x{H}, one view per GPU, fwd+bwd",
                        "protocol": "SURVEY 8d: 1 / median of per-call device-synchronised wall-clock fwd+bwd",
                        "pose_table": "off for value (every pose a first visit); on for value_warm",
                        "gaussians": P, "width": W, "height": H, "sh_degree": deg, "exp_mode": exp_mode, "poses_per_rank": n_poses,
-                       "views_per_step": world, "R": st["R"], "R_listed": st["R_listed"], "Q": st["Q"], "R_eff": st["R_eff"], "visible": st["P_vis"],
-                       "late_gaussians_cold": late_cold, "late_gaussians_warm": late_warm,
+                       "views_per_step": world, "late_gaussians_cold": late_cold,
                        "word_fork": _C.get_option("word_fork"),
                        "exchange": a.exchange if exchanging else None},
-            "roofline": roofline_of(st, bwd_ms, P),
-            "roofline_fwd": roofline_of(st, fwd_ms, P, kernel="blend_fwd_cull_kernel") if fwd_ms > 0 else None,
-            "stage_ms": {k: v["ms"] for k, v in per_kernel.items()} if per_kernel else None,
-            "host": {"enqueue_ms_median": host_cold.get("median"), "device_mallocs_in_timed_steps": host_cold.get("device_mallocs")},
             "per_step_ms": {"min": min(per_step), "max": max(per_step)} if per_step else None,
         }
+        if full:
+            bwd_ms = prof["blend_bwd"][0] / max(prof["blend_bwd"][1], 1)
+            fwd_ms = pk["blend_fwd"][0] / max(pk["blend_fwd"][1], 1) if per_kernel else 0.0   # (the event-bracketed all-stages pass behind the timed region)
+            result.update({
+                "value_warm": round(world / med_w, 3), "ms_per_step_warm": round(med_w * 1e3, 4), "warmup_warm": warm_warmup,
+                "value_no_list_cut": round(1.0 / med_nc, 3) if med_nc else None,
+                "pipelined": {"views_per_s_cold": round(world * a.steps / d_pipe_cold, 1), "views_per_s_warm": round(world * a.steps / d_pipe_warm, 1),
+                              "note": "K steps back to back, one sync (rounds 1-5's headline): throughput, not the metric"},
+                "roofline": roofline_of(st, bwd_ms, P),
+                "roofline_fwd": roofline_of(st, fwd_ms, P, kernel="blend_fwd_cull_kernel") if fwd_ms > 0 else None,
+                "stage_ms": {k: v["ms"] for k, v in per_kernel.items()} if per_kernel else None,
+                "host": {"enqueue_ms_median": host_cold.get("median"), "device_mallocs_in_timed_steps": host_cold.get("device_mallocs")},
+            })
+            result["config"].update({"R": st["R"], "R_listed": st["R_listed"], "Q": st["Q"], "R_eff": st["R_eff"], "visible": st["P_vis"],
+                                     "late_gaussians_warm": late_warm})
         if exchanging:
             result["config"].update({
                 "exchange_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
@@ -676,7 +753,7 @@ def main():
                 "exchange_bytes_per_rank_and_step": getattr(wl, "exchanged", None)})
 
     # ---- the metric's "vs #Gaussians": more points at 1080p, same protocol (single GPU only) ----
-    if rank == 0 and world == 1 and a.sweep:
+    if full and rank == 0 and world == 1 and a.sweep:
         del wl
         torch.cuda.empty_cache()
         sweep = {}
@@ -684,7 +761,7 @@ def main():
             sweep[str(p)] = result["value"] if p == P else sweep_point(rast, scenes, vp, p, W, H, deg, dev, a.steps, a.warmup, n_poses)
         sweep[str(P)] = result["value"]
         result["sweep_1080p_cold"] = sweep
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(scenes, P, W, H, deg, a.cpu_budget_s)
         except Exception as e:  # the baseline is reported, never required for the GPU number

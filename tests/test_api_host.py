@@ -184,4 +184,46 @@ def test_bench_extras_and_tools_import_without_a_gpu():
         assert hasattr(bench, name), name
     a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
     assert a.steps == 20 and a.warmup == 5 and a.extras is None and a.exchange == "gather" and a.gaussians == 3_000_000
+    assert not a.full and a.dump_outputs is None
     assert bench.parse(["--extras"]).extras.endswith("bench_report.json")
+    assert bench.parse(["--full", "--dump-outputs", "out"]).full and bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): float32 / float64 .npy files, at most 64 MB in all, images whole at 1080p and sampled at
+    fixed pixels beyond DUMP_IMAGE_LIMIT, per-Gaussian arrays at fixed rows -- the same rows and pixels for the same P, H, W in every run."""
+    import os
+    import sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    for P, H, W, whole_image in ((3_000_000, 1080, 1920, True), (5000, 112, 160, True), (200_000, 4096, 4096, False)):
+        g = torch.Generator().manual_seed(P)
+        cap = dict(color=torch.rand(3, H, W, generator=g), radii=torch.randint(0, 50, (P,), dtype=torch.int32, generator=g),
+                   depth=torch.rand(1, H, W, generator=g), grad_means3D=torch.rand(P, 3, generator=g), grad_opacities=torch.rand(P, 1, generator=g),
+                   grad_shs=torch.rand(P, 16, 3, generator=g), grad_scales=torch.rand(P, 3, generator=g), grad_rotations=torch.rand(P, 4, generator=g),
+                   grad_means2D=None)
+        runs = []
+        for k in range(2):
+            d = tmp_path / f"{P}_{k}"
+            total = bench.dump_outputs(str(d), cap, P, H, W)
+            files = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+            assert total == sum(v.nbytes for v in files.values()) <= bench.DUMP_LIMIT == 64 << 20
+            assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+            assert "grad_means2D" not in files
+            runs.append(files)
+        assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+        files = runs[0]
+        rows = files["rows"].astype(np.int64)
+        assert len(rows) == min(P, bench.DUMP_ROWS) and np.all(np.diff(rows) > 0) and rows[-1] < P
+        for name in ("radii", "grad_means3D", "grad_opacities", "grad_shs", "grad_scales", "grad_rotations"):
+            assert np.array_equal(files[name], cap[name].numpy()[rows].astype(np.float32)), name
+        if whole_image:
+            assert "pixels" not in files and np.array_equal(files["color"], cap["color"].numpy()) and files["depth"].shape == (1, H, W)
+        else:
+            px = files["pixels"].astype(np.int64)
+            assert np.all(np.diff(px) > 0) and px[-1] < H * W
+            assert np.array_equal(files["color"], cap["color"].numpy().reshape(3, -1)[:, px])
+            assert np.array_equal(files["depth"], cap["depth"].numpy().reshape(1, -1)[:, px])

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 ( time timeout 900 python bench.py $extra --extras $out/bench_report_${tag}.json > $out/bench_${tag}_with_extras.out 2> $out/bench_${tag}.err ) 2> $out/bench_${tag}_with_extras.time
 tail -1 $out/bench_${tag}_with_extras.out > $out/bench_${tag}.json
 ( time timeout 600 python bench.py $extra --steps 20 --warmup 5 > $out/bench_${tag}_driver_command.json 2>> $out/bench_${tag}.err ) 2> $out/bench_${tag}_driver_command.time
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o trace -- python bench.py $extra --sweep "" --no-cpu-baseline > $out/bench_${tag}_under_rocprof.json 2> $out/rocprof.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o trace -- python bench.py $extra --full --sweep "" --no-cpu-baseline > $out/bench_${tag}_under_rocprof.json 2> $out/rocprof.err
 f=$(ls $out/trace/*kernel_trace.csv 2>/dev/null | head -1)
 [ -n "$f" ] && python tools/rocprof_summary.py $f > $out/${tag}_kernel_stats_bench_command.txt
 s=$(ls $out/trace/*kernel_stats.csv 2>/dev/null | head -1)
