@@ -322,6 +322,46 @@ int gsrast_backward_ex(const gsrast_options* options,
                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream);
 
+/* ---- Differentiable alpha and accumulated depth (no counterpart in the reference, whose only depth output is the median depth
+ * above, whose gradient it drops) ----
+ * gsrast_forward_aux = gsrast_forward_ex that also writes, for every pixel, over the same contributors and the same early stop as the
+ * colour:
+ *     out_acc_depth [1][H][W] = sum_i alpha_i T_i z_i     z_i = Gaussian i's view-space depth; the background adds nothing; NOT normalised
+ *                                                        (expected depth = acc_depth / alpha, left to the caller)
+ *     out_alpha     [1][H][W] = 1 - T_final
+ * Both must be non-NULL.  Everything else it computes and leaves in the state buffers is what gsrast_forward_ex computes.
+ * gsrast_backward_aux = gsrast_backward_ex plus the upstream gradients dL_dacc_depth / dL_dalpha [1][H][W]; either may be NULL (= zero),
+ * with both NULL it is exactly gsrast_backward_ex.  The gradients reach the same outputs as the colour's (means3D through the view-space
+ * depth as well, means2D, opacities, scales / rotations or cov3D; the raw leaves on the raw pair) with the colour's conventions (the 0.99
+ * clamp passes gradients through).  The backward rebuilds the depth recurrence from final_T and n_contrib back to front, as the colour's:
+ * it needs nothing of the forward's aux outputs, so an aux backward on the state of a plain gsrast_forward_ex is valid.  With
+ * options->backward_phase, pass the same two pointers to both phases.
+ * gsrast_forward_raw_aux / gsrast_backward_raw_aux: the same for the raw pair below.
+ * Only the default culled blend kernels have the aux outputs: options->cull == 0 (and, forward, fwd_pixels_per_lane != 0) return
+ * GSRAST_E_ARG.  The aux backward always runs the one-pixel-per-lane transposed blend backward, whatever bwd_pixels_per_lane says (the
+ * automatic choice would take two pixels per lane from 8 192 tiles, 4K images, on).  Argument errors return before any device work. */
+int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
+                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
+                       gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                       gsrast_alloc_fn image_alloc, void* image_ctx,
+                       int P, int D, int M, const float* background, int width, int height,
+                       const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                       float tan_fovx, float tan_fovy, int prefiltered,
+                       float* out_color, float* out_depth, int* radii, void* stream,
+                       float* out_acc_depth, float* out_alpha);
+int gsrast_backward_aux(const gsrast_options* options,
+                        int P, int D, int M, int R, const float* background, int width, int height,
+                        const float* means3D, const float* shs, const float* colors_precomp,
+                        const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                        const float* viewmatrix, const float* projmatrix, const float* campos,
+                        float tan_fovx, float tan_fovy, const int* radii,
+                        char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                        const float* dL_dacc_depth, const float* dL_dalpha);
+
 /* Process defaults of the options above (and process-wide diagnostics): "exp_mode" 0 = fixed-sequence exp (bit-reproducible vs the CPU oracle), 1 = libm-grade
  * expf, 2 = hardware v_exp_f32;  "profile" = bit mask of kernel ids (gsrast_profile_kernel_name) whose launches are bracketed
  * with HIP events on the launch stream, -1 = all, 0 = off;
@@ -443,6 +483,22 @@ int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int 
                         const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
                         const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                         const float* dL_dpix, const gsrast_raw_grads* grads, void* stream);
+/* the raw pair with the aux outputs / gradients (gsrast_forward_aux / gsrast_backward_aux above) */
+int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
+                           gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
+                           gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                           gsrast_alloc_fn image_alloc, void* image_ctx,
+                           int P, int D, int M, const float* background, int width, int height,
+                           const gsrast_raw_inputs* inputs, float scale_modifier,
+                           const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                           float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
+                           float* out_acc_depth, float* out_alpha);
+int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
+                            const gsrast_raw_inputs* inputs, float scale_modifier,
+                            const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                            const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                            const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
+                            const float* dL_dacc_depth, const float* dL_dalpha);
 
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose

@@ -128,7 +128,10 @@ __device__ __forceinline__ bool strip_may_touch(const float4 a, const float cz, 
 }
 
 // Forward blend, 4 wave64 per tile, one pixel per lane, with wave-level culling (see above).
-template <int EXPMODE>
+// AUX: also the differentiable geometry outputs over the same contributors and the same early stop as the colour --
+// acc_depth = sum_i alpha_i T_i z_i (z = the view-space depth of rec1.z; the background adds nothing; not normalised) and
+// alpha = 1 - T_final.  The AUX = false instantiation is the plain kernel (no extra register, no extra store).
+template <int EXPMODE, bool AUX = false>
 __device__ __forceinline__ void
 blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                       const uint32_t* __restrict__ order, int W, int H,
@@ -152,7 +155,8 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
                       // their full lists (the launch with `pred`); every other tile is final after this launch
                       unsigned char* __restrict__ tile_flags = nullptr,
                       uint32_t cut_margin_x4 = GSRAST_CUT_MARGIN_X4 /* round 5: the context's margin (6 = 1.5 x; it widens while completion passes are reported) */,
-                      unsigned char* __restrict__ untouched = nullptr /* GeomLayout::untouched: byte i cleared = some pixel consumed Gaussian i */)
+                      unsigned char* __restrict__ untouched = nullptr /* GeomLayout::untouched: byte i cleared = some pixel consumed Gaussian i */,
+                      float* __restrict__ out_acc_depth = nullptr, float* __restrict__ out_alpha = nullptr /* AUX: [H][W] each */)
 {
     constexpr uint32_t FB = 256;                  // instances staged per batch (64 / 128 / 256 measured equal)
     if (pred && *pred == 0u) return;
@@ -209,6 +213,7 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
     bool cut_here = false;
 
     float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, Dm = 15.0f;
+    float Dacc = 0.0f;                            // AUX: accumulated depth
     uint32_t last = 0;
     // A finished pixel (T would drop below 1e-4, forward.cu:377-381) moves to x = FAR: its power becomes ~ -1e30 x conic
     // (finite: conic entries are <= 1/0.3), so it fails the skip test like any far pixel and needs no flag in the loop.
@@ -306,6 +311,7 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
                     C0 = __builtin_fmaf(c.x * alpha, T, C0);
                     C1 = __builtin_fmaf(c.y * alpha, T, C1);
                     C2 = __builtin_fmaf(c.z * alpha, T, C2);
+                    if constexpr (AUX) Dacc = __builtin_fmaf(b.z * alpha, T, Dacc);       // the colour's association, z as a fourth channel
                     T = test_T;
                     last = base + j + 1;
                 }
@@ -345,6 +351,7 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
         out_color[plane + pid] = __builtin_fmaf(T, bg1, C1);
         out_color[2 * plane + pid] = __builtin_fmaf(T, bg2, C2);
         out_depth[pid] = Dm;
+        if constexpr (AUX) { out_acc_depth[pid] = Dacc; out_alpha[pid] = 1.0f - T; }
     }
     uint32_t m = last;
 #pragma unroll
@@ -419,7 +426,7 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
 // ChainGate): every workgroup counts itself out; the last one knows the launch's verdict (cut_scalars[SC_UNDONE]: tiles whose cut list was
 // too short), copies it into the context's own word for the pass's predicated launches and, if it is "none", releases the caller's stream.
 struct GateArgs { uint32_t* count /* zeroed by preprocess_fwd */; uint32_t* pred; uint32_t* done; uint32_t seq; };
-template <int EXPMODE>
+template <int EXPMODE, bool AUX = false>
 __global__ void __launch_bounds__(256)
 blend_fwd_cull_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                       const uint32_t* __restrict__ order, int W, int H,
@@ -430,10 +437,12 @@ blend_fwd_cull_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
                       uint32_t* __restrict__ bucket_cnt, uint16_t* __restrict__ bucket_list, int order_from_buckets,
                       float4* __restrict__ zero4, uint32_t n_zero4, HintTable* __restrict__ hints, const uint32_t* __restrict__ hint_sel,
                       const uint32_t* __restrict__ zcut_used, uint32_t* __restrict__ cut_scalars, const uint32_t* __restrict__ pred,
-                      unsigned char* __restrict__ tile_flags, GateArgs gate, uint32_t cut_margin_x4, unsigned char* __restrict__ untouched)
+                      unsigned char* __restrict__ tile_flags, GateArgs gate, uint32_t cut_margin_x4, unsigned char* __restrict__ untouched,
+                      float* __restrict__ out_acc_depth, float* __restrict__ out_alpha /* AUX only: [H][W] each */)
 {
-    blend_fwd_cull_body<EXPMODE>(ranges, point_list, order, W, H, gx, ntiles, rec0, rec1, rec2, bg, out_color, out_depth, final_T, n_contrib, tile_max,
-                                 bucket_cnt, bucket_list, order_from_buckets, zero4, n_zero4, hints, hint_sel, zcut_used, cut_scalars, pred, tile_flags, cut_margin_x4, untouched);
+    blend_fwd_cull_body<EXPMODE, AUX>(ranges, point_list, order, W, H, gx, ntiles, rec0, rec1, rec2, bg, out_color, out_depth, final_T, n_contrib, tile_max,
+                                      bucket_cnt, bucket_list, order_from_buckets, zero4, n_zero4, hints, hint_sel, zcut_used, cut_scalars, pred, tile_flags, cut_margin_x4, untouched,
+                                      out_acc_depth, out_alpha);
     // (no fence: a release fence here writes the L2 back once per workgroup -- measured: the launch 0.24 -> 0.62 ms.  None is needed: the
     // verdict travels in device-scope atomics, each workgroup's has returned before it counts itself out, and everything else the blend
     // wrote is ordered by the end of the kernel -- the wait behind it is a later command on the same stream)
@@ -1006,7 +1015,12 @@ blend_bwd_cull_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
 #else
 #define GSRAST_BWD_OCC
 #endif
-template <int EXPMODE>
+// AUX: the gradients of blend_fwd_cull_kernel<.., true>'s acc_depth and alpha as well (dL_dacc_depth / dL_dalpha [H][W], either may be
+// null = zero).  They need nothing of the forward's aux outputs: the depth recurrence is rebuilt back to front from final_T and n_contrib
+// like the colour's.  Per pair dL/dalpha gains (z - acD) dD (acD: the accumulated depth behind the pair), the background term becomes
+// -T_final (bg . dp - dA) (alpha = 1 - T_final), and dL/dz = sum over pixels of alpha T dD -- a fourth colour-like sum of the
+// transposed phase, committed to float 9 of the record (preprocess_bwd_kernel adds it to the gradient of the view-space z).
+template <int EXPMODE, bool AUX = false>
 __global__ void __launch_bounds__(256) GSRAST_BWD_OCC
 blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                         const uint32_t* __restrict__ order, int W, int H,
@@ -1016,7 +1030,8 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                         const uint32_t* __restrict__ tile_max, const float* __restrict__ dL_dpix,
                         float* __restrict__ grec /*[P][GREC]: per-Gaussian gradient records, zero on entry*/,
                         const uint32_t* __restrict__ bucket_cnt, const uint16_t* __restrict__ bucket_list,
-                        uint32_t* __restrict__ fork_word /* or null: "this kernel has started" for a stream that waits for it (gsrast_capi.hip: WORD FORKS) */, uint32_t fork_seq)
+                        uint32_t* __restrict__ fork_word /* or null: "this kernel has started" for a stream that waits for it (gsrast_capi.hip: WORD FORKS) */, uint32_t fork_seq,
+                        const float* __restrict__ dL_dacc_depth = nullptr, const float* __restrict__ dL_dalpha = nullptr /* AUX only */)
 {
 #pragma clang fp contract(fast)
     if (fork_word && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(fork_word, fork_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1040,6 +1055,9 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
     // {u, dch} of the current group, [instance][pixel of the wave's strip]
     __shared__ float2 pbuf[NW][GB][PS];
     __shared__ uint32_t s_tile;
+    // AUX: dL/dacc_depth of the wave's 64 pixels, read by the transposed phase (1 KB of LDS; in registers beside dpr it took the kernel
+    // from 80 to 97 VGPRs = four waves per SIMD instead of six).  Unreferenced -- and not allocated -- without AUX.
+    __shared__ float sdD[NW][64];
     if (blockIdx.x >= ntiles) return;
     const uint32_t tile = bucket_cnt ? tile_from_buckets_global(bucket_cnt + XCD_GROUPS * WORK_BUCKETS, bucket_list + (size_t)XCD_GROUPS * WORK_BUCKETS * xcd_group_tiles((uint32_t)gx, ntiles), ntiles, blockIdx.x, &s_tile)
                                      : (order ? order[blockIdx.x] : blockIdx.x);
@@ -1077,8 +1095,14 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
     float T = Tf;
     const uint32_t last = inside ? n_contrib[pid] : 0u;
     const float dp0 = inside ? dL_dpix[pid] : 0.f, dp1 = inside ? dL_dpix[plane + pid] : 0.f, dp2 = inside ? dL_dpix[2 * plane + pid] : 0.f;
-    const float tfbg = -Tf * (bg0 * dp0 + bg1 * dp1 + bg2 * dp2);
+    float dD = 0.f, dA = 0.f;                     // AUX: dL/dacc_depth, dL/dalpha of the pixel
+    if constexpr (AUX) {
+        dD = (inside && dL_dacc_depth) ? dL_dacc_depth[pid] : 0.f;
+        dA = (inside && dL_dalpha) ? dL_dalpha[pid] : 0.f;
+    }
+    const float tfbg = AUX ? -Tf * ((bg0 * dp0 + bg1 * dp1 + bg2 * dp2) - dA) : -Tf * (bg0 * dp0 + bg1 * dp1 + bg2 * dp2);
     float ac0 = 0.f, ac1 = 0.f, ac2 = 0.f;
+    float acD = 0.f;                              // AUX: accumulated depth behind the current contributor
     uint32_t strip_last;
     {
         uint32_t m = last;                            // deepest position the strip needs (wave-uniform)
@@ -1100,6 +1124,7 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
         for (int i = 0; i < 8; i++) { const float4 v = ex[kk + 8 * i]; dpr[i][0] = v.x; dpr[i][1] = v.y; dpr[i][2] = v.z; }
         __builtin_amdgcn_wave_barrier();
     }
+    if constexpr (AUX) { sdD[wave][lane] = dD; __builtin_amdgcn_wave_barrier(); }       // (same wave: read back in order)
     // transposed phase: this lane's role
     const unsigned k = lane & 7u, jj = lane >> 3;
     const float commit_scale = k == 0 ? -0.5f * (float)W : k == 1 ? -0.5f * (float)H : (k >= 2 && k <= 4) ? -0.5f : 1.0f;
@@ -1181,6 +1206,10 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                     ac0 = alpha * c0 + om * ac0;
                     ac1 = alpha * c1 + om * ac1;
                     ac2 = alpha * c2 + om * ac2;
+                    if constexpr (AUX) {        // z as a fourth channel with a black background
+                        dL_dalpha += (b.z - acD) * dD;
+                        acD = alpha * b.z + om * acD;
+                    }
                     dL_dalpha *= T;
                     dL_dalpha += tfbg * rcp1ma;
                     dch = alpha * T; u = G * dL_dalpha;
@@ -1195,7 +1224,7 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
             const uint32_t j = g * GB + jj;
             const float4 a = s0[j];
             const float4 b = s1[j];
-            float v8[8], Cb = 0.f;
+            float v8[8], Cb = 0.f, Cd = 0.f;        // (Cd: AUX, sum of alpha T dL/dacc_depth)
             const float2* urow = &pbuf[wave][jj][k];
             if constexpr (B8) {
                 // Round 5: SEPARABLE moments.  In the 8 x 8 block lane (k, jj) walks ONE column (pixel k + 8 i = column k of row i): dx is the
@@ -1215,6 +1244,7 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                     if (i == 1) { M1 += uu; M2 += uu; }
                     else if (i > 1) { M1 = __builtin_fmaf(uu, (float)i, M1); M2 = __builtin_fmaf(uu, (float)(i * i), M2); }
                     Cr = __builtin_fmaf(dd, dpr[i][0], Cr); Cg = __builtin_fmaf(dd, dpr[i][1], Cg); Cb = __builtin_fmaf(dd, dpr[i][2], Cb);
+                    if constexpr (AUX) Cd = __builtin_fmaf(dd, sdD[wave][k + 8 * i], Cd);
                 }
                 const float dx = a.x - pxk0, by = a.y - sy0;
                 const float m0 = M0 * b.y, m1 = M1 * b.y, m2 = M2 * b.y;  // the opacity factor of dL/dG = opacity * dL/dalpha, once
@@ -1237,22 +1267,25 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                     Sxx = __builtin_fmaf(gxv, dx, Sxx); Sxy = __builtin_fmaf(gxv, dy, Sxy); Syy = __builtin_fmaf(gyv, dy, Syy);
                     Su += uu;
                     Cr = __builtin_fmaf(dd, dpr[i][0], Cr); Cg = __builtin_fmaf(dd, dpr[i][1], Cg); Cb = __builtin_fmaf(dd, dpr[i][2], Cb);
+                    if constexpr (AUX) Cd = __builtin_fmaf(dd, sdD[wave][k + 8 * i], Cd);
                 }
                 Sx *= b.y; Sy *= b.y; Sxx *= b.y; Sxy *= b.y; Syy *= b.y;
                 v8[0] = Sx * a.z + Sy * a.w; v8[1] = Sy * b.x + Sx * a.w; v8[2] = Sxx; v8[3] = Sxy; v8[4] = Syy; v8[5] = Su; v8[6] = Cr; v8[7] = Cg;
             }
             const float tot = group8_sum8_transposed(v8, lane);     // lane (k, jj): total of value k for instance jj
             const float tb = group8_sum(Cb);
+            const float td = AUX ? group8_sum(Cd) : 0.f;
             if ((alive >> jj) & 1u) {
                 lds_add_f32(&acc[j][k], tot * commit_scale);
                 if (k == 0u) lds_add_f32(&acc[j][8], tb);
+                if constexpr (AUX) { if (k == 1u) lds_add_f32(&acc[j][9], td); }
             }
         }
         __syncthreads();
-        // commit: 16 adjacent lanes per staged instance, lane q < 9 adds sum q to float q of the Gaussian's 64-byte record
+        // commit: 16 adjacent lanes per staged instance, lane q < 9 (AUX: 10) adds sum q to float q of the Gaussian's 64-byte record
         for (uint32_t e = t; e < cnt * 16u; e += NT) {
             const uint32_t slot = e >> 4, q = e & 15u;
-            if (q < 9u) {
+            if (q < (AUX ? 10u : 9u)) {
                 const float v = acc[slot][q];
                 if (v != 0.f) atomicAdd(grec + (size_t)sid[slot] * GREC + q, v);
             }

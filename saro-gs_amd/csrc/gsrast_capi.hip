@@ -680,6 +680,8 @@ struct BlendArgs {
     uint32_t cut_margin_x4 = 6;                                  // forward: the next cut depth's margin (gsrast_context::cut_margin)
     unsigned char* untouched = nullptr;                          // forward (culling kernel): GeomLayout::untouched
     uint32_t* fork_word = nullptr; uint32_t fork_seq = 0;        // backward (transposed kernel): the word fork's signal (SideStream)
+    float *oad = nullptr, *oal = nullptr;                        // forward (culling kernel), aux: acc_depth / alpha -- non-null selects AUX
+    const float *dad = nullptr, *dal = nullptr;                  // backward, aux: dL/dacc_depth / dL/dalpha (either may be null)
 };
 template <int MODE, int PPL>
 void launch_fwd(uint32_t grid, hipStream_t s, const BlendArgs& a)
@@ -717,8 +719,21 @@ void dispatch_bwd_cull(int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a
 template <int MODE>
 void launch_fwd_cull(uint32_t grid, hipStream_t s, const BlendArgs& a)
 {
-    blend_fwd_cull_kernel<MODE><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
-                                                     a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched);
+    if (a.oad)
+        blend_fwd_cull_kernel<MODE, true><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
+                                                               a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched,
+                                                               a.oad, a.oal);
+    else
+        blend_fwd_cull_kernel<MODE, false><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
+                                                                a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched,
+                                                                nullptr, nullptr);
+}
+// aux backward (gsrast_backward_aux): always the transposed kernel, whatever the pixels per lane and the A/B switch say
+template <int MODE>
+void launch_bwd_aux(uint32_t grid, hipStream_t s, const BlendArgs& a)
+{
+    blend_bwd_cull_t_kernel<MODE, true><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
+                                                             a.from_buckets ? a.bcnt : nullptr, a.blist, a.fork_word, a.fork_seq, a.dad, a.dal);
 }
 template <int MODE>
 void dispatch_bwd(int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a)
@@ -1003,7 +1018,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                      const gsrast_raw_inputs* rawin)
+                      const gsrast_raw_inputs* rawin, float* out_acc_depth = nullptr, float* out_alpha = nullptr /* gsrast_forward_aux: both or neither */)
 {
     const auto t_entry = std::chrono::steady_clock::now();
     RoctxRange range_fwd(rawin ? "gsrast_forward_raw" : "gsrast_forward");
@@ -1015,6 +1030,9 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
     }
     const gsrast_options o = options ? *options : snapshot_defaults();
     if (!options_valid(o)) return fail(GSRAST_E_ARG, "forward: bad option value");
+    const bool aux = out_acc_depth != nullptr;
+    if (aux && (o.cull == 0 || o.fwd_pixels_per_lane != 0))
+        return fail(GSRAST_E_ARG, "forward_aux: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)");
     if (!ctx) ctx = thread_context();
     hipStream_t s = (hipStream_t)stream;
     const int W = width, H = height;
@@ -1025,6 +1043,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
     if (P == 0) { // reference rasterize_points.cu:81 -- nothing is rendered, outputs stay zero
         GS_HIP(hipMemsetAsync(out_color, 0, 3 * N * sizeof(float), s));
         GS_HIP(hipMemsetAsync(out_depth, 0, N * sizeof(float), s));
+        if (aux) { GS_HIP(hipMemsetAsync(out_acc_depth, 0, N * sizeof(float), s)); GS_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), s)); }
         return 0;
     }
     if (!means3D || !opacities || !viewmatrix || !projmatrix || !radii) return fail(GSRAST_E_ARG, "forward: NULL required input");
@@ -1494,6 +1513,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
         BlendArgs ba{};
         ba.ranges = ranges; ba.plist = plist; ba.W = W; ba.H = H; ba.gx = cam.gx; ba.T = T; ba.r0 = rec0; ba.r1 = rec1; ba.r2 = rec2;
         ba.bg = background; ba.oc = out_color; ba.od = out_depth; ba.fT = fT; ba.nc = nc; ba.tm = tm;
+        ba.oad = out_acc_depth; ba.oal = out_alpha;           // (every launch: the first pass, the completion pass, a redo)
         const int ppl = pick_ppl(T, false, o);
         const bool cull = o.cull != 0 && o.fwd_pixels_per_lane == 0;   // a forced pixels-per-lane selects the un-culled template
         if (zero_in_blend && !zero_touched && !o.forward_only && mode != 2) { ba.zero4 = at<float4>(geom, GL.grec); ba.n_zero4 = (uint32_t)((size_t)P * 4); }
@@ -1768,6 +1788,22 @@ int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                         tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr);
 }
 
+int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
+                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
+                       void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
+                       const float* background, int width, int height, const float* means3D, const float* shs,
+                       const float* colors_precomp, const float* opacities, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
+                       float* out_acc_depth, float* out_alpha)
+{
+    if (!out_acc_depth || !out_alpha) return fail(GSRAST_E_ARG, "forward_aux: NULL acc_depth / alpha output");
+    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, out_acc_depth, out_alpha);
+}
+
 static const char* raw_inputs_check(int P, int M, const gsrast_raw_inputs* in)
 {
     if (!in) return "raw: NULL inputs";
@@ -1788,6 +1824,21 @@ int gsrast_forward_raw(gsrast_context* ctx, const gsrast_options* options,
     return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
                         in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
                         viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in);
+}
+
+int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
+                           gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                           gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
+                           const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                           float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
+                           float* out_acc_depth, float* out_alpha)
+{
+    if (!out_acc_depth || !out_alpha) return fail(GSRAST_E_ARG, "forward_raw_aux: NULL acc_depth / alpha output");
+    if ((options ? *options : snapshot_defaults()).cull == 0) return fail(GSRAST_E_ARG, "forward_raw_aux: acc_depth / alpha need the culled blend kernel (options.cull != 0)");
+    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
+    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
+                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in, out_acc_depth, out_alpha);
 }
 
 int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_res, const float* rotation,
@@ -2245,7 +2296,8 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
                        float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                        const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                       const gsrast_raw_inputs* rawin, const gsrast_raw_grads* rawout)
+                       const gsrast_raw_inputs* rawin, const gsrast_raw_grads* rawout,
+                       const float* dL_dacc_depth = nullptr, const float* dL_dalpha = nullptr /* gsrast_backward_aux: either may be null */)
 {
     RoctxRange range_bwd(rawin ? "gsrast_backward_raw" : "gsrast_backward");
     CallScope call_scope;
@@ -2258,6 +2310,8 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
     }
     const gsrast_options o = options ? *options : snapshot_defaults();
     if (!options_valid(o)) return fail(GSRAST_E_ARG, "backward: bad option value");
+    const bool aux = dL_dacc_depth != nullptr || dL_dalpha != nullptr;
+    if (aux && o.cull == 0) return fail(GSRAST_E_ARG, "backward_aux: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
     hipStream_t s = (hipStream_t)stream;
     const int W = width, H = height;
     if (P < 0 || R < 0 || W <= 0 || H <= 0) return fail(GSRAST_E_ARG, "backward: bad sizes");
@@ -2329,7 +2383,7 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         if (!side) {
             side = side_stream_of(thread_context());
             // word fork: the blend backward below signals its own start, the side stream waits for that -- when it is the transposed kernel
-            if (side && o.cull != 0 && o.lpt && pick_ppl(T, true, o) == 1 && g_bwd_transposed.load() && g_ablate.load() == 0) late_fork = fork_word_next(thread_context(), side, s);
+            if (side && o.cull != 0 && o.lpt && (aux || (pick_ppl(T, true, o) == 1 && g_bwd_transposed.load() && g_ablate.load() == 0))) late_fork = fork_word_next(thread_context(), side, s);
             if (side && !late_fork.word) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
         }
         if (side) {
@@ -2365,6 +2419,7 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         ba.bg = background; ba.fT = const_cast<float*>(fT); ba.nc = const_cast<uint32_t*>(nc); ba.tm = const_cast<uint32_t*>(tm);
         ba.dpix = dL_dpix; ba.grec = grec;
         ba.fork_word = late_fork.word; ba.fork_seq = late_fork.seq;
+        ba.dad = dL_dacc_depth; ba.dal = dL_dalpha;
         if (const int mut = g_mutate.load()) {      // tests only: see g_mutate
             if (mut & 1) {
                 mutate_drop_front_batch_kernel<<<1, 256, 0, s>>>(at<uint2>(img, IL.ranges), at<uint32_t>(img, IL.n_contrib), at<uint32_t>(img, IL.tile_max),
@@ -2390,6 +2445,9 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
                 ba.order = ord;
             }
         }
+        if (aux) {
+            switch (o.exp_mode) { case 0: launch_bwd_aux<0>(grid, s, ba); break; case 1: launch_bwd_aux<1>(grid, s, ba); break; default: launch_bwd_aux<2>(grid, s, ba); break; }
+        } else
         if (g_ablate.load() == 1) launch_bwd<0, 4, 1>(grid, s, ba);
         else if (g_ablate.load() == 2) launch_bwd<0, 4, 2>(grid, s, ba);
         else
@@ -2400,7 +2458,7 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         }
         GS_LAUNCHED("blend_bwd");
         // (belt and braces: should anything but the signalling kernel have been launched, the caller's stream releases the side stream itself)
-        if (late_fork.word && !(g_ablate.load() == 0 && cull && ppl == 1 && g_bwd_transposed.load())) GS_HIP(hipStreamWriteValue32(s, late_fork.word, late_fork.seq, 0));
+        if (late_fork.word && !aux && !(g_ablate.load() == 0 && cull && ppl == 1 && g_bwd_transposed.load())) GS_HIP(hipStreamWriteValue32(s, late_fork.word, late_fork.seq, 0));
     }
     if (late_fork.word) { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }      // (its wait was released by the kernel just launched, or will be)
     if (do_blend && use_sh && o.sh_grad_factors) {      // dL_dsh is [P][3] in this mode: the factor, final after the blend backward
@@ -2422,7 +2480,8 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         const int factors = (use_sh && o.sh_grad_factors) ? 1 : 0;
 #define GS_PB_ARGS P, D, M, means3D, radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB), \
                    at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,  \
-                   dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched)
+                   dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched), \
+                   aux ? 1 : 0
         const bool skip = !o.dense_backward;        // Gaussians with an all-zero gradient record are not read
         if (late_fill) {       // (late_fill implies skip) grouped: 1024 Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
             const int gg = (P + PB_GROUP - 1) / PB_GROUP;
@@ -2450,10 +2509,25 @@ int gsrast_backward_ex(const gsrast_options* options, int P, int D, int M, int R
                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
 }
 
-int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                        const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                        float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                        const float* dL_dpix, const gsrast_raw_grads* out, void* stream)
+int gsrast_backward_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
+                        const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                        float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                        const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                        float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                        const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                        const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    return backward_impl(options, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr,
+                         dL_dacc_depth, dL_dalpha);
+}
+
+static int backward_raw_impl(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
+                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                             float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                             const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
 {
     if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
     if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
@@ -2475,7 +2549,28 @@ int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int 
     float* sh_marker = fac ? out->d_sh_factor : (out->d_shs_res ? out->d_shs_res : out->d_features_dc);
     return backward_impl(&o, P, D, M, R, background, width, height, in->xyz, in->features_dc, nullptr, in->scaling, scale_modifier, in->rotation, nullptr,
                          viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out->dL_dmean2D,
-                         nullptr, out->d_opacity_logit, nullptr, out->d_xyz, nullptr, sh_marker, out->d_scaling, out->d_rotation, stream, in, out);
+                         nullptr, out->d_opacity_logit, nullptr, out->d_xyz, nullptr, sh_marker, out->d_scaling, out->d_rotation, stream, in, out,
+                         dL_dacc_depth, dL_dalpha);
+}
+
+int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
+                        const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                        float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                        const float* dL_dpix, const gsrast_raw_grads* out, void* stream)
+{
+    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, nullptr, nullptr);
+}
+
+int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
+                            const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                            float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                            const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    if ((dL_dacc_depth || dL_dalpha) && (options ? *options : snapshot_defaults()).cull == 0)
+        return fail(GSRAST_E_ARG, "backward_raw_aux: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
+    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, dL_dacc_depth, dL_dalpha);
 }
 
 int gsrast_debug_export(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,

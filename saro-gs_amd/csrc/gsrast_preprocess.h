@@ -1096,7 +1096,10 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       // Round 5: `untouched` (GeomLayout::untouched, kept by the forward blend whenever scalars[SC_TOUCH_VALID] says so) takes
                       // the bits' place -- "no pixel consumed this Gaussian", a superset of "culled or late" that needs no pose table
                       const unsigned long long* __restrict__ late_bits = nullptr, const uint32_t* __restrict__ cut_scalars = nullptr,
-                      const unsigned char* __restrict__ untouched = nullptr)
+                      const unsigned char* __restrict__ untouched = nullptr,
+                      // aux (gsrast_backward_aux): float 9 of the record (gr2.y) is dL/d(view-space z) from the blend backward's acc_depth
+                      // gradient -- added to the projection chain's own; 0: the record's nine sums only, exactly as without it
+                      int aux = 0)
 {
     __shared__ float sh_lds[PP_THREADS * PP_SH_STRIDE];
     __shared__ uint32_t s_list[GROUPED ? PB_GROUP : 1];
@@ -1158,7 +1161,8 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     float4 gr0 = grec[4 * (size_t)ic], gr1 = grec[4 * (size_t)ic + 1], gr2 = grec[4 * (size_t)ic + 2];
     if (record_is_stale(cut_scalars, untouched, ic)) { gr0 = make_float4(0.f, 0.f, 0.f, 0.f); gr1 = gr0; gr2 = gr0; }      // (nobody zeroed it: no pixel consumed the Gaussian)
     bool touched = true;
-    if (SPARSE) touched = gr0.x != 0.f || gr0.y != 0.f || gr0.z != 0.f || gr0.w != 0.f || gr1.x != 0.f || gr1.y != 0.f || gr1.z != 0.f || gr1.w != 0.f || gr2.x != 0.f;
+    if (SPARSE) touched = gr0.x != 0.f || gr0.y != 0.f || gr0.z != 0.f || gr0.w != 0.f || gr1.x != 0.f || gr1.y != 0.f || gr1.z != 0.f || gr1.w != 0.f || gr2.x != 0.f ||
+                          (aux && gr2.y != 0.f);
     const bool live = i < P && radius_in > 0 && touched;
     float mean[3] = { 0.f, 0.f, 0.f };
     float s[3] = { 0.f, 0.f, 0.f };
@@ -1186,7 +1190,8 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         if (!SPARSE) {
             // the dense form reads every Gaussian -- but under the forward's list cut (gsrast_common.h) the colour kernel has left the
             // direction derivatives and clamp flags of a late Gaussian unwritten: its gradient record is zero, so they are taken as zero
-            const bool zero_rec = gr0.x == 0.f && gr0.y == 0.f && gr0.z == 0.f && gr0.w == 0.f && gr1.x == 0.f && gr1.y == 0.f && gr1.z == 0.f && gr1.w == 0.f && gr2.x == 0.f;
+            const bool zero_rec = gr0.x == 0.f && gr0.y == 0.f && gr0.z == 0.f && gr0.w == 0.f && gr1.x == 0.f && gr1.y == 0.f && gr1.z == 0.f && gr1.w == 0.f && gr2.x == 0.f &&
+                                  !(aux && gr2.y != 0.f);
             if (zero_rec) { sdA = make_float4(0.f, 0.f, 0.f, 0.f); sdB = sdA; sdC = 0.0f; clamped_in = 0; }
         }
     }
@@ -1281,7 +1286,8 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     const float tz = 1.0f / cv.t[2], tz2 = tz * tz, tz3 = tz2 * tz;
     const float dtx = xgm * -cam.fx * tz2 * dJ02;
     const float dty = ygm * -cam.fy * tz2 * dJ12;
-    const float dtz = -cam.fx * tz2 * dJ00 - cam.fy * tz2 * dJ11 + (2.0f * cam.fx * cv.t[0]) * tz3 * dJ02 + (2.0f * cam.fy * cv.t[1]) * tz3 * dJ12;
+    float dtz = -cam.fx * tz2 * dJ00 - cam.fy * tz2 * dJ11 + (2.0f * cam.fx * cv.t[0]) * tz3 * dJ02 + (2.0f * cam.fy * cv.t[1]) * tz3 * dJ12;
+    if (aux) dtz += gr2.y;          // the accumulated depth's z is the view-space z itself (uniform branch)
     float dmean[3] = { cam.view[0] * dtx + cam.view[1] * dty + cam.view[2] * dtz,
                        cam.view[4] * dtx + cam.view[5] * dty + cam.view[6] * dtz,
                        cam.view[8] * dtx + cam.view[9] * dty + cam.view[10] * dtz };

@@ -40,6 +40,7 @@ EXPORTS = (
     "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event",
     "gsrast_forward_ex", "gsrast_backward_ex", "gsrast_forward_raw", "gsrast_backward_raw", "gsrast_alloc_prealloc",
+    "gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux",
 )
 
 
@@ -150,6 +151,11 @@ def lib() -> C.CDLL:
     L.gsrast_backward_raw.restype = ci
     L.gsrast_backward_raw.argtypes = [C.POINTER(OptionsStruct), ci, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf,
                                       vp, vp, vp, vp, vp, C.POINTER(RawGradsStruct), vp]
+    # the aux entry points: their siblings' arguments + the two [1,H,W] arrays (outputs / upstream gradients, NULL = zero)
+    for name, sib in (("gsrast_forward_aux", "gsrast_forward_ex"), ("gsrast_backward_aux", "gsrast_backward_ex"),
+                      ("gsrast_forward_raw_aux", "gsrast_forward_raw"), ("gsrast_backward_raw_aux", "gsrast_backward_raw")):
+        getattr(L, name).restype = ci
+        getattr(L, name).argtypes = getattr(L, sib).argtypes + [vp, vp]
     L.gsrast_options_init.restype = None
     L.gsrast_options_init.argtypes = [C.POINTER(OptionsStruct)]
     L.gsrast_context_create.restype = vp
@@ -495,12 +501,14 @@ class _Arena:
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height,
-                        image_width, sh, degree, campos, prefiltered, *, forward_only: bool = False
-                        ) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                        image_width, sh, degree, campos, prefiltered, *, forward_only: bool = False, aux: bool = False
+                        ) -> Tuple[torch.Tensor, ...]:
     """Forward.  Mirrors RasterizeGaussiansCUDA (rasterize_points.cu:35-115): returns
     ``(num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer,
     out_depth[1,H,W])``.  `forward_only` (not in the reference): no backward will follow on the returned state (the autograd
-    node passes it when no input requires a gradient): the library skips what it only prepares for the backward."""
+    node passes it when no input requires a gradient): the library skips what it only prepares for the backward.
+    `aux` (not in the reference): gsrast_forward_aux, the tuple continues with ``acc_depth[1,H,W], alpha[1,H,W]``
+    (include/gsrast.h); without it the call is gsrast_forward_ex and allocates nothing more."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:56-58
     dev = _require_gpu(means3D)
@@ -515,20 +523,24 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
     out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    aux_out = (torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev)) if aux else ()
     arena = _Arena.acquire(dev)
     try:
         with _on_device(dev):
             stream = _stream_of(dev)
-            rendered = L.gsrast_forward_ex(
-                _current_context(), C.byref(_options_struct(forward_only=forward_only)),       # context: the innermost `with Context()` of the calling thread, else the thread's own
-                *arena.forward_allocators(P, W, H),
-                P, int(degree), M, background.data_ptr(), W, H, means3D.data_ptr(), _ptr(sh), _ptr(colors), opacity.data_ptr(),
-                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
-                projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), stream)
+            args = (_current_context(), C.byref(_options_struct(forward_only=forward_only)),       # context: the innermost `with Context()` of the calling thread, else the thread's own
+                    *arena.forward_allocators(P, W, H),
+                    P, int(degree), M, background.data_ptr(), W, H, means3D.data_ptr(), _ptr(sh), _ptr(colors), opacity.data_ptr(),
+                    _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
+                    projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+                    out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), stream)
+            if aux:
+                rendered = L.gsrast_forward_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
+            else:
+                rendered = L.gsrast_forward_ex(*args)
         if rendered < 0:
-            raise _err(rendered, "gsrast_forward")
-        return rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth
+            raise _err(rendered, "gsrast_forward_aux" if aux else "gsrast_forward")
+        return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
     finally:
         arena.close()       # break the arena <-> callback cycle now, not whenever the cyclic GC runs
 
@@ -536,16 +548,20 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
-                                 first_backward: bool = False):
+                                 first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
+                                 dL_dalpha: Optional[torch.Tensor] = None):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
     instead of the calling thread's (current_options() captured at forward time); `first_backward`: no backward has touched
-    geomBuffer since its forward, whose gradient records are therefore still zero (the library skips its zero-fill)."""
+    geomBuffer since its forward, whose gradient records are therefore still zero (the library skips its zero-fill).
+    `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- gsrast_backward_aux when
+    either is given, else gsrast_backward_ex."""
     dev = _require_gpu(means3D)
     L = lib()
     P = int(means3D.shape[0])
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])  # rasterize_points.cu:141-142
+    aux = _aux_grads(dL_dacc_depth, dL_dalpha, H, W, dev)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, means3D, colors = f(background, "bg"), f(means3D, "means3D"), f(colors, "colors_precomp")
     scales, rotations, cov3D_precomp = f(scales, "scales"), f(rotations, "rotations"), f(cov3D_precomp, "cov3D_precomp")
@@ -599,15 +615,17 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             radii_c = radii.contiguous()
 
             def call(phase):      # options travel per call: no process-wide switch is flipped
-                return L.gsrast_backward_ex(
-                    C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),
-                    P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                    _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
-                    _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii_c),
-                    _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL_dout_color),
-                    dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
-                    dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), sh_out, dL_dscales.data_ptr(),
-                    dL_drotations.data_ptr(), stream)
+                args = (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),
+                        P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
+                        _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
+                        _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii_c),
+                        _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL_dout_color),
+                        dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
+                        dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), sh_out, dL_dscales.data_ptr(),
+                        dL_drotations.data_ptr(), stream)
+                if aux is not None:
+                    return L.gsrast_backward_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
+                return L.gsrast_backward_ex(*args)
 
             if factors:
                 # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
@@ -624,8 +642,22 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             else:
                 rc = call(0)
         if rc != 0:
-            raise _err(rc, "gsrast_backward")
+            raise _err(rc, "gsrast_backward_aux" if aux is not None else "gsrast_backward")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def _aux_grads(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device):
+    """(dL/dacc_depth, dL/dalpha) as contiguous fp32 [1,H,W] device tensors or None each; None for the pair when both are absent."""
+    if dL_dacc_depth is None and dL_dalpha is None:
+        return None
+    out = []
+    for t, n in ((dL_dacc_depth, "dL_dacc_depth"), (dL_dalpha, "dL_dalpha")):
+        if t is not None:
+            if t.numel() != H * W:
+                raise RuntimeError(f"{n} must hold one value per pixel ([1,{H},{W}])")
+            t = _dev_f32(t, n, dev)
+        out.append(t)
+    return tuple(out)
 
 
 # ---- raw-parameter entry points (include/gsrast.h: gsrast_forward_raw / gsrast_backward_raw; no counterpart in the reference's _C) ----
@@ -659,9 +691,9 @@ def _raw_struct(raw: dict, dev: torch.device, P: int):
 
 
 def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                            degree, campos, *, forward_only: bool = False):
+                            degree, campos, *, forward_only: bool = False, aux: bool = False):
     """rasterize_gaussians taking the model's raw leaves + optional residuals (`raw`: RAW_NAMES -> tensor / None); the activations
-    of scene/saro_gaussian.py:39-47, :807-847 run inside the per-Gaussian kernels.  Same return tuple."""
+    of scene/saro_gaussian.py:39-47, :807-847 run inside the per-Gaussian kernels.  Same return tuple (`aux`: + acc_depth, alpha)."""
     dev = _require_gpu(raw["xyz"])
     L = lib()
     P, H, W = int(raw["xyz"].shape[0]), int(image_height), int(image_width)
@@ -671,27 +703,33 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
     out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
     out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    aux_out = (torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev)) if aux else ()
     arena = _Arena.acquire(dev)
     try:
         with _on_device(dev):
-            rendered = L.gsrast_forward_raw(
-                _current_context(), C.byref(_options_struct(forward_only=forward_only)),
-                *arena.forward_allocators(P, W, H),
-                P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                float(tan_fovx), float(tan_fovy), out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii),
-                _stream_of(dev))
+            args = (_current_context(), C.byref(_options_struct(forward_only=forward_only)),
+                    *arena.forward_allocators(P, W, H),
+                    P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                    float(tan_fovx), float(tan_fovy), out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii),
+                    _stream_of(dev))
+            if aux:
+                rendered = L.gsrast_forward_raw_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
+            else:
+                rendered = L.gsrast_forward_raw(*args)
         if rendered < 0:
-            raise _err(rendered, "gsrast_forward_raw")
-        return rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth
+            raise _err(rendered, "gsrast_forward_raw_aux" if aux else "gsrast_forward_raw")
+        return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
     finally:
         arena.close()
 
 
 def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
-                                     first_backward: bool = False) -> dict:
+                                     first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
+                                     dL_dalpha: Optional[torch.Tensor] = None) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
-    features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3]."""
+    features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
+    rasterize_gaussians_backward (gsrast_backward_raw_aux when either is given)."""
     dev = _require_gpu(raw["xyz"])
     L = lib()
     P = int(raw["xyz"].shape[0])
@@ -700,6 +738,7 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, viewmatrix, projmatrix, campos = f(background, "bg"), f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(campos, "campos")
     dL_dout_color = f(dL_dout_color, "dL_dout_color")
+    aux = _aux_grads(dL_dacc_depth, dL_dalpha, H, W, dev)
     o = dict(dtype=torch.float32, device=dev)
     ar = _grad_arena
     if ar is not None and not (getattr(ar, "raw", False) and ar.P == P and ar.M == M and ar.flat.device == dev):
@@ -746,11 +785,13 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
         radii_c = radii.contiguous()
         with _on_device(dev):
             def call(phase):
-                return L.gsrast_backward_raw(
-                    C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)), P, int(degree), M, int(R),
-                    _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                    float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
-                    _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
+                args = (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)), P, int(degree), M, int(R),
+                        _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                        float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                        _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
+                if aux is not None:
+                    return L.gsrast_backward_raw_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
+                return L.gsrast_backward_raw(*args)
 
             if factors:
                 # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
@@ -767,7 +808,7 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
             else:
                 rc = call(0)
         if rc != 0:
-            raise _err(rc, "gsrast_backward_raw")
+            raise _err(rc, "gsrast_backward_raw_aux" if aux is not None else "gsrast_backward_raw")
     if keep["motion_res"] is not None:
         g["motion_res"] = g["xyz"]
     return g

@@ -19,12 +19,17 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   shs / colors_precomp, opacities, scales, rotations, cov3D_precomp; depth and radii carry no
   gradient (REF:88, REF:120-130).
 * ``GaussianRasterizer.markVisible(positions)`` (REF:152-161).
+* not in the reference: ``forward(..., return_aux=True)`` (also ``rasterize_gaussians`` and ``GaussianRasterizerRaw``) returns
+  ``(color, radii, depth, acc_depth[1,H,W], alpha[1,H,W])`` -- alpha = 1 - T_final and the accumulated depth
+  sum_i alpha_i T_i z_i (not normalised: expected depth = acc_depth / alpha), both differentiable like the colour
+  (include/gsrast.h: gsrast_forward_aux / gsrast_backward_aux).  The median ``depth`` keeps the reference's zero gradient.
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
 """
 from __future__ import annotations
 
+import inspect
 from typing import NamedTuple, Optional
 
 import torch
@@ -104,11 +109,63 @@ class _RasterizeGaussians(torch.autograd.Function):
                 opt(grad_cov3Ds_precomp, cov3Ds_precomp), None)
 
 
+def _no_arena_for_aux():
+    if _C._grad_arena is not None:
+        raise RuntimeError("return_aux=True is not supported with a GradArena installed (multi-GPU / view_parallel training): "
+                           "uninstall it with _C.set_grad_arena(None) for renders that need acc_depth / alpha")
+
+
+class _RasterizeGaussiansAux(_RasterizeGaussians):
+    """_RasterizeGaussians with the two aux outputs (gsrast_forward_aux / gsrast_backward_aux): returns
+    (color, radii, depth, acc_depth, alpha)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        _no_arena_for_aux()
+        rs = raster_settings
+        (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians(
+            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
+            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=True)
+        ctx.raster_settings = rs
+        ctx.num_rendered = num_rendered
+        ctx.gs_options = _C.current_options()
+        ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))
+        ctx.gs_backwards = 0
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
+                              geom_buf, bin_buf, img_buf)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, acc_depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, grad_acc_depth, grad_alpha):
+        rs = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
+         geom_buf, bin_buf, img_buf) = ctx.saved_tensors
+        if grad_out_color is None:      # a loss built from the aux outputs (or the median depth) alone
+            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=means3D.device)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
+            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
+            geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha)      # (None = zero; both None: the plain backward)
+        ctx.gs_backwards += 1
+        def opt(g, x):
+            return g if x.numel() != 0 else None
+        return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
+                grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
-    """Functional form (REF:17-39)."""
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                        raster_settings, return_aux=False):
+    """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha (module docstring)."""
+    fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
+    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                    cov3Ds_precomp, raster_settings)
 
 
 _EMPTY = torch.empty(0)
@@ -127,7 +184,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs: Optional[torch.Tensor] = None,
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
-                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None):
+                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *, return_aux: bool = False):
         have_sh, have_rgb = shs is not None, colors_precomp is not None
         if have_sh == have_rgb:
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -146,7 +203,11 @@ class GaussianRasterizer(nn.Module):
             scales if scales is not None else empty,
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
-            self.raster_settings)
+            self.raster_settings, return_aux=return_aux)
+
+    # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
+    # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__).
+    forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values() if q.name != "return_aux"])
 
 
 # ---- raw-parameter module (no counterpart in the reference: SURVEY.md 8f rank 3 as written -- the activation / deformation epilogue
@@ -190,20 +251,63 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         return (g["dL_dmeans2D"], None) + grads
 
 
+class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
+    """_RasterizeGaussiansRaw with the two aux outputs (gsrast_forward_raw_aux / gsrast_backward_raw_aux)."""
+
+    @staticmethod
+    def forward(ctx, means2D, raster_settings, *raw_tensors):
+        _no_arena_for_aux()
+        rs = raster_settings
+        raw = dict(zip(_C.RAW_NAMES, raw_tensors))
+        forward_only = not any(ctx.needs_input_grad)
+        (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians_raw(
+            rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
+            rs.sh_degree, rs.campos, forward_only=forward_only, aux=True)
+        ctx.raster_settings, ctx.num_rendered = rs, num_rendered
+        ctx.gs_options = _C.current_options()
+        ctx.gs_options["forward_only"] = int(forward_only)
+        ctx.gs_backwards = 0
+        ctx.present = tuple(t is not None for t in raw_tensors)
+        ctx.save_for_backward(*[t for t in raw_tensors if t is not None], radii, geom_buf, bin_buf, img_buf)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, acc_depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, grad_acc_depth, grad_alpha):
+        rs = ctx.raster_settings
+        saved = list(ctx.saved_tensors)
+        img_buf, bin_buf, geom_buf, radii = saved.pop(), saved.pop(), saved.pop(), saved.pop()
+        it = iter(saved)
+        raw = {n: (next(it) if here else None) for n, here in zip(_C.RAW_NAMES, ctx.present)}
+        if grad_out_color is None:
+            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=radii.device)
+        g = _C.rasterize_gaussians_raw_backward(
+            rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
+            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha)      # (None = zero; both None: the plain backward)
+        ctx.gs_backwards += 1
+        shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
+        grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
+        return (g["dL_dmeans2D"], None) + grads
+
+
 class GaussianRasterizerRaw(nn.Module):
     """GaussianRasterizer for callers that hold SaRO-GS's RAW parameters: forward(xyz, means2D, rotation, scaling, opacity, features_dc,
     features_rest, motion_residual=None, rot_residual=None, trbfoutput=None, shs_residual=None) renders
     means3D = xyz + motion_residual, rotations = normalize(rotation + rot_residual[:, :4]), scales = exp(scaling + rot_residual[:, 4:]),
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
-    being written.  Gradients flow to every tensor given."""
+    being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), as
+    GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
         self.raster_settings = raster_settings
 
     def forward(self, xyz, means2D, rotation, scaling, opacity, features_dc, features_rest, motion_residual=None, rot_residual=None,
-                trbfoutput=None, shs_residual=None):
+                trbfoutput=None, shs_residual=None, *, return_aux: bool = False):
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
-        return _RasterizeGaussiansRaw.apply(means2D, self.raster_settings, *[raw[n] for n in _C.RAW_NAMES])
+        fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
+        return fn.apply(means2D, self.raster_settings, *[raw[n] for n in _C.RAW_NAMES])
