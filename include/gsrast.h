@@ -500,6 +500,60 @@ int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, 
                             const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
                             const float* dL_dacc_depth, const float* dL_dalpha);
 
+/* ---- Render flags: one family of entry points for every combination of the optional render features ----
+ * gsrast_forward_flags / gsrast_backward_flags take gsrast_forward_ex's / gsrast_backward_ex's arguments, a flags word behind the options,
+ * and the aux arrays of gsrast_forward_aux / gsrast_backward_aux at the end; the _raw_flags pair is the same for the raw pair.
+ *   flags = 0                        exactly gsrast_forward_ex / gsrast_backward_ex (the aux pointers are ignored)
+ *   GSRAST_RENDER_AUX                exactly gsrast_forward_aux / gsrast_backward_aux (the same rules: outputs non-NULL, gradients either NULL)
+ *   GSRAST_RENDER_ANTIALIAS          the 2-D Mip filter of Mip-Splatting (Yu et al., CVPR 2024), upstream 3DGS's `antialiasing`: every
+ *                                    Gaussian's 2-D covariance keeps the 0.3 px^2 dilation, and its opacity is scaled by
+ *                                        comp = sqrt(max(0.000025, rho)),   rho = det(cov2D) / det(cov2D + 0.3 I)     (cov2D before the dilation)
+ *                                    so that the dilation does not inflate the energy of small or distant Gaussians.  o * comp replaces the opacity
+ *                                    in every downstream use (blend, median depth, acc_depth / alpha, the skip threshold, the list cut); conic,
+ *                                    radius, means2D, depths and tiles are unchanged.  The backward adds the opacity's dependence on the covariance
+ *                                    (zero where rho sits on the floor) and scales dL/dopacity by comp.
+ * The backward must get the same GSRAST_RENDER_ANTIALIAS bit as the forward that filled the state (the state does not record it).  With
+ * options->backward_phase, pass the same flags to both phases.
+ * GSRAST_E_ARG before any device work: unknown bits; GSRAST_RENDER_AUX with options->cull == 0; forward, GSRAST_RENDER_AUX with a NULL aux output. */
+#define GSRAST_RENDER_AUX        0x1u
+#define GSRAST_RENDER_ANTIALIAS  0x2u
+int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
+                         gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                         gsrast_alloc_fn image_alloc, void* image_ctx,
+                         int P, int D, int M, const float* background, int width, int height,
+                         const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                         const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                         const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                         float tan_fovx, float tan_fovy, int prefiltered,
+                         float* out_color, float* out_depth, int* radii, void* stream,
+                         float* out_acc_depth, float* out_alpha);
+int gsrast_backward_flags(const gsrast_options* options, unsigned flags,
+                          int P, int D, int M, int R, const float* background, int width, int height,
+                          const float* means3D, const float* shs, const float* colors_precomp,
+                          const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                          const float* viewmatrix, const float* projmatrix, const float* campos,
+                          float tan_fovx, float tan_fovy, const int* radii,
+                          char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                          float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                          const float* dL_dacc_depth, const float* dL_dalpha);
+int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
+                             gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                             gsrast_alloc_fn image_alloc, void* image_ctx,
+                             int P, int D, int M, const float* background, int width, int height,
+                             const gsrast_raw_inputs* inputs, float scale_modifier,
+                             const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
+                             float* out_acc_depth, float* out_alpha);
+int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                              const gsrast_raw_inputs* inputs, float scale_modifier,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                              const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
+                              const float* dL_dacc_depth, const float* dL_dalpha);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

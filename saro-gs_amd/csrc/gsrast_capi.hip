@@ -1018,7 +1018,8 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                      const gsrast_raw_inputs* rawin, float* out_acc_depth = nullptr, float* out_alpha = nullptr /* gsrast_forward_aux: both or neither */)
+                      const gsrast_raw_inputs* rawin, float* out_acc_depth = nullptr, float* out_alpha = nullptr /* gsrast_forward_aux: both or neither */,
+                      bool aa = false /* GSRAST_RENDER_ANTIALIAS: the per-Gaussian kernel's AA instantiation */)
 {
     const auto t_entry = std::chrono::steady_clock::now();
     RoctxRange range_fwd(rawin ? "gsrast_forward_raw" : "gsrast_forward");
@@ -1303,16 +1304,12 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
             if (tau_ctx_device < 0) GS_HIP(hipMemsetAsync(tau_hist, 0, words * sizeof(uint32_t), s));
         }
         const int nzero = bucket_sort ? (int)nbk * BK_XCD + BK_XCD * BK_NBC_MAX : 0;      // (fine counters + the two-launch scatter's coarse ones, contiguous)
-        if (rawin)
-            preprocess_fwd_kernel<true><<<pf_grid, PF_THREADS, 0, s>>>(
-                P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg,
-                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel,
-                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins);
-        else
-            preprocess_fwd_kernel<false><<<pf_grid, PF_THREADS, 0, s>>>(
-                P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg,
-                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel,
-                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins);
+#define GS_PF_ARGS P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg, \
+                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel, \
+                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins
+        if (rawin) { if (aa) preprocess_fwd_kernel<true, true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); else preprocess_fwd_kernel<true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); }
+        else { if (aa) preprocess_fwd_kernel<false, true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); else preprocess_fwd_kernel<false><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); }
+#undef GS_PF_ARGS
         GS_LAUNCHED("preprocess_fwd");
         ctx->last_prologue_ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(), 0xFFFFFFFFll);
         if (tau_hist) {       // the predicted cut depths of a pose without remembered ones (a no-op for a pose the table knows, unless forced)
@@ -1841,6 +1838,52 @@ int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
                         viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in, out_acc_depth, out_alpha);
 }
 
+// ---- the flags-word entry points (GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS): one family for every combination ----
+// flags = 0 is gsrast_forward_ex / _raw, AUX is gsrast_forward_aux / _raw_aux; argument errors return before any device work.
+static const char* render_flags_check(unsigned flags, const gsrast_options* options)
+{
+    if (flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return "flags: unknown bits";
+    if ((flags & GSRAST_RENDER_AUX) && (options ? *options : snapshot_defaults()).cull == 0)
+        return "flags: GSRAST_RENDER_AUX (acc_depth / alpha) needs the culled blend kernels (options.cull != 0)";
+    return nullptr;
+}
+
+int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
+                         void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
+                         const float* background, int width, int height, const float* means3D, const float* shs,
+                         const float* colors_precomp, const float* opacities, const float* scales,
+                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                         const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                         float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
+                         float* out_acc_depth, float* out_alpha)
+{
+    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
+    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
+    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward_flags: NULL acc_depth / alpha output");
+    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, aux ? out_acc_depth : nullptr,
+                        aux ? out_alpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
+}
+
+int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                             gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
+                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
+                             float* out_acc_depth, float* out_alpha)
+{
+    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
+    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
+    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward_raw_flags: NULL acc_depth / alpha output");
+    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
+    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
+                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in, aux ? out_acc_depth : nullptr,
+                        aux ? out_alpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
+}
+
 int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_res, const float* rotation,
                             const float* rot_res, const float* scaling, const float* opacity_logit, const float* trbf,
                             const float* features_dc, const float* features_rest, const float* shs_res,
@@ -2297,7 +2340,8 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
                        const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
                        const gsrast_raw_inputs* rawin, const gsrast_raw_grads* rawout,
-                       const float* dL_dacc_depth = nullptr, const float* dL_dalpha = nullptr /* gsrast_backward_aux: either may be null */)
+                       const float* dL_dacc_depth = nullptr, const float* dL_dalpha = nullptr /* gsrast_backward_aux: either may be null */,
+                       bool aa = false /* GSRAST_RENDER_ANTIALIAS: the state comes from an anti-aliased forward */)
 {
     RoctxRange range_bwd(rawin ? "gsrast_backward_raw" : "gsrast_backward");
     CallScope call_scope;
@@ -2481,14 +2525,18 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
 #define GS_PB_ARGS P, D, M, means3D, radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB), \
                    at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,  \
                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched), \
-                   aux ? 1 : 0
+                   aux ? 1 : 0, rec1
+        // (aa: the kernel's AA instantiation -- the plain ones are the same code as before the flag existed)
+#define GS_PB_LAUNCH(RW, SP, GR, grid) do { if (aa) preprocess_bwd_kernel<RW, SP, GR, true><<<grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); \
+                                            else preprocess_bwd_kernel<RW, SP, GR><<<grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); } while (0)
         const bool skip = !o.dense_backward;        // Gaussians with an all-zero gradient record are not read
         if (late_fill) {       // (late_fill implies skip) grouped: 1024 Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
             const int gg = (P + PB_GROUP - 1) / PB_GROUP;
-            if (rawin) preprocess_bwd_kernel<true, true, true><<<gg, PP_THREADS, 0, s>>>(GS_PB_ARGS); else preprocess_bwd_kernel<false, true, true><<<gg, PP_THREADS, 0, s>>>(GS_PB_ARGS);
+            if (rawin) GS_PB_LAUNCH(true, true, true, gg); else GS_PB_LAUNCH(false, true, true, gg);
         } else
-        if (rawin) { if (skip) preprocess_bwd_kernel<true, true><<<pb_grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); else preprocess_bwd_kernel<true, false><<<pb_grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); }
-        else { if (skip) preprocess_bwd_kernel<false, true><<<pb_grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); else preprocess_bwd_kernel<false, false><<<pb_grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); }
+        if (rawin) { if (skip) GS_PB_LAUNCH(true, true, false, pb_grid); else GS_PB_LAUNCH(true, false, false, pb_grid); }
+        else { if (skip) GS_PB_LAUNCH(false, true, false, pb_grid); else GS_PB_LAUNCH(false, false, false, pb_grid); }
+#undef GS_PB_LAUNCH
 #undef GS_PB_ARGS
         GS_LAUNCHED("preprocess_bwd");
     }
@@ -2527,7 +2575,8 @@ int gsrast_backward_aux(const gsrast_options* options, int P, int D, int M, int 
 static int backward_raw_impl(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
                              const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
                              float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                             const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
+                             const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
+                             bool aa = false)
 {
     if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
     if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
@@ -2550,7 +2599,7 @@ static int backward_raw_impl(const gsrast_options* options, int P, int D, int M,
     return backward_impl(&o, P, D, M, R, background, width, height, in->xyz, in->features_dc, nullptr, in->scaling, scale_modifier, in->rotation, nullptr,
                          viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out->dL_dmean2D,
                          nullptr, out->d_opacity_logit, nullptr, out->d_xyz, nullptr, sh_marker, out->d_scaling, out->d_rotation, stream, in, out,
-                         dL_dacc_depth, dL_dalpha);
+                         dL_dacc_depth, dL_dalpha, aa);
 }
 
 int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
@@ -2571,6 +2620,37 @@ int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, 
         return fail(GSRAST_E_ARG, "backward_raw_aux: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
     return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
                              radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, dL_dacc_depth, dL_dalpha);
+}
+
+// flags = 0 is gsrast_backward_ex / _raw, AUX is gsrast_backward_aux / _raw_aux (the aux gradients: either may be NULL); ANTIALIAS must be what
+// the forward that filled the state was given
+int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                          const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                          float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                          const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                          const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
+    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
+    return backward_impl(options, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr,
+                         aux ? dL_dacc_depth : nullptr, aux ? dL_dalpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
+}
+
+int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                              const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                              float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                              const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
+    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
+    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, aux ? dL_dacc_depth : nullptr,
+                             aux ? dL_dalpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
 }
 
 int gsrast_debug_export(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,

@@ -139,7 +139,10 @@ __device__ __forceinline__ void cov3d_from_scale_rot(const float s_in[3], float 
 #undef GS_SIG
 }
 
-struct Cov2D { float t[3]; float txtz, tytz, limx, limy; M3 T, Wm, V; float a, b, c; };
+// a, b, c: the screen-space covariance with the 0.3 px^2 dilation (b = c01); c00, c11: its diagonal BEFORE the dilation, for the
+// anti-aliasing filter (aa_rho below) -- not recovered as a - 0.3f, which would add a rounding error to the quantity that cancels.
+// (Dead in the plain kernels: nothing reads them there.)
+struct Cov2D { float t[3]; float txtz, tytz, limx, limy; M3 T, Wm, V; float a, b, c; float c00, c11; };
 
 __device__ __forceinline__ void cov2d_eval(const float mean[3], const Cam& cam, const float c6[6], Cov2D& o)
 {
@@ -176,7 +179,22 @@ __device__ __forceinline__ void cov2d_eval(const float mean[3], const Cam& cam, 
     const float c01 = A[0][1] * o.T.m[0][0] + A[1][1] * o.T.m[0][1] + A[2][1] * o.T.m[0][2];
     const float c11 = A[0][1] * o.T.m[1][0] + A[1][1] * o.T.m[1][1] + A[2][1] * o.T.m[1][2];
     o.a = c00 + 0.3f; o.b = c01; o.c = c11 + 0.3f;
+    o.c00 = c00; o.c11 = c11;
 }
+
+// ---- anti-aliasing: the 2-D Mip filter of Mip-Splatting (Yu et al., CVPR 2024), as upstream 3DGS's `antialiasing` ----------------
+// The 0.3 px^2 dilation above widens every footprint; with AA the opacity is scaled by the ratio of the two footprints' areas so that a
+// small or distant Gaussian keeps its energy:  rho = det(cov2D) / det(cov2D + 0.3 I),  comp = sqrt(max(AA_FLOOR, rho)),  o_eff = o * comp.
+// o_eff replaces o in every downstream use (rec1.y, the skip threshold, the predicted cut's mass); conic, radius and tiles do not change.
+// det_h is the forward's `det` (the backward's `denom`): the same expression on the same operands.  rho <= 0 (fp32 cancellation of a
+// needle) lands on the floor, where the covariance term of the backward is zero.
+constexpr float AA_FLOOR = 0.000025f;      // upstream's literal
+__device__ __forceinline__ float aa_rho(const Cov2D& cv, float det_h)
+{
+    const float det_cov = cv.c00 * cv.c11 - cv.b * cv.b;
+    return det_cov / det_h;
+}
+__device__ __forceinline__ float aa_comp(float rho) { return sqrtf(fmaxf(AA_FLOOR, rho)); }
 
 // colour before clamping (SH + 0.5); sh points at this Gaussian's [M][3] block
 __device__ __forceinline__ void sh_to_rgb(int deg, const float pos[3], const float campos[3], const float* __restrict__ sh, float out[3])
@@ -660,7 +678,9 @@ preprocess_color_compact_kernel(int P, int D, int M, const float* __restrict__ m
 constexpr int PF_THREADS = GSRAST_PF_THREADS;
 // RAW (gsrast_forward_raw): means3D / scales / rotations / opacities are the model's _xyz / _scaling / _rotation / _opacity leaves
 // and `raw` carries the optional residuals; the activations happen right behind the loads (RawArgs above).
-template <bool RAW>
+// AA (gsrast_forward_flags with GSRAST_RENDER_ANTIALIAS): the opacity is scaled by aa_comp right behind the covariance; everything
+// downstream takes o_eff.  A template parameter, so that the plain instantiations keep their code (and registers) as they were.
+template <bool RAW, bool AA = false>
 __global__ void __launch_bounds__(PF_THREADS)
 preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __restrict__ scales,
                       const float* __restrict__ rotations, const float* __restrict__ opacities, RawArgs raw,
@@ -833,7 +853,7 @@ preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __r
             tile_rect(px, py, rad, cam.gx, cam.gy, rmin, rmax);
             const int area = (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]);
             if (area != 0) {
-                const float op = op_in;
+                const float op = AA ? op_in * aa_comp(aa_rho(cv, det)) : op_in;
                 // Conservative pre-test for the blend kernels: power < thr  ==>  op*exp(power) < 1/255
                 // with a 2% margin, so skipping the exp for such pairs never changes a decision.
                 // (clamped at -80 so that exp() is only ever evaluated on [-80, 0]: gs_exp<., BOUNDED>)
@@ -1071,7 +1091,10 @@ sh_dir_derivs_kernel(int P, int D, int M, const float* __restrict__ means3D, con
 // at 1 M).  Measured and dropped: not writing those rows either, the arrays zero-filled by a kernel on the side stream under the blend
 // backward -- preprocess_bwd 229 -> 130 us at 3 M, but the fill's 700 MB slowed the VALU-bound blend backward by 45 us and the extra
 // launches cost the small scenes 10-50 us: no better than this at 3 M, worse everywhere else.
-template <bool RAW, bool SPARSE, bool GROUPED = false>
+// AA (gsrast_backward_flags with GSRAST_RENDER_ANTIALIAS; the state must come from an anti-aliased forward): the record's dL/do_eff = g
+// becomes dL/do = g * comp, and g * o_eff * 0.5 * d(ln rho)/d(c00, c01, c11) joins dL/d(a, b, c) in front of the covariance chain (zero on
+// the floor).  o_eff is the forward's rec1.y.  Every output is still linear in the record: the SPARSE shortcut holds.
+template <bool RAW, bool SPARSE, bool GROUPED = false, bool AA = false>
 __global__ void __launch_bounds__(PP_THREADS)
 preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, const int* __restrict__ radii, RawArgs raw, RawGrads rawg,
                       const float* __restrict__ shs /* only its presence matters: the coefficients are not read */,
@@ -1099,7 +1122,8 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       const unsigned char* __restrict__ untouched = nullptr,
                       // aux (gsrast_backward_aux): float 9 of the record (gr2.y) is dL/d(view-space z) from the blend backward's acc_depth
                       // gradient -- added to the projection chain's own; 0: the record's nine sums only, exactly as without it
-                      int aux = 0)
+                      int aux = 0,
+                      const float4* __restrict__ rec1 = nullptr /* AA: GeomLayout::rec1 of the forward, whose .y is o_eff */)
 {
     __shared__ float sh_lds[PP_THREADS * PP_SH_STRIDE];
     __shared__ uint32_t s_list[GROUPED ? PB_GROUP : 1];
@@ -1201,6 +1225,8 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     const Cam cam = load_cam(cam_args);
     if (i < P) {    // the screen-space gradients leave in the reference's arrays (rasterize_points.cu:150-158), written once
         dL_dmean2D[3 * (size_t)i] = g2x; dL_dmean2D[3 * (size_t)i + 1] = g2y; dL_dmean2D[3 * (size_t)i + 2] = 0.0f;
+        if (AA && live) { }     // (written below, once comp is known)
+        else
         if (RAW) {      // d(opacity logit) = d_opacity * trbf * s (1 - s),  d(trbf) = d_opacity * s
             const float go = gr1.y;
             const bool have = !SPARSE || live;          // (an untouched Gaussian has go = 0: zeros, without its logit)
@@ -1252,11 +1278,28 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     float dL_da = 0, dL_db = 0, dL_dc = 0;
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
     const M3& T = cv.T; const M3& V = cv.V; const M3& Wm = cv.Wm;
+    bool aa_on = false;          // AA: rho above the floor -- the covariance term is live
+    if (AA) {
+        const float rho = aa_rho(cv, denom);
+        const float go = gr1.y * aa_comp(rho);          // dL/do = dL/do_eff * comp
+        if (RAW) {
+            dL_dopacity[i] = go * raw_tb * raw_sg * (1.0f - raw_sg);
+            if (rawg.d_trbf) rawg.d_trbf[i] = go * raw_sg;
+        } else dL_dopacity[i] = go;
+        aa_on = rho > AA_FLOOR;
+    }
     float dcov[6];
     if (denom2inv != 0) {
         dL_da = denom2inv * (-c * c * dcx + 2.0f * b * c * dcy + (denom - a * c) * dcz);
         dL_dc = denom2inv * (-a * a * dcz + 2.0f * a * b * dcy + (denom - a * c) * dcx);
         dL_db = denom2inv * 2.0f * (b * c * dcx - (denom + 2.0f * b * b) * dcy + a * b * dcz);
+        if (AA && aa_on) {      // + g o_eff d(comp)/d(c00, c01, c11) = g o_eff 0.5 d(ln rho)/d(.)  (b: the scalar c01, as dL_db)
+            const float w = gr1.y * rec1[(size_t)REC_STRIDE * i].y * 0.5f;
+            const float icov = 1.0f / (cv.c00 * cv.c11 - b * b), ih = 1.0f / denom;
+            dL_da = dL_da + w * (cv.c11 * icov - c * ih);
+            dL_dc = dL_dc + w * (cv.c00 * icov - a * ih);
+            dL_db = dL_db + w * (2.0f * b * ih - 2.0f * b * icov);
+        }
         dcov[0] = (T.m[0][0] * T.m[0][0] * dL_da + T.m[0][0] * T.m[1][0] * dL_db + T.m[1][0] * T.m[1][0] * dL_dc);
         dcov[3] = (T.m[0][1] * T.m[0][1] * dL_da + T.m[0][1] * T.m[1][1] * dL_db + T.m[1][1] * T.m[1][1] * dL_dc);
         dcov[5] = (T.m[0][2] * T.m[0][2] * dL_da + T.m[0][2] * T.m[1][2] * dL_db + T.m[1][2] * T.m[1][2] * dL_dc);

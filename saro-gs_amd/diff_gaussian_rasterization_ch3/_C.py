@@ -41,7 +41,12 @@ EXPORTS = (
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event",
     "gsrast_forward_ex", "gsrast_backward_ex", "gsrast_forward_raw", "gsrast_backward_raw", "gsrast_alloc_prealloc",
     "gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux",
+    "gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags",
 )
+
+# include/gsrast.h: the flags word of the gsrast_*_flags entry points
+RENDER_AUX = 0x1
+RENDER_ANTIALIAS = 0x2
 
 
 class OptionsStruct(C.Structure):
@@ -156,6 +161,12 @@ def lib() -> C.CDLL:
                       ("gsrast_forward_raw_aux", "gsrast_forward_raw"), ("gsrast_backward_raw_aux", "gsrast_backward_raw")):
         getattr(L, name).restype = ci
         getattr(L, name).argtypes = getattr(L, sib).argtypes + [vp, vp]
+    # the flags entry points: the aux ones' arguments with the flags word behind the options
+    for name, sib, at in (("gsrast_forward_flags", "gsrast_forward_aux", 2), ("gsrast_backward_flags", "gsrast_backward_aux", 1),
+                          ("gsrast_forward_raw_flags", "gsrast_forward_raw_aux", 2), ("gsrast_backward_raw_flags", "gsrast_backward_raw_aux", 1)):
+        a = list(getattr(L, sib).argtypes)
+        getattr(L, name).restype = ci
+        getattr(L, name).argtypes = a[:at] + [C.c_uint] + a[at:]
     L.gsrast_options_init.restype = None
     L.gsrast_options_init.argtypes = [C.POINTER(OptionsStruct)]
     L.gsrast_context_create.restype = vp
@@ -501,14 +512,16 @@ class _Arena:
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height,
-                        image_width, sh, degree, campos, prefiltered, *, forward_only: bool = False, aux: bool = False
-                        ) -> Tuple[torch.Tensor, ...]:
+                        image_width, sh, degree, campos, prefiltered, *, forward_only: bool = False, aux: bool = False,
+                        antialiasing: bool = False) -> Tuple[torch.Tensor, ...]:
     """Forward.  Mirrors RasterizeGaussiansCUDA (rasterize_points.cu:35-115): returns
     ``(num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer,
     out_depth[1,H,W])``.  `forward_only` (not in the reference): no backward will follow on the returned state (the autograd
     node passes it when no input requires a gradient): the library skips what it only prepares for the backward.
     `aux` (not in the reference): gsrast_forward_aux, the tuple continues with ``acc_depth[1,H,W], alpha[1,H,W]``
-    (include/gsrast.h); without it the call is gsrast_forward_ex and allocates nothing more."""
+    (include/gsrast.h); without it the call is gsrast_forward_ex and allocates nothing more.
+    `antialiasing` (not in the reference): gsrast_forward_flags with GSRAST_RENDER_ANTIALIAS -- the opacity-compensated 2-D filter; the
+    backward on the returned state must be given antialiasing=True as well."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:56-58
     dev = _require_gpu(means3D)
@@ -534,12 +547,15 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                     _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
                     projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
                     out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), stream)
-            if aux:
+            if antialiasing:
+                flags = RENDER_ANTIALIAS | (RENDER_AUX if aux else 0)
+                rendered = L.gsrast_forward_flags(args[0], args[1], flags, *args[2:], *((aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None)))
+            elif aux:
                 rendered = L.gsrast_forward_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
             else:
                 rendered = L.gsrast_forward_ex(*args)
         if rendered < 0:
-            raise _err(rendered, "gsrast_forward_aux" if aux else "gsrast_forward")
+            raise _err(rendered, "gsrast_forward_flags" if antialiasing else "gsrast_forward_aux" if aux else "gsrast_forward")
         return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
     finally:
         arena.close()       # break the arena <-> callback cycle now, not whenever the cyclic GC runs
@@ -549,14 +565,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                  first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
-                                 dL_dalpha: Optional[torch.Tensor] = None):
+                                 dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
     instead of the calling thread's (current_options() captured at forward time); `first_backward`: no backward has touched
     geomBuffer since its forward, whose gradient records are therefore still zero (the library skips its zero-fill).
     `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- gsrast_backward_aux when
-    either is given, else gsrast_backward_ex."""
+    either is given, else gsrast_backward_ex.  `antialiasing`: the state comes from an antialiasing=True forward (gsrast_backward_flags
+    with GSRAST_RENDER_ANTIALIAS; the same flags for both phases of a two-phase backward)."""
     dev = _require_gpu(means3D)
     L = lib()
     P = int(means3D.shape[0])
@@ -623,6 +640,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                         dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
                         dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), sh_out, dL_dscales.data_ptr(),
                         dL_drotations.data_ptr(), stream)
+                if antialiasing:
+                    flags = RENDER_ANTIALIAS | (RENDER_AUX if aux is not None else 0)
+                    return L.gsrast_backward_flags(args[0], flags, *args[1:], *((_ptr(aux[0]), _ptr(aux[1])) if aux is not None else (None, None)))
                 if aux is not None:
                     return L.gsrast_backward_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
                 return L.gsrast_backward_ex(*args)
@@ -642,7 +662,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             else:
                 rc = call(0)
         if rc != 0:
-            raise _err(rc, "gsrast_backward_aux" if aux is not None else "gsrast_backward")
+            raise _err(rc, "gsrast_backward_flags" if antialiasing else "gsrast_backward_aux" if aux is not None else "gsrast_backward")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
@@ -691,9 +711,10 @@ def _raw_struct(raw: dict, dev: torch.device, P: int):
 
 
 def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                            degree, campos, *, forward_only: bool = False, aux: bool = False):
+                            degree, campos, *, forward_only: bool = False, aux: bool = False, antialiasing: bool = False):
     """rasterize_gaussians taking the model's raw leaves + optional residuals (`raw`: RAW_NAMES -> tensor / None); the activations
-    of scene/saro_gaussian.py:39-47, :807-847 run inside the per-Gaussian kernels.  Same return tuple (`aux`: + acc_depth, alpha)."""
+    of scene/saro_gaussian.py:39-47, :807-847 run inside the per-Gaussian kernels.  Same return tuple (`aux`: + acc_depth, alpha;
+    `antialiasing`: as rasterize_gaussians)."""
     dev = _require_gpu(raw["xyz"])
     L = lib()
     P, H, W = int(raw["xyz"].shape[0]), int(image_height), int(image_width)
@@ -712,12 +733,15 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
                     P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
                     float(tan_fovx), float(tan_fovy), out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii),
                     _stream_of(dev))
-            if aux:
+            if antialiasing:
+                flags = RENDER_ANTIALIAS | (RENDER_AUX if aux else 0)
+                rendered = L.gsrast_forward_raw_flags(args[0], args[1], flags, *args[2:], *((aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None)))
+            elif aux:
                 rendered = L.gsrast_forward_raw_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
             else:
                 rendered = L.gsrast_forward_raw(*args)
         if rendered < 0:
-            raise _err(rendered, "gsrast_forward_raw_aux" if aux else "gsrast_forward_raw")
+            raise _err(rendered, "gsrast_forward_raw_flags" if antialiasing else "gsrast_forward_raw_aux" if aux else "gsrast_forward_raw")
         return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
     finally:
         arena.close()
@@ -726,10 +750,10 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
 def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                      first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
-                                     dL_dalpha: Optional[torch.Tensor] = None) -> dict:
+                                     dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
-    rasterize_gaussians_backward (gsrast_backward_raw_aux when either is given)."""
+    rasterize_gaussians_backward (gsrast_backward_raw_aux when either is given); `antialiasing`: as rasterize_gaussians_backward."""
     dev = _require_gpu(raw["xyz"])
     L = lib()
     P = int(raw["xyz"].shape[0])
@@ -789,6 +813,9 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                         _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
                         float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                         _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
+                if antialiasing:
+                    flags = RENDER_ANTIALIAS | (RENDER_AUX if aux is not None else 0)
+                    return L.gsrast_backward_raw_flags(args[0], flags, *args[1:], *((_ptr(aux[0]), _ptr(aux[1])) if aux is not None else (None, None)))
                 if aux is not None:
                     return L.gsrast_backward_raw_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
                 return L.gsrast_backward_raw(*args)
@@ -808,7 +835,7 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
             else:
                 rc = call(0)
         if rc != 0:
-            raise _err(rc, "gsrast_backward_raw_aux" if aux is not None else "gsrast_backward_raw")
+            raise _err(rc, "gsrast_backward_raw_flags" if antialiasing else "gsrast_backward_raw_aux" if aux is not None else "gsrast_backward_raw")
     if keep["motion_res"] is not None:
         g["motion_res"] = g["xyz"]
     return g

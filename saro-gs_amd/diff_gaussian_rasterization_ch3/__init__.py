@@ -23,6 +23,11 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   ``(color, radii, depth, acc_depth[1,H,W], alpha[1,H,W])`` -- alpha = 1 - T_final and the accumulated depth
   sum_i alpha_i T_i z_i (not normalised: expected depth = acc_depth / alpha), both differentiable like the colour
   (include/gsrast.h: gsrast_forward_aux / gsrast_backward_aux).  The median ``depth`` keeps the reference's zero gradient.
+* not in the reference: ``forward(..., antialiasing=True)`` (keyword-only, default False; also ``rasterize_gaussians`` and
+  ``GaussianRasterizerRaw``, and together with ``return_aux``) -- upstream 3DGS's ``antialiasing``, the 2-D Mip filter of
+  Mip-Splatting: each Gaussian's opacity is scaled by sqrt(det cov2D / det(cov2D + 0.3 I)) so that the 0.3 px^2 dilation does not
+  inflate small or distant Gaussians; differentiable, also through that factor (include/gsrast.h: GSRAST_RENDER_ANTIALIAS).  Train
+  and evaluate with the same setting.
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -60,7 +65,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, antialiasing):
         rs = raster_settings
         ar = _C._grad_arena
         if ar is not None and ar.sh_factors and sh.numel() != 0 and sh.requires_grad and not sh.is_leaf:
@@ -72,8 +77,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth = _C.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad))
+            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), antialiasing=antialiasing)
         ctx.raster_settings = rs
+        ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
         ctx.num_rendered = num_rendered
         ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
         ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
@@ -99,14 +105,15 @@ class _RasterizeGaussians(torch.autograd.Function):
          grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
-            geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0)
+            geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
+            antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         # one gradient per forward input, in input order; absent optionals get None
         def opt(g, x):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None)
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
 
 
 def _no_arena_for_aux():
@@ -121,14 +128,15 @@ class _RasterizeGaussiansAux(_RasterizeGaussians):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, antialiasing):
         _no_arena_for_aux()
         rs = raster_settings
         (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=True)
+            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=True, antialiasing=antialiasing)
         ctx.raster_settings = rs
+        ctx.antialiasing = bool(antialiasing)
         ctx.num_rendered = num_rendered
         ctx.gs_options = _C.current_options()
         ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))
@@ -151,21 +159,32 @@ class _RasterizeGaussiansAux(_RasterizeGaussians):
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
             geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha)      # (None = zero; both None: the plain backward)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha,      # (None = zero; both None: the plain backward)
+            antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         def opt(g, x):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None)
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_aux=False):
-    """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha (module docstring)."""
+                        raster_settings, return_aux=False, *, antialiasing: bool = False):
+    """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha; `antialiasing` (not in the
+    reference): the opacity-compensated 2-D filter (module docstring)."""
     fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                    cov3Ds_precomp, raster_settings)
+                    cov3Ds_precomp, raster_settings, bool(antialiasing))
+
+
+def _antialiasing_of(render_options: dict) -> bool:
+    """The keyword-only `antialiasing` (default False) of GaussianRasterizer.forward / GaussianRasterizerRaw.forward.  It arrives through
+    **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone."""
+    unknown = set(render_options) - {"antialiasing"}
+    if unknown:
+        raise TypeError(f"forward() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    return bool(render_options.get("antialiasing", False))
 
 
 _EMPTY = torch.empty(0)
@@ -184,7 +203,9 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs: Optional[torch.Tensor] = None,
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
-                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *, return_aux: bool = False):
+                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *, return_aux: bool = False,
+                **render_options):
+        antialiasing = _antialiasing_of(render_options)
         have_sh, have_rgb = shs is not None, colors_precomp is not None
         if have_sh == have_rgb:
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -203,27 +224,30 @@ class GaussianRasterizer(nn.Module):
             scales if scales is not None else empty,
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
-            self.raster_settings, return_aux=return_aux)
+            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing)
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
-    # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__).
-    forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values() if q.name != "return_aux"])
+    # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so is antialiasing
+    # (default False, through **render_options: _antialiasing_of).
+    forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
+                                               if q.name not in ("return_aux", "render_options")])
 
 
 # ---- raw-parameter module (no counterpart in the reference: SURVEY.md 8f rank 3 as written -- the activation / deformation epilogue
 # of scene/saro_gaussian.py:807-847 fused into the per-Gaussian kernels) -------------------------------------------------------------
 class _RasterizeGaussiansRaw(torch.autograd.Function):
-    """Inputs in _C.RAW_NAMES order (absent residuals: None) + means2D (the gradient sink of REF:42) + the settings."""
+    """Inputs in _C.RAW_NAMES order (absent residuals: None) + means2D (the gradient sink of REF:42) + the settings + antialiasing."""
 
     @staticmethod
-    def forward(ctx, means2D, raster_settings, *raw_tensors):
+    def forward(ctx, means2D, raster_settings, antialiasing, *raw_tensors):
         rs = raster_settings
         raw = dict(zip(_C.RAW_NAMES, raw_tensors))
         forward_only = not any(ctx.needs_input_grad)
         num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth = _C.rasterize_gaussians_raw(
             rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-            rs.sh_degree, rs.campos, forward_only=forward_only)
+            rs.sh_degree, rs.campos, forward_only=forward_only, antialiasing=antialiasing)
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
+        ctx.antialiasing = bool(antialiasing)
         ctx.gs_options = _C.current_options()
         ctx.gs_options["forward_only"] = int(forward_only)
         ctx.gs_backwards = 0
@@ -244,26 +268,28 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=radii.device)
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
-            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0)
+            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
+            antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None) + grads
+        return (g["dL_dmeans2D"], None, None) + grads
 
 
 class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
     """_RasterizeGaussiansRaw with the two aux outputs (gsrast_forward_raw_aux / gsrast_backward_raw_aux)."""
 
     @staticmethod
-    def forward(ctx, means2D, raster_settings, *raw_tensors):
+    def forward(ctx, means2D, raster_settings, antialiasing, *raw_tensors):
         _no_arena_for_aux()
         rs = raster_settings
         raw = dict(zip(_C.RAW_NAMES, raw_tensors))
         forward_only = not any(ctx.needs_input_grad)
         (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians_raw(
             rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-            rs.sh_degree, rs.campos, forward_only=forward_only, aux=True)
+            rs.sh_degree, rs.campos, forward_only=forward_only, aux=True, antialiasing=antialiasing)
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
+        ctx.antialiasing = bool(antialiasing)
         ctx.gs_options = _C.current_options()
         ctx.gs_options["forward_only"] = int(forward_only)
         ctx.gs_backwards = 0
@@ -285,11 +311,12 @@ class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
             rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha)      # (None = zero; both None: the plain backward)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha,      # (None = zero; both None: the plain backward)
+            antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None) + grads
+        return (g["dL_dmeans2D"], None, None) + grads
 
 
 class GaussianRasterizerRaw(nn.Module):
@@ -298,16 +325,17 @@ class GaussianRasterizerRaw(nn.Module):
     means3D = xyz + motion_residual, rotations = normalize(rotation + rot_residual[:, :4]), scales = exp(scaling + rot_residual[:, 4:]),
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
-    being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), as
-    GaussianRasterizer."""
+    being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), and the keyword-only
+    `antialiasing=True` (default False), as GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
         self.raster_settings = raster_settings
 
     def forward(self, xyz, means2D, rotation, scaling, opacity, features_dc, features_rest, motion_residual=None, rot_residual=None,
-                trbfoutput=None, shs_residual=None, *, return_aux: bool = False):
+                trbfoutput=None, shs_residual=None, *, return_aux: bool = False, **render_options):
+        antialiasing = _antialiasing_of(render_options)
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
         fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
-        return fn.apply(means2D, self.raster_settings, *[raw[n] for n in _C.RAW_NAMES])
+        return fn.apply(means2D, self.raster_settings, antialiasing, *[raw[n] for n in _C.RAW_NAMES])
