@@ -331,7 +331,7 @@ int gsrast_backward_ex(const gsrast_options* options,
  *     out_alpha     [1][H][W] = 1 - T_final
  * Both must be non-NULL.  Everything else it computes and leaves in the state buffers is what gsrast_forward_ex computes.
  * gsrast_backward_aux = gsrast_backward_ex plus the upstream gradients dL_dacc_depth / dL_dalpha [1][H][W]; either may be NULL (= zero),
- * with both NULL it is exactly gsrast_backward_ex.  The gradients reach the same outputs as the colour's (means3D through the view-space
+ * with both NULL it is gsrast_backward_ex (the options->cull rule below is checked first).  The gradients reach the same outputs as the colour's (means3D through the view-space
  * depth as well, means2D, opacities, scales / rotations or cov3D; the raw leaves on the raw pair) with the colour's conventions (the 0.99
  * clamp passes gradients through).  The backward rebuilds the depth recurrence from final_T and n_contrib back to front, as the colour's:
  * it needs nothing of the forward's aux outputs, so an aux backward on the state of a plain gsrast_forward_ex is valid.  With
@@ -514,7 +514,8 @@ int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, 
  *                                    (zero where rho sits on the floor) and scales dL/dopacity by comp.
  * The backward must get the same GSRAST_RENDER_ANTIALIAS bit as the forward that filled the state (the state does not record it).  With
  * options->backward_phase, pass the same flags to both phases.
- * GSRAST_E_ARG before any device work: unknown bits; GSRAST_RENDER_AUX with options->cull == 0; forward, GSRAST_RENDER_AUX with a NULL aux output. */
+ * GSRAST_E_ARG before any device work: unknown bits; GSRAST_RENDER_AUX with options->cull == 0; forward, GSRAST_RENDER_AUX with a NULL aux output.
+ * Every gsrast_forward* / gsrast_backward* symbol of this header is an adapter over these: one set of checks, one error text per condition. */
 #define GSRAST_RENDER_AUX        0x1u
 #define GSRAST_RENDER_ANTIALIAS  0x2u
 int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,

@@ -683,62 +683,74 @@ struct BlendArgs {
     float *oad = nullptr, *oal = nullptr;                        // forward (culling kernel), aux: acc_depth / alpha -- non-null selects AUX
     const float *dad = nullptr, *dal = nullptr;                  // backward, aux: dL/dacc_depth / dL/dalpha (either may be null)
 };
-template <int MODE, int PPL>
-void launch_fwd(uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    blend_fwd_kernel<MODE, PPL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm, a.bcnt, a.blist);
-}
-template <int MODE, int PPL, int ABL>
-void launch_bwd(uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    blend_bwd_kernel<MODE, PPL, ABL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec);
-}
-template <int MODE>
-void dispatch_fwd(int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    if (ppl == 4) launch_fwd<MODE, 4>(grid, s, a); else if (ppl == 2) launch_fwd<MODE, 2>(grid, s, a); else launch_fwd<MODE, 1>(grid, s, a);
-}
-template <int MODE, int PPL>
-void launch_bwd_cull(uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    blend_bwd_cull_kernel<MODE, PPL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
-                                                                 a.from_buckets ? a.bcnt : nullptr, a.blist);
-}
 std::atomic<int> g_sort_hint{1};          // 1: enqueue three depth-sort passes when the context's last forward had short keys (A/B switch)
 std::atomic<int> g_bwd_transposed{1};     // 1: blend_bwd_cull_t_kernel for one pixel per lane (default); 0: blend_bwd_cull_kernel<.., 1> (A/B switch)
-template <int MODE>
-void dispatch_bwd_cull(int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a)
+
+// ---- kernel selection: a runtime value -> the template instantiation.  f is called with the std::integral_constant of the V that equals v
+// (of the last V if none does); a generic lambda instantiates its kernel only for the constants it is called with. ----
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int V, int... Vs, class F>
+void pick_int(int v, F&& f)
 {
-    if (ppl == 1 && g_bwd_transposed.load()) {
-        blend_bwd_cull_t_kernel<MODE><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
-                                                           a.from_buckets ? a.bcnt : nullptr, a.blist, a.fork_word, a.fork_seq);
-        return;
+    if constexpr (sizeof...(Vs) == 0) f(int_c<V>{});
+    else if (v == V) f(int_c<V>{});
+    else pick_int<Vs...>(v, f);
+}
+template <class F>
+void pick_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
+// blend forward: <exp_mode> x (culled: <aux> | un-culled: <pixels per lane>)
+void launch_blend_fwd(int exp_mode, bool cull, int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a)
+{
+    pick_int<0, 1, 2>(exp_mode, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (cull) pick_bool(a.oad != nullptr, [&](auto aux) {
+            constexpr bool AUX = decltype(aux)::value;
+            blend_fwd_cull_kernel<MODE, AUX><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
+                                                                  a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched,
+                                                                  AUX ? a.oad : nullptr, AUX ? a.oal : nullptr);
+        });
+        else pick_int<4, 2, 1>(ppl, [&](auto lanes) {
+            constexpr int PPL = decltype(lanes)::value;
+            blend_fwd_kernel<MODE, PPL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm, a.bcnt, a.blist);
+        });
+    });
+}
+
+// Which blend backward a call launches.  `transposed` = blend_bwd_cull_t_kernel, the kernel that signals the word fork itself: decided
+// once per call (backward_impl), for the launch, for arming the fork and for the fallback signal.
+struct BwdBlendPick {
+    int ppl; bool cull; bool transposed; bool aux; int ablate;   // ablate: 1 / 2 = blend_bwd_kernel<0, 4, ablate> (experiments), else 0
+    BwdBlendPick(const gsrast_options& o, uint32_t T, bool aux_) : ppl(pick_ppl(T, true, o)), cull(o.cull != 0), aux(aux_)
+    {
+        const int abl = g_ablate.load();
+        ablate = (!aux && (abl == 1 || abl == 2)) ? abl : 0;
+        // aux: always the transposed kernel, whatever the pixels per lane and the A/B switch say
+        transposed = aux || (cull && !ablate && ppl == 1 && g_bwd_transposed.load() != 0);
     }
-    if (ppl == 4) launch_bwd_cull<MODE, 4>(grid, s, a); else if (ppl == 2) launch_bwd_cull<MODE, 2>(grid, s, a); else launch_bwd_cull<MODE, 1>(grid, s, a);
-}
-template <int MODE>
-void launch_fwd_cull(uint32_t grid, hipStream_t s, const BlendArgs& a)
+};
+// blend backward: ablation | <exp_mode> x (transposed: <aux> | culled: <pixels per lane> | un-culled: <pixels per lane>)
+void launch_blend_bwd(int exp_mode, const BwdBlendPick& k, uint32_t grid, hipStream_t s, const BlendArgs& a)
 {
-    if (a.oad)
-        blend_fwd_cull_kernel<MODE, true><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
-                                                               a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched,
-                                                               a.oad, a.oal);
-    else
-        blend_fwd_cull_kernel<MODE, false><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.oc, a.od, a.fT, a.nc, a.tm,
-                                                                a.bcnt, a.blist, a.from_buckets, a.zero4, a.n_zero4, a.hints, a.hint_sel, a.zcut_used, a.cut_scalars, a.pred, a.tile_flags, a.gate, a.cut_margin_x4, a.untouched,
-                                                                nullptr, nullptr);
-}
-// aux backward (gsrast_backward_aux): always the transposed kernel, whatever the pixels per lane and the A/B switch say
-template <int MODE>
-void launch_bwd_aux(uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    blend_bwd_cull_t_kernel<MODE, true><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
-                                                             a.from_buckets ? a.bcnt : nullptr, a.blist, a.fork_word, a.fork_seq, a.dad, a.dal);
-}
-template <int MODE>
-void dispatch_bwd(int ppl, uint32_t grid, hipStream_t s, const BlendArgs& a)
-{
-    if (ppl == 4) launch_bwd<MODE, 4, 0>(grid, s, a); else if (ppl == 2) launch_bwd<MODE, 2, 0>(grid, s, a); else launch_bwd<MODE, 1, 0>(grid, s, a);
+    const uint32_t* bcnt = a.from_buckets ? a.bcnt : nullptr;
+    auto uncull = [&](auto mode, auto lanes, auto abl) {
+        constexpr int PPL = decltype(lanes)::value;
+        blend_bwd_kernel<decltype(mode)::value, PPL, decltype(abl)::value><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec);
+    };
+    if (k.ablate) return pick_int<1, 2>(k.ablate, [&](auto abl) { uncull(int_c<0>{}, int_c<4>{}, abl); });
+    pick_int<0, 1, 2>(exp_mode, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (k.transposed) pick_bool(k.aux, [&](auto aux) {
+            constexpr bool AUX = decltype(aux)::value;
+            blend_bwd_cull_t_kernel<MODE, AUX><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
+                                                                    bcnt, a.blist, a.fork_word, a.fork_seq, AUX ? a.dad : nullptr, AUX ? a.dal : nullptr);
+        });
+        else if (k.cull) pick_int<4, 2, 1>(k.ppl, [&](auto lanes) {
+            constexpr int PPL = decltype(lanes)::value;
+            blend_bwd_cull_kernel<MODE, PPL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec, bcnt, a.blist);
+        });
+        else pick_int<4, 2, 1>(k.ppl, [&](auto lanes) { uncull(mode, lanes, int_c<0>{}); });
+    });
 }
 
 } // namespace
@@ -986,20 +998,6 @@ int gsrast_mark_visible(int P, const float* means3D, const float* viewmatrix, co
     return GSRAST_OK;
 }
 
-int gsrast_forward(gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                   void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                   const float* background, int width, int height, const float* means3D, const float* shs,
-                   const float* colors_precomp, const float* opacities, const float* scales,
-                   float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                   const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                   float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream)
-{
-    return gsrast_forward_ex(nullptr, nullptr, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M,
-                             background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                             cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth,
-                             radii, stream);
-}
-
 static int prefilter_verdict(const uint32_t* word, hipStream_t s)
 {
     uint32_t v = 0;
@@ -1008,32 +1006,65 @@ static int prefilter_verdict(const uint32_t* word, hipStream_t s)
     return v ? fail(GSRAST_E_ARG, "forward: a Gaussian passed as prefiltered was culled by the near plane (the reference traps: auxiliary.h:156-160)") : GSRAST_OK;
 }
 
-// The forward behind gsrast_forward_ex (rawin == nullptr) and gsrast_forward_raw (rawin: means3D / opacities / scales / rotations
-// are then the model's raw leaves, shs a non-null placeholder; the per-Gaussian kernels run as their RAW instantiations).
-static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
-                      gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                      void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                      const float* background, int width, int height, const float* means3D, const float* shs,
-                      const float* colors_precomp, const float* opacities, const float* scales,
-                      float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                      const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                      float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                      const gsrast_raw_inputs* rawin, float* out_acc_depth = nullptr, float* out_alpha = nullptr /* gsrast_forward_aux: both or neither */,
-                      bool aa = false /* GSRAST_RENDER_ANTIALIAS: the per-Gaussian kernel's AA instantiation */)
+static const char* raw_inputs_check(int P, int M, const gsrast_raw_inputs* in)
+{
+    if (!in) return "raw: NULL inputs";
+    if (P == 0) return nullptr;
+    if (!in->xyz || !in->rotation || !in->scaling || !in->opacity_logit || !in->features_dc || (M > 1 && !in->features_rest)) return "raw: NULL required input";
+    if (M < 1 || M * 3 > PP_SH_MAX || ((M * 3) & 3)) return "raw: M must be 4 or 16 (SH rows of a multiple of 16 bytes, at most 16 coefficients)";
+    if (((uintptr_t)in->rotation | (uintptr_t)in->features_dc | (uintptr_t)in->features_rest | (uintptr_t)in->shs_res) & 15) return "raw: rotation / features_dc / features_rest / shs_res must be 16-byte aligned";
+    return nullptr;
+}
+
+// Everything a forward is called with: every exported gsrast_forward* fills one of these from its positional arguments.
+// raw_family: the call came through a gsrast_forward_raw* symbol -- `raw` replaces the dense inputs (which stay null), prefiltered is 0.
+namespace {
+struct FwdCall {
+    gsrast_alloc_fn geometry_alloc; void* geometry_ctx; gsrast_alloc_fn binning_alloc; void* binning_ctx; gsrast_alloc_fn image_alloc; void* image_ctx;
+    int P, D, M; const float* background; int width, height;
+    const float *means3D, *shs, *colors_precomp, *opacities, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
+    const float *viewmatrix, *projmatrix, *cam_pos; float tan_fovx, tan_fovy; int prefiltered;
+    float *out_color, *out_depth; int* radii; void* stream;
+    bool raw_family; const gsrast_raw_inputs* raw;
+    unsigned flags; float *out_acc_depth, *out_alpha;      // GSRAST_RENDER_*; the aux outputs are looked at only with GSRAST_RENDER_AUX
+};
+} // namespace
+
+// The one forward.  Dense: the inputs are the activated arrays.  Raw family: means3D / opacities / scales / rotations are the model's raw
+// leaves, shs a non-null placeholder, and the per-Gaussian kernels run as their RAW instantiations.
+static int forward_impl(gsrast_context* ctx, const gsrast_options* options, const FwdCall& c)
 {
     const auto t_entry = std::chrono::steady_clock::now();
-    RoctxRange range_fwd(rawin ? "gsrast_forward_raw" : "gsrast_forward");
+    RoctxRange range_fwd(c.raw_family ? "gsrast_forward_raw" : "gsrast_forward");
     CallScope call_scope;
+    const gsrast_alloc_fn geometry_alloc = c.geometry_alloc, binning_alloc = c.binning_alloc, image_alloc = c.image_alloc;
+    void *const geometry_ctx = c.geometry_ctx, *const binning_ctx = c.binning_ctx, *const image_ctx = c.image_ctx, *const stream = c.stream;
+    const int P = c.P, D = c.D, M = c.M, width = c.width, height = c.height, prefiltered = c.prefiltered;
+    const float *const background = c.background, *const colors_precomp = c.colors_precomp, *const cov3D_precomp = c.cov3D_precomp;
+    const float *const viewmatrix = c.viewmatrix, *const projmatrix = c.projmatrix, *const cam_pos = c.cam_pos;
+    const float scale_modifier = c.scale_modifier, tan_fovx = c.tan_fovx, tan_fovy = c.tan_fovy;
+    float *const out_color = c.out_color, *const out_depth = c.out_depth; int* const radii = c.radii;
+    const float *means3D = c.means3D, *shs = c.shs, *opacities = c.opacities, *scales = c.scales, *rotations = c.rotations;
+    const bool aux = (c.flags & GSRAST_RENDER_AUX) != 0;
+    const bool aa = (c.flags & GSRAST_RENDER_ANTIALIAS) != 0;      // the per-Gaussian kernel's AA instantiation
+    float *const out_acc_depth = aux ? c.out_acc_depth : nullptr, *const out_alpha = aux ? c.out_alpha : nullptr;
+    // ---- the checks every entry point shares (before any device work or allocator callback) ----
+    if (c.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return fail(GSRAST_E_ARG, "flags: unknown bits");
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (!options_valid(o)) return fail(GSRAST_E_ARG, "forward: bad option value");
+    if (aux && (o.cull == 0 || o.fwd_pixels_per_lane != 0))
+        return fail(GSRAST_E_ARG, "forward: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)");
+    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward: NULL acc_depth / alpha output");
+    const gsrast_raw_inputs* const rawin = c.raw_family ? c.raw : nullptr;
+    if (c.raw_family) {
+        if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
+        means3D = rawin->xyz; shs = rawin->features_dc /* "there are SH coefficients" */; opacities = rawin->opacity_logit; scales = rawin->scaling; rotations = rawin->rotation;
+    }
     RawArgs raw{};
     if (rawin) {
         raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
         raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
     }
-    const gsrast_options o = options ? *options : snapshot_defaults();
-    if (!options_valid(o)) return fail(GSRAST_E_ARG, "forward: bad option value");
-    const bool aux = out_acc_depth != nullptr;
-    if (aux && (o.cull == 0 || o.fwd_pixels_per_lane != 0))
-        return fail(GSRAST_E_ARG, "forward_aux: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)");
     if (!ctx) ctx = thread_context();
     hipStream_t s = (hipStream_t)stream;
     const int W = width, H = height;
@@ -1304,12 +1335,12 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
             if (tau_ctx_device < 0) GS_HIP(hipMemsetAsync(tau_hist, 0, words * sizeof(uint32_t), s));
         }
         const int nzero = bucket_sort ? (int)nbk * BK_XCD + BK_XCD * BK_NBC_MAX : 0;      // (fine counters + the two-launch scatter's coarse ones, contiguous)
-#define GS_PF_ARGS P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg, \
-                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel, \
-                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins
-        if (rawin) { if (aa) preprocess_fwd_kernel<true, true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); else preprocess_fwd_kernel<true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); }
-        else { if (aa) preprocess_fwd_kernel<false, true><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); else preprocess_fwd_kernel<false><<<pf_grid, PF_THREADS, 0, s>>>(GS_PF_ARGS); }
-#undef GS_PF_ARGS
+        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(aa, [&](auto aa_c) {       // <RAW, AA>
+            preprocess_fwd_kernel<decltype(raw_c)::value, decltype(aa_c)::value><<<pf_grid, PF_THREADS, 0, s>>>(
+                P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg,
+                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel,
+                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins);
+        }); });
         GS_LAUNCHED("preprocess_fwd");
         ctx->last_prologue_ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(), 0xFFFFFFFFll);
         if (tau_hist) {       // the predicted cut depths of a pose without remembered ones (a no-op for a pose the table knows, unless forced)
@@ -1549,11 +1580,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
                 ba.order = ord;
             }
         }
-        switch (o.exp_mode) {
-        case 0: if (cull) launch_fwd_cull<0>(grid, s, ba); else dispatch_fwd<0>(ppl, grid, s, ba); break;
-        case 1: if (cull) launch_fwd_cull<1>(grid, s, ba); else dispatch_fwd<1>(ppl, grid, s, ba); break;
-        default: if (cull) launch_fwd_cull<2>(grid, s, ba); else dispatch_fwd<2>(ppl, grid, s, ba); break;
-        }
+        launch_blend_fwd(o.exp_mode, cull, ppl, grid, s, ba);
         GS_LAUNCHED("blend_fwd");
         if (side && !zero_in_blend) { GS_HIP(hipStreamWaitEvent(s, side->join2, 0)); side_guard.joined = true; }      // the gradient records are zero before anything after this forward
         return GSRAST_OK;
@@ -1771,6 +1798,34 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options,
     return (int)R;
 }
 
+// ---- the exported forwards: adapters that fill a FwdCall (include/gsrast.h: gsrast_forward = _ex(NULL, NULL) = _flags(0), _aux = _flags(AUX)) ----
+int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
+                         void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
+                         const float* background, int width, int height, const float* means3D, const float* shs,
+                         const float* colors_precomp, const float* opacities, const float* scales,
+                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                         const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                         float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
+                         float* out_acc_depth, float* out_alpha)
+{
+    return forward_impl(ctx, options, FwdCall{ geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, false, nullptr, flags, out_acc_depth, out_alpha });
+}
+
+int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
+                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
+                             gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
+                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
+                             float* out_acc_depth, float* out_alpha)
+{
+    return forward_impl(ctx, options, FwdCall{ geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix, projmatrix, cam_pos,
+                        tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, true, in, flags, out_acc_depth, out_alpha });
+}
+
 int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
                       void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
@@ -1780,9 +1835,22 @@ int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream)
 {
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr);
+    return gsrast_forward_flags(ctx, options, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, nullptr);
+}
+
+int gsrast_forward(gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
+                   void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
+                   const float* background, int width, int height, const float* means3D, const float* shs,
+                   const float* colors_precomp, const float* opacities, const float* scales,
+                   float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                   const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                   float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream)
+{
+    return gsrast_forward_flags(nullptr, nullptr, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, nullptr);
 }
 
 int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
@@ -1795,20 +1863,9 @@ int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
                        float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
                        float* out_acc_depth, float* out_alpha)
 {
-    if (!out_acc_depth || !out_alpha) return fail(GSRAST_E_ARG, "forward_aux: NULL acc_depth / alpha output");
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, out_acc_depth, out_alpha);
-}
-
-static const char* raw_inputs_check(int P, int M, const gsrast_raw_inputs* in)
-{
-    if (!in) return "raw: NULL inputs";
-    if (P == 0) return nullptr;
-    if (!in->xyz || !in->rotation || !in->scaling || !in->opacity_logit || !in->features_dc || (M > 1 && !in->features_rest)) return "raw: NULL required input";
-    if (M < 1 || M * 3 > PP_SH_MAX || ((M * 3) & 3)) return "raw: M must be 4 or 16 (SH rows of a multiple of 16 bytes, at most 16 coefficients)";
-    if (((uintptr_t)in->rotation | (uintptr_t)in->features_dc | (uintptr_t)in->features_rest | (uintptr_t)in->shs_res) & 15) return "raw: rotation / features_dc / features_rest / shs_res must be 16-byte aligned";
-    return nullptr;
+    return gsrast_forward_flags(ctx, options, GSRAST_RENDER_AUX, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, out_acc_depth, out_alpha);
 }
 
 int gsrast_forward_raw(gsrast_context* ctx, const gsrast_options* options,
@@ -1817,10 +1874,8 @@ int gsrast_forward_raw(gsrast_context* ctx, const gsrast_options* options,
                        const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                        float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream)
 {
-    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in);
+    return gsrast_forward_raw_flags(ctx, options, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                                    in, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, radii, stream, nullptr, nullptr);
 }
 
 int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
@@ -1830,58 +1885,8 @@ int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
                            float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
                            float* out_acc_depth, float* out_alpha)
 {
-    if (!out_acc_depth || !out_alpha) return fail(GSRAST_E_ARG, "forward_raw_aux: NULL acc_depth / alpha output");
-    if ((options ? *options : snapshot_defaults()).cull == 0) return fail(GSRAST_E_ARG, "forward_raw_aux: acc_depth / alpha need the culled blend kernel (options.cull != 0)");
-    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in, out_acc_depth, out_alpha);
-}
-
-// ---- the flags-word entry points (GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS): one family for every combination ----
-// flags = 0 is gsrast_forward_ex / _raw, AUX is gsrast_forward_aux / _raw_aux; argument errors return before any device work.
-static const char* render_flags_check(unsigned flags, const gsrast_options* options)
-{
-    if (flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return "flags: unknown bits";
-    if ((flags & GSRAST_RENDER_AUX) && (options ? *options : snapshot_defaults()).cull == 0)
-        return "flags: GSRAST_RENDER_AUX (acc_depth / alpha) needs the culled blend kernels (options.cull != 0)";
-    return nullptr;
-}
-
-int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                         void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                         const float* background, int width, int height, const float* means3D, const float* shs,
-                         const float* colors_precomp, const float* opacities, const float* scales,
-                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                         const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                         float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                         float* out_acc_depth, float* out_alpha)
-{
-    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
-    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
-    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward_flags: NULL acc_depth / alpha output");
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, aux ? out_acc_depth : nullptr,
-                        aux ? out_alpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
-}
-
-int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                             gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
-                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
-                             float* out_acc_depth, float* out_alpha)
-{
-    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
-    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
-    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward_raw_flags: NULL acc_depth / alpha output");
-    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
-    return forward_impl(ctx, options, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        in->xyz, in->features_dc /* "there are SH coefficients" */, nullptr, in->opacity_logit, in->scaling, scale_modifier, in->rotation, nullptr,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, in, aux ? out_acc_depth : nullptr,
-                        aux ? out_alpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
+    return gsrast_forward_raw_flags(ctx, options, GSRAST_RENDER_AUX, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
+                                    in, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, radii, stream, out_acc_depth, out_alpha);
 }
 
 int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_res, const float* rotation,
@@ -2318,44 +2323,68 @@ int gsrast_sh_grad_combine_union(int P, int D, int M, int N, const float* means3
     return GSRAST_OK;
 }
 
-int gsrast_backward(int P, int D, int M, int R, const float* background, int width, int height,
-                    const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                    float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                    const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                    float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                    const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream)
-{
-    return gsrast_backward_ex(nullptr, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                              cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
-                              image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                              dL_dscale, dL_drot, stream);
-}
+// Everything a backward is called with: every exported gsrast_backward* fills one of these from its positional arguments.
+// raw_family: the call came through a gsrast_backward_raw* symbol -- `raw` / `raw_grads` replace the dense inputs and gradient outputs (which stay null).
+namespace {
+struct BwdCall {
+    int P, D, M, R; const float* background; int width, height;
+    const float *means3D, *shs, *colors_precomp, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
+    const float *viewmatrix, *projmatrix, *campos; float tan_fovx, tan_fovy; const int* radii;
+    char *geom_buffer, *binning_buffer, *image_buffer; const float* dL_dpix;
+    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot; void* stream;
+    bool raw_family; const gsrast_raw_inputs* raw; const gsrast_raw_grads* raw_grads;
+    unsigned flags; const float *dL_dacc_depth, *dL_dalpha;      // GSRAST_RENDER_*; the aux gradients are looked at only with GSRAST_RENDER_AUX
+};
+} // namespace
 
-static int backward_impl(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                       const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                       const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                       const gsrast_raw_inputs* rawin, const gsrast_raw_grads* rawout,
-                       const float* dL_dacc_depth = nullptr, const float* dL_dalpha = nullptr /* gsrast_backward_aux: either may be null */,
-                       bool aa = false /* GSRAST_RENDER_ANTIALIAS: the state comes from an anti-aliased forward */)
+// The one backward.  Raw family: the dense arrays are the model's raw leaves and their gradients, taken from the two structs here.
+static int backward_impl(const gsrast_options* options, const BwdCall& c)
 {
-    RoctxRange range_bwd(rawin ? "gsrast_backward_raw" : "gsrast_backward");
+    RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
     CallScope call_scope;
+    const int P = c.P, D = c.D, M = c.M, R = c.R, width = c.width, height = c.height;
+    const float *const background = c.background, *const viewmatrix = c.viewmatrix, *const projmatrix = c.projmatrix, *const campos = c.campos;
+    const float scale_modifier = c.scale_modifier, tan_fovx = c.tan_fovx, tan_fovy = c.tan_fovy;
+    const int* const radii = c.radii; const float* const dL_dpix = c.dL_dpix; void* const stream = c.stream;
+    char *const geom_buffer = c.geom_buffer, *const binning_buffer = c.binning_buffer, *const image_buffer = c.image_buffer;
+    const float *means3D = c.means3D, *shs = c.shs, *colors_precomp = c.colors_precomp, *scales = c.scales, *rotations = c.rotations, *cov3D_precomp = c.cov3D_precomp;
+    float *dL_dmean2D = c.dL_dmean2D, *dL_dconic = c.dL_dconic, *dL_dopacity = c.dL_dopacity, *dL_dcolor = c.dL_dcolor, *dL_dmean3D = c.dL_dmean3D;
+    float *dL_dcov3D = c.dL_dcov3D, *dL_dsh = c.dL_dsh, *dL_dscale = c.dL_dscale, *dL_drot = c.dL_drot;
+    const bool aux_flag = (c.flags & GSRAST_RENDER_AUX) != 0;
+    const bool aa = (c.flags & GSRAST_RENDER_ANTIALIAS) != 0;      // the state comes from an anti-aliased forward
+    // the aux gradients: either may be null (= zero); both null is the plain backward
+    const float *const dL_dacc_depth = aux_flag ? c.dL_dacc_depth : nullptr, *const dL_dalpha = aux_flag ? c.dL_dalpha : nullptr;
+    const bool aux = dL_dacc_depth != nullptr || dL_dalpha != nullptr;
+    // ---- the checks every entry point shares (before any device work) ----
+    if (c.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return fail(GSRAST_E_ARG, "flags: unknown bits");
+    gsrast_options o = options ? *options : snapshot_defaults();
+    if (!options_valid(o)) return fail(GSRAST_E_ARG, "backward: bad option value");
+    if (aux_flag && o.cull == 0) return fail(GSRAST_E_ARG, "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
+    const gsrast_raw_inputs* const rawin = c.raw_family ? c.raw : nullptr;
     RawArgs raw{}; RawGrads rawg{};
-    if (rawin) {
+    if (c.raw_family) {
+        const gsrast_raw_grads* const out = c.raw_grads;
+        if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
+        if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
+        if (P == 0) return GSRAST_OK;
+        if (!out->dL_dmean2D || !out->d_xyz || !out->d_rotation || !out->d_scaling || !out->d_opacity_logit) return fail(GSRAST_E_ARG, "backward_raw: NULL required gradient output");
+        if ((rawin->rot_res != nullptr) != (out->d_rot_res != nullptr) && rawin->rot_res == nullptr) return fail(GSRAST_E_ARG, "backward_raw: d_rot_res without rot_res");
+        if (out->d_shs_res && !rawin->shs_res) return fail(GSRAST_E_ARG, "backward_raw: d_shs_res without shs_res");
+        const bool fac = out->d_sh_factor != nullptr;       // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
+        if (fac && (rawin->shs_res || out->d_shs_res)) return fail(GSRAST_E_ARG, "backward_raw: d_sh_factor cannot be combined with shs_res / d_shs_res");
+        if ((out->d_features_dc != nullptr) != (M > 1 ? out->d_features_rest != nullptr : out->d_features_dc != nullptr) || (!fac && !out->d_shs_res && !out->d_features_dc))
+            return fail(GSRAST_E_ARG, "backward_raw: give d_features_dc + d_features_rest and / or (with shs_res) d_shs_res, whose rows hold both");
+        if (((uintptr_t)out->d_rotation | (uintptr_t)out->d_features_dc | (uintptr_t)out->d_features_rest | (uintptr_t)out->d_shs_res) & 15)
+            return fail(GSRAST_E_ARG, "backward_raw: d_rotation / d_features_dc / d_features_rest / d_shs_res must be 16-byte aligned");
+        o.sh_grad_factors = fac ? 1 : 0;
+        means3D = rawin->xyz; shs = rawin->features_dc; scales = rawin->scaling; rotations = rawin->rotation;
+        dL_dmean2D = out->dL_dmean2D; dL_dopacity = out->d_opacity_logit; dL_dmean3D = out->d_xyz; dL_dscale = out->d_scaling; dL_drot = out->d_rotation;
+        dL_dsh = fac ? out->d_sh_factor : (out->d_shs_res ? out->d_shs_res : out->d_features_dc);      // (a marker, but for the factor)
         raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
         raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
-        rawg.d_rot_res = rawout->d_rot_res; rawg.d_trbf = rawout->d_trbf; rawg.d_dc = rawout->d_features_dc; rawg.d_rest = rawout->d_features_rest;
-        rawg.d_shs_res = rawout->d_shs_res;
+        rawg.d_rot_res = out->d_rot_res; rawg.d_trbf = out->d_trbf; rawg.d_shs_res = out->d_shs_res;
+        if (!fac) { rawg.d_dc = out->d_features_dc; rawg.d_rest = out->d_features_rest; }     // (factor: not written, the caller completes them after the exchange)
     }
-    const gsrast_options o = options ? *options : snapshot_defaults();
-    if (!options_valid(o)) return fail(GSRAST_E_ARG, "backward: bad option value");
-    const bool aux = dL_dacc_depth != nullptr || dL_dalpha != nullptr;
-    if (aux && o.cull == 0) return fail(GSRAST_E_ARG, "backward_aux: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
     hipStream_t s = (hipStream_t)stream;
     const int W = width, H = height;
     if (P < 0 || R < 0 || W <= 0 || H <= 0) return fail(GSRAST_E_ARG, "backward: bad sizes");
@@ -2374,6 +2403,7 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
 
     const CamArgs cam = make_cam(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, W, H);
     const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
+    const BwdBlendPick bwd_pick(o, T, aux);
     const GeomLayout GL = geom_layout((size_t)P);
     const ImgLayout IL = img_layout((size_t)W, (size_t)H);
     char* geom = geom_buffer; char* bin = binning_buffer; char* img = image_buffer;
@@ -2427,7 +2457,8 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         if (!side) {
             side = side_stream_of(thread_context());
             // word fork: the blend backward below signals its own start, the side stream waits for that -- when it is the transposed kernel
-            if (side && o.cull != 0 && o.lpt && (aux || (pick_ppl(T, true, o) == 1 && g_bwd_transposed.load() && g_ablate.load() == 0))) late_fork = fork_word_next(thread_context(), side, s);
+            // (the experiments' ablations keep the event fork)
+            if (side && bwd_pick.transposed && o.lpt && (aux || g_ablate.load() == 0)) late_fork = fork_word_next(thread_context(), side, s);
             if (side && !late_fork.word) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
         }
         if (side) {
@@ -2476,9 +2507,7 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
                 ba.bg = zero_bg;
             }
         }
-        const int ppl = pick_ppl(T, true, o);
-        const bool cull = o.cull != 0;
-        if (cull && o.lpt) {
+        if (bwd_pick.cull && o.lpt) {
             if (T <= BUCKET_MAX_TILES) {      // the forward blend appended every tile to the backward work buckets
                 ba.bcnt = const_cast<uint32_t*>(at<uint32_t>(img, IL.bucket_cnt)); ba.blist = const_cast<uint16_t*>(at<uint16_t>(img, IL.bucket_list));
                 ba.from_buckets = 1;
@@ -2489,20 +2518,10 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
                 ba.order = ord;
             }
         }
-        if (aux) {
-            switch (o.exp_mode) { case 0: launch_bwd_aux<0>(grid, s, ba); break; case 1: launch_bwd_aux<1>(grid, s, ba); break; default: launch_bwd_aux<2>(grid, s, ba); break; }
-        } else
-        if (g_ablate.load() == 1) launch_bwd<0, 4, 1>(grid, s, ba);
-        else if (g_ablate.load() == 2) launch_bwd<0, 4, 2>(grid, s, ba);
-        else
-        switch (o.exp_mode) {
-        case 0: if (cull) dispatch_bwd_cull<0>(ppl, grid, s, ba); else dispatch_bwd<0>(ppl, grid, s, ba); break;
-        case 1: if (cull) dispatch_bwd_cull<1>(ppl, grid, s, ba); else dispatch_bwd<1>(ppl, grid, s, ba); break;
-        default: if (cull) dispatch_bwd_cull<2>(ppl, grid, s, ba); else dispatch_bwd<2>(ppl, grid, s, ba); break;
-        }
+        launch_blend_bwd(o.exp_mode, bwd_pick, grid, s, ba);
         GS_LAUNCHED("blend_bwd");
         // (belt and braces: should anything but the signalling kernel have been launched, the caller's stream releases the side stream itself)
-        if (late_fork.word && !aux && !(g_ablate.load() == 0 && cull && ppl == 1 && g_bwd_transposed.load())) GS_HIP(hipStreamWriteValue32(s, late_fork.word, late_fork.seq, 0));
+        if (late_fork.word && !bwd_pick.transposed) GS_HIP(hipStreamWriteValue32(s, late_fork.word, late_fork.seq, 0));
     }
     if (late_fork.word) { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }      // (its wait was released by the kernel just launched, or will be)
     if (do_blend && use_sh && o.sh_grad_factors) {      // dL_dsh is [P][3] in this mode: the factor, final after the blend backward
@@ -2522,26 +2541,50 @@ static int backward_impl(const gsrast_options* options, int P, int D, int M, int
         const float* sc_in = rawin ? scales : (use_sr ? scales : nullptr);
         const float* ro_in = rawin ? rotations : (use_sr ? rotations : nullptr);
         const int factors = (use_sh && o.sh_grad_factors) ? 1 : 0;
-#define GS_PB_ARGS P, D, M, means3D, radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB), \
-                   at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,  \
-                   dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched), \
-                   aux ? 1 : 0, rec1
-        // (aa: the kernel's AA instantiation -- the plain ones are the same code as before the flag existed)
-#define GS_PB_LAUNCH(RW, SP, GR, grid) do { if (aa) preprocess_bwd_kernel<RW, SP, GR, true><<<grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); \
-                                            else preprocess_bwd_kernel<RW, SP, GR><<<grid, PP_THREADS, 0, s>>>(GS_PB_ARGS); } while (0)
         const bool skip = !o.dense_backward;        // Gaussians with an all-zero gradient record are not read
-        if (late_fill) {       // (late_fill implies skip) grouped: 1024 Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
-            const int gg = (P + PB_GROUP - 1) / PB_GROUP;
-            if (rawin) GS_PB_LAUNCH(true, true, true, gg); else GS_PB_LAUNCH(false, true, true, gg);
-        } else
-        if (rawin) { if (skip) GS_PB_LAUNCH(true, true, false, pb_grid); else GS_PB_LAUNCH(true, false, false, pb_grid); }
-        else { if (skip) GS_PB_LAUNCH(false, true, false, pb_grid); else GS_PB_LAUNCH(false, false, false, pb_grid); }
-#undef GS_PB_LAUNCH
-#undef GS_PB_ARGS
+        // <RAW, SPARSE, GROUPED, AA> (aa: the kernel's AA instantiation -- the plain ones are the same code as before the flag existed)
+        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(aa, [&](auto aa_c) {
+            auto launch = [&](auto sparse_c, auto grouped_c, int grid) {
+                preprocess_bwd_kernel<decltype(raw_c)::value, decltype(sparse_c)::value, decltype(grouped_c)::value, decltype(aa_c)::value><<<grid, PP_THREADS, 0, s>>>(
+                    P, D, M, means3D, radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB),
+                    at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched),
+                    aux ? 1 : 0, rec1);
+            };
+            // (late_fill implies skip) grouped: 1024 Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
+            if (late_fill) launch(std::true_type{}, std::true_type{}, (P + PB_GROUP - 1) / PB_GROUP);
+            else pick_bool(skip, [&](auto sparse_c) { launch(sparse_c, std::false_type{}, pb_grid); });
+        }); });
         GS_LAUNCHED("preprocess_bwd");
     }
     if (join_late) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); side_guard.joined = true; }
     return GSRAST_OK;
+}
+
+// ---- the exported backwards: adapters that fill a BwdCall (include/gsrast.h: gsrast_backward = _ex(NULL) = _flags(0), _aux = _flags(AUX)) ----
+int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                          const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                          float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                          const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                          const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
+                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha });
+}
+
+int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                              const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                              float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                              const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha });
 }
 
 int gsrast_backward_ex(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
@@ -2552,9 +2595,22 @@ int gsrast_backward_ex(const gsrast_options* options, int P, int D, int M, int R
                        const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream)
 {
-    return backward_impl(options, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
+    return gsrast_backward_flags(options, 0, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
+}
+
+int gsrast_backward(int P, int D, int M, int R, const float* background, int width, int height,
+                    const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                    float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                    const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                    float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                    const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream)
+{
+    return gsrast_backward_flags(nullptr, 0, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
 }
 
 int gsrast_backward_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
@@ -2566,40 +2622,9 @@ int gsrast_backward_aux(const gsrast_options* options, int P, int D, int M, int 
                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
                         const float* dL_dacc_depth, const float* dL_dalpha)
 {
-    return backward_impl(options, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr,
-                         dL_dacc_depth, dL_dalpha);
-}
-
-static int backward_raw_impl(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                             float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                             const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
-                             bool aa = false)
-{
-    if (const char* e = raw_inputs_check(P, M, in)) return fail(GSRAST_E_ARG, e);
-    if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
-    if (P == 0) return GSRAST_OK;
-    if (!out->dL_dmean2D || !out->d_xyz || !out->d_rotation || !out->d_scaling || !out->d_opacity_logit) return fail(GSRAST_E_ARG, "backward_raw: NULL required gradient output");
-    if ((in->rot_res != nullptr) != (out->d_rot_res != nullptr) && in->rot_res == nullptr) return fail(GSRAST_E_ARG, "backward_raw: d_rot_res without rot_res");
-    if (out->d_shs_res && !in->shs_res) return fail(GSRAST_E_ARG, "backward_raw: d_shs_res without shs_res");
-    const bool fac = out->d_sh_factor != nullptr;       // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
-    if (fac && (in->shs_res || out->d_shs_res)) return fail(GSRAST_E_ARG, "backward_raw: d_sh_factor cannot be combined with shs_res / d_shs_res");
-    if ((out->d_features_dc != nullptr) != (M > 1 ? out->d_features_rest != nullptr : out->d_features_dc != nullptr) || (!fac && !out->d_shs_res && !out->d_features_dc))
-        return fail(GSRAST_E_ARG, "backward_raw: give d_features_dc + d_features_rest and / or (with shs_res) d_shs_res, whose rows hold both");
-    if (((uintptr_t)out->d_rotation | (uintptr_t)out->d_features_dc | (uintptr_t)out->d_features_rest | (uintptr_t)out->d_shs_res) & 15)
-        return fail(GSRAST_E_ARG, "backward_raw: d_rotation / d_features_dc / d_features_rest / d_shs_res must be 16-byte aligned");
-    gsrast_options o = options ? *options : snapshot_defaults();
-    o.sh_grad_factors = fac ? 1 : 0;
-    gsrast_raw_grads og = *out;
-    if (fac) { og.d_features_dc = nullptr; og.d_features_rest = nullptr; }     // (not written: the caller completes them after the exchange)
-    out = &og;
-    float* sh_marker = fac ? out->d_sh_factor : (out->d_shs_res ? out->d_shs_res : out->d_features_dc);
-    return backward_impl(&o, P, D, M, R, background, width, height, in->xyz, in->features_dc, nullptr, in->scaling, scale_modifier, in->rotation, nullptr,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out->dL_dmean2D,
-                         nullptr, out->d_opacity_logit, nullptr, out->d_xyz, nullptr, sh_marker, out->d_scaling, out->d_rotation, stream, in, out,
-                         dL_dacc_depth, dL_dalpha, aa);
+    return gsrast_backward_flags(options, GSRAST_RENDER_AUX, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, dL_dacc_depth, dL_dalpha);
 }
 
 int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
@@ -2607,8 +2632,8 @@ int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int 
                         float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                         const float* dL_dpix, const gsrast_raw_grads* out, void* stream)
 {
-    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, nullptr, nullptr);
+    return gsrast_backward_raw_flags(options, 0, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                     radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, nullptr, nullptr);
 }
 
 int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
@@ -2616,41 +2641,8 @@ int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, 
                             float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                             const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
 {
-    if ((dL_dacc_depth || dL_dalpha) && (options ? *options : snapshot_defaults()).cull == 0)
-        return fail(GSRAST_E_ARG, "backward_raw_aux: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
-    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, dL_dacc_depth, dL_dalpha);
-}
-
-// flags = 0 is gsrast_backward_ex / _raw, AUX is gsrast_backward_aux / _raw_aux (the aux gradients: either may be NULL); ANTIALIAS must be what
-// the forward that filled the state was given
-int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                          const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                          float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                          const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                          const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
-    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
-    return backward_impl(options, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr,
-                         aux ? dL_dacc_depth : nullptr, aux ? dL_dalpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
-}
-
-int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                              const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                              float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                              const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    if (const char* e = render_flags_check(flags, options)) return fail(GSRAST_E_ARG, e);
-    const bool aux = (flags & GSRAST_RENDER_AUX) != 0;
-    return backward_raw_impl(options, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                             radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, aux ? dL_dacc_depth : nullptr,
-                             aux ? dL_dalpha : nullptr, (flags & GSRAST_RENDER_ANTIALIAS) != 0);
+    return gsrast_backward_raw_flags(options, GSRAST_RENDER_AUX, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                     radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, dL_dacc_depth, dL_dalpha);
 }
 
 int gsrast_debug_export(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,

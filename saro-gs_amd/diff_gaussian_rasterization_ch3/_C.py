@@ -140,33 +140,20 @@ def lib() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
     vp, ci, cf = C.c_void_p, C.c_int, C.c_float
-    L.gsrast_forward.restype = ci
-    L.gsrast_forward.argtypes = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp,
-                                 vp, cf, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]
-    L.gsrast_backward.restype = ci
-    L.gsrast_backward.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp,
-                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_forward_ex.restype = ci
-    L.gsrast_forward_ex.argtypes = [vp, C.POINTER(OptionsStruct)] + L.gsrast_forward.argtypes
-    L.gsrast_backward_ex.restype = ci
-    L.gsrast_backward_ex.argtypes = [C.POINTER(OptionsStruct)] + L.gsrast_backward.argtypes
-    L.gsrast_forward_raw.restype = ci
-    L.gsrast_forward_raw.argtypes = [vp, C.POINTER(OptionsStruct), _ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci,
-                                     C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf, vp, vp, vp, vp]
-    L.gsrast_backward_raw.restype = ci
-    L.gsrast_backward_raw.argtypes = [C.POINTER(OptionsStruct), ci, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf,
-                                      vp, vp, vp, vp, vp, C.POINTER(RawGradsStruct), vp]
-    # the aux entry points: their siblings' arguments + the two [1,H,W] arrays (outputs / upstream gradients, NULL = zero)
-    for name, sib in (("gsrast_forward_aux", "gsrast_forward_ex"), ("gsrast_backward_aux", "gsrast_backward_ex"),
-                      ("gsrast_forward_raw_aux", "gsrast_forward_raw"), ("gsrast_backward_raw_aux", "gsrast_backward_raw")):
-        getattr(L, name).restype = ci
-        getattr(L, name).argtypes = getattr(L, sib).argtypes + [vp, vp]
-    # the flags entry points: the aux ones' arguments with the flags word behind the options
-    for name, sib, at in (("gsrast_forward_flags", "gsrast_forward_aux", 2), ("gsrast_backward_flags", "gsrast_backward_aux", 1),
-                          ("gsrast_forward_raw_flags", "gsrast_forward_raw_aux", 2), ("gsrast_backward_raw_flags", "gsrast_backward_raw_aux", 1)):
-        a = list(getattr(L, sib).argtypes)
-        getattr(L, name).restype = ci
-        getattr(L, name).argtypes = a[:at] + [C.c_uint] + a[at:]
+    opt = C.POINTER(OptionsStruct)
+    fwd = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]
+    bwd = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    fwd_raw = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf, vp, vp, vp, vp]
+    bwd_raw = [ci, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, C.POINTER(RawGradsStruct), vp]
+    # every render family: the legacy symbol without options, the plain one, _aux (+ the two [1,H,W] arrays: outputs / upstream gradients,
+    # NULL = zero) and _flags (the flags word behind the options) -- the one this binding calls (_render_call)
+    for family, legacy, plain, head, args in (("forward", "gsrast_forward", "_ex", [vp, opt], fwd), ("backward", "gsrast_backward", "_ex", [opt], bwd),
+                                              ("forward_raw", None, "", [vp, opt], fwd_raw), ("backward_raw", None, "", [opt], bwd_raw)):
+        table = [("gsrast_" + family + plain, head + args), ("gsrast_" + family + "_aux", head + args + [vp, vp]),
+                 ("gsrast_" + family + "_flags", head + [C.c_uint] + args + [vp, vp])]
+        for name, types in table + ([(legacy, args)] if legacy else []):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = types
     L.gsrast_options_init.restype = None
     L.gsrast_options_init.argtypes = [C.POINTER(OptionsStruct)]
     L.gsrast_context_create.restype = vp
@@ -510,6 +497,37 @@ class _Arena:
             self.callbacks = None
 
 
+def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple) -> int:
+    """The one native render call: gsrast_<family>_flags(*head, flags, *args, *aux) for family "forward" / "backward" / "forward_raw" /
+    "backward_raw" (flags = 0 is exactly the _ex / _raw call, include/gsrast.h).  Returns its result (forward: the number of rendered
+    instances), raises on an error code."""
+    name = "gsrast_" + family + "_flags"
+    rc = getattr(lib(), name)(*head, flags, *args, *aux)
+    if rc < 0:
+        raise _err(rc, name)
+    return rc
+
+
+def _forward(family: str, dev: torch.device, P: int, H: int, W: int, inputs: tuple, forward_only: bool, aux: bool, antialiasing: bool):
+    """What the dense and the raw forward share: the outputs, the state arena, the call (`inputs`: the symbol's arguments between the
+    allocators and out_color) and the return tuple."""
+    o = dict(dtype=torch.float32, device=dev)
+    out_color, out_depth = torch.empty((NUM_CHANNELS, H, W), **o), torch.empty((1, H, W), **o)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    aux_out = (torch.empty((1, H, W), **o), torch.empty((1, H, W), **o)) if aux else ()
+    arena = _Arena.acquire(dev)
+    try:
+        with _on_device(dev):
+            rendered = _render_call(
+                family, (_current_context(), C.byref(_options_struct(forward_only=forward_only))),       # context: the innermost `with Context()` of the calling thread, else the thread's own
+                (*arena.forward_allocators(P, W, H), *inputs, out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), _stream_of(dev)),
+                (RENDER_AUX if aux else 0) | (RENDER_ANTIALIAS if antialiasing else 0),
+                (aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None))
+        return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
+    finally:
+        arena.close()       # break the arena <-> callback cycle now, not whenever the cyclic GC runs
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height,
                         image_width, sh, degree, campos, prefiltered, *, forward_only: bool = False, aux: bool = False,
@@ -518,47 +536,65 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     ``(num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer,
     out_depth[1,H,W])``.  `forward_only` (not in the reference): no backward will follow on the returned state (the autograd
     node passes it when no input requires a gradient): the library skips what it only prepares for the backward.
-    `aux` (not in the reference): gsrast_forward_aux, the tuple continues with ``acc_depth[1,H,W], alpha[1,H,W]``
-    (include/gsrast.h); without it the call is gsrast_forward_ex and allocates nothing more.
-    `antialiasing` (not in the reference): gsrast_forward_flags with GSRAST_RENDER_ANTIALIAS -- the opacity-compensated 2-D filter; the
+    `aux` (not in the reference): GSRAST_RENDER_AUX, the tuple continues with ``acc_depth[1,H,W], alpha[1,H,W]``
+    (include/gsrast.h); without it nothing more is allocated.
+    `antialiasing` (not in the reference): GSRAST_RENDER_ANTIALIAS -- the opacity-compensated 2-D filter; the
     backward on the returned state must be given antialiasing=True as well."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:56-58
     dev = _require_gpu(means3D)
-    L = lib()
     P, H, W = int(means3D.shape[0]), int(image_height), int(image_width)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, means3D, colors, opacity = f(background, "bg"), f(means3D, "means3D"), f(colors, "colors_precomp"), f(opacity, "opacities")
     scales, rotations, cov3D_precomp = f(scales, "scales"), f(rotations, "rotations"), f(cov3D_precomp, "cov3D_precomp")
     viewmatrix, projmatrix, sh, campos = f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(sh, "shs"), f(campos, "campos")
     M = int(sh.shape[1]) if sh.numel() != 0 else 0  # rasterize_points.cu:83-87
+    inputs = (P, int(degree), M, background.data_ptr(), W, H, means3D.data_ptr(), _ptr(sh), _ptr(colors), opacity.data_ptr(),
+              _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
+              projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)))
+    return _forward("forward", dev, P, H, W, inputs, forward_only, aux, antialiasing)
 
-    out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
-    out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-    radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    aux_out = (torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev)) if aux else ()
-    arena = _Arena.acquire(dev)
-    try:
-        with _on_device(dev):
-            stream = _stream_of(dev)
-            args = (_current_context(), C.byref(_options_struct(forward_only=forward_only)),       # context: the innermost `with Context()` of the calling thread, else the thread's own
-                    *arena.forward_allocators(P, W, H),
-                    P, int(degree), M, background.data_ptr(), W, H, means3D.data_ptr(), _ptr(sh), _ptr(colors), opacity.data_ptr(),
-                    _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
-                    projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                    out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), stream)
-            if antialiasing:
-                flags = RENDER_ANTIALIAS | (RENDER_AUX if aux else 0)
-                rendered = L.gsrast_forward_flags(args[0], args[1], flags, *args[2:], *((aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None)))
-            elif aux:
-                rendered = L.gsrast_forward_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
-            else:
-                rendered = L.gsrast_forward_ex(*args)
-        if rendered < 0:
-            raise _err(rendered, "gsrast_forward_flags" if antialiasing else "gsrast_forward_aux" if aux else "gsrast_forward")
-        return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
-    finally:
-        arena.close()       # break the arena <-> callback cycle now, not whenever the cyclic GC runs
+
+def _claim_grad_arena(fits, P: int, campos: torch.Tensor, degree: int, no_factors: Optional[str] = None) -> Optional["GradArena"]:
+    """The installed GradArena if this backward writes into it, else None: it must fit the call (`fits(arena)`) and be clean -- a second
+    backward of the same step gets ordinary tensors (GradArena docstring), which factor mode cannot allow.  `no_factors`: why this call
+    cannot be served in factor mode.  A claimed arena is marked dirty; in factor mode the camera position goes behind the factor."""
+    ar = _grad_arena
+    if ar is None or not fits(ar):
+        return None
+    if ar.dirty:
+        if ar.sh_factors:
+            raise RuntimeError("GradArena(sh_factors=True): a second backward before zero_grad() would overwrite the first view's "
+                               "factor; use one view per rank and exchange, or the plain arena (which accumulates)")
+        return None                     # ordinary tensors: autograd adds them into the arena views it adopted as .grad
+    if ar.sh_factors and no_factors:
+        raise RuntimeError(no_factors)
+    ar.dirty = True
+    if ar.sh_factors:
+        # the SH gradient (views of the arena) is returned to autograd as usual but only becomes valid after
+        # sh_grad_combine(); the kernel writes this view's factor g[P,3] (+ the camera position behind it)
+        ar.factor[3 * P: 3 * P + 3].copy_(campos.reshape(-1)[:3])
+        ar.last_degree = int(degree)
+    return ar
+
+
+def _run_backward(ar: Optional["GradArena"], call, P: int, geomBuffer: torch.Tensor, dev: torch.device) -> None:
+    """call(phase) enqueues the native backward (0: all of it).  In factor mode the touched rows are exported first and, with a
+    factor-ready hook, the backward runs in two phases around it."""
+    factors = ar is not None and ar.sh_factors
+    if factors:
+        # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
+        # is enqueued, so that a caller's hook can start on it -- the all-gather exchange agrees on its row capacity beside
+        # the backward instead of waiting for it (view_parallel._touched_hook)
+        _export_touched(ar, P, geomBuffer, dev)
+        if _touched_ready_hook is not None:
+            _touched_ready_hook(ar)
+    if factors and _factor_ready_hook is not None:
+        call(1)                      # blend backward + the factors
+        _factor_ready_hook(ar)       # e.g. the asynchronous all-gather of the factors
+        call(2)                      # the per-Gaussian backward, beside it
+    else:
+        call(0)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -571,14 +607,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
     instead of the calling thread's (current_options() captured at forward time); `first_backward`: no backward has touched
     geomBuffer since its forward, whose gradient records are therefore still zero (the library skips its zero-fill).
-    `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- gsrast_backward_aux when
-    either is given, else gsrast_backward_ex.  `antialiasing`: the state comes from an antialiasing=True forward (gsrast_backward_flags
-    with GSRAST_RENDER_ANTIALIAS; the same flags for both phases of a two-phase backward)."""
+    `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- GSRAST_RENDER_AUX when
+    either is given.  `antialiasing`: the state comes from an antialiasing=True forward (GSRAST_RENDER_ANTIALIAS; the same flags for
+    both phases of a two-phase backward)."""
     dev = _require_gpu(means3D)
-    L = lib()
     P = int(means3D.shape[0])
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])  # rasterize_points.cu:141-142
-    aux = _aux_grads(dL_dacc_depth, dL_dalpha, H, W, dev)
+    flags, aux, _keep = _backward_flags(dL_dacc_depth, dL_dalpha, H, W, dev, antialiasing)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, means3D, colors = f(background, "bg"), f(means3D, "means3D"), f(colors, "colors_precomp")
     scales, rotations, cov3D_precomp = f(scales, "scales"), f(rotations, "rotations"), f(cov3D_precomp, "cov3D_precomp")
@@ -588,16 +623,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     opts = dict(dtype=torch.float32, device=dev)
     use_sh = sh.numel() != 0 and colors.numel() == 0
     use_sr = cov3D_precomp.numel() == 0
-    ar = _grad_arena
-    if ar is not None and not (ar.P == P and ar.M == M and use_sh and use_sr and ar.flat.device == dev):
-        ar = None                       # the arena only serves the SH + scale/rotation training path
-    if ar is not None and ar.dirty:     # a second backward of the same step (GradArena docstring)
-        if ar.sh_factors:
-            raise RuntimeError("GradArena(sh_factors=True): a second backward before zero_grad() would overwrite the first view's "
-                               "factor; use one view per rank and exchange, or the plain arena (which accumulates)")
-        ar = None                       # ordinary tensors: autograd adds them into the arena views it adopted as .grad
-    if ar is not None:
-        ar.dirty = True
+    # (the arena only serves the SH + scale/rotation training path)
+    ar = _claim_grad_arena(lambda a: a.P == P and a.M == M and use_sh and use_sr and a.flat.device == dev, P, campos, degree)
 
     def out(name, shape, zero):
         if ar is not None and name in ar.offsets:
@@ -617,67 +644,42 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     # cov3D_precomp input): not computed, not written -- the binding returns an empty tensor in its place
     dL_dcov3D = torch.empty((0, 6) if use_sr else (P, 6), **opts)
     dL_dsh = out("sh", (P, M, 3), not use_sh)
-    factors = ar is not None and ar.sh_factors
-    if factors:
-        # dL_dsh (a view of the arena) is returned to autograd as usual but only becomes valid after
-        # sh_grad_combine(); the kernel writes this view's factor g[P,3] (+ the camera position behind it)
-        ar.factor[3 * P: 3 * P + 3].copy_(campos.reshape(-1)[:3])
-        ar.last_degree = int(degree)
+    factors = ar is not None and ar.sh_factors      # dL_dsh is then only valid after sh_grad_combine(): the kernel writes this view's factor
     dL_dscales = out("scales", (P, 3), not use_sr)
     dL_drotations = out("rotations", (P, 4), not use_sr)
     if P != 0:
         with _on_device(dev):
-            stream = _stream_of(dev)
-            sh_out = ar.factor.data_ptr() if factors else _ptr(dL_dsh)
             radii_c = radii.contiguous()
+            args = (P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
+                    _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
+                    _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii_c),
+                    _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL_dout_color),
+                    dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
+                    dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscales.data_ptr(),
+                    dL_drotations.data_ptr(), _stream_of(dev))
 
             def call(phase):      # options travel per call: no process-wide switch is flipped
-                args = (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),
-                        P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                        _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
-                        _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii_c),
-                        _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL_dout_color),
-                        dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
-                        dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), sh_out, dL_dscales.data_ptr(),
-                        dL_drotations.data_ptr(), stream)
-                if antialiasing:
-                    flags = RENDER_ANTIALIAS | (RENDER_AUX if aux is not None else 0)
-                    return L.gsrast_backward_flags(args[0], flags, *args[1:], *((_ptr(aux[0]), _ptr(aux[1])) if aux is not None else (None, None)))
-                if aux is not None:
-                    return L.gsrast_backward_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
-                return L.gsrast_backward_ex(*args)
+                _render_call("backward", (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),),
+                             args, flags, aux)
 
-            if factors:
-                # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
-                # is enqueued, so that a caller's hook can start on it -- the all-gather exchange agrees on its row capacity beside
-                # the backward instead of waiting for it (view_parallel._touched_hook)
-                _export_touched(ar, P, geomBuffer, dev)
-                if _touched_ready_hook is not None:
-                    _touched_ready_hook(ar)
-            if factors and _factor_ready_hook is not None:
-                rc = call(1)                     # blend backward + the factors
-                if rc == 0:
-                    _factor_ready_hook(ar)       # e.g. the asynchronous all-gather of the factors
-                    rc = call(2)                 # the per-Gaussian backward, beside it
-            else:
-                rc = call(0)
-        if rc != 0:
-            raise _err(rc, "gsrast_backward_flags" if antialiasing else "gsrast_backward_aux" if aux is not None else "gsrast_backward")
+            _run_backward(ar, call, P, geomBuffer, dev)
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
-def _aux_grads(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device):
-    """(dL/dacc_depth, dL/dalpha) as contiguous fp32 [1,H,W] device tensors or None each; None for the pair when both are absent."""
+def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, antialiasing: bool):
+    """A backward's (flags, (dL/dacc_depth, dL/dalpha) pointers, the tensors they point into): each gradient a contiguous fp32 [1,H,W]
+    device tensor or None = zero; GSRAST_RENDER_AUX when either is given."""
+    flags = RENDER_ANTIALIAS if antialiasing else 0
     if dL_dacc_depth is None and dL_dalpha is None:
-        return None
-    out = []
+        return flags, (None, None), ()
+    keep = []
     for t, n in ((dL_dacc_depth, "dL_dacc_depth"), (dL_dalpha, "dL_dalpha")):
         if t is not None:
             if t.numel() != H * W:
                 raise RuntimeError(f"{n} must hold one value per pixel ([1,{H},{W}])")
             t = _dev_f32(t, n, dev)
-        out.append(t)
-    return tuple(out)
+        keep.append(t)
+    return flags | RENDER_AUX, (_ptr(keep[0]), _ptr(keep[1])), keep
 
 
 # ---- raw-parameter entry points (include/gsrast.h: gsrast_forward_raw / gsrast_backward_raw; no counterpart in the reference's _C) ----
@@ -716,35 +718,13 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
     of scene/saro_gaussian.py:39-47, :807-847 run inside the per-Gaussian kernels.  Same return tuple (`aux`: + acc_depth, alpha;
     `antialiasing`: as rasterize_gaussians)."""
     dev = _require_gpu(raw["xyz"])
-    L = lib()
     P, H, W = int(raw["xyz"].shape[0]), int(image_height), int(image_width)
     st, keep, M = _raw_struct(raw, dev, P)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, viewmatrix, projmatrix, campos = f(background, "bg"), f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(campos, "campos")
-    out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
-    out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-    radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    aux_out = (torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev)) if aux else ()
-    arena = _Arena.acquire(dev)
-    try:
-        with _on_device(dev):
-            args = (_current_context(), C.byref(_options_struct(forward_only=forward_only)),
-                    *arena.forward_allocators(P, W, H),
-                    P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                    float(tan_fovx), float(tan_fovy), out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii),
-                    _stream_of(dev))
-            if antialiasing:
-                flags = RENDER_ANTIALIAS | (RENDER_AUX if aux else 0)
-                rendered = L.gsrast_forward_raw_flags(args[0], args[1], flags, *args[2:], *((aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None)))
-            elif aux:
-                rendered = L.gsrast_forward_raw_aux(*args, aux_out[0].data_ptr(), aux_out[1].data_ptr())
-            else:
-                rendered = L.gsrast_forward_raw(*args)
-        if rendered < 0:
-            raise _err(rendered, "gsrast_forward_raw_flags" if antialiasing else "gsrast_forward_raw_aux" if aux else "gsrast_forward_raw")
-        return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
-    finally:
-        arena.close()
+    inputs = (P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+              float(tan_fovx), float(tan_fovy))
+    return _forward("forward_raw", dev, P, H, W, inputs, forward_only, aux, antialiasing)
 
 
 def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
@@ -753,31 +733,22 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                                      dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
-    rasterize_gaussians_backward (gsrast_backward_raw_aux when either is given); `antialiasing`: as rasterize_gaussians_backward."""
+    rasterize_gaussians_backward; `antialiasing`: as rasterize_gaussians_backward."""
     dev = _require_gpu(raw["xyz"])
-    L = lib()
     P = int(raw["xyz"].shape[0])
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])
     st, keep, M = _raw_struct(raw, dev, P)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, viewmatrix, projmatrix, campos = f(background, "bg"), f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(campos, "campos")
     dL_dout_color = f(dL_dout_color, "dL_dout_color")
-    aux = _aux_grads(dL_dacc_depth, dL_dalpha, H, W, dev)
+    flags, aux, _keep = _backward_flags(dL_dacc_depth, dL_dalpha, H, W, dev, antialiasing)
     o = dict(dtype=torch.float32, device=dev)
-    ar = _grad_arena
-    if ar is not None and not (getattr(ar, "raw", False) and ar.P == P and ar.M == M and ar.flat.device == dev):
-        ar = None                       # (the bucket of another call shape)
-    if ar is not None and ar.dirty:     # a second backward of the same step (GradArena docstring)
-        if ar.sh_factors:
-            raise RuntimeError("GradArena(sh_factors=True): a second backward before zero_grad() would overwrite the first view's "
-                               "factor; use one view per rank and exchange, or the plain arena (which accumulates)")
-        ar = None
+    ar = _claim_grad_arena(      # (else: the bucket of another call shape)
+        lambda a: getattr(a, "raw", False) and a.P == P and a.M == M and a.flat.device == dev, P, campos, degree,
+        no_factors=None if keep["shs_res"] is None else
+        "GradArena(raw=True, sh_factors=True) cannot serve a call with shs_residual: every rank needs the whole "
+        "gradient of its own residual; use GradArena(raw=True) + view_parallel.allreduce_mean_inplace")
     factors = ar is not None and ar.sh_factors
-    if factors and keep["shs_res"] is not None:
-        raise RuntimeError("GradArena(raw=True, sh_factors=True) cannot serve a call with shs_residual: every rank needs the whole "
-                           "gradient of its own residual; use GradArena(raw=True) + view_parallel.allreduce_mean_inplace")
-    if ar is not None:
-        ar.dirty = True
 
     def out(name, shape):
         return ar.take(name, shape, False) if ar is not None else torch.empty(shape, **o)
@@ -795,47 +766,25 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
     g["features_dc"], g["features_rest"] = out("features_dc", (P, 1, 3)), out("features_rest", (P, M - 1, 3))
     p_dc, p_rest = g["features_dc"].data_ptr(), _ptr(g["features_rest"])
     p_fac = None
-    if factors:
-        # the two SH leaves' gradients (views of the bucket) are returned to autograd as usual but only become valid after
-        # sh_grad_combine(); the kernel writes this view's factor g[P,3], the camera position goes behind it
-        ar.factor[3 * P: 3 * P + 3].copy_(campos.reshape(-1)[:3])
-        ar.last_degree = int(degree)
+    if factors:     # the two SH leaves' gradients are then only valid after sh_grad_combine(): the kernel writes this view's factor
         p_dc, p_rest, p_fac = None, None, ar.factor.data_ptr()
     gs = RawGradsStruct(dL_dmean2D=g["dL_dmeans2D"].data_ptr(), d_xyz=g["xyz"].data_ptr(), d_rotation=g["rotation"].data_ptr(),
                         d_scaling=g["scaling"].data_ptr(), d_rot_res=_ptr(g.get("rot_res")), d_opacity_logit=g["opacity_logit"].data_ptr(),
                         d_trbf=_ptr(g.get("trbf")), d_features_dc=p_dc, d_features_rest=p_rest, d_shs_res=_ptr(g.get("shs_res")),
                         d_sh_factor=p_fac)
     if P != 0:
-        radii_c = radii.contiguous()
         with _on_device(dev):
-            def call(phase):
-                args = (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)), P, int(degree), M, int(R),
-                        _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                        float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
-                        _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
-                if antialiasing:
-                    flags = RENDER_ANTIALIAS | (RENDER_AUX if aux is not None else 0)
-                    return L.gsrast_backward_raw_flags(args[0], flags, *args[1:], *((_ptr(aux[0]), _ptr(aux[1])) if aux is not None else (None, None)))
-                if aux is not None:
-                    return L.gsrast_backward_raw_aux(*args, _ptr(aux[0]), _ptr(aux[1]))
-                return L.gsrast_backward_raw(*args)
+            radii_c = radii.contiguous()
+            args = (P, int(degree), M, int(R),
+                    _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                    float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                    _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
 
-            if factors:
-                # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
-                # is enqueued, so that a caller's hook can start on it -- the all-gather exchange agrees on its row capacity beside
-                # the backward instead of waiting for it (view_parallel._touched_hook)
-                _export_touched(ar, P, geomBuffer, dev)
-                if _touched_ready_hook is not None:
-                    _touched_ready_hook(ar)
-            if factors and _factor_ready_hook is not None:
-                rc = call(1)                     # blend backward + the factors
-                if rc == 0:
-                    _factor_ready_hook(ar)       # e.g. the asynchronous all-gather of the factors
-                    rc = call(2)                 # the per-Gaussian backward, beside it
-            else:
-                rc = call(0)
-        if rc != 0:
-            raise _err(rc, "gsrast_backward_raw_flags" if antialiasing else "gsrast_backward_raw_aux" if aux is not None else "gsrast_backward_raw")
+            def call(phase):
+                _render_call("backward_raw", (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)),),
+                             args, flags, aux)
+
+            _run_backward(ar, call, P, geomBuffer, dev)
     if keep["motion_res"] is not None:
         g["motion_res"] = g["xyz"]
     return g

@@ -59,13 +59,23 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool
 
 
+def _no_arena_for_aux():
+    if _C._grad_arena is not None:
+        raise RuntimeError("return_aux=True is not supported with a GradArena installed (multi-GPU / view_parallel training): "
+                           "uninstall it with _C.set_grad_arena(None) for renders that need acc_depth / alpha")
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Opaque-state autograd node: forward saves the three state buffers the native library
-    filled, backward hands them back (REF:42-132)."""
+    filled, backward hands them back (REF:42-132).  AUX (the subclass below): two more outputs, two more incoming gradients."""
+    AUX = False
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, antialiasing):
+        aux = ctx._forward_cls.AUX      # (of the class .apply was called on)
+        if aux:
+            _no_arena_for_aux()
         rs = raster_settings
         ar = _C._grad_arena
         if ar is not None and ar.sh_factors and sh.numel() != 0 and sh.requires_grad and not sh.is_leaf:
@@ -74,10 +84,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise RuntimeError("GradArena(sh_factors=True) needs the rasterizer's `shs` to be a leaf tensor; for "
                                "cat(features_dc, features_rest) or shs + residual use GradArena(sh_factors=False) + "
                                "view_parallel.allreduce_mean_inplace")
-        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth = _C.rasterize_gaussians(
+        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = _C.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), antialiasing=antialiasing)
+            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=aux, antialiasing=antialiasing)
         ctx.raster_settings = rs
         ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
         ctx.num_rendered = num_rendered
@@ -92,21 +102,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         # non-differentiable, which raised instead).  radii is int32: never differentiable.
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)     # no zero-filled [1,H,W] / [P] gradients for the two outputs nothing flows through
-        return color, radii, depth
+        return (color, radii, depth, *aux_out)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_depth):
+    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, *grad_aux):
+        grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
         rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
          geom_buf, bin_buf, img_buf) = ctx.saved_tensors
-        if grad_out_color is None:      # a loss that reaches this node through depth only: the reference sees a zero colour gradient (REF:88)
+        if grad_out_color is None:      # a loss that reaches this node through depth (or the aux outputs) only: the reference sees a zero colour gradient (REF:88)
             grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=means3D.device)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
          grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
             geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            antialiasing=ctx.antialiasing)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         # one gradient per forward input, in input order; absent optionals get None
         def opt(g, x):
@@ -116,57 +127,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
 
 
-def _no_arena_for_aux():
-    if _C._grad_arena is not None:
-        raise RuntimeError("return_aux=True is not supported with a GradArena installed (multi-GPU / view_parallel training): "
-                           "uninstall it with _C.set_grad_arena(None) for renders that need acc_depth / alpha")
-
-
 class _RasterizeGaussiansAux(_RasterizeGaussians):
-    """_RasterizeGaussians with the two aux outputs (gsrast_forward_aux / gsrast_backward_aux): returns
-    (color, radii, depth, acc_depth, alpha)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, antialiasing):
-        _no_arena_for_aux()
-        rs = raster_settings
-        (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians(
-            rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=True, antialiasing=antialiasing)
-        ctx.raster_settings = rs
-        ctx.antialiasing = bool(antialiasing)
-        ctx.num_rendered = num_rendered
-        ctx.gs_options = _C.current_options()
-        ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))
-        ctx.gs_backwards = 0
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-                              geom_buf, bin_buf, img_buf)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, acc_depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, grad_acc_depth, grad_alpha):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-         geom_buf, bin_buf, img_buf) = ctx.saved_tensors
-        if grad_out_color is None:      # a loss built from the aux outputs (or the median depth) alone
-            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=means3D.device)
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
-            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
-            geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha,      # (None = zero; both None: the plain backward)
-            antialiasing=ctx.antialiasing)
-        ctx.gs_backwards += 1
-        def opt(g, x):
-            return g if x.numel() != 0 else None
-        return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
-                grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
+    """_RasterizeGaussians with the two aux outputs: returns (color, radii, depth, acc_depth, alpha)."""
+    AUX = True
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -236,16 +199,21 @@ class GaussianRasterizer(nn.Module):
 # ---- raw-parameter module (no counterpart in the reference: SURVEY.md 8f rank 3 as written -- the activation / deformation epilogue
 # of scene/saro_gaussian.py:807-847 fused into the per-Gaussian kernels) -------------------------------------------------------------
 class _RasterizeGaussiansRaw(torch.autograd.Function):
-    """Inputs in _C.RAW_NAMES order (absent residuals: None) + means2D (the gradient sink of REF:42) + the settings + antialiasing."""
+    """Inputs in _C.RAW_NAMES order (absent residuals: None) + means2D (the gradient sink of REF:42) + the settings + antialiasing.
+    AUX: as _RasterizeGaussians."""
+    AUX = False
 
     @staticmethod
     def forward(ctx, means2D, raster_settings, antialiasing, *raw_tensors):
+        aux = ctx._forward_cls.AUX
+        if aux:
+            _no_arena_for_aux()
         rs = raster_settings
         raw = dict(zip(_C.RAW_NAMES, raw_tensors))
         forward_only = not any(ctx.needs_input_grad)
-        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth = _C.rasterize_gaussians_raw(
+        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = _C.rasterize_gaussians_raw(
             rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-            rs.sh_degree, rs.campos, forward_only=forward_only, antialiasing=antialiasing)
+            rs.sh_degree, rs.campos, forward_only=forward_only, aux=aux, antialiasing=antialiasing)
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
         ctx.antialiasing = bool(antialiasing)
         ctx.gs_options = _C.current_options()
@@ -255,10 +223,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.save_for_backward(*[t for t in raw_tensors if t is not None], radii, geom_buf, bin_buf, img_buf)
         ctx.mark_non_differentiable(radii)      # (depth: as _RasterizeGaussians -- differentiable in name, its gradient ignored)
         ctx.set_materialize_grads(False)
-        return color, radii, depth
+        return (color, radii, depth, *aux_out)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_depth):
+    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, *grad_aux):
+        grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
         rs = ctx.raster_settings
         saved = list(ctx.saved_tensors)
         img_buf, bin_buf, geom_buf, radii = saved.pop(), saved.pop(), saved.pop(), saved.pop()
@@ -269,7 +238,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
             rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            antialiasing=ctx.antialiasing)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing)
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
@@ -277,46 +246,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
 
 class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
-    """_RasterizeGaussiansRaw with the two aux outputs (gsrast_forward_raw_aux / gsrast_backward_raw_aux)."""
-
-    @staticmethod
-    def forward(ctx, means2D, raster_settings, antialiasing, *raw_tensors):
-        _no_arena_for_aux()
-        rs = raster_settings
-        raw = dict(zip(_C.RAW_NAMES, raw_tensors))
-        forward_only = not any(ctx.needs_input_grad)
-        (num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, acc_depth, alpha) = _C.rasterize_gaussians_raw(
-            rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-            rs.sh_degree, rs.campos, forward_only=forward_only, aux=True, antialiasing=antialiasing)
-        ctx.raster_settings, ctx.num_rendered = rs, num_rendered
-        ctx.antialiasing = bool(antialiasing)
-        ctx.gs_options = _C.current_options()
-        ctx.gs_options["forward_only"] = int(forward_only)
-        ctx.gs_backwards = 0
-        ctx.present = tuple(t is not None for t in raw_tensors)
-        ctx.save_for_backward(*[t for t in raw_tensors if t is not None], radii, geom_buf, bin_buf, img_buf)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, acc_depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_depth, grad_acc_depth, grad_alpha):
-        rs = ctx.raster_settings
-        saved = list(ctx.saved_tensors)
-        img_buf, bin_buf, geom_buf, radii = saved.pop(), saved.pop(), saved.pop(), saved.pop()
-        it = iter(saved)
-        raw = {n: (next(it) if here else None) for n, here in zip(_C.RAW_NAMES, ctx.present)}
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=radii.device)
-        g = _C.rasterize_gaussians_raw_backward(
-            rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
-            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha,      # (None = zero; both None: the plain backward)
-            antialiasing=ctx.antialiasing)
-        ctx.gs_backwards += 1
-        shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
-        grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None, None) + grads
+    """_RasterizeGaussiansRaw with the two aux outputs."""
+    AUX = True
 
 
 class GaussianRasterizerRaw(nn.Module):

@@ -97,6 +97,69 @@ def test_flags_entry_points_refuse_bad_arguments_before_any_device_work(L, rast)
     L.gsrast_options_init(C.byref(opts))
 
 
+def test_every_render_symbol_is_an_adapter_over_one_path(L, rast):
+    """The same bad argument through every symbol of a family that can express it: the same return code and the same
+    gsrast_last_error() text, forward and backward, dense (_ex, _aux, _flags) and raw (_raw, _raw_aux, _raw_flags).  All of these return
+    before any device work (the allocators would fail: a refusal that got that far would say "allocation")."""
+    _C = rast._C
+    cb = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)(lambda ctx, n: None)
+    one = C.c_void_p(16)
+    AUX = _C.RENDER_AUX
+    opts = _C.OptionsStruct()
+    o = C.byref(opts)
+    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
+    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
+    body = {      # the arguments between the options (+ flags) and the aux pair, as a function of P
+        "forward": lambda P: (cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one, None, one, one, one,
+                              0.5, 0.5, 0, one, one, one, None),
+        "backward": lambda P: (P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one, one, one, one,
+                               one, one, None, one, None, one, None, one, one, one, None),
+        "forward_raw": lambda P: (cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0,
+                                  one, one, one, None),
+        "backward_raw": lambda P: (P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one,
+                                   C.byref(gr), None),
+    }
+
+    def outcomes(family, P, flags, a, b):
+        """(symbol, return code, error text) of every symbol of the family that can express (flags, aux pair)."""
+        head = (None, o) if family.startswith("forward") else (o,)
+        plain = "gsrast_" + family + ("" if family.endswith("raw") else "_ex")
+        calls = [("gsrast_" + family + "_flags", head + (flags,) + body[family](P) + (a, b))]
+        if flags == AUX:
+            calls.append(("gsrast_" + family + "_aux", head + body[family](P) + (a, b)))
+        if flags == 0:
+            calls.append((plain, head + body[family](P)))
+        out = []
+        for name, args in calls:
+            rc = getattr(L, name)(*args)
+            out.append((name, rc, L.gsrast_last_error()))
+        return out
+
+    def same(results, n_symbols, needle):
+        assert len(results) == n_symbols, results
+        assert {r[1] for r in results} == {-1}, results
+        assert len({r[2] for r in results}) == 1, results
+        assert needle in results[0][2], results
+
+    for family in ("forward", "backward", "forward_raw", "backward_raw"):
+        L.gsrast_options_init(o)
+        # P = -1: through all three (plain and _flags with flags = 0, _aux and _flags with AUX)
+        sizes = b"bad P" if family.startswith("forward") else b"bad sizes"
+        plain = outcomes(family, -1, 0, None, None)
+        auxed = outcomes(family, -1, AUX, one, one)
+        same(plain + auxed, 4, sizes)
+        # an unknown flag bit: _flags alone can express it
+        same(outcomes(family, 10, 0x4, one, one), 1, b"unknown bits")
+        # forward, AUX with a NULL aux output: _aux and _flags
+        if family.startswith("forward"):
+            for a, b in ((None, one), (one, None), (None, None)):
+                same(outcomes(family, 10, AUX, a, b), 2, b"NULL acc_depth / alpha")
+        # AUX with cull = 0: _aux and _flags
+        opts.cull = 0
+        same(outcomes(family, 10, AUX, one, one), 2, b"cull")
+    L.gsrast_options_init(o)
+
+
 def test_antialiasing_is_keyword_only_and_false_by_default_on_every_surface(rast):
     # functional form: a plain keyword-only parameter
     p = inspect.signature(rast.rasterize_gaussians).parameters["antialiasing"]
