@@ -380,15 +380,11 @@ int gsrast_backward_aux(const gsrast_options* options,
  * "chain_gate" (process-wide A/B switch) 1 (default) = the list cut's completion pass (no_list_cut above) is enqueued on the context's
  * second stream and the caller's stream is released by the cut forward's blend itself (hipStreamWaitValue32 on a word of the
  * context's own), 0 = its predicated launches on the caller's stream (also chosen by itself when the process runs under a counter-collecting
- * profiler -- ROCPROF_COUNTERS / ROCPROF_COUNTER_GROUPS in the environment: such a profiler serialises kernels, a stream that waits for another deadlocks);  "layer_cut" 1 = a pose without remembered cut depths lists
- * the nearest eighth of the Gaussians first (measured slower: default 0);  "list_cut_always" 1 = the cut also where it does not pay;
- * "near_pose" r (default 0 = off; 3 in round 4): a camera pose the context's table does not know takes the launch order and the cut depths of a
- * NEAR pose's slot (a camera path's previous frame), the cut depths widened over (2 r + 1)^2 tiles -- verified like any cut.  Off since such a
- * pose gets predicted cut depths ("tau_cut"), which measured faster along a camera path.
+ * profiler -- ROCPROF_COUNTERS / ROCPROF_COUNTER_GROUPS in the environment: such a profiler serialises kernels, a stream that waits for another deadlocks);
+ * "list_cut_always" 1 = the cut also where it does not pay;
  * Round 5 (process-wide A/B switches, default 1): "tau_cut" = cut depths PREDICTED from the call's own opacity mass for a pose without remembered
  * ones;  "touch_bits" = the forward blend keeps one "no pixel consumed it" bit per Gaussian for the backward;  "sparse_grec" = such a forward
  * zeroes only the consumed Gaussians' gradient records instead of all P (the backward takes every other record for zero);
- * "word_fork" = the side stream is forked by the next kernel's own start (a stored word, hipStreamWaitValue32) instead of an event where a kernel can do that;
  * "late_fill_min_p" (default 750000): scenes of at least that many Gaussians write the untouched Gaussians' zero rows beside the blend backward.
  * Read-only through gsrast_get_option: "last_instances" (num_rendered) and "last_runs" (column runs) of the
  * last forward call of the CALLING THREAD's context, "redo_count" (= gsrast_context_query(NULL, name)). */

@@ -446,7 +446,7 @@ tau_cut_kernel(const uint32_t* __restrict__ tau_hist /* [TAU_COPIES][ntiles][TAU
                uint32_t* __restrict__ zcut_used /* [ntiles] out */, int coarse_range /* 1: the depth histogram has no learned range (a context's first forward): no prediction */)
 {
     __shared__ int s_bin[TAU_BLK][TAU_BLK];
-    const bool known = hint_sel && hint_sel[1] != 0u;      // (1: the pose's own slot, 2: a near pose's, widened -- both tighter than a prediction)
+    const bool known = hint_sel && hint_sel[1] != 0u;      // (the pose's own slot: tighter than a prediction)
     if (known && !force) return;                                   // (uniform) the remembered cut depths are already in zcut_used
     const int lx = (int)(threadIdx.x % (unsigned)TAU_BLK), ly = (int)(threadIdx.x / (unsigned)TAU_BLK);
     const int tx = (int)blockIdx.x * TAU_TILE - 1 + lx, ty = (int)blockIdx.y * TAU_TILE - 1 + ly;
@@ -537,13 +537,7 @@ depth_bucket_scatter_kernel(const uint32_t* __restrict__ keys, const uint2* __re
                                                                                   late: no list will hold it, the colour kernel need not evaluate it */,
                             uint32_t cshift = 1 /* the cells of the cut-depth table are (1 << cshift)^2 tiles: 2 x 2 up to 1080p-class images,
                                                    4 x 4 / 8 x 8 for larger ones (at most CUT_MAX_CELLS cells) */,
-                            // LAYER mode (round 4): without remembered cut depths -- a pose the table does not know (layer_mode 1 and
-                            // hint_sel[1] == 0), or no table at all (layer_mode 2) -- every tile's cut depth is ONE depth: the key below
-                            // which the nearest `layer_frac` of the visible Gaussians lie (the bucket map's inverse).  The first pass
-                            // then lists that layer only; the completion pass behind the blend lists the rest into the tiles that did
-                            // not saturate inside it.  zcut_used (uninitialised or all "none") is filled with that key here
-                            int layer_mode = 0, const uint32_t* __restrict__ hint_sel = nullptr, float layer_frac = 0.125f,
-                            uint32_t* __restrict__ zcut_fill = nullptr, uint32_t ccap = 0 /* COARSE: slots per (coarse bucket, XCD) of the coarse slab (depth_coarse_cap) */)
+                            uint32_t ccap = 0 /* COARSE: slots per (coarse bucket, XCD) of the coarse slab (depth_coarse_cap) */)
 {
     // per-bucket counters of this workgroup, two 16-bit counters per word (a workgroup has 2048 elements): 16 KB instead of 32 -- with
     // the 4 KB of the bucket map and the 6 KB of cut depths this latency-bound kernel keeps five workgroups per compute unit
@@ -615,11 +609,9 @@ depth_bucket_scatter_kernel(const uint32_t* __restrict__ keys, const uint2* __re
             }
         }
     }
-    const bool layer = zcut_used && (layer_mode == 2 || (layer_mode == 1 && hint_sel[1] == 0u));      // (uniform)
     const uint32_t csz = 1u << cshift;
     const uint32_t gy_tiles = zcut_used ? ntiles_img / gx_tiles : 0u, cgx = (gx_tiles + csz - 1u) >> cshift, cgy = (gy_tiles + csz - 1u) >> cshift;
-    if (layer) { }
-    else if (zcut_used && cshift != 1u) {        // larger cells (images beyond the 1080p class): plain loops
+    if (zcut_used && cshift != 1u) {        // larger cells (images beyond the 1080p class): plain loops
         for (uint32_t c = threadIdx.x; c < cgx * cgy; c += 256) {
             const uint32_t cx = c % cgx, cy = c / cgx;
             uint32_t m = 0;
@@ -652,18 +644,6 @@ depth_bucket_scatter_kernel(const uint32_t* __restrict__ keys, const uint2* __re
     SCAT_T(2);          // cut cells in LDS
     const float scale = (float)nb / (float)s_C[ZH_BINS];
     if (blockIdx.x == 0 && threadIdx.x == 0) *zbins_out = s_fl[0] == 0xFFFFu ? 0xFFFFFFFFu : (s_fl[0] | (s_fl[1] << 16));
-    uint32_t kB = ZCUT_NONE;
-    if (layer) {      // the layer's far end: the key where the running sum reaches layer_frac of the samples (every lane computes the same)
-        const float u = layer_frac * (float)s_C[ZH_BINS];
-        uint32_t i = 0;
-#pragma unroll
-        for (uint32_t st = ZH_BINS / 2; st; st >>= 1) if ((float)s_C[i + st] <= u) i += st;
-        const long long k0 = zh_bin_start(i, zh_klo, zh_shift), k1 = zh_bin_start(i + 1u, zh_klo, zh_shift);
-        const float c0 = (float)s_C[i], c1 = (float)s_C[i + 1u];
-        const long long k = k0 + (long long)(fminf(fmaxf((u - c0) / (c1 - c0), 0.0f), 1.0f) * (float)(k1 - k0));
-        kB = k < 1 ? 1u : (k < (long long)ZH_KEY_TOP ? (uint32_t)k : ZH_KEY_TOP);
-        for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < ntiles_img; t += gridDim.x * 256u) zcut_fill[t] = kB;
-    }
 
     uint32_t dg[BK_ITEMS_T], lr[BK_ITEMS_T];
 #pragma unroll
@@ -733,8 +713,7 @@ depth_bucket_scatter_kernel(const uint32_t* __restrict__ keys, const uint2* __re
                 const uint32_t x0 = rc[r].x & 0xFFFFu, y0 = rc[r].x >> 16, x1 = rc[r].y & 0xFFFFu, y1 = rc[r].y >> 16;
                 const uint32_t kq = key[r] >> 16;
                 bool late = wword != 0u && (x1 - x0) * (y1 - y0) <= 64u;       // (a large rectangle is not worth the walk: early)
-                if (layer) late = late && key[r] > kB;
-                else if (late) {
+                if (late) {
                     const uint32_t cx0 = x0 >> cshift, cx1 = (x1 - 1u) >> cshift, cy0 = y0 >> cshift, cy1 = (y1 - 1u) >> cshift;
                     uint32_t m = 0;
                     if (cx1 - cx0 <= 1u && cy1 - cy0 <= 1u)                    // the usual case: four independent reads, no loop
@@ -1219,11 +1198,8 @@ emit_column_runs_kernel(int P, const uint32_t* __restrict__ order, const uint32_
                         const unsigned char* __restrict__ need2 = nullptr, int gx_tiles = 0, uint32_t* __restrict__ pass2_counts = nullptr,
                         // binrec == null (list cut: preprocess_fwd did not write the 32-byte binning records): the same numbers from the blend's
                         // records and the rectangles -- three gathers instead of two, for the few Gaussians that are listed
-                        const float4* __restrict__ rec0 = nullptr, const float4* __restrict__ rec1 = nullptr, const uint2* __restrict__ rect = nullptr,
-                        // word fork (gsrast_capi.hip: WORD FORKS): "this kernel has started", for the side stream's colour kernel
-                        uint32_t* __restrict__ fork_word = nullptr, uint32_t fork_seq = 0)
+                        const float4* __restrict__ rec0 = nullptr, const float4* __restrict__ rec1 = nullptr, const uint2* __restrict__ rect = nullptr)
 {
-    if (fork_word && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(fork_word, fork_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     if (pred && *pred == 0u) return;
     __shared__ uint32_t s_e[4][64], s_g[4][64], s_x0[4][64], s_yh[4][64];
     // per-Gaussian ellipse terms (fp64): det, 2tc, 1/c, dy_max, dx_top (b, the mean: exact in fp32);  mode 0 = keep the column, 1 = clip, 2 = empty
@@ -1498,7 +1474,7 @@ tile_ranges_from_runs_body(uint32_t column, const uint16_t* __restrict__ run_key
     work = before1 > before0 ? before1 - before0 : 0u;
     // forward launch order: the prefix this tile consumed the last time this pose was rendered, if the context knows (never more than the list)
     if (hints && hint_sel[1] && work && y < (uint32_t)gy) {
-        const uint32_t h = hint_work(hints, 0u)[(size_t)hint_sel[2] * ((uint32_t)gx * (uint32_t)gy) + y * (uint32_t)gx + x];      // ([2]: the pose's own slot, or the near pose's it borrows from)
+        const uint32_t h = hint_work(hints, 0u)[(size_t)hint_sel[0] * ((uint32_t)gx * (uint32_t)gy) + y * (uint32_t)gx + x];
         work = h < work ? (h ? h : 1u) : work;
     } else if (zcut_pred && work && y < (uint32_t)gy && zcut_pred[y * (uint32_t)gx + x] != ZCUT_NONE) {
         // Under PREDICTED cut depths nobody knows what the tile consumed last time, but a tile that got a cut is one whose pixels saturate

@@ -407,13 +407,11 @@ blend_fwd_cull_body(const uint2* __restrict__ ranges, const uint32_t* __restrict
                 }
             }
             *zslot = znew;
-            // the pose's key and camera are published HERE, not by preprocess_fwd's block 0 while that kernel's other blocks look the
-            // table up (round 4's benign race): whoever blends tile 0 writes them (scalars[HINT_PUB ...] of this call's geometry buffer)
+            // the pose's key is published HERE, not by preprocess_fwd's block 0 while that kernel's other blocks look the
+            // table up (round 4's benign race): whoever blends tile 0 writes it (scalars[HINT_PUB ...] of this call's geometry buffer)
             if (tile == 0u && hint_sel[HINT_PUB - HINT_SEL] == 1u) {
                 const uint32_t slot = hint_sel[0];
                 hints->key[slot][0] = hint_sel[HINT_PUB - HINT_SEL + 1]; hints->key[slot][1] = hint_sel[HINT_PUB - HINT_SEL + 2];
-#pragma unroll
-                for (int q = 0; q < 6; q++) hints->cam[slot][q] = __uint_as_float(hint_sel[HINT_PUB - HINT_SEL + 3 + q]);
             }
         }
         // backward launch order: this tile's work there = the deepest list entry any of its pixels consumed (a tile that is blended
@@ -1030,11 +1028,9 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                         const uint32_t* __restrict__ tile_max, const float* __restrict__ dL_dpix,
                         float* __restrict__ grec /*[P][GREC]: per-Gaussian gradient records, zero on entry*/,
                         const uint32_t* __restrict__ bucket_cnt, const uint16_t* __restrict__ bucket_list,
-                        uint32_t* __restrict__ fork_word /* or null: "this kernel has started" for a stream that waits for it (gsrast_capi.hip: WORD FORKS) */, uint32_t fork_seq,
                         const float* __restrict__ dL_dacc_depth = nullptr, const float* __restrict__ dL_dalpha = nullptr /* AUX only */)
 {
 #pragma clang fp contract(fast)
-    if (fork_word && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(fork_word, fork_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     constexpr int NT = 256, BATCH = 64, NW = 4;
     constexpr int GB = 8;            // instances per group
     // (Round 5, measured and dropped: the pair's derivative FRONT TO BACK --  dC/dalpha_i . g = T_i (c_i . g) - R_i / (1 - alpha_i), R_i = what

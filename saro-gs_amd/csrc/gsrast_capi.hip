@@ -29,7 +29,6 @@
 #include <cstdlib>
 #include <thread>
 #include <functional>
-#include <map>
 #include <cstdio>
 #include <cmath>
 #include <cstring>
@@ -48,7 +47,7 @@ using namespace gsrast;
 namespace {
 
 thread_local std::string g_err;
-std::atomic<int> g_profile{0}, g_debug_sync{0}, g_ablate{0}, g_debug_state{0}, g_list_cut_always{0}, g_chain_gate{1} /* 1: the completion pass of the list cut runs on its own stream behind a gate (ChainGate); 0: inline, eleven predicated launches on the caller's stream */, g_touch_bits{1} /* 1: the forward blend keeps GeomLayout::untouched for the backward (A/B switch) */, g_sparse_grec{1} /* 1: a forward that keeps those bits zeroes only the consumed Gaussians' gradient records (A/B switch) */, g_late_fill_min_p{750000} /* scenes of at least this many Gaussians write their zero rows beside the blend backward */, g_near_pose{0} /* r > 0: a pose the table does not know borrows a near pose's launch order and cut depths (HintTable::cam), widened over (2 r + 1)^2 tiles.  Default 3 in round 4; 0 since round 5: such a pose gets PREDICTED cut depths, which serve a camera path better (3 M, 50 new poses 1.5 degrees apart, forward only: 0.786 ms per view against 0.887 with borrowing, which left 11 of the 50 frames without a cut) */, g_layer_cut{0} /* 1: a pose without remembered cut depths lists a depth LAYER first (measured slower, see DESIGN.md: off) */,
+std::atomic<int> g_profile{0}, g_debug_sync{0}, g_ablate{0}, g_debug_state{0}, g_list_cut_always{0}, g_chain_gate{1} /* 1: the completion pass of the list cut runs on its own stream behind a gate (ChainGate); 0: inline, eleven predicated launches on the caller's stream */, g_touch_bits{1} /* 1: the forward blend keeps GeomLayout::untouched for the backward (A/B switch) */, g_sparse_grec{1} /* 1: a forward that keeps those bits zeroes only the consumed Gaussians' gradient records (A/B switch) */, g_late_fill_min_p{750000} /* scenes of at least this many Gaussians write their zero rows beside the blend backward */,
                  g_tau_sample{1} /* the predicted cut's opacity mass comes from one wave in 2^this of preprocess_fwd */, g_tau_cut{1} /* 1: a pose without (trustworthy) remembered cut depths gets PREDICTED ones from this call's own opacity mass (gsrast_common.h) */;      // process-wide diagnostics (not per-call behaviour)
 
 // Per-call behaviour lives in a gsrast_options value: the *_ex entry points take one, the reference-shaped entry points
@@ -379,14 +378,7 @@ int read_u32(const uint32_t* dev, hipStream_t s, uint32_t* out, int nwords = 1)
 // These hints (and the counts of the last call) belong to a gsrast_context: one per caller that renders a sequence of similar
 // views.  The reference-shaped entry points use a context private to the calling host thread.
 } // namespace
-// WORD FORKS (round 5).  Forking work onto the side stream with an event costs the CALLER's stream ~7 us (tools/fork_probe.hip: A; record, other stream
-// waits + kernel; B = +7.5 us against A; B -- the record is a barrier packet between A and B).  Where the caller's next kernel can say "I have
-// started" itself -- thread 0 of its first workgroup stores a sequence number into a word of the context's -- the side stream waits for that word
-// with hipStreamWaitValue32 instead (+0.0 us in the probe): everything in front of that kernel on the caller's stream has completed, which is all
-// the event said.  The wait is enqueued AFTER the kernel that releases it (submission order, as for the completion pass's gate), one word and one
-// counter per caller stream (two streams sharing a context must not release each other's waits).
-struct ForkWord { uint32_t* word = nullptr; uint32_t seq = 0; };
-struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr; bool can_wait = false; std::map<hipStream_t, ForkWord> words; };
+struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr; };
 // The list cut's completion pass OFF the critical path (round 4).  Its eleven predicated launches used to sit between the forward blend and
 // whatever the caller enqueues next: 55-80 us of dependent-launch latency in the steady state, where every one of them returns at once.
 // Now the blend's LAST workgroup (gsrast_blend.h, GateArgs) copies the blend's verdict into a word of the context's own (`pred`: the chain's predicate; the
@@ -431,7 +423,6 @@ struct gsrast_context {
     std::atomic<int> depth_short{0};  // the last forward's depth keys spanned < 2^24: the next one enqueues three sort passes, not four
     std::atomic<int> bucket_skip{0};  // > 0: a recent forward's bucket depth sort overflowed a bucket; that many forwards go straight to the radix sort
     std::atomic<int> bucket_backoff{0}, bucket_clean{0};   // length of the last such pause (doubles per overflow), bucket-sorted forwards without one since
-    bool counted_streams = false;     // this context is one of g_stream_contexts (it owns a side stream)
     SideStream side[32];              // per device: the stream the colour kernel runs on beside the sort (created on first use)
     ChainGate gate[32];               // per device: the completion pass's own stream and release words (created on first use)
     uint32_t* tau_dev[32] = {}; size_t tau_dev_words[32] = {}; bool tau_dev_dirty[32] = {};      // per device: the predicted cut's opacity-mass table [TAU_COPIES][T][TAU_BINS] (ImgLayout::tau_hist's twin), kept ZERO between
@@ -446,22 +437,6 @@ struct gsrast_context {
 namespace {
 // The context's side stream on the current device (created on first use, lowest priority: its bandwidth-heavy kernels should fill
 // the gaps the critical path leaves, not compete with it for compute units).  nullptr if it cannot be had.
-// Word forks are used only while the library's calls do not OVERLAP in time and at most two contexts own streams (PyTorch's usual shape: the
-// forward on the caller's thread, the backward on the autograd engine's thread, one after the other).  tests/test_gpu_gate.py's soak -- two threads
-// submitting concurrently, completion passes for real -- hung in 3 of 28 runs with word forks forced on (tools/soak_stress.sh; both threads stuck in
-// the forward's read-back, the device making no progress) and in 0 of 20 without them; the backward's late join alone: 0 of 14.  Every wait is
-// still submitted behind its releaser, so this is not a dependency cycle; what grows with concurrent submitters is the number of queues sitting in
-// a value wait at the same time (two gate waits + up to three side-stream waits there), and a queue that polls a word seems to keep its place
-// on the command processor -- with enough of them the queue that holds a releaser is not scheduled.  One submitter at a time keeps it at two.
-// Once two calls have been seen inside the library at the same time, or a third context has created its streams, the library forks with events for good.
-static std::atomic<int> g_calls_inside{0}, g_stream_contexts{0};
-static std::atomic<bool> g_concurrent_callers{false};
-struct CallScope { CallScope() { if (g_calls_inside.fetch_add(1) > 0) g_concurrent_callers = true; } ~CallScope() { g_calls_inside.fetch_sub(1); } };
-static bool single_host_thread()
-{
-    static const bool forced = getenv("GSRAST_FORCE_WORD_FORK") != nullptr;      // (experiments only: switches the rule off -- to reproduce the hang it avoids)
-    return forced || (!g_concurrent_callers.load(std::memory_order_relaxed) && g_stream_contexts.load(std::memory_order_relaxed) <= 2);
-}
 SideStream* side_stream_of(gsrast_context* ctx)
 {
     int device = 0;
@@ -482,23 +457,15 @@ SideStream* side_stream_of(gsrast_context* ctx)
             x = SideStream{};
             return nullptr;
         }
-        int can = 0;
-        x.can_wait = hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) == hipSuccess && can != 0;
-        if (!ctx->counted_streams) { ctx->counted_streams = true; g_stream_contexts++; }
     }
     return &x;
 }
-std::atomic<int> g_word_fork{getenv("GSRAST_WORD_FORK") ? 1 : 0};          // (GSRAST_WORD_FORK: experiments, tools/soak_stress.sh) 1: word forks where a kernel can signal its own start.  OPT-IN since round 6 (default 0: every fork is an event): the hang the
-                                          // soak test showed with them (3 of 28 runs, two concurrent submitters) was never root-caused, and what they buy is 13 us of a
-                                          // 1.1 ms step (1.2 %).  The reference's statics are callable from any number of threads (rasterizer.h:24-83); a drop-in may not
-                                          // trade that for a percent.  With the option on, the rule of single_host_thread() still applies.
 // TESTS ONLY (option "mutate"): a backward that is wrong on purpose, so that a test can show its tolerance would catch it (the
 // full-size gradient bar let an all-zero dL/dsh pass).  bit 0: the blend backward of ONE tile -- the image's centre tile -- does not see the 64
 // front-most entries of the tile's list (one staged batch dropped: the tile's range, its pixels' n_contrib and its tile_max are shifted by a
 // small kernel in front of the blend backward; every other (pixel, Gaussian) pair gets exactly what it gets without the mutation).
 // bit 1: the background term of dL/dalpha (backward.cu:531-534) is dropped (the blend backward is handed a zero background).
 std::atomic<int> g_mutate{0};
-std::atomic<int> g_binrec_cut{0} /* 1 (A/B): the 32-byte binning records are written under the list cut too */;
 std::atomic<int> g_two_level{1} /* 1: the bucket scatter as two launches, coarse + refine (gsrast_binning.h; A/B switch) */, g_two_level_min_p{2500000} /* measured (kernel times, one box): 0.3 M 16.1 us in one launch against 15.8 + 5.7 in two, 1 M 41.0 against 36.6 + 9.1, 3 M 88.2 against 60.5 + 19.9: the second launch only pays where the scattered stores dominate */;
 __global__ void mutate_drop_front_batch_kernel(uint2* ranges, uint32_t* n_contrib, uint32_t* tile_max, uint32_t tile, int W, int H, int gx)
 {
@@ -509,26 +476,6 @@ __global__ void mutate_drop_front_batch_kernel(uint2* ranges, uint32_t* n_contri
     __syncthreads();
     if (px < (uint32_t)W && py < (uint32_t)H) { const size_t pid = (size_t)W * py + px; const uint32_t c = n_contrib[pid]; n_contrib[pid] = c > drop ? c - drop : 0u; }
     if (threadIdx.x == 0) { ranges[tile] = make_uint2(r.x + drop, r.y); const uint32_t m = tile_max[tile]; tile_max[tile] = m > drop ? m - drop : 0u; }
-}
-// the caller stream's fork word and the next sequence number to signal, or {nullptr, 0}: fork with the event
-static ForkWord fork_word_next(gsrast_context* ctx, SideStream* side, hipStream_t caller)
-{
-    if (!side || !side->can_wait || !g_word_fork.load() || counter_collection_env() || !single_host_thread()) return ForkWord{};
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ForkWord& w = side->words[caller];
-    if (!w.word) {
-        if (side->words.size() > 64) { side->words.erase(caller); return ForkWord{}; }      // (a caller that creates streams without end: events for it)
-        uint32_t* p = nullptr;
-        if (hipMalloc((void**)&p, 64) != hipSuccess) { side->words.erase(caller); return ForkWord{}; }
-        if (hipMemset(p, 0, 64) != hipSuccess) { (void)hipFree(p); side->words.erase(caller); return ForkWord{}; }
-        w.word = p; w.seq = 0;
-    }
-    if (w.seq >= 0xFFFFFFF0u) {      // (the comparison is >=: start over before the counter wraps -- nothing may still be waiting on the old values)
-        if (hipStreamSynchronize(side->stream) != hipSuccess || hipStreamSynchronize(caller) != hipSuccess || hipMemset(w.word, 0, 64) != hipSuccess) return ForkWord{};
-        w.seq = 0;
-    }
-    w.seq++;
-    return w;
 }
 ChainGate* chain_gate_of(gsrast_context* ctx)
 {
@@ -679,7 +626,6 @@ struct BlendArgs {
     GateArgs gate{};                                             // forward, list cut's first pass: the completion pass's gate (ChainGate)
     uint32_t cut_margin_x4 = 6;                                  // forward: the next cut depth's margin (gsrast_context::cut_margin)
     unsigned char* untouched = nullptr;                          // forward (culling kernel): GeomLayout::untouched
-    uint32_t* fork_word = nullptr; uint32_t fork_seq = 0;        // backward (transposed kernel): the word fork's signal (SideStream)
     float *oad = nullptr, *oal = nullptr;                        // forward (culling kernel), aux: acc_depth / alpha -- non-null selects AUX
     const float *dad = nullptr, *dal = nullptr;                  // backward, aux: dL/dacc_depth / dL/dalpha (either may be null)
 };
@@ -717,8 +663,7 @@ void launch_blend_fwd(int exp_mode, bool cull, int ppl, uint32_t grid, hipStream
     });
 }
 
-// Which blend backward a call launches.  `transposed` = blend_bwd_cull_t_kernel, the kernel that signals the word fork itself: decided
-// once per call (backward_impl), for the launch, for arming the fork and for the fallback signal.
+// Which blend backward a call launches.  `transposed` = blend_bwd_cull_t_kernel.
 struct BwdBlendPick {
     int ppl; bool cull; bool transposed; bool aux; int ablate;   // ablate: 1 / 2 = blend_bwd_kernel<0, 4, ablate> (experiments), else 0
     BwdBlendPick(const gsrast_options& o, uint32_t T, bool aux_) : ppl(pick_ppl(T, true, o)), cull(o.cull != 0), aux(aux_)
@@ -743,7 +688,7 @@ void launch_blend_bwd(int exp_mode, const BwdBlendPick& k, uint32_t grid, hipStr
         if (k.transposed) pick_bool(k.aux, [&](auto aux) {
             constexpr bool AUX = decltype(aux)::value;
             blend_bwd_cull_t_kernel<MODE, AUX><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
-                                                                    bcnt, a.blist, a.fork_word, a.fork_seq, AUX ? a.dad : nullptr, AUX ? a.dal : nullptr);
+                                                                    bcnt, a.blist, AUX ? a.dad : nullptr, AUX ? a.dal : nullptr);
         });
         else if (k.cull) pick_int<4, 2, 1>(k.ppl, [&](auto lanes) {
             constexpr int PPL = decltype(lanes)::value;
@@ -779,13 +724,11 @@ void gsrast_context_destroy(gsrast_context* c)
     }
     for (uint32_t* z : c->zhist_dev) if (z) (void)hipFree(z);
     for (uint32_t* z : c->tau_dev) if (z) (void)hipFree(z);
-    if (c->counted_streams) g_stream_contexts--;
     for (SideStream& x : c->side) {
         if (x.stream) { (void)hipStreamSynchronize(x.stream); (void)hipStreamDestroy(x.stream); }
         if (x.fork) (void)hipEventDestroy(x.fork);
         if (x.join) (void)hipEventDestroy(x.join);
         if (x.join2) (void)hipEventDestroy(x.join2);
-        for (auto& kv : x.words) if (kv.second.word) (void)hipFree(kv.second.word);
     }
     delete c;
 }
@@ -868,14 +811,11 @@ int gsrast_set_option(const char* name, int value)
     if (!strcmp(name, "touch_bits")) { g_touch_bits = value ? 1 : 0; return 0; }               // 0: only the list cut's late bits serve the backward (round 4)
     if (!strcmp(name, "late_fill_min_p")) { g_late_fill_min_p = value < 0 ? 0 : value; return 0; }
     if (!strcmp(name, "sparse_grec")) { g_sparse_grec = value != 0; return 0; }
-    if (!strcmp(name, "word_fork")) { g_word_fork = value != 0; return 0; }
-    if (!strcmp(name, "near_pose")) { g_near_pose = value < 0 ? 0 : (value > 8 ? 8 : value); return 0; }                 // 0: only the pose's own slot (round 3)
+    if (!strcmp(name, "word_fork")) return value == 0 ? 0 : GSRAST_E_ARG;      // (word forks were removed, DESIGN_LOG.md; bench.py still reads the name)
     if (!strcmp(name, "tau_sample")) { g_tau_sample = value < 0 ? 0 : (value > 6 ? 6 : value); return 0; }
     if (!strcmp(name, "tau_cut")) { g_tau_cut = value ? 1 : 0; return 0; }                    // 0: only poses with remembered cut depths are cut (round 4's behaviour)
-    if (!strcmp(name, "layer_cut")) { g_layer_cut = value ? 1 : 0; return 0; }                // 0: only poses with remembered cut depths are cut (round 3's behaviour)
     if (!strcmp(name, "debug_state")) { g_debug_state = value ? 1 : 0; return 0; }   // forwards also store what only gsrast_debug_export reads (cov3D)
     if (!strcmp(name, "ablate")) { g_ablate = value; return 0; }   // experiments only
-    if (!strcmp(name, "binrec_cut")) { g_binrec_cut = value ? 1 : 0; return 0; }
     if (!strcmp(name, "two_level")) { g_two_level = value ? 1 : 0; return 0; }
     if (!strcmp(name, "two_level_min_p")) { g_two_level_min_p = value < 0 ? 0 : value; return 0; }
     if (!strcmp(name, "mutate")) { g_mutate = value; return 0; }   // tests only: a deliberately WRONG backward (see g_mutate) -- proves that a parity bar bites
@@ -914,16 +854,12 @@ int gsrast_get_option(const char* name)
     if (!strcmp(name, "touch_bits")) return g_touch_bits.load();
     if (!strcmp(name, "late_fill_min_p")) return g_late_fill_min_p.load();
     if (!strcmp(name, "sparse_grec")) return g_sparse_grec.load();
-    if (!strcmp(name, "word_fork")) return g_word_fork.load();
+    if (!strcmp(name, "word_fork")) return 0;
     if (!strcmp(name, "mutate")) return g_mutate.load();
     if (!strcmp(name, "two_level")) return g_two_level.load();
     if (!strcmp(name, "two_level_min_p")) return g_two_level_min_p.load();
-    if (!strcmp(name, "stream_contexts")) return g_stream_contexts.load();          // (diagnostics: the rule of the word forks)
-    if (!strcmp(name, "concurrent_callers")) return g_concurrent_callers.load() ? 1 : 0;
-    if (!strcmp(name, "near_pose")) return g_near_pose.load();
     if (!strcmp(name, "tau_sample")) return g_tau_sample.load();
     if (!strcmp(name, "tau_cut")) return g_tau_cut.load();
-    if (!strcmp(name, "layer_cut")) return g_layer_cut.load();
     if (!strcmp(name, "debug_state")) return g_debug_state.load();
     if (!strcmp(name, "pixels_per_lane") || !strcmp(name, "fwd_pixels_per_lane")) return g_def.fwd_ppl.load();
     if (!strcmp(name, "bwd_pixels_per_lane")) return g_def.bwd_ppl.load();
@@ -1036,7 +972,6 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
 {
     const auto t_entry = std::chrono::steady_clock::now();
     RoctxRange range_fwd(c.raw_family ? "gsrast_forward_raw" : "gsrast_forward");
-    CallScope call_scope;
     const gsrast_alloc_fn geometry_alloc = c.geometry_alloc, binning_alloc = c.binning_alloc, image_alloc = c.image_alloc;
     void *const geometry_ctx = c.geometry_ctx, *const binning_ctx = c.binning_ctx, *const image_ctx = c.image_ctx, *const stream = c.stream;
     const int P = c.P, D = c.D, M = c.M, width = c.width, height = c.height, prefiltered = c.prefiltered;
@@ -1108,14 +1043,6 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     // (SaRO-GS always passes False, renderer/__init__.py:63: the promise costs a synchronisation, nobody makes it on a hot path).
     uint32_t* prefilter_word = prefiltered ? scalars + SC_PREFILTER : nullptr;
     if (prefilter_word) GS_HIP(hipMemsetAsync(prefilter_word, 0, sizeof(uint32_t), s));
-    // near-pose borrowing (HintTable::cam): the position tolerance is relative to the camera's distance from the scene = the middle of the
-    // depth range the context has learned (0: nothing learned yet, the kernel falls back to the distance from the origin)
-    float near_scale2 = 0.0f;
-    {   const uint32_t klo = ctx->zrange.klo.load(); const int sh = ctx->zrange.shift.load();
-        if (!(klo == ZH_KLO_DEFAULT && sh == ZH_SHIFT_DEFAULT)) {
-            const uint64_t kmid = (uint64_t)klo + (((uint64_t)ZH_MID << sh) >> 1);
-            if (kmid < (uint64_t)ZH_KEY_TOP) { const uint32_t kb = (uint32_t)kmid; float z; memcpy(&z, &kb, sizeof z); if (z > 0.0f && z < 1e18f) near_scale2 = z * z; }
-        } }
     // Run-compressed binning needs one 8-bit pass over tile rows and 16-bit tile ids.
     const bool runbin = o.binning == 0 && cam.gy <= 256 && T <= 65536u;
     const bool buckets_ok = T <= BUCKET_MAX_TILES;      // launch order of the blend kernels from work buckets (u16 tile ids)
@@ -1153,23 +1080,22 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
         int device = 0;
         std::lock_guard<std::mutex> lk(ctx->mu);
         if (hints && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32)
-            for (auto& c : ctx->hints[device]) if (c.table) GS_HIP(hipMemsetAsync(c.table, 0, offsetof(HintTable, cam), s));
+            for (auto& c : ctx->hints[device]) if (c.table) GS_HIP(hipMemsetAsync(c.table, 0, sizeof(HintTable) /* everything in front of work[] */, s));
         ctx->pose_seen.clear(); ctx->Qe_hint = 0; ctx->Qe_hint_tau = 0;
     }
     const bool cut_pays = pol.pays(ctx->last_Q.load(), g_list_cut_always.load() != 0);
     const int cut_cs = cut_cell_shift((size_t)cam.gx, (size_t)cam.gy);
-    // Round 4: the cut no longer needs the pose table.  With remembered cut depths (a pose the table knows) the first pass lists what lies
-    // in front of them; WITHOUT -- a first-seen pose, the table switched off -- it lists the nearest eighth of the Gaussians (one cut
-    // depth for every tile: LAYER mode, depth_bucket_scatter_kernel), and the completion pass behind the blend lists the rest into the
-    // tiles that did not saturate inside that layer.  Either way the result is exact, and a pause (the passes did not pay) stops both.
+    // The cut does not need the pose table.  With remembered cut depths (a pose the table knows) the first pass lists what lies in front
+    // of them; WITHOUT -- a first-seen pose, the table switched off -- it lists what lies in front of PREDICTED ones (tau_cut_kernel), and
+    // the completion pass behind the blend lists the rest into the tiles that did not saturate.  Either way the result is exact, and a
+    // pause (the passes did not pay) stops both.
     const bool cut_base = runbin && buckets_ok && o.cull != 0 && o.lpt != 0 && o.fwd_pixels_per_lane == 0 && bucket_sort && o.tile_clip != 0 && !o.no_list_cut &&
                           cut_cs != 0 && o.speculative != 0 && ctx->R_hint.load() != 0 && cut_pays;
-    const bool tau_mode = g_tau_cut.load() != 0 && g_layer_cut.load() == 0;
-    const bool cut = cut_base && (hints != nullptr || g_layer_cut.load() != 0 || tau_mode);
+    const bool tau_mode = g_tau_cut.load() != 0;
+    const bool cut = cut_base && (hints != nullptr || tau_mode);
     // the 32-byte binning records (everything the run emission needs of a Gaussian in one line) are written where the emission gathers
     // EVERY visible Gaussian; under the list cut it gathers one in eight, from the blend's records, and preprocess_fwd writes 96 MB less at 3 M
-    float4* binrec_p = (cut && g_binrec_cut.load() == 0) ? nullptr : at<float4>(geom, GL.binrec);
-    const int layer_mode = !cut || g_layer_cut.load() == 0 ? 0 : (hints ? 1 : 2);
+    float4* binrec_p = cut ? nullptr : at<float4>(geom, GL.binrec);
     if (!cut && !o.no_list_cut) pol.sits_out();
     const int tau_forced = cut && tau_mode && pol.forced_prediction() ? 1 : 0;
     bool pose_expected = false;         // (see gsrast_context::pose_seen)
@@ -1242,13 +1168,9 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     // List cut: a Gaussian the bucket scatter found late is in no list -- its colour is not evaluated (3 M cube: 87 % of them).
     // Not under the diagnostic option debug_state (gsrast_debug_export shows every Gaussian's colour).
     bool cut_colors = cut && zero_in_blend && !g_debug_state.load();       // (switched off below for a pose the table does not know: everything is early)
-    // WORD FORK (see SideStream): with the run emission about to be launched, the colour kernels are not forked with an event here but
-    // enqueued behind that launch, waiting for the word the emission kernel stores when it starts (color_fork: pending until then)
-    ForkWord color_fork{};
-    auto launch_color = [&](bool emit_follows = false) -> int {
+    auto launch_color = [&]() -> int {
         if (color_launched) return GSRAST_OK;
         color_launched = true;
-        if (side && emit_follows) { color_fork = fork_word_next(ctx, side, s); if (color_fork.word) return GSRAST_OK; }
         if (side) {
             GS_HIP(hipEventRecord(side->fork, s));             // the inputs (and the buffers just handed out) are ordered on s
             GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
@@ -1261,22 +1183,6 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
                 GS_HIP(hipMemsetAsync(at<float>(geom, GL.grec), 0, (size_t)P * GREC * sizeof(float), side->stream));
                 GS_HIP(hipEventRecord(side->join2, side->stream));
             }
-        }
-        return GSRAST_OK;
-    };
-    // the pending word fork's side-stream half: `signalled` = the kernel that stores the word has been launched on s; otherwise s stores it itself
-    auto flush_color_fork = [&](bool signalled) -> int {
-        if (!color_fork.word) return GSRAST_OK;
-        const ForkWord fw = color_fork;
-        color_fork = ForkWord{};
-        if (!signalled) GS_HIP(hipStreamWriteValue32(s, fw.word, fw.seq, 0));
-        GS_HIP(hipStreamWaitValue32(side->stream, fw.word, fw.seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-        cs = side->stream;
-        { int rc = color_kernels(cs, cut_colors, nullptr); if (rc != GSRAST_OK) return rc; }
-        GS_HIP(hipEventRecord(side->join, side->stream));
-        if (!zero_in_blend) {
-            GS_HIP(hipMemsetAsync(at<float>(geom, GL.grec), 0, (size_t)P * GREC * sizeof(float), side->stream));
-            GS_HIP(hipEventRecord(side->join2, side->stream));
         }
         return GSRAST_OK;
     };
@@ -1339,7 +1245,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
             preprocess_fwd_kernel<decltype(raw_c)::value, decltype(aa_c)::value><<<pf_grid, PF_THREADS, 0, s>>>(
                 P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg,
                 tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel,
-                zcut_used, T, scalars, host_found, pre_seq, g_near_pose.load(), near_scale2, prefilter_word, untouched, tau_hist, tau_bins);
+                zcut_used, T, scalars, host_found, pre_seq, prefilter_word, untouched, tau_hist, tau_bins);
         }); });
         GS_LAUNCHED("preprocess_fwd");
         ctx->last_prologue_ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(), 0xFFFFFFFFll);
@@ -1372,8 +1278,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
                 uint32_t* gccount = at<uint32_t>(geom, GL.bk_ccount);
                 scatter<<<(P + 256 * items - 1) / (256 * items), 256, 0, s>>>(kA, rect, tiles, (uint32_t)P, zhist_call, zh_klo, zh_shift, nbk, two ? gccount : gcount, two ? cslab : slab, at<uint32_t>(geom, GL.bk_key), scalars + SC_ZBINS,
                                                                                zcut_used, T, (uint32_t)cam.gx, scalars + SC_N_LATE,
-                                                                               cut ? at<unsigned long long>(geom, GL.color_skip) : nullptr, (uint32_t)cut_cs,
-                                                                               layer_mode, hint_sel, 0.125f, zcut_used, ccap);
+                                                                               cut ? at<unsigned long long>(geom, GL.color_skip) : nullptr, (uint32_t)cut_cs, ccap);
                 GS_LAUNCHED("depth_bucket_scatter");
                 if (two) {
                     depth_bucket_refine_kernel<<<(nbk >> BK_CSHIFT) * BK_XCD, 256, 0, s>>>(cslab, gccount, nbk, gcount, slab, ccap);
@@ -1432,7 +1337,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
         if (ctx->pose_seen.size() > 4096) ctx->pose_seen.clear();
         ctx->pose_seen[viewmatrix] = pose_known ? 1 : 0;
     }
-    if (!pose_known && layer_mode == 0 && !tau_on) cut_colors = false;
+    if (!pose_known && !tau_on) cut_colors = false;
     // Everything that does not depend on num_rendered is enqueued / prepared before the host waits.
     uint2* ranges = at<uint2>(img, IL.ranges);
     // reference rasterizer_impl.cu:311 (the run-compressed path writes every tile's range itself, empty ones included)
@@ -1454,8 +1359,8 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
         if (!bin) cap = capQ = 0;
     }
     auto t1 = std::chrono::steady_clock::now();
-    // the colour kernels, beside the binning (with the speculative run emission next on s: forked by that kernel's own start, no event)
-    { int rc = launch_color(runbin && bin != nullptr && o.speculative != 0 && bucketed && totals_pending); if (rc != GSRAST_OK) return rc; }
+    // the colour kernels, beside the binning
+    { int rc = launch_color(); if (rc != GSRAST_OK) return rc; }
 
     // ---- the rest of the forward as two re-launchable pieces ----
     // run-compressed binning; nQ / capR are either exact counts (counts_dev == nullptr) or capacities with the real
@@ -1475,12 +1380,10 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
         const uint32_t* Q_dev = counts_dev ? counts_dev + 1 : nullptr;
         const int xbits = tile_bits((size_t)cam.gx);
         {   ProfScope ps(K_EMIT, s);
-            const ForkWord fw = mode != 2 ? color_fork : ForkWord{};      // (pending word fork of the colour kernels: this launch signals it)
             if (bucketed && mode == 1)
                 emit_column_runs_kernel<<<nbk + 1, 256, 0, s>>>(P, at<uint32_t>(geom, GL.bk_order_e), at<uint32_t>(geom, GL.bk_wincl_e), binrec_p, W, H,
                                                             o.tile_clip, capQ_, rkA, rvA, at<uint4>(geom, GL.bk_info_e), at<uint32_t>(geom, GL.bk_base_e), nbk, scalars,
-                                                            flag_alias, flag_seq, at<uint4>(geom, GL.bk_info), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect,
-                                                            fw.word, fw.seq);
+                                                            flag_alias, flag_seq, at<uint4>(geom, GL.bk_info), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
             else if (bucketed && mode == 2) {
                 // COMPLETION pass: only the CANDIDATES -- the Gaussians, early or late, whose rectangle touches a tile flagged by the
                 // blend -- are sorted (the buckets' non-early arrays are free) and listed, and only into flagged tiles
@@ -1500,14 +1403,11 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
                 }
                 emit_column_runs_kernel<<<nbk + 1, 256, 0, s>>>(P, at<uint32_t>(geom, GL.bk_order), at<uint32_t>(geom, GL.bk_wincl), binrec_p, W, H,
                                                             o.tile_clip, capQ_, rkA, rvA, at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base), nbk, scalars,
-                                                            flag_alias, flag_seq, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect,
-                                                            fw.word, fw.seq);
+                                                            flag_alias, flag_seq, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
             } else
                 emit_column_runs_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, order, woffsets, binrec_p, W, H,
                                                                        o.tile_clip, capQ_, rkA, rvA, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
-            GS_LAUNCHED("emit_column_runs");
-            // (signalled only by the two bucketed launches above that were handed the word)
-            if (fw.word) { int rc = flush_color_fork(bucketed); if (rc != GSRAST_OK) return rc; } }
+            GS_LAUNCHED("emit_column_runs"); }
         if (bucketed && mode != 2) totals_pending = false;
         if (after_emit) { int rc = after_emit(); if (rc != GSRAST_OK) return rc; }
         const uint32_t nblk = (nQ + RUNS_PER_BLOCK - 1) / RUNS_PER_BLOCK;
@@ -1532,7 +1432,6 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     ChainGate* gate = nullptr; uint32_t gseq = 0, *gdone = nullptr, *gpred = nullptr;
     auto launch_blend = [&](const uint32_t* plist, bool fwd_lists_built, int mode = 0 /* list cut: as launch_run_binning */) -> int {
         { int rc = launch_color(); if (rc != GSRAST_OK) return rc; }  // the other binning scheme / nothing to bin: not forked yet
-        { int rc = flush_color_fork(false); if (rc != GSRAST_OK) return rc; }      // (a word fork no emission picked up: s releases it itself)
         if (side) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); if (zero_in_blend) side_guard.joined = true; }       // the colours (rec2) are the blend's input
         ProfScope ps(K_BLEND_FWD, s);
         uint32_t grid = ((T + 7) / 8) * 8;
@@ -1612,15 +1511,12 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
         // (the early set differs from pose to pose -- 0.98 M / 1.29 M column runs at two neighbouring poses of the 3 M cube --, a launch
         // sized too small costs a whole second forward, one sized too large a few empty workgroups: half again as much as the largest of
         // the recent forwards)
-        // (LAYER mode -- an unknown pose, or no table: the nearest eighth of the Gaussians owns about a fifth of the column runs)
         if (cut) {
             // (a forward under predicted cut depths keeps two or three times the early set of one under remembered ones: each kind is sized by its own history)
             const bool predicted_call = tau_on && (tau_forced || !pose_known || !hints);
             const uint32_t qe = predicted_call ? ctx->Qe_hint_tau.load() : ctx->Qe_hint.load();
-            const bool layer_call = layer_mode == 2 || (layer_mode == 1 && !pose_known);
-            const bool early_set_expected = pose_known || layer_mode != 0 || tau_on;
-            if (layer_call) nQ1 = (qe && early_set_expected) ? (uint32_t)std::min<uint64_t>(capQ, std::max<uint64_t>((uint64_t)qe + qe / 2, (uint64_t)ctx->Q_hint.load() / 3) + 4096) : capQ;
-            else nQ1 = early_launch_runs(qe, capQ, early_set_expected);
+            const bool early_set_expected = pose_known || tau_on;
+            nQ1 = early_launch_runs(qe, capQ, early_set_expected);
         }
         int rc = launch_run_binning(bin, cap, capQ, cut ? nQ1 : capQ, cut ? scalars + SC_EARLY_COUNTS : scalars, (late && !rb_flag) ? std::function<int()>(begin_readback) : std::function<int()>(), cut ? 1 : 0);
         flag_alias = nullptr;                    // (a repeated emission below reads its counts back the ordinary way)
@@ -1741,7 +1637,6 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     if (speculative && !sort_redone) ctx->redo_count++;
     if (cut) GS_HIP(hipMemsetAsync(scalars + SC_N_LATE, 0, sizeof(uint32_t), s));      // (the backward must not take a late Gaussian's rows for zero: below it is listed)
     if (cut_colors && color_launched) {     // everything from here on lists ALL Gaussians: the colours the list cut left out are evaluated now
-        { int rc = flush_color_fork(false); if (rc != GSRAST_OK) return rc; }
         if (side) GS_HIP(hipStreamWaitEvent(s, side->join, 0));
         int rc = color_kernels(s, false, nullptr);
         if (rc != GSRAST_OK) return rc;
@@ -2341,7 +2236,6 @@ struct BwdCall {
 static int backward_impl(const gsrast_options* options, const BwdCall& c)
 {
     RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
-    CallScope call_scope;
     const int P = c.P, D = c.D, M = c.M, R = c.R, width = c.width, height = c.height;
     const float *const background = c.background, *const viewmatrix = c.viewmatrix, *const projmatrix = c.projmatrix, *const campos = c.campos;
     const float scale_modifier = c.scale_modifier, tan_fovx = c.tan_fovx, tan_fovy = c.tan_fovy;
@@ -2451,15 +2345,10 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
     // backward; preprocess_bwd then neither reads nor writes them.  Both kernels check on the device that the forward's cut was in force
     // and held.  Only where it pays for the two events (large scenes), with the sparse per-Gaussian backward, in a one-phase call.
     bool late_fill = false;
-    ForkWord late_fork{};
-    std::function<int()> launch_late_fill;
     if (do_blend && do_geom && R > 0 && !o.dense_backward && o.side_stream && (P >= g_late_fill_min_p.load() || g_list_cut_always.load() != 0)) {
         if (!side) {
             side = side_stream_of(thread_context());
-            // word fork: the blend backward below signals its own start, the side stream waits for that -- when it is the transposed kernel
-            // (the experiments' ablations keep the event fork)
-            if (side && bwd_pick.transposed && o.lpt && (aux || g_ablate.load() == 0)) late_fork = fork_word_next(thread_context(), side, s);
-            if (side && !late_fork.word) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
+            if (side) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
         }
         if (side) {
             LateRowsArgs la{}; int n = 0;
@@ -2469,8 +2358,7 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
             if (rawin) { add(rawg.d_rot_res, 7); add(rawg.d_trbf, 1); add(rawg.d_shs_res, M * 3); add(rawg.d_dc, 3); add(rawg.d_rest, M * 3 - 3); }
             else if (use_sh && !o.sh_grad_factors) add(dL_dsh, M * 3);
             la.n = n;
-            launch_late_fill = [=]() -> int {
-                if (late_fork.word) GS_HIP(hipStreamWaitValue32(side->stream, late_fork.word, late_fork.seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+            auto launch_late_fill = [&]() -> int {
                 if (g_ablate.load() != 3)      // (3, experiments only: the step without the zero rows -- what a caller with persistent outputs could save)
                 {   ProfScope ps(K_LATE_ZERO, side->stream);
                     late_rows_zero_kernel<<<GSRAST_LATE_FILL_WGS, 256, 0, side->stream>>>(P, at<unsigned long long>(geom, GL.color_skip), at<uint32_t>(geom, GL.scalars), la, at<unsigned char>(geom, GL.untouched)); }
@@ -2479,7 +2367,7 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
                 GS_HIP(hipEventRecord(side->join, side->stream));
                 return GSRAST_OK;
             };
-            if (!late_fork.word) { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }       // (word fork: behind the blend backward's launch, below)
+            { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }
             late_fill = true;
         }
     }
@@ -2493,7 +2381,6 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
         ba.ranges = ranges; ba.plist = plist; ba.W = W; ba.H = H; ba.gx = cam.gx; ba.T = T; ba.r0 = rec0; ba.r1 = rec1; ba.r2 = rec2;
         ba.bg = background; ba.fT = const_cast<float*>(fT); ba.nc = const_cast<uint32_t*>(nc); ba.tm = const_cast<uint32_t*>(tm);
         ba.dpix = dL_dpix; ba.grec = grec;
-        ba.fork_word = late_fork.word; ba.fork_seq = late_fork.seq;
         ba.dad = dL_dacc_depth; ba.dal = dL_dalpha;
         if (const int mut = g_mutate.load()) {      // tests only: see g_mutate
             if (mut & 1) {
@@ -2520,10 +2407,7 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
         }
         launch_blend_bwd(o.exp_mode, bwd_pick, grid, s, ba);
         GS_LAUNCHED("blend_bwd");
-        // (belt and braces: should anything but the signalling kernel have been launched, the caller's stream releases the side stream itself)
-        if (late_fork.word && !bwd_pick.transposed) GS_HIP(hipStreamWriteValue32(s, late_fork.word, late_fork.seq, 0));
     }
-    if (late_fork.word) { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }      // (its wait was released by the kernel just launched, or will be)
     if (do_blend && use_sh && o.sh_grad_factors) {      // dL_dsh is [P][3] in this mode: the factor, final after the blend backward
         sh_factor_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, radii, at<unsigned char>(geom, GL.clamped), reinterpret_cast<const float4*>(grec), dL_dsh, at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched));
         GS_LAUNCHED("sh_factor");

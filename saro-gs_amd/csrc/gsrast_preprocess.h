@@ -701,8 +701,6 @@ preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __r
                       uint32_t ntiles_img, uint32_t* __restrict__ cut_scalars /* or null: GeomLayout::scalars, whose `undone` counter is zeroed here */,
                       unsigned long long* __restrict__ host_found = nullptr, uint32_t host_seq = 0 /* pinned host word: {this pose was in the table, the
                                                              call's sequence number} -- the host sizes the launches over the cut lists by it */,
-                      int borrow = 0 /* r > 0: a pose the table does not know takes the estimates and cut depths of a near pose's slot (HintTable::cam), the cut depths widened over (2 r + 1)^2 tiles */,
-                      float near_scale2 = 0.0f /* (camera-to-scene distance)^2 the near-pose tolerance is relative to; 0: the camera's distance from the origin */,
                       uint32_t* __restrict__ prefilter_violation = nullptr /* or a word that is set when a Gaussian is culled although the caller said `prefiltered` (auxiliary.h:156-160) */,
                       unsigned char* __restrict__ untouched = nullptr /* or GeomLayout::untouched: every byte set here, cleared by the forward blend */,
                       uint32_t* __restrict__ tau_hist = nullptr /* or ImgLayout::tau_hist [TAU_COPIES][ntiles_img][TAU_BINS] (zeroed by a memset): the predicted cut's opacity mass */,
@@ -729,64 +727,31 @@ preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __r
         }
         h0 = (h0 ^ (uint32_t)cam_args.W) * 16777619u; h1 = (h1 + (uint32_t)cam_args.H) * 0x85EBCA6Bu;
         h0 |= 1u;                                                   // (0, 0) means "free"
-        // this camera: position, viewing direction (third row of the world-to-view rotation; the matrices are stored transposed)
-        const float cpx = cam_args.campos[0], cpy = cam_args.campos[1], cpz = cam_args.campos[2];
-        const float fwx = cam_args.view[2], fwy = cam_args.view[6], fwz = cam_args.view[10];
-        __shared__ unsigned long long s_near;
-        if (threadIdx.x == 0) s_near = 0ull;
-        __syncthreads();
         for (int k = threadIdx.x; k < HINT_SLOTS; k += blockDim.x) {        // one lane per slot
-            const bool used = (hints->key[k][0] | hints->key[k][1]) != 0u;
             if (hints->key[k][0] == h0 && hints->key[k][1] == h1) s_slot = k;
             if (blockIdx.x == 0) atomicMin(&s_lru, ((unsigned long long)hints->stamp[k] << 32) | (unsigned long long)k);      // least recently used, lowest index first (block 0 alone reads and writes the stamps)
-            if (used && borrow) {
-                // a NEAR pose (a camera path's previous frame): within 12 % of the distance to the world origin and 12 degrees of the viewing
-                // direction; the closest direction wins, the lower index on a tie.  (Lookup blocks that read a slot while block 0 rewrites
-                // it may decide differently: a tile's snapshot then comes from another slot -- only a poorer speculation, verified like any.)
-                const float* c = hints->cam[k];
-                const float dx = c[0] - cpx, dy = c[1] - cpy, dz = c[2] - cpz;
-                // (the tolerance is relative to the camera's distance from the SCENE -- the middle of the depth range this context has
-                // learned from its forwards, near_scale2 --, not from the world origin, which a scene need not be centred on; a context's
-                // first forwards have learned nothing yet and fall back to the distance from the origin)
-                const float d2 = dx * dx + dy * dy + dz * dz, r2 = near_scale2 > 0.0f ? near_scale2 : fmaxf(cpx * cpx + cpy * cpy + cpz * cpz, 1e-12f);
-                const float dot = c[3] * fwx + c[4] * fwy + c[5] * fwz;
-                if (d2 <= 0.0144f * r2 && dot >= 0.978f)
-                    atomicMax(&s_near, ((unsigned long long)__float_as_uint(dot) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)k));
-            }
         }
         __syncthreads();
-        const int near_slot = (s_slot < 0 && s_near != 0ull) ? (int)(0xFFFFFFFFu - (uint32_t)(s_near & 0xFFFFFFFFull)) : -1;
         if (threadIdx.x == 0 && blockIdx.x == 0) {
             int slot = s_slot;
             const uint32_t now = hints->clock + 1u;
-            const uint32_t found = slot >= 0 ? 1u : (near_slot >= 0 ? 2u : 0u);
-            // A pose the table does not hold takes the least recently used slot.  Its key and camera are NOT written here: this kernel's
-            // other lookup blocks are reading the table right now (round 4 left that race in as benign); they travel in the call's own
-            // scalars (HINT_PUB) and the forward blend -- a later kernel of the same stream -- publishes them with the slot's new contents.
+            const uint32_t found = slot >= 0 ? 1u : 0u;
+            // A pose the table does not hold takes the least recently used slot.  Its key is NOT written here: this kernel's
+            // other lookup blocks are reading the table right now (round 4 left that race in as benign); it travels in the call's own
+            // scalars (HINT_PUB) and the forward blend -- a later kernel of the same stream -- publishes it with the slot's new contents.
             if (slot < 0) slot = (int)(uint32_t)(s_lru & 0xFFFFFFFFull);
             hints->stamp[slot] = now; hints->clock = now;
             uint32_t* pub = hint_sel + (HINT_PUB - HINT_SEL);
             pub[0] = found == 1u ? 0u : 1u; pub[1] = h0; pub[2] = h1;
-            pub[3] = __float_as_uint(cpx); pub[4] = __float_as_uint(cpy); pub[5] = __float_as_uint(cpz);
-            pub[6] = __float_as_uint(fwx); pub[7] = __float_as_uint(fwy); pub[8] = __float_as_uint(fwz);
-            hint_sel[0] = (uint32_t)slot; hint_sel[1] = found; hint_sel[2] = found == 2u ? (uint32_t)near_slot : (uint32_t)slot;
+            hint_sel[0] = (uint32_t)slot; hint_sel[1] = found;
             if (host_found) __hip_atomic_store(host_found, ((unsigned long long)host_seq << 32) | (unsigned long long)found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (snap) {
-            const int slot = s_slot >= 0 ? s_slot : near_slot;
+            const int slot = s_slot;
             const uint32_t* zc = hint_zcut(hints, ntiles_img) + (size_t)(slot < 0 ? 0 : slot) * ntiles_img;
             const uint32_t nsb = gridDim.x < (unsigned)SNAP_BLOCKS ? gridDim.x : (unsigned)SNAP_BLOCKS;
-            // (a BORROWED slot is another camera's: what a tile sees there, a tile a few columns or rows away sees here -- the cut depth is
-            // the deepest of the (2 borrow + 1)^2 tiles around it, none if one of them has none)
-            const int rad = s_slot >= 0 ? 0 : borrow, gxt = cam_args.gx, gyt = (int)ntiles_img / cam_args.gx;
             for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < ntiles_img; t += nsb * blockDim.x) {
-                uint32_t z = slot < 0 ? ZCUT_NONE : zc[t];
-                if (slot >= 0 && rad > 0) {
-                    const int tx = (int)t % gxt, ty = (int)t / gxt;
-                    for (int y = max(ty - rad, 0); y <= min(ty + rad, gyt - 1); y++)
-                        for (int x = max(tx - rad, 0); x <= min(tx + rad, gxt - 1); x++) z = max(z, zc[y * gxt + x]);
-                }
-                zcut_used[t] = z;
+                zcut_used[t] = slot < 0 ? ZCUT_NONE : zc[t];
             }
         }
     }

@@ -36,5 +36,4 @@ torch.cuda.synchronize()
 if ts:
     import statistics
     print("per-call synchronised: median %.4f ms, min %.4f, max %.4f" % (statistics.median(ts) * 1e3, min(ts) * 1e3, max(ts) * 1e3))
-print("steady_loop P=%d poses=%d %s: %.4f ms per step (contexts with streams %d, overlapping calls seen %d)" % (P, V, " ".join(sys.argv[4:]), (time.perf_counter() - t0) * 1e3 / (N - N // 2),
-      rast._C.get_option("stream_contexts"), rast._C.get_option("concurrent_callers")))
+print("steady_loop P=%d poses=%d %s: %.4f ms per step" % (P, V, " ".join(sys.argv[4:]), (time.perf_counter() - t0) * 1e3 / (N - N // 2)))
