@@ -302,6 +302,14 @@ int gsrast_context_query(const gsrast_context* ctx, const char* name);
  *   "reset"  (a fresh policy: tests);   "tau_min" (a = the predicted cut's requirement and its floor: experiments)
  * ctx NULL = the calling thread's context. */
 int gsrast_policy_event(gsrast_context* ctx, const char* what, int a, int b, int c);
+/* The forward's host-side plan (csrc/gsrast_policy.h: ForwardPlan) WITHOUT a device: what a forward with these options, flags and shape would decide
+ * on a context whose remembered words are words[6] = { bucket_skip, R_hint, last_Q, depth_short, (1: SH coefficients) | (2: colors_precomp) | degree << 4,
+ * 1: the pose table was acquired }, under the process-wide switches in force (gsrast_set_option) and ctx's cut policy.  Returns GSRAST_E_ARG (the
+ * forward's own refusal in gsrast_last_error) or the decisions as bits: 0 run-compressed binning, 1 work buckets, 2 bucket depth sort, 3 its two-launch
+ * scatter, 4 culled blend kernel, 5 heaviest tiles first, 6 launch-order hints wanted, 7 list cut's base condition, 8 predicted-cut mode, 9 records
+ * zeroed in the blend, 10 only touched records zeroed, 11 untouched bits kept, 12 tile clip, 13 SH direction derivatives, 14 speculative launch
+ * eligible, 15 adaptive radix sort, 16 three passes assumed, 17 the cut pays, 18 the list cut is applied.  ctx NULL = the calling thread's context. */
+int gsrast_debug_forward_plan(gsrast_context* ctx, const gsrast_options* options, unsigned flags, int P, int W, int H, const int* words);
 int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
                       gsrast_alloc_fn binning_alloc, void* binning_ctx,

@@ -1,6 +1,7 @@
 // gsrast_capi.hip -- host orchestration + the C ABI declared in include/gsrast.h.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -munsafe-fp-atomics (see build.py).
 //
+// Host side of the forward: forward_impl runs the stages of one ForwardRun; what a call does is decided once, by plan_forward (gsrast_policy.h).
 // Launch plan of the default path (every launch on the caller's stream except the colour kernel):
 //   forward : preprocess_fwd (geometry; claims the pose's launch-order hint slot) -> depth_bucket_scatter -> depth_bucket_sort
 //             -> [fork: preprocess_color on the context's side stream] -> emit_column_runs (workgroup 0: totals -> pinned host memory,
@@ -28,7 +29,6 @@
 #include <chrono>
 #include <cstdlib>
 #include <thread>
-#include <functional>
 #include <cstdio>
 #include <cmath>
 #include <cstring>
@@ -36,7 +36,6 @@
 #ifndef GSRAST_LATE_FILL_WGS
 #define GSRAST_LATE_FILL_WGS 256      // workgroups of late_rows_zero_kernel beside the blend backward: as few as finish under it -- 3 M views/s with 64 / 128 / 256 / 512 / 1024 / 4096: 676 (too slow: the per-Gaussian backward waits) / 803-806 / 790-813 / 806-808 / 801-804 / 797; 2 M: 883 / 935 / 953
 #endif
-#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -64,12 +63,6 @@ gsrast_options snapshot_defaults()
     o.sh_grad_factors = g_def.sh_grad_factors; o.side_stream = g_def.side_stream; o.depth_sort = g_def.depth_sort;
     o.forward_only = g_def.forward_only; o.no_order_hint = g_def.no_order_hint; o.dense_backward = g_def.dense_backward; o.no_list_cut = g_def.no_list_cut;
     return o;
-}
-bool options_valid(const gsrast_options& o)
-{
-    auto ppl_ok = [](int v) { return v == 0 || v == 1 || v == 2 || v == 4; };
-    return o.exp_mode >= 0 && o.exp_mode <= 2 && (o.binning == 0 || o.binning == 1) && ppl_ok(o.fwd_pixels_per_lane) && ppl_ok(o.bwd_pixels_per_lane) &&
-           o.backward_phase >= 0 && o.backward_phase <= 2 && (o.depth_sort == 0 || o.depth_sort == 1) && (o.dense_backward == 0 || o.dense_backward == 1);
 }
 
 int fail(int code, const char* what, hipError_t e = hipSuccess)
@@ -631,6 +624,11 @@ struct BlendArgs {
 };
 std::atomic<int> g_sort_hint{1};          // 1: enqueue three depth-sort passes when the context's last forward had short keys (A/B switch)
 std::atomic<int> g_bwd_transposed{1};     // 1: blend_bwd_cull_t_kernel for one pixel per lane (default); 0: blend_bwd_cull_kernel<.., 1> (A/B switch)
+PlanSwitches snapshot_switches()      // one load of every A/B switch the forward's plan depends on
+{
+    return PlanSwitches{ g_list_cut_always.load() != 0, g_tau_cut.load() != 0, g_touch_bits.load() != 0, g_sparse_grec.load() != 0, g_two_level.load() != 0,
+                         g_chain_gate.load() != 0, g_sort_hint.load() != 0, g_debug_state.load() != 0, g_two_level_min_p.load(), g_tau_sample.load() };
+}
 
 // ---- kernel selection: a runtime value -> the template instantiation.  f is called with the std::integral_constant of the V that equals v
 // (of the last V if none does); a generic lambda instantiates its kernel only for the constants it is called with. ----
@@ -666,7 +664,7 @@ void launch_blend_fwd(int exp_mode, bool cull, int ppl, uint32_t grid, hipStream
 // Which blend backward a call launches.  `transposed` = blend_bwd_cull_t_kernel.
 struct BwdBlendPick {
     int ppl; bool cull; bool transposed; bool aux; int ablate;   // ablate: 1 / 2 = blend_bwd_kernel<0, 4, ablate> (experiments), else 0
-    BwdBlendPick(const gsrast_options& o, uint32_t T, bool aux_) : ppl(pick_ppl(T, true, o)), cull(o.cull != 0), aux(aux_)
+    BwdBlendPick(const gsrast_options& o, uint32_t T, bool aux_) : ppl(pick_ppl(T, true, o)), cull(culled_blend(o, true)), aux(aux_)
     {
         const int abl = g_ablate.load();
         ablate = (!aux && (abl == 1 || abl == 2)) ? abl : 0;
@@ -798,6 +796,20 @@ int gsrast_policy_event(gsrast_context* c, const char* what, int a, int b, int c
                      case 4: return pol.tau_force.load(); case 5: return pol.fb_pause.load(); default: return GSRAST_E_ARG; }
     }
     return GSRAST_E_ARG;
+}
+
+int gsrast_debug_forward_plan(gsrast_context* c, const gsrast_options* options, unsigned flags, int P, int W, int H, const int* words)
+{
+    if (!options || !words) return fail(GSRAST_E_ARG, "debug_forward_plan: NULL argument");
+    if (!c) c = thread_context();
+    ForwardPlan p = plan_forward(*options, PlanInputs{ flags, P, W, H, words[4] >> 4, (words[4] & 1) != 0, (words[4] & 2) != 0, words[0], (uint32_t)words[1], (uint32_t)words[2], words[3] != 0 }, snapshot_switches());
+    if (p.refusal) return fail(GSRAST_E_ARG, p.refusal);
+    p.policy_answer(c->pol.pays(p.last_Q, p.list_cut_always), words[5] != 0);
+    const bool bits[] = { p.runbin, p.buckets_ok, p.bucket_sort, p.two_level, p.culled, p.ordered, p.want_hints, p.cut_base, p.tau_mode, p.zero_in_blend, p.zero_touched,
+                          p.keep_untouched, p.clip, p.want_shd, p.spec_eligible, p.adaptive_sort, p.assume_short, p.cut_pays, p.cut };
+    int v = 0;
+    for (size_t k = 0; k < sizeof bits / sizeof bits[0]; k++) v |= bits[k] ? 1 << k : 0;
+    return v;
 }
 
 int gsrast_set_option(const char* name, int value)
@@ -954,7 +966,7 @@ static const char* raw_inputs_check(int P, int M, const gsrast_raw_inputs* in)
 
 // Everything a forward is called with: every exported gsrast_forward* fills one of these from its positional arguments.
 // raw_family: the call came through a gsrast_forward_raw* symbol -- `raw` replaces the dense inputs (which stay null), prefiltered is 0.
-namespace {
+extern "C++" { namespace {      // (C++ linkage: a member template lives here)
 struct FwdCall {
     gsrast_alloc_fn geometry_alloc; void* geometry_ctx; gsrast_alloc_fn binning_alloc; void* binning_ctx; gsrast_alloc_fn image_alloc; void* image_ctx;
     int P, D, M; const float* background; int width, height;
@@ -964,244 +976,203 @@ struct FwdCall {
     bool raw_family; const gsrast_raw_inputs* raw;
     unsigned flags; float *out_acc_depth, *out_alpha;      // GSRAST_RENDER_*; the aux outputs are looked at only with GSRAST_RENDER_AUX
 };
-} // namespace
 
-// The one forward.  Dense: the inputs are the activated arrays.  Raw family: means3D / opacities / scales / rotations are the model's raw
-// leaves, shs a non-null placeholder, and the per-Gaussian kernels run as their RAW instantiations.
-static int forward_impl(gsrast_context* ctx, const gsrast_options* options, const FwdCall& c)
+// ---- the two binning kernels with long argument lists: one record each, filled by name, the positional list written once ----
+struct BucketSortArgs {      // depth_bucket_sort_kernel
+    const uint4* slab; const uint32_t* gcount; uint32_t nb; const uint32_t* bkey; uint32_t *border, *bwincl; uint4* binfo; uint32_t* bwsum;
+    uint4* binfo_all = nullptr;                                                        // list cut, early-only mode: the totals over ALL Gaussians
+    const uint32_t* pred = nullptr; const unsigned long long* keep_bits = nullptr;     // completion pass: its predicate, the candidates
+    uint32_t* zero_words = nullptr; uint32_t n_zero_words = 0; uint4* zero_quads = nullptr; uint32_t n_zero_quads = 0;   // the context's tables, zeroed for its next forward
+};
+void launch_bucket_sort(hipStream_t s, const BucketSortArgs& a)
 {
-    const auto t_entry = std::chrono::steady_clock::now();
-    RoctxRange range_fwd(c.raw_family ? "gsrast_forward_raw" : "gsrast_forward");
-    const gsrast_alloc_fn geometry_alloc = c.geometry_alloc, binning_alloc = c.binning_alloc, image_alloc = c.image_alloc;
-    void *const geometry_ctx = c.geometry_ctx, *const binning_ctx = c.binning_ctx, *const image_ctx = c.image_ctx, *const stream = c.stream;
-    const int P = c.P, D = c.D, M = c.M, width = c.width, height = c.height, prefiltered = c.prefiltered;
-    const float *const background = c.background, *const colors_precomp = c.colors_precomp, *const cov3D_precomp = c.cov3D_precomp;
-    const float *const viewmatrix = c.viewmatrix, *const projmatrix = c.projmatrix, *const cam_pos = c.cam_pos;
-    const float scale_modifier = c.scale_modifier, tan_fovx = c.tan_fovx, tan_fovy = c.tan_fovy;
-    float *const out_color = c.out_color, *const out_depth = c.out_depth; int* const radii = c.radii;
-    const float *means3D = c.means3D, *shs = c.shs, *opacities = c.opacities, *scales = c.scales, *rotations = c.rotations;
-    const bool aux = (c.flags & GSRAST_RENDER_AUX) != 0;
-    const bool aa = (c.flags & GSRAST_RENDER_ANTIALIAS) != 0;      // the per-Gaussian kernel's AA instantiation
-    float *const out_acc_depth = aux ? c.out_acc_depth : nullptr, *const out_alpha = aux ? c.out_alpha : nullptr;
-    // ---- the checks every entry point shares (before any device work or allocator callback) ----
-    if (c.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return fail(GSRAST_E_ARG, "flags: unknown bits");
-    const gsrast_options o = options ? *options : snapshot_defaults();
-    if (!options_valid(o)) return fail(GSRAST_E_ARG, "forward: bad option value");
-    if (aux && (o.cull == 0 || o.fwd_pixels_per_lane != 0))
-        return fail(GSRAST_E_ARG, "forward: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)");
-    if (aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward: NULL acc_depth / alpha output");
-    const gsrast_raw_inputs* const rawin = c.raw_family ? c.raw : nullptr;
-    if (c.raw_family) {
-        if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
-        means3D = rawin->xyz; shs = rawin->features_dc /* "there are SH coefficients" */; opacities = rawin->opacity_logit; scales = rawin->scaling; rotations = rawin->rotation;
-    }
-    RawArgs raw{};
-    if (rawin) {
-        raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
-        raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
-    }
-    if (!ctx) ctx = thread_context();
-    hipStream_t s = (hipStream_t)stream;
-    const int W = width, H = height;
-    if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return fail(GSRAST_E_ARG, "forward: bad P / image size / SH degree");
-    if (!geometry_alloc || !binning_alloc || !image_alloc) return fail(GSRAST_E_ARG, "forward: NULL allocator");
-    if (!out_color || !out_depth || !background) return fail(GSRAST_E_ARG, "forward: NULL output / background");
-    const size_t N = (size_t)W * H;
-    if (P == 0) { // reference rasterize_points.cu:81 -- nothing is rendered, outputs stay zero
-        GS_HIP(hipMemsetAsync(out_color, 0, 3 * N * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(out_depth, 0, N * sizeof(float), s));
-        if (aux) { GS_HIP(hipMemsetAsync(out_acc_depth, 0, N * sizeof(float), s)); GS_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), s)); }
-        return 0;
-    }
-    if (!means3D || !opacities || !viewmatrix || !projmatrix || !radii) return fail(GSRAST_E_ARG, "forward: NULL required input");
-    if (!shs && !colors_precomp) return fail(GSRAST_E_ARG, "forward: need shs or colors_precomp");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(GSRAST_E_ARG, "forward: need scales+rotations or cov3D_precomp");
-    if (shs && !colors_precomp && (!cam_pos || M < (D + 1) * (D + 1))) return fail(GSRAST_E_ARG, "forward: SH path needs campos and M >= (D+1)^2");
+    depth_bucket_sort_kernel<<<(a.nb + BK_WAVES - 1) / BK_WAVES, 64 * BK_WAVES, 0, s>>>(a.slab, a.gcount, a.nb, a.bkey, a.border, a.bwincl, a.binfo, a.bwsum, a.binfo_all, a.pred, a.keep_bits,
+                                                                                   a.zero_words, a.n_zero_words, a.zero_quads, a.n_zero_quads);
+}
+struct EmitArgs {            // emit_column_runs_kernel
+    uint32_t grid; int P; const uint32_t *order, *woffsets; const float4* binrec; int W, H, clip; uint32_t capQ; uint16_t* run_keys; uint2* run_vals;
+    const float4 *rec0, *rec1; const uint2* rect;
+    const uint4* binfo = nullptr; const uint32_t* bwsum = nullptr; uint32_t nbuckets = 0;      // bucket depth sort: one workgroup per bucket
+    uint32_t* scalars = nullptr; uint32_t* host_out = nullptr; uint32_t host_seq = 0;           // the totals, on the device and in pinned host memory
+    const uint4* binfo_all = nullptr; const uint32_t* pred = nullptr;                           // list cut: the set over all Gaussians; the completion pass's predicate
+    uint32_t* redo_bucket_cnt = nullptr; int n_redo_cnt = 0; HintTable* redo_hints = nullptr; unsigned long long* host_fallback = nullptr; uint32_t host_fb_seq = 0;
+    const unsigned char* need2 = nullptr; int gx_tiles = 0; uint32_t* pass2_counts = nullptr;   // completion pass: the tiles listed again
+};
+void launch_emit(hipStream_t s, const EmitArgs& a)
+{
+    emit_column_runs_kernel<<<a.grid, 256, 0, s>>>(a.P, a.order, a.woffsets, a.binrec, a.W, a.H, a.clip, a.capQ, a.run_keys, a.run_vals, a.binfo, a.bwsum, a.nbuckets, a.scalars,
+                                               a.host_out, a.host_seq, a.binfo_all, a.pred, a.redo_bucket_cnt, a.n_redo_cnt, a.redo_hints, a.host_fallback, a.host_fb_seq,
+                                               a.need2, a.gx_tiles, a.pass2_counts, a.rec0, a.rec1, a.rect);
+}
+bool trace_on() { static const bool on = getenv("GSRAST_TRACE") != nullptr; return on; }
 
-    const CamArgs cam = make_cam(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, scale_modifier, W, H);
-    const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
-
-    const GeomLayout GL = geom_layout((size_t)P);
-    char* geom = (char*)geometry_alloc(geometry_ctx, GL.total);
-    if (!geom) return fail(GSRAST_E_ALLOC, "forward: geometry allocation failed");
-    const ImgLayout IL = img_layout((size_t)W, (size_t)H);
-    char* img = (char*)image_alloc(image_ctx, IL.total);
-    if (!img) return fail(GSRAST_E_ALLOC, "forward: image allocation failed");
-
-    float4* rec0 = at<float4>(geom, GL.rec0); float4* rec1 = at<float4>(geom, GL.rec1); float4* rec2 = at<float4>(geom, GL.rec2);
-    uint32_t* tiles = at<uint32_t>(geom, GL.tiles);
-    uint2* rect = at<uint2>(geom, GL.rect);
-    uint32_t *kA = at<uint32_t>(geom, GL.keyA), *kB = at<uint32_t>(geom, GL.keyB);
-    uint32_t *vA = at<uint32_t>(geom, GL.valA), *vB = at<uint32_t>(geom, GL.valB);
-    uint32_t* offsets = at<uint32_t>(geom, GL.offsets);
-    uint32_t* woffsets = at<uint32_t>(geom, GL.woffsets);
-    uint32_t* hist = at<uint32_t>(geom, GL.hist);
-    uint32_t* scan_tmp = at<uint32_t>(geom, GL.scan_tmp);
-    uint32_t* scalars = at<uint32_t>(geom, GL.scalars);
-    // `prefiltered` is the caller's promise that no Gaussian will be culled by the near plane; the reference prints and traps when one is
-    // (auxiliary.h:156-160).  Here preprocess_fwd raises a word and this call returns GSRAST_E_ARG after it has waited for the device
-    // (SaRO-GS always passes False, renderer/__init__.py:63: the promise costs a synchronisation, nobody makes it on a hot path).
-    uint32_t* prefilter_word = prefiltered ? scalars + SC_PREFILTER : nullptr;
-    if (prefilter_word) GS_HIP(hipMemsetAsync(prefilter_word, 0, sizeof(uint32_t), s));
-    // Run-compressed binning needs one 8-bit pass over tile rows and 16-bit tile ids.
-    const bool runbin = o.binning == 0 && cam.gy <= 256 && T <= 65536u;
-    const bool buckets_ok = T <= BUCKET_MAX_TILES;      // launch order of the blend kernels from work buckets (u16 tile ids)
-    // Depth order of the Gaussians: bucket sort (two launches, gsrast_binning.h) unless the caller or the context's recent history
-    // says radix sort
-    const bool bucket_sort = runbin && o.depth_sort == 0 && (size_t)P >= BUCKET_SORT_MIN_P && ctx->bucket_skip.load() == 0;
-    const uint32_t nbk = depth_buckets_host((size_t)P);
-    // equalised depth buckets: the histogram's bins (range hint of this context) and which waves of preprocess_fwd are sampled (512-1024 of them)
-    const uint32_t zh_klo = ctx->zrange.klo.load(); const int zh_shift = ctx->zrange.shift.load();
-    uint32_t zh_wave_mask = 0u;
-    while ((((size_t)P + 63) / 64) / ((size_t)zh_wave_mask + 1) > 1024) zh_wave_mask = 2u * zh_wave_mask + 1u;
-    // Colour half of the per-Gaussian forward (SH -> RGB: most of its bytes) on the context's side stream, forked off the
-    // caller's stream here and joined in front of the blend: it overlaps the geometry kernel, the depth sort and the binning.
-    SideStream* side = nullptr;
-    hipStream_t cs = s;
-    if (o.side_stream) side = side_stream_of(ctx);
-    // Where it forks matters little: its 200 MB of traffic stretches whatever latency-bound kernel runs beside it by about as much as
-    // it hides (measured: beside the geometry kernel + depth sort +55 us, beside the run emission + run sort +45 / +65 us, beside the
-    // LDS-bound run_scatter_rows it starves itself and delays the blend) -- round 2 forked it at entry, the best of those by ~20 us.
-    // Round 3 (colour kernel now 162 us alone at 3 M, geometry kernel 68): it forks behind the depth sort -- see there.
-    // The 64 B / Gaussian zero-fill of the backward's gradient records follows on the side stream, under the VALU-bound forward blend.
-    // launch-order hints of the forward blend: per context, device and camera pose (gsrast_common.h); only with the work-bucket order
-    HintTable* hints = (runbin && buckets_ok && o.cull != 0 && o.lpt != 0 && o.fwd_pixels_per_lane == 0 && !o.no_order_hint) ? hints_of(ctx, T, s) : nullptr;
-    uint32_t* hint_sel = scalars + HINT_SEL;
-    // List cut (gsrast_common.h): only with the hints, the bucket depth sort, clipped lists, and a capacity hint (the cut lists are
-    // blended by the speculative launch; the verified fallback is enqueued behind it).  Whether THIS pose has cut depths is decided on the device.
-    // It costs ~80 us per forward (the late test in the scatter, the compacting colour kernel, ten predicated launches behind the blend)
-    // and saves ~50 us per million column runs it removes: it is used when the context's last forward had at least CUT_MIN_RUNS column
-    // runs, and paused for CUT_PAUSE forwards whenever a cut forward removed fewer than that (a surface-like scene; measured
-    // 1 M-Gaussian shell -7 %, 0.3 M cube -3 %, 0.1 M cube -8 % with the cut forced on; 1 M cube +8 %, 3 M cube +16 %).
-    CutPolicy& pol = ctx->pol;          // (the decisions: gsrast_policy.h)
-    if (pol.begin_forward((uint32_t)P)) {     // (what was learned belongs to the scene it was learned on: a context that moves on to a scene of another size starts afresh)
-        // keys, stamps, clock: every slot free again, ordered in front of this call's lookup -- of EVERY image size's table of this device (round 6,
-        // the other resolutions' tables kept the old scene's cut depths, running maxima that take eight visits to fade)
-        int device = 0;
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (hints && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32)
-            for (auto& c : ctx->hints[device]) if (c.table) GS_HIP(hipMemsetAsync(c.table, 0, sizeof(HintTable) /* everything in front of work[] */, s));
-        ctx->pose_seen.clear(); ctx->Qe_hint = 0; ctx->Qe_hint_tau = 0;
-    }
-    const bool cut_pays = pol.pays(ctx->last_Q.load(), g_list_cut_always.load() != 0);
-    const int cut_cs = cut_cell_shift((size_t)cam.gx, (size_t)cam.gy);
-    // The cut does not need the pose table.  With remembered cut depths (a pose the table knows) the first pass lists what lies in front
-    // of them; WITHOUT -- a first-seen pose, the table switched off -- it lists what lies in front of PREDICTED ones (tau_cut_kernel), and
-    // the completion pass behind the blend lists the rest into the tiles that did not saturate.  Either way the result is exact, and a
-    // pause (the passes did not pay) stops both.
-    const bool cut_base = runbin && buckets_ok && o.cull != 0 && o.lpt != 0 && o.fwd_pixels_per_lane == 0 && bucket_sort && o.tile_clip != 0 && !o.no_list_cut &&
-                          cut_cs != 0 && o.speculative != 0 && ctx->R_hint.load() != 0 && cut_pays;
-    const bool tau_mode = g_tau_cut.load() != 0;
-    const bool cut = cut_base && (hints != nullptr || tau_mode);
-    // the 32-byte binning records (everything the run emission needs of a Gaussian in one line) are written where the emission gathers
-    // EVERY visible Gaussian; under the list cut it gathers one in eight, from the blend's records, and preprocess_fwd writes 96 MB less at 3 M
-    float4* binrec_p = cut ? nullptr : at<float4>(geom, GL.binrec);
-    if (!cut && !o.no_list_cut) pol.sits_out();
-    const int tau_forced = cut && tau_mode && pol.forced_prediction() ? 1 : 0;
-    bool pose_expected = false;         // (see gsrast_context::pose_seen)
-    if (cut && tau_mode && hints && !tau_forced) { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->pose_seen.find(viewmatrix); pose_expected = it != ctx->pose_seen.end() && it->second != 0; }
-    const bool tau_on = cut && tau_mode && !pose_expected;
-    uint32_t* tau_hist = tau_on ? at<uint32_t>(img, IL.tau_hist) : nullptr;
-    TauBins tau_bins{0u, 0.0f, 0.0f, (1u << g_tau_sample.load()) - 1u};      // (scale 0: the context has not learned a depth range yet -- no prediction in this call)
-    {   const uint32_t klo = ctx->zrange.klo.load(), khi = ctx->zrange.khi.load();
-        if (tau_on && khi > klo + (uint32_t)TAU_BINS) { tau_bins.lo = klo; tau_bins.scale = (float)TAU_BINS / (float)(khi - klo); tau_bins.inv_scale = (float)(khi - klo) / (float)TAU_BINS; } }
-    uint32_t* zcut_used = cut ? at<uint32_t>(img, IL.zcut_used) : nullptr;
-    // The backward's gradient records (64 B / Gaussian) are zero-filled by the forward: inside the default (culling) blend kernel; by a
-    // memset behind the colour kernel (side stream) / by the colour kernel itself (no side stream) when another blend kernel runs.
-    const bool zero_in_blend = o.cull != 0 && o.fwd_pixels_per_lane == 0 && (size_t)P * 4 <= 0xFFFFFFFFull;
-    // ... and it keeps the "no pixel consumed this Gaussian" bits for the backward (GeomLayout::untouched), unless no backward will follow
-    unsigned char* untouched = (o.cull != 0 && o.fwd_pixels_per_lane == 0 && !o.forward_only && g_touch_bits.load() != 0) ? at<unsigned char>(geom, GL.untouched) : nullptr;
-    // ... and then only the records of the Gaussians somebody consumed are zeroed, by a kernel of their own behind the last blend (gsrast_preprocess.h:
-    // grec_zero_touched_kernel) instead of all P records from inside the blend
-    const bool zero_touched = untouched != nullptr && zero_in_blend && g_sparse_grec.load() != 0;
-    auto finish_records = [&]() -> int {
-        if (!zero_touched) return GSRAST_OK;
-        ProfScope ps(K_GREC_ZERO, s);
-        grec_zero_touched_kernel<<<(unsigned)(((size_t)P + 256 * GZ_PER - 1) / (256 * GZ_PER)), 256, 0, s>>>(P, untouched, at<float4>(geom, GL.grec), scalars);
-        GS_LAUNCHED("grec_zero_touched");
-        return GSRAST_OK;
-    };
-    bool color_launched = false;
+// One forward call's state and its stages (forward_impl below is the order they run in).  Every stage that launches is told its stream
+// -- `stream` is the caller's and is never re-aimed -- and, where it has one, its predicate word.
+struct ForwardRun {
+    gsrast_context* const ctx; const FwdCall& c; const gsrast_options o; const std::chrono::steady_clock::time_point t_entry; const hipStream_t stream;
+    ForwardPlan plan;
+    const float *means3D, *shs, *opacities, *scales, *rotations;      // as the kernels see them (raw family: the model's leaves)
+    const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{};
+    float *out_acc_depth = nullptr, *out_alpha = nullptr;
+    int P = 0, W = 0, H = 0; uint32_t T = 0, nbk = 0; CamArgs cam;
+    // the three state buffers and their typed pointers, resolved once
+    GeomLayout GL; ImgLayout IL; char *geom = nullptr, *img = nullptr, *bin = nullptr; uint32_t cap = 0, capQ = 0;
+    float4 *rec0, *rec1, *rec2, *binrec, *grec; uint32_t* tiles; uint2* rect; uint32_t *kA, *kB, *vA, *vB, *offsets, *woffsets, *hist, *scan_tmp, *scalars, *hint_sel, *prefilter_word;
+    uint4 *bk_slab, *bk_info, *bk_info_e; uint32_t *bk_count, *bk_key, *bk_order, *bk_wincl, *bk_base, *bk_order_e, *bk_wincl_e, *bk_base_e;
+    unsigned long long *color_skip, *cand_bits; unsigned char *untouched = nullptr, *tile_flags; uint32_t* bucket_cnt; uint16_t* bucket_list; uint2* ranges;
+    uint32_t *zcut_used = nullptr, *tau_hist = nullptr, *zhist_call = nullptr; TauBins tau_bins{};
+    HintTable* hints = nullptr;
+    uint32_t zh_klo = 0, zh_wave_mask = 0; int zh_shift = 0;      // equalised depth buckets: the histogram's bins (range hint of this context), the sampled waves
+    bool zhist_ctx = false; int tau_ctx_device = -1;               // the depth histogram / the opacity-mass table this call fills is the context's (>= 0: on that device)
     // Every exit after the fork must order the caller's stream behind the side stream: the colour kernel and the zero-fill write
-    // into the geometry buffer, which the caller is free to release (on `s`) as soon as this function has returned -- an error
+    // into the geometry buffer, which the caller is free to release (on its stream) as soon as this function has returned -- an error
     // return (allocation failure, overflow, a failed launch) included: those drain the side stream.  The normal path enqueues the
     // two waits itself (in front of / behind the blend) and disarms the guard.
     struct SideJoinGuard {
-        SideStream*& side; hipStream_t s; bool& launched; bool joined = false;
+        SideStream* side = nullptr; bool launched = false /* the colour kernel is enqueued */, joined = false;
         ~SideJoinGuard() { if (launched && side && !joined) (void)hipStreamSynchronize(side->stream); }    // error path: cost is irrelevant
-    } side_guard{ side, s, color_launched };
-    // the colour kernel itself.  List cut: early_only = only the Gaussians the bucket scatter did not mark culled or late (the compacting
-    // kernel); pred = the predicated launch over ALL Gaussians in front of the second blend
-    auto color_kernels = [&](hipStream_t cs, bool early_only, const uint32_t* pred) -> int {
-        {
-            ProfScope ps(K_COLOR, cs);
-            // d(colour)/d(view direction) for the backward (36 B / Gaussian), unless the caller said that no backward will follow
-            const bool want_shd = shs && !colors_precomp && D > 0 && !o.forward_only;
-            float4* sA = want_shd ? at<float4>(geom, GL.shdA) : nullptr;
-            float4* sB = want_shd ? at<float4>(geom, GL.shdB) : nullptr;
-            float* sC = want_shd ? at<float>(geom, GL.shdC) : nullptr;
-            const float* sh_in = colors_precomp ? nullptr : shs;
-            unsigned char* cl = at<unsigned char>(geom, GL.clamped);
-            float4* gz = (side || zero_in_blend) ? nullptr : at<float4>(geom, GL.grec);
-            const bool staged = sh_in && M * 3 <= PP_SH_MAX && ((M * 3) & 3) == 0 && ((uintptr_t)sh_in & 15) == 0;
-            const int grid = (P + PP_THREADS - 1) / PP_THREADS;
-            if (early_only) {       // list cut: Gaussians the bucket scatter found culled or late are skipped (gsrast_preprocess.h)
-                // (with `pred`: the completion pass -- the colours of the late Gaussians that are listed after all, GeomLayout::skip2)
-                const unsigned char* skip = at<unsigned char>(geom, pred ? GL.skip2 : GL.color_skip);
-                const int cgrid = (P + PCC_IDS - 1) / PCC_IDS;
-                if (rawin) preprocess_color_compact_kernel<true><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, nullptr, nullptr, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
-                else preprocess_color_compact_kernel<false><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, sh_in, colors_precomp, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
-            } else if (rawin) {        // (gsrast_forward_raw has checked M and the alignment of the three SH arrays)
-                if (M * 3 == PP_SH_MAX) preprocess_color_kernel<PP_SH_MAX, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
-                else preprocess_color_kernel<0, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
-            } else if (staged && M * 3 == PP_SH_MAX)
-                preprocess_color_kernel<PP_SH_MAX, false><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, sh_in, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
-            else if (staged)
-                preprocess_color_kernel<0, false><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, sh_in, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
-            else
-                preprocess_color_direct_kernel<<<(P + 255) / 256, 256, 0, cs>>>(P, D, M, means3D, sh_in, colors_precomp, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(GSRAST_E_DEVICE, "preprocess_color", e);
+    } fork;
+    bool bucketed = false;          // the order in force comes from the bucket sort (per-bucket slot ranges) rather than vA
+    bool totals_pending = false;    // ... and nobody has summed the buckets' totals (R, Q, overflow verdict) into `scalars` yet
+    bool sort_redone = false;
+    // read-back handles: the pose-found word (RB_FOUND), the counts by the emission's own store (flag) or by a copy (rb)
+    Readback *rb_pre = nullptr, *rb_flag = nullptr, *rb = nullptr; uint32_t *pre_alias = nullptr, *flag_alias = nullptr; uint32_t pre_seq = 0, flag_seq = 0;
+    // the completion pass's gate (ChainGate): claimed when the cut forward's blend is launched -- its last workgroup is the gate
+    ChainGate* gate = nullptr; uint32_t gseq = 0, *gdone = nullptr, *gpred = nullptr;
+    // {instances R (low word), column runs Q, -, R (high word, run-compressed path), ..., [8] significant depth-key bits,
+    //  [9] key base, [10] "three sort passes were assumed and were not enough"}
+    uint32_t counts[12] = { 0 }; uint32_t nQ1 = 0;
+    std::chrono::steady_clock::time_point t0, t1;
+
+    ForwardRun(gsrast_context* ctx_, const gsrast_options* options, const FwdCall& c_, std::chrono::steady_clock::time_point t)
+        : ctx(ctx_ ? ctx_ : thread_context()), c(c_), o(options ? *options : snapshot_defaults()), t_entry(t), stream((hipStream_t)c_.stream),
+          means3D(c_.means3D), shs(c_.shs), opacities(c_.opacities), scales(c_.scales), rotations(c_.rotations) {}
+
+    // ---- the plan, and the checks every entry point shares (before any device work or allocator callback) ----
+    int check_and_plan(hipStream_t s)
+    {
+        P = c.P; W = c.width; H = c.height;
+        plan = plan_forward(o, PlanInputs{ c.flags, P, W, H, c.D, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr), c.colors_precomp != nullptr,
+                                           ctx->bucket_skip.load(), ctx->R_hint.load(), ctx->last_Q.load(), ctx->depth_short.load() != 0 }, snapshot_switches());
+        if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
+        if (plan.aux) { out_acc_depth = c.out_acc_depth; out_alpha = c.out_alpha; }
+        if (plan.aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward: NULL acc_depth / alpha output");
+        if (c.raw_family) {
+            rawin = c.raw;
+            if (const char* e = raw_inputs_check(P, c.M, rawin)) return fail(GSRAST_E_ARG, e);
+            means3D = rawin->xyz; shs = rawin->features_dc /* "there are SH coefficients" */; opacities = rawin->opacity_logit; scales = rawin->scaling; rotations = rawin->rotation;
+            raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
+            raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
         }
+        if (P < 0 || W <= 0 || H <= 0 || c.D < 0 || c.D > 3) return fail(GSRAST_E_ARG, "forward: bad P / image size / SH degree");
+        if (!c.geometry_alloc || !c.binning_alloc || !c.image_alloc) return fail(GSRAST_E_ARG, "forward: NULL allocator");
+        if (!c.out_color || !c.out_depth || !c.background) return fail(GSRAST_E_ARG, "forward: NULL output / background");
+        const size_t N = (size_t)W * H;
+        if (P == 0) { // reference rasterize_points.cu:81 -- nothing is rendered, outputs stay zero
+            GS_HIP(hipMemsetAsync(c.out_color, 0, 3 * N * sizeof(float), s));
+            GS_HIP(hipMemsetAsync(c.out_depth, 0, N * sizeof(float), s));
+            if (plan.aux) { GS_HIP(hipMemsetAsync(out_acc_depth, 0, N * sizeof(float), s)); GS_HIP(hipMemsetAsync(out_alpha, 0, N * sizeof(float), s)); }
+            return 0;
+        }
+        if (!means3D || !opacities || !c.viewmatrix || !c.projmatrix || !c.radii) return fail(GSRAST_E_ARG, "forward: NULL required input");
+        if (!shs && !c.colors_precomp) return fail(GSRAST_E_ARG, "forward: need shs or colors_precomp");
+        if (!c.cov3D_precomp && (!scales || !rotations)) return fail(GSRAST_E_ARG, "forward: need scales+rotations or cov3D_precomp");
+        if (shs && !c.colors_precomp && (!c.cam_pos || c.M < (c.D + 1) * (c.D + 1))) return fail(GSRAST_E_ARG, "forward: SH path needs campos and M >= (D+1)^2");
         return GSRAST_OK;
-    };
-    // List cut: a Gaussian the bucket scatter found late is in no list -- its colour is not evaluated (3 M cube: 87 % of them).
-    // Not under the diagnostic option debug_state (gsrast_debug_export shows every Gaussian's colour).
-    bool cut_colors = cut && zero_in_blend && !g_debug_state.load();       // (switched off below for a pose the table does not know: everything is early)
-    auto launch_color = [&]() -> int {
-        if (color_launched) return GSRAST_OK;
-        color_launched = true;
-        if (side) {
-            GS_HIP(hipEventRecord(side->fork, s));             // the inputs (and the buffers just handed out) are ordered on s
-            GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-            cs = side->stream;
-        }
-        { int rc = color_kernels(cs, cut_colors, nullptr); if (rc != GSRAST_OK) return rc; }
-        if (side) {
-            GS_HIP(hipEventRecord(side->join, side->stream));
-            if (!zero_in_blend) {
-                GS_HIP(hipMemsetAsync(at<float>(geom, GL.grec), 0, (size_t)P * GREC * sizeof(float), side->stream));
-                GS_HIP(hipEventRecord(side->join2, side->stream));
-            }
-        }
+    }
+
+    // ---- the geometry and image buffers (allocator callbacks), their typed pointers, the side stream ----
+    int buffers(hipStream_t s)
+    {
+        cam = make_cam(c.viewmatrix, c.projmatrix, c.cam_pos, c.tan_fovx, c.tan_fovy, c.scale_modifier, W, H);
+        T = plan.T;
+        GL = geom_layout((size_t)P);
+        geom = (char*)c.geometry_alloc(c.geometry_ctx, GL.total);
+        if (!geom) return fail(GSRAST_E_ALLOC, "forward: geometry allocation failed");
+        IL = img_layout((size_t)W, (size_t)H);
+        img = (char*)c.image_alloc(c.image_ctx, IL.total);
+        if (!img) return fail(GSRAST_E_ALLOC, "forward: image allocation failed");
+        rec0 = at<float4>(geom, GL.rec0); rec1 = at<float4>(geom, GL.rec1); rec2 = at<float4>(geom, GL.rec2); grec = at<float4>(geom, GL.grec);
+        tiles = at<uint32_t>(geom, GL.tiles); rect = at<uint2>(geom, GL.rect);
+        kA = at<uint32_t>(geom, GL.keyA); kB = at<uint32_t>(geom, GL.keyB); vA = at<uint32_t>(geom, GL.valA); vB = at<uint32_t>(geom, GL.valB);
+        offsets = at<uint32_t>(geom, GL.offsets); woffsets = at<uint32_t>(geom, GL.woffsets); hist = at<uint32_t>(geom, GL.hist); scan_tmp = at<uint32_t>(geom, GL.scan_tmp);
+        scalars = at<uint32_t>(geom, GL.scalars); hint_sel = scalars + HINT_SEL;
+        bk_slab = at<uint4>(geom, GL.bk_slab); bk_info = at<uint4>(geom, GL.bk_info); bk_info_e = at<uint4>(geom, GL.bk_info_e);
+        bk_count = at<uint32_t>(geom, GL.bk_count); bk_key = at<uint32_t>(geom, GL.bk_key);
+        bk_order = at<uint32_t>(geom, GL.bk_order); bk_wincl = at<uint32_t>(geom, GL.bk_wincl); bk_base = at<uint32_t>(geom, GL.bk_base);
+        bk_order_e = at<uint32_t>(geom, GL.bk_order_e); bk_wincl_e = at<uint32_t>(geom, GL.bk_wincl_e); bk_base_e = at<uint32_t>(geom, GL.bk_base_e);
+        color_skip = at<unsigned long long>(geom, GL.color_skip); cand_bits = at<unsigned long long>(geom, GL.cand_bits);
+        tile_flags = at<unsigned char>(img, IL.tile_flags); bucket_cnt = at<uint32_t>(img, IL.bucket_cnt); bucket_list = at<uint16_t>(img, IL.bucket_list);
+        ranges = at<uint2>(img, IL.ranges);
+        // `prefiltered` is the caller's promise that no Gaussian will be culled by the near plane; the reference prints and traps when one is
+        // (auxiliary.h:156-160).  Here preprocess_fwd raises a word and this call returns GSRAST_E_ARG after it has waited for the device
+        // (SaRO-GS always passes False, renderer/__init__.py:63: the promise costs a synchronisation, nobody makes it on a hot path).
+        prefilter_word = c.prefiltered ? scalars + SC_PREFILTER : nullptr;
+        if (prefilter_word) GS_HIP(hipMemsetAsync(prefilter_word, 0, sizeof(uint32_t), s));
+        nbk = depth_buckets_host((size_t)P);
+        // equalised depth buckets: which waves of preprocess_fwd are sampled (512-1024 of them)
+        zh_klo = ctx->zrange.klo.load(); zh_shift = ctx->zrange.shift.load();
+        while ((((size_t)P + 63) / 64) / ((size_t)zh_wave_mask + 1) > 1024) zh_wave_mask = 2u * zh_wave_mask + 1u;
+        // Colour half of the per-Gaussian forward (SH -> RGB: most of its bytes) on the context's side stream, forked off the
+        // caller's stream behind the depth sort and joined in front of the blend: it overlaps the binning.
+        // Where it forks matters little: its 200 MB of traffic stretches whatever latency-bound kernel runs beside it by about as much as
+        // it hides (measured: beside the geometry kernel + depth sort +55 us, beside the run emission + run sort +45 / +65 us, beside the
+        // LDS-bound run_scatter_rows it starves itself and delays the blend) -- round 2 forked it at entry, the best of those by ~20 us.
+        // The 64 B / Gaussian zero-fill of the backward's gradient records follows on the side stream, under the VALU-bound forward blend.
+        if (o.side_stream) fork.side = side_stream_of(ctx);
         return GSRAST_OK;
-    };
-    // list cut: the device says at once whether the pose has a slot in the table (RB_FOUND); the launches over the cut lists of a pose
-    // that has none -- everything is early -- are sized for all column runs, not for the early runs of recent forwards (a launch
-    // that turned out too small cost a first-seen pose a whole second forward: 1.35 instead of 1.05 ms forward-only at 3 M)
-    int tau_ctx_device = -1;             // >= 0: tau_hist is the context's table on that device (gsrast_context::tau_dev)
-    uint32_t* zhist_call = nullptr; bool zhist_ctx = false;      // the depth histogram this call fills and reads: the context's (zeroed by the bucket sort) or the call's own
-    Readback* rb_pre = nullptr; uint32_t* pre_alias = nullptr; uint32_t pre_seq = 0;
-    if (cut) rb_pre = read_flag_prepare(&pre_alias, &pre_seq);
-    unsigned long long* host_found = rb_pre ? reinterpret_cast<unsigned long long*>(pre_alias) + RB_FOUND : nullptr;
+    }
+
+    // ---- the pose table, the policy's answer, the plan's second phase ----
+    // List cut (gsrast_common.h): whether THIS pose has cut depths is decided on the device; whether the cut pays, by CutPolicy (gsrast_policy.h).
+    int begin_policy(hipStream_t s)
+    {
+        // launch-order hints of the forward blend: per context, device and camera pose (gsrast_common.h)
+        hints = plan.want_hints ? hints_of(ctx, T, s) : nullptr;
+        CutPolicy& pol = ctx->pol;          // (the decisions: gsrast_policy.h)
+        if (pol.begin_forward((uint32_t)P)) {     // (what was learned belongs to the scene it was learned on: a context that moves on to a scene of another size starts afresh)
+            // keys, stamps, clock: every slot free again, ordered in front of this call's lookup -- of EVERY image size's table of this device (round 6,
+            // the other resolutions' tables kept the old scene's cut depths, running maxima that take eight visits to fade)
+            int device = 0;
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            if (hints && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32)
+                for (auto& h : ctx->hints[device]) if (h.table) GS_HIP(hipMemsetAsync(h.table, 0, sizeof(HintTable) /* everything in front of work[] */, s));
+            ctx->pose_seen.clear(); ctx->Qe_hint = 0; ctx->Qe_hint_tau = 0;
+        }
+        // The cut does not need the pose table.  With remembered cut depths (a pose the table knows) the first pass lists what lies in front
+        // of them; WITHOUT -- a first-seen pose, the table switched off -- it lists what lies in front of PREDICTED ones (tau_cut_kernel), and
+        // the completion pass behind the blend lists the rest into the tiles that did not saturate.  Either way the result is exact, and a
+        // pause (the passes did not pay) stops both.
+        plan.policy_answer(pol.pays(plan.last_Q, plan.list_cut_always), hints != nullptr);
+        // the 32-byte binning records (everything the run emission needs of a Gaussian in one line) are written where the emission gathers
+        // EVERY visible Gaussian; under the list cut it gathers one in eight, from the blend's records, and preprocess_fwd writes 96 MB less at 3 M
+        binrec = plan.cut ? nullptr : at<float4>(geom, GL.binrec);
+        if (!plan.cut && !o.no_list_cut) pol.sits_out();
+        const bool forced = plan.cut && plan.tau_mode && pol.forced_prediction();
+        bool pose_expected = false;         // (see gsrast_context::pose_seen)
+        if (plan.cut && plan.tau_mode && hints && !forced) { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->pose_seen.find(c.viewmatrix); pose_expected = it != ctx->pose_seen.end() && it->second != 0; }
+        plan.prediction_answer(forced, pose_expected);
+        tau_hist = plan.tau_on ? at<uint32_t>(img, IL.tau_hist) : nullptr;
+        tau_bins = TauBins{0u, 0.0f, 0.0f, plan.tau_sample_mask};      // (scale 0: the context has not learned a depth range yet -- no prediction in this call)
+        {   const uint32_t klo = ctx->zrange.klo.load(), khi = ctx->zrange.khi.load();
+            if (plan.tau_on && khi > klo + (uint32_t)TAU_BINS) { tau_bins.lo = klo; tau_bins.scale = (float)TAU_BINS / (float)(khi - klo); tau_bins.inv_scale = (float)(khi - klo) / (float)TAU_BINS; } }
+        zcut_used = plan.cut ? at<uint32_t>(img, IL.zcut_used) : nullptr;
+        untouched = plan.keep_untouched ? at<unsigned char>(geom, GL.untouched) : nullptr;
+        // list cut: the device says at once whether the pose has a slot in the table (RB_FOUND); the launches over the cut lists of a pose
+        // that has none -- everything is early -- are sized for all column runs, not for the early runs of recent forwards (a launch
+        // that turned out too small cost a first-seen pose a whole second forward: 1.35 instead of 1.05 ms forward-only at 3 M)
+        if (plan.cut) rb_pre = read_flag_prepare(&pre_alias, &pre_seq);
+        return GSRAST_OK;
+    }
+
+    // ---- the geometry half of the per-Gaussian forward, and the predicted cut depths ----
+    int preprocess(hipStream_t s)
     {
         ProfScope ps(K_PREPROCESS_FWD, s);
         const int pf_grid = (P + PF_THREADS - 1) / PF_THREADS;
-        float* cov_dbg = g_debug_state.load() ? at<float>(geom, GL.cov3D) : nullptr;     // 24 B / Gaussian nobody but gsrast_debug_export reads
-        const int clip = (runbin && o.tile_clip) ? 1 : 0;
-        // equalised depth buckets (gsrast_common.h): the sampled depth histogram, zeroed in front of the kernel that fills it
-        uint32_t* zr = nullptr;
-        if (bucket_sort) {
+        float* cov_dbg = plan.debug_state ? at<float>(geom, GL.cov3D) : nullptr;     // 24 B / Gaussian nobody but gsrast_debug_export reads
+        if (plan.bucket_sort) {      // the context's depth histogram on this device, zeroed again by the bucket sort (no memset launch per forward)
+            uint32_t* zr = nullptr;
             int device = 0;
             if (hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32) {
                 std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1218,13 +1189,12 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
                 zr = at<uint32_t>(geom, GL.zhist);
                 GS_HIP(hipMemsetAsync(zr, 0, ZH_COPIES * ZH_BINS * sizeof(uint32_t), s));
             }
+            zhist_call = zr;
         }
-        zhist_call = zr;
-        if (tau_hist) {
-            // the context's table where the bucket sort will zero it again behind tau_cut_kernel; else the call's own and a memset
+        if (tau_hist) {      // the context's opacity-mass table where the bucket sort will zero it again behind tau_cut_kernel; else the call's own and a memset
             const size_t words = (size_t)TAU_COPIES * T * TAU_BINS;
             int device = 0;
-            if (bucket_sort && zhist_ctx && !g_debug_state.load() /* (diagnostics read the table back from the image buffer: tools/tau_debug.py) */ && (words & 3) == 0 && words / 4 <= 0xFFFFFFFFull && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32) {
+            if (plan.bucket_sort && zhist_ctx && !plan.debug_state /* (diagnostics read the table back from the image buffer: tools/tau_debug.py) */ && (words & 3) == 0 && words / 4 <= 0xFFFFFFFFull && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32) {
                 std::lock_guard<std::mutex> lk(ctx->mu);
                 if (ctx->tau_dev_words[device] < words) {
                     if (ctx->tau_dev[device]) { (void)hipFree(ctx->tau_dev[device]); ctx->tau_dev[device] = nullptr; ctx->tau_dev_words[device] = 0; }
@@ -1240,238 +1210,285 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
             }
             if (tau_ctx_device < 0) GS_HIP(hipMemsetAsync(tau_hist, 0, words * sizeof(uint32_t), s));
         }
-        const int nzero = bucket_sort ? (int)nbk * BK_XCD + BK_XCD * BK_NBC_MAX : 0;      // (fine counters + the two-launch scatter's coarse ones, contiguous)
-        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(aa, [&](auto aa_c) {       // <RAW, AA>
+        const int nzero = plan.bucket_sort ? (int)nbk * BK_XCD + BK_XCD * BK_NBC_MAX : 0;      // (fine counters + the two-launch scatter's coarse ones, contiguous)
+        unsigned long long* host_found = rb_pre ? reinterpret_cast<unsigned long long*>(pre_alias) + RB_FOUND : nullptr;
+        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(plan.aa, [&](auto aa_c) {       // <RAW, AA>
             preprocess_fwd_kernel<decltype(raw_c)::value, decltype(aa_c)::value><<<pf_grid, PF_THREADS, 0, s>>>(
-                P, means3D, scales, rotations, opacities, raw, cov3D_precomp, cam, radii, rec0, rec1, cov_dbg,
-                tiles, rect, binrec_p, kA, bucket_sort ? nullptr : vA, clip, at<uint32_t>(img, IL.bucket_cnt), zr, zh_klo, zh_shift, zh_wave_mask, at<uint32_t>(geom, GL.bk_count), nzero, hints, hint_sel,
+                P, means3D, scales, rotations, opacities, raw, c.cov3D_precomp, cam, c.radii, rec0, rec1, cov_dbg,
+                tiles, rect, binrec, kA, plan.bucket_sort ? nullptr : vA, plan.clip ? 1 : 0, bucket_cnt, zhist_call, zh_klo, zh_shift, zh_wave_mask, bk_count, nzero, hints, hint_sel,
                 zcut_used, T, scalars, host_found, pre_seq, prefilter_word, untouched, tau_hist, tau_bins);
         }); });
         GS_LAUNCHED("preprocess_fwd");
         ctx->last_prologue_ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(), 0xFFFFFFFFll);
         if (tau_hist) {       // the predicted cut depths of a pose without remembered ones (a no-op for a pose the table knows, unless forced)
             const dim3 tg((unsigned)((cam.gx + TAU_TILE - 1) / TAU_TILE), (unsigned)((cam.gy + TAU_TILE - 1) / TAU_TILE));
-            tau_cut_kernel<<<tg, TAU_BLK * TAU_BLK, 0, s>>>(tau_hist, T, cam.gx, cam.gy, tau_bins, (uint32_t)pol.tau_req.load() * 256u, hints ? hint_sel : nullptr, tau_forced,
+            tau_cut_kernel<<<tg, TAU_BLK * TAU_BLK, 0, s>>>(tau_hist, T, cam.gx, cam.gy, tau_bins, (uint32_t)ctx->pol.tau_req.load() * 256u, hints ? hint_sel : nullptr, plan.tau_forced ? 1 : 0,
                                               zcut_used, tau_bins.scale > 0.0f ? 0 : 1);
             GS_LAUNCHED("tau_cut");
         }
+        return GSRAST_OK;
     }
-    const bool adaptive_sort = rs_blocks_n((size_t)P, GSRAST_DEPTH_ITEMS) > RS_SELF_SCAN_BLOCKS;      // see radix_sort
-    const bool assume_short = adaptive_sort && g_sort_hint.load() != 0 && ctx->depth_short.load() != 0;
-    const uint32_t* order = vA;     // the radix-sorted sequence ends in A under every pass count; the bucket sort leaves (kA, vA) alone
-    bool bucketed = false;          // the order in force comes from the bucket sort (per-bucket slot ranges) rather than `order`
-    bool totals_pending = false;    // ... and nobody has summed the buckets' totals (R, Q, overflow verdict) into `scalars` yet
-    auto sort_and_scan = [&](bool assume, bool buckets) -> int {
+
+    BucketSortArgs whole_buckets() const { return BucketSortArgs{ bk_slab, bk_count, nbk, bk_key, bk_order, bk_wincl, bk_info, bk_base }; }
+    // ---- depth order of the Gaussians: the bucket sort (gsrast_binning.h), or the radix passes and the scan of the widths ----
+    int sort_and_scan(hipStream_t s, bool assume, bool buckets)
+    {
         bucketed = buckets; totals_pending = false;
-        if (buckets) {      // three launches instead of the radix passes and the scan (gsrast_binning.h)
-            uint32_t* gcount = at<uint32_t>(geom, GL.bk_count);
-            uint4* slab = at<uint4>(geom, GL.bk_slab);
-            {   ProfScope ps(K_SORT_DEPTH, s);
-                const int items = depth_scatter_items((size_t)P);       // (elements per lane: whatever makes the launch ONE round of workgroups)
-                // two-launch form (gsrast_binning.h, round 6; from g_two_level_min_p Gaussians on): coarse scatter, then the refine kernel
-                const bool two = g_two_level.load() != 0 && (size_t)P >= (size_t)g_two_level_min_p.load();
-                auto scatter = two ? (items == BK_ITEMS_WIDE ? depth_bucket_scatter_kernel<BK_ITEMS_WIDE, true> : depth_bucket_scatter_kernel<BK_ITEMS, true>)
-                                   : (items == BK_ITEMS_WIDE ? depth_bucket_scatter_kernel<BK_ITEMS_WIDE, false> : depth_bucket_scatter_kernel<BK_ITEMS, false>);
-                // (the coarse slab: the gradient records' memory -- 64 B per Gaussian, nobody's until this forward's last blend; whoever zeroes or reads the records does so behind it)
-                uint4* cslab = reinterpret_cast<uint4*>(at<float>(geom, GL.grec));
-                const uint32_t ccap = depth_coarse_cap((size_t)P, nbk);
-                uint32_t* gccount = at<uint32_t>(geom, GL.bk_ccount);
-                scatter<<<(P + 256 * items - 1) / (256 * items), 256, 0, s>>>(kA, rect, tiles, (uint32_t)P, zhist_call, zh_klo, zh_shift, nbk, two ? gccount : gcount, two ? cslab : slab, at<uint32_t>(geom, GL.bk_key), scalars + SC_ZBINS,
-                                                                               zcut_used, T, (uint32_t)cam.gx, scalars + SC_N_LATE,
-                                                                               cut ? at<unsigned long long>(geom, GL.color_skip) : nullptr, (uint32_t)cut_cs, ccap);
-                GS_LAUNCHED("depth_bucket_scatter");
-                if (two) {
-                    depth_bucket_refine_kernel<<<(nbk >> BK_CSHIFT) * BK_XCD, 256, 0, s>>>(cslab, gccount, nbk, gcount, slab, ccap);
-                    GS_LAUNCHED("depth_bucket_refine");
-                }
-                // (List cut: the compacting colour kernel needs nothing but the scatter's late flags.  Forked HERE, beside the bucket sort and
-                // the emission, instead of behind the depth sort: 3 M 767 / 764 vs 763 / 762 views/s, 1 M 1219 / 1222 vs 1221 / 1220 -- equal.)
-                // list cut: only the bucket's EARLY Gaussians are sorted (into the early set); the late ones count into bk_info's totals
-                uint4* const tau_zero = tau_ctx_device >= 0 ? reinterpret_cast<uint4*>(tau_hist) : nullptr;
-                const uint32_t tau_zero_n = tau_ctx_device >= 0 ? (uint32_t)((size_t)TAU_COPIES * T * TAU_BINS / 4) : 0u;
-                if (cut) depth_bucket_sort_kernel<<<(nbk + BK_WAVES - 1) / BK_WAVES, 64 * BK_WAVES, 0, s>>>(slab, gcount, nbk, at<uint32_t>(geom, GL.bk_key), at<uint32_t>(geom, GL.bk_order_e), at<uint32_t>(geom, GL.bk_wincl_e),
-                                                                                                            at<uint4>(geom, GL.bk_info_e), at<uint32_t>(geom, GL.bk_base_e), at<uint4>(geom, GL.bk_info),
-                                                                                                            nullptr, nullptr, zhist_ctx ? zhist_call : nullptr, ZH_COPIES * ZH_BINS, tau_zero, tau_zero_n);
-                else depth_bucket_sort_kernel<<<(nbk + BK_WAVES - 1) / BK_WAVES, 64 * BK_WAVES, 0, s>>>(slab, gcount, nbk, at<uint32_t>(geom, GL.bk_key), at<uint32_t>(geom, GL.bk_order), at<uint32_t>(geom, GL.bk_wincl),
-                                                                                                        at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base),
-                                                                                                        nullptr, nullptr, nullptr, zhist_ctx ? zhist_call : nullptr, ZH_COPIES * ZH_BINS, tau_zero, tau_zero_n);
-                GS_LAUNCHED("depth_bucket_sort");
-                if (tau_zero) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->tau_dev_dirty[tau_ctx_device] = false; } }
-            totals_pending = true;      // by the run emission's last workgroup, or by launch_bucket_totals() if the host needs them first
-            return GSRAST_OK;
-        } else {
-            order = vA;
+        if (buckets) {      // three launches instead of the radix passes and the scan
             ProfScope ps(K_SORT_DEPTH, s);
-            if (bucket_sort) {      // the geometry kernel left the values to the bucket sort (which overflowed): the identity, now
+            const int items = depth_scatter_items((size_t)P);       // (elements per lane: whatever makes the launch ONE round of workgroups)
+            // two-launch form (gsrast_binning.h, round 6; from two_level_min_p Gaussians on): coarse scatter, then the refine kernel
+            const bool two = plan.two_level;
+            auto scatter = two ? (items == BK_ITEMS_WIDE ? depth_bucket_scatter_kernel<BK_ITEMS_WIDE, true> : depth_bucket_scatter_kernel<BK_ITEMS, true>)
+                               : (items == BK_ITEMS_WIDE ? depth_bucket_scatter_kernel<BK_ITEMS_WIDE, false> : depth_bucket_scatter_kernel<BK_ITEMS, false>);
+            // (the coarse slab: the gradient records' memory -- 64 B per Gaussian, nobody's until this forward's last blend; whoever zeroes or reads the records does so behind it)
+            uint4* cslab = reinterpret_cast<uint4*>(grec);
+            const uint32_t ccap = depth_coarse_cap((size_t)P, nbk);
+            uint32_t* gccount = at<uint32_t>(geom, GL.bk_ccount);
+            scatter<<<(P + 256 * items - 1) / (256 * items), 256, 0, s>>>(kA, rect, tiles, (uint32_t)P, zhist_call, zh_klo, zh_shift, nbk, two ? gccount : bk_count, two ? cslab : bk_slab, bk_key, scalars + SC_ZBINS,
+                                                                           zcut_used, T, (uint32_t)cam.gx, scalars + SC_N_LATE, plan.cut ? color_skip : nullptr, (uint32_t)plan.cut_cs, ccap);
+            GS_LAUNCHED("depth_bucket_scatter");
+            if (two) {
+                depth_bucket_refine_kernel<<<(nbk >> BK_CSHIFT) * BK_XCD, 256, 0, s>>>(cslab, gccount, nbk, bk_count, bk_slab, ccap);
+                GS_LAUNCHED("depth_bucket_refine");
+            }
+            // list cut: only the bucket's EARLY Gaussians are sorted (into the early set); the late ones count into bk_info's totals
+            BucketSortArgs a = whole_buckets();
+            if (plan.cut) { a.border = bk_order_e; a.bwincl = bk_wincl_e; a.binfo = bk_info_e; a.bwsum = bk_base_e; a.binfo_all = bk_info; }
+            a.zero_words = zhist_ctx ? zhist_call : nullptr; a.n_zero_words = ZH_COPIES * ZH_BINS;
+            if (tau_ctx_device >= 0) { a.zero_quads = reinterpret_cast<uint4*>(tau_hist); a.n_zero_quads = (uint32_t)((size_t)TAU_COPIES * T * TAU_BINS / 4); }
+            launch_bucket_sort(s, a);
+            GS_LAUNCHED("depth_bucket_sort");
+            if (a.zero_quads) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->tau_dev_dirty[tau_ctx_device] = false; }
+            totals_pending = true;      // by the run emission's last workgroup, or by depth_bucket_scan_kernel if the host needs them first
+            return GSRAST_OK;
+        }
+        {   ProfScope ps(K_SORT_DEPTH, s);      // (the radix-sorted sequence ends in (kA, vA) under every pass count)
+            if (plan.bucket_sort) {      // the geometry kernel left the values to the bucket sort (which overflowed): the identity, now
                 iota_kernel<<<(P + 255) / 256, 256, 0, s>>>(vA, (uint32_t)P);
                 GS_LAUNCHED("iota");
             }
             // the last pass also writes rectangle widths (and, for the instance-level binning, tile counts) in depth order
             const SortAdapt<uint32_t, uint32_t> ad{ at<uint32_t>(geom, GL.keyC), at<uint32_t>(geom, GL.valC), at<uint32_t>(geom, GL.sort_minmax), scalars + 8, assume };
-            int rc = radix_sort<uint32_t, uint32_t, GSRAST_DEPTH_ITEMS>(kA, vA, kB, vB, (uint32_t)P, 32, hist, scan_tmp, s, rect, runbin ? nullptr : offsets, woffsets, nullptr, &ad);
+            int rc = radix_sort<uint32_t, uint32_t, GSRAST_DEPTH_ITEMS>(kA, vA, kB, vB, (uint32_t)P, 32, hist, scan_tmp, s, rect, plan.runbin ? nullptr : offsets, woffsets, nullptr, &ad);
             if (rc != GSRAST_OK) return rc;
         }
         ProfScope ps(K_SCAN_TILES, s);
-        int rc;
-        if (runbin) {   // only the widths are scanned (-> run offsets, Q); num_rendered is just the sum of the tile counts
-            rc = scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s, nullptr, tiles, scalars, scalars + 3);
-        } else {
-            rc = scan_u32(offsets, nullptr, (uint32_t)P, offsets, true, scan_tmp, scalars, s);
-            if (rc != GSRAST_OK) return rc;
-            rc = scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s);   // column runs
+        if (plan.runbin)   // only the widths are scanned (-> run offsets, Q); num_rendered is just the sum of the tile counts
+            return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s, nullptr, tiles, scalars, scalars + 3);
+        int rc = scan_u32(offsets, nullptr, (uint32_t)P, offsets, true, scan_tmp, scalars, s);
+        if (rc != GSRAST_OK) return rc;
+        return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s);   // column runs
+    }
+
+    // ---- plan, second phase: the device's word on the pose (written at the very start of preprocess_fwd, long before this point) ----
+    void learn_pose()
+    {
+        plan.pose_answer(!(plan.cut && rb_pre && hints) || read_found(rb_pre));
+        if (plan.cut && plan.tau_mode && hints && rb_pre) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            if (ctx->pose_seen.size() > 4096) ctx->pose_seen.clear();
+            ctx->pose_seen[c.viewmatrix] = plan.pose_known ? 1 : 0;
         }
-        return rc;
-    };
-    { int rc = sort_and_scan(assume_short, bucket_sort); if (rc != GSRAST_OK) return rc; }
-    // The colour kernel forks HERE, behind the geometry kernel and the depth sort (round 3; rounds 1-2: at entry): the geometry kernel
+    }
+    size_t bin_bytes() const { return plan.runbin ? runbin_layout((size_t)cap, (size_t)capQ).total : bin_layout((size_t)cap).total; }
+    // ---- the binning buffer of the speculative launch: requested for 1.25 x the hints BEFORE the host knows the counts ----
+    int speculative_buffer(hipStream_t s)
+    {
+        // reference rasterizer_impl.cu:311 (the run-compressed path writes every tile's range itself, empty ones included)
+        if (!plan.runbin) GS_HIP(hipMemsetAsync(ranges, 0, (size_t)T * sizeof(uint2), s));
+        t0 = std::chrono::steady_clock::now();
+        if (plan.R_hint) {
+            cap = grow_capacity(plan.R_hint); capQ = grow_capacity(ctx->Q_hint.load());
+            bin = (char*)c.binning_alloc(c.binning_ctx, bin_bytes());
+            if (!bin) cap = capQ = 0;
+        }
+        t1 = std::chrono::steady_clock::now();
+        plan.binning_answer(bin != nullptr);
+        return GSRAST_OK;
+    }
+
+    // ---- the colour half.  List cut: early_only = only the Gaussians the bucket scatter did not mark culled or late (the compacting
+    // kernel: a Gaussian found late is in no list, its colour is not evaluated -- 3 M cube: 87 % of them); pred = the predicated launch ----
+    int color_kernels(hipStream_t cs, bool early_only, const uint32_t* pred)
+    {
+        ProfScope ps(K_COLOR, cs);
+        const float* const colors_precomp = c.colors_precomp; const float* const cam_pos = c.cam_pos; const int D = c.D, M = c.M;
+        // d(colour)/d(view direction) for the backward (36 B / Gaussian), unless the caller said that no backward will follow
+        float4 *sA = plan.want_shd ? at<float4>(geom, GL.shdA) : nullptr, *sB = plan.want_shd ? at<float4>(geom, GL.shdB) : nullptr; float* sC = plan.want_shd ? at<float>(geom, GL.shdC) : nullptr;
+        const float* sh_in = colors_precomp ? nullptr : shs;
+        unsigned char* cl = at<unsigned char>(geom, GL.clamped);
+        float4* gz = (fork.side || plan.zero_in_blend) ? nullptr : grec;
+        const bool staged = sh_in && M * 3 <= PP_SH_MAX && ((M * 3) & 3) == 0 && ((uintptr_t)sh_in & 15) == 0;
+        const int grid = (P + PP_THREADS - 1) / PP_THREADS;
+        if (early_only) {       // list cut: Gaussians the bucket scatter found culled or late are skipped (gsrast_preprocess.h)
+            // (with `pred`: the completion pass -- the colours of the late Gaussians that are listed after all, GeomLayout::skip2)
+            const unsigned char* skip = at<unsigned char>(geom, pred ? GL.skip2 : GL.color_skip);
+            const int cgrid = (P + PCC_IDS - 1) / PCC_IDS;
+            if (rawin) preprocess_color_compact_kernel<true><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, nullptr, nullptr, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
+            else preprocess_color_compact_kernel<false><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, sh_in, colors_precomp, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
+        } else if (rawin) {        // (gsrast_forward_raw has checked M and the alignment of the three SH arrays)
+            if (M * 3 == PP_SH_MAX) preprocess_color_kernel<PP_SH_MAX, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
+            else preprocess_color_kernel<0, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
+        } else if (staged && M * 3 == PP_SH_MAX)
+            preprocess_color_kernel<PP_SH_MAX, false><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, sh_in, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
+        else if (staged)
+            preprocess_color_kernel<0, false><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, sh_in, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
+        else
+            preprocess_color_direct_kernel<<<(P + 255) / 256, 256, 0, cs>>>(P, D, M, means3D, sh_in, colors_precomp, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(GSRAST_E_DEVICE, "preprocess_color", e);
+        return GSRAST_OK;
+    }
+    // The colour kernel forks off `s` behind the geometry kernel and the depth sort (round 3; rounds 1-2: at entry): the geometry kernel
     // is as bandwidth-bound as the colours are (running both at once is the sum of their times) and the bucket scatter's returning
     // atomics are what the colour traffic hurts most (70 -> 150 us at 3 M); the gather-bound run emission and the run sort that now
     // run beside it stretch less.  Two alternating runs each, views/s, entry -> here: 3 M 609 -> 619, 2 M 745 -> 753, 1 M 1059 -> 1082,
     // 0.3 M 1504 -> 1551, 0.1 M 1878 -> 1894, shell 1 M 884 -> 917, cfg2 2692 -> 2787.  Behind the geometry kernel only: 3 M -3.8 %
     // (the scatter beside the colours); behind the run emission: 3 M -4 % (the colours end after the binning, the blend waits).
-    // (a pose without a slot in the table has no cut depths: every visible Gaussian is early and the plain colour kernel, not the
-    // compacting one, evaluates them -- the device said so at the very start of preprocess_fwd, long before this point)
-    const bool pose_known = !(cut && rb_pre && hints) || read_found(rb_pre);
-    if (cut && tau_mode && hints && rb_pre) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->pose_seen.size() > 4096) ctx->pose_seen.clear();
-        ctx->pose_seen[viewmatrix] = pose_known ? 1 : 0;
+    int launch_color(hipStream_t s)
+    {
+        if (fork.launched) return GSRAST_OK;
+        fork.launched = true;
+        SideStream* const side = fork.side;
+        if (side) {
+            GS_HIP(hipEventRecord(side->fork, s));             // the inputs (and the buffers just handed out) are ordered on s
+            GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
+        }
+        { int rc = color_kernels(side ? side->stream : s, plan.cut_colors, nullptr); if (rc != GSRAST_OK) return rc; }
+        // The backward's gradient records (64 B / Gaussian) are zero-filled by the forward: inside the default (culling) blend kernel; by a
+        // memset behind the colour kernel (side stream) / by the colour kernel itself (no side stream) when another blend kernel runs.
+        if (side) {
+            GS_HIP(hipEventRecord(side->join, side->stream));
+            if (!plan.zero_in_blend) {
+                GS_HIP(hipMemsetAsync(grec, 0, (size_t)P * GREC * sizeof(float), side->stream));
+                GS_HIP(hipEventRecord(side->join2, side->stream));
+            }
+        }
+        return GSRAST_OK;
     }
-    if (!pose_known && !tau_on) cut_colors = false;
-    // Everything that does not depend on num_rendered is enqueued / prepared before the host waits.
-    uint2* ranges = at<uint2>(img, IL.ranges);
-    // reference rasterizer_impl.cu:311 (the run-compressed path writes every tile's range itself, empty ones included)
-    if (!runbin) GS_HIP(hipMemsetAsync(ranges, 0, (size_t)T * sizeof(uint2), s));
-    const int tpasses = tile_passes(T);
-    auto bin_bytes = [&](uint32_t capR, uint32_t capQ) {
-        return runbin ? runbin_layout((size_t)capR, (size_t)capQ).total : bin_layout((size_t)capR).total;
-    };
-    auto grow = [](uint32_t v) { return grow_capacity(v); };
-    uint32_t cap = 0, capQ = 0;
-    char* bin = nullptr;
-    Readback* rb_flag = nullptr;                 // the counts arrive by the emission kernel's own store into pinned memory (no copy enqueued)
-    uint32_t* flag_alias = nullptr; uint32_t flag_seq = 0;
-    static const bool trace = getenv("GSRAST_TRACE") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    if (const uint32_t hint = ctx->R_hint.load()) {
-        cap = grow(hint); capQ = grow(ctx->Q_hint.load());
-        bin = (char*)binning_alloc(binning_ctx, bin_bytes(cap, capQ));
-        if (!bin) cap = capQ = 0;
-    }
-    auto t1 = std::chrono::steady_clock::now();
-    // the colour kernels, beside the binning
-    { int rc = launch_color(); if (rc != GSRAST_OK) return rc; }
 
-    // ---- the rest of the forward as two re-launchable pieces ----
-    // run-compressed binning; nQ / capR are either exact counts (counts_dev == nullptr) or capacities with the real
-    // counts read on the device (speculative launch: grids and histogram strides follow the capacities)
+    // ---- run-compressed binning on the buffer in force; nQ / cap are either exact counts (counts_dev == nullptr) or capacities with the
+    // real counts read on the device (speculative launch: grids and histogram strides follow the capacities) ----
     // mode (list cut): 0 = all Gaussians (as ever); 1 = the EARLY Gaussians only (counts_dev = scalars + SC_EARLY_COUNTS); 2 = all
-    // Gaussians again behind a blend over cut lists, every kernel predicated on scalars[SC_REDO_PRED] (counts_dev = scalars)
-    const uint32_t* redo_pred = scalars + SC_REDO_PRED;      // the completion pass's predicate (the gate's copy of it when the pass runs on its own stream)
-    auto launch_run_binning = [&](char* binb, uint32_t capR_, uint32_t capQ_, uint32_t nQ, const uint32_t* counts_dev, const std::function<int()>& after_emit = nullptr, int mode = 0) -> int {
-        const uint32_t* pred = mode == 2 ? redo_pred : nullptr;
-        const RunBinLayout RL = runbin_layout((size_t)capR_, (size_t)capQ_);
-        uint16_t *rkA = at<uint16_t>(binb, RL.rkeyA), *rkB = at<uint16_t>(binb, RL.rkeyB);
-        uint2 *rvA = at<uint2>(binb, RL.rvalA), *rvB = at<uint2>(binb, RL.rvalB);
-        uint32_t* hist_x = at<uint32_t>(binb, RL.hist_x);
-        uint32_t* hist_y = at<uint32_t>(binb, RL.hist_y);
-        uint32_t* rscan = at<uint32_t>(binb, RL.scan_tmp);
-        uint32_t* plist_w = at<uint32_t>(binb, RL.point_list);
+    // Gaussians again behind a blend over cut lists, every kernel predicated on *pred (counts_dev = scalars + SC_PASS2)
+    int run_binning(hipStream_t s, uint32_t nQ, const uint32_t* counts_dev, int mode, const uint32_t* pred, bool readback_after_emit)
+    {
+        const RunBinLayout RL = runbin_layout((size_t)cap, (size_t)capQ);
+        uint16_t *rkA = at<uint16_t>(bin, RL.rkeyA), *rkB = at<uint16_t>(bin, RL.rkeyB);
+        uint2 *rvA = at<uint2>(bin, RL.rvalA), *rvB = at<uint2>(bin, RL.rvalB);
+        uint32_t *hist_x = at<uint32_t>(bin, RL.hist_x), *hist_y = at<uint32_t>(bin, RL.hist_y), *rscan = at<uint32_t>(bin, RL.scan_tmp), *plist_w = at<uint32_t>(bin, RL.point_list);
         const uint32_t* Q_dev = counts_dev ? counts_dev + 1 : nullptr;
         const int xbits = tile_bits((size_t)cam.gx);
         {   ProfScope ps(K_EMIT, s);
-            if (bucketed && mode == 1)
-                emit_column_runs_kernel<<<nbk + 1, 256, 0, s>>>(P, at<uint32_t>(geom, GL.bk_order_e), at<uint32_t>(geom, GL.bk_wincl_e), binrec_p, W, H,
-                                                            o.tile_clip, capQ_, rkA, rvA, at<uint4>(geom, GL.bk_info_e), at<uint32_t>(geom, GL.bk_base_e), nbk, scalars,
-                                                            flag_alias, flag_seq, at<uint4>(geom, GL.bk_info), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
-            else if (bucketed && mode == 2) {
+            EmitArgs e{};
+            e.grid = nbk + 1; e.P = P; e.order = bk_order; e.woffsets = bk_wincl; e.binrec = binrec; e.W = W; e.H = H; e.clip = o.tile_clip; e.capQ = capQ; e.run_keys = rkA; e.run_vals = rvA;
+            e.rec0 = rec0; e.rec1 = rec1; e.rect = rect;
+            if (bucketed) { e.binfo = bk_info; e.bwsum = bk_base; e.nbuckets = nbk; }
+            if (bucketed && mode == 1) {
+                e.order = bk_order_e; e.woffsets = bk_wincl_e; e.binfo = bk_info_e; e.bwsum = bk_base_e; e.binfo_all = bk_info;
+                e.scalars = scalars; e.host_out = flag_alias; e.host_seq = flag_seq;
+            } else if (bucketed && mode == 2) {
                 // COMPLETION pass: only the CANDIDATES -- the Gaussians, early or late, whose rectangle touches a tile flagged by the
                 // blend -- are sorted (the buckets' non-early arrays are free) and listed, and only into flagged tiles
-                depth_bucket_sort_kernel<<<(nbk + BK_WAVES - 1) / BK_WAVES, 64 * BK_WAVES, 0, s>>>(at<uint4>(geom, GL.bk_slab), at<uint32_t>(geom, GL.bk_count), nbk, at<uint32_t>(geom, GL.bk_key), at<uint32_t>(geom, GL.bk_order),
-                                                                                                   at<uint32_t>(geom, GL.bk_wincl), at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base), nullptr, pred,
-                                                                                                   at<unsigned long long>(geom, GL.cand_bits));
-                emit_column_runs_kernel<<<nbk + 1, 256, 0, s>>>(P, at<uint32_t>(geom, GL.bk_order), at<uint32_t>(geom, GL.bk_wincl), binrec_p, W, H,
-                                                            o.tile_clip, capQ_, rkA, rvA, at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base), nbk, nullptr,
-                                                            nullptr, 0, nullptr, pred, at<uint32_t>(img, IL.bucket_cnt), XCD_GROUPS * WORK_BUCKETS /* (the forward's order only: the backward's keeps the tiles that are final) */, hints,
-                                                            rb_pre ? reinterpret_cast<unsigned long long*>(pre_alias) + RB_FALLBACK : nullptr, pre_seq,
-                                                            at<unsigned char>(img, IL.tile_flags), cam.gx, scalars + SC_PASS2, rec0, rec1, rect); }
-            else if (bucketed) {
-                if (cut) {      // (a list-cut forward sorted the early Gaussians only, and now everything is listed after all: the buckets are sorted again, whole)
-                    depth_bucket_sort_kernel<<<(nbk + BK_WAVES - 1) / BK_WAVES, 64 * BK_WAVES, 0, s>>>(at<uint4>(geom, GL.bk_slab), at<uint32_t>(geom, GL.bk_count), nbk, at<uint32_t>(geom, GL.bk_key), at<uint32_t>(geom, GL.bk_order),
-                                                                                                       at<uint32_t>(geom, GL.bk_wincl), at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base));
+                BucketSortArgs a = whole_buckets(); a.pred = pred; a.keep_bits = cand_bits;
+                launch_bucket_sort(s, a);
+                e.pred = pred; e.redo_bucket_cnt = bucket_cnt; e.n_redo_cnt = XCD_GROUPS * WORK_BUCKETS /* (the forward's order only: the backward's keeps the tiles that are final) */; e.redo_hints = hints;
+                e.host_fallback = rb_pre ? reinterpret_cast<unsigned long long*>(pre_alias) + RB_FALLBACK : nullptr; e.host_fb_seq = pre_seq;
+                e.need2 = tile_flags; e.gx_tiles = cam.gx; e.pass2_counts = scalars + SC_PASS2;
+            } else if (bucketed) {
+                if (plan.cut) {      // (a list-cut forward sorted the early Gaussians only, and now everything is listed after all: the buckets are sorted again, whole)
+                    launch_bucket_sort(s, whole_buckets());
                     GS_LAUNCHED("depth_bucket_sort");
                 }
-                emit_column_runs_kernel<<<nbk + 1, 256, 0, s>>>(P, at<uint32_t>(geom, GL.bk_order), at<uint32_t>(geom, GL.bk_wincl), binrec_p, W, H,
-                                                            o.tile_clip, capQ_, rkA, rvA, at<uint4>(geom, GL.bk_info), at<uint32_t>(geom, GL.bk_base), nbk, scalars,
-                                                            flag_alias, flag_seq, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
-            } else
-                emit_column_runs_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, order, woffsets, binrec_p, W, H,
-                                                                       o.tile_clip, capQ_, rkA, rvA, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, rec0, rec1, rect);
+                e.scalars = scalars; e.host_out = flag_alias; e.host_seq = flag_seq;
+            } else { e.grid = (uint32_t)((P + 255) / 256); e.order = vA; e.woffsets = woffsets; }
+            launch_emit(s, e);
             GS_LAUNCHED("emit_column_runs"); }
         if (bucketed && mode != 2) totals_pending = false;
-        if (after_emit) { int rc = after_emit(); if (rc != GSRAST_OK) return rc; }
+        if (readback_after_emit) { int rc = read_u32_begin(scalars, s, 12, &rb); if (rc != GSRAST_OK) return rc; }
         const uint32_t nblk = (nQ + RUNS_PER_BLOCK - 1) / RUNS_PER_BLOCK;
-        {   ProfScope ps(K_SORT_TILE, s);
-            int rc = radix_sort<uint16_t, uint2, GSRAST_RUN_SORT_ITEMS>(rkA, rvA, rkB, rvB, nQ, xbits, hist_x, rscan, s, nullptr, nullptr, nullptr, Q_dev, nullptr, pred);   // runs by column
-            if (rc != GSRAST_OK) return rc;
-            if (radix_passes(xbits) & 1) { std::swap(rkA, rkB); std::swap(rvA, rvB); }                   // sorted runs now in (rkA, rvA)
-            run_hist_rows_kernel<<<nblk, 256, 0, s>>>(rvA, nQ, Q_dev, hist_y, nblk, (uint32_t)cam.gy, pred);
-            GS_LAUNCHED("run_hist_rows");
-            radix_rowscan_kernel<<<cam.gy, 256, 0, s>>>(hist_y, nblk, rscan, nullptr, 0, nullptr, 0, pred);     // one workgroup per tile row
-            GS_LAUNCHED("radix_rowscan");
-            // the row pass and the tile ranges in one launch (gsrast_binning.h)
-            rows_and_ranges_kernel<<<nblk + (uint32_t)cam.gx, RS_THREADS, 0, s>>>(rkA, rvA, nQ, counts_dev, capR_, tile_bits((size_t)cam.gy), cam.gx, cam.gy, hist_y, rscan, nblk,
-                                                                                 mode == 2 ? plist_w + capR_ : plist_w, mode == 2 ? scalars + SC_PASS2 + 2 : scalars + 2, ranges,
-                                                                                 buckets_ok ? at<uint32_t>(img, IL.bucket_cnt) : nullptr, at<uint16_t>(img, IL.bucket_list), hints, hint_sel, pred,
-                                                                                 mode == 2 ? at<unsigned char>(img, IL.tile_flags) : nullptr, mode == 2 ? capR_ : 0u,
-                                                                                 (mode == 1 && tau_on) ? zcut_used : nullptr);
-            GS_LAUNCHED("rows_and_ranges"); }
+        ProfScope ps(K_SORT_TILE, s);
+        int rc = radix_sort<uint16_t, uint2, GSRAST_RUN_SORT_ITEMS>(rkA, rvA, rkB, rvB, nQ, xbits, hist_x, rscan, s, nullptr, nullptr, nullptr, Q_dev, nullptr, pred);   // runs by column
+        if (rc != GSRAST_OK) return rc;
+        if (radix_passes(xbits) & 1) { std::swap(rkA, rkB); std::swap(rvA, rvB); }                   // sorted runs now in (rkA, rvA)
+        run_hist_rows_kernel<<<nblk, 256, 0, s>>>(rvA, nQ, Q_dev, hist_y, nblk, (uint32_t)cam.gy, pred);
+        GS_LAUNCHED("run_hist_rows");
+        radix_rowscan_kernel<<<cam.gy, 256, 0, s>>>(hist_y, nblk, rscan, nullptr, 0, nullptr, 0, pred);     // one workgroup per tile row
+        GS_LAUNCHED("radix_rowscan");
+        // the row pass and the tile ranges in one launch (gsrast_binning.h)
+        rows_and_ranges_kernel<<<nblk + (uint32_t)cam.gx, RS_THREADS, 0, s>>>(rkA, rvA, nQ, counts_dev, cap, tile_bits((size_t)cam.gy), cam.gx, cam.gy, hist_y, rscan, nblk,
+                                                                             mode == 2 ? plist_w + cap : plist_w, mode == 2 ? scalars + SC_PASS2 + 2 : scalars + 2, ranges,
+                                                                             plan.buckets_ok ? bucket_cnt : nullptr, bucket_list, hints, hint_sel, pred,
+                                                                             mode == 2 ? tile_flags : nullptr, mode == 2 ? cap : 0u,
+                                                                             (mode == 1 && plan.tau_on) ? zcut_used : nullptr);
+        GS_LAUNCHED("rows_and_ranges");
         return GSRAST_OK;
-    };
-    // the completion pass's gate (ChainGate): claimed when the cut forward's blend is launched -- its last workgroup is the gate
-    ChainGate* gate = nullptr; uint32_t gseq = 0, *gdone = nullptr, *gpred = nullptr;
-    auto launch_blend = [&](const uint32_t* plist, bool fwd_lists_built, int mode = 0 /* list cut: as launch_run_binning */) -> int {
-        { int rc = launch_color(); if (rc != GSRAST_OK) return rc; }  // the other binning scheme / nothing to bin: not forked yet
-        if (side) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); if (zero_in_blend) side_guard.joined = true; }       // the colours (rec2) are the blend's input
+    }
+    // ---- instance-level binning (options.binning = 1, or an image too large for the run-compressed scheme) ----
+    // Tile ids fit 16 bits up to 65 536 tiles (4096 x 4096 pixels): the R-sized key streams are then half as wide (the key buffers are
+    // sized for 32-bit ids either way).
+    template <typename KeyT> int instance_binning(hipStream_t s, uint32_t R)
+    {
+        const BinLayout BL = bin_layout((size_t)cap);
+        uint32_t *tkA = at<uint32_t>(bin, BL.keyA), *tkB = at<uint32_t>(bin, BL.keyB);
+        uint32_t *tvA = at<uint32_t>(bin, BL.valA), *tvB = at<uint32_t>(bin, BL.valB);
+        if (tile_passes(T) & 1) { std::swap(tkA, tkB); std::swap(tvA, tvB); }   // odd pass count: start in B, finish in A
+        KeyT *hA = reinterpret_cast<KeyT*>(tkA), *hB = reinterpret_cast<KeyT*>(tkB);
+        { ProfScope ps(K_EMIT, s);
+          emit_instances_kernel<KeyT><<<(P + 255) / 256, 256, 0, s>>>(P, vA, offsets, tiles, rect, cam.gx, hA, tvA);
+          GS_LAUNCHED("emit_instances"); }
+        { ProfScope ps(K_SORT_TILE, s);
+          int rc = radix_sort<KeyT>(hA, tvA, hB, tvB, R, tile_bits(T), at<uint32_t>(bin, BL.hist), at<uint32_t>(bin, BL.scan_tmp), s);
+          if (rc != GSRAST_OK) return rc; }
+        ProfScope ps(K_RANGES, s);
+        tile_ranges_kernel<KeyT><<<(R + 255) / 256, 256, 0, s>>>(R, nullptr, reinterpret_cast<const KeyT*>(at<uint32_t>(bin, BL.keyA)), ranges);
+        GS_LAUNCHED("tile_ranges");
+        return GSRAST_OK;
+    }
+
+    // claims the completion pass's gate for the blend about to be launched; without one (gate == nullptr) the pass runs inline
+    void claim_gate()
+    {
+        if (!plan.chain_gate || counter_collection_env() || (gate = chain_gate_of(ctx)) == nullptr) return;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        uint32_t n = gate->seq + 1u; if (n == 0u) n = 1u;
+        // the slot of n was last used by n - GATE_RING; it is free once the chain of n - GATE_RING / 2 (enqueued later on the same
+        // in-order stream) has run.  Not yet?  Then this call does without the gate (inline chain).
+        // (a call that claimed a number but never enqueued a chain recorded no event: the youngest recorded chain among
+        // n - GATE_RING / 2 ... n - GATE_RING answers for all older ones)
+        bool free_slot = true;
+        for (uint32_t back = GATE_RING / 2u; back <= GATE_RING; back++) {
+            const uint32_t k = n - back;
+            if (k != 0u && gate->tail_seq[k % GATE_RING] == k) { free_slot = hipEventQuery(gate->tail[k % GATE_RING]) == hipSuccess; break; }
+        }
+        if (!free_slot) { gate->inline_calls++; gate = nullptr; return; }
+        gate->seq = n; gseq = n; gate->tail_seq[n % GATE_RING] = 0u;
+        gdone = gate->words + (gseq % GATE_RING); gpred = gate->words + GATE_RING + (gseq % GATE_RING);
+    }
+    // ---- the forward blend over `plist`; mode as run_binning (2: predicated on *pred) ----
+    int blend(hipStream_t s, const uint32_t* plist, bool fwd_lists_built, int mode, const uint32_t* pred)
+    {
+        { int rc = launch_color(s); if (rc != GSRAST_OK) return rc; }  // the other binning scheme / nothing to bin: not forked yet
+        SideStream* const side = fork.side;
+        if (side) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); if (plan.zero_in_blend) fork.joined = true; }       // the colours (rec2) are the blend's input
         ProfScope ps(K_BLEND_FWD, s);
         uint32_t grid = ((T + 7) / 8) * 8;
-        float* fT = at<float>(img, IL.final_T); uint32_t* nc = at<uint32_t>(img, IL.n_contrib);
-        uint32_t* tm = at<uint32_t>(img, IL.tile_max);
         BlendArgs ba{};
         ba.ranges = ranges; ba.plist = plist; ba.W = W; ba.H = H; ba.gx = cam.gx; ba.T = T; ba.r0 = rec0; ba.r1 = rec1; ba.r2 = rec2;
-        ba.bg = background; ba.oc = out_color; ba.od = out_depth; ba.fT = fT; ba.nc = nc; ba.tm = tm;
+        ba.bg = c.background; ba.oc = c.out_color; ba.od = c.out_depth; ba.fT = at<float>(img, IL.final_T); ba.nc = at<uint32_t>(img, IL.n_contrib); ba.tm = at<uint32_t>(img, IL.tile_max);
         ba.oad = out_acc_depth; ba.oal = out_alpha;           // (every launch: the first pass, the completion pass, a redo)
-        const int ppl = pick_ppl(T, false, o);
-        const bool cull = o.cull != 0 && o.fwd_pixels_per_lane == 0;   // a forced pixels-per-lane selects the un-culled template
-        if (zero_in_blend && !zero_touched && !o.forward_only && mode != 2) { ba.zero4 = at<float4>(geom, GL.grec); ba.n_zero4 = (uint32_t)((size_t)P * 4); }
+        if (plan.zero_in_blend && !plan.zero_touched && !o.forward_only && mode != 2) { ba.zero4 = grec; ba.n_zero4 = (uint32_t)((size_t)P * 4); }
         if (fwd_lists_built) { ba.hints = hints; ba.hint_sel = hint_sel; }      // (the slot is only claimed on the work-bucket path)
-        ba.cut_margin_x4 = (uint32_t)pol.margin.load();
+        ba.cut_margin_x4 = (uint32_t)ctx->pol.margin.load();
         ba.untouched = untouched;
-        if (mode == 1) { ba.zcut_used = zcut_used; ba.cut_scalars = scalars; ba.tile_flags = at<unsigned char>(img, IL.tile_flags); }
-        if (mode == 1 && cull && g_chain_gate.load() != 0 && !counter_collection_env() && (gate = chain_gate_of(ctx)) != nullptr) {
-            {   std::lock_guard<std::mutex> lk(ctx->mu);
-                uint32_t n = gate->seq + 1u; if (n == 0u) n = 1u;
-                // the slot of n was last used by n - GATE_RING; it is free once the chain of n - GATE_RING / 2 (enqueued later on the same
-                // in-order stream) has run.  Not yet?  Then this call does without the gate (inline chain below).
-                // (a call that claimed a number but never enqueued a chain recorded no event: the youngest recorded chain among
-                // n - GATE_RING / 2 ... n - GATE_RING answers for all older ones)
-                bool free_slot = true;
-                for (uint32_t back = GATE_RING / 2u; back <= GATE_RING; back++) {
-                    const uint32_t k = n - back;
-                    if (k != 0u && gate->tail_seq[k % GATE_RING] == k) { free_slot = hipEventQuery(gate->tail[k % GATE_RING]) == hipSuccess; break; }
-                }
-                if (!free_slot) { gate->inline_calls++; gate = nullptr; }
-                else { gate->seq = n; gseq = n; gate->tail_seq[n % GATE_RING] = 0u; }
-            }
-            if (gate) {
-                gdone = gate->words + (gseq % GATE_RING); gpred = gate->words + GATE_RING + (gseq % GATE_RING);
-                ba.gate = GateArgs{ at<uint32_t>(img, IL.bucket_cnt) + (XCD_GROUPS + 1) * WORK_BUCKETS, gpred, gdone, gseq };
-            }
-        }
-        if (mode == 2) ba.pred = redo_pred;
-        if (buckets_ok) { ba.bcnt = at<uint32_t>(img, IL.bucket_cnt); ba.blist = at<uint16_t>(img, IL.bucket_list); }   // backward order: always appended
-        if (cull && o.lpt) {
-            if (buckets_ok && fwd_lists_built) { ba.from_buckets = 1; grid = (uint32_t)(XCD_GROUPS * xcd_group_tiles_host((size_t)cam.gx, (size_t)cam.gy)); }   // the tile-range kernel already bucketed the tiles
+        if (mode == 1) { ba.zcut_used = zcut_used; ba.cut_scalars = scalars; ba.tile_flags = tile_flags; }
+        if (mode == 1 && plan.culled) claim_gate();
+        if (mode == 1 && gate) ba.gate = GateArgs{ bucket_cnt + (XCD_GROUPS + 1) * WORK_BUCKETS, gpred, gdone, gseq };
+        if (mode == 2) ba.pred = pred;
+        if (plan.buckets_ok) { ba.bcnt = bucket_cnt; ba.blist = bucket_list; }   // backward order: always appended
+        if (plan.ordered) {
+            if (plan.buckets_ok && fwd_lists_built) { ba.from_buckets = 1; grid = (uint32_t)(XCD_GROUPS * xcd_group_tiles_host((size_t)cam.gx, (size_t)cam.gy)); }   // the tile-range kernel already bucketed the tiles
             else {
                 uint32_t* ord = at<uint32_t>(img, IL.order_fwd);
                 tile_order_kernel<<<1, 1024, 0, s>>>(T, ranges, nullptr, ord);
@@ -1479,218 +1496,210 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
                 ba.order = ord;
             }
         }
-        launch_blend_fwd(o.exp_mode, cull, ppl, grid, s, ba);
+        launch_blend_fwd(o.exp_mode, plan.culled, pick_ppl(T, false, o), grid, s, ba);
         GS_LAUNCHED("blend_fwd");
-        if (side && !zero_in_blend) { GS_HIP(hipStreamWaitEvent(s, side->join2, 0)); side_guard.joined = true; }      // the gradient records are zero before anything after this forward
+        if (side && !plan.zero_in_blend) { GS_HIP(hipStreamWaitEvent(s, side->join2, 0)); fork.joined = true; }      // the gradient records are zero before anything after this forward
         return GSRAST_OK;
-    };
-
-    // {instances R (low word), column runs Q, -, R (high word, run-compressed path), ..., [8] significant depth-key bits,
-    //  [9] key base, [10] "three sort passes were assumed and were not enough"}
-    uint32_t counts[12] = { 0 };
-    uint32_t nQ1 = 0;
-    Readback* rb = nullptr;
-    const bool speculative = runbin && bin != nullptr && o.speculative != 0;
-    auto begin_readback = [&]() -> int { return read_u32_begin(scalars, s, 12, &rb); };
-    if (!(speculative && totals_pending)) {       // (with the bucket sort the totals come out of the speculative run emission: read back right behind it)
-        if (totals_pending) {
-            ProfScope ps(K_SCAN_TILES, s);
-            depth_bucket_scan_kernel<<<1, 256, 0, s>>>(at<uint4>(geom, GL.bk_info), nbk, scalars);
-            GS_LAUNCHED("depth_bucket_scan");
-            totals_pending = false;
-        }
-        int rc = begin_readback(); if (rc != GSRAST_OK) return rc;
     }
-    // Speculative launch: with a buffer sized from the previous call, binning and blend are enqueued BEFORE the host knows
-    // R and Q (the kernels read the counts on the device), so the GPU never idles on the read-back.  If the counts turn
-    // out not to fit, the device published empty ranges and the two pieces are simply launched again with exact sizes.
-    if (speculative) {
-        const bool late = totals_pending;
+
+    // ---- the counts' read-back is begun; with a buffer sized from the previous call, binning and blend are enqueued BEFORE the host knows
+    // R and Q (the kernels read the counts on the device), so the GPU never idles on the read-back.  If the counts turn out not to fit,
+    // the device published empty ranges and the two pieces are simply launched again with exact sizes (exact_redo). ----
+    int speculative_launch(hipStream_t s)
+    {
+        if (!(plan.speculative && totals_pending)) {       // (with the bucket sort the totals come out of the speculative run emission: read back right behind it)
+            if (totals_pending) {
+                ProfScope ps(K_SCAN_TILES, s);
+                depth_bucket_scan_kernel<<<1, 256, 0, s>>>(bk_info, nbk, scalars);
+                GS_LAUNCHED("depth_bucket_scan");
+                totals_pending = false;
+            }
+            int rc = read_u32_begin(scalars, s, 12, &rb); if (rc != GSRAST_OK) return rc;
+        }
+        if (!plan.speculative) return GSRAST_OK;
+        const bool late = totals_pending;      // the counts arrive by the emission kernel's own store into pinned memory (no copy enqueued)
         if (late) { if (rb_pre) { rb_flag = rb_pre; flag_alias = pre_alias; flag_seq = pre_seq; } else rb_flag = read_flag_prepare(&flag_alias, &flag_seq); }
         // (list cut: the sorts over the cut lists are sized for the early runs of recent forwards, not for all runs)
         // (the early set differs from pose to pose -- 0.98 M / 1.29 M column runs at two neighbouring poses of the 3 M cube --, a launch
         // sized too small costs a whole second forward, one sized too large a few empty workgroups: half again as much as the largest of
         // the recent forwards)
-        if (cut) {
-            // (a forward under predicted cut depths keeps two or three times the early set of one under remembered ones: each kind is sized by its own history)
-            const bool predicted_call = tau_on && (tau_forced || !pose_known || !hints);
-            const uint32_t qe = predicted_call ? ctx->Qe_hint_tau.load() : ctx->Qe_hint.load();
-            const bool early_set_expected = pose_known || tau_on;
-            nQ1 = early_launch_runs(qe, capQ, early_set_expected);
-        }
-        int rc = launch_run_binning(bin, cap, capQ, cut ? nQ1 : capQ, cut ? scalars + SC_EARLY_COUNTS : scalars, (late && !rb_flag) ? std::function<int()>(begin_readback) : std::function<int()>(), cut ? 1 : 0);
-        flag_alias = nullptr;                    // (a repeated emission below reads its counts back the ordinary way)
-        if (rc == GSRAST_OK) rc = launch_blend(at<uint32_t>(bin, 0), true, cut ? 1 : 0);
-        if (rc != GSRAST_OK) return rc;
+        if (plan.cut) nQ1 = early_launch_runs(early_hint().load(), capQ, plan.pose_known || plan.tau_on);
+        int rc = run_binning(s, plan.cut ? nQ1 : capQ, plan.cut ? scalars + SC_EARLY_COUNTS : scalars, plan.cut ? 1 : 0, nullptr, late && !rb_flag);
+        flag_alias = nullptr;                    // (a repeated emission reads its counts back the ordinary way)
+        if (rc == GSRAST_OK) rc = blend(s, at<uint32_t>(bin, 0), true, plan.cut ? 1 : 0, nullptr);
+        return rc;
     }
-    { int rc = rb_flag ? read_flag_finish(rb_flag, scalars, s, counts, 12) : read_u32_finish(rb, scalars, s, counts, 12); if (rc != GSRAST_OK) return rc; }
-    // equalised depth buckets: the MIDDLE of the next forward's histogram (448-895 bins) covers this one's occupied key range, padded by
-    // an eighth on either side (the tails beyond take a view a whole range away); it widens at once and narrows slowly (consecutive
-    // forwards render different views).  Returns whether this call's table was a learned one that held every key.
-    auto learn_depth_range = [&](uint32_t zb) -> bool { return ctx->zrange.learn(zb, zh_klo, zh_shift); };      // (gsrast_policy.h: DepthRange)
-    bool sort_redone = false;
-    if (!bucket_sort && o.depth_sort == 0) dec_to_zero(ctx->bucket_skip);
-    if (bucket_sort) {
-        if (counts[11] == 0 && ctx->bucket_clean.load() < 1024 && ++ctx->bucket_clean >= 64) ctx->bucket_backoff = 0;      // the scene changed: forget
-        if (counts[11] != 0) {
-            const int clean_before = ctx->bucket_clean.exchange(0);      // more Gaussians at (nearly) one depth than a bucket holds: sort
-            ctx->redo_count++;      // again with the radix passes (everything enqueued so far used a wrong order, as below)
-            // An ISOLATED overflow (32 clean forwards before it: one pose of a cycle whose depth profile has a hard edge inside a
-            // histogram bin, which doubles a few buckets' share and now and then tips one over) costs this one repeat and nothing
-            // else.  Overflows in quick succession start with the radix passes for a while -- exponential back-off: 16 radix forwards,
-            // twice as many after each further one (a scene whose depths pile up for good pays the discarded speculative launch ever
-            // more rarely), capped at 4096 --
-            // ... unless the histogram behind the bucket map was not up to this view (a context's first forward: four bins per octave;
-            // a depth range that has moved out of the table): the range is learned from this call, the next forward tries again at once
-            if (learn_depth_range(counts[SC_ZBINS]) && (clean_before < 32 || ctx->bucket_backoff.load() > 0))
-            { const int prev = ctx->bucket_backoff.load(); const int next = prev <= 0 ? 16 : (prev >= 2048 ? 4096 : prev * 2);
-              ctx->bucket_backoff = next; ctx->bucket_skip = next; }
-            ctx->depth_short = 0;   // the radix path's pass-count hint is stale (not refreshed on the bucket path): assume four passes
-            int rc = sort_and_scan(false, false);
-            if (rc == GSRAST_OK) rc = read_u32(scalars, s, counts, 12);
-            if (rc != GSRAST_OK) return rc;
-            sort_redone = true;
-            if (adaptive_sort) ctx->depth_short = counts[8] <= 24u ? 1 : 0;
-        }
-    } else if (adaptive_sort) {
-        if (assume_short && counts[10] != 0) {      // the scene's depth range widened: sort again with all four passes, then as after
-            ctx->redo_count++;                      // an undersized speculative launch (everything enqueued so far used a wrong order)
-            int rc = sort_and_scan(false, false);
-            if (rc == GSRAST_OK) rc = read_u32(scalars, s, counts, 12);
-            if (rc != GSRAST_OK) return rc;
-            sort_redone = true;
-        }
-        ctx->depth_short = counts[8] <= 24u ? 1 : 0;
+    // (a forward under predicted cut depths keeps two or three times the early set of one under remembered ones: each kind is sized by its own history)
+    std::atomic<uint32_t>& early_hint() const { return (plan.tau_on && (plan.tau_forced || !plan.pose_known || !hints)) ? ctx->Qe_hint_tau : ctx->Qe_hint; }
+
+    int sort_again(hipStream_t s)      // with all four radix passes; everything enqueued so far used a wrong order, as after an undersized speculative launch
+    {
+        ctx->redo_count++;
+        int rc = sort_and_scan(s, false, false);
+        if (rc == GSRAST_OK) rc = read_u32(scalars, s, counts, 12);
+        sort_redone = true;
+        return rc;
     }
-    if (runbin && counts[3] != 0) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
-    auto t2 = std::chrono::steady_clock::now();
-    if (trace) fprintf(stderr, "[gsrast] alloc(spec) %.1f us, readback wait %.1f us, cap %u R %u Q %u%s | cut %d (pays %d: last_Q %u pause %d) late %u Q_early %u nQ1 %u capQ %u bucket_sort %d (over %u) hints %d zh %08x >> %d bins %u-%u\n",
-                       std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(), cap, counts[0], counts[1],
-                       speculative ? " (speculative)" : "", (int)cut, (int)cut_pays, ctx->last_Q.load(), pol.pause.load(), counts[SC_N_LATE], counts[SC_Q_EARLY], nQ1, capQ,
-                       (int)bucket_sort, counts[11], hints ? 1 : 0, zh_klo, zh_shift, counts[SC_ZBINS] & 0xFFFFu, counts[SC_ZBINS] >> 16);
-    if (counts[0] > 0x7FFFFFFFu) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
-    const uint32_t R = counts[0], Q = counts[1];
-    if (bucket_sort && !sort_redone) (void)learn_depth_range(counts[SC_ZBINS]);
-    // capacity hints decay slowly: consecutive calls render different views, a buffer sized for the largest recent one
-    // keeps the speculative launch valid
-    ctx->R_hint = follow_hint(ctx->R_hint.load(), R, 4); ctx->Q_hint = follow_hint(ctx->Q_hint.load(), Q, 4);
-    ctx->last_R = R; ctx->last_Q = Q;
-    ctx->last_late = cut ? counts[SC_N_LATE] : 0u; ctx->last_Qe = cut ? counts[SC_Q_EARLY] : counts[1];
-    // (a cut forward that removed too little to pay for itself; round 5: FOUR in a row before the context sits out)
-    if (cut) pol.forward_counts(tau_on, counts[SC_N_LATE], counts[1], counts[SC_Q_EARLY], (uint32_t)P, g_list_cut_always.load() != 0);
-    if (cut && speculative && !sort_redone) {
-        std::atomic<uint32_t>& hint = (tau_on && (tau_forced || !pose_known || !hints)) ? ctx->Qe_hint_tau : ctx->Qe_hint;
-        hint = follow_hint(hint.load(), counts[SC_Q_EARLY], 5); }
-    // fallbacks of this thread's earlier cut forwards, as the device reported them (everything enqueued before this forward's counts has run)
-    // (a completion pass over a few tiles is cheap and expected; its cost grows with the tiles it lists again: one over an eighth of
-    // the image counts like rounds 3's whole second forward, smaller ones in proportion)
-    if (const uint32_t q2 = take_fallback_event()) {       // (the column runs of the pass's candidates)
-        const int before = pol.fb_score.load();
-        const int pts = pol.completion_pass(q2, ctx->last_Q.load(), (uint32_t)P, g_list_cut_always.load() != 0, tau_mode);
-        if (trace) fprintf(stderr, "[gsrast] completion pass reported: %u column runs of %u, %d points on a score of %d; margin %d / 4, tau_req %d, pause %d\n", q2, ctx->last_Q.load(), pts, before,
-                           pol.margin.load(), pol.tau_req.load(), pol.pause.load());
-    } else if (cut && counts[SC_N_LATE] != 0u) pol.clean_cut_forward();
-    const bool early_fits = !cut || counts[SC_Q_EARLY] <= nQ1;
-    if (speculative && !sort_redone && R <= cap && Q <= capQ && early_fits) {          // everything is already in flight
-        if (cut && counts[SC_N_LATE] != 0u) {
-            // List cut: the lists in flight hold the early Gaussians only.  The blend verifies them; behind it, the whole binning and
-            // blend over ALL Gaussians, predicated on its verdict (gsrast_common.h).  Nothing of this runs in the steady state.
-            // the pass on its own stream behind a gate (ChainGate above), unless that cannot be had
-            const hipStream_t s_caller = s;
-            if (gate) {      // (claimed with the blend's launch: its last workgroup has copied the verdict and, if there is nothing to do, released us)
-                GS_HIP(hipEventRecord(gate->ev, s));
-                GS_HIP(hipStreamWaitEvent(gate->stream, gate->ev, 0));
-                redo_pred = gpred;
-                s = gate->stream;                  // (the lambdas below launch on `s`)
+    // ---- the counts arrive; what they say about the depth sort: the histogram's range, the bucket sort's back-off, a sort to be repeated ----
+    int absorb_depth_sort(hipStream_t s)
+    {
+        { int rc = rb_flag ? read_flag_finish(rb_flag, scalars, s, counts, 12) : read_u32_finish(rb, scalars, s, counts, 12); if (rc != GSRAST_OK) return rc; }
+        if (!plan.bucket_sort && o.depth_sort == 0) dec_to_zero(ctx->bucket_skip);
+        if (plan.bucket_sort) {
+            if (counts[11] == 0 && ctx->bucket_clean.load() < 1024 && ++ctx->bucket_clean >= 64) ctx->bucket_backoff = 0;      // the scene changed: forget
+            if (counts[11] != 0) {      // more Gaussians at (nearly) one depth than a bucket holds: sort again with the radix passes
+                const int clean_before = ctx->bucket_clean.exchange(0);
+                // An ISOLATED overflow (32 clean forwards before it: one pose of a cycle whose depth profile has a hard edge inside a
+                // histogram bin, which doubles a few buckets' share and now and then tips one over) costs this one repeat and nothing
+                // else.  Overflows in quick succession start with the radix passes for a while -- exponential back-off: 16 radix forwards,
+                // twice as many after each further one (a scene whose depths pile up for good pays the discarded speculative launch ever
+                // more rarely), capped at 4096 --
+                // ... unless the histogram behind the bucket map was not up to this view (a context's first forward: four bins per octave;
+                // a depth range that has moved out of the table): the range is learned from this call, the next forward tries again at once
+                if (ctx->zrange.learn(counts[SC_ZBINS], zh_klo, zh_shift) && (clean_before < 32 || ctx->bucket_backoff.load() > 0))
+                { const int prev = ctx->bucket_backoff.load(); const int next = prev <= 0 ? 16 : (prev >= 2048 ? 4096 : prev * 2);
+                  ctx->bucket_backoff = next; ctx->bucket_skip = next; }
+                ctx->depth_short = 0;   // the radix path's pass-count hint is stale (not refreshed on the bucket path): assume four passes
+                int rc = sort_again(s); if (rc != GSRAST_OK) return rc;
+                if (plan.adaptive_sort) ctx->depth_short = counts[8] <= 24u ? 1 : 0;
             }
-            struct Back { hipStream_t& s; hipStream_t v; const uint32_t*& p; const uint32_t* pv; ~Back() { s = v; p = pv; } } back{ s, s_caller, redo_pred, scalars + SC_REDO_PRED };
-            ProfScope ps(K_CUT_REDO, s);           // (on the stream the pass runs on: its events bracket the chain, not an empty interval of the caller's stream)
-            struct Off { Off() { t_prof_off++; } ~Off() { t_prof_off--; } } off;
-            // (round 4: a COMPLETION pass, not a second forward: the Gaussians that touch a flagged tile -- the candidates --, their
-            // missing colours, their column runs through flagged tiles, and the flagged tiles' blend from their full lists)
-            cut_candidates_kernel<<<std::min((P + 255) / 256, 2048), 256, 0, s>>>((uint32_t)P, tiles, rect, at<unsigned char>(img, IL.tile_flags), T, (uint32_t)cam.gx,
-                                                                                at<unsigned long long>(geom, GL.color_skip), at<unsigned long long>(geom, GL.cand_bits),
-                                                                                at<unsigned long long>(geom, GL.skip2), redo_pred);
-            GS_LAUNCHED("cut_candidates");
-            int rc = cut_colors ? color_kernels(s, true, redo_pred) : GSRAST_OK;      // (the late candidates' colours)
-            if (rc == GSRAST_OK) rc = launch_run_binning(bin, cap, capQ, capQ, scalars + SC_PASS2, nullptr, 2);
-            if (rc == GSRAST_OK) rc = launch_blend(at<uint32_t>(bin, 0), true, 2);
-            if (gate) {
-                // (also after an error above: the caller's stream must not wait for a release nobody sends)
-                chain_done_kernel<<<1, 1, 0, gate->stream>>>(redo_pred, gdone, gseq);
-                const hipError_t e1 = hipGetLastError();
-                {   std::lock_guard<std::mutex> lk(ctx->mu);      // the chain's tail: whoever wants this slot's successor asks this event
-                    if (hipEventRecord(gate->tail[gseq % GATE_RING], gate->stream) == hipSuccess) gate->tail_seq[gseq % GATE_RING] = gseq; }
-                const hipError_t e2 = hipStreamWaitValue32(s_caller, gdone, gseq, hipStreamWaitValueEq, 0xFFFFFFFFu);
-                if (e1 != hipSuccess || e2 != hipSuccess) {     // no gate after all: an ordinary join behind the chain, and never again
-                    { std::lock_guard<std::mutex> lk(ctx->mu); gate->failed = true; }
-                    (void)hipEventRecord(gate->ev, gate->stream);
-                    (void)hipStreamWaitEvent(s_caller, gate->ev, 0);
-                }
-            }
-            if (rc != GSRAST_OK) return rc;
+        } else if (plan.adaptive_sort) {
+            if (plan.assume_short && counts[10] != 0) { int rc = sort_again(s); if (rc != GSRAST_OK) return rc; }      // the scene's depth range widened
+            ctx->depth_short = counts[8] <= 24u ? 1 : 0;
         }
-        { int rc = finish_records(); if (rc != GSRAST_OK) return rc; }
+        if (plan.runbin && counts[3] != 0) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
+        return GSRAST_OK;
+    }
+    // ---- what the counts teach the context: capacity hints, the early set's size, the cut's policy (gsrast_policy.h) ----
+    int absorb_counts()
+    {
+        const auto t2 = std::chrono::steady_clock::now();
+        CutPolicy& pol = ctx->pol;
+        if (trace_on()) fprintf(stderr, "[gsrast] alloc(spec) %.1f us, readback wait %.1f us, cap %u R %u Q %u%s | cut %d (pays %d: last_Q %u pause %d) late %u Q_early %u nQ1 %u capQ %u bucket_sort %d (over %u) hints %d zh %08x >> %d bins %u-%u\n",
+                               std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(), cap, counts[0], counts[1],
+                               plan.speculative ? " (speculative)" : "", (int)plan.cut, (int)plan.cut_pays, ctx->last_Q.load(), pol.pause.load(), counts[SC_N_LATE], counts[SC_Q_EARLY], nQ1, capQ,
+                               (int)plan.bucket_sort, counts[11], hints ? 1 : 0, zh_klo, zh_shift, counts[SC_ZBINS] & 0xFFFFu, counts[SC_ZBINS] >> 16);
+        if (counts[0] > 0x7FFFFFFFu) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
+        const uint32_t R = counts[0], Q = counts[1];
+        if (plan.bucket_sort && !sort_redone) (void)ctx->zrange.learn(counts[SC_ZBINS], zh_klo, zh_shift);
+        // capacity hints decay slowly: consecutive calls render different views, a buffer sized for the largest recent one
+        // keeps the speculative launch valid
+        ctx->R_hint = follow_hint(ctx->R_hint.load(), R, 4); ctx->Q_hint = follow_hint(ctx->Q_hint.load(), Q, 4);
+        ctx->last_R = R; ctx->last_Q = Q;
+        ctx->last_late = plan.cut ? counts[SC_N_LATE] : 0u; ctx->last_Qe = plan.cut ? counts[SC_Q_EARLY] : counts[1];
+        // (a cut forward that removed too little to pay for itself; round 5: FOUR in a row before the context sits out)
+        if (plan.cut) pol.forward_counts(plan.tau_on, counts[SC_N_LATE], counts[1], counts[SC_Q_EARLY], (uint32_t)P, plan.list_cut_always);
+        if (plan.cut && plan.speculative && !sort_redone) { std::atomic<uint32_t>& hint = early_hint(); hint = follow_hint(hint.load(), counts[SC_Q_EARLY], 5); }
+        // fallbacks of this thread's earlier cut forwards, as the device reported them (everything enqueued before this forward's counts has run)
+        // (a completion pass over a few tiles is cheap and expected; its cost grows with the tiles it lists again: one over an eighth of
+        // the image counts like rounds 3's whole second forward, smaller ones in proportion)
+        if (const uint32_t q2 = take_fallback_event()) {       // (the column runs of the pass's candidates)
+            const int before = pol.fb_score.load();
+            const int pts = pol.completion_pass(q2, ctx->last_Q.load(), (uint32_t)P, plan.list_cut_always, plan.tau_mode);
+            if (trace_on()) fprintf(stderr, "[gsrast] completion pass reported: %u column runs of %u, %d points on a score of %d; margin %d / 4, tau_req %d, pause %d\n", q2, ctx->last_Q.load(), pts, before,
+                                   pol.margin.load(), pol.tau_req.load(), pol.pause.load());
+        } else if (plan.cut && counts[SC_N_LATE] != 0u) pol.clean_cut_forward();
+        return GSRAST_OK;
+    }
+
+    // ---- List cut: the lists in flight hold the early Gaussians only.  The blend verified them; behind it, a COMPLETION pass (round 4), every
+    // kernel predicated on the blend's verdict (gsrast_common.h): the Gaussians that touch a flagged tile -- the candidates --, their missing
+    // colours, their column runs through flagged tiles, and the flagged tiles' blend from their full lists.  Nothing of this runs in the
+    // steady state.  The pass runs on its own stream behind a gate (ChainGate above), unless that cannot be had: then on the caller's. ----
+    int completion_pass(hipStream_t s_caller)
+    {
+        if (gate) {      // (claimed with the blend's launch: its last workgroup has copied the verdict and, if there is nothing to do, released us)
+            GS_HIP(hipEventRecord(gate->ev, s_caller));
+            GS_HIP(hipStreamWaitEvent(gate->stream, gate->ev, 0));
+        }
+        const hipStream_t s = gate ? gate->stream : s_caller;
+        const uint32_t* const pred = gate ? gpred : scalars + SC_REDO_PRED;      // (the gate's copy of the predicate: the forward's buffers may be gone when the chain's no-ops run)
+        ProfScope ps(K_CUT_REDO, s);           // (on the stream the pass runs on: its events bracket the chain, not an empty interval of the caller's stream)
+        struct Off { Off() { t_prof_off++; } ~Off() { t_prof_off--; } } off;
+        cut_candidates_kernel<<<std::min((P + 255) / 256, 2048), 256, 0, s>>>((uint32_t)P, tiles, rect, tile_flags, T, (uint32_t)cam.gx, color_skip, cand_bits, at<unsigned long long>(geom, GL.skip2), pred);
+        int rc = post_launch("cut_candidates", s);
+        if (rc == GSRAST_OK && plan.cut_colors) rc = color_kernels(s, true, pred);      // (the late candidates' colours)
+        if (rc == GSRAST_OK) rc = run_binning(s, capQ, scalars + SC_PASS2, 2, pred, false);
+        if (rc == GSRAST_OK) rc = blend(s, at<uint32_t>(bin, 0), true, 2, pred);
+        if (gate) {
+            // (also after an error above: the caller's stream must not wait for a release nobody sends)
+            chain_done_kernel<<<1, 1, 0, gate->stream>>>(pred, gdone, gseq);
+            const hipError_t e1 = hipGetLastError();
+            {   std::lock_guard<std::mutex> lk(ctx->mu);      // the chain's tail: whoever wants this slot's successor asks this event
+                if (hipEventRecord(gate->tail[gseq % GATE_RING], gate->stream) == hipSuccess) gate->tail_seq[gseq % GATE_RING] = gseq; }
+            const hipError_t e2 = hipStreamWaitValue32(s_caller, gdone, gseq, hipStreamWaitValueEq, 0xFFFFFFFFu);
+            if (e1 != hipSuccess || e2 != hipSuccess) {     // no gate after all: an ordinary join behind the chain, and never again
+                { std::lock_guard<std::mutex> lk(ctx->mu); gate->failed = true; }
+                (void)hipEventRecord(gate->ev, gate->stream);
+                (void)hipStreamWaitEvent(s_caller, gate->ev, 0);
+            }
+        }
+        return rc;
+    }
+    // ---- the end of every successful forward: the consumed Gaussians' gradient records, the prefilter promise's verdict ----
+    int finish(hipStream_t s, uint32_t R)
+    {
+        if (plan.zero_touched) {
+            ProfScope ps(K_GREC_ZERO, s);
+            grec_zero_touched_kernel<<<(unsigned)(((size_t)P + 256 * GZ_PER - 1) / (256 * GZ_PER)), 256, 0, s>>>(P, untouched, grec, scalars);
+            GS_LAUNCHED("grec_zero_touched");
+        }
         if (prefilter_word) { int rc = prefilter_verdict(prefilter_word, s); if (rc != GSRAST_OK) return rc; }
         return (int)R;
     }
-    if (speculative && !sort_redone) ctx->redo_count++;
-    if (cut) GS_HIP(hipMemsetAsync(scalars + SC_N_LATE, 0, sizeof(uint32_t), s));      // (the backward must not take a late Gaussian's rows for zero: below it is listed)
-    if (cut_colors && color_launched) {     // everything from here on lists ALL Gaussians: the colours the list cut left out are evaluated now
-        if (side) GS_HIP(hipStreamWaitEvent(s, side->join, 0));
-        int rc = color_kernels(s, false, nullptr);
-        if (rc != GSRAST_OK) return rc;
-    }
-    if (speculative)    // redo: the truncated pass already appended every tile to the work buckets once
-        GS_HIP(hipMemsetAsync(at<uint32_t>(img, IL.bucket_cnt), 0, (XCD_GROUPS + 1) * WORK_BUCKETS * sizeof(uint32_t), s));
-    if (!bin || R > cap || Q > capQ) {   // first call, or the scene grew by more than 25 %: ask again (the callback's last answer counts)
-        cap = R; capQ = Q;
-        bin = (char*)binning_alloc(binning_ctx, bin_bytes(cap, capQ));
-        if (!bin) return fail(GSRAST_E_ALLOC, "forward: binning allocation failed");
-    }
-    // The layout inside the buffer follows its CAPACITY; the sorted Gaussian ids (point_list) always end in the
-    // array at offset 0, whatever the capacity, the pass count and the binning scheme -- all the backward needs.
-    const uint32_t* plist = at<uint32_t>(bin, 0);
-    if (runbin && (R == 0 || Q == 0)) GS_HIP(hipMemsetAsync(ranges, 0, (size_t)T * sizeof(uint2), s));
-    if (R > 0 && Q > 0 && runbin) {
-        int rc = launch_run_binning(bin, cap, capQ, Q, nullptr);
-        if (rc != GSRAST_OK) return rc;
-    } else if (R > 0 && !runbin) {
-        const BinLayout BL = bin_layout((size_t)cap);
-        uint32_t *tkA = at<uint32_t>(bin, BL.keyA), *tkB = at<uint32_t>(bin, BL.keyB);
-        uint32_t *tvA = at<uint32_t>(bin, BL.valA), *tvB = at<uint32_t>(bin, BL.valB);
-        if (tpasses & 1) { std::swap(tkA, tkB); std::swap(tvA, tvB); }   // odd pass count: start in B, finish in A
-        uint32_t* bhist = at<uint32_t>(bin, BL.hist);
-        uint32_t* bscan = at<uint32_t>(bin, BL.scan_tmp);
-        // Tile ids fit 16 bits up to 65 536 tiles (4096 x 4096 pixels): the R-sized key streams are then
-        // half as wide (the key buffers are sized for 32-bit ids either way).
-        const bool k16 = T <= 65536u;
-        int rc = GSRAST_OK;
-        if (k16) {
-            uint16_t *hA = reinterpret_cast<uint16_t*>(tkA), *hB = reinterpret_cast<uint16_t*>(tkB);
-            { ProfScope ps(K_EMIT, s);
-              emit_instances_kernel<uint16_t><<<(P + 255) / 256, 256, 0, s>>>(P, order, offsets, tiles, rect, cam.gx, hA, tvA);
-              GS_LAUNCHED("emit_instances"); }
-            { ProfScope ps(K_SORT_TILE, s); rc = radix_sort<uint16_t>(hA, tvA, hB, tvB, R, tile_bits(T), bhist, bscan, s); }
+    // ---- binning + blend with exact sizes: no speculative launch, or one whose capacities (or order) did not fit ----
+    int exact_redo(hipStream_t s, uint32_t R, uint32_t Q)
+    {
+        if (plan.speculative && !sort_redone) ctx->redo_count++;
+        if (plan.cut) GS_HIP(hipMemsetAsync(scalars + SC_N_LATE, 0, sizeof(uint32_t), s));      // (the backward must not take a late Gaussian's rows for zero: below it is listed)
+        if (plan.cut_colors && fork.launched) {     // everything from here on lists ALL Gaussians: the colours the list cut left out are evaluated now
+            if (fork.side) GS_HIP(hipStreamWaitEvent(s, fork.side->join, 0));
+            int rc = color_kernels(s, false, nullptr);
             if (rc != GSRAST_OK) return rc;
-            { ProfScope ps(K_RANGES, s);
-              tile_ranges_kernel<uint16_t><<<(R + 255) / 256, 256, 0, s>>>(R, nullptr, reinterpret_cast<const uint16_t*>(at<uint32_t>(bin, BL.keyA)), ranges);
-              GS_LAUNCHED("tile_ranges"); }
-        } else {
-            { ProfScope ps(K_EMIT, s);
-              emit_instances_kernel<uint32_t><<<(P + 255) / 256, 256, 0, s>>>(P, order, offsets, tiles, rect, cam.gx, tkA, tvA);
-              GS_LAUNCHED("emit_instances"); }
-            { ProfScope ps(K_SORT_TILE, s); rc = radix_sort<uint32_t>(tkA, tvA, tkB, tvB, R, tile_bits(T), bhist, bscan, s); }
-            if (rc != GSRAST_OK) return rc;
-            { ProfScope ps(K_RANGES, s);
-              tile_ranges_kernel<uint32_t><<<(R + 255) / 256, 256, 0, s>>>(R, nullptr, at<uint32_t>(bin, BL.keyA), ranges);
-              GS_LAUNCHED("tile_ranges"); }
         }
+        if (plan.speculative)    // redo: the truncated pass already appended every tile to the work buckets once
+            GS_HIP(hipMemsetAsync(bucket_cnt, 0, (XCD_GROUPS + 1) * WORK_BUCKETS * sizeof(uint32_t), s));
+        if (!bin || R > cap || Q > capQ) {   // first call, or the scene grew by more than 25 %: ask again (the callback's last answer counts)
+            cap = R; capQ = Q;
+            bin = (char*)c.binning_alloc(c.binning_ctx, bin_bytes());
+            if (!bin) return fail(GSRAST_E_ALLOC, "forward: binning allocation failed");
+        }
+        // The layout inside the buffer follows its CAPACITY; the sorted Gaussian ids (point_list) always end in the
+        // array at offset 0, whatever the capacity, the pass count and the binning scheme -- all the backward needs.
+        if (plan.runbin && (R == 0 || Q == 0)) GS_HIP(hipMemsetAsync(ranges, 0, (size_t)T * sizeof(uint2), s));
+        int rc = GSRAST_OK;
+        if (R > 0 && Q > 0 && plan.runbin) rc = run_binning(s, Q, nullptr, 0, nullptr, false);
+        else if (R > 0 && !plan.runbin) rc = T <= 65536u ? instance_binning<uint16_t>(s, R) : instance_binning<uint32_t>(s, R);
+        if (rc == GSRAST_OK) rc = blend(s, at<uint32_t>(bin, 0), plan.runbin && R > 0 && Q > 0, 0, nullptr);
+        return rc == GSRAST_OK ? finish(s, R) : rc;
     }
-    { int rc = launch_blend(plist, runbin && R > 0 && Q > 0); if (rc != GSRAST_OK) return rc; }
-    { int rc = finish_records(); if (rc != GSRAST_OK) return rc; }
-    if (prefilter_word) { int rc = prefilter_verdict(prefilter_word, s); if (rc != GSRAST_OK) return rc; }
-    return (int)R;
+};
+} } // namespace
+
+// The one forward.  Dense: the inputs are the activated arrays.  Raw family: means3D / opacities / scales / rotations are the model's raw
+// leaves, shs a non-null placeholder, and the per-Gaussian kernels run as their RAW instantiations.
+// checks -> plan -> preprocess -> sort -> speculative binning + blend -> read-back -> (sort redo) -> accept, completion pass, or exact redo
+static int forward_impl(gsrast_context* ctx, const gsrast_options* options, const FwdCall& c)
+{
+    const auto t_entry = std::chrono::steady_clock::now();
+    RoctxRange range_fwd(c.raw_family ? "gsrast_forward_raw" : "gsrast_forward");
+    ForwardRun r(ctx, options, c, t_entry);
+    const hipStream_t s = r.stream;
+    int rc = r.check_and_plan(s);
+    if (rc != GSRAST_OK || c.P == 0) return rc;
+    if ((rc = r.buffers(s)) != GSRAST_OK || (rc = r.begin_policy(s)) != GSRAST_OK) return rc;
+    if ((rc = r.preprocess(s)) != GSRAST_OK || (rc = r.sort_and_scan(s, r.plan.assume_short, r.plan.bucket_sort)) != GSRAST_OK) return rc;
+    r.learn_pose();
+    // Everything that does not depend on num_rendered is enqueued / prepared before the host waits: the colour kernels, beside the binning
+    if ((rc = r.speculative_buffer(s)) != GSRAST_OK || (rc = r.launch_color(s)) != GSRAST_OK || (rc = r.speculative_launch(s)) != GSRAST_OK) return rc;
+    if ((rc = r.absorb_depth_sort(s)) != GSRAST_OK || (rc = r.absorb_counts()) != GSRAST_OK) return rc;
+    const ForwardPlan& plan = r.plan;
+    const uint32_t R = r.counts[0], Q = r.counts[1];
+    const bool early_fits = !plan.cut || r.counts[SC_Q_EARLY] <= r.nQ1;
+    if (!(plan.speculative && !r.sort_redone && R <= r.cap && Q <= r.capQ && early_fits)) return r.exact_redo(s, R, Q);
+    // everything is already in flight
+    if (plan.cut && r.counts[SC_N_LATE] != 0u && (rc = r.completion_pass(s)) != GSRAST_OK) return rc;
+    return r.finish(s, R);
 }
 
 // ---- the exported forwards: adapters that fill a FwdCall (include/gsrast.h: gsrast_forward = _ex(NULL, NULL) = _flags(0), _aux = _flags(AUX)) ----
@@ -2253,7 +2262,7 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
     if (c.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return fail(GSRAST_E_ARG, "flags: unknown bits");
     gsrast_options o = options ? *options : snapshot_defaults();
     if (!options_valid(o)) return fail(GSRAST_E_ARG, "backward: bad option value");
-    if (aux_flag && o.cull == 0) return fail(GSRAST_E_ARG, "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
+    if (aux_flag && !culled_blend(o, true)) return fail(GSRAST_E_ARG, "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
     const gsrast_raw_inputs* const rawin = c.raw_family ? c.raw : nullptr;
     RawArgs raw{}; RawGrads rawg{};
     if (c.raw_family) {

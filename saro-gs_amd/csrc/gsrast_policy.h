@@ -1,12 +1,13 @@
 // gsrast_policy.h -- the HOST-side decisions of the forward, free of any HIP call: when the list cut is applied, paused and widened, how
-// the speculative launch is sized, how the depth histogram's range follows the scene.  gsrast_capi.hip enqueues; this file decides.
-// Everything here runs on a CPU box: tests/test_policy.py drives it through gsrast_policy_event() (include/gsrast.h) on a context that
-// never touches a device.  No result of a call depends on any of it -- only how much work the call enqueues.
+// the speculative launch is sized, how the depth histogram's range follows the scene, which path a call takes (ForwardPlan).  gsrast_capi.hip
+// enqueues; this file decides.  Everything here runs on a CPU box: tests/test_policy.py drives it through gsrast_policy_event() and
+// gsrast_debug_forward_plan() (include/gsrast.h) on a context that never touches a device.  No result of a call depends on any of it -- only how much work the call enqueues.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
 #include <atomic>
-#include "gsrast_common.h"      // (the depth histogram's bin geometry: ZH_*, zh_bin_start)
+#include "../../include/gsrast.h"   // (gsrast_options, GSRAST_RENDER_*)
+#include "gsrast_common.h"     // (the depth histogram's bin geometry: ZH_*, zh_bin_start)
 
 namespace gsrast {
 
@@ -15,7 +16,7 @@ inline void dec_to_zero(std::atomic<int>& a) { int v = a.load(); while (v > 0 &&
 
 // ---- the list cut's policy (gsrast_common.h: LIST CUT, PREDICTED CUT) ----------------------------------------------------------------
 // The cut costs ~80 us per forward (the late test in the scatter, the compacting colour kernel, the predicated launches behind the blend)
-// and saves ~50 us per million column runs it removes.
+// and saves ~50 us per million column runs it removes (measured with the cut forced on: 1 M-Gaussian shell -7 %, 0.3 M cube -3 %, 0.1 M cube -8 %; 1 M cube +8 %, 3 M cube +16 %).
 struct CutPolicy {
     static constexpr uint32_t MIN_RUNS = 1500000u;     // it is applied when the context's last forward had at least this many column runs
     static constexpr int PAUSE = 64;                   // forwards a context sits out after SMALL_STREAK cut forwards that removed fewer than MIN_RUNS
@@ -150,6 +151,76 @@ inline uint32_t early_launch_runs(uint32_t qe_hint, uint32_t capQ, bool early_se
 {
     if (!qe_hint || !early_set_expected) return capQ;
     return (uint32_t)std::min<uint64_t>(capQ, (uint64_t)qe_hint + qe_hint / 2 + 4096);
+}
+
+// ---- the forward's plan ----------------------------------------------------------------------------------------------------------------
+// Every decision of a forward call that follows from its options, flags and shape, the context's remembered words and the process-wide
+// switches: made ONCE, at the top of the call, from one snapshot of them (plan_forward).  What needs an answer from the policy or the device
+// is a second-phase field, written by the one *_answer function below.  tests/test_policy.py reads the plan through gsrast_debug_forward_plan.
+inline bool options_valid(const gsrast_options& o)
+{
+    auto ppl_ok = [](int v) { return v == 0 || v == 1 || v == 2 || v == 4; };
+    return o.exp_mode >= 0 && o.exp_mode <= 2 && (o.binning == 0 || o.binning == 1) && ppl_ok(o.fwd_pixels_per_lane) && ppl_ok(o.bwd_pixels_per_lane) &&
+           o.backward_phase >= 0 && o.backward_phase <= 2 && (o.depth_sort == 0 || o.depth_sort == 1) && (o.dense_backward == 0 || o.dense_backward == 1);
+}
+// "the culled blend kernel runs".  Forward: a forced pixels-per-lane selects the un-culled template; backward: it picks among the culled ones.
+inline bool culled_blend(const gsrast_options& o, bool backward) { return o.cull != 0 && (backward || o.fwd_pixels_per_lane == 0); }
+struct PlanSwitches { bool list_cut_always, tau_cut, touch_bits, sparse_grec, two_level, chain_gate, sort_hint, debug_state; int two_level_min_p, tau_sample; };   // the g_* A/B switches, read once per call
+struct PlanInputs { unsigned flags; int P, W, H, D; bool sh, colors_precomp; int bucket_skip; uint32_t R_hint, last_Q; bool depth_short; };      // the call's shape; the context's words
+struct ForwardPlan {
+    const char* refusal = nullptr;      // GSRAST_E_ARG with this text: unknown flags, a bad option value, aux without the culled kernel (in this order)
+    bool aux = false, aa = false;
+    bool runbin = false, buckets_ok = false;          // run-compressed binning (one 8-bit pass over tile rows, 16-bit tile ids); the blends' launch order from work buckets (u16 tile ids)
+    bool bucket_sort = false, two_level = false;      // depth order by the bucket sort (else radix); its scatter as two launches, coarse + refine
+    bool culled = false, ordered = false;             // the culled blend kernel runs; ... heaviest tiles first
+    bool want_hints = false, cut_base = false;        // the context's launch-order hints are asked for; list cut: everything it needs but the policy's and the pose table's answer
+    bool tau_mode = false;                            // predicted cut depths for a pose without remembered ones
+    bool zero_in_blend = false, zero_touched = false; // the gradient records are zeroed inside the blend / only the consumed Gaussians', behind it
+    bool keep_untouched = false, clip = false, want_shd = false;      // GeomLayout::untouched is kept for the backward; clipped tile rectangles; d(colour)/d(view direction) stored
+    bool spec_eligible = false;                       // binning + blend may be enqueued before the counts are known
+    bool adaptive_sort = false, assume_short = false; // the radix depth sort adapts its pass count on the device; three passes are enqueued
+    bool list_cut_always = false, chain_gate = false, debug_state = false; uint32_t tau_sample_mask = 0, T = 0, R_hint = 0, last_Q = 0; int cut_cs = 0;
+    // second phase: the policy's answer; prediction; the device's word on the pose (only the early Gaussians' colours are evaluated); the binning buffer
+    bool cut_pays = false, cut = false, tau_forced = false, tau_on = false, pose_known = true, cut_colors = false, speculative = false;
+    void policy_answer(bool pays, bool hints_acquired) { cut_pays = pays; cut = cut_base && pays && (hints_acquired || tau_mode); }
+    void prediction_answer(bool forced, bool pose_expected) { tau_forced = forced; tau_on = cut && tau_mode && !pose_expected; }
+    // (a pose without a slot has no cut depths: unless predicted ones stand in, every visible Gaussian is early and the plain colour kernel
+    // evaluates them; not under debug_state: gsrast_debug_export shows every Gaussian's colour)
+    void pose_answer(bool known) { pose_known = known; cut_colors = cut && zero_in_blend && !debug_state && (known || tau_on); }
+    void binning_answer(bool have_buffer) { speculative = spec_eligible && have_buffer; }
+};
+inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, const PlanSwitches& g)
+{
+    ForwardPlan p;
+    p.aux = (in.flags & GSRAST_RENDER_AUX) != 0; p.aa = (in.flags & GSRAST_RENDER_ANTIALIAS) != 0;
+    p.culled = culled_blend(o, false);
+    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) p.refusal = "flags: unknown bits";
+    else if (!options_valid(o)) p.refusal = "forward: bad option value";
+    else if (p.aux && !p.culled) p.refusal = "forward: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)";
+    if (p.refusal || in.P <= 0 || in.W <= 0 || in.H <= 0) return p;      // (the shape is refused, or nothing is rendered)
+    p.list_cut_always = g.list_cut_always; p.tau_mode = g.tau_cut; p.chain_gate = g.chain_gate; p.debug_state = g.debug_state;
+    p.tau_sample_mask = (1u << g.tau_sample) - 1u; p.R_hint = in.R_hint; p.last_Q = in.last_Q;
+    const size_t P = (size_t)in.P, gx = ((size_t)in.W + TILE_X - 1) / TILE_X, gy = ((size_t)in.H + TILE_Y - 1) / TILE_Y;
+    p.T = (uint32_t)gx * (uint32_t)gy;
+    p.runbin = o.binning == 0 && gy <= 256 && p.T <= 65536u;
+    p.buckets_ok = p.T <= BUCKET_MAX_TILES;
+    p.bucket_sort = p.runbin && o.depth_sort == 0 && P >= BUCKET_SORT_MIN_P && in.bucket_skip == 0;
+    p.two_level = p.bucket_sort && g.two_level && P >= (size_t)g.two_level_min_p;
+    p.ordered = p.culled && o.lpt != 0;
+    const bool bucket_order = p.runbin && p.buckets_ok && p.ordered;
+    p.want_hints = bucket_order && !o.no_order_hint;
+    // (the cut lists are blended by the speculative launch: a capacity hint is needed; the verified fallback is enqueued behind it)
+    p.cut_cs = cut_cell_shift(gx, gy);
+    p.cut_base = bucket_order && p.bucket_sort && o.tile_clip != 0 && !o.no_list_cut && p.cut_cs != 0 && o.speculative != 0 && in.R_hint != 0;
+    p.zero_in_blend = p.culled && P * 4 <= 0xFFFFFFFFull;
+    p.keep_untouched = p.culled && !o.forward_only && g.touch_bits;      // ... unless no backward will follow
+    p.zero_touched = p.keep_untouched && p.zero_in_blend && g.sparse_grec;
+    p.clip = p.runbin && o.tile_clip != 0;
+    p.want_shd = in.sh && !in.colors_precomp && in.D > 0 && !o.forward_only;
+    p.spec_eligible = p.runbin && o.speculative != 0;
+    p.adaptive_sort = rs_blocks_n(P, GSRAST_DEPTH_ITEMS) > RS_SELF_SCAN_BLOCKS;      // see radix_sort
+    p.assume_short = p.adaptive_sort && g.sort_hint && in.depth_short;
+    return p;
 }
 
 }  // namespace gsrast

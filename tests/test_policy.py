@@ -187,3 +187,120 @@ def test_depth_range_widens_at_once_and_narrows_slowly(ctx):
         assert now <= prev
         prev = now
     assert prev < wide // 4
+
+
+# ---- the forward's plan (gsrast_policy.h: ForwardPlan) through gsrast_debug_forward_plan: what a forward WOULD decide, no device involved ----
+(RUNBIN, BUCKETS, BUCKET_SORT, TWO_LEVEL, CULLED, ORDERED, HINTS, CUT_BASE, TAU_MODE, ZERO_IN_BLEND, ZERO_TOUCHED, UNTOUCHED, CLIP, SH_DERIVS,
+ SPECULATIVE, ADAPTIVE, ASSUME_SHORT, PAYS, CUT) = (1 << k for k in range(19))
+AUX = 1
+
+
+@pytest.fixture()
+def plan(rast, ctx):
+    import ctypes as C
+    L = rast._C.lib()
+    fn = C.CDLL(rast._C.LIB_PATH).gsrast_debug_forward_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    switched = {}
+
+    def run(P=3_000_000, W=1920, H=1080, flags=0, bucket_skip=0, R_hint=9_000_000, last_Q=Q, depth_short=0, sh=1, precomp=0, D=3, table=1, switches=None, **opts):
+        for name, v in (switches or {}).items():
+            switched.setdefault(name, L.gsrast_get_option(name.encode()))
+            assert L.gsrast_set_option(name.encode(), v) == 0
+        o = rast._C.OptionsStruct()
+        L.gsrast_options_init(C.byref(o))
+        for k, v in opts.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        words = (C.c_int * 6)(bucket_skip, R_hint, last_Q, depth_short, sh | precomp << 1 | D << 4, table)
+        try:
+            return fn(ctx.handle, C.byref(o), flags, P, W, H, words)
+        finally:
+            for name, v in switched.items():
+                L.gsrast_set_option(name.encode(), v)
+    run.error = lambda: L.gsrast_last_error().decode()
+    return run
+
+
+def test_plan_of_the_default_path(plan):
+    v = plan()
+    want = (RUNBIN | BUCKETS | BUCKET_SORT | TWO_LEVEL | CULLED | ORDERED | HINTS | CUT_BASE | TAU_MODE | ZERO_IN_BLEND | ZERO_TOUCHED | UNTOUCHED | CLIP
+            | SH_DERIVS | SPECULATIVE | ADAPTIVE | PAYS | CUT)
+    assert v == want, bin(v ^ want)
+
+
+@pytest.mark.parametrize("opt", [dict(fwd_pixels_per_lane=2), dict(cull=0), dict(lpt=0)])
+def test_plan_without_the_ordered_culled_kernel_has_no_hints_and_no_cut(plan, opt):
+    v = plan(**opt)
+    assert not v & (HINTS | CUT_BASE | CUT | ORDERED)
+    if "lpt" in opt:      # the culled kernel still runs, in tile order: it zeroes the records and keeps the bits
+        assert v & CULLED and v & ZERO_IN_BLEND and v & UNTOUCHED
+    else:
+        assert not v & (CULLED | ZERO_IN_BLEND | ZERO_TOUCHED | UNTOUCHED)
+    assert v & RUNBIN and v & BUCKET_SORT and v & SPECULATIVE
+
+
+@pytest.mark.parametrize("kw", [dict(binning=1), dict(W=1920, H=16 * 257), dict(W=16 * 300, H=16 * 256)])
+def test_plan_without_run_compressed_binning(plan, kw):
+    v = plan(**kw)      # binning = 1; more than 256 tile rows; more than 65536 tiles
+    assert not v & (RUNBIN | BUCKET_SORT | TWO_LEVEL | HINTS | CUT_BASE | CUT | CLIP | SPECULATIVE)
+    assert v & CULLED and v & ZERO_IN_BLEND
+    assert bool(v & BUCKETS) == (kw.get("W", 1920) // 16 * (kw.get("H", 1080) // 16) <= 65535)
+
+
+def test_plan_depth_sort_selection(plan):
+    assert plan() & BUCKET_SORT
+    for kw in (dict(depth_sort=1), dict(bucket_skip=3), dict(P=32767)):      # the caller, a recent overflow, a small scene: radix
+        v = plan(**kw)
+        assert not v & (BUCKET_SORT | TWO_LEVEL | CUT_BASE | CUT) and v & RUNBIN and v & HINTS, kw
+    assert plan(P=32768) & BUCKET_SORT
+    # the scatter as two launches from two_level_min_p Gaussians on, unless switched off
+    assert not plan(P=2_499_999) & TWO_LEVEL and plan(P=2_500_000) & TWO_LEVEL
+    assert not plan(switches=dict(two_level=0)) & TWO_LEVEL
+    assert plan(P=100_000, switches=dict(two_level_min_p=100_000)) & TWO_LEVEL
+    # the radix sort adapts its pass count above 64 blocks of 2048; three passes are assumed after a forward with short keys
+    assert not plan(P=64 * 2048) & ADAPTIVE and plan(P=64 * 2048 + 1) & ADAPTIVE
+    assert plan(depth_short=1) & ASSUME_SHORT and not plan(depth_short=1, P=100_000) & ASSUME_SHORT
+    assert not plan(depth_short=1, switches=dict(sort_hint=0)) & ASSUME_SHORT
+
+
+def test_plan_list_cut_conditions(plan, ctx):
+    assert plan() & CUT
+    for kw in (dict(tile_clip=0), dict(speculative=0), dict(R_hint=0), dict(no_list_cut=1)):
+        v = plan(**kw)
+        assert not v & (CUT_BASE | CUT) and v & PAYS, kw
+    v = plan(last_Q=1_499_999)      # pays(): too few column runs in the last forward ...
+    assert v & CUT_BASE and not v & (PAYS | CUT)
+    assert plan(last_Q=1_499_999, switches=dict(list_cut_always=1)) & CUT
+    ctx.policy_event("begin", 3_000_000, Q, 0)
+    for _ in range(4):
+        ctx.policy_event("counts", Q, Q - 100, 2)
+    assert not plan() & (PAYS | CUT)      # ... or a pause
+    ctx.policy_event("reset")
+    # without the pose table the cut needs predicted depths
+    assert plan(table=0) & CUT and plan(no_order_hint=1, table=0) & CUT and not plan(no_order_hint=1) & HINTS
+    v = plan(table=0, switches=dict(tau_cut=0))
+    assert v & CUT_BASE and not v & (CUT | TAU_MODE)
+    assert plan(table=1, switches=dict(tau_cut=0)) & CUT
+
+
+def test_plan_gradient_records_and_derivatives(plan):
+    v = plan(forward_only=1)
+    assert not v & (UNTOUCHED | ZERO_TOUCHED | SH_DERIVS) and v & ZERO_IN_BLEND
+    v = plan(switches=dict(touch_bits=0))
+    assert not v & (UNTOUCHED | ZERO_TOUCHED) and v & ZERO_IN_BLEND
+    v = plan(switches=dict(sparse_grec=0))
+    assert v & UNTOUCHED and not v & ZERO_TOUCHED
+    assert not plan(D=0) & SH_DERIVS and not plan(precomp=1) & SH_DERIVS and not plan(sh=0, precomp=1) & SH_DERIVS
+    assert not plan(tile_clip=0) & CLIP
+
+
+def test_plan_refusals_keep_their_texts(plan):
+    assert plan(flags=AUX) & CULLED
+    for kw in (dict(cull=0), dict(fwd_pixels_per_lane=1)):
+        assert plan(flags=AUX, **kw) == -1
+        assert plan.error() == "forward: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)"
+    assert plan(flags=8) == -1 and plan.error() == "flags: unknown bits"
+    assert plan(fwd_pixels_per_lane=3) == -1 and plan.error() == "forward: bad option value"
+    assert plan(flags=8, fwd_pixels_per_lane=3) == -1 and plan.error() == "flags: unknown bits"      # (the order of the checks)
