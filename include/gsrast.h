@@ -310,6 +310,15 @@ int gsrast_policy_event(gsrast_context* ctx, const char* what, int a, int b, int
  * zeroed in the blend, 10 only touched records zeroed, 11 untouched bits kept, 12 tile clip, 13 SH direction derivatives, 14 speculative launch
  * eligible, 15 adaptive radix sort, 16 three passes assumed, 17 the cut pays, 18 the list cut is applied.  ctx NULL = the calling thread's context. */
 int gsrast_debug_forward_plan(gsrast_context* ctx, const gsrast_options* options, unsigned flags, int P, int W, int H, const int* words);
+/* The backward's host-side plan (csrc/gsrast_policy.h: BackwardPlan) WITHOUT a device: what a backward with these options and flags would decide for
+ * words[7] = { P, D, R, width, height, (1: a gsrast_backward_raw* call) | (2: SH coefficients) | (4: colors_precomp) | (8: cov3D_precomp) | (16: dL_dacc_depth or
+ * dL_dalpha given), 1: the context's side stream can be had }, under the process-wide switches in force (gsrast_set_option).  Returns GSRAST_E_ARG (the
+ * backward's own refusal in gsrast_last_error) or the decisions as bits: 0 aux gradients, 1 anti-aliased state, 2 blend phase, 3 per-Gaussian phase, 4 gradient
+ * records zero-filled, 5 sh_dir_derivs runs, 6 ... on the side stream, 7 late fill wanted, 8 late fill (late_rows_zero on the side stream), 9 its kernel skipped
+ * ("ablate" 3), 10 side stream joined BEHIND preprocess_bwd, 11 the blend backward runs, 12 culled, 13 transposed, 14 its aux instantiation, 15 launch order from
+ * the work buckets, 16 from tile_order, 17 sh_factor runs, 18 preprocess_bwd leaves dL_dsh to it, 19 sparse preprocess_bwd, 20 grouped; bits 21-23 pixels per
+ * lane (1 / 2 / 4), 24-25 the "ablate" blend kernel (0 / 1 / 2), 26-27 "mutate".  grids (may be NULL) receives { sh_dir_derivs' grid, preprocess_bwd's grid } (0: not launched). */
+int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, const int* words, int* grids);
 int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
                       gsrast_alloc_fn binning_alloc, void* binning_ctx,
@@ -394,6 +403,7 @@ int gsrast_backward_aux(const gsrast_options* options,
  * ones;  "touch_bits" = the forward blend keeps one "no pixel consumed it" bit per Gaussian for the backward;  "sparse_grec" = such a forward
  * zeroes only the consumed Gaussians' gradient records instead of all P (the backward takes every other record for zero);
  * "late_fill_min_p" (default 750000): scenes of at least that many Gaussians write the untouched Gaussians' zero rows beside the blend backward.
+ * gsrast_get_option answers for every name gsrast_set_option accepts (the value stored: a flag reads 0 / 1, a clamped word its clamped value).
  * Read-only through gsrast_get_option: "last_instances" (num_rendered) and "last_runs" (column runs) of the
  * last forward call of the CALLING THREAD's context, "redo_count" (= gsrast_context_query(NULL, name)). */
 int gsrast_set_option(const char* name, int value);

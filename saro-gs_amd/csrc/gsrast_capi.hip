@@ -1,7 +1,8 @@
 // gsrast_capi.hip -- host orchestration + the C ABI declared in include/gsrast.h.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -munsafe-fp-atomics (see build.py).
 //
-// Host side of the forward: forward_impl runs the stages of one ForwardRun; what a call does is decided once, by plan_forward (gsrast_policy.h).
+// Host side: forward_impl / backward_impl run the stages of one ForwardRun / BackwardRun; what a call does is decided once, at its top, by
+// plan_forward / plan_backward (gsrast_policy.h).  The process-wide words of gsrast_set_option live in one table (kOptions).
 // Launch plan of the default path (every launch on the caller's stream except the colour kernel):
 //   forward : preprocess_fwd (geometry; claims the pose's launch-order hint slot) -> depth_bucket_scatter -> depth_bucket_sort
 //             -> [fork: preprocess_color on the context's side stream] -> emit_column_runs (workgroup 0: totals -> pinned host memory,
@@ -46,23 +47,78 @@ using namespace gsrast;
 namespace {
 
 thread_local std::string g_err;
-std::atomic<int> g_profile{0}, g_debug_sync{0}, g_ablate{0}, g_debug_state{0}, g_list_cut_always{0}, g_chain_gate{1} /* 1: the completion pass of the list cut runs on its own stream behind a gate (ChainGate); 0: inline, eleven predicated launches on the caller's stream */, g_touch_bits{1} /* 1: the forward blend keeps GeomLayout::untouched for the backward (A/B switch) */, g_sparse_grec{1} /* 1: a forward that keeps those bits zeroes only the consumed Gaussians' gradient records (A/B switch) */, g_late_fill_min_p{750000} /* scenes of at least this many Gaussians write their zero rows beside the blend backward */,
-                 g_tau_sample{1} /* the predicted cut's opacity mass comes from one wave in 2^this of preprocess_fwd */, g_tau_cut{1} /* 1: a pose without (trustworthy) remembered cut depths gets PREDICTED ones from this call's own opacity mass (gsrast_common.h) */;      // process-wide diagnostics (not per-call behaviour)
-
-// Per-call behaviour lives in a gsrast_options value: the *_ex entry points take one, the reference-shaped entry points
-// snapshot the process defaults (gsrast_set_option) once at entry, so a call never sees a half-changed set and two host
-// threads driving different streams / devices with different options cannot disturb each other.
-struct DefaultOptions {
-    std::atomic<int> exp_mode{0}, binning{0}, tile_clip{1}, cull{1}, lpt{1}, speculative{1}, fwd_ppl{0}, bwd_ppl{0}, sh_grad_factors{0}, side_stream{1}, depth_sort{0}, forward_only{0}, no_order_hint{0}, dense_backward{0}, no_list_cut{0};
-} g_def;
+// ---- every process-wide word gsrast_set_option addresses: ONE table -- name, word, default, how a value is taken ------------------------
+// Per-call behaviour lives in a gsrast_options value: the *_ex entry points take one, the reference-shaped entry points snapshot the
+// process defaults (the rows with a `field`) once at entry, so a call never sees a half-changed set and two host threads driving
+// different streams / devices with different options cannot disturb each other.  The other rows are process-wide diagnostics and A/B
+// switches, not per-call behaviour: a render call loads each of them ONCE, at its top (snapshot_switches).
+struct OptionWords {
+    std::atomic<int> exp_mode, binning, tile_clip, cull, lpt, speculative, fwd_pixels_per_lane, bwd_pixels_per_lane, sh_grad_factors, side_stream, depth_sort, forward_only,
+                     no_order_hint, dense_backward, no_list_cut, profile, debug_sync, debug_state, ablate, mutate, list_cut_always, chain_gate, touch_bits, sparse_grec,
+                     late_fill_min_p, tau_sample, tau_cut, two_level, two_level_min_p, sort_hint, bwd_transposed, hexplane_scatter;
+    OptionWords();      // (stores the table's defaults)
+} g_opt;
+enum OptionKind { OPT_FLAG /* non-zero means 1 */, OPT_ONE_OF /* bit v of `a` set: v is accepted; else GSRAST_E_ARG */, OPT_CLAMP /* to [a, b] */, OPT_WORD /* stored as given */ };
+struct OptionRow { const char* name; std::atomic<int>* word; int def; OptionKind kind; int a, b; int gsrast_options::* field /* the per-call option this word is the process default of */; };
+constexpr int OPT_01 = 0b11, OPT_012 = 0b111, OPT_PPL = 0b10111 /* 0 auto, 1 / 2 / 4 */, OPT_MAX = 0x7FFFFFFF;
+constexpr OptionRow kOptions[] = {
+    { "exp_mode", &g_opt.exp_mode, 0, OPT_ONE_OF, OPT_012, 0, &gsrast_options::exp_mode },
+    { "binning", &g_opt.binning, 0, OPT_ONE_OF, OPT_01, 0, &gsrast_options::binning },
+    { "tile_clip", &g_opt.tile_clip, 1, OPT_FLAG, 0, 0, &gsrast_options::tile_clip },
+    { "cull", &g_opt.cull, 1, OPT_FLAG, 0, 0, &gsrast_options::cull },
+    { "lpt", &g_opt.lpt, 1, OPT_FLAG, 0, 0, &gsrast_options::lpt },      // heaviest-tile-first launch order
+    { "speculative", &g_opt.speculative, 1, OPT_FLAG, 0, 0, &gsrast_options::speculative },
+    { "fwd_pixels_per_lane", &g_opt.fwd_pixels_per_lane, 0, OPT_ONE_OF, OPT_PPL, 0, &gsrast_options::fwd_pixels_per_lane },
+    { "bwd_pixels_per_lane", &g_opt.bwd_pixels_per_lane, 0, OPT_ONE_OF, OPT_PPL, 0, &gsrast_options::bwd_pixels_per_lane },
+    { "sh_grad_factors", &g_opt.sh_grad_factors, 0, OPT_FLAG, 0, 0, &gsrast_options::sh_grad_factors },
+    { "side_stream", &g_opt.side_stream, 1, OPT_FLAG, 0, 0, &gsrast_options::side_stream },
+    { "depth_sort", &g_opt.depth_sort, 0, OPT_ONE_OF, OPT_01, 0, &gsrast_options::depth_sort },
+    { "forward_only", &g_opt.forward_only, 0, OPT_FLAG, 0, 0, &gsrast_options::forward_only },
+    { "no_order_hint", &g_opt.no_order_hint, 0, OPT_FLAG, 0, 0, &gsrast_options::no_order_hint },
+    { "dense_backward", &g_opt.dense_backward, 0, OPT_FLAG, 0, 0, &gsrast_options::dense_backward },
+    { "no_list_cut", &g_opt.no_list_cut, 0, OPT_FLAG, 0, 0, &gsrast_options::no_list_cut },
+    { "profile", &g_opt.profile, 0, OPT_WORD, 0, 0, nullptr },                    // bit k = time kernel id k; -1 = all
+    { "debug_sync", &g_opt.debug_sync, 0, OPT_FLAG, 0, 0, nullptr },
+    { "debug_state", &g_opt.debug_state, 0, OPT_FLAG, 0, 0, nullptr },            // forwards also store what only gsrast_debug_export reads (cov3D)
+    { "ablate", &g_opt.ablate, 0, OPT_WORD, 0, 0, nullptr },                      // experiments only
+    { "mutate", &g_opt.mutate, 0, OPT_WORD, 0, 0, nullptr },                      // tests only: a deliberately WRONG backward (mutate_drop_front_batch_kernel) -- proves that a parity bar bites
+    { "list_cut_always", &g_opt.list_cut_always, 0, OPT_FLAG, 0, 0, nullptr },    // the list cut also where it does not pay (tests)
+    { "chain_gate", &g_opt.chain_gate, 1, OPT_FLAG, 0, 0, nullptr },              // 1: the completion pass of the list cut runs on its own stream behind a gate (ChainGate); 0: inline, eleven predicated launches on the caller's stream
+    { "touch_bits", &g_opt.touch_bits, 1, OPT_FLAG, 0, 0, nullptr },              // 1: the forward blend keeps GeomLayout::untouched for the backward; 0: only the list cut's late bits serve it (A/B switch)
+    { "sparse_grec", &g_opt.sparse_grec, 1, OPT_FLAG, 0, 0, nullptr },            // 1: a forward that keeps those bits zeroes only the consumed Gaussians' gradient records (A/B switch)
+    { "late_fill_min_p", &g_opt.late_fill_min_p, 750000, OPT_CLAMP, 0, OPT_MAX, nullptr },      // scenes of at least this many Gaussians write their zero rows beside the blend backward
+    { "tau_sample", &g_opt.tau_sample, 1, OPT_CLAMP, 0, 6, nullptr },             // the predicted cut's opacity mass comes from one wave in 2^this of preprocess_fwd
+    { "tau_cut", &g_opt.tau_cut, 1, OPT_FLAG, 0, 0, nullptr },                    // 1: a pose without (trustworthy) remembered cut depths gets PREDICTED ones from this call's own opacity mass (gsrast_common.h); 0: only poses with remembered cut depths are cut
+    { "two_level", &g_opt.two_level, 1, OPT_FLAG, 0, 0, nullptr },                // 1: the bucket scatter as two launches, coarse + refine (gsrast_binning.h; A/B switch)
+    { "two_level_min_p", &g_opt.two_level_min_p, 2500000, OPT_CLAMP, 0, OPT_MAX, nullptr },     // measured (kernel times, one box): 0.3 M 16.1 us in one launch against 15.8 + 5.7 in two, 1 M 41.0 against 36.6 + 9.1, 3 M 88.2 against 60.5 + 19.9: the second launch only pays where the scattered stores dominate
+    { "sort_hint", &g_opt.sort_hint, 1, OPT_FLAG, 0, 0, nullptr },                // 1: enqueue three depth-sort passes when the context's last forward had short keys (A/B switch)
+    { "bwd_transposed", &g_opt.bwd_transposed, 1, OPT_FLAG, 0, 0, nullptr },      // 1: blend_bwd_cull_t_kernel for one pixel per lane (default); 0: blend_bwd_cull_kernel<.., 1> (A/B switch)
+    { "hexplane_scatter", &g_opt.hexplane_scatter, 0, OPT_ONE_OF, OPT_01, 0, nullptr },         // hexplane backward to the texels: 0 = sorted runs, 1 = direct global atomics
+};
+OptionWords::OptionWords() { for (const OptionRow& r : kOptions) r.word->store(r.def); }
+const OptionRow* option_row(const char* name)
+{
+    for (const OptionRow& r : kOptions) if (!strcmp(name, r.name)) return &r;
+    return nullptr;
+}
+// what a row stores for `value`; false: the value is refused
+bool option_take(const OptionRow& r, int value, int* stored)
+{
+    *stored = r.kind == OPT_FLAG ? (value ? 1 : 0) : r.kind == OPT_CLAMP ? std::min(std::max(value, r.a), r.b) : value;
+    return r.kind != OPT_ONE_OF || (value >= 0 && value < 31 && ((r.a >> value) & 1) != 0);
+}
 gsrast_options snapshot_defaults()
 {
     gsrast_options o{};
-    o.exp_mode = g_def.exp_mode; o.binning = g_def.binning; o.tile_clip = g_def.tile_clip; o.cull = g_def.cull; o.lpt = g_def.lpt;
-    o.speculative = g_def.speculative; o.fwd_pixels_per_lane = g_def.fwd_ppl; o.bwd_pixels_per_lane = g_def.bwd_ppl;
-    o.sh_grad_factors = g_def.sh_grad_factors; o.side_stream = g_def.side_stream; o.depth_sort = g_def.depth_sort;
-    o.forward_only = g_def.forward_only; o.no_order_hint = g_def.no_order_hint; o.dense_backward = g_def.dense_backward; o.no_list_cut = g_def.no_list_cut;
+    for (const OptionRow& r : kOptions) if (r.field) o.*r.field = r.word->load();
     return o;
+}
+PlanSwitches snapshot_switches()      // one load of every switch a render call's plan depends on
+{
+    const OptionWords& g = g_opt;
+    return PlanSwitches{ g.list_cut_always.load() != 0, g.tau_cut.load() != 0, g.touch_bits.load() != 0, g.sparse_grec.load() != 0, g.two_level.load() != 0, g.chain_gate.load() != 0,
+                         g.sort_hint.load() != 0, g.debug_state.load() != 0, g.two_level_min_p.load(), g.tau_sample.load(), g.bwd_transposed.load() != 0, g.late_fill_min_p.load(),
+                         g.ablate.load(), g.mutate.load() };
 }
 
 int fail(int code, const char* what, hipError_t e = hipSuccess)
@@ -120,7 +176,7 @@ struct RoctxRange {
 
 struct ProfScope {
     int id; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on; RoctxRange range;
-    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_), on(((g_profile.load() >> id_) & 1) != 0 && (t_prof_off == 0 || id_ == K_CUT_REDO)), range(kKernelNames[id_])
+    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_), on(((g_opt.profile.load() >> id_) & 1) != 0 && (t_prof_off == 0 || id_ == K_CUT_REDO)), range(kKernelNames[id_])
     {
         if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
     }
@@ -139,7 +195,7 @@ int post_launch(const char* what, hipStream_t s)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GSRAST_E_DEVICE, what, e);
     static const bool env_sync = getenv("GSRAST_DEBUG_SYNC") != nullptr;      // (diagnostics: localise a faulting launch)
-    if (g_debug_sync.load() || env_sync) {
+    if (g_opt.debug_sync.load() || env_sync) {
         if (env_sync) fprintf(stderr, "[gsrast] %s\n", what);
         e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail(GSRAST_E_DEVICE, what, e);
@@ -458,8 +514,6 @@ SideStream* side_stream_of(gsrast_context* ctx)
 // front-most entries of the tile's list (one staged batch dropped: the tile's range, its pixels' n_contrib and its tile_max are shifted by a
 // small kernel in front of the blend backward; every other (pixel, Gaussian) pair gets exactly what it gets without the mutation).
 // bit 1: the background term of dL/dalpha (backward.cu:531-534) is dropped (the blend backward is handed a zero background).
-std::atomic<int> g_mutate{0};
-std::atomic<int> g_two_level{1} /* 1: the bucket scatter as two launches, coarse + refine (gsrast_binning.h; A/B switch) */, g_two_level_min_p{2500000} /* measured (kernel times, one box): 0.3 M 16.1 us in one launch against 15.8 + 5.7 in two, 1 M 41.0 against 36.6 + 9.1, 3 M 88.2 against 60.5 + 19.9: the second launch only pays where the scattered stores dominate */;
 __global__ void mutate_drop_front_batch_kernel(uint2* ranges, uint32_t* n_contrib, uint32_t* tile_max, uint32_t tile, int W, int H, int gx)
 {
     const uint32_t tx = tile % (uint32_t)gx, ty = tile / (uint32_t)gx;
@@ -594,19 +648,6 @@ export_keys_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict_
     }
 }
 
-std::atomic<int> g_hex_scatter{0};    // hexplane backward to the texels: 0 = sorted runs, 1 = direct global atomics
-int pick_ppl(uint32_t ntiles, bool backward, const gsrast_options& o)
-{
-    const int forced = backward ? o.bwd_pixels_per_lane : o.fwd_pixels_per_lane;
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
-    // Measured on MI355X (profiles/): the forward is fastest with one pixel per lane (finest cull /
-    // early-exit granularity, most waves in flight).  With per-wave accumulator slices the backward is
-    // within 2 % for 1, 2 and 4 pixels per lane at 1080p and above; fewer pixels per lane win for small
-    // images (more waves) and small Gaussians (finer culling), more pixels per lane win at 4K.
-    if (!backward) return 1;
-    return ntiles >= 32768 ? 4 : (ntiles >= 8192 ? 2 : 1);
-}
-
 struct BlendArgs {
     uint32_t* bcnt = nullptr; uint16_t* blist = nullptr; int from_buckets = 0;   // launch order from the work buckets (ImgLayout)
     const uint2* ranges; const uint32_t* plist; const uint32_t* order; int W, H, gx; uint32_t T; const float4 *r0, *r1, *r2; const float* bg;
@@ -622,13 +663,6 @@ struct BlendArgs {
     float *oad = nullptr, *oal = nullptr;                        // forward (culling kernel), aux: acc_depth / alpha -- non-null selects AUX
     const float *dad = nullptr, *dal = nullptr;                  // backward, aux: dL/dacc_depth / dL/dalpha (either may be null)
 };
-std::atomic<int> g_sort_hint{1};          // 1: enqueue three depth-sort passes when the context's last forward had short keys (A/B switch)
-std::atomic<int> g_bwd_transposed{1};     // 1: blend_bwd_cull_t_kernel for one pixel per lane (default); 0: blend_bwd_cull_kernel<.., 1> (A/B switch)
-PlanSwitches snapshot_switches()      // one load of every A/B switch the forward's plan depends on
-{
-    return PlanSwitches{ g_list_cut_always.load() != 0, g_tau_cut.load() != 0, g_touch_bits.load() != 0, g_sparse_grec.load() != 0, g_two_level.load() != 0,
-                         g_chain_gate.load() != 0, g_sort_hint.load() != 0, g_debug_state.load() != 0, g_two_level_min_p.load(), g_tau_sample.load() };
-}
 
 // ---- kernel selection: a runtime value -> the template instantiation.  f is called with the std::integral_constant of the V that equals v
 // (of the last V if none does); a generic lambda instantiates its kernel only for the constants it is called with. ----
@@ -661,19 +695,8 @@ void launch_blend_fwd(int exp_mode, bool cull, int ppl, uint32_t grid, hipStream
     });
 }
 
-// Which blend backward a call launches.  `transposed` = blend_bwd_cull_t_kernel.
-struct BwdBlendPick {
-    int ppl; bool cull; bool transposed; bool aux; int ablate;   // ablate: 1 / 2 = blend_bwd_kernel<0, 4, ablate> (experiments), else 0
-    BwdBlendPick(const gsrast_options& o, uint32_t T, bool aux_) : ppl(pick_ppl(T, true, o)), cull(culled_blend(o, true)), aux(aux_)
-    {
-        const int abl = g_ablate.load();
-        ablate = (!aux && (abl == 1 || abl == 2)) ? abl : 0;
-        // aux: always the transposed kernel, whatever the pixels per lane and the A/B switch say
-        transposed = aux || (cull && !ablate && ppl == 1 && g_bwd_transposed.load() != 0);
-    }
-};
 // blend backward: ablation | <exp_mode> x (transposed: <aux> | culled: <pixels per lane> | un-culled: <pixels per lane>)
-void launch_blend_bwd(int exp_mode, const BwdBlendPick& k, uint32_t grid, hipStream_t s, const BlendArgs& a)
+void launch_blend_bwd(int exp_mode, const BlendBwdPick& k, uint32_t grid, hipStream_t s, const BlendArgs& a)
 {
     const uint32_t* bcnt = a.from_buckets ? a.bcnt : nullptr;
     auto uncull = [&](auto mode, auto lanes, auto abl) {
@@ -707,7 +730,7 @@ void gsrast_options_init(gsrast_options* o)
 {
     if (!o) return;
     memset(o, 0, sizeof *o);
-    o->tile_clip = 1; o->cull = 1; o->lpt = 1; o->speculative = 1; o->side_stream = 1;
+    for (const OptionRow& r : kOptions) if (r.field) o->*r.field = r.def;
 }
 gsrast_context* gsrast_context_create(void) { return new (std::nothrow) gsrast_context(); }
 void gsrast_context_destroy(gsrast_context* c)
@@ -812,84 +835,43 @@ int gsrast_debug_forward_plan(gsrast_context* c, const gsrast_options* options, 
     return v;
 }
 
+int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, const int* words, int* grids)
+{
+    if (!options || !words) return fail(GSRAST_E_ARG, "debug_backward_plan: NULL argument");
+    const int in = words[5];
+    BackwardPlan p = plan_backward(*options, BackwardInputs{ flags, words[0], words[1], words[2], words[3], words[4], (in & 1) != 0, (in & 2) != 0, (in & 4) != 0, (in & 8) != 0, (in & 16) != 0 },
+                                   snapshot_switches());
+    if (p.refusal) return fail(GSRAST_E_ARG, p.refusal);
+    p.side_answer(p.wants_side() && words[6] != 0);
+    if (grids) { grids[0] = p.derivs_grid; grids[1] = p.per_gaussian_grid; }
+    const bool bits[] = { p.aux, p.aa, p.do_blend, p.do_geom, p.zero_records, p.derivs, p.derivs_on_side, p.late_fill_wanted, p.late_fill, p.skip_zero_rows, p.join_late,
+                          p.blend, p.pick.cull, p.pick.transposed, p.pick.aux, p.from_buckets, p.tile_order, p.sh_factor, p.factors != 0, p.sparse, p.grouped };
+    int v = 0;
+    for (size_t k = 0; k < sizeof bits / sizeof bits[0]; k++) v |= bits[k] ? 1 << k : 0;
+    return v | p.pick.ppl << 21 | p.pick.ablate << 24 | (p.mutate & 3) << 26;
+}
+
+// A lookup in kOptions, plus the names that are not plain words: "pixels_per_lane" writes both directions and reads the forward's, "word_fork"
+// (word forks were removed, DESIGN_LOG.md; bench.py still reads the name) reads 0 and accepts only 0, the context's words are read-only.
 int gsrast_set_option(const char* name, int value)
 {
     if (!name) return GSRAST_E_ARG;
-    if (!strcmp(name, "exp_mode")) { if (value < 0 || value > 2) return GSRAST_E_ARG; g_def.exp_mode = value; return 0; }
-    if (!strcmp(name, "profile")) { g_profile = value; return 0; }  // bit k = time kernel id k; -1 = all
-    if (!strcmp(name, "debug_sync")) { g_debug_sync = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "list_cut_always")) { g_list_cut_always = value ? 1 : 0; return 0; }   // the list cut also where it does not pay (tests)
-    if (!strcmp(name, "chain_gate")) { g_chain_gate = value ? 1 : 0; return 0; }               // 0: the completion pass's launches on the caller's stream (round 3)
-    if (!strcmp(name, "touch_bits")) { g_touch_bits = value ? 1 : 0; return 0; }               // 0: only the list cut's late bits serve the backward (round 4)
-    if (!strcmp(name, "late_fill_min_p")) { g_late_fill_min_p = value < 0 ? 0 : value; return 0; }
-    if (!strcmp(name, "sparse_grec")) { g_sparse_grec = value != 0; return 0; }
-    if (!strcmp(name, "word_fork")) return value == 0 ? 0 : GSRAST_E_ARG;      // (word forks were removed, DESIGN_LOG.md; bench.py still reads the name)
-    if (!strcmp(name, "tau_sample")) { g_tau_sample = value < 0 ? 0 : (value > 6 ? 6 : value); return 0; }
-    if (!strcmp(name, "tau_cut")) { g_tau_cut = value ? 1 : 0; return 0; }                    // 0: only poses with remembered cut depths are cut (round 4's behaviour)
-    if (!strcmp(name, "debug_state")) { g_debug_state = value ? 1 : 0; return 0; }   // forwards also store what only gsrast_debug_export reads (cov3D)
-    if (!strcmp(name, "ablate")) { g_ablate = value; return 0; }   // experiments only
-    if (!strcmp(name, "two_level")) { g_two_level = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "two_level_min_p")) { g_two_level_min_p = value < 0 ? 0 : value; return 0; }
-    if (!strcmp(name, "mutate")) { g_mutate = value; return 0; }   // tests only: a deliberately WRONG backward (see g_mutate) -- proves that a parity bar bites
-    if (!strcmp(name, "bwd_transposed")) { g_bwd_transposed = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "sort_hint")) { g_sort_hint = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "cull")) { g_def.cull = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "binning")) { if (value != 0 && value != 1) return GSRAST_E_ARG; g_def.binning = value; return 0; }
-    if (!strcmp(name, "tile_clip")) { g_def.tile_clip = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "sh_grad_factors")) { g_def.sh_grad_factors = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "speculative")) { g_def.speculative = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "side_stream")) { g_def.side_stream = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "depth_sort")) { if (value != 0 && value != 1) return GSRAST_E_ARG; g_def.depth_sort = value; return 0; }
-    if (!strcmp(name, "forward_only")) { g_def.forward_only = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "no_order_hint")) { g_def.no_order_hint = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "dense_backward")) { g_def.dense_backward = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "no_list_cut")) { g_def.no_list_cut = value ? 1 : 0; return 0; }
-    if (!strcmp(name, "lpt")) { g_def.lpt = value ? 1 : 0; return 0; }   // heaviest-tile-first launch order
-    if (!strcmp(name, "hexplane_scatter")) { if (value != 0 && value != 1) return GSRAST_E_ARG; g_hex_scatter = value; return 0; }
-    if (!strcmp(name, "pixels_per_lane") || !strcmp(name, "fwd_pixels_per_lane") || !strcmp(name, "bwd_pixels_per_lane")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return GSRAST_E_ARG;
-        if (name[0] != 'b') g_def.fwd_ppl = value;
-        if (name[0] != 'f') g_def.bwd_ppl = value;
-        return 0;
-    }
-    return GSRAST_E_ARG;
+    if (!strcmp(name, "word_fork")) return value == 0 ? 0 : GSRAST_E_ARG;
+    const bool both = !strcmp(name, "pixels_per_lane");
+    const OptionRow* r = option_row(both ? "fwd_pixels_per_lane" : name);
+    int stored = 0;
+    if (!r || !option_take(*r, value, &stored)) return GSRAST_E_ARG;
+    r->word->store(stored);
+    if (both) g_opt.bwd_pixels_per_lane = stored;
+    return 0;
 }
 int gsrast_get_option(const char* name)
 {
     if (!name) return GSRAST_E_ARG;
-    if (!strcmp(name, "exp_mode")) return g_def.exp_mode.load();
-    if (!strcmp(name, "profile")) return g_profile.load();
-    if (!strcmp(name, "bwd_transposed")) return g_bwd_transposed.load();
-    if (!strcmp(name, "debug_sync")) return g_debug_sync.load();
-    if (!strcmp(name, "list_cut_always")) return g_list_cut_always.load();
-    if (!strcmp(name, "chain_gate")) return g_chain_gate.load();
-    if (!strcmp(name, "touch_bits")) return g_touch_bits.load();
-    if (!strcmp(name, "late_fill_min_p")) return g_late_fill_min_p.load();
-    if (!strcmp(name, "sparse_grec")) return g_sparse_grec.load();
     if (!strcmp(name, "word_fork")) return 0;
-    if (!strcmp(name, "mutate")) return g_mutate.load();
-    if (!strcmp(name, "two_level")) return g_two_level.load();
-    if (!strcmp(name, "two_level_min_p")) return g_two_level_min_p.load();
-    if (!strcmp(name, "tau_sample")) return g_tau_sample.load();
-    if (!strcmp(name, "tau_cut")) return g_tau_cut.load();
-    if (!strcmp(name, "debug_state")) return g_debug_state.load();
-    if (!strcmp(name, "pixels_per_lane") || !strcmp(name, "fwd_pixels_per_lane")) return g_def.fwd_ppl.load();
-    if (!strcmp(name, "bwd_pixels_per_lane")) return g_def.bwd_ppl.load();
-    if (!strcmp(name, "cull")) return g_def.cull.load();
-    if (!strcmp(name, "binning")) return g_def.binning.load();
-    if (!strcmp(name, "tile_clip")) return g_def.tile_clip.load();
-    if (!strcmp(name, "sh_grad_factors")) return g_def.sh_grad_factors.load();
-    if (!strcmp(name, "last_instances") || !strcmp(name, "last_runs") || !strcmp(name, "redo_count") || !strcmp(name, "bucket_skip")) return gsrast_context_query(nullptr, name);
-    if (!strcmp(name, "speculative")) return g_def.speculative.load();
-    if (!strcmp(name, "side_stream")) return g_def.side_stream.load();
-    if (!strcmp(name, "depth_sort")) return g_def.depth_sort.load();
-    if (!strcmp(name, "forward_only")) return g_def.forward_only.load();
-    if (!strcmp(name, "no_order_hint")) return g_def.no_order_hint.load();
-    if (!strcmp(name, "dense_backward")) return g_def.dense_backward.load();
-    if (!strcmp(name, "no_list_cut")) return g_def.no_list_cut.load();
-    if (!strcmp(name, "lpt")) return g_def.lpt.load();
-    if (!strcmp(name, "hexplane_scatter")) return g_hex_scatter.load();
-    return GSRAST_E_ARG;
+    for (const char* word : { "last_instances", "last_runs", "redo_count", "bucket_skip" }) if (!strcmp(name, word)) return gsrast_context_query(nullptr, name);
+    const OptionRow* r = option_row(!strcmp(name, "pixels_per_lane") ? "fwd_pixels_per_lane" : name);
+    return r ? r->word->load() : GSRAST_E_ARG;
 }
 
 int gsrast_profile_kernel_count(void) { return K_COUNT; }
@@ -1496,7 +1478,7 @@ struct ForwardRun {
                 ba.order = ord;
             }
         }
-        launch_blend_fwd(o.exp_mode, plan.culled, pick_ppl(T, false, o), grid, s, ba);
+        launch_blend_fwd(o.exp_mode, plan.culled, o.fwd_pixels_per_lane ? o.fwd_pixels_per_lane : 1 /* the un-culled template is fastest with one pixel per lane */, grid, s, ba);
         GS_LAUNCHED("blend_fwd");
         if (side && !plan.zero_in_blend) { GS_HIP(hipStreamWaitEvent(s, side->join2, 0)); fork.joined = true; }      // the gradient records are zero before anything after this forward
         return GSRAST_OK;
@@ -2000,7 +1982,7 @@ int hex_launch_sorted(const HexArgs& a, int cell_bits, unsigned E, const uint32_
                       const float* levels, const float* dy, hipStream_t s)
 {
     const unsigned long long groups = ((unsigned long long)E + HEX_RUN_CHUNK - 1) / HEX_RUN_CHUNK;
-    hex_grad_tex_sorted_kernel<C><<<(unsigned)((groups * C + 255) / 256), 256, 0, s>>>(a, cell_bits, E, keys, vals, pairs, pts, levels, dy, g_ablate.load());
+    hex_grad_tex_sorted_kernel<C><<<(unsigned)((groups * C + 255) / 256), 256, 0, s>>>(a, cell_bits, E, keys, vals, pairs, pts, levels, dy, g_opt.ablate.load());
     GS_LAUNCHED("hex_grad_tex_sorted");
     return GSRAST_OK;
 }
@@ -2049,7 +2031,7 @@ int gsrast_hexplane_backward(int N, int D, int C, int F, int n_planes, const gsr
     for (int p = 0; p < n_planes; p++) top = std::max(top, a.pl[p].n_levels);
     if (top) GS_HIP(hipMemsetAsync(scratch + L.gmips_begin, 0, L.gmips_end - L.gmips_begin, s));
     const unsigned long long E = (unsigned long long)n_planes * N;
-    if (g_hex_scatter.load() == 0 && L.key_bits <= 32 && E < 0xFFFFFFFFull && (unsigned long long)N * F < 0xFFFFFFFFull) {
+    if (g_opt.hexplane_scatter.load() == 0 && L.key_bits <= 32 && E < 0xFFFFFFFFull && (unsigned long long)N * F < 0xFFFFFFFFull) {
         uint32_t *kA = at<uint32_t>(scratch, L.kA), *kB = at<uint32_t>(scratch, L.kB), *vA = at<uint32_t>(scratch, L.vA), *vB = at<uint32_t>(scratch, L.vB);
         hex_keys_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)n_planes), 256, 0, s>>>(a, L.cell_bits, pts, levels, kA, vA, at<HexPair>(scratch, L.pairs));
         GS_LAUNCHED("hex_keys");
@@ -2241,217 +2223,214 @@ struct BwdCall {
 };
 } // namespace
 
-// The one backward.  Raw family: the dense arrays are the model's raw leaves and their gradients, taken from the two structs here.
-static int backward_impl(const gsrast_options* options, const BwdCall& c)
-{
-    RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
-    const int P = c.P, D = c.D, M = c.M, R = c.R, width = c.width, height = c.height;
-    const float *const background = c.background, *const viewmatrix = c.viewmatrix, *const projmatrix = c.projmatrix, *const campos = c.campos;
-    const float scale_modifier = c.scale_modifier, tan_fovx = c.tan_fovx, tan_fovy = c.tan_fovy;
-    const int* const radii = c.radii; const float* const dL_dpix = c.dL_dpix; void* const stream = c.stream;
-    char *const geom_buffer = c.geom_buffer, *const binning_buffer = c.binning_buffer, *const image_buffer = c.image_buffer;
-    const float *means3D = c.means3D, *shs = c.shs, *colors_precomp = c.colors_precomp, *scales = c.scales, *rotations = c.rotations, *cov3D_precomp = c.cov3D_precomp;
-    float *dL_dmean2D = c.dL_dmean2D, *dL_dconic = c.dL_dconic, *dL_dopacity = c.dL_dopacity, *dL_dcolor = c.dL_dcolor, *dL_dmean3D = c.dL_dmean3D;
-    float *dL_dcov3D = c.dL_dcov3D, *dL_dsh = c.dL_dsh, *dL_dscale = c.dL_dscale, *dL_drot = c.dL_drot;
-    const bool aux_flag = (c.flags & GSRAST_RENDER_AUX) != 0;
-    const bool aa = (c.flags & GSRAST_RENDER_ANTIALIAS) != 0;      // the state comes from an anti-aliased forward
-    // the aux gradients: either may be null (= zero); both null is the plain backward
-    const float *const dL_dacc_depth = aux_flag ? c.dL_dacc_depth : nullptr, *const dL_dalpha = aux_flag ? c.dL_dalpha : nullptr;
-    const bool aux = dL_dacc_depth != nullptr || dL_dalpha != nullptr;
-    // ---- the checks every entry point shares (before any device work) ----
-    if (c.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) return fail(GSRAST_E_ARG, "flags: unknown bits");
-    gsrast_options o = options ? *options : snapshot_defaults();
-    if (!options_valid(o)) return fail(GSRAST_E_ARG, "backward: bad option value");
-    if (aux_flag && !culled_blend(o, true)) return fail(GSRAST_E_ARG, "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)");
-    const gsrast_raw_inputs* const rawin = c.raw_family ? c.raw : nullptr;
-    RawArgs raw{}; RawGrads rawg{};
-    if (c.raw_family) {
-        const gsrast_raw_grads* const out = c.raw_grads;
-        if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
-        if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
-        if (P == 0) return GSRAST_OK;
-        if (!out->dL_dmean2D || !out->d_xyz || !out->d_rotation || !out->d_scaling || !out->d_opacity_logit) return fail(GSRAST_E_ARG, "backward_raw: NULL required gradient output");
-        if ((rawin->rot_res != nullptr) != (out->d_rot_res != nullptr) && rawin->rot_res == nullptr) return fail(GSRAST_E_ARG, "backward_raw: d_rot_res without rot_res");
-        if (out->d_shs_res && !rawin->shs_res) return fail(GSRAST_E_ARG, "backward_raw: d_shs_res without shs_res");
-        const bool fac = out->d_sh_factor != nullptr;       // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
-        if (fac && (rawin->shs_res || out->d_shs_res)) return fail(GSRAST_E_ARG, "backward_raw: d_sh_factor cannot be combined with shs_res / d_shs_res");
-        if ((out->d_features_dc != nullptr) != (M > 1 ? out->d_features_rest != nullptr : out->d_features_dc != nullptr) || (!fac && !out->d_shs_res && !out->d_features_dc))
-            return fail(GSRAST_E_ARG, "backward_raw: give d_features_dc + d_features_rest and / or (with shs_res) d_shs_res, whose rows hold both");
-        if (((uintptr_t)out->d_rotation | (uintptr_t)out->d_features_dc | (uintptr_t)out->d_features_rest | (uintptr_t)out->d_shs_res) & 15)
-            return fail(GSRAST_E_ARG, "backward_raw: d_rotation / d_features_dc / d_features_rest / d_shs_res must be 16-byte aligned");
-        o.sh_grad_factors = fac ? 1 : 0;
-        means3D = rawin->xyz; shs = rawin->features_dc; scales = rawin->scaling; rotations = rawin->rotation;
-        dL_dmean2D = out->dL_dmean2D; dL_dopacity = out->d_opacity_logit; dL_dmean3D = out->d_xyz; dL_dscale = out->d_scaling; dL_drot = out->d_rotation;
-        dL_dsh = fac ? out->d_sh_factor : (out->d_shs_res ? out->d_shs_res : out->d_features_dc);      // (a marker, but for the factor)
-        raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
-        raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
-        rawg.d_rot_res = out->d_rot_res; rawg.d_trbf = out->d_trbf; rawg.d_shs_res = out->d_shs_res;
-        if (!fac) { rawg.d_dc = out->d_features_dc; rawg.d_rest = out->d_features_rest; }     // (factor: not written, the caller completes them after the exchange)
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int W = width, H = height;
-    if (P < 0 || R < 0 || W <= 0 || H <= 0) return fail(GSRAST_E_ARG, "backward: bad sizes");
-    if (P == 0) return GSRAST_OK;
-    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail(GSRAST_E_ARG, "backward: NULL state buffer");
-    if (!means3D || !radii || !viewmatrix || !projmatrix || !dL_dpix || !background) return fail(GSRAST_E_ARG, "backward: NULL required input");
-    if (!dL_dmean2D || !dL_dopacity || !dL_dmean3D) return fail(GSRAST_E_ARG, "backward: NULL gradient output");
-    if (colors_precomp && !dL_dcolor) return fail(GSRAST_E_ARG, "backward: colors_precomp path needs dL_dcolor");
-    if (dL_dconic && ((uintptr_t)dL_dconic & 15)) return fail(GSRAST_E_ARG, "backward: dL_dconic must be 16-byte aligned");
-    if (rotations && (((uintptr_t)rotations | (uintptr_t)dL_drot) & 15)) return fail(GSRAST_E_ARG, "backward: rotations / dL_drot must be 16-byte aligned");
-    if (cov3D_precomp && !dL_dcov3D) return fail(GSRAST_E_ARG, "backward: cov3D_precomp path needs dL_dcov3D");
-    const bool use_sh = shs && !colors_precomp;
-    const bool use_sr = !cov3D_precomp;
-    if (use_sh && (!dL_dsh || !campos)) return fail(GSRAST_E_ARG, "backward: SH path needs dL_dsh and campos");
-    if (use_sr && (!scales || !rotations || !dL_dscale || !dL_drot)) return fail(GSRAST_E_ARG, "backward: scale/rotation path needs their gradients");
-
-    const CamArgs cam = make_cam(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, W, H);
-    const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
-    const BwdBlendPick bwd_pick(o, T, aux);
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)W, (size_t)H);
-    char* geom = geom_buffer; char* bin = binning_buffer; char* img = image_buffer;
-    const uint32_t* plist = bin ? at<uint32_t>(bin, 0) : nullptr;     // BinLayout: point_list lives at offset 0
-    const float4* rec0 = at<float4>(geom, GL.rec0); const float4* rec1 = at<float4>(geom, GL.rec1); const float4* rec2 = at<float4>(geom, GL.rec2);
-
+// One backward call's state and its stages (backward_impl below is the order they run in).  What the call does is decided once, by
+// plan_backward (gsrast_policy.h), from one snapshot of the options and the process-wide switches; the stages only check pointers and enqueue.
+// Raw family: the dense arrays are the model's raw leaves and their gradients, taken from the two structs in check_and_plan.
+namespace {
+struct BackwardRun {
+    BwdCall c;      // (a copy: the raw family's leaves and gradient arrays take the dense pointers' places)
+    gsrast_options o; const hipStream_t s;
+    BackwardPlan plan;
+    const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{}; RawGrads rawg{};
+    CamArgs cam; GeomLayout GL; ImgLayout IL; char *geom = nullptr, *img = nullptr;
     // per-Gaussian gradient records: the only memory the backward accumulates into (64 B / Gaussian, in the geometry buffer)
     // (the forward leaves them zero: a caller that knows this is the first backward on this state says so and saves the fill)
-    float* grec = at<float>(geom, GL.grec);
-    const bool do_blend = o.backward_phase != 2, do_geom = o.backward_phase != 1;
-    // (a forward that was told no backward would follow has not zeroed the records)
-    if (do_blend && (!o.grads_zeroed || o.forward_only)) GS_HIP(hipMemsetAsync(grec, 0, (size_t)P * GREC * sizeof(float), s));
+    float* grec = nullptr;
+    struct SideJoinGuard {      // an error exit must not leave side-stream work running on the caller's arrays
+        SideStream* side = nullptr; bool joined = false;
+        ~SideJoinGuard() { if (side && !joined) (void)hipStreamSynchronize(side->stream); }
+    } fork;
+
+    BackwardRun(const gsrast_options* options, const BwdCall& c_) : c(c_), o(options ? *options : snapshot_defaults()), s((hipStream_t)c_.stream) {}
+
+    // ---- the plan, and the checks every entry point shares (before any device work) ----
+    int check_and_plan()
+    {
+        const int P = c.P, M = c.M;
+        if (c.raw_family) o.sh_grad_factors = (c.raw_grads && c.raw_grads->d_sh_factor) ? 1 : 0;      // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
+        plan = plan_backward(o, BackwardInputs{ c.flags, P, c.D, c.R, c.width, c.height, c.raw_family, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr),
+                                                c.colors_precomp != nullptr, c.cov3D_precomp != nullptr, c.dL_dacc_depth != nullptr || c.dL_dalpha != nullptr }, snapshot_switches());
+        if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
+        if (c.raw_family) {
+            rawin = c.raw;
+            const gsrast_raw_grads* const out = c.raw_grads;
+            if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
+            if (!out) return fail(GSRAST_E_ARG, "backward_raw: NULL gradient set");
+            if (P == 0) return GSRAST_OK;
+            if (!out->dL_dmean2D || !out->d_xyz || !out->d_rotation || !out->d_scaling || !out->d_opacity_logit) return fail(GSRAST_E_ARG, "backward_raw: NULL required gradient output");
+            if ((rawin->rot_res != nullptr) != (out->d_rot_res != nullptr) && rawin->rot_res == nullptr) return fail(GSRAST_E_ARG, "backward_raw: d_rot_res without rot_res");
+            if (out->d_shs_res && !rawin->shs_res) return fail(GSRAST_E_ARG, "backward_raw: d_shs_res without shs_res");
+            const bool fac = out->d_sh_factor != nullptr;
+            if (fac && (rawin->shs_res || out->d_shs_res)) return fail(GSRAST_E_ARG, "backward_raw: d_sh_factor cannot be combined with shs_res / d_shs_res");
+            if ((out->d_features_dc != nullptr) != (M > 1 ? out->d_features_rest != nullptr : out->d_features_dc != nullptr) || (!fac && !out->d_shs_res && !out->d_features_dc))
+                return fail(GSRAST_E_ARG, "backward_raw: give d_features_dc + d_features_rest and / or (with shs_res) d_shs_res, whose rows hold both");
+            if (((uintptr_t)out->d_rotation | (uintptr_t)out->d_features_dc | (uintptr_t)out->d_features_rest | (uintptr_t)out->d_shs_res) & 15)
+                return fail(GSRAST_E_ARG, "backward_raw: d_rotation / d_features_dc / d_features_rest / d_shs_res must be 16-byte aligned");
+            c.means3D = rawin->xyz; c.shs = rawin->features_dc; c.scales = rawin->scaling; c.rotations = rawin->rotation;
+            c.dL_dmean2D = out->dL_dmean2D; c.dL_dopacity = out->d_opacity_logit; c.dL_dmean3D = out->d_xyz; c.dL_dscale = out->d_scaling; c.dL_drot = out->d_rotation;
+            c.dL_dsh = fac ? out->d_sh_factor : (out->d_shs_res ? out->d_shs_res : out->d_features_dc);      // (a marker, but for the factor)
+            raw.motion_res = rawin->motion_res; raw.rot_res = rawin->rot_res; raw.trbf = rawin->trbf; raw.opacity_logit = rawin->opacity_logit;
+            raw.features_dc = rawin->features_dc; raw.features_rest = rawin->features_rest; raw.shs_res = rawin->shs_res;
+            rawg.d_rot_res = out->d_rot_res; rawg.d_trbf = out->d_trbf; rawg.d_shs_res = out->d_shs_res;
+            if (!fac) { rawg.d_dc = out->d_features_dc; rawg.d_rest = out->d_features_rest; }     // (factor: not written, the caller completes them after the exchange)
+        }
+        if (P < 0 || c.R < 0 || c.width <= 0 || c.height <= 0) return fail(GSRAST_E_ARG, "backward: bad sizes");
+        if (P == 0) return GSRAST_OK;
+        if (!c.geom_buffer || !c.image_buffer || (c.R > 0 && !c.binning_buffer)) return fail(GSRAST_E_ARG, "backward: NULL state buffer");
+        if (!c.means3D || !c.radii || !c.viewmatrix || !c.projmatrix || !c.dL_dpix || !c.background) return fail(GSRAST_E_ARG, "backward: NULL required input");
+        if (!c.dL_dmean2D || !c.dL_dopacity || !c.dL_dmean3D) return fail(GSRAST_E_ARG, "backward: NULL gradient output");
+        if (c.colors_precomp && !c.dL_dcolor) return fail(GSRAST_E_ARG, "backward: colors_precomp path needs dL_dcolor");
+        if (c.dL_dconic && ((uintptr_t)c.dL_dconic & 15)) return fail(GSRAST_E_ARG, "backward: dL_dconic must be 16-byte aligned");
+        if (c.rotations && (((uintptr_t)c.rotations | (uintptr_t)c.dL_drot) & 15)) return fail(GSRAST_E_ARG, "backward: rotations / dL_drot must be 16-byte aligned");
+        if (c.cov3D_precomp && !c.dL_dcov3D) return fail(GSRAST_E_ARG, "backward: cov3D_precomp path needs dL_dcov3D");
+        if (plan.use_sh && (!c.dL_dsh || !c.campos)) return fail(GSRAST_E_ARG, "backward: SH path needs dL_dsh and campos");
+        if (plan.use_sr && (!c.scales || !c.rotations || !c.dL_dscale || !c.dL_drot)) return fail(GSRAST_E_ARG, "backward: scale/rotation path needs their gradients");
+        cam = make_cam(c.viewmatrix, c.projmatrix, c.campos, c.tan_fovx, c.tan_fovy, c.scale_modifier, c.width, c.height);
+        GL = geom_layout((size_t)P); IL = img_layout((size_t)c.width, (size_t)c.height);
+        geom = c.geom_buffer; img = c.image_buffer; grec = at<float>(geom, GL.grec);
+        return GSRAST_OK;
+    }
+    int zero_records()
+    {
+        if (plan.zero_records) GS_HIP(hipMemsetAsync(grec, 0, (size_t)c.P * GREC * sizeof(float), s));
+        return GSRAST_OK;
+    }
     // What the per-Gaussian backward needs of the SH coefficients -- d(colour)/d(view direction), 36 B instead of 12*M -- depends on
     // nothing the blend backward produces: evaluated on the side stream of the calling thread's context WHILE the VALU-bound blend
     // backward runs, joined in front of preprocess_bwd (or at the end of phase 1 of a two-phase backward).
     // Round 3: the forward's colour kernel leaves those nine floats per Gaussian while it has the coefficient block in LDS
     // (preprocess_color_kernel), so this kernel only runs for a state whose forward was told that no backward would follow
     // (options.forward_only, passed to both calls by a caller that changed its mind).
-    SideStream* side = nullptr;
-    bool side_has_derivs = false;       // the side stream computes something the per-Gaussian backward reads (a forward_only state's direction derivatives)
-    struct BwdSideGuard {       // an error exit below must not leave side-stream work running on the caller's arrays
-        SideStream*& side; bool joined = false;
-        ~BwdSideGuard() { if (side && !joined) (void)hipStreamSynchronize(side->stream); }
-    } side_guard{ side };
-    if (do_blend && use_sh && D > 0 && o.forward_only) {
-        if (rawin) return fail(GSRAST_E_ARG, "backward_raw: the forward was run with forward_only");
-        if (o.side_stream && R > 0 && !side) {
-            side = side_stream_of(thread_context());
-            if (side) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
-        }
-        hipStream_t ds = side ? side->stream : s;
-        // two waves per compute unit, grid-stride: enough loads in flight for ~1.5 TB/s, few enough not to push the blend kernel's
-        // workgroups off the chip (an unthrottled launch slowed the blend backward by 20 %, this one by 2 %)
-        const int grid = side ? std::min((P + 63) / 64, 512) : (P + 63) / 64;
+    // The side stream is forked here, for the zero rows below as well, and the plan gets its answer: inline and ungrouped if it cannot be had.
+    int fork_derivs()
+    {
+        if (plan.derivs && rawin) return fail(GSRAST_E_ARG, "backward_raw: the forward was run with forward_only");
+        if (plan.wants_side() && (fork.side = side_stream_of(thread_context()))) { GS_HIP(hipEventRecord(fork.side->fork, s)); GS_HIP(hipStreamWaitEvent(fork.side->stream, fork.side->fork, 0)); }
+        plan.side_answer(fork.side != nullptr);
+        if (!plan.derivs) return GSRAST_OK;
+        const hipStream_t ds = plan.derivs_on_side ? fork.side->stream : s;
         {
             ProfScope ps(K_SH_DERIVS, ds);
-            sh_dir_derivs_kernel<<<grid, 64, 0, ds>>>(P, D, M, means3D, shs, campos, radii,
-                                                      at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB), at<float>(geom, GL.shdC));
+            sh_dir_derivs_kernel<<<plan.derivs_grid, 64, 0, ds>>>(c.P, c.D, c.M, c.means3D, c.shs, c.campos, c.radii,
+                                                                  at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB), at<float>(geom, GL.shdC));
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail(GSRAST_E_DEVICE, "sh_dir_derivs", e);
         }
-        if (side) { GS_HIP(hipEventRecord(side->join, side->stream)); side_has_derivs = true; }
+        if (plan.derivs_on_side) GS_HIP(hipEventRecord(fork.side->join, fork.side->stream));
+        return GSRAST_OK;
     }
     // List cut (gsrast_common.h): the zero rows of the Gaussians the forward left out are written on the side stream, beside the blend
     // backward; preprocess_bwd then neither reads nor writes them.  Both kernels check on the device that the forward's cut was in force
     // and held.  Only where it pays for the two events (large scenes), with the sparse per-Gaussian backward, in a one-phase call.
-    bool late_fill = false;
-    if (do_blend && do_geom && R > 0 && !o.dense_backward && o.side_stream && (P >= g_late_fill_min_p.load() || g_list_cut_always.load() != 0)) {
-        if (!side) {
-            side = side_stream_of(thread_context());
-            if (side) { GS_HIP(hipEventRecord(side->fork, s)); GS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0)); }
+    int fork_zero_rows()
+    {
+        if (!plan.late_fill) return GSRAST_OK;
+        LateRowsArgs la{}; int n = 0;
+        auto add = [&](float* p, int rl) { if (p && rl > 0) { la.ptr[n] = p; la.rowlen[n] = rl; n++; } };
+        add(c.dL_dmean2D, 3); add(c.dL_dopacity, 1); add(c.dL_dmean3D, 3); add(c.dL_dconic, 4); add(c.dL_dcolor, 3); add(c.dL_dcov3D, 6);
+        if (rawin || plan.use_sr) { add(c.dL_dscale, 3); add(c.dL_drot, 4); }
+        if (rawin) { add(rawg.d_rot_res, 7); add(rawg.d_trbf, 1); add(rawg.d_shs_res, c.M * 3); add(rawg.d_dc, 3); add(rawg.d_rest, c.M * 3 - 3); }
+        else if (plan.use_sh && !o.sh_grad_factors) add(c.dL_dsh, c.M * 3);
+        la.n = n;
+        if (!plan.skip_zero_rows) {      // (experiments only: the step without the zero rows -- what a caller with persistent outputs could save)
+            ProfScope ps(K_LATE_ZERO, fork.side->stream);
+            late_rows_zero_kernel<<<GSRAST_LATE_FILL_WGS, 256, 0, fork.side->stream>>>(c.P, at<unsigned long long>(geom, GL.color_skip), at<uint32_t>(geom, GL.scalars), la, at<unsigned char>(geom, GL.untouched));
         }
-        if (side) {
-            LateRowsArgs la{}; int n = 0;
-            auto add = [&](float* p, int rl) { if (p && rl > 0) { la.ptr[n] = p; la.rowlen[n] = rl; n++; } };
-            add(dL_dmean2D, 3); add(dL_dopacity, 1); add(dL_dmean3D, 3); add(dL_dconic, 4); add(dL_dcolor, 3); add(dL_dcov3D, 6);
-            if (rawin || use_sr) { add(dL_dscale, 3); add(dL_drot, 4); }
-            if (rawin) { add(rawg.d_rot_res, 7); add(rawg.d_trbf, 1); add(rawg.d_shs_res, M * 3); add(rawg.d_dc, 3); add(rawg.d_rest, M * 3 - 3); }
-            else if (use_sh && !o.sh_grad_factors) add(dL_dsh, M * 3);
-            la.n = n;
-            auto launch_late_fill = [&]() -> int {
-                if (g_ablate.load() != 3)      // (3, experiments only: the step without the zero rows -- what a caller with persistent outputs could save)
-                {   ProfScope ps(K_LATE_ZERO, side->stream);
-                    late_rows_zero_kernel<<<GSRAST_LATE_FILL_WGS, 256, 0, side->stream>>>(P, at<unsigned long long>(geom, GL.color_skip), at<uint32_t>(geom, GL.scalars), la, at<unsigned char>(geom, GL.untouched)); }
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return fail(GSRAST_E_DEVICE, "late_rows_zero", e);
-                GS_HIP(hipEventRecord(side->join, side->stream));
-                return GSRAST_OK;
-            };
-            { int rc = launch_late_fill(); if (rc != GSRAST_OK) return rc; }
-            late_fill = true;
-        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(GSRAST_E_DEVICE, "late_rows_zero", e);
+        GS_HIP(hipEventRecord(fork.side->join, fork.side->stream));
+        return GSRAST_OK;
     }
-    if (do_blend && R > 0) {
+    int blend()
+    {
+        if (!plan.blend) return GSRAST_OK;
         ProfScope ps(K_BLEND_BWD, s);
-        const uint32_t grid = ((T + 7) / 8) * 8;
-        const uint2* ranges = at<uint2>(img, IL.ranges);
-        const float* fT = at<float>(img, IL.final_T); const uint32_t* nc = at<uint32_t>(img, IL.n_contrib);
-        const uint32_t* tm = at<uint32_t>(img, IL.tile_max);
+        const uint32_t T = plan.T, grid = ((T + 7) / 8) * 8;
+        uint2* ranges = at<uint2>(img, IL.ranges); uint32_t* tm = at<uint32_t>(img, IL.tile_max);
         BlendArgs ba{};
-        ba.ranges = ranges; ba.plist = plist; ba.W = W; ba.H = H; ba.gx = cam.gx; ba.T = T; ba.r0 = rec0; ba.r1 = rec1; ba.r2 = rec2;
-        ba.bg = background; ba.fT = const_cast<float*>(fT); ba.nc = const_cast<uint32_t*>(nc); ba.tm = const_cast<uint32_t*>(tm);
-        ba.dpix = dL_dpix; ba.grec = grec;
-        ba.dad = dL_dacc_depth; ba.dal = dL_dalpha;
-        if (const int mut = g_mutate.load()) {      // tests only: see g_mutate
-            if (mut & 1) {
-                mutate_drop_front_batch_kernel<<<1, 256, 0, s>>>(at<uint2>(img, IL.ranges), at<uint32_t>(img, IL.n_contrib), at<uint32_t>(img, IL.tile_max),
-                                                                 (uint32_t)(cam.gy / 2) * (uint32_t)cam.gx + (uint32_t)(cam.gx / 2), W, H, cam.gx);
-                GS_LAUNCHED("mutate_drop_front_batch");
-            }
-            if (mut & 2) {
-                static float* zero_bg = nullptr;      // (never freed: a test-only path)
-                if (!zero_bg) { GS_HIP(hipMalloc((void**)&zero_bg, 16)); GS_HIP(hipMemset(zero_bg, 0, 16)); }
-                ba.bg = zero_bg;
-            }
+        ba.ranges = ranges; ba.plist = at<uint32_t>(c.binning_buffer, 0) /* BinLayout: point_list lives at offset 0 */; ba.W = c.width; ba.H = c.height; ba.gx = cam.gx; ba.T = T;
+        ba.r0 = at<float4>(geom, GL.rec0); ba.r1 = at<float4>(geom, GL.rec1); ba.r2 = at<float4>(geom, GL.rec2);
+        ba.bg = c.background; ba.fT = at<float>(img, IL.final_T); ba.nc = at<uint32_t>(img, IL.n_contrib); ba.tm = tm;
+        ba.dpix = c.dL_dpix; ba.grec = grec;
+        if (plan.aux) { ba.dad = c.dL_dacc_depth; ba.dal = c.dL_dalpha; }      // (either may be null = zero)
+        if (plan.mutate & 1) {      // tests only: see mutate_drop_front_batch_kernel
+            mutate_drop_front_batch_kernel<<<1, 256, 0, s>>>(ranges, ba.nc, tm, (uint32_t)(cam.gy / 2) * (uint32_t)cam.gx + (uint32_t)(cam.gx / 2), c.width, c.height, cam.gx);
+            GS_LAUNCHED("mutate_drop_front_batch");
         }
-        if (bwd_pick.cull && o.lpt) {
-            if (T <= BUCKET_MAX_TILES) {      // the forward blend appended every tile to the backward work buckets
-                ba.bcnt = const_cast<uint32_t*>(at<uint32_t>(img, IL.bucket_cnt)); ba.blist = const_cast<uint16_t*>(at<uint16_t>(img, IL.bucket_list));
-                ba.from_buckets = 1;
-            } else {
-                uint32_t* ord = at<uint32_t>(img, IL.order_bwd);
-                tile_order_kernel<<<1, 1024, 0, s>>>(T, ranges, tm, ord);
-                GS_LAUNCHED("tile_order");
-                ba.order = ord;
-            }
+        if (plan.mutate & 2) {
+            static float* zero_bg = nullptr;      // (never freed: a test-only path)
+            if (!zero_bg) { GS_HIP(hipMalloc((void**)&zero_bg, 16)); GS_HIP(hipMemset(zero_bg, 0, 16)); }
+            ba.bg = zero_bg;
         }
-        launch_blend_bwd(o.exp_mode, bwd_pick, grid, s, ba);
+        if (plan.from_buckets) {
+            ba.bcnt = at<uint32_t>(img, IL.bucket_cnt); ba.blist = at<uint16_t>(img, IL.bucket_list);
+            ba.from_buckets = 1;
+        } else if (plan.tile_order) {
+            uint32_t* ord = at<uint32_t>(img, IL.order_bwd);
+            tile_order_kernel<<<1, 1024, 0, s>>>(T, ranges, tm, ord);
+            GS_LAUNCHED("tile_order");
+            ba.order = ord;
+        }
+        launch_blend_bwd(o.exp_mode, plan.pick, grid, s, ba);
         GS_LAUNCHED("blend_bwd");
+        return GSRAST_OK;
     }
-    if (do_blend && use_sh && o.sh_grad_factors) {      // dL_dsh is [P][3] in this mode: the factor, final after the blend backward
-        sh_factor_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, radii, at<unsigned char>(geom, GL.clamped), reinterpret_cast<const float4*>(grec), dL_dsh, at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched));
+    int sh_factor()      // dL_dsh is [P][3] in this mode: the factor, final after the blend backward
+    {
+        if (!plan.sh_factor) return GSRAST_OK;
+        sh_factor_kernel<<<(c.P + 255) / 256, 256, 0, s>>>(c.P, c.radii, at<unsigned char>(geom, GL.clamped), reinterpret_cast<const float4*>(grec), c.dL_dsh, at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched));
         GS_LAUNCHED("sh_factor");
+        return GSRAST_OK;
     }
-    // The zero rows and the per-Gaussian backward write DISJOINT rows (untouched / touched Gaussians, by the same bits): when they are all the side
-    // stream carries, it is joined BEHIND the per-Gaussian backward -- that kernel neither waits for the last zero row nor pays the join's latency
-    // in front of it (the table-off step showed it waiting 18 us for a fill that had started later than the blend backward)
-    const bool join_late = side && late_fill && !side_has_derivs && do_geom && g_ablate.load() != 5 /* (5, experiments only: the join in front, as before) */;
-    if (side && !join_late) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); side_guard.joined = true; }
-    if (do_geom) {
+    // In front of the per-Gaussian backward -- or, when the zero rows are all the side stream carries, BEHIND it (plan.join_late): that kernel
+    // neither waits for the last zero row nor pays the join's latency in front of it (the table-off step showed it waiting 18 us for a
+    // fill that had started later than the blend backward)
+    int join()
+    {
+        if (fork.side) { GS_HIP(hipStreamWaitEvent(s, fork.side->join, 0)); fork.joined = true; }
+        return GSRAST_OK;
+    }
+    int per_gaussian()
+    {
+        if (!plan.do_geom) return GSRAST_OK;
         ProfScope ps(K_PREPROCESS_BWD, s);
-        const float* cov = cov3D_precomp ? cov3D_precomp : at<float>(geom, GL.cov3D);
-        const int pb_grid = (P + PP_THREADS - 1) / PP_THREADS;
-        const float* sh_in = rawin ? shs : (use_sh ? shs : nullptr);
-        const float* sc_in = rawin ? scales : (use_sr ? scales : nullptr);
-        const float* ro_in = rawin ? rotations : (use_sr ? rotations : nullptr);
-        const int factors = (use_sh && o.sh_grad_factors) ? 1 : 0;
-        const bool skip = !o.dense_backward;        // Gaussians with an all-zero gradient record are not read
+        const int P = c.P;
+        const float* cov = c.cov3D_precomp ? c.cov3D_precomp : at<float>(geom, GL.cov3D);
+        const float* sh_in = rawin ? c.shs : (plan.use_sh ? c.shs : nullptr);
+        const float* sc_in = rawin ? c.scales : (plan.use_sr ? c.scales : nullptr);
+        const float* ro_in = rawin ? c.rotations : (plan.use_sr ? c.rotations : nullptr);
         // <RAW, SPARSE, GROUPED, AA> (aa: the kernel's AA instantiation -- the plain ones are the same code as before the flag existed)
-        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(aa, [&](auto aa_c) {
-            auto launch = [&](auto sparse_c, auto grouped_c, int grid) {
-                preprocess_bwd_kernel<decltype(raw_c)::value, decltype(sparse_c)::value, decltype(grouped_c)::value, decltype(aa_c)::value><<<grid, PP_THREADS, 0, s>>>(
-                    P, D, M, means3D, radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB),
-                    at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, factors, (late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched),
-                    aux ? 1 : 0, rec1);
+        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(plan.aa, [&](auto aa_c) {
+            auto launch = [&](auto sparse_c, auto grouped_c) {
+                preprocess_bwd_kernel<decltype(raw_c)::value, decltype(sparse_c)::value, decltype(grouped_c)::value, decltype(aa_c)::value><<<plan.per_gaussian_grid, PP_THREADS, 0, s>>>(
+                    P, c.D, c.M, c.means3D, c.radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB),
+                    at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), c.dL_dmean2D, c.dL_dconic, c.dL_dopacity, c.dL_dcolor,
+                    c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, plan.factors, (plan.late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched),
+                    plan.aux ? 1 : 0, at<float4>(geom, GL.rec1));
             };
-            // (late_fill implies skip) grouped: 1024 Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
-            if (late_fill) launch(std::true_type{}, std::true_type{}, (P + PB_GROUP - 1) / PB_GROUP);
-            else pick_bool(skip, [&](auto sparse_c) { launch(sparse_c, std::false_type{}, pb_grid); });
+            // (grouped implies sparse)
+            if (plan.grouped) launch(std::true_type{}, std::true_type{});
+            else pick_bool(plan.sparse, [&](auto sparse_c) { launch(sparse_c, std::false_type{}); });
         }); });
         GS_LAUNCHED("preprocess_bwd");
+        return GSRAST_OK;
     }
-    if (join_late) { GS_HIP(hipStreamWaitEvent(s, side->join, 0)); side_guard.joined = true; }
-    return GSRAST_OK;
+};
+} // namespace
+
+// The one backward: checks -> plan -> zero-fill -> [fork: direction derivatives, zero rows] -> blend backward -> factor -> join and
+// per-Gaussian backward, in the order the plan says
+static int backward_impl(const gsrast_options* options, const BwdCall& c)
+{
+    RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
+    BackwardRun r(options, c);
+    int rc = r.check_and_plan();
+    if (rc != GSRAST_OK || c.P == 0) return rc;
+    if ((rc = r.zero_records()) != GSRAST_OK || (rc = r.fork_derivs()) != GSRAST_OK || (rc = r.fork_zero_rows()) != GSRAST_OK) return rc;
+    if ((rc = r.blend()) != GSRAST_OK || (rc = r.sh_factor()) != GSRAST_OK) return rc;
+    if (!r.plan.join_late && (rc = r.join()) != GSRAST_OK) return rc;
+    if ((rc = r.per_gaussian()) != GSRAST_OK) return rc;
+    return r.plan.join_late ? r.join() : GSRAST_OK;
 }
 
 // ---- the exported backwards: adapters that fill a BwdCall (include/gsrast.h: gsrast_backward = _ex(NULL) = _flags(0), _aux = _flags(AUX)) ----
@@ -2545,7 +2524,7 @@ int gsrast_debug_export(int P, int R, int width, int height, const char* geom_bu
 {
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0 || !geom_buffer) return fail(GSRAST_E_ARG, "debug_export: bad arguments");
-    if (cov3D && !g_debug_state.load()) return fail(GSRAST_E_ARG, "debug_export: cov3D is only kept by forwards run with gsrast_set_option(\"debug_state\", 1)");
+    if (cov3D && !g_opt.debug_state.load()) return fail(GSRAST_E_ARG, "debug_export: cov3D is only kept by forwards run with gsrast_set_option(\"debug_state\", 1)");
     const GeomLayout GL = geom_layout((size_t)P);
     const ImgLayout IL = img_layout((size_t)width, (size_t)height);
     const uint32_t T = (uint32_t)((width + TILE_X - 1) / TILE_X) * (uint32_t)((height + TILE_Y - 1) / TILE_Y);

@@ -1,13 +1,14 @@
-// gsrast_policy.h -- the HOST-side decisions of the forward, free of any HIP call: when the list cut is applied, paused and widened, how
-// the speculative launch is sized, how the depth histogram's range follows the scene, which path a call takes (ForwardPlan).  gsrast_capi.hip
-// enqueues; this file decides.  Everything here runs on a CPU box: tests/test_policy.py drives it through gsrast_policy_event() and
-// gsrast_debug_forward_plan() (include/gsrast.h) on a context that never touches a device.  No result of a call depends on any of it -- only how much work the call enqueues.
+// gsrast_policy.h -- the HOST-side decisions of a render call, free of any HIP call: when the list cut is applied, paused and widened, how
+// the speculative launch is sized, how the depth histogram's range follows the scene, which path a call takes (ForwardPlan, BackwardPlan).  gsrast_capi.hip
+// enqueues; this file decides.  Everything here runs on a CPU box: tests/test_policy.py drives it through gsrast_policy_event(),
+// gsrast_debug_forward_plan() and gsrast_debug_backward_plan() (include/gsrast.h), which touch no device.  No result of a call depends on any of it -- only how much work the call enqueues.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
 #include <atomic>
 #include "../../include/gsrast.h"   // (gsrast_options, GSRAST_RENDER_*)
 #include "gsrast_common.h"     // (the depth histogram's bin geometry: ZH_*, zh_bin_start)
+#include "gsrast_preprocess.h" // (the per-Gaussian backward's workgroup sizes: PP_THREADS, PB_GROUP)
 
 namespace gsrast {
 
@@ -165,7 +166,8 @@ inline bool options_valid(const gsrast_options& o)
 }
 // "the culled blend kernel runs".  Forward: a forced pixels-per-lane selects the un-culled template; backward: it picks among the culled ones.
 inline bool culled_blend(const gsrast_options& o, bool backward) { return o.cull != 0 && (backward || o.fwd_pixels_per_lane == 0); }
-struct PlanSwitches { bool list_cut_always, tau_cut, touch_bits, sparse_grec, two_level, chain_gate, sort_hint, debug_state; int two_level_min_p, tau_sample; };   // the g_* A/B switches, read once per call
+struct PlanSwitches { bool list_cut_always, tau_cut, touch_bits, sparse_grec, two_level, chain_gate, sort_hint, debug_state; int two_level_min_p, tau_sample;      // the process-wide A/B switches, read once per call
+                      bool bwd_transposed; int late_fill_min_p, ablate, mutate; };                                                                                  // ... the backward's
 struct PlanInputs { unsigned flags; int P, W, H, D; bool sh, colors_precomp; int bucket_skip; uint32_t R_hint, last_Q; bool depth_short; };      // the call's shape; the context's words
 struct ForwardPlan {
     const char* refusal = nullptr;      // GSRAST_E_ARG with this text: unknown flags, a bad option value, aux without the culled kernel (in this order)
@@ -220,6 +222,79 @@ inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, c
     p.spec_eligible = p.runbin && o.speculative != 0;
     p.adaptive_sort = rs_blocks_n(P, GSRAST_DEPTH_ITEMS) > RS_SELF_SCAN_BLOCKS;      // see radix_sort
     p.assume_short = p.adaptive_sort && g.sort_hint && in.depth_short;
+    return p;
+}
+
+// ---- the backward's plan ---------------------------------------------------------------------------------------------------------------
+// The same for a backward call: everything that follows from its options, flags and shape, the kind of its inputs and the one snapshot of the
+// switches (plan_backward).  Whether the context's side stream could be had is the one second-phase answer (side_answer).
+// tests/test_policy.py reads the plan through gsrast_debug_backward_plan.
+struct BackwardInputs { unsigned flags; int P, D, R, W, H; bool raw_family, sh, colors_precomp, cov3D_precomp, aux_grads /* dL_dacc_depth or dL_dalpha is given */; };
+// Which blend backward runs.  transposed: blend_bwd_cull_t_kernel; ablate 1 / 2: blend_bwd_kernel<0, 4, ablate> (experiments), else 0
+struct BlendBwdPick { int ppl = 1; bool cull = false, transposed = false, aux = false; int ablate = 0; };
+struct BackwardPlan {
+    const char* refusal = nullptr;      // GSRAST_E_ARG with this text: unknown flags, a bad option value, aux without the culled kernels (in this order)
+    bool aux = false, aa = false;                     // an aux gradient is given (both NULL is the plain backward); the state comes from an anti-aliased forward
+    bool do_blend = false, do_geom = false;           // options.backward_phase: the blend backward / the per-Gaussian backward is part of this call
+    bool use_sh = false, use_sr = false;              // colours from SH coefficients; covariances from scales + rotations
+    bool zero_records = false;                        // the gradient records are zero-filled (the caller does not vouch for them, or the forward was told no backward would follow)
+    bool derivs = false, derivs_side_wanted = false;  // sh_dir_derivs runs (a forward_only state); ... beside the blend backward
+    bool late_fill_wanted = false;                    // the untouched Gaussians' zero rows beside the blend backward: one-phase sparse call, large scene (or list_cut_always)
+    bool skip_zero_rows = false, join_in_front = false;   // experiments only (ablate 3: late fill without its kernel; 5: the join never moves behind preprocess_bwd)
+    bool blend = false, from_buckets = false, tile_order = false;     // the blend backward runs (R > 0); its launch order from the forward's work buckets / from tile_order_kernel
+    BlendBwdPick pick; uint32_t T = 0; int P = 0;
+    bool sh_factor = false; int factors = 0;          // sh_factor_kernel runs (dL_dsh is the [P][3] factor); preprocess_bwd leaves dL_dsh to it
+    bool sparse = false;                              // preprocess_bwd does not read Gaussians whose gradient record is all zero
+    int mutate = 0;                                   // tests only: a backward that is wrong on purpose (bit 0: one tile's front batch dropped, bit 1: zero background)
+    // second phase: what the side stream carries; preprocess_bwd<.., GROUPED, ..>; the join behind preprocess_bwd; the grids that follow
+    bool derivs_on_side = false, late_fill = false, grouped = false, join_late = false; int derivs_grid = 0, per_gaussian_grid = 0;
+    bool wants_side() const { return derivs_side_wanted || late_fill_wanted; }
+    void side_answer(bool acquired)
+    {
+        derivs_on_side = derivs_side_wanted && acquired; late_fill = late_fill_wanted && acquired; grouped = late_fill;
+        // The zero rows and the per-Gaussian backward write DISJOINT rows: when they are all the side stream carries, it is joined BEHIND preprocess_bwd
+        join_late = late_fill && !derivs_on_side && !join_in_front;
+        // two waves per compute unit, grid-stride: enough loads in flight for ~1.5 TB/s, few enough not to push the blend kernel's
+        // workgroups off the chip (an unthrottled launch slowed the blend backward by 20 %, this one by 2 %)
+        derivs_grid = !derivs ? 0 : derivs_on_side ? std::min((P + 63) / 64, 512) : (P + 63) / 64;
+        // grouped: PB_GROUP Gaussians per workgroup, the ones late_rows_zero_kernel does not write compacted
+        per_gaussian_grid = !do_geom ? 0 : grouped ? (P + PB_GROUP - 1) / PB_GROUP : (P + PP_THREADS - 1) / PP_THREADS;
+    }
+};
+inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs& in, const PlanSwitches& g)
+{
+    BackwardPlan p;
+    const bool aux_flag = (in.flags & GSRAST_RENDER_AUX) != 0;
+    p.aux = aux_flag && in.aux_grads; p.aa = (in.flags & GSRAST_RENDER_ANTIALIAS) != 0;
+    p.pick.cull = culled_blend(o, true);
+    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) p.refusal = "flags: unknown bits";
+    else if (!options_valid(o)) p.refusal = "backward: bad option value";
+    else if (aux_flag && !p.pick.cull) p.refusal = "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)";
+    if (p.refusal || in.P <= 0 || in.R < 0 || in.W <= 0 || in.H <= 0) return p;      // (the shape is refused, or there is nothing to do)
+    p.P = in.P; p.do_blend = o.backward_phase != 2; p.do_geom = o.backward_phase != 1;
+    p.use_sh = in.sh && !in.colors_precomp; p.use_sr = !in.cov3D_precomp;
+    p.zero_records = p.do_blend && (!o.grads_zeroed || o.forward_only);
+    p.derivs = p.do_blend && p.use_sh && in.D > 0 && o.forward_only;
+    p.derivs_side_wanted = p.derivs && o.side_stream && in.R > 0;
+    p.late_fill_wanted = p.do_blend && p.do_geom && in.R > 0 && !o.dense_backward && o.side_stream && (in.P >= g.late_fill_min_p || g.list_cut_always);
+    p.skip_zero_rows = g.ablate == 3; p.join_in_front = g.ablate == 5;
+    p.T = (uint32_t)((in.W + TILE_X - 1) / TILE_X) * (uint32_t)((in.H + TILE_Y - 1) / TILE_Y);
+    // Pixels per lane, measured on MI355X (profiles/): with per-wave accumulator slices the backward is within 2 % for 1, 2 and 4 at 1080p
+    // and above; fewer win for small images (more waves) and small Gaussians (finer culling), more win at 4K.
+    const int forced = o.bwd_pixels_per_lane;
+    p.pick.ppl = forced ? forced : p.T >= 32768 ? 4 : (p.T >= 8192 ? 2 : 1);
+    p.pick.aux = p.aux;
+    p.pick.ablate = (!p.aux && (g.ablate == 1 || g.ablate == 2)) ? g.ablate : 0;
+    // aux: always the transposed kernel, whatever the pixels per lane and the A/B switch say
+    p.pick.transposed = p.aux || (p.pick.cull && !p.pick.ablate && p.pick.ppl == 1 && g.bwd_transposed);
+    p.blend = p.do_blend && in.R > 0;
+    const bool ordered = p.blend && p.pick.cull && o.lpt != 0;
+    p.from_buckets = ordered && p.T <= BUCKET_MAX_TILES;      // the forward blend appended every tile to the backward work buckets
+    p.tile_order = ordered && !p.from_buckets;
+    p.factors = (p.use_sh && o.sh_grad_factors) ? 1 : 0;
+    p.sh_factor = p.do_blend && p.factors;      // the factor is final after the blend backward
+    p.sparse = !o.dense_backward;
+    p.mutate = p.blend ? g.mutate : 0;
     return p;
 }
 

@@ -1,4 +1,5 @@
 """CPU: the host-side mirror of the reference's Python interface (no GPU needed)."""
+import ctypes as C
 import inspect
 
 import pytest
@@ -227,3 +228,107 @@ def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
             assert np.all(np.diff(px) > 0) and px[-1] < H * W
             assert np.array_equal(files["color"], cap["color"].numpy().reshape(3, -1)[:, px])
             assert np.array_equal(files["depth"], cap["depth"].numpy().reshape(1, -1)[:, px])
+
+
+# ---- gsrast_set_option / gsrast_get_option: every name, every kind of value (saro-gs_amd/csrc/gsrast_capi.hip: the option table) ----
+E_ARG = -1
+FLAG, ONE_OF, CLAMP, WORD = "non-zero means 1", "one of a set, else GSRAST_E_ARG", "clamped to a range", "stored as given"
+INT_MAX = 2**31 - 1
+OPTION_TABLE = dict(      # name: (default, kind, the accepted set / the range)
+    debug_sync=(0, FLAG, None), list_cut_always=(0, FLAG, None), chain_gate=(1, FLAG, None), touch_bits=(1, FLAG, None), sparse_grec=(1, FLAG, None),
+    tau_cut=(1, FLAG, None), debug_state=(0, FLAG, None), two_level=(1, FLAG, None), bwd_transposed=(1, FLAG, None), sort_hint=(1, FLAG, None),
+    cull=(1, FLAG, None), tile_clip=(1, FLAG, None), sh_grad_factors=(0, FLAG, None), speculative=(1, FLAG, None), side_stream=(1, FLAG, None),
+    forward_only=(0, FLAG, None), no_order_hint=(0, FLAG, None), dense_backward=(0, FLAG, None), no_list_cut=(0, FLAG, None), lpt=(1, FLAG, None),
+    exp_mode=(0, ONE_OF, (0, 1, 2)), binning=(0, ONE_OF, (0, 1)), depth_sort=(0, ONE_OF, (0, 1)), hexplane_scatter=(0, ONE_OF, (0, 1)),
+    fwd_pixels_per_lane=(0, ONE_OF, (0, 1, 2, 4)), bwd_pixels_per_lane=(0, ONE_OF, (0, 1, 2, 4)),
+    tau_sample=(1, CLAMP, (0, 6)), late_fill_min_p=(750000, CLAMP, (0, INT_MAX)), two_level_min_p=(2500000, CLAMP, (0, INT_MAX)),
+    profile=(0, WORD, None), ablate=(0, WORD, None), mutate=(0, WORD, None))
+CONTEXT_WORDS = ("last_instances", "last_runs", "redo_count", "bucket_skip")      # read-only: gsrast_context_query(NULL, name)
+
+
+@pytest.fixture()
+def option_calls(rast):
+    L = rast._C.lib()
+    return (lambda name, v: L.gsrast_set_option(name.encode(), v)), (lambda name: L.gsrast_get_option(name.encode())), L
+
+
+@pytest.mark.parametrize("name", sorted(OPTION_TABLE))
+def test_every_option_name_default_values_refusals(option_calls, name):
+    """The default; set-then-get for every kind of value (what is stored, not what was passed); every refusal leaves the stored value alone;
+    the default restored at the end."""
+    set_, get, _ = option_calls
+    default, kind, arg = OPTION_TABLE[name]
+    assert get(name) == default
+    try:
+        if kind == FLAG:
+            for v, stored in ((0, 0), (1, 1), (0, 0), (7, 1), (-3, 1), (INT_MAX, 1), (0, 0)):
+                assert set_(name, v) == 0 and get(name) == stored, v
+        elif kind == ONE_OF:
+            for v in arg + arg[::-1]:
+                assert set_(name, v) == 0 and get(name) == v, v
+            assert set_(name, arg[-1]) == 0
+            for bad in (-1, -4, 3, 5, 7, 8, 31, 32, 33, 34, 36, 64, 1 << 20, INT_MAX, -INT_MAX - 1):
+                if bad not in arg:
+                    assert set_(name, bad) == E_ARG and get(name) == arg[-1], bad
+        elif kind == CLAMP:
+            lo, hi = arg
+            for v, stored in ((lo, lo), (lo - 1, lo), (-INT_MAX - 1, lo), (lo + 1, lo + 1), (hi, hi), (min(hi, 5), min(hi, 5)), (INT_MAX, hi)):
+                assert set_(name, v) == 0 and get(name) == stored, v
+            if hi < INT_MAX:
+                assert set_(name, hi + 1) == 0 and get(name) == hi
+        else:
+            for v in (5, -1, 7, INT_MAX, -INT_MAX - 1, 0):
+                assert set_(name, v) == 0 and get(name) == v, v
+    finally:
+        assert set_(name, default) == 0
+    assert get(name) == default
+
+
+def test_the_option_names_that_are_not_plain_words(option_calls):
+    set_, get, L = option_calls
+    fwd, bwd = "fwd_pixels_per_lane", "bwd_pixels_per_lane"
+    try:      # "pixels_per_lane" writes both directions and reads the forward's
+        assert get("pixels_per_lane") == 0
+        assert set_("pixels_per_lane", 2) == 0 and (get(fwd), get(bwd), get("pixels_per_lane")) == (2, 2, 2)
+        assert set_(fwd, 4) == 0 and (get(fwd), get(bwd), get("pixels_per_lane")) == (4, 2, 4)
+        assert set_(bwd, 1) == 0 and (get(fwd), get(bwd), get("pixels_per_lane")) == (4, 1, 4)
+        for bad in (3, -1, 8, 32, 34):
+            assert set_("pixels_per_lane", bad) == E_ARG and (get(fwd), get(bwd)) == (4, 1)
+    finally:
+        assert set_("pixels_per_lane", 0) == 0
+    assert (get(fwd), get(bwd)) == (0, 0)
+    # "word_fork" (removed; bench.py reports it) reads 0 and accepts only 0
+    assert get("word_fork") == 0 and set_("word_fork", 0) == 0
+    for bad in (1, -1, 7):
+        assert set_("word_fork", bad) == E_ARG and get("word_fork") == 0
+    # the context's words are read-only
+    L.gsrast_context_query.restype = C.c_int
+    for name in CONTEXT_WORDS:
+        assert get(name) == L.gsrast_context_query(None, name.encode()) >= 0
+        assert set_(name, 0) == E_ARG and set_(name, 1) == E_ARG
+    # the other context words are not options
+    for name in ("last_late", "cut_pause", "no_such_option", "", "g_ablate", "Cull", "cull "):
+        assert get(name) == E_ARG and set_(name, 0) == E_ARG and set_(name, 1) == E_ARG, name
+    assert L.gsrast_get_option(None) == E_ARG and L.gsrast_set_option(None, 1) == E_ARG
+
+
+def test_python_option_tables_match_the_library(option_calls, rast):
+    """_C._OPTION_DEFAULTS / _OPTION_RANGE / PER_CALL_OPTIONS (the per-thread options of the Python side) against gsrast_options_init, the
+    process defaults and what gsrast_set_option accepts."""
+    set_, get, L = option_calls
+    _C = rast._C
+    o = _C.OptionsStruct()
+    for name, _ in o._fields_:
+        setattr(o, name, 0x5A5A)
+    L.gsrast_options_init(C.byref(o))
+    init = {name: getattr(o, name) for name, _ in o._fields_}
+    assert set(_C._OPTION_DEFAULTS) == set(_C.PER_CALL_OPTIONS) == set(init) - {"sh_grad_factors", "grads_zeroed", "backward_phase"}
+    assert init["sh_grad_factors"] == init["grads_zeroed"] == init["backward_phase"] == 0
+    for name, v in _C._OPTION_DEFAULTS.items():
+        assert init[name] == v == get(name) == OPTION_TABLE[name][0], name
+    assert get("sh_grad_factors") == 0
+    ranged = {n: a for n, (_, kind, a) in OPTION_TABLE.items() if kind == ONE_OF and n in init}
+    assert _C._OPTION_RANGE == ranged
+    for name in _C._OPTION_DEFAULTS:      # everything else the Python side normalises to 0 / 1, as the library does
+        if name not in ranged:
+            assert OPTION_TABLE[name][1] == FLAG, name

@@ -95,7 +95,7 @@ BITES = [FULL[0], FULL[3]]
 
 @pytest.mark.parametrize("name,P,W,H", BITES, ids=[c[0] for c in BITES])
 def test_the_gradient_bar_bites(name, P, W, H, orc, scenes, rast, gpu):
-    """the full-size gradient bar must be able to fail.  Option "mutate" = 1 (tests only, csrc/gsrast_capi.hip: g_mutate)
+    """the full-size gradient bar must be able to fail.  Option "mutate" = 1 (tests only, csrc/gsrast_capi.hip: mutate_drop_front_batch_kernel)
     makes the blend backward of ONE tile -- the image's centre tile, 1 of 2 500 / 8 160 -- miss the 64 front-most entries of its list: one
     staged batch dropped, every other (pixel, Gaussian) pair untouched (reference: backward.cu:472-557 walks the whole range).  The
     unmutated backward passes _check_grads, the mutated one must not -- at cfg2 and at cfg5 (3 M @ 1080p), where rounds 1-5's absolute

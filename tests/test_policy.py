@@ -1,5 +1,5 @@
-"""CPU: the host-side decisions of a gsrast_context (saro-gs_amd/csrc/gsrast_policy.h) driven through gsrast_policy_event -- no device is
-touched: when the list cut is applied, paused and put on probation, how its margin and the predicted cut's requirement follow the
+"""CPU: the host-side decisions of a gsrast_context and of a render call (saro-gs_amd/csrc/gsrast_policy.h) driven through gsrast_policy_event,
+gsrast_debug_forward_plan and gsrast_debug_backward_plan -- no device is touched: when the list cut is applied, paused and put on probation, how its margin and the predicted cut's requirement follow the
 completion passes the device reports, how the speculative launch is sized."""
 import pytest
 
@@ -218,7 +218,7 @@ def plan(rast, ctx):
             return fn(ctx.handle, C.byref(o), flags, P, W, H, words)
         finally:
             for name, v in switched.items():
-                L.gsrast_set_option(name.encode(), v)
+                assert L.gsrast_set_option(name.encode(), v) == 0 and L.gsrast_get_option(name.encode()) == v
     run.error = lambda: L.gsrast_last_error().decode()
     return run
 
@@ -304,3 +304,185 @@ def test_plan_refusals_keep_their_texts(plan):
     assert plan(flags=8) == -1 and plan.error() == "flags: unknown bits"
     assert plan(fwd_pixels_per_lane=3) == -1 and plan.error() == "forward: bad option value"
     assert plan(flags=8, fwd_pixels_per_lane=3) == -1 and plan.error() == "flags: unknown bits"      # (the order of the checks)
+
+
+# ---- the backward's plan (gsrast_policy.h: BackwardPlan) through gsrast_debug_backward_plan: what a backward WOULD decide, no device involved ----
+(B_AUX, B_AA, B_DO_BLEND, B_DO_GEOM, B_ZERO_RECORDS, B_DERIVS, B_DERIVS_ON_SIDE, B_LATE_FILL_WANTED, B_LATE_FILL, B_SKIP_ZERO_ROWS, B_JOIN_LATE, B_BLEND, B_CULL,
+ B_TRANSPOSED, B_PICK_AUX, B_BUCKETS, B_TILE_ORDER, B_SH_FACTOR, B_FACTORS, B_SPARSE, B_GROUPED) = (1 << k for k in range(21))
+ANTIALIAS = 2
+
+
+class BwdPlan(int):
+    ppl = property(lambda v: v >> 21 & 7)
+    ablate = property(lambda v: v >> 24 & 3)
+    mutate = property(lambda v: v >> 26 & 3)
+
+
+@pytest.fixture()
+def bplan(rast):
+    import ctypes as C
+    L = rast._C.lib()
+    fn = C.CDLL(rast._C.LIB_PATH).gsrast_debug_backward_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    switched = {}
+
+    def run(P=3_000_000, D=3, R=40_000_000, W=1920, H=1080, flags=0, raw=0, sh=1, precomp=0, cov3D=0, aux_grads=0, side=1, switches=None, **opts):
+        for name, v in (switches or {}).items():
+            switched.setdefault(name, L.gsrast_get_option(name.encode()))
+            assert L.gsrast_set_option(name.encode(), v) == 0
+        o = rast._C.OptionsStruct()
+        L.gsrast_options_init(C.byref(o))
+        for k, v in opts.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        words = (C.c_int * 7)(P, D, R, W, H, raw | sh << 1 | precomp << 2 | cov3D << 3 | aux_grads << 4, side)
+        grids = (C.c_int * 2)(-1, -1)
+        try:
+            v = fn(C.byref(o), flags, words, grids)
+            run.grids = tuple(grids)
+            return BwdPlan(v) if v >= 0 else v
+        finally:
+            for name, v in switched.items():
+                assert L.gsrast_set_option(name.encode(), v) == 0 and L.gsrast_get_option(name.encode()) == v
+    run.error = lambda: L.gsrast_last_error().decode()
+    return run
+
+
+B_DEFAULT = (B_DO_BLEND | B_DO_GEOM | B_ZERO_RECORDS | B_LATE_FILL_WANTED | B_LATE_FILL | B_JOIN_LATE | B_BLEND | B_CULL | B_TRANSPOSED | B_BUCKETS
+             | B_SPARSE | B_GROUPED)
+
+
+def test_backward_plan_of_the_default_path(bplan):
+    """3 M Gaussians at 1080p: transposed blend from the work buckets, zero rows beside it, grouped sparse preprocess_bwd, join behind it."""
+    v = bplan()
+    assert v & (1 << 21) - 1 == B_DEFAULT, bin(v ^ B_DEFAULT)
+    assert (v.ppl, v.ablate, v.mutate) == (1, 0, 0)
+    assert bplan.grids == (0, (3_000_000 + 1023) // 1024)      # no sh_dir_derivs; PB_GROUP = 1024 Gaussians per workgroup
+    assert bplan(flags=ANTIALIAS) == v | B_AA
+
+
+def test_backward_plan_late_fill_conditions(bplan):
+    lost = B_LATE_FILL_WANTED | B_LATE_FILL | B_JOIN_LATE | B_GROUPED
+    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(backward_phase=2), dict(R=0), dict(P=749_999)):
+        v = bplan(**kw)
+        assert not v & lost, kw
+        assert bool(v & B_SPARSE) == ("dense_backward" not in kw)
+        if v & B_DO_GEOM:
+            assert bplan.grids[1] == (kw.get("P", 3_000_000) + 127) // 128, kw      # ungrouped: PP_THREADS = 128 Gaussians per workgroup
+    assert bplan(P=750_000) & lost == lost
+    assert bplan(P=749_999, switches=dict(late_fill_min_p=0)) & lost == lost
+    assert bplan(P=1000, switches=dict(list_cut_always=1)) & lost == lost      # regained
+    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(backward_phase=2), dict(R=0)):
+        assert not bplan(P=1000, switches=dict(list_cut_always=1), **kw) & lost, kw
+    # the phases
+    v = bplan(backward_phase=1)
+    assert v & B_DO_BLEND and v & B_BLEND and v & B_ZERO_RECORDS and not v & B_DO_GEOM and bplan.grids == (0, 0)
+    v = bplan(backward_phase=2)
+    assert v & B_DO_GEOM and not v & (B_DO_BLEND | B_BLEND | B_ZERO_RECORDS | B_BUCKETS | B_SH_FACTOR)
+    v = bplan(R=0)
+    assert v & B_DO_BLEND and v & B_ZERO_RECORDS and not v & (B_BLEND | B_BUCKETS | B_TILE_ORDER)
+
+
+def test_backward_plan_without_a_side_stream(bplan):
+    v = bplan(side=0)      # side_stream_of returned null: late fill wanted and not had, the ungrouped sparse kernel
+    assert v & B_LATE_FILL_WANTED and v & B_SPARSE and not v & (B_LATE_FILL | B_GROUPED | B_JOIN_LATE)
+    assert bplan.grids == (0, (3_000_000 + 127) // 128)
+    v = bplan(side=0, forward_only=1)      # ... and sh_dir_derivs inline with the full grid
+    assert v & B_DERIVS and not v & (B_DERIVS_ON_SIDE | B_LATE_FILL | B_GROUPED | B_JOIN_LATE)
+    assert bplan.grids == ((3_000_000 + 63) // 64, (3_000_000 + 127) // 128)
+
+
+def test_backward_plan_of_a_forward_only_state(bplan):
+    v = bplan(forward_only=1, grads_zeroed=1)      # the forward has not zeroed the records, whatever the caller says
+    assert v & B_ZERO_RECORDS and v & B_DERIVS and v & B_DERIVS_ON_SIDE and v & B_LATE_FILL and v & B_GROUPED
+    assert not v & B_JOIN_LATE      # the side stream carries derivatives preprocess_bwd reads: joined in front
+    assert bplan.grids[0] == 512
+    assert bplan(P=10_000, forward_only=1) & B_DERIVS_ON_SIDE and bplan.grids[0] == (10_000 + 63) // 64
+    for kw in (dict(side_stream=0), dict(R=0)):      # inline
+        v = bplan(forward_only=1, **kw)
+        assert v & B_DERIVS and not v & B_DERIVS_ON_SIDE and bplan.grids[0] == (3_000_000 + 63) // 64, kw
+    for kw in (dict(D=0), dict(precomp=1), dict(sh=0, precomp=1), dict(backward_phase=2)):      # nothing to differentiate / not this phase
+        assert not bplan(forward_only=1, **kw) & (B_DERIVS | B_DERIVS_ON_SIDE), kw
+    v = bplan(forward_only=1, backward_phase=1)      # phase 1 of two: derivatives beside the blend, no zero rows
+    assert v & B_DERIVS_ON_SIDE and not v & (B_LATE_FILL | B_JOIN_LATE)
+    assert not bplan() & B_DERIVS
+
+
+def test_backward_plan_grads_zeroed(bplan):
+    assert bplan() & B_ZERO_RECORDS and not bplan(grads_zeroed=1) & B_ZERO_RECORDS
+    assert not bplan(backward_phase=2) & B_ZERO_RECORDS and not bplan(grads_zeroed=1, backward_phase=1) & B_ZERO_RECORDS
+
+
+def test_backward_plan_launch_order(bplan):
+    assert bplan(W=16 * 255, H=16 * 257) & B_BUCKETS and not bplan(W=16 * 255, H=16 * 257) & B_TILE_ORDER      # 65535 tiles: BUCKET_MAX_TILES
+    v = bplan(W=16 * 256, H=16 * 256)                                                                         # 65536
+    assert v & B_TILE_ORDER and not v & B_BUCKETS
+    for kw in (dict(lpt=0), dict(cull=0)):
+        assert not bplan(**kw) & (B_BUCKETS | B_TILE_ORDER), kw
+        assert not bplan(W=16 * 256, H=16 * 256, **kw) & (B_BUCKETS | B_TILE_ORDER), kw
+
+
+def test_backward_plan_blend_kernel(bplan):
+    # pixels per lane by tile count: 1 below 8192 tiles, 2 from there, 4 from 32768; forced
+    for W, H, ppl in ((1920, 1080, 1), (16 * 128, 16 * 64 - 1, 2), (16 * 128 - 1, 16 * 64, 2), (16 * 127, 16 * 64, 1), (16 * 256, 16 * 128, 4), (16 * 256, 16 * 127, 2)):
+        v = bplan(W=W, H=H)
+        assert v.ppl == ppl and v & B_CULL and bool(v & B_TRANSPOSED) == (ppl == 1), (W, H)
+    for forced in (1, 2, 4):
+        for W, H in ((1920, 1080), (3840, 2160), (16 * 256, 16 * 128)):
+            v = bplan(W=W, H=H, bwd_pixels_per_lane=forced)
+            assert v.ppl == forced and v & B_CULL and bool(v & B_TRANSPOSED) == (forced == 1), (forced, W)
+    assert bplan(fwd_pixels_per_lane=2).ppl == 1      # the forward's is not the backward's
+    v = bplan(switches=dict(bwd_transposed=0))
+    assert v & B_CULL and not v & B_TRANSPOSED and v.ppl == 1
+    v = bplan(cull=0)
+    assert not v & (B_CULL | B_TRANSPOSED | B_BUCKETS) and v.ppl == 1
+    # aux forces the transposed kernel, whatever the pixels per lane and the A/B switch say
+    for kw in (dict(), dict(bwd_pixels_per_lane=4), dict(W=3840, H=2160), dict(switches=dict(bwd_transposed=0))):
+        v = bplan(flags=AUX, aux_grads=1, **kw)
+        assert v & B_AUX and v & B_PICK_AUX and v & B_TRANSPOSED, kw
+    v = bplan(flags=AUX, aux_grads=0)      # both aux gradients NULL: the plain backward
+    assert v == bplan() and not v & (B_AUX | B_PICK_AUX)
+    assert not bplan(flags=0, aux_grads=1) & (B_AUX | B_PICK_AUX)      # without the flag the pointers are not looked at
+
+
+def test_backward_plan_ablate_and_mutate(bplan):
+    for a in (1, 2):
+        v = bplan(switches=dict(ablate=a))
+        assert v.ablate == a and not v & B_TRANSPOSED and v & B_LATE_FILL and v & B_JOIN_LATE
+        v = bplan(flags=AUX, aux_grads=1, switches=dict(ablate=a))      # ignored under aux
+        assert v.ablate == 0 and v & B_TRANSPOSED and v & B_PICK_AUX
+    v = bplan(switches=dict(ablate=3))      # late fill without its kernel: everything else as if the rows had been written
+    assert v & B_SKIP_ZERO_ROWS and v & B_LATE_FILL and v & B_GROUPED and v & B_JOIN_LATE and v.ablate == 0 and v & B_TRANSPOSED
+    v = bplan(switches=dict(ablate=5))      # the join in front
+    assert v & B_LATE_FILL and v & B_GROUPED and not v & (B_JOIN_LATE | B_SKIP_ZERO_ROWS) and v.ablate == 0
+    assert bplan(switches=dict(ablate=4)) == bplan() and bplan(switches=dict(ablate=-1)) == bplan()
+    for m in (1, 2, 3):
+        assert bplan(switches=dict(mutate=m)).mutate == m
+    assert bplan(switches=dict(mutate=3), backward_phase=2).mutate == 0 and bplan(switches=dict(mutate=3), R=0).mutate == 0      # no blend backward to mutate
+    assert bplan().mutate == 0      # (the fixture restored the switch)
+
+
+def test_backward_plan_sh_grad_factors(bplan):
+    v = bplan(sh_grad_factors=1)
+    assert v & B_SH_FACTOR and v & B_FACTORS and v & B_LATE_FILL
+    assert not bplan() & (B_SH_FACTOR | B_FACTORS)
+    v = bplan(sh_grad_factors=1, backward_phase=1)      # the factor is final after the blend backward: all a multi-GPU caller needs to start its exchange
+    assert v & B_SH_FACTOR and v & B_FACTORS
+    v = bplan(sh_grad_factors=1, backward_phase=2)
+    assert v & B_FACTORS and not v & B_SH_FACTOR
+    for kw in (dict(precomp=1), dict(sh=0, precomp=1)):
+        assert not bplan(sh_grad_factors=1, **kw) & (B_SH_FACTOR | B_FACTORS), kw
+    assert bplan(sh_grad_factors=1, raw=1) & B_SH_FACTOR
+
+
+def test_backward_plan_refusals_keep_their_texts(bplan):
+    assert bplan(flags=AUX, aux_grads=1) & B_AUX and bplan(flags=AUX, aux_grads=1, bwd_pixels_per_lane=2) & B_AUX
+    for aux_grads in (0, 1):      # the rule is checked first: also with both gradients NULL
+        assert bplan(flags=AUX, aux_grads=aux_grads, cull=0) == -1
+        assert bplan.error() == "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)"
+    assert bplan(flags=8) == -1 and bplan.error() == "flags: unknown bits"
+    for kw in (dict(bwd_pixels_per_lane=3), dict(backward_phase=3), dict(dense_backward=2), dict(exp_mode=3)):
+        assert bplan(**kw) == -1 and bplan.error() == "backward: bad option value", kw
+    assert bplan(flags=8, bwd_pixels_per_lane=3) == -1 and bplan.error() == "flags: unknown bits"      # (the order of the checks)
+    assert bplan(flags=AUX, cull=0, bwd_pixels_per_lane=3) == -1 and bplan.error() == "backward: bad option value"
