@@ -583,6 +583,49 @@ typedef struct gsrast_adam_group {
 int gsrast_adam_step(int n_groups, const gsrast_adam_group* groups /* host array */, double beta1, double beta2, double eps,
                      int step /* 1-based */, void* stream);   /* betas in fp64: (1 - 0.999f) would be off by 1.3e-5 relative */
 
+/* ---- densification: clone / split / prune of every per-Gaussian array with its Adam moments, on the device ----
+ * Replaces scene/saro_gaussian.py:705-736 densify_pruneclone with :685-701 densify_and_clone, :646-682 densify_and_splitv2,
+ * :577-593 prune_points and the optimizer surgery of :555-617 (_prune_optimizer, cat_tensors_to_optimizer).  For Gaussian i < P:
+ *   g_i    = accum_i / denom_i (NaN -> 0) [* grad_scale_i]             (accum == NULL: g_i = 0)
+ *   smax_i = max_k exp(scaling[i][k])
+ *   pruned = prune_src[i] != 0 (if given)  or  sigmoid(opacity_logit[i]) < min_opacity (if min_opacity > 0)
+ *   clone  = g_i >= grad_threshold and smax_i <= size_threshold;   split = g_i >= grad_threshold and smax_i > size_threshold
+ * grad_threshold must be > 0; +inf selects nothing ("prune only"; accum / denom / scaling may then be NULL).  Output rows:
+ *   [ originals !split && !pruned | clones of clone && !pruned | split copy 0 of split && !pruned | copy 1 | ... | copy N-1 ]
+ * each part in index order -- what the reference's clone, split, remove-the-sources, prune sequence leaves when the copies inherit their
+ * source's prune flag.  counts[5] = { n_kept, n_clone, n_split, n_split_all, P' = n_kept + n_clone + N * n_split } (device memory);
+ * n_split_all counts every split-selected source, pruned or not: copy k of source i reads noise[k * n_split_all + rank_all(i)], so a
+ * caller who draws randn(N * n_split_all, 3) consumes its generator as torch.normal at :662 does.
+ * gsrast_densify_plan classifies and scans (no atomics); the caller reads `counts` back -- the one synchronisation --, allocates
+ * the P' rows and hands the counts to gsrast_densify_apply with the same P, N and scratch (>= gsrast_densify_scratch_bytes(P)).
+ * The apply moves up to 16 groups in ONE launch.  A group: src [P][width] -> dst [P'][width], width in [1, 64]; with moments
+ * (src_m -> dst_m, src_v -> dst_v; each optional) kept originals gather their rows bit for bit, clones and split copies get zeros.
+ * Roles: COPY -- every row is a bit copy of its source; XYZ (width 3) -- a split copy is xyz + R(q / |q|) (noise * exp(scaling)), R as
+ * utils/general_utils.py:127-148 build_rotation over `rotation` [P][4] raw (r, x, y, z); SCALING -- a split copy is
+ * log(exp(scaling) / (0.8 N)).  `scaling` [P][3] raw.  A group without moments carries per-Gaussian extras through a prune.
+ * Deterministic: the same bits on every run and every rank.  P = 0 and P' = 0 are valid. */
+#define GSRAST_DENSIFY_COPY 0
+#define GSRAST_DENSIFY_XYZ 1
+#define GSRAST_DENSIFY_SCALING 2
+typedef struct gsrast_densify_group {
+    const float *src, *src_m, *src_v;   /* [P][width]; src_m / src_v NULL: no moments */
+    float *dst, *dst_m, *dst_v;         /* [P'][width] */
+    int width, role;
+} gsrast_densify_group;
+size_t gsrast_densify_scratch_bytes(int P);
+int gsrast_densify_plan(int P, int N /* 1..4 */, const float* accum, const float* denom, const float* grad_scale /* NULL */,
+                        const float* scaling /* [P][3] raw */, const float* opacity_logit /* [P] or NULL */, const unsigned char* prune_src /* NULL */,
+                        float grad_threshold, float size_threshold /* percent_dense * extent */, float min_opacity /* <= 0: off */,
+                        char* scratch, unsigned* counts /* device [5] */, void* stream);
+int gsrast_densify_apply(int P, int N, const char* scratch, const unsigned* counts_host /* [5], as read back */, int n_groups /* <= 16 */,
+                         const gsrast_densify_group* groups /* host array */, const float* rotation /* [P][4] raw */, const float* scaling,
+                         const float* noise /* [N * n_split_all][3]; NULL allowed when n_split == 0 */, void* stream);
+/* The per-iteration statistics of train.py:282-292 + add_densification_stats_grad (scene/saro_gaussian.py:745-750), one launch:
+ * where visibility_count[i] > 0:  accum[i] += grad_is_mean ? grad[i] : grad[i] / visibility_count[i];  denom[i] += 1;
+ * max_radii[i] = max(max_radii[i], radii[i]) (both NULL: skipped).  Other rows are untouched.  All arrays fp32 [P]. */
+int gsrast_densify_stats_update(int P, const float* grad, const float* visibility_count, const float* radii,
+                                float* accum, float* denom, float* max_radii, int grad_is_mean, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

@@ -21,6 +21,7 @@
 #include "gsrast_loss.h"
 #include "gsrast_epilogue.h"
 #include "gsrast_adam.h"
+#include "gsrast_densify.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include "gsrast_exchange.h"
@@ -138,13 +139,15 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
-                K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO, K_COUNT };
+                K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
                                             "cut_redo" /* list cut: the predicated second binning + blend behind the forward blend, as ONE stage */,
                                             "late_rows_zero" /* list cut: the late Gaussians' zero rows, on the side stream beside the blend backward */,
-                                            "grec_zero_touched" /* the consumed Gaussians' gradient records zeroed behind the forward's last blend */ };
+                                            "grec_zero_touched" /* the consumed Gaussians' gradient records zeroed behind the forward's last blend */,
+                                            "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -1843,6 +1846,99 @@ int gsrast_adam_step(int n_groups, const gsrast_adam_group* groups, double beta1
     a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)step)));
     adam_step_kernel<<<(unsigned)blocks, ADAM_THREADS, 0, s>>>(a);
     GS_LAUNCHED("adam_step");
+    return GSRAST_OK;
+}
+
+// scratch: class byte per source | four arrays of workgroup sums (kept, clone, split, split_all), scanned in place by the plan
+namespace {
+struct DensifyLayout { size_t cls, sums, total; uint32_t nb; };
+DensifyLayout densify_layout(size_t P)
+{
+    DensifyLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    L.nb = (uint32_t)((P + DN_RUN - 1) / DN_RUN);
+    L.cls = take(P ? P : 1); L.sums = take((size_t)4 * (L.nb ? L.nb : 1) * 4);
+    L.total = o + 256;
+    return L;
+}
+}
+size_t gsrast_densify_scratch_bytes(int P) { return densify_layout(P > 0 ? (size_t)P : 0).total; }
+
+int gsrast_densify_plan(int P, int N, const float* accum, const float* denom, const float* grad_scale, const float* scaling,
+                        const float* opacity_logit, const unsigned char* prune_src, float grad_threshold, float size_threshold,
+                        float min_opacity, char* scratch, unsigned* counts, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "densify_plan: negative P");
+    if (N < 1 || N > DN_MAX_N) return fail(GSRAST_E_ARG, "densify_plan: N (copies per split source) must be in [1, 4]");
+    if (!(grad_threshold > 0.0f)) return fail(GSRAST_E_ARG, "densify_plan: grad_threshold must be > 0 (+inf: prune only); with a threshold <= 0 the reference splits its fresh clones");
+    if (!scratch || !counts) return fail(GSRAST_E_ARG, "densify_plan: NULL scratch / counts");
+    const bool select = grad_threshold < INFINITY;
+    if (P > 0 && select && (!scaling || (accum != nullptr) != (denom != nullptr))) return fail(GSRAST_E_ARG, "densify_plan: a finite threshold needs scaling, and accum and denom together");
+    if (P > 0 && min_opacity > 0.0f && !opacity_logit) return fail(GSRAST_E_ARG, "densify_plan: min_opacity > 0 without opacity_logit");
+    const DensifyLayout L = densify_layout((size_t)P);
+    uint32_t* sums = at<uint32_t>(scratch, L.sums);
+    if (L.nb) {
+        ProfScope ps(K_DENSIFY_CLASSIFY, s);
+        densify_classify_kernel<<<L.nb, DN_RUN, 0, s>>>(P, accum, denom, grad_scale, scaling, opacity_logit, prune_src, grad_threshold, select ? 1 : 0,
+                                                       size_threshold, min_opacity, at<unsigned char>(scratch, L.cls), sums, L.nb);
+        GS_LAUNCHED("densify_classify");
+    }
+    {
+        ProfScope ps(K_DENSIFY_SCAN, s);
+        densify_scan_kernel<<<1, DN_RUN, 0, s>>>(sums, L.nb, N, counts);
+        GS_LAUNCHED("densify_scan");
+    }
+    return GSRAST_OK;
+}
+
+int gsrast_densify_apply(int P, int N, const char* scratch, const unsigned* counts_host, int n_groups, const gsrast_densify_group* groups,
+                         const float* rotation, const float* scaling, const float* noise, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "densify_apply: negative P");
+    if (N < 1 || N > DN_MAX_N) return fail(GSRAST_E_ARG, "densify_apply: N (copies per split source) must be in [1, 4]");
+    if (n_groups < 0 || n_groups > DN_MAX_GROUPS) return fail(GSRAST_E_ARG, "densify_apply: at most 16 groups");
+    if (!scratch || !counts_host || (n_groups > 0 && !groups)) return fail(GSRAST_E_ARG, "densify_apply: NULL scratch / counts / groups");
+    const unsigned n_kept = counts_host[0], n_clone = counts_host[1], n_split = counts_host[2], n_split_all = counts_host[3], p_new = counts_host[4];
+    if (n_kept > (unsigned)P || n_clone > n_kept || n_split > n_split_all || (unsigned long long)n_kept + n_split_all > (unsigned long long)P ||
+        (unsigned long long)p_new != (unsigned long long)n_kept + n_clone + (unsigned long long)N * n_split)
+        return fail(GSRAST_E_ARG, "densify_apply: counts are not those of a plan for this P and N");
+    DnApplyArgs a{};
+    for (int k = 0; k < n_groups; k++) {
+        const gsrast_densify_group& g = groups[k];
+        if (g.width < 1 || g.width > DN_MAX_WIDTH) return fail(GSRAST_E_ARG, "densify_apply: group width must be in [1, 64]");
+        if (g.role != GSRAST_DENSIFY_COPY && g.role != GSRAST_DENSIFY_XYZ && g.role != GSRAST_DENSIFY_SCALING) return fail(GSRAST_E_ARG, "densify_apply: unknown group role");
+        if ((g.src_m && !g.dst_m) || (g.src_v && !g.dst_v)) return fail(GSRAST_E_ARG, "densify_apply: src_m / src_v given without dst_m / dst_v");
+        if ((g.dst_m && !g.src_m) || (g.dst_v && !g.src_v)) return fail(GSRAST_E_ARG, "densify_apply: dst_m / dst_v given without src_m / src_v");
+        if ((P > 0 && !g.src) || (p_new > 0 && !g.dst)) return fail(GSRAST_E_ARG, "densify_apply: NULL src / dst");
+        if (g.role == GSRAST_DENSIFY_XYZ && g.width != 3) return fail(GSRAST_E_ARG, "densify_apply: the xyz role needs width 3");
+        if (g.role == GSRAST_DENSIFY_XYZ && n_split > 0 && (!rotation || !scaling || !noise)) return fail(GSRAST_E_ARG, "densify_apply: the xyz role needs rotation, scaling and noise while n_split > 0");
+        a.grp[k] = DnGroup{ g.src, g.src_m, g.src_v, g.dst, g.dst_m, g.dst_v, g.width, g.role };
+    }
+    if (P == 0 || n_groups == 0) return GSRAST_OK;
+    const DensifyLayout L = densify_layout((size_t)P);
+    a.n_groups = n_groups; a.P = P; a.N = N;
+    a.n_kept = n_kept; a.n_clone = n_clone; a.n_split = n_split; a.n_split_all = n_split_all; a.p_new = p_new; a.nb = L.nb;
+    a.cls = at<unsigned char>(scratch, L.cls); a.sums = at<uint32_t>(scratch, L.sums);
+    a.rotation = rotation; a.scaling = scaling; a.noise = noise;
+    ProfScope ps(K_DENSIFY_APPLY, s);
+    densify_apply_kernel<<<L.nb, DN_RUN, 0, s>>>(a);
+    GS_LAUNCHED("densify_apply");
+    return GSRAST_OK;
+}
+
+int gsrast_densify_stats_update(int P, const float* grad, const float* visibility_count, const float* radii,
+                                float* accum, float* denom, float* max_radii, int grad_is_mean, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "densify_stats_update: negative P");
+    if (P == 0) return GSRAST_OK;
+    if (!grad || !visibility_count || !accum || !denom || ((max_radii != nullptr) != (radii != nullptr)))
+        return fail(GSRAST_E_ARG, "densify_stats_update: NULL pointer (max_radii and radii go together)");
+    ProfScope ps(K_DENSIFY_STATS, s);
+    densify_stats_update_kernel<<<(unsigned)(((size_t)P + 255) / 256), 256, 0, s>>>(P, grad, visibility_count, radii, accum, denom, max_radii, grad_is_mean ? 1 : 0);
+    GS_LAUNCHED("densify_stats_update");
     return GSRAST_OK;
 }
 

@@ -36,6 +36,7 @@ EXPORTS = (
     "gsrast_profile_collect", "gsrast_profile_read", "gsrast_profile_reset", "gsrast_last_error",
     "gsrast_abi_version", "gsrast_loss_scratch_bytes", "gsrast_loss_forward", "gsrast_loss_backward",
     "gsrast_sh_grad_combine", "gsrast_sh_grad_combine_rows", "gsrast_sh_grad_combine_union", "gsrast_rows_pack", "gsrast_rows_unpack", "gsrast_grad_rows_pack", "gsrast_grad_rows_clear", "gsrast_grad_rows_add", "gsrast_touched_rows", "gsrast_activate_forward", "gsrast_activate_backward", "gsrast_adam_step",
+    "gsrast_densify_scratch_bytes", "gsrast_densify_plan", "gsrast_densify_apply", "gsrast_densify_stats_update",
     "gsrast_knn_scratch_bytes", "gsrast_knn3_mean_dist2",
     "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event", "gsrast_debug_forward_plan", "gsrast_debug_backward_plan",
@@ -121,6 +122,15 @@ class AdamGroupStruct(C.Structure):
     """gsrast_adam_group (include/gsrast.h)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("lr_rows", C.c_void_p), ("lr", C.c_float), ("rows", C.c_int), ("width", C.c_int)]
+
+
+class DensifyGroupStruct(C.Structure):
+    """gsrast_densify_group (include/gsrast.h)."""
+    _fields_ = [("src", C.c_void_p), ("src_m", C.c_void_p), ("src_v", C.c_void_p), ("dst", C.c_void_p), ("dst_m", C.c_void_p), ("dst_v", C.c_void_p),
+                ("width", C.c_int), ("role", C.c_int)]
+
+
+DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2      # include/gsrast.h: GSRAST_DENSIFY_*
 
 
 class PlaneStruct(C.Structure):
@@ -220,6 +230,14 @@ def lib() -> C.CDLL:
     L.gsrast_knn3_mean_dist2.argtypes = [ci, vp, vp, vp, vp]
     L.gsrast_adam_step.restype = ci
     L.gsrast_adam_step.argtypes = [ci, C.POINTER(AdamGroupStruct), C.c_double, C.c_double, C.c_double, ci, vp]
+    L.gsrast_densify_scratch_bytes.restype = C.c_size_t
+    L.gsrast_densify_scratch_bytes.argtypes = [ci]
+    L.gsrast_densify_plan.restype = ci
+    L.gsrast_densify_plan.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp]
+    L.gsrast_densify_apply.restype = ci
+    L.gsrast_densify_apply.argtypes = [ci, ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp, vp, vp, vp]
+    L.gsrast_densify_stats_update.restype = ci
+    L.gsrast_densify_stats_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp]
     L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
     L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
     L.gsrast_hexplane_forward.restype = ci

@@ -1,0 +1,242 @@
+"""Densification on the device: clone / split / prune of the per-Gaussian parameter groups TOGETHER with their Adam moments, and
+the per-iteration statistics the criterion reads (include/gsrast.h: gsrast_densify_plan / _apply / _stats_update,
+csrc/gsrast_densify.h).
+
+Mirror of the reference (paths relative to its root):
+  scene/saro_gaussian.py:705-736  densify_pruneclone  (clone :685-701, split :646-682, prune :577-593)            -> densify_and_prune
+  scene/saro_gaussian.py:555-640  _prune_optimizer / cat_tensors_to_optimizer / densification_postfix             -> inside both calls
+  scene/saro_gaussian.py:577-593  prune_points; :347-356 the every-50-iterations integral prune                    -> prune
+  train.py:282-292 + scene/saro_gaussian.py:745-750 add_densification_stats_grad                                   -> DensifyStats.update
+
+One classification pass, one scan and ONE row-moving launch for all groups replace the reference's chain of boolean-mask indexing
+and torch.cat over seven groups and fourteen moment tensors; the only host read-back is the five counts (for the new P).  The result
+is the reference's layout row for row:
+  [ originals !split && !pruned | clones | split copy 0 | copy 1 | ... ]      (every part in index order)
+and is bit-identical from run to run and from rank to rank (no atomics), so replicated models stay replicated.
+
+What stays the caller's: `reset_opacity`; the integral `get_intergral() < min_intergral` (it needs the hex-plane model) and the colmap
+`z < 4.5` rule -- both arrive here as `prune_mask`; per-row `lr` tensors of the old P (GaussianAdam.step raises on a mismatch) and the
+`view_parallel.StepBucket`, which is rebuilt after P changed.  GPU tensors only; no fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import torch
+from torch import nn
+
+from diff_gaussian_rasterization_ch3 import _C
+
+MAX_GROUPS = 16
+COUNT_NAMES = ("n_kept", "n_clone", "n_split", "n_split_all", "P")
+DEFAULT_NAMES = dict(xyz="xyz", scaling="scaling", rotation="rotation", opacity="opacity")
+
+
+class DensifyStats:
+    """xyz_gradient_accum [P,1], denom [P,1], max_radii2D [P] (scene/saro_gaussian.py:638-640), updated by one launch per iteration."""
+
+    def __init__(self, P: int, device):
+        self.device = torch.device(device)
+        self.reset(P)
+
+    def reset(self, P: int) -> None:
+        """Zeros at P rows, as densification_postfix leaves them (scene/saro_gaussian.py:638-641)."""
+        o = dict(dtype=torch.float32, device=self.device)
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = torch.zeros((P, 1), **o), torch.zeros((P, 1), **o), torch.zeros((P,), **o)
+
+    @property
+    def P(self) -> int:
+        return int(self.denom.shape[0])
+
+    @torch.no_grad()
+    def update(self, step_out: Dict[str, torch.Tensor]) -> None:
+        """step_out: what `view_parallel.distributed_step` returns.  Its "viewspace_point_grad" [P,1] is ALREADY the per-visible mean
+        (sum of the per-view norms / visibility count, train.py:286-287) and is added as it is.  A dict with "viewspace_point_grad_sum"
+        [P] or [P,1] instead -- the plain sum over the batch -- is divided by "visibility_count" here.  "visibility_count" [P] (rows
+        with count > 0 are updated, the others untouched) and "radii" [P] (max over the batch) are read in both forms."""
+        is_mean = "viewspace_point_grad_sum" not in step_out
+        grad = step_out["viewspace_point_grad" if is_mean else "viewspace_point_grad_sum"]
+        P = self.P
+        dev = _C._require_gpu(self.denom)
+        f = lambda t, n: _flat_f32(t, n, P, dev)  # noqa: E731
+        grad, count, radii = f(grad, "viewspace_point_grad"), f(step_out["visibility_count"], "visibility_count"), f(step_out["radii"], "radii")
+        with _C._on_device(dev):
+            rc = _C.lib().gsrast_densify_stats_update(P, _C._ptr(grad), _C._ptr(count), _C._ptr(radii), _C._ptr(self.xyz_gradient_accum),
+                                                      _C._ptr(self.denom), _C._ptr(self.max_radii2D), int(is_mean), _C._stream_of(dev))
+        if rc != 0:
+            raise _C._err(rc, "gsrast_densify_stats_update")
+
+
+def _flat_f32(t: torch.Tensor, name: str, P: int, dev: torch.device) -> torch.Tensor:
+    if t.numel() != P:
+        raise RuntimeError(f"fused_densify: {name} has {t.numel()} entries, the model {P} Gaussians")
+    if t.device != dev:
+        raise RuntimeError(f"fused_densify: {name} must live on {dev} (got {t.device}); there is no CPU fallback")
+    return t.detach().to(torch.float32).reshape(-1).contiguous()
+
+
+def _rows_width(t: torch.Tensor) -> int:
+    return max(int(math.prod(t.shape[1:])), 1)
+
+
+def _check_param(p: torch.Tensor, name: str, P: int) -> None:
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+        raise RuntimeError(f"fused_densify: {name} must be a contiguous float32 GPU tensor (no CPU fallback)")
+    if p.dim() < 1 or int(p.shape[0]) != P:
+        raise RuntimeError(f"fused_densify: {name} has {tuple(p.shape)}, expected {P} rows")
+
+
+def _run(P: int, dev: torch.device, N: int, plan_args: dict, moved: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], int]],
+         rotation: Optional[torch.Tensor], scaling: Optional[torch.Tensor], generator, noise: Optional[torch.Tensor]):
+    """plan -> read the counts back (the one synchronisation) -> noise -> allocate -> apply.  `moved`: (src, exp_avg, exp_avg_sq, role) per
+    group.  Returns (counts dict, [(dst, dst_m, dst_v)])."""
+    if len(moved) > MAX_GROUPS:
+        raise RuntimeError(f"fused_densify: {len(moved)} arrays to move, at most {MAX_GROUPS} per launch")
+    L = _C.lib()
+    scratch = torch.empty(int(L.gsrast_densify_scratch_bytes(P)), dtype=torch.uint8, device=dev)
+    counts_dev = torch.empty(5, dtype=torch.int32, device=dev)
+    with _C._on_device(dev):
+        stream = _C._stream_of(dev)
+        rc = L.gsrast_densify_plan(P, N, plan_args.get("accum"), plan_args.get("denom"), plan_args.get("grad_scale"), plan_args.get("scaling"),
+                                   plan_args.get("opacity"), plan_args.get("prune_src"), float(plan_args["thr"]), float(plan_args.get("tau", 0.0)),
+                                   float(plan_args.get("min_opacity", 0.0)), scratch.data_ptr(), counts_dev.data_ptr(), stream)
+        if rc != 0:
+            raise _C._err(rc, "gsrast_densify_plan")
+        host = [int(v) & 0xFFFFFFFF for v in counts_dev.cpu().tolist()]
+        counts = dict(zip(COUNT_NAMES, host))
+        n_all, P_new = counts["n_split_all"], counts["P"]
+        if noise is None:
+            noise = torch.randn((N * n_all, 3), generator=generator, device=dev, dtype=torch.float32) if n_all else None
+        elif n_all:
+            if tuple(noise.shape) != (N * n_all, 3) or noise.device != dev:
+                raise RuntimeError(f"fused_densify: noise must be [{N * n_all}, 3] on {dev} (N * n_split_all rows), got {tuple(noise.shape)} on {noise.device}")
+            noise = noise.to(torch.float32).contiguous()
+        arr = (_C.DensifyGroupStruct * max(len(moved), 1))()
+        out = []
+        for a, (src, m, v, role) in zip(arr, moved):
+            shape = (P_new,) + tuple(src.shape[1:])
+            dst = torch.empty(shape, dtype=torch.float32, device=dev)
+            dm = torch.empty(shape, dtype=torch.float32, device=dev) if m is not None else None
+            dv = torch.empty(shape, dtype=torch.float32, device=dev) if v is not None else None
+            a.src, a.src_m, a.src_v = _C._ptr(src), _C._ptr(m), _C._ptr(v)
+            a.dst, a.dst_m, a.dst_v = _C._ptr(dst), _C._ptr(dm), _C._ptr(dv)
+            a.width, a.role = _rows_width(src), role
+            out.append((dst, dm, dv))
+        if P_new == 0:          # nothing survives: the new tensors are empty, there is no row to move
+            return counts, out
+        ch = (C.c_uint * 5)(*host)
+        rc = L.gsrast_densify_apply(P, N, scratch.data_ptr(), ch, len(moved), arr, _C._ptr(rotation), _C._ptr(scaling),
+                                    _C._ptr(noise) if n_all else None, stream)
+        if rc != 0:
+            raise _C._err(rc, "gsrast_densify_apply")
+    return counts, out
+
+
+def _optimizer_groups(opt, P: Optional[int] = None):
+    """[(group, parameter, state or None)] of the optimizer's per-Gaussian groups (one tensor each, saro_gaussian.py:306-318)."""
+    rows = []
+    for g in opt.param_groups:
+        if len(g["params"]) != 1:
+            raise RuntimeError("fused_densify: one tensor per group (the per-Gaussian groups of saro_gaussian.py:306-318)")
+        p = g["params"][0]
+        if P is None:
+            P = int(p.shape[0])
+        _check_param(p, f"group {g.get('name')}", P)
+        st = opt.state.get(p)
+        if st is not None and ("exp_avg" not in st or "exp_avg_sq" not in st):
+            st = None
+        if st is not None:
+            for k in ("exp_avg", "exp_avg_sq"):
+                if st[k].shape != p.shape or not st[k].is_contiguous() or st[k].dtype != torch.float32 or st[k].device != p.device:
+                    raise RuntimeError(f"fused_densify: {k} of group {g.get('name')} does not match its parameter")
+        rows.append((g, p, st))
+    return rows, (P or 0)
+
+
+def _install(opt, rows, results) -> Dict[str, nn.Parameter]:
+    """Every group's params[0] becomes a fresh leaf; opt.state is re-keyed with the new moments (other entries, e.g. torch.optim's
+    "step", are kept -- as is GaussianAdam's own step count)."""
+    new = {}
+    for (g, p, st), (dst, dm, dv) in zip(rows, results):
+        q = nn.Parameter(dst.requires_grad_(True))
+        old = opt.state.pop(p, None)
+        if st is not None:
+            ns = dict(old)
+            ns["exp_avg"], ns["exp_avg_sq"] = dm, dv
+            opt.state[q] = ns
+        g["params"][0] = q
+        new[g.get("name")] = q
+    return new
+
+
+@torch.no_grad()
+def densify_and_prune(opt, stats: DensifyStats, *, grad_threshold: float, percent_dense: float, extent: float, min_opacity: Optional[float] = None,
+                      prune_mask: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None, n_split: int = 2,
+                      generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None, names: Dict[str, str] = DEFAULT_NAMES):
+    """densify_pruneclone (scene/saro_gaussian.py:705-736) on `opt`'s per-Gaussian groups (GaussianAdam, or any optimizer with
+    torch.optim's `param_groups` / `state` surface) with the statistics in `stats`:
+      g = accum / denom (NaN -> 0) * grad_scale;  clone where g >= grad_threshold and max exp(scaling) <= percent_dense * extent,
+      split into n_split copies where g >= grad_threshold and max exp(scaling) > percent_dense * extent,
+      prune where prune_mask (bool / uint8 [P]) or sigmoid(opacity) < min_opacity -- a pruned source leaves neither clone nor copies.
+    grad_scale: the reference's inv_intergral_fordensify [P] / [P,1].  names: which group is xyz / scaling / rotation / opacity.
+    noise [n_split * n_split_all, 3] (row k * n_split_all + rank among ALL split-selected sources) is drawn with torch.randn(...,
+    generator=generator) on the device unless given.  Every group's params[0] is replaced by a fresh nn.Parameter leaf, opt.state is
+    re-keyed with the new moments (kept rows gathered, new rows zero), `stats` is reset to zeros at the new P.
+    Returns (counts, {group name: new parameter}); counts = dict(n_kept, n_clone, n_split, n_split_all, P)."""
+    rows, P = _optimizer_groups(opt, stats.P)
+    by_name = {g.get("name"): p for g, p, _ in rows}
+    for role in ("xyz", "scaling", "rotation", "opacity"):
+        if names.get(role) not in by_name:
+            raise RuntimeError(f"fused_densify: no group named {names.get(role)!r} (names[{role!r}])")
+    xyz, scaling, rotation, opacity = (by_name[names[r]] for r in ("xyz", "scaling", "rotation", "opacity"))
+    if _rows_width(xyz) != 3 or _rows_width(scaling) != 3 or _rows_width(rotation) != 4 or _rows_width(opacity) != 1:
+        raise RuntimeError("fused_densify: xyz / scaling / rotation / opacity must be [P,3] / [P,3] / [P,4] / [P,1]")
+    dev = _C._require_gpu(xyz)
+    keep = [_flat_f32(stats.xyz_gradient_accum, "xyz_gradient_accum", P, dev), _flat_f32(stats.denom, "denom", P, dev)]
+    plan = dict(accum=_C._ptr(keep[0]), denom=_C._ptr(keep[1]), scaling=_C._ptr(scaling), opacity=_C._ptr(opacity),
+                thr=grad_threshold, tau=float(percent_dense) * float(extent), min_opacity=0.0 if min_opacity is None else min_opacity)
+    if grad_scale is not None:
+        keep.append(_flat_f32(grad_scale, "grad_scale", P, dev))
+        plan["grad_scale"] = _C._ptr(keep[-1])
+    if prune_mask is not None:
+        keep.append(_mask_u8(prune_mask, P, dev))
+        plan["prune_src"] = _C._ptr(keep[-1])
+    role_of = {id(xyz): _C.DENSIFY_XYZ, id(scaling): _C.DENSIFY_SCALING}
+    moved = [(p, st["exp_avg"] if st else None, st["exp_avg_sq"] if st else None, role_of.get(id(p), _C.DENSIFY_COPY)) for _, p, st in rows]
+    counts, results = _run(P, dev, int(n_split), plan, moved, rotation, scaling, generator, noise)
+    new = _install(opt, rows, results)
+    stats.reset(counts["P"])
+    return counts, new
+
+
+def _mask_u8(mask: torch.Tensor, P: int, dev: torch.device) -> torch.Tensor:
+    if mask.numel() != P:
+        raise RuntimeError(f"fused_densify: the prune mask has {mask.numel()} entries, the model {P} Gaussians")
+    if mask.device != dev:
+        raise RuntimeError(f"fused_densify: the prune mask must live on {dev}; there is no CPU fallback")
+    return mask.reshape(-1).to(torch.uint8).contiguous()
+
+
+@torch.no_grad()
+def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras: Iterable[torch.Tensor] = ()):
+    """prune_points (scene/saro_gaussian.py:577-593) and the integral prune of update_learning_rate (:347-356): rows with mask != 0
+    leave every group, its moments, `stats` (gathered, NOT reset) and every tensor of `extras` ([P, ...] float32 each, e.g.
+    t_gradient_accum).  The same plan / apply pair with an infinite threshold.  Returns (counts, {group name: new parameter},
+    [new extras])."""
+    rows, P = _optimizer_groups(opt, stats.P if stats is not None else None)
+    dev = _C._require_gpu(rows[0][1]) if rows else _C._require_gpu(mask)
+    m8 = _mask_u8(mask, P, dev)
+    moved = [(p, st["exp_avg"] if st else None, st["exp_avg_sq"] if st else None, _C.DENSIFY_COPY) for _, p, st in rows]
+    carried: List[torch.Tensor] = ([stats.xyz_gradient_accum, stats.denom, stats.max_radii2D] if stats is not None else []) + list(extras)
+    for k, t in enumerate(carried):
+        _check_param(t, f"carried tensor {k}", P)
+        moved.append((t, None, None, _C.DENSIFY_COPY))
+    counts, results = _run(P, dev, 1, dict(thr=math.inf, prune_src=_C._ptr(m8)), moved, None, None, None, None)
+    new = _install(opt, rows, results[: len(rows)])
+    rest = [r[0] for r in results[len(rows):]]
+    if stats is not None:
+        stats.xyz_gradient_accum, stats.denom, stats.max_radii2D = rest[:3]
+        rest = rest[3:]
+    return counts, new, rest
