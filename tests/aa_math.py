@@ -23,9 +23,10 @@ def comp_of_cov2(a, b, c):
     return torch.sqrt(torch.clamp(rho, min=FLOOR)), rho
 
 
-def comp(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None):
-    """fp64 (comp [P], rho [P]) for the scales / rotations form, or for cov3D_precomp ([P,6]: xx xy xz yy yz zz) with cov3D given."""
-    pr = mr.project(means3D, scales, rotations, cam, scale_modifier, cov3D)
+def comp(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, clamp_grad="reference"):
+    """fp64 (comp [P], rho [P]) for the scales / rotations form, or for cov3D_precomp ([P,6]: xx xy xz yy yz zz) with cov3D given.
+    clamp_grad: math_renderer.project's (how the frustum-clamped t.x / t.y are differentiated)."""
+    pr = mr.project(means3D, scales, rotations, cam, scale_modifier, cov3D, clamp_grad=clamp_grad)
     return comp_of_cov2(*pr["cov2"])
 
 
@@ -36,8 +37,9 @@ def _rot32(q):
                         2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
 
 
-def comp32(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None):
-    """(comp, rho) in fp32, the kernel's chain: cov3D = (S R)^T (S R), J W Sigma W^T J^T with the frustum clamp, undilated c00 / c11."""
+def comp32(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, clamp_grad="reference"):
+    """(comp, rho) in fp32, the kernel's chain: cov3D = (S R)^T (S R), J W Sigma W^T J^T with the frustum clamp, undilated c00 / c11.
+    clamp_grad as in comp: "reference" = a clamped t.x / t.y is a constant of the backward, as in the kernel (preprocess_bwd_kernel)."""
     f = torch.float32
     dev = means3D.device
     V = torch.as_tensor(np.asarray(cam["viewmatrix"], np.float32), device=dev)
@@ -56,6 +58,10 @@ def comp32(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None):
     tz = t[:, 2]
     txc = torch.clamp(t[:, 0] / tz, -limx, limx) * tz
     tyc = torch.clamp(t[:, 1] / tz, -limy, limy) * tz
+    if clamp_grad == "reference":
+        with torch.no_grad():
+            clx, cly = (t[:, 0] / tz).abs() > limx, (t[:, 1] / tz).abs() > limy
+        txc, tyc = torch.where(clx, txc.detach(), txc), torch.where(cly, tyc.detach(), tyc)
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -(fx * txc) / (tz * tz), zero, fy / tz, -(fy * tyc) / (tz * tz)], 1).reshape(-1, 2, 3)
     A = J @ V[:3, :3].T

@@ -13,7 +13,17 @@ What is taken from the reference (cited) is only what DEFINES the function being
     stop before T (1 - alpha) < 1e-4 (forward.cu:343-357), colour = max(SH + 0.5, 0) (forward.cu:60-70);
   * two deliberate deviations of the reference's backward from the true derivative, reproduced so that the comparison is
     meaningful: the 0.99 clamp of alpha passes gradients through (backward.cu:538, :554 apply no mask) -> straight-through
-    here (`clamp_passthrough`); the depth output carries no gradient.
+    here (`clamp_passthrough`); the depth output carries no gradient;
+  * a third one, on by default (`clamp_grad="reference"`): outside 1.3 x the field of view the backward recomputes the
+    clamped t.x, t.y and treats them as constants in J (backward.cu:172-176), and zeroes only the direct dL/dt.x, dL/dt.y
+    (x_grad_mul / y_grad_mul, :262-264) -- it drops d(clamp(t.x / t.z) * t.z)/dt.z = +-lim, which autograd of the forward
+    expression keeps.  Here: the value entering J on a clamped axis is (+-lim * t.z).detach().  `clamp_grad="true"` is the
+    forward expression differentiated as written; the forward VALUES of the two modes are identical;
+  * a fourth: the gradient of the conic (the inverse of the 2-D covariance) with respect to that covariance is computed with
+    1 / (det^2 + 1e-7) in place of 1 / det^2 (backward.cu:203-212), i.e. scaled by det^2 / (det^2 + 1e-7) -- 1.2e-5 relative
+    for the smallest footprints (det -> 0.09), which the fp64 comparison with the oracle resolves (`_scale_grad`);
+  * a fifth: dL/dscales is the gradient with respect to scale_modifier * scales -- computeCov3D's backward forms s = mod * scale
+    and returns dL/ds (backward.cu:295, :323-325), dropping the chain rule's factor mod.  Invisible at scale_modifier = 1.
 
 Discrete decisions (culling, rectangles, depth order, the alpha / transmittance thresholds) are taken on detached float64
 values; `ambiguous` flags every pixel in which one of those decisions sits within fp32 rounding of its threshold -- the
@@ -68,8 +78,10 @@ def rotation_matrix(q: torch.Tensor) -> torch.Tensor:
     return torch.stack(rows, dim=1).reshape(-1, 3, 3)
 
 
-def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc_offset=None):
-    """Per-Gaussian screen-space quantities (all differentiable) + the discrete ones (numpy)."""
+def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc_offset=None, clamp_grad="reference"):
+    """Per-Gaussian screen-space quantities (all differentiable) + the discrete ones (numpy).  clamp_grad: "reference" (the
+    frustum-clamped t.x / t.y enter J as constants, backward.cu:172-176, :262-264) or "true" (the clamp differentiated as written)."""
+    assert clamp_grad in ("reference", "true"), clamp_grad
     W, H = int(cam["image_width"]), int(cam["image_height"])
     V = torch.as_tensor(np.asarray(cam["viewmatrix"], np.float64))            # transposed storage: row vector @ V
     Pm = torch.as_tensor(np.asarray(cam["projmatrix"], np.float64))
@@ -86,7 +98,10 @@ def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc
     pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
     if cov3D is None:
         R = rotation_matrix(rotations)
-        Mx = R * (scale_modifier * scales)[:, None, :]                        # R @ diag(s)
+        s_mod = scale_modifier * scales
+        if scale_modifier != 1.0:
+            s_mod = _scale_grad(s_mod, 1.0 / scale_modifier)                   # dL/dscales as the reference's: of mod * scale
+        Mx = R * s_mod[:, None, :]                                            # R @ diag(s)
         Sigma = Mx @ Mx.transpose(1, 2)
     else:
         c = cov3D
@@ -95,6 +110,13 @@ def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc
     tz = t[:, 2]
     txc = torch.clamp(t[:, 0] / tz, -limx, limx) * tz
     tyc = torch.clamp(t[:, 1] / tz, -limy, limy) * tz
+    with torch.no_grad():
+        clx, cly = (t[:, 0] / tz).abs() > limx, (t[:, 1] / tz).abs() > limy
+    if clamp_grad == "reference":
+        # x and y independently: +-lim * t.z as a constant on a clamped axis; elsewhere t.x itself, kept in the form
+        # clamp(t.x / t.z) * t.z so that the two modes are the same expression (bit-equal gradients) on unclamped rows
+        txc = torch.where(clx, txc.detach(), txc)
+        tyc = torch.where(cly, tyc.detach(), tyc)
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], dim=1).reshape(-1, 2, 3)
     Wr = V[:3, :3].T                                                          # world -> view rotation (math layout)
@@ -103,8 +125,12 @@ def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc
     a = cov2[:, 0, 0] + C_DILATE
     b = cov2[:, 0, 1]
     c2 = cov2[:, 1, 1] + C_DILATE
-    det = a * c2 - b * b
-    conic = torch.stack([c2 / det, -b / det, a / det], dim=1)
+    with torch.no_grad():
+        det0 = a * c2 - b * b
+        reg = det0 * det0 / (det0 * det0 + C_WEPS)
+    ar, br, cr = _scale_grad(a, reg), _scale_grad(b, reg), _scale_grad(c2, reg)
+    det = ar * cr - br * br
+    conic = torch.stack([cr / det, -br / det, ar / det], dim=1)
     # discrete part
     with torch.no_grad():
         mid = 0.5 * (a + c2)
@@ -124,8 +150,26 @@ def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc
         rect_margin = torch.minimum(torch.minimum(edge((pix[:, 0] - radius) / 16.0), edge((pix[:, 0] + radius + 15.0) / 16.0)),
                                     torch.minimum(edge((pix[:, 1] - radius) / 16.0), edge((pix[:, 1] + radius + 15.0) / 16.0)))
     disc = dict(vis=vis.numpy(), radius=(radius * vis).numpy().astype(np.int64), rect=torch.stack([x0, y0, x1, y1], 1).numpy().astype(np.int64),
-                tiles=(tiles * vis).numpy().astype(np.int64), radius_margin=frac.numpy(), rect_margin=rect_margin.numpy())
+                tiles=(tiles * vis).numpy().astype(np.int64), radius_margin=frac.numpy(), rect_margin=rect_margin.numpy(),
+                clamped=(clx | cly).numpy())
     return dict(pix=pix, conic=conic, depth=tz, cov2=(a, b, c2), Sigma=Sigma, disc=disc, W=W, H=H)
+
+
+def _scale_grad(x: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+    """x itself, with the gradient arriving through this copy multiplied by the constant f."""
+    y = x.clone()
+    if y.requires_grad:
+        y.register_hook(lambda g: g * f)
+    return y
+
+
+def _tile_list_max(rect, W, H):
+    """The longest per-tile list: how many visible Gaussians' rectangles cover the fullest 16 x 16 tile."""
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    n = np.zeros((gy, gx), np.int64)
+    for x0, y0, x1, y1 in rect:
+        n[y0:y1, x0:x1] += 1
+    return int(n.max())
 
 
 def clamp_passthrough(alpha: torch.Tensor, hi: float) -> torch.Tensor:
@@ -133,9 +177,9 @@ def clamp_passthrough(alpha: torch.Tensor, hi: float) -> torch.Tensor:
 
 
 def render(means3D, scales, rotations, opacities, shs, sh_degree, cam, bg, *, colors_precomp=None, cov3D=None,
-           scale_modifier=1.0, ndc_offset=None, fp32_eps=4e-6):
-    """Returns dict(color [3,H,W], depth [H,W], final_T [H,W], ambiguous [H,W] bool, proj=...)."""
-    pr = project(means3D, scales, rotations, cam, scale_modifier, cov3D, ndc_offset)
+           scale_modifier=1.0, ndc_offset=None, fp32_eps=4e-6, clamp_grad="reference"):
+    """Returns dict(color [3,H,W], depth [H,W], final_T [H,W], ambiguous [H,W] bool, proj=...).  clamp_grad: see project()."""
+    pr = project(means3D, scales, rotations, cam, scale_modifier, cov3D, ndc_offset, clamp_grad)
     W, H = pr["W"], pr["H"]
     vis = torch.as_tensor(pr["disc"]["vis"])
     if colors_precomp is None:
@@ -201,4 +245,6 @@ def render(means3D, scales, rotations, opacities, shs, sh_degree, cam, bg, *, co
     return dict(color=colour.T.reshape(3, H, W), depth=depth.reshape(H, W), final_T=T_final.reshape(H, W),
                 ambiguous=amb_pix.reshape(H, W).numpy(), proj=pr, order=idx.numpy(), min_depth_gap=gap,
                 colour_clamp_margin=col_margin.numpy(), n_live=n_live.reshape(H, W).numpy(),
-                clamped_pairs=int((live & (alpha_raw > C_AMAX)).sum().item()))
+                clamped_pairs=int((live & (alpha_raw > C_AMAX)).sum().item()),
+                tile_list_max=_tile_list_max(rect.numpy(), W, H),
+                stopped=((ok & ~live).any(dim=1)).reshape(H, W).numpy())

@@ -13,6 +13,7 @@ import torch
 import aa_math
 import math_renderer as mr
 from conftest import grad_tol, settings_from
+from edge_scenes import clamped_mask, edge_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -283,20 +284,17 @@ SMALL = [dict(P=600, seed=31, W=96, H=64, k=1, V=5, deg=3, smul=0.6, bg=(0.1, 0.
 
 @pytest.mark.parametrize("c", SMALL, ids=lambda c: f"P{c['P']}_{c['W']}x{c['H']}")
 def test_against_the_fp64_math_renderer(c, scenes, rast, gpu):
-    sc = scenes.synth(c["P"], c["seed"], sh_degree=c["deg"], scale_mul=c["smul"])
-    sc["bg"] = np.array(c["bg"], np.float32)
-    for i in range(4):      # needles among them
-        sc["scales"][i] = np.array([0.3, 0.004, 0.004], np.float32) * c["smul"]
-    cam = scenes.camera(c["k"], c["V"], c["W"], c["H"])
-    P, W, H, deg = c["P"], c["W"], c["H"], c["deg"]
+    sc, cam = edge_scene(scenes, c)      # (needles, near-plane Gaussians and Gaussians outside the frustum clamp among them)
+    P, W, H, deg = sc["means3D"].shape[0], c["W"], c["H"], c["deg"]
     t64 = {n: torch.as_tensor(np.asarray(sc[n], np.float64)).requires_grad_(True) for n in LEAVES}
     off = torch.zeros((P, 2), dtype=torch.float64, requires_grad=True)
     vis = mr.project(t64["means3D"].detach(), t64["scales"].detach(), t64["rotations"].detach(), cam)["disc"]["vis"]
     idx = torch.as_tensor(vis).nonzero()[:, 0]
-    comp, rho = aa_math.comp(t64["means3D"][idx], t64["scales"][idx], t64["rotations"][idx], cam)
+    comp, rho = aa_math.comp(t64["means3D"][idx], t64["scales"][idx], t64["rotations"][idx], cam, clamp_grad="reference")
     assert float((comp < 0.9).double().mean()) > 0.1
     o_eff = t64["opacities"][:, 0].index_put((idx,), t64["opacities"][idx, 0] * comp)[:, None]
-    ref = mr.render(t64["means3D"], t64["scales"], t64["rotations"], o_eff, t64["shs"], deg, cam, sc["bg"], ndc_offset=off)
+    ref = mr.render(t64["means3D"], t64["scales"], t64["rotations"], o_eff, t64["shs"], deg, cam, sc["bg"], ndc_offset=off,
+                    clamp_grad="reference")
     amb = ref["ambiguous"]
     assert amb.mean() < 0.05
     g = scenes.upstream_grad(H, W, c["seed"] + 1).astype(np.float64)
@@ -321,17 +319,17 @@ def test_against_the_fp64_math_renderer(c, scenes, rast, gpu):
     cond = aa_math.conditioning(t64["means3D"].detach()[idx], t64["scales"].detach()[idx], t64["rotations"].detach()[idx], cam).numpy()
     near_floor = np.zeros(P, bool)
     near_floor[idx.numpy()] = np.abs(rho.detach().numpy() - aa_math.FLOOR) <= 64 * EPS32 * (cond + 1.0)
-    V = np.asarray(cam["viewmatrix"], np.float64)
-    tv = sc["means3D"].astype(np.float64) @ V[:3, :3] + V[3, :3]
-    unc = (tv[:, 2] > 0.2) & (np.abs(tv[:, 0] / tv[:, 2]) < 1.29 * cam["tanfovx"]) & (np.abs(tv[:, 1] / tv[:, 2]) < 1.29 * cam["tanfovy"])
+    cl = clamped_mask(sc, cam)      # the frustum-clamped rows once more, as a tensor of their own: their gradients are small
+    assert (cl & ~near_floor).sum() >= 16
     for n in ("means3D", "opacities", "shs", "scales", "rotations"):
         want = t64[n].grad.numpy().reshape(P, -1)
         got = _np(t[n].grad).reshape(P, -1)
         f32 = _np(pred32[n]).reshape(P, -1)
-        sel = ~near_floor & (unc if n == "means3D" else True)
-        tol = grad_tol(want[sel], f32[sel])
-        assert (np.abs(got[sel] - want[sel]) <= tol).all(), (n, float(np.abs(got[sel] - want[sel]).max()), float(np.abs(want[sel]).max()))
-    assert float(np.abs(t64["means3D"].grad.numpy()[unc]).max()) > 1e-3
+        for what, sel in ((n, ~near_floor),) + (((n + ", clamped rows", cl & ~near_floor),) if n == "means3D" else ()):
+            tol = grad_tol(want[sel], f32[sel])
+            assert (np.abs(got[sel] - want[sel]) <= tol).all(), (what, float(np.abs(got[sel] - want[sel]).max()), float(np.abs(want[sel]).max()))
+    assert float(np.abs(t64["means3D"].grad.numpy()).max()) > 1e-3
+    assert float(np.abs(t64["means3D"].grad.numpy()[cl & ~near_floor]).max()) > 0.0
     want2, got2 = off.grad.numpy(), _np(m2.grad[:, :2])
     assert (np.abs(got2 - want2) <= grad_tol(want2, _np(pred32["means2D"])[:, :2])).all()
 

@@ -12,6 +12,7 @@ import torch
 
 import math_renderer as mr
 from conftest import grad_tol, settings_from
+from edge_scenes import clamped_mask, edge_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -176,47 +177,20 @@ SMALL = [
 ]
 
 
-def _edge_scene(scenes, c):
-    """scenes.synth + a few Gaussians at the near plane, outside the frustum clamp, and needle-shaped."""
-    sc = scenes.synth(c["P"], c["seed"], sh_degree=c["deg"], scale_mul=c["smul"])
-    sc["bg"] = np.array(c["bg"], np.float32)
-    sc["opacities"] = (sc["opacities"] * c["omul"]).astype(np.float32)
-    cam = scenes.camera(c["k"], c["V"], c["W"], c["H"])
-    V = cam["viewmatrix"].astype(np.float64)
-    Vi = np.linalg.inv(V)
-    rng = np.random.default_rng(c["seed"] + 7)
-    pts = []
-    for _ in range(4):      # just in front of / behind the near plane (z = 0.2) near the optical axis
-        pts.append([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), 0.2 + rng.choice([-1, 1]) * rng.uniform(0.02, 0.1)])
-    for _ in range(4):      # centres outside 1.3 x the field of view, footprints reaching into the image
-        z = rng.uniform(2.0, 4.0)
-        pts.append([1.45 * cam["tanfovx"] * z * rng.choice([-1, 1]), rng.uniform(-0.5, 0.5) * cam["tanfovy"] * z, z])
-    pts = np.array(pts)
-    world = (np.concatenate([pts, np.ones((len(pts), 1))], 1) @ Vi)[:, :3]
-    n = len(pts)
-    for i in range(6):      # needles among the visible ones
-        sc["scales"][i] = np.array([0.3, 0.004, 0.004], np.float32) * c["smul"]
-    sc["means3D"] = np.concatenate([sc["means3D"], world.astype(np.float32)])
-    sc["scales"] = np.concatenate([sc["scales"], np.full((n, 3), 0.15, np.float32)])
-    sc["rotations"] = np.concatenate([sc["rotations"], np.tile(np.array([[1, 0, 0, 0]], np.float32), (n, 1))])
-    sc["opacities"] = np.concatenate([sc["opacities"], np.full((n, 1), 0.6, np.float32)])
-    sc["shs"] = np.concatenate([sc["shs"], sc["shs"][:n]])
-    return sc, cam
-
-
 @pytest.mark.parametrize("c", SMALL, ids=lambda c: f"P{c['P']}_deg{c['deg']}")
 def test_aux_outputs_and_gradients_against_fp64_math(c, scenes, rast, gpu):
-    sc, cam = _edge_scene(scenes, c)
+    sc, cam = edge_scene(scenes, c)
     P, W, H, deg = sc["means3D"].shape[0], c["W"], c["H"], c["deg"]
     # truth: alpha = 1 - final_T, acc_depth = the colour of a (z, 0, 0) render on black, z differentiable
     t64 = {n: torch.as_tensor(np.asarray(sc[n], np.float64)).requires_grad_(True) for n in ("means3D", "scales", "rotations", "opacities", "shs")}
     off = torch.zeros((P, 2), dtype=torch.float64, requires_grad=True)
-    ref = mr.render(t64["means3D"], t64["scales"], t64["rotations"], t64["opacities"], t64["shs"], deg, cam, sc["bg"], ndc_offset=off)
+    ref = mr.render(t64["means3D"], t64["scales"], t64["rotations"], t64["opacities"], t64["shs"], deg, cam, sc["bg"], ndc_offset=off,
+                    clamp_grad="reference")
     V = torch.as_tensor(np.asarray(cam["viewmatrix"], np.float64))
     z = t64["means3D"] @ V[:3, 2] + V[3, 2]
     zc = torch.stack([z, torch.zeros_like(z), torch.zeros_like(z)], 1)
     refd = mr.render(t64["means3D"], t64["scales"], t64["rotations"], t64["opacities"], t64["shs"], deg, cam, np.zeros(3),
-                     colors_precomp=zc, ndc_offset=off)
+                     colors_precomp=zc, ndc_offset=off, clamp_grad="reference")
     amb = ref["ambiguous"] | refd["ambiguous"]
     assert amb.mean() < 0.05
     keep = ~amb
@@ -245,25 +219,21 @@ def test_aux_outputs_and_gradients_against_fp64_math(c, scenes, rast, gpu):
     np.testing.assert_allclose(alpha[0].detach().cpu().numpy()[keep], alpha64.detach().numpy()[keep], rtol=0, atol=2e-6)
     acc_ref = refd["color"][0].detach().numpy()
     np.testing.assert_allclose(acc[0].detach().cpu().numpy()[keep], acc_ref[keep], rtol=1e-5, atol=2e-6 * max(1.0, float(np.abs(acc_ref).max())))
-    unc = _unclamped(sc, cam)
+    cl = clamped_mask(sc, cam)      # the frustum-clamped rows once more, as a tensor of their own: their gradients are small
+    assert cl.sum() >= 16
     for n in ("means3D", "opacities", "scales", "rotations"):
         want = t64[n].grad.numpy()
         got = t[n].grad.detach().double().cpu().numpy().reshape(want.shape)
         f32 = t2[n].grad.detach().double().cpu().numpy().reshape(want.shape)
-        sel = unc if n == "means3D" else np.ones(P, bool)
-        tol = grad_tol(want[sel], f32[sel])
-        assert (np.abs(got[sel] - want[sel]) <= tol).all(), (n, float(np.abs(got[sel] - want[sel]).max()), float(np.abs(want[sel]).max()))
-    assert float(np.abs(t64["means3D"].grad.numpy()[unc]).max()) > 1e-3
+        for what, sel in ((n, np.ones(P, bool)),) + (((n + ", clamped rows", cl),) if n == "means3D" else ()):
+            tol = grad_tol(want[sel], f32[sel])
+            assert (np.abs(got[sel] - want[sel]) <= tol).all(), (what, float(np.abs(got[sel] - want[sel]).max()), float(np.abs(want[sel]).max()))
+    assert float(np.abs(t64["means3D"].grad.numpy()).max()) > 1e-3
+    assert float(np.abs(t64["means3D"].grad.numpy()[cl]).max()) > 0.0
     assert float(t["shs"].grad.abs().max()) == 0.0
     want2 = off.grad.numpy()
     got2 = m2.grad[:, :2].double().cpu().numpy()
     assert (np.abs(got2 - want2) <= grad_tol(want2, m22.grad[:, :2].double().cpu().numpy())).all()
-
-
-def _unclamped(sc, cam):
-    V = cam["viewmatrix"].astype(np.float64)
-    tv = sc["means3D"].astype(np.float64) @ V[:3, :3] + V[3, :3]
-    return (tv[:, 2] > 0.2) & (np.abs(tv[:, 0] / tv[:, 2]) < 1.29 * cam["tanfovx"]) & (np.abs(tv[:, 1] / tv[:, 2]) < 1.29 * cam["tanfovy"])
 
 
 def test_depth_or_alpha_only_losses_train_the_geometry(scenes, rast, gpu):
