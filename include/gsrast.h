@@ -569,6 +569,40 @@ int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int
                               const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
                               const float* dL_dacc_depth, const float* dL_dalpha);
 
+/* ---- Absolute screen-space gradient: the densification statistic of AbsGS (Ye et al., 2024), gsplat's `absgrad` ----
+ * dL_dmean2D[i] is the SIGNED sum over pixels of each pixel's gradient with respect to Gaussian i's projected centre: a large Gaussian
+ * that half of its pixels pull one way and half the other gets a gradient near zero and is never split.  With GSRAST_RENDER_ABSGRAD the
+ * backward also writes
+ *     dL_dmean2D_abs[i][k] = sum over pixels p of | d(sum_c dL_dpix[c][p] colour[c][p]  (+ the aux terms of GSRAST_RENDER_AUX)) / d mean2D[i][k] |,  k = 0, 1
+ * in the units of dL_dmean2D (the reference's normalised device coordinates: a pixel offset times 0.5 W, 0.5 H), so that
+ * dL_dmean2D_abs[i][k] >= |dL_dmean2D[i][k]|, with equality when every pixel pulls the same way.  [P][2] floats, fully overwritten like every
+ * other output: zero for every Gaussian whose dL_dmean2D row is zero because no pixel consumed it.  Densification thresholds for it are the
+ * caller's choice and are higher than for the signed gradient (AbsGS: about 2x).
+ * gsrast_backward_flags_abs / gsrast_backward_raw_flags_abs are gsrast_backward_flags / gsrast_backward_raw_flags with the sink as one more
+ * trailing argument; without the bit (and with a NULL sink) they ARE those calls.  The bit belongs to these two symbols: every other
+ * backward symbol, and every forward, refuses it as an unknown bit (mask it off the flags word given to the forward).  With
+ * options->backward_phase, pass the bit and the sink to both phases.  No other output changes with it.
+ * GSRAST_E_ARG before any device work, one text each: the bit with a NULL sink; a sink without the bit; the bit on a symbol without a sink
+ * (unknown bit); the bit where the transposed blend backward would not run (options->cull == 0, the ablation kernels) -- the rule of
+ * GSRAST_RENDER_AUX.  Like GSRAST_RENDER_AUX it selects the transposed blend backward whatever the pixels per lane say. */
+#define GSRAST_RENDER_ABSGRAD    0x4u
+int gsrast_backward_flags_abs(const gsrast_options* options, unsigned flags,
+                              int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp,
+                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* viewmatrix, const float* projmatrix, const float* campos,
+                              float tan_fovx, float tan_fovy, const int* radii,
+                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                              const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs);
+int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                                  const gsrast_raw_inputs* inputs, float scale_modifier,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                  const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
+                                  const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

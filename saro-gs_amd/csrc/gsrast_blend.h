@@ -1018,7 +1018,12 @@ blend_bwd_cull_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
 // like the colour's.  Per pair dL/dalpha gains (z - acD) dD (acD: the accumulated depth behind the pair), the background term becomes
 // -T_final (bg . dp - dA) (alpha = 1 - T_final), and dL/dz = sum over pixels of alpha T dD -- a fourth colour-like sum of the
 // transposed phase, committed to float 9 of the record (preprocess_bwd_kernel adds it to the gradient of the view-space z).
-template <int EXPMODE, bool AUX = false>
+// ABS (GSRAST_RENDER_ABSGRAD): the absolute screen-space gradient of AbsGS (Ye et al., 2024; gsplat's absgrad) as well -- per pixel
+// |u (dx conic.x + dy conic.y)| and |u (dy conic.z + dx conic.y)|, the magnitudes of the terms whose SIGNED sums are floats 0 and 1 of the
+// record, summed into floats 10 and 11 with |opacity| 0.5 W and |opacity| 0.5 H (|commit_scale| of k = 0, 1).  The sign changes from pixel to
+// pixel, so the separable row moments cannot give them: two more chains per pixel in the transposed phase (one FMA for each factor, one
+// for each sum: the |.| are source modifiers) and two more group sums.  Without ABS none of it is instantiated.
+template <int EXPMODE, bool AUX = false, bool ABS = false>
 __global__ void __launch_bounds__(256) GSRAST_BWD_OCC
 blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                         const uint32_t* __restrict__ order, int W, int H,
@@ -1221,6 +1226,7 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
             const float4 a = s0[j];
             const float4 b = s1[j];
             float v8[8], Cb = 0.f, Cd = 0.f;        // (Cd: AUX, sum of alpha T dL/dacc_depth)
+            float Ax = 0.f, Ay = 0.f;               // (ABS: sum |u (dx conic.x + dy conic.y)|, sum |u (dy conic.z + dx conic.y)|)
             const float2* urow = &pbuf[wave][jj][k];
             if constexpr (B8) {
                 // Round 5: SEPARABLE moments.  In the 8 x 8 block lane (k, jj) walks ONE column (pixel k + 8 i = column k of row i): dx is the
@@ -1231,6 +1237,9 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                 // per phase.  SQ_INSTS_VALU per launch at 3 M: 230 M -> see profiles/r05_*.  The rounding differs from summing u dx^2 term by
                 // term but is of the same size (both are relative to |by|^2 sum |u|); gradients stay within the 1e-5 bar of the fp64 oracle.
                 float M0 = 0.f, M1 = 0.f, M2 = 0.f, Cr = 0.f, Cg = 0.f;
+                // ABS: the pixel's factors are linear in the row, e(i) = e(0) - i conic: one FMA each from the lane's two constants
+                float ex0 = 0.f, ey0 = 0.f;
+                if constexpr (ABS) { const float dxc = a.x - pxk0, byc = a.y - sy0; ex0 = dxc * a.z + byc * a.w; ey0 = byc * b.x + dxc * a.w; }
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     const float2 ud = urow[i * 8];
@@ -1241,6 +1250,10 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                     else if (i > 1) { M1 = __builtin_fmaf(uu, (float)i, M1); M2 = __builtin_fmaf(uu, (float)(i * i), M2); }
                     Cr = __builtin_fmaf(dd, dpr[i][0], Cr); Cg = __builtin_fmaf(dd, dpr[i][1], Cg); Cb = __builtin_fmaf(dd, dpr[i][2], Cb);
                     if constexpr (AUX) Cd = __builtin_fmaf(dd, sdD[wave][k + 8 * i], Cd);
+                    if constexpr (ABS) {
+                        const float ex = i == 0 ? ex0 : __builtin_fmaf(-(float)i, a.w, ex0), ey = i == 0 ? ey0 : __builtin_fmaf(-(float)i, b.x, ey0);
+                        Ax = __builtin_fmaf(__builtin_fabsf(uu), __builtin_fabsf(ex), Ax); Ay = __builtin_fmaf(__builtin_fabsf(uu), __builtin_fabsf(ey), Ay);
+                    }
                 }
                 const float dx = a.x - pxk0, by = a.y - sy0;
                 const float m0 = M0 * b.y, m1 = M1 * b.y, m2 = M2 * b.y;  // the opacity factor of dL/dG = opacity * dL/dalpha, once
@@ -1264,6 +1277,10 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
                     Su += uu;
                     Cr = __builtin_fmaf(dd, dpr[i][0], Cr); Cg = __builtin_fmaf(dd, dpr[i][1], Cg); Cb = __builtin_fmaf(dd, dpr[i][2], Cb);
                     if constexpr (AUX) Cd = __builtin_fmaf(dd, sdD[wave][k + 8 * i], Cd);
+                    if constexpr (ABS) {
+                        Ax = __builtin_fmaf(__builtin_fabsf(uu), __builtin_fabsf(dx * a.z + dy * a.w), Ax);
+                        Ay = __builtin_fmaf(__builtin_fabsf(uu), __builtin_fabsf(dy * b.x + dx * a.w), Ay);
+                    }
                 }
                 Sx *= b.y; Sy *= b.y; Sxx *= b.y; Sxy *= b.y; Syy *= b.y;
                 v8[0] = Sx * a.z + Sy * a.w; v8[1] = Sy * b.x + Sx * a.w; v8[2] = Sxx; v8[3] = Sxy; v8[4] = Syy; v8[5] = Su; v8[6] = Cr; v8[7] = Cg;
@@ -1271,17 +1288,22 @@ blend_bwd_cull_t_kernel(const uint2* __restrict__ ranges, const uint32_t* __rest
             const float tot = group8_sum8_transposed(v8, lane);     // lane (k, jj): total of value k for instance jj
             const float tb = group8_sum(Cb);
             const float td = AUX ? group8_sum(Cd) : 0.f;
+            const float tax = ABS ? group8_sum(Ax) : 0.f, tay = ABS ? group8_sum(Ay) : 0.f;
             if ((alive >> jj) & 1u) {
                 lds_add_f32(&acc[j][k], tot * commit_scale);
                 if (k == 0u) lds_add_f32(&acc[j][8], tb);
                 if constexpr (AUX) { if (k == 1u) lds_add_f32(&acc[j][9], td); }
+                if constexpr (ABS) {
+                    if (k == 2u) lds_add_f32(&acc[j][10], tax * (__builtin_fabsf(b.y) * (0.5f * (float)W)));
+                    if (k == 3u) lds_add_f32(&acc[j][11], tay * (__builtin_fabsf(b.y) * (0.5f * (float)H)));
+                }
             }
         }
         __syncthreads();
-        // commit: 16 adjacent lanes per staged instance, lane q < 9 (AUX: 10) adds sum q to float q of the Gaussian's 64-byte record
+        // commit: 16 adjacent lanes per staged instance, lane q < 9 (AUX: 10, ABS: 12) adds sum q to float q of the Gaussian's 64-byte record
         for (uint32_t e = t; e < cnt * 16u; e += NT) {
             const uint32_t slot = e >> 4, q = e & 15u;
-            if (q < (AUX ? 10u : 9u)) {
+            if (q < (ABS ? 12u : AUX ? 10u : 9u)) {
                 const float v = acc[slot][q];
                 if (v != 0.f) atomicAdd(grec + (size_t)sid[slot] * GREC + q, v);
             }

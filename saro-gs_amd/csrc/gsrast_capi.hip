@@ -698,7 +698,7 @@ void launch_blend_fwd(int exp_mode, bool cull, int ppl, uint32_t grid, hipStream
     });
 }
 
-// blend backward: ablation | <exp_mode> x (transposed: <aux> | culled: <pixels per lane> | un-culled: <pixels per lane>)
+// blend backward: ablation | <exp_mode> x (transposed: <aux, abs> | culled: <pixels per lane> | un-culled: <pixels per lane>)
 void launch_blend_bwd(int exp_mode, const BlendBwdPick& k, uint32_t grid, hipStream_t s, const BlendArgs& a)
 {
     const uint32_t* bcnt = a.from_buckets ? a.bcnt : nullptr;
@@ -709,11 +709,11 @@ void launch_blend_bwd(int exp_mode, const BlendBwdPick& k, uint32_t grid, hipStr
     if (k.ablate) return pick_int<1, 2>(k.ablate, [&](auto abl) { uncull(int_c<0>{}, int_c<4>{}, abl); });
     pick_int<0, 1, 2>(exp_mode, [&](auto mode) {
         constexpr int MODE = decltype(mode)::value;
-        if (k.transposed) pick_bool(k.aux, [&](auto aux) {
-            constexpr bool AUX = decltype(aux)::value;
-            blend_bwd_cull_t_kernel<MODE, AUX><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
-                                                                    bcnt, a.blist, AUX ? a.dad : nullptr, AUX ? a.dal : nullptr);
-        });
+        if (k.transposed) pick_bool(k.aux, [&](auto aux) { pick_bool(k.abs, [&](auto abs_c) {
+            constexpr bool AUX = decltype(aux)::value, ABS = decltype(abs_c)::value;
+            blend_bwd_cull_t_kernel<MODE, AUX, ABS><<<grid, 256, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec,
+                                                                         bcnt, a.blist, AUX ? a.dad : nullptr, AUX ? a.dal : nullptr);
+        }); });
         else if (k.cull) pick_int<4, 2, 1>(k.ppl, [&](auto lanes) {
             constexpr int PPL = decltype(lanes)::value;
             blend_bwd_cull_kernel<MODE, PPL><<<grid, 256 / PPL, 0, s>>>(a.ranges, a.plist, a.order, a.W, a.H, a.gx, a.T, a.r0, a.r1, a.r2, a.bg, a.fT, a.nc, a.tm, a.dpix, a.grec, bcnt, a.blist);
@@ -2316,6 +2316,7 @@ struct BwdCall {
     float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot; void* stream;
     bool raw_family; const gsrast_raw_inputs* raw; const gsrast_raw_grads* raw_grads;
     unsigned flags; const float *dL_dacc_depth, *dL_dalpha;      // GSRAST_RENDER_*; the aux gradients are looked at only with GSRAST_RENDER_AUX
+    bool abs_symbol = false; float* dL_dmean2D_abs = nullptr;    // a *_flags_abs symbol; its [P][2] sink (GSRAST_RENDER_ABSGRAD)
 };
 } // namespace
 
@@ -2345,7 +2346,8 @@ struct BackwardRun {
         const int P = c.P, M = c.M;
         if (c.raw_family) o.sh_grad_factors = (c.raw_grads && c.raw_grads->d_sh_factor) ? 1 : 0;      // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
         plan = plan_backward(o, BackwardInputs{ c.flags, P, c.D, c.R, c.width, c.height, c.raw_family, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr),
-                                                c.colors_precomp != nullptr, c.cov3D_precomp != nullptr, c.dL_dacc_depth != nullptr || c.dL_dalpha != nullptr }, snapshot_switches());
+                                                c.colors_precomp != nullptr, c.cov3D_precomp != nullptr, c.dL_dacc_depth != nullptr || c.dL_dalpha != nullptr,
+                                                c.abs_symbol, c.dL_dmean2D_abs != nullptr }, snapshot_switches());
         if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
         if (c.raw_family) {
             rawin = c.raw;
@@ -2424,6 +2426,7 @@ struct BackwardRun {
         LateRowsArgs la{}; int n = 0;
         auto add = [&](float* p, int rl) { if (p && rl > 0) { la.ptr[n] = p; la.rowlen[n] = rl; n++; } };
         add(c.dL_dmean2D, 3); add(c.dL_dopacity, 1); add(c.dL_dmean3D, 3); add(c.dL_dconic, 4); add(c.dL_dcolor, 3); add(c.dL_dcov3D, 6);
+        if (plan.abs) add(c.dL_dmean2D_abs, 2);
         if (rawin || plan.use_sr) { add(c.dL_dscale, 3); add(c.dL_drot, 4); }
         if (rawin) { add(rawg.d_rot_res, 7); add(rawg.d_trbf, 1); add(rawg.d_shs_res, c.M * 3); add(rawg.d_dc, 3); add(rawg.d_rest, c.M * 3 - 3); }
         else if (plan.use_sh && !o.sh_grad_factors) add(c.dL_dsh, c.M * 3);
@@ -2502,7 +2505,7 @@ struct BackwardRun {
                     P, c.D, c.M, c.means3D, c.radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB),
                     at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), c.dL_dmean2D, c.dL_dconic, c.dL_dopacity, c.dL_dcolor,
                     c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, plan.factors, (plan.late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched),
-                    plan.aux ? 1 : 0, at<float4>(geom, GL.rec1));
+                    plan.aux ? 1 : 0, at<float4>(geom, GL.rec1), plan.abs ? c.dL_dmean2D_abs : nullptr);
             };
             // (grouped implies sparse)
             if (plan.grouped) launch(std::true_type{}, std::true_type{});
@@ -2529,7 +2532,35 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
     return r.plan.join_late ? r.join() : GSRAST_OK;
 }
 
-// ---- the exported backwards: adapters that fill a BwdCall (include/gsrast.h: gsrast_backward = _ex(NULL) = _flags(0), _aux = _flags(AUX)) ----
+// ---- the exported backwards: adapters that fill a BwdCall (include/gsrast.h: gsrast_backward = _ex(NULL) = _flags(0), _aux = _flags(AUX),
+// _flags = _flags_abs without the sink: GSRAST_RENDER_ABSGRAD is refused there) ----
+int gsrast_backward_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                              float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                              const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                              const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
+                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha, true, dL_dmean2D_abs });
+}
+
+int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                                  const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                                  float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
+                                  float* dL_dmean2D_abs)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha,
+                                           true, dL_dmean2D_abs });
+}
+
 int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                           float scale_modifier, const float* rotations, const float* cov3D_precomp,

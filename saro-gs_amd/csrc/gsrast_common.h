@@ -36,9 +36,11 @@ constexpr int WAVE = 64;            // CDNA4 wavefront
 //                        the bucket depth sort (gsrast_binning.h, NB ~ P/256 buckets of CAP slots) cuts the depth axis into
 //                        buckets of EQUAL POPULATION by it; bk_count u32[8][NB], bk_slab uint4[NB][8][CAP/8] (arrival order), bk_order / bk_wincl
 //                        u32[NB][CAP] (sorted ids, inclusive width scan inside the bucket), bk_info uint4[NB], bk_base u32[NB] (compact column-run totals)
-//   grec     f32[16P]    backward only: per-Gaussian gradient record {dL/dmean2D.x, .y, dL/dconic a, b, c, dL/dopacity, dL/dr, dg, db,
-//                        7 unused}, one 64-byte line per Gaussian.  gsrast_backward zero-fills it, the blend backward adds the nine sums
-//                        of a (tile, Gaussian) pair with nine adjacent lanes, the per-Gaussian backward reads it with three 16-byte loads
+//   grec     f32[16P]    backward only: per-Gaussian gradient record {0, 1: dL/dmean2D.x, .y; 2-4: dL/dconic a, b, c; 5: dL/dopacity;
+//                        6-8: dL/dr, dg, db; 9: dL/d(view-space z), aux only; 10, 11: sum over pixels of |dL/dmean2D.x|, |.y|,
+//                        GSRAST_RENDER_ABSGRAD only; 4 unused}, one 64-byte line per Gaussian.  gsrast_backward zero-fills it (floats 0-11
+//                        at least), the blend backward adds the nine (ten, twelve) sums of a (tile, Gaussian) pair with as many adjacent
+//                        lanes, the per-Gaussian backward reads it with three 16-byte loads
 #ifndef GSRAST_REC_STRIDE
 #define GSRAST_REC_STRIDE 1
 #endif

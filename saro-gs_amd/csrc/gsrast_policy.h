@@ -196,7 +196,7 @@ inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, c
     ForwardPlan p;
     p.aux = (in.flags & GSRAST_RENDER_AUX) != 0; p.aa = (in.flags & GSRAST_RENDER_ANTIALIAS) != 0;
     p.culled = culled_blend(o, false);
-    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) p.refusal = "flags: unknown bits";
+    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) p.refusal = "flags: unknown bits";      // (GSRAST_RENDER_ABSGRAD is a backward's bit)
     else if (!options_valid(o)) p.refusal = "forward: bad option value";
     else if (p.aux && !p.culled) p.refusal = "forward: acc_depth / alpha need the culled blend kernel (options.cull != 0, fwd_pixels_per_lane == 0)";
     if (p.refusal || in.P <= 0 || in.W <= 0 || in.H <= 0) return p;      // (the shape is refused, or nothing is rendered)
@@ -229,12 +229,14 @@ inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, c
 // The same for a backward call: everything that follows from its options, flags and shape, the kind of its inputs and the one snapshot of the
 // switches (plan_backward).  Whether the context's side stream could be had is the one second-phase answer (side_answer).
 // tests/test_policy.py reads the plan through gsrast_debug_backward_plan.
-struct BackwardInputs { unsigned flags; int P, D, R, W, H; bool raw_family, sh, colors_precomp, cov3D_precomp, aux_grads /* dL_dacc_depth or dL_dalpha is given */; };
-// Which blend backward runs.  transposed: blend_bwd_cull_t_kernel; ablate 1 / 2: blend_bwd_kernel<0, 4, ablate> (experiments), else 0
-struct BlendBwdPick { int ppl = 1; bool cull = false, transposed = false, aux = false; int ablate = 0; };
+struct BackwardInputs { unsigned flags; int P, D, R, W, H; bool raw_family, sh, colors_precomp, cov3D_precomp, aux_grads /* dL_dacc_depth or dL_dalpha is given */;
+                        bool abs_symbol = false /* the call came through a symbol that has a dL_dmean2D_abs argument */, abs_sink = false /* ... and it is not NULL */; };
+// Which blend backward runs.  transposed: blend_bwd_cull_t_kernel<.., aux, abs>; ablate 1 / 2: blend_bwd_kernel<0, 4, ablate> (experiments), else 0
+struct BlendBwdPick { int ppl = 1; bool cull = false, transposed = false, aux = false; int ablate = 0; bool abs = false; };
 struct BackwardPlan {
     const char* refusal = nullptr;      // GSRAST_E_ARG with this text: unknown flags, a bad option value, aux without the culled kernels (in this order)
     bool aux = false, aa = false;                     // an aux gradient is given (both NULL is the plain backward); the state comes from an anti-aliased forward
+    bool abs = false;                                 // GSRAST_RENDER_ABSGRAD: the blend backward sums |dL/dmean2D| per pixel, the per-Gaussian backward writes dL_dmean2D_abs
     bool do_blend = false, do_geom = false;           // options.backward_phase: the blend backward / the per-Gaussian backward is part of this call
     bool use_sh = false, use_sr = false;              // colours from SH coefficients; covariances from scales + rotations
     bool zero_records = false;                        // the gradient records are zero-filled (the caller does not vouch for them, or the forward was told no backward would follow)
@@ -266,10 +268,16 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     BackwardPlan p;
     const bool aux_flag = (in.flags & GSRAST_RENDER_AUX) != 0;
     p.aux = aux_flag && in.aux_grads; p.aa = (in.flags & GSRAST_RENDER_ANTIALIAS) != 0;
+    p.abs = (in.flags & GSRAST_RENDER_ABSGRAD) != 0;
     p.pick.cull = culled_blend(o, true);
-    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS)) p.refusal = "flags: unknown bits";
+    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS | GSRAST_RENDER_ABSGRAD)) p.refusal = "flags: unknown bits";
     else if (!options_valid(o)) p.refusal = "backward: bad option value";
     else if (aux_flag && !p.pick.cull) p.refusal = "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)";
+    else if (p.abs && !in.abs_symbol) p.refusal = "flags: unknown bits (GSRAST_RENDER_ABSGRAD is known only to the gsrast_backward*_flags_abs symbols, which have its sink)";
+    else if (p.abs && !in.abs_sink) p.refusal = "backward: GSRAST_RENDER_ABSGRAD with a NULL dL_dmean2D_abs";
+    else if (!p.abs && in.abs_sink) p.refusal = "backward: dL_dmean2D_abs without GSRAST_RENDER_ABSGRAD";
+    else if (p.abs && (!p.pick.cull || g.ablate == 1 || g.ablate == 2))
+        p.refusal = "backward: GSRAST_RENDER_ABSGRAD needs the transposed blend backward (options.cull != 0, no ablation kernel)";
     if (p.refusal || in.P <= 0 || in.R < 0 || in.W <= 0 || in.H <= 0) return p;      // (the shape is refused, or there is nothing to do)
     p.P = in.P; p.do_blend = o.backward_phase != 2; p.do_geom = o.backward_phase != 1;
     p.use_sh = in.sh && !in.colors_precomp; p.use_sr = !in.cov3D_precomp;
@@ -283,10 +291,10 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     // and above; fewer win for small images (more waves) and small Gaussians (finer culling), more win at 4K.
     const int forced = o.bwd_pixels_per_lane;
     p.pick.ppl = forced ? forced : p.T >= 32768 ? 4 : (p.T >= 8192 ? 2 : 1);
-    p.pick.aux = p.aux;
+    p.pick.aux = p.aux; p.pick.abs = p.abs;
     p.pick.ablate = (!p.aux && (g.ablate == 1 || g.ablate == 2)) ? g.ablate : 0;
-    // aux: always the transposed kernel, whatever the pixels per lane and the A/B switch say
-    p.pick.transposed = p.aux || (p.pick.cull && !p.pick.ablate && p.pick.ppl == 1 && g.bwd_transposed);
+    // aux, abs: always the transposed kernel, whatever the pixels per lane and the A/B switch say
+    p.pick.transposed = p.aux || p.abs || (p.pick.cull && !p.pick.ablate && p.pick.ppl == 1 && g.bwd_transposed);
     p.blend = p.do_blend && in.R > 0;
     const bool ordered = p.blend && p.pick.cull && o.lpt != 0;
     p.from_buckets = ordered && p.T <= BUCKET_MAX_TILES;      // the forward blend appended every tile to the backward work buckets

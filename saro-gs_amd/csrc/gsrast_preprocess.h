@@ -1088,7 +1088,10 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       // aux (gsrast_backward_aux): float 9 of the record (gr2.y) is dL/d(view-space z) from the blend backward's acc_depth
                       // gradient -- added to the projection chain's own; 0: the record's nine sums only, exactly as without it
                       int aux = 0,
-                      const float4* __restrict__ rec1 = nullptr /* AA: GeomLayout::rec1 of the forward, whose .y is o_eff */)
+                      const float4* __restrict__ rec1 = nullptr /* AA: GeomLayout::rec1 of the forward, whose .y is o_eff */,
+                      // GSRAST_RENDER_ABSGRAD: floats 10 and 11 of the record (gr2.z, gr2.w), blend_bwd_cull_t_kernel<.., ABS>'s sums of the
+                      // per-pixel |dL/dmean2D| -- written wherever dL_dmean2D is, zero for the same rows; null: not wanted
+                      float* __restrict__ dL_dmean2D_abs = nullptr /* [P][2] out */)
 {
     __shared__ float sh_lds[PP_THREADS * PP_SH_STRIDE];
     __shared__ uint32_t s_list[GROUPED ? PB_GROUP : 1];
@@ -1190,6 +1193,7 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     const Cam cam = load_cam(cam_args);
     if (i < P) {    // the screen-space gradients leave in the reference's arrays (rasterize_points.cu:150-158), written once
         dL_dmean2D[3 * (size_t)i] = g2x; dL_dmean2D[3 * (size_t)i + 1] = g2y; dL_dmean2D[3 * (size_t)i + 2] = 0.0f;
+        if (dL_dmean2D_abs) { dL_dmean2D_abs[2 * (size_t)i] = gr2.z; dL_dmean2D_abs[2 * (size_t)i + 1] = gr2.w; }      // (uniform)
         if (AA && live) { }     // (written below, once comp is known)
         else
         if (RAW) {      // d(opacity logit) = d_opacity * trbf * s (1 - s),  d(trbf) = d_opacity * s

@@ -43,11 +43,13 @@ EXPORTS = (
     "gsrast_forward_ex", "gsrast_backward_ex", "gsrast_forward_raw", "gsrast_backward_raw", "gsrast_alloc_prealloc",
     "gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux",
     "gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags",
+    "gsrast_backward_flags_abs", "gsrast_backward_raw_flags_abs",
 )
 
 # include/gsrast.h: the flags word of the gsrast_*_flags entry points
 RENDER_AUX = 0x1
 RENDER_ANTIALIAS = 0x2
+RENDER_ABSGRAD = 0x4      # the two gsrast_backward*_flags_abs symbols only
 
 
 class OptionsStruct(C.Structure):
@@ -161,6 +163,8 @@ def lib() -> C.CDLL:
                                               ("forward_raw", None, "", [vp, opt], fwd_raw), ("backward_raw", None, "", [opt], bwd_raw)):
         table = [("gsrast_" + family + plain, head + args), ("gsrast_" + family + "_aux", head + args + [vp, vp]),
                  ("gsrast_" + family + "_flags", head + [C.c_uint] + args + [vp, vp])]
+        if family.startswith("backward"):      # + the [P,2] sink of GSRAST_RENDER_ABSGRAD
+            table.append(("gsrast_" + family + "_flags_abs", head + [C.c_uint] + args + [vp, vp, vp]))
         for name, types in table + ([(legacy, args)] if legacy else []):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = types
@@ -515,11 +519,14 @@ class _Arena:
             self.callbacks = None
 
 
-def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple) -> int:
+def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple, absgrad: Optional[torch.Tensor] = None) -> int:
     """The one native render call: gsrast_<family>_flags(*head, flags, *args, *aux) for family "forward" / "backward" / "forward_raw" /
     "backward_raw" (flags = 0 is exactly the _ex / _raw call, include/gsrast.h).  Returns its result (forward: the number of rendered
-    instances), raises on an error code."""
+    instances), raises on an error code.  `absgrad` (backward families): the [P,2] sink of GSRAST_RENDER_ABSGRAD -- the _flags_abs
+    symbol with the bit set; None: the _flags symbol, as before the sink existed."""
     name = "gsrast_" + family + "_flags"
+    if absgrad is not None:
+        name, flags, aux = name + "_abs", flags | RENDER_ABSGRAD, (*aux, absgrad.data_ptr())
     rc = getattr(lib(), name)(*head, flags, *args, *aux)
     if rc < 0:
         raise _err(rc, name)
@@ -619,7 +626,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                  first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
-                                 dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False):
+                                 dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
+                                 absgrad: Optional[torch.Tensor] = None):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
@@ -627,9 +635,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     geomBuffer since its forward, whose gradient records are therefore still zero (the library skips its zero-fill).
     `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- GSRAST_RENDER_AUX when
     either is given.  `antialiasing`: the state comes from an antialiasing=True forward (GSRAST_RENDER_ANTIALIAS; the same flags for
-    both phases of a two-phase backward)."""
+    both phases of a two-phase backward).  `absgrad`: a [P,2] sink (check_absgrad) that the call overwrites with the absolute
+    screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD); it is no gradient of anything and never lives in a GradArena."""
     dev = _require_gpu(means3D)
     P = int(means3D.shape[0])
+    check_absgrad(absgrad, P, dev)
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])  # rasterize_points.cu:141-142
     flags, aux, _keep = _backward_flags(dL_dacc_depth, dL_dalpha, H, W, dev, antialiasing)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
@@ -678,10 +688,29 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
             def call(phase):      # options travel per call: no process-wide switch is flipped
                 _render_call("backward", (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux)
+                             args, flags, aux, absgrad)
 
             _run_backward(ar, call, P, geomBuffer, dev)
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+def check_absgrad(absgrad: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
+    """The caller-owned sink of the absolute screen-space gradient: a contiguous float32 [P,2] tensor on the render's device (None: not
+    wanted).  ValueError otherwise -- the library gets a pointer and would write P * 2 floats through it."""
+    if absgrad is None:
+        return
+    if not isinstance(absgrad, torch.Tensor):
+        raise ValueError(f"absgrad must be a tensor or None (got {type(absgrad).__name__})")
+    if tuple(absgrad.shape) != (P, 2):
+        raise ValueError(f"absgrad must be [{P}, 2] (got {list(absgrad.shape)})")
+    if absgrad.dtype is not torch.float32:
+        raise ValueError(f"absgrad must be float32 (got {absgrad.dtype})")
+    if absgrad.device != dev:
+        raise ValueError(f"absgrad must live on {dev} (got {absgrad.device})")
+    if not absgrad.is_contiguous():
+        raise ValueError("absgrad must be contiguous")
+    if absgrad.requires_grad:
+        raise ValueError("absgrad is a statistic the backward writes, not a differentiable tensor (requires_grad must be False)")
 
 
 def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, antialiasing: bool):
@@ -748,12 +777,14 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
 def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                      first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
-                                     dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False) -> dict:
+                                     dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
+                                     absgrad: Optional[torch.Tensor] = None) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
-    rasterize_gaussians_backward; `antialiasing`: as rasterize_gaussians_backward."""
+    rasterize_gaussians_backward; `antialiasing`, `absgrad`: as rasterize_gaussians_backward."""
     dev = _require_gpu(raw["xyz"])
     P = int(raw["xyz"].shape[0])
+    check_absgrad(absgrad, P, dev)
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])
     st, keep, M = _raw_struct(raw, dev, P)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
@@ -800,7 +831,7 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
 
             def call(phase):
                 _render_call("backward_raw", (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux)
+                             args, flags, aux, absgrad)
 
             _run_backward(ar, call, P, geomBuffer, dev)
     if keep["motion_res"] is not None:

@@ -28,6 +28,12 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   Mip-Splatting: each Gaussian's opacity is scaled by sqrt(det cov2D / det(cov2D + 0.3 I)) so that the 0.3 px^2 dilation does not
   inflate small or distant Gaussians; differentiable, also through that factor (include/gsrast.h: GSRAST_RENDER_ANTIALIAS).  Train
   and evaluate with the same setting.
+* not in the reference: ``forward(..., absgrad=sink)`` (keyword-only, default None; also ``rasterize_gaussians`` and
+  ``GaussianRasterizerRaw``, together with ``return_aux`` and ``antialiasing``) -- the absolute screen-space gradient of AbsGS
+  (gsplat's ``absgrad``): `sink` is a caller-owned contiguous float32 ``[P, 2]`` tensor on the render's device, and every backward of
+  that render OVERWRITES it with sum over pixels |d loss_pixel / d means2D[:, :2]|, in the units of ``means2D.grad`` (>= its absolute
+  value; zero for Gaussians no pixel used).  Nothing is attached to ``means2D``; ``.backward()`` and ``torch.autograd.grad`` fill it
+  alike.  A wrong shape / dtype / device / layout raises ``ValueError`` at forward time (include/gsrast.h: GSRAST_RENDER_ABSGRAD).
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -72,7 +78,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, antialiasing):
+                raster_settings, antialiasing, absgrad):
         aux = ctx._forward_cls.AUX      # (of the class .apply was called on)
         if aux:
             _no_arena_for_aux()
@@ -90,6 +96,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=aux, antialiasing=antialiasing)
         ctx.raster_settings = rs
         ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
+        ctx.absgrad = absgrad                      # the caller's [P,2] sink (not a saved tensor: every backward writes it)
         ctx.num_rendered = num_rendered
         ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
         ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
@@ -117,14 +124,14 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
             geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad)
         ctx.gs_backwards += 1
         # one gradient per forward input, in input order; absent optionals get None
         def opt(g, x):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None)
 
 
 class _RasterizeGaussiansAux(_RasterizeGaussians):
@@ -133,21 +140,29 @@ class _RasterizeGaussiansAux(_RasterizeGaussians):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_aux=False, *, antialiasing: bool = False):
+                        raster_settings, return_aux=False, *, antialiasing: bool = False, absgrad: Optional[torch.Tensor] = None):
     """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha; `antialiasing` (not in the
-    reference): the opacity-compensated 2-D filter (module docstring)."""
+    reference): the opacity-compensated 2-D filter; `absgrad` (not in the reference): the [P,2] sink of the absolute screen-space
+    gradient (module docstring)."""
     fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
+    if absgrad is not None:
+        _C.check_absgrad(absgrad, int(means3D.shape[0]), means3D.device)
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                    cov3Ds_precomp, raster_settings, bool(antialiasing))
+                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad)
 
 
 def _antialiasing_of(render_options: dict) -> bool:
     """The keyword-only `antialiasing` (default False) of GaussianRasterizer.forward / GaussianRasterizerRaw.forward.  It arrives through
     **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone."""
-    unknown = set(render_options) - {"antialiasing"}
+    unknown = set(render_options) - {"antialiasing", "absgrad"}
     if unknown:
         raise TypeError(f"forward() got an unexpected keyword argument {sorted(unknown)[0]!r}")
     return bool(render_options.get("antialiasing", False))
+
+
+def _absgrad_of(render_options: dict) -> Optional[torch.Tensor]:
+    """The keyword-only `absgrad` (default None) of the same two methods, through **render_options like `antialiasing`."""
+    return render_options.get("absgrad", None)
 
 
 _EMPTY = torch.empty(0)
@@ -168,7 +183,7 @@ class GaussianRasterizer(nn.Module):
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
                 rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *, return_aux: bool = False,
                 **render_options):
-        antialiasing = _antialiasing_of(render_options)
+        antialiasing, absgrad = _antialiasing_of(render_options), _absgrad_of(render_options)
         have_sh, have_rgb = shs is not None, colors_precomp is not None
         if have_sh == have_rgb:
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -187,11 +202,11 @@ class GaussianRasterizer(nn.Module):
             scales if scales is not None else empty,
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
-            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing)
+            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing, absgrad=absgrad)
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
     # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so is antialiasing
-    # (default False, through **render_options: _antialiasing_of).
+    # (default False, through **render_options: _antialiasing_of) and absgrad (default None: _absgrad_of).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
 
@@ -204,7 +219,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     AUX = False
 
     @staticmethod
-    def forward(ctx, means2D, raster_settings, antialiasing, *raw_tensors):
+    def forward(ctx, means2D, raster_settings, antialiasing, absgrad, *raw_tensors):
         aux = ctx._forward_cls.AUX
         if aux:
             _no_arena_for_aux()
@@ -216,6 +231,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             rs.sh_degree, rs.campos, forward_only=forward_only, aux=aux, antialiasing=antialiasing)
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
         ctx.antialiasing = bool(antialiasing)
+        ctx.absgrad = absgrad
         ctx.gs_options = _C.current_options()
         ctx.gs_options["forward_only"] = int(forward_only)
         ctx.gs_backwards = 0
@@ -238,11 +254,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
             rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad)
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None, None) + grads
+        return (g["dL_dmeans2D"], None, None, None) + grads
 
 
 class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
@@ -257,7 +273,7 @@ class GaussianRasterizerRaw(nn.Module):
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
     being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), and the keyword-only
-    `antialiasing=True` (default False), as GaussianRasterizer."""
+    `antialiasing=True` (default False) and `absgrad=sink` (default None), as GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -265,8 +281,10 @@ class GaussianRasterizerRaw(nn.Module):
 
     def forward(self, xyz, means2D, rotation, scaling, opacity, features_dc, features_rest, motion_residual=None, rot_residual=None,
                 trbfoutput=None, shs_residual=None, *, return_aux: bool = False, **render_options):
-        antialiasing = _antialiasing_of(render_options)
+        antialiasing, absgrad = _antialiasing_of(render_options), _absgrad_of(render_options)
+        if absgrad is not None:
+            _C.check_absgrad(absgrad, int(xyz.shape[0]), xyz.device)
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
         fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
-        return fn.apply(means2D, self.raster_settings, antialiasing, *[raw[n] for n in _C.RAW_NAMES])
+        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, *[raw[n] for n in _C.RAW_NAMES])

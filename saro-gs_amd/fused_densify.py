@@ -51,13 +51,19 @@ class DensifyStats:
         return int(self.denom.shape[0])
 
     @torch.no_grad()
-    def update(self, step_out: Dict[str, torch.Tensor]) -> None:
+    def update(self, step_out: Dict[str, torch.Tensor], use_absgrad: bool = False) -> None:
         """step_out: what `view_parallel.distributed_step` returns.  Its "viewspace_point_grad" [P,1] is ALREADY the per-visible mean
         (sum of the per-view norms / visibility count, train.py:286-287) and is added as it is.  A dict with "viewspace_point_grad_sum"
         [P] or [P,1] instead -- the plain sum over the batch -- is divided by "visibility_count" here.  "visibility_count" [P] (rows
-        with count > 0 are updated, the others untouched) and "radii" [P] (max over the batch) are read in both forms."""
-        is_mean = "viewspace_point_grad_sum" not in step_out
-        grad = step_out["viewspace_point_grad" if is_mean else "viewspace_point_grad_sum"]
+        with count > 0 are updated, the others untouched) and "radii" [P] (max over the batch) are read in both forms.
+        use_absgrad=True: "viewspace_point_absgrad" [P,1] (distributed_step's per-visible mean of the absolute screen-space gradient,
+        there when the views rendered with ``absgrad=``) is accumulated in place of "viewspace_point_grad"; KeyError if it is absent.
+        The densification threshold for it is the caller's: higher than for the signed gradient (AbsGS: about 2x)."""
+        if use_absgrad:
+            is_mean, grad = True, step_out["viewspace_point_absgrad"]
+        else:
+            is_mean = "viewspace_point_grad_sum" not in step_out
+            grad = step_out["viewspace_point_grad" if is_mean else "viewspace_point_grad_sum"]
         P = self.P
         dev = _C._require_gpu(self.denom)
         f = lambda t, n: _flat_f32(t, n, P, dev)  # noqa: E731

@@ -510,6 +510,16 @@ def _lane_streams(dev: torch.device, n: int) -> list:
     return _LANE_STREAMS[key]
 
 
+def _absgrad_norm(out: dict) -> Optional[torch.Tensor]:
+    """||viewspace_absgrad[:, :2]|| of one view's `out` (the sink its backward has just filled), or None if the view carries none."""
+    sink = out.get("viewspace_absgrad")
+    return None if sink is None else torch.norm(sink.detach()[:, :2], dim=-1)
+
+
+def _add_opt(a: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return b if a is None else a if b is None else a + b
+
+
 def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch: Optional[int] = None,
                      views_in_flight: int = 1) -> Dict[str, torch.Tensor]:
     """One training iteration's gradient computation, sharded one view per rank -- the drop-in for the reference's sequential batch
@@ -529,6 +539,11 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
     "radii" [P] (max over the batch), "viewspace_point_grad" [P,1] (sum of the per-view norms / visibility count where
     visible), plus "loss" (mean over the batch, for logging).  `batch` defaults to len(views).
 
+    A view whose `out` also carries "viewspace_absgrad" -- the [P,2] sink it gave the rasterizer as ``absgrad=`` (the absolute
+    screen-space gradient of AbsGS, filled by that view's backward) -- adds ||viewspace_absgrad[:, :2]|| to a second statistic, and the
+    result has "viewspace_point_absgrad" [P,1]: the same per-visible mean, reduced across ranks like its sibling (one more SUM of [P];
+    a rank without a view learns from the loss reduction that it has to take part).  Every view of the batch carries the key, or none.
+
     views_in_flight = n > 1 (a rank that renders several views of the batch, i.e. batch > world size): consecutive views of this
     rank alternate between n streams, so that one view's binning (latency-bound) runs under the other's blend kernels (VALU-bound)
     -- measured on one MI355X at 1e6 Gaussians, 1080p: 1050 -> 1227 views/s with two views in flight (three: no better).  Each lane
@@ -543,6 +558,7 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
     batch = len(views) if batch is None else batch
     bucket.zero()
     grad_norm = vis_count = max_radii = None
+    abs_norm = None             # sum of the per-view ||viewspace_absgrad[:, :2]||, if the views carry it
     loss_sum = None
     mine = list(views_of_rank(len(views), rank, world))
     if views_in_flight > 1 and len(mine) > 1:
@@ -570,8 +586,9 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
                 vis = out["visibility_filter"].to(gn.dtype)
                 rad = out["radii"].to(gn.dtype)
                 ls = out["loss"].detach()
+                an = _absgrad_norm(out)
                 st = stats[k]
-                stats[k] = (gn, vis, rad, ls) if st is None else (st[0] + gn, st[1] + vis, torch.maximum(st[2], rad), st[3] + ls)
+                stats[k] = (gn, vis, rad, ls, an) if st is None else (st[0] + gn, st[1] + vis, torch.maximum(st[2], rad), st[3] + ls, _add_opt(st[4], an))
         for k in range(n):
             if streams[k] is not None:
                 main.wait_stream(streams[k])
@@ -583,6 +600,7 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
             vis_count = st[1] if vis_count is None else vis_count + st[1]
             max_radii = st[2] if max_radii is None else torch.maximum(max_radii, st[2])
             loss_sum = st[3] if loss_sum is None else loss_sum + st[3]
+            abs_norm = _add_opt(abs_norm, st[4])
         mine = []
     for i in mine:
         out = render_loss_fn(views[i])
@@ -595,8 +613,10 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
         vis_count = vis if vis_count is None else vis_count + vis
         max_radii = rad if max_radii is None else torch.maximum(max_radii, rad)
         loss_sum = out["loss"].detach() if loss_sum is None else loss_sum + out["loss"].detach()
+        abs_norm = _add_opt(abs_norm, _absgrad_norm(out))
         vsp.grad = None
         bucket.cache()
+    had_view = grad_norm is not None
     if grad_norm is None:       # a rank without a view in this iteration (batch < world) still takes part in the collectives
         P = bucket.leaves[0].shape[0]
         z = torch.zeros(P, dtype=torch.float32, device=bucket.flat.device)
@@ -604,11 +624,24 @@ def distributed_step(bucket: StepBucket, views: Sequence, render_loss_fn, batch:
     work = dist.all_reduce(bucket.flat, op=dist.ReduceOp.SUM, async_op=True) if multi else None
     reduce_densification_stats(grad_norm, vis_count, max_radii)
     if multi:
-        dist.all_reduce(loss_sum, op=dist.ReduceOp.SUM)
+        # (the loss travels with "some rank has the absgrad statistic": a rank without a view must join that reduction too)
+        pair = torch.stack([loss_sum.reshape(()), torch.full_like(loss_sum, 1.0 if abs_norm is not None else 0.0).reshape(())])
+        dist.all_reduce(pair, op=dist.ReduceOp.SUM)
+        loss_sum = pair[0]
+        # (a rank that rendered knows the answer; only one without a view reads the flag back)
+        if (abs_norm is not None) if had_view else float(pair[1]) > 0.0:
+            if abs_norm is None:
+                abs_norm = torch.zeros_like(grad_norm)
+            dist.all_reduce(abs_norm, op=dist.ReduceOp.SUM)
         work.wait()
     bucket.assign(1.0 / batch)
     visible = vis_count > 0
     vgrad = grad_norm.clone()
     vgrad[visible] = vgrad[visible] / vis_count[visible]                            # train.py:286-287
-    return {"visibility_count": vis_count, "visibility_filter": visible, "radii": max_radii,
-            "viewspace_point_grad": vgrad.unsqueeze(1), "loss": loss_sum / batch}
+    res = {"visibility_count": vis_count, "visibility_filter": visible, "radii": max_radii,
+           "viewspace_point_grad": vgrad.unsqueeze(1), "loss": loss_sum / batch}
+    if abs_norm is not None:
+        agrad = abs_norm.clone()
+        agrad[visible] = agrad[visible] / vis_count[visible]
+        res["viewspace_point_absgrad"] = agrad.unsqueeze(1)
+    return res
