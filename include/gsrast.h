@@ -317,7 +317,9 @@ int gsrast_debug_forward_plan(gsrast_context* ctx, const gsrast_options* options
  * records zero-filled, 5 sh_dir_derivs runs, 6 ... on the side stream, 7 late fill wanted, 8 late fill (late_rows_zero on the side stream), 9 its kernel skipped
  * ("ablate" 3), 10 side stream joined BEHIND preprocess_bwd, 11 the blend backward runs, 12 culled, 13 transposed, 14 its aux instantiation, 15 launch order from
  * the work buckets, 16 from tile_order, 17 sh_factor runs, 18 preprocess_bwd leaves dL_dsh to it, 19 sparse preprocess_bwd, 20 grouped; bits 21-23 pixels per
- * lane (1 / 2 / 4), 24-25 the "ablate" blend kernel (0 / 1 / 2), 26-27 "mutate".  grids (may be NULL) receives { sh_dir_derivs' grid, preprocess_bwd's grid } (0: not launched). */
+ * lane (1 / 2 / 4), 24-25 the "ablate" blend kernel (0 / 1 / 2), 26-27 "mutate", 28 pose sums (GSRAST_RENDER_POSEGRAD).  words[5] also takes 32: a
+ * gsrast_backward*_flags_pose call, 64: its dL_dcamera given, 128: its pose_scratch given, 256: its dL_dmean2D_abs given -- without 32 the plan stands for a
+ * symbol that has none of them.  grids (may be NULL) receives { sh_dir_derivs' grid, preprocess_bwd's grid } (0: not launched). */
 int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, const int* words, int* grids);
 int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
@@ -602,6 +604,47 @@ int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags,
                                   const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
                                   const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
                                   const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs);
+
+/* ---- Camera-pose gradients: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos (gsplat's gradients on `viewmats`; the pose-optimising 3DGS forks) ----
+ * viewmatrix [4][4], projmatrix [4][4] and campos [3] are three INDEPENDENT inputs, as they are passed: a caller that composes them
+ * (projmatrix = viewmatrix @ projection, campos = inverse(viewmatrix)[3][:3]) chains through its own composition.  Storage is row-vector,
+ * transposed: t = [mean, 1] @ viewmatrix, hom = [mean, 1] @ projmatrix.  With GSRAST_RENDER_POSEGRAD the backward also writes
+ *     dL_dcamera[35] = dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]      (row-major like the inputs, fully overwritten)
+ * -- the gradient of the function every other output of this backward differentiates, with its conventions (the 0.99 alpha clamp straight-through,
+ * no gradient through the median depth, a frustum-clamped t.x / t.y a constant inside the Jacobian, det^2 / (det^2 + 1e-7) in the conic chain):
+ *   viewmatrix: through the view-space mean (the accumulated depth of GSRAST_RENDER_AUX included) and through the rotation inside T = J W;
+ *   projmatrix: through means2D, ndc = hom.xy / (hom.w + 1e-7): columns 0, 1 and 3;
+ *   campos:     through the SH view direction: minus the sum of the direction part of dL_dmean3D.
+ * Column 3 of dL_dviewmatrix and column 2 of dL_dprojmatrix are exactly zero (the forward never reads them), dL_dcampos is exactly zero with
+ * colors_precomp or SH degree 0.  tan_fovx / tan_fovy (the focal lengths inside the Jacobian) are not differentiated.
+ * Every workgroup of the per-Gaussian backward reduces its Gaussians' terms and writes one row of partial sums to pose_scratch
+ * (gsrast_pose_scratch_bytes(P) bytes, 16-byte aligned, the caller's; no state buffer grows); a one-workgroup kernel adds the rows in a fixed order
+ * in fp64.  No atomics: the same gradient records give the same bits.  No other output changes with the bit.
+ * gsrast_backward_flags_pose / gsrast_backward_raw_flags_pose are the _flags_abs symbols with two more trailing arguments; without the bit (and
+ * with both NULL) they ARE those calls.  The bit belongs to these two symbols: every other backward symbol, and every forward, refuses it as an
+ * unknown bit.  With options->backward_phase, pass the bit and both pointers to both phases: dL_dcamera is written by phase 2 (or by phase 0).
+ * GSRAST_E_ARG before any device work, one text each: the bit on a symbol without the arguments ("flags: unknown bits"); the bit with a NULL dL_dcamera;
+ * the bit with a NULL pose_scratch; dL_dcamera or pose_scratch without the bit. */
+#define GSRAST_RENDER_POSEGRAD   0x8u
+size_t gsrast_pose_scratch_bytes(int P);
+int gsrast_backward_flags_pose(const gsrast_options* options, unsigned flags,
+                               int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp,
+                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos,
+                               float tan_fovx, float tan_fovy, const int* radii,
+                               char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                               float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                               const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs,
+                               float* dL_dcamera /*[35]*/, char* pose_scratch);
+int gsrast_backward_raw_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                                   const gsrast_raw_inputs* inputs, float scale_modifier,
+                                   const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                   const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                   const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
+                                   const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs,
+                                   float* dL_dcamera /*[35]*/, char* pose_scratch);
 
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose

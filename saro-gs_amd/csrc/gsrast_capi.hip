@@ -842,8 +842,10 @@ int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, co
 {
     if (!options || !words) return fail(GSRAST_E_ARG, "debug_backward_plan: NULL argument");
     const int in = words[5];
-    BackwardPlan p = plan_backward(*options, BackwardInputs{ flags, words[0], words[1], words[2], words[3], words[4], (in & 1) != 0, (in & 2) != 0, (in & 4) != 0, (in & 8) != 0, (in & 16) != 0 },
-                                   snapshot_switches());
+    BackwardInputs bi{ flags, words[0], words[1], words[2], words[3], words[4], (in & 1) != 0, (in & 2) != 0, (in & 4) != 0, (in & 8) != 0, (in & 16) != 0 };
+    bi.pose_symbol = (in & 32) != 0; bi.pose_out = (in & 64) != 0; bi.pose_scratch = (in & 128) != 0;
+    bi.abs_symbol = bi.pose_symbol; bi.abs_sink = (in & 256) != 0;      // (a _pose symbol has the _abs symbol's sink argument too)
+    BackwardPlan p = plan_backward(*options, bi, snapshot_switches());
     if (p.refusal) return fail(GSRAST_E_ARG, p.refusal);
     p.side_answer(p.wants_side() && words[6] != 0);
     if (grids) { grids[0] = p.derivs_grid; grids[1] = p.per_gaussian_grid; }
@@ -851,7 +853,7 @@ int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, co
                           p.blend, p.pick.cull, p.pick.transposed, p.pick.aux, p.from_buckets, p.tile_order, p.sh_factor, p.factors != 0, p.sparse, p.grouped };
     int v = 0;
     for (size_t k = 0; k < sizeof bits / sizeof bits[0]; k++) v |= bits[k] ? 1 << k : 0;
-    return v | p.pick.ppl << 21 | p.pick.ablate << 24 | (p.mutate & 3) << 26;
+    return v | p.pick.ppl << 21 | p.pick.ablate << 24 | (p.mutate & 3) << 26 | (p.pose ? 1 << 28 : 0);
 }
 
 // A lookup in kOptions, plus the names that are not plain words: "pixels_per_lane" writes both directions and reads the forward's, "word_fork"
@@ -2317,6 +2319,7 @@ struct BwdCall {
     bool raw_family; const gsrast_raw_inputs* raw; const gsrast_raw_grads* raw_grads;
     unsigned flags; const float *dL_dacc_depth, *dL_dalpha;      // GSRAST_RENDER_*; the aux gradients are looked at only with GSRAST_RENDER_AUX
     bool abs_symbol = false; float* dL_dmean2D_abs = nullptr;    // a *_flags_abs symbol; its [P][2] sink (GSRAST_RENDER_ABSGRAD)
+    bool pose_symbol = false; float* dL_dcamera = nullptr; char* pose_scratch = nullptr;      // a *_flags_pose symbol; its [35] output and scratch (GSRAST_RENDER_POSEGRAD)
 };
 } // namespace
 
@@ -2347,7 +2350,7 @@ struct BackwardRun {
         if (c.raw_family) o.sh_grad_factors = (c.raw_grads && c.raw_grads->d_sh_factor) ? 1 : 0;      // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
         plan = plan_backward(o, BackwardInputs{ c.flags, P, c.D, c.R, c.width, c.height, c.raw_family, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr),
                                                 c.colors_precomp != nullptr, c.cov3D_precomp != nullptr, c.dL_dacc_depth != nullptr || c.dL_dalpha != nullptr,
-                                                c.abs_symbol, c.dL_dmean2D_abs != nullptr }, snapshot_switches());
+                                                c.abs_symbol, c.dL_dmean2D_abs != nullptr, c.pose_symbol, c.dL_dcamera != nullptr, c.pose_scratch != nullptr }, snapshot_switches());
         if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
         if (c.raw_family) {
             rawin = c.raw;
@@ -2383,6 +2386,7 @@ struct BackwardRun {
         if (c.cov3D_precomp && !c.dL_dcov3D) return fail(GSRAST_E_ARG, "backward: cov3D_precomp path needs dL_dcov3D");
         if (plan.use_sh && (!c.dL_dsh || !c.campos)) return fail(GSRAST_E_ARG, "backward: SH path needs dL_dsh and campos");
         if (plan.use_sr && (!c.scales || !c.rotations || !c.dL_dscale || !c.dL_drot)) return fail(GSRAST_E_ARG, "backward: scale/rotation path needs their gradients");
+        if (plan.pose && ((uintptr_t)c.pose_scratch & 15)) return fail(GSRAST_E_ARG, "backward: pose_scratch must be 16-byte aligned");
         cam = make_cam(c.viewmatrix, c.projmatrix, c.campos, c.tan_fovx, c.tan_fovy, c.scale_modifier, c.width, c.height);
         GL = geom_layout((size_t)P); IL = img_layout((size_t)c.width, (size_t)c.height);
         geom = c.geom_buffer; img = c.image_buffer; grec = at<float>(geom, GL.grec);
@@ -2498,20 +2502,25 @@ struct BackwardRun {
         const float* sh_in = rawin ? c.shs : (plan.use_sh ? c.shs : nullptr);
         const float* sc_in = rawin ? c.scales : (plan.use_sr ? c.scales : nullptr);
         const float* ro_in = rawin ? c.rotations : (plan.use_sr ? c.rotations : nullptr);
-        // <RAW, SPARSE, GROUPED, AA> (aa: the kernel's AA instantiation -- the plain ones are the same code as before the flag existed)
-        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(plan.aa, [&](auto aa_c) {
+        // <RAW, SPARSE, GROUPED, AA, POSE> (aa, pose: the kernel's own instantiations -- the plain ones are the same code as before the flags existed)
+        float* const pose_rows = plan.pose ? reinterpret_cast<float*>(c.pose_scratch) : nullptr;
+        pick_bool(rawin != nullptr, [&](auto raw_c) { pick_bool(plan.aa, [&](auto aa_c) { pick_bool(plan.pose, [&](auto pose_c) {
             auto launch = [&](auto sparse_c, auto grouped_c) {
-                preprocess_bwd_kernel<decltype(raw_c)::value, decltype(sparse_c)::value, decltype(grouped_c)::value, decltype(aa_c)::value><<<plan.per_gaussian_grid, PP_THREADS, 0, s>>>(
+                preprocess_bwd_kernel<decltype(raw_c)::value, decltype(sparse_c)::value, decltype(grouped_c)::value, decltype(aa_c)::value, decltype(pose_c)::value><<<plan.per_gaussian_grid, PP_THREADS, 0, s>>>(
                     P, c.D, c.M, c.means3D, c.radii, raw, rawg, sh_in, at<unsigned char>(geom, GL.clamped), at<float4>(geom, GL.shdA), at<float4>(geom, GL.shdB),
                     at<float>(geom, GL.shdC), sc_in, ro_in, cov, cam, reinterpret_cast<const float4*>(grec), c.dL_dmean2D, c.dL_dconic, c.dL_dopacity, c.dL_dcolor,
                     c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, plan.factors, (plan.late_fill ? at<unsigned long long>(geom, GL.color_skip) : nullptr), at<uint32_t>(geom, GL.scalars), at<unsigned char>(geom, GL.untouched),
-                    plan.aux ? 1 : 0, at<float4>(geom, GL.rec1), plan.abs ? c.dL_dmean2D_abs : nullptr);
+                    plan.aux ? 1 : 0, at<float4>(geom, GL.rec1), plan.abs ? c.dL_dmean2D_abs : nullptr, pose_rows);
             };
             // (grouped implies sparse)
             if (plan.grouped) launch(std::true_type{}, std::true_type{});
             else pick_bool(plan.sparse, [&](auto sparse_c) { launch(sparse_c, std::false_type{}); });
-        }); });
+        }); }); });
         GS_LAUNCHED("preprocess_bwd");
+        if (plan.pose) {      // the workgroups' rows -> dL_dcamera, one workgroup, a fixed order (inside the kernel timer: it is part of the per-Gaussian backward)
+            pose_grad_reduce_kernel<<<1, 1024, 0, s>>>(plan.per_gaussian_grid, pose_rows, c.dL_dcamera);
+            GS_LAUNCHED("pose_grad_reduce");
+        }
         return GSRAST_OK;
     }
 };
@@ -2524,6 +2533,8 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
     RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
     BackwardRun r(options, c);
     int rc = r.check_and_plan();
+    if (rc == GSRAST_OK && c.P == 0 && r.plan.pose && r.o.backward_phase != 1 && hipMemsetAsync(c.dL_dcamera, 0, POSE_OUT * sizeof(float), r.s) != hipSuccess)
+        return fail(GSRAST_E_DEVICE, "backward: dL_dcamera of an empty scene");      // (no Gaussian: the camera's gradient is zero, written like any other)
     if (rc != GSRAST_OK || c.P == 0) return rc;
     if ((rc = r.zero_records()) != GSRAST_OK || (rc = r.fork_derivs()) != GSRAST_OK || (rc = r.fork_zero_rows()) != GSRAST_OK) return rc;
     if ((rc = r.blend()) != GSRAST_OK || (rc = r.sh_factor()) != GSRAST_OK) return rc;
@@ -2560,6 +2571,37 @@ int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags,
                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha,
                                            true, dL_dmean2D_abs });
 }
+
+// _flags_abs = _flags_pose without the camera's output: GSRAST_RENDER_POSEGRAD is refused there
+int gsrast_backward_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                               float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                               const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                               float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
+                               const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs, float* dL_dcamera, char* pose_scratch)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
+                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha, true, dL_dmean2D_abs, true, dL_dcamera, pose_scratch });
+}
+
+int gsrast_backward_raw_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
+                                   const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                                   float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                   const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
+                                   float* dL_dmean2D_abs, float* dL_dcamera, char* pose_scratch)
+{
+    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
+                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha,
+                                           true, dL_dmean2D_abs, true, dL_dcamera, pose_scratch });
+}
+
+// One row of POSE_ROW floats per workgroup of the per-Gaussian backward, sized for its larger grid (the plain form: PP_THREADS Gaussians each)
+size_t gsrast_pose_scratch_bytes(int P) { return P > 0 ? (((size_t)P + PP_THREADS - 1) / PP_THREADS) * POSE_ROW * sizeof(float) : (size_t)POSE_ROW * sizeof(float); }
 
 int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales,

@@ -230,13 +230,16 @@ inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, c
 // switches (plan_backward).  Whether the context's side stream could be had is the one second-phase answer (side_answer).
 // tests/test_policy.py reads the plan through gsrast_debug_backward_plan.
 struct BackwardInputs { unsigned flags; int P, D, R, W, H; bool raw_family, sh, colors_precomp, cov3D_precomp, aux_grads /* dL_dacc_depth or dL_dalpha is given */;
-                        bool abs_symbol = false /* the call came through a symbol that has a dL_dmean2D_abs argument */, abs_sink = false /* ... and it is not NULL */; };
+                        bool abs_symbol = false /* the call came through a symbol that has a dL_dmean2D_abs argument */, abs_sink = false /* ... and it is not NULL */;
+                        // the call came through a gsrast_backward*_flags_pose symbol; its dL_dcamera / pose_scratch argument is not NULL
+                        bool pose_symbol = false, pose_out = false, pose_scratch = false; };
 // Which blend backward runs.  transposed: blend_bwd_cull_t_kernel<.., aux, abs>; ablate 1 / 2: blend_bwd_kernel<0, 4, ablate> (experiments), else 0
 struct BlendBwdPick { int ppl = 1; bool cull = false, transposed = false, aux = false; int ablate = 0; bool abs = false; };
 struct BackwardPlan {
     const char* refusal = nullptr;      // GSRAST_E_ARG with this text: unknown flags, a bad option value, aux without the culled kernels (in this order)
     bool aux = false, aa = false;                     // an aux gradient is given (both NULL is the plain backward); the state comes from an anti-aliased forward
     bool abs = false;                                 // GSRAST_RENDER_ABSGRAD: the blend backward sums |dL/dmean2D| per pixel, the per-Gaussian backward writes dL_dmean2D_abs
+    bool pose = false;                                // GSRAST_RENDER_POSEGRAD: preprocess_bwd<.., POSE> sums the camera's gradient, pose_grad_reduce_kernel writes dL_dcamera (with do_geom)
     bool do_blend = false, do_geom = false;           // options.backward_phase: the blend backward / the per-Gaussian backward is part of this call
     bool use_sh = false, use_sr = false;              // colours from SH coefficients; covariances from scales + rotations
     bool zero_records = false;                        // the gradient records are zero-filled (the caller does not vouch for them, or the forward was told no backward would follow)
@@ -269,8 +272,10 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     const bool aux_flag = (in.flags & GSRAST_RENDER_AUX) != 0;
     p.aux = aux_flag && in.aux_grads; p.aa = (in.flags & GSRAST_RENDER_ANTIALIAS) != 0;
     p.abs = (in.flags & GSRAST_RENDER_ABSGRAD) != 0;
+    p.pose = (in.flags & GSRAST_RENDER_POSEGRAD) != 0;
     p.pick.cull = culled_blend(o, true);
-    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS | GSRAST_RENDER_ABSGRAD)) p.refusal = "flags: unknown bits";
+    // (GSRAST_RENDER_POSEGRAD is a known bit only where the symbol has its arguments: everywhere else it is an unknown bit like any other)
+    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS | GSRAST_RENDER_ABSGRAD | (in.pose_symbol ? GSRAST_RENDER_POSEGRAD : 0u))) p.refusal = "flags: unknown bits";
     else if (!options_valid(o)) p.refusal = "backward: bad option value";
     else if (aux_flag && !p.pick.cull) p.refusal = "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)";
     else if (p.abs && !in.abs_symbol) p.refusal = "flags: unknown bits (GSRAST_RENDER_ABSGRAD is known only to the gsrast_backward*_flags_abs symbols, which have its sink)";
@@ -278,6 +283,9 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     else if (!p.abs && in.abs_sink) p.refusal = "backward: dL_dmean2D_abs without GSRAST_RENDER_ABSGRAD";
     else if (p.abs && (!p.pick.cull || g.ablate == 1 || g.ablate == 2))
         p.refusal = "backward: GSRAST_RENDER_ABSGRAD needs the transposed blend backward (options.cull != 0, no ablation kernel)";
+    else if (p.pose && !in.pose_out) p.refusal = "backward: GSRAST_RENDER_POSEGRAD with a NULL dL_dcamera";
+    else if (p.pose && !in.pose_scratch) p.refusal = "backward: GSRAST_RENDER_POSEGRAD with a NULL pose_scratch";
+    else if (!p.pose && (in.pose_out || in.pose_scratch)) p.refusal = "backward: dL_dcamera / pose_scratch without GSRAST_RENDER_POSEGRAD";
     if (p.refusal || in.P <= 0 || in.R < 0 || in.W <= 0 || in.H <= 0) return p;      // (the shape is refused, or there is nothing to do)
     p.P = in.P; p.do_blend = o.backward_phase != 2; p.do_geom = o.backward_phase != 1;
     p.use_sh = in.sh && !in.colors_precomp; p.use_sr = !in.cov3D_precomp;

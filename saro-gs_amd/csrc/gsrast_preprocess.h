@@ -915,11 +915,13 @@ mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __res
 // FACTORS: dL/dsh is not written at all.  Row k of it is w_k(view direction) * g, with g = the clamp-masked colour
 // gradient: a rank-1 outer product of 16 weights that any rank can recompute from the camera position and 3 numbers.
 // The multi-GPU exchange moves g (returned in g_out) instead of the 48 products (gsrast_sh_grad_combine).
-template <bool FACTORS = false>
+// DIR: the term added to dmean is also returned in dir_out[3] -- it is -dL/dcampos of this Gaussian (preprocess_bwd_kernel<.., POSE>).
+template <bool FACTORS = false, bool DIR = false>
 __device__ __forceinline__ void sh_backward(int deg, const float pos[3], const float campos[3],
                                             const float dx[3], const float dy[3], const float dz[3] /* sh_dir_derivs */,
                                             unsigned cl, const float dcol[3],
-                                            float dmean[3], float* __restrict__ dsh)
+                                            float dmean[3], float* __restrict__ dsh,
+                                            float* dir_out = nullptr /* DIR: [3] */)
 {
     const float o0 = pos[0] - campos[0], o1 = pos[1] - campos[1], o2 = pos[2] - campos[2];
     const float len = sqrtf(o0 * o0 + o1 * o1 + o2 * o2);
@@ -950,6 +952,13 @@ __device__ __forceinline__ void sh_backward(int deg, const float pos[3], const f
     const float dd2 = dz[0] * g[0] + dz[1] * g[1] + dz[2] * g[2];
     const float sum2 = o0 * o0 + o1 * o1 + o2 * o2;
     const float inv32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+    if (DIR) {      // the same three sums, kept before they are added
+        dir_out[0] = ((+sum2 - o0 * o0) * dd0 - o1 * o0 * dd1 - o2 * o0 * dd2) * inv32;
+        dir_out[1] = (-o0 * o1 * dd0 + (sum2 - o1 * o1) * dd1 - o2 * o1 * dd2) * inv32;
+        dir_out[2] = (-o0 * o2 * dd0 - o1 * o2 * dd1 + (sum2 - o2 * o2) * dd2) * inv32;
+        dmean[0] += dir_out[0]; dmean[1] += dir_out[1]; dmean[2] += dir_out[2];
+        return;
+    }
     dmean[0] += ((+sum2 - o0 * o0) * dd0 - o1 * o0 * dd1 - o2 * o0 * dd2) * inv32;
     dmean[1] += (-o0 * o1 * dd0 + (sum2 - o1 * o1) * dd1 - o2 * o1 * dd2) * inv32;
     dmean[2] += (-o0 * o2 * dd0 - o1 * o2 * dd1 + (sum2 - o2 * o2) * dd2) * inv32;
@@ -1059,7 +1068,20 @@ sh_dir_derivs_kernel(int P, int D, int M, const float* __restrict__ means3D, con
 // AA (gsrast_backward_flags with GSRAST_RENDER_ANTIALIAS; the state must come from an anti-aliased forward): the record's dL/do_eff = g
 // becomes dL/do = g * comp, and g * o_eff * 0.5 * d(ln rho)/d(c00, c01, c11) joins dL/d(a, b, c) in front of the covariance chain (zero on
 // the floor).  o_eff is the forward's rec1.y.  Every output is still linear in the record: the SPARSE shortcut holds.
-template <bool RAW, bool SPARSE, bool GROUPED = false, bool AA = false>
+// POSE (gsrast_backward_flags_pose with GSRAST_RENDER_POSEGRAD): the gradient of the camera.  viewmatrix, projmatrix and campos are three
+// independent inputs in the row-vector storage t = [mean, 1] @ viewmatrix, hom = [mean, 1] @ projmatrix; every Gaussian adds POSE_TERMS sums:
+//   dV[r][c]  += mean_r dt_c, dV[3][c] += dt_c (c < 3; dt = dtx, dty, dtz below, the aux depth term included) and, through the rotation inside
+//                T = J W, dV[r][c] += sum_j J[j][c] dT[j][r] (the frustum-clamped entries of J constants, as everywhere in this backward);
+//   dPm[r][c] += mean_r dhom_c, dPm[3][c] += dhom_c for c = 0, 1, 3: ndc = hom.xy / (hom.w + 1e-7) through g2x, g2y;
+//   dcampos   -= the view-direction term sh_backward adds to dmean.
+// Column 3 of dV and column 2 of dPm are never read by the forward: not summed, zero in the result.  A lane keeps its sums in registers
+// across the rounds; a Gaussian that is not live adds nothing and is not read.  After the last round: wave_sum_to_lane63 per term, the waves
+// combined through LDS, one row of POSE_ROW floats (POSE_TERMS used) per workgroup written with plain stores to pose_rows[blockIdx.x] --
+// no atomics; pose_grad_reduce_kernel adds the rows in a fixed order.  No other output changes with it.
+constexpr int POSE_TERMS = 27;      // dV rows 0-3 x columns 0-2 | dPm rows 0-3 x columns 0, 1, 3 | dcampos
+constexpr int POSE_ROW = 32;        // floats per workgroup in pose_rows: one 128-byte line
+constexpr int POSE_OUT = 35;        // dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
+template <bool RAW, bool SPARSE, bool GROUPED = false, bool AA = false, bool POSE = false>
 __global__ void __launch_bounds__(PP_THREADS)
 preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, const int* __restrict__ radii, RawArgs raw, RawGrads rawg,
                       const float* __restrict__ shs /* only its presence matters: the coefficients are not read */,
@@ -1091,11 +1113,18 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       const float4* __restrict__ rec1 = nullptr /* AA: GeomLayout::rec1 of the forward, whose .y is o_eff */,
                       // GSRAST_RENDER_ABSGRAD: floats 10 and 11 of the record (gr2.z, gr2.w), blend_bwd_cull_t_kernel<.., ABS>'s sums of the
                       // per-pixel |dL/dmean2D| -- written wherever dL_dmean2D is, zero for the same rows; null: not wanted
-                      float* __restrict__ dL_dmean2D_abs = nullptr /* [P][2] out */)
+                      float* __restrict__ dL_dmean2D_abs = nullptr /* [P][2] out */,
+                      float* __restrict__ pose_rows = nullptr /* POSE: [gridDim.x][POSE_ROW] out, this workgroup's partial sums */)
 {
     __shared__ float sh_lds[PP_THREADS * PP_SH_STRIDE];
     __shared__ uint32_t s_list[GROUPED ? PB_GROUP : 1];
     __shared__ uint32_t s_wtot[PP_THREADS / 64];
+    __shared__ float s_pose[POSE ? (PP_THREADS / 64) * POSE_ROW : 1];
+    float pz[POSE ? POSE_TERMS : 1];
+    if (POSE) {
+#pragma unroll
+        for (int k = 0; k < POSE_TERMS; k++) pz[k] = 0.0f;
+    }
     const int ncoef = (D + 1) * (D + 1);
     const bool staged = shs && M * 3 <= PP_SH_MAX;
     float* my_lds = sh_lds + threadIdx.x * PP_SH_STRIDE;
@@ -1313,18 +1342,33 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     dmean[0] += (pj[0] * mw - pj[3] * mul1) * g2x + (pj[1] * mw - pj[3] * mul2) * g2y;
     dmean[1] += (pj[4] * mw - pj[7] * mul1) * g2x + (pj[5] * mw - pj[7] * mul2) * g2y;
     dmean[2] += (pj[8] * mw - pj[11] * mul1) * g2x + (pj[9] * mw - pj[11] * mul2) * g2y;
+    float ddir[3] = { 0.f, 0.f, 0.f };          // POSE: what sh_backward adds to dmean
     if (shs) {
         const float ddx[3] = { sdA.x, sdA.y, sdA.z }, ddy[3] = { sdA.w, sdB.x, sdB.y }, ddz[3] = { sdB.z, sdB.w, sdC };
         if (sh_factors) {    // the factor itself left with sh_factor_kernel, right after the blend backward
-            sh_backward<true>(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, nullptr);
+            sh_backward<true, POSE>(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, nullptr, ddir);
         } else if (staged) {
-            sh_backward(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, my_lds);
+            sh_backward<false, POSE>(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, my_lds, ddir);
             for (int k = ncoef * 3; k < M * 3; k++) my_lds[k] = 0.0f;
         } else {
             float* dsh = dL_dsh + (size_t)i * M * 3;
-            sh_backward(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, dsh);
+            sh_backward<false, POSE>(D, mean, cam.campos, ddx, ddy, ddz, clamped_in, dcol, dmean, dsh, ddir);
             for (int k = ncoef * 3; k < M * 3; k++) dsh[k] = 0.0f;
         }
+    }
+    if (POSE) {
+        const float J00 = cam.fx * tz, J11 = cam.fy * tz, J02 = -(cam.fx * cv.t[0]) * tz2, J12 = -(cam.fy * cv.t[1]) * tz2;      // (cv.t: clamped)
+        const float dh0 = g2x * mw, dh1 = g2y * mw, dh3 = -(mh[0] * g2x + mh[1] * g2y) * (mw * mw);
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            pz[3 * r + 0] += mean[r] * dtx + J00 * dT[0][r];
+            pz[3 * r + 1] += mean[r] * dty + J11 * dT[1][r];
+            pz[3 * r + 2] += mean[r] * dtz + (J02 * dT[0][r] + J12 * dT[1][r]);
+            pz[12 + 3 * r + 0] += mean[r] * dh0; pz[12 + 3 * r + 1] += mean[r] * dh1; pz[12 + 3 * r + 2] += mean[r] * dh3;
+            pz[24 + r] -= ddir[r];
+        }
+        pz[9] += dtx; pz[10] += dty; pz[11] += dtz;
+        pz[21] += dh0; pz[22] += dh1; pz[23] += dh3;
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) dL_dmeans3D[3 * (size_t)i + k] = dmean[k];
@@ -1399,6 +1443,51 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         if (GROUPED) __syncthreads();           // the next round overwrites the rows
     }
     } // round
+    if (POSE) {      // (every workgroup of the grid writes its row, also one without a live Gaussian: the reduction reads them all)
+        const unsigned wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int k = 0; k < POSE_TERMS; k++) {
+            const float tot = wave_sum_to_lane63(pz[k]);
+            if ((threadIdx.x & 63u) == 63u) s_pose[wv * POSE_ROW + k] = tot;
+        }
+        __syncthreads();
+        if (threadIdx.x < (unsigned)POSE_ROW) {
+            float v = 0.0f;
+            if (threadIdx.x < (unsigned)POSE_TERMS) {
+#pragma unroll
+                for (int w = 0; w < PP_THREADS / 64; w++) v += s_pose[w * POSE_ROW + threadIdx.x];
+            }
+            pose_rows[(size_t)blockIdx.x * POSE_ROW + threadIdx.x] = v;
+        }
+    }
+}
+
+// The second step of the camera gradient: the `rows` partial-sum rows of preprocess_bwd_kernel<.., POSE> added in a fixed order with fp64
+// accumulators by ONE workgroup -- lane (slice, term) takes rows slice, slice + 32, ... of its term, LDS holds the 32 slices, term t's
+// lane adds them in ascending order -- and the 35-float result fully overwritten, the columns nobody sums included.  The same rows give
+// the same bits.  out: dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3], row-major like the inputs.
+__global__ void __launch_bounds__(1024)
+pose_grad_reduce_kernel(int rows, const float* __restrict__ pose_rows, float* __restrict__ out)
+{
+    __shared__ double s_part[32][POSE_ROW];
+    const int t = threadIdx.x & (POSE_ROW - 1), slice = threadIdx.x / POSE_ROW;
+    double a0 = 0.0, a1 = 0.0;
+    int r = slice;
+    for (; r + 32 < rows; r += 64) { a0 += (double)pose_rows[(size_t)r * POSE_ROW + t]; a1 += (double)pose_rows[(size_t)(r + 32) * POSE_ROW + t]; }
+    if (r < rows) a0 += (double)pose_rows[(size_t)r * POSE_ROW + t];
+    s_part[slice][t] = a0 + a1;
+    __syncthreads();
+    if (threadIdx.x < POSE_OUT) {
+        // output float -> term: viewmatrix / projmatrix entry [r][c] is term base + 3 r + (its place among the summed columns)
+        const int o = threadIdx.x;
+        int term = -1;
+        if (o < 16) { const int c = o & 3; if (c < 3) term = 3 * (o >> 2) + c; }
+        else if (o < 32) { const int c = o & 3; if (c != 2) term = 12 + 3 * ((o - 16) >> 2) + (c == 3 ? 2 : c); }
+        else term = 24 + (o - 32);
+        double v = 0.0;
+        if (term >= 0) for (int sl = 0; sl < 32; sl++) v += s_part[sl][term];
+        out[o] = (float)v;
+    }
 }
 
 // The zero rows of the Gaussians the forward's list cut left out (gsrast_common.h; preprocess_bwd_kernel's late_bits): 87 % of the 0.8 GB

@@ -44,12 +44,15 @@ EXPORTS = (
     "gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux",
     "gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags",
     "gsrast_backward_flags_abs", "gsrast_backward_raw_flags_abs",
+    "gsrast_backward_flags_pose", "gsrast_backward_raw_flags_pose", "gsrast_pose_scratch_bytes",
 )
 
 # include/gsrast.h: the flags word of the gsrast_*_flags entry points
 RENDER_AUX = 0x1
 RENDER_ANTIALIAS = 0x2
-RENDER_ABSGRAD = 0x4      # the two gsrast_backward*_flags_abs symbols only
+RENDER_ABSGRAD = 0x4      # the two gsrast_backward*_flags_abs symbols only (and their _pose siblings)
+RENDER_POSEGRAD = 0x8     # the two gsrast_backward*_flags_pose symbols only
+CAMERA_FLOATS = 35        # dL_dcamera: dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
 
 
 class OptionsStruct(C.Structure):
@@ -165,6 +168,8 @@ def lib() -> C.CDLL:
                  ("gsrast_" + family + "_flags", head + [C.c_uint] + args + [vp, vp])]
         if family.startswith("backward"):      # + the [P,2] sink of GSRAST_RENDER_ABSGRAD
             table.append(("gsrast_" + family + "_flags_abs", head + [C.c_uint] + args + [vp, vp, vp]))
+            # + the [35] output and the scratch of GSRAST_RENDER_POSEGRAD
+            table.append(("gsrast_" + family + "_flags_pose", head + [C.c_uint] + args + [vp, vp, vp, vp, vp]))
         for name, types in table + ([(legacy, args)] if legacy else []):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = types
@@ -182,6 +187,8 @@ def lib() -> C.CDLL:
     for name in ("gsrast_geometry_bytes",):
         getattr(L, name).restype = C.c_size_t
         getattr(L, name).argtypes = [ci]
+    L.gsrast_pose_scratch_bytes.restype = C.c_size_t
+    L.gsrast_pose_scratch_bytes.argtypes = [ci]
     L.gsrast_binning_bytes.restype = C.c_size_t
     L.gsrast_binning_bytes.argtypes = [ci, ci, ci]
     L.gsrast_image_bytes.restype = C.c_size_t
@@ -519,18 +526,45 @@ class _Arena:
             self.callbacks = None
 
 
-def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple, absgrad: Optional[torch.Tensor] = None) -> int:
+def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple, absgrad: Optional[torch.Tensor] = None,
+                 camera: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> int:
     """The one native render call: gsrast_<family>_flags(*head, flags, *args, *aux) for family "forward" / "backward" / "forward_raw" /
     "backward_raw" (flags = 0 is exactly the _ex / _raw call, include/gsrast.h).  Returns its result (forward: the number of rendered
     instances), raises on an error code.  `absgrad` (backward families): the [P,2] sink of GSRAST_RENDER_ABSGRAD -- the _flags_abs
-    symbol with the bit set; None: the _flags symbol, as before the sink existed."""
+    symbol with the bit set; None: the _flags symbol, as before the sink existed.  `camera` (backward families): (the [35] output, the
+    scratch) of GSRAST_RENDER_POSEGRAD (_pose_buffers) -- the _flags_pose symbol with the bit set; None: the call as before it existed."""
     name = "gsrast_" + family + "_flags"
-    if absgrad is not None:
+    if camera is not None:
+        name, aux = name + "_pose", (*aux, None if absgrad is None else absgrad.data_ptr(), camera[0].data_ptr(), camera[1].data_ptr())
+        flags |= RENDER_POSEGRAD | (0 if absgrad is None else RENDER_ABSGRAD)
+    elif absgrad is not None:
         name, flags, aux = name + "_abs", flags | RENDER_ABSGRAD, (*aux, absgrad.data_ptr())
     rc = getattr(lib(), name)(*head, flags, *args, *aux)
     if rc < 0:
         raise _err(rc, name)
     return rc
+
+
+_pose_cache: dict = {}
+
+
+def _pose_buffers(P: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(the [35] float32 output, the scratch) of a backward with GSRAST_RENDER_POSEGRAD, kept per device, stream and P: both are fully
+    overwritten by every such backward, and the backward hands autograd a copy of the output."""
+    k = (dev.index, int(_stream_of(dev) or 0), P)
+    v = _pose_cache.get(k)
+    if v is None:
+        if len(_pose_cache) > 16:
+            _pose_cache.clear()
+        v = _pose_cache[k] = (torch.empty((CAMERA_FLOATS,), dtype=torch.float32, device=dev),
+                              torch.empty((int(lib().gsrast_pose_scratch_bytes(P)),), dtype=torch.uint8, device=dev))
+    return v
+
+
+def _camera_result(camera: Optional[Tuple[torch.Tensor, torch.Tensor]]):
+    """(dL_dviewmatrix [4,4], dL_dprojmatrix [4,4], dL_dcampos [3]): views of one fresh copy of the cached output."""
+    g = camera[0].clone()
+    return g[:16].view(4, 4), g[16:32].view(4, 4), g[32:]
 
 
 def _forward(family: str, dev: torch.device, P: int, H: int, W: int, inputs: tuple, forward_only: bool, aux: bool, antialiasing: bool):
@@ -627,7 +661,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                  first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                  dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                 absgrad: Optional[torch.Tensor] = None):
+                                 absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
@@ -636,7 +670,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     `dL_dacc_depth` / `dL_dalpha` ([1,H,W] or None = zero): the upstream gradients of the aux outputs -- GSRAST_RENDER_AUX when
     either is given.  `antialiasing`: the state comes from an antialiasing=True forward (GSRAST_RENDER_ANTIALIAS; the same flags for
     both phases of a two-phase backward).  `absgrad`: a [P,2] sink (check_absgrad) that the call overwrites with the absolute
-    screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD); it is no gradient of anything and never lives in a GradArena."""
+    screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD); it is no gradient of anything and never lives in a GradArena.
+    `camera_grads`: the tuple continues with ``(dL_dviewmatrix[4,4], dL_dprojmatrix[4,4], dL_dcampos[3])`` (include/gsrast.h:
+    GSRAST_RENDER_POSEGRAD); without it the call and its result are what they were before the flag existed."""
     dev = _require_gpu(means3D)
     P = int(means3D.shape[0])
     check_absgrad(absgrad, P, dev)
@@ -675,6 +711,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     factors = ar is not None and ar.sh_factors      # dL_dsh is then only valid after sh_grad_combine(): the kernel writes this view's factor
     dL_dscales = out("scales", (P, 3), not use_sr)
     dL_drotations = out("rotations", (P, 4), not use_sr)
+    camera = _pose_buffers(P, dev) if camera_grads else None
+    if camera is not None and P == 0:
+        camera[0].zero_()
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
@@ -688,10 +727,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
             def call(phase):      # options travel per call: no process-wide switch is flipped
                 _render_call("backward", (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux, absgrad)
+                             args, flags, aux, absgrad, camera)
 
             _run_backward(ar, call, P, geomBuffer, dev)
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    grads = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+    return grads if camera is None else grads + (_camera_result(camera),)
 
 
 def check_absgrad(absgrad: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
@@ -778,10 +818,11 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                      first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                      dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                     absgrad: Optional[torch.Tensor] = None) -> dict:
+                                     absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
-    rasterize_gaussians_backward; `antialiasing`, `absgrad`: as rasterize_gaussians_backward."""
+    rasterize_gaussians_backward; `antialiasing`, `absgrad`: as rasterize_gaussians_backward; `camera_grads`: also "camera", the
+    (dL_dviewmatrix, dL_dprojmatrix, dL_dcampos) of rasterize_gaussians_backward."""
     dev = _require_gpu(raw["xyz"])
     P = int(raw["xyz"].shape[0])
     check_absgrad(absgrad, P, dev)
@@ -821,6 +862,9 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                         d_scaling=g["scaling"].data_ptr(), d_rot_res=_ptr(g.get("rot_res")), d_opacity_logit=g["opacity_logit"].data_ptr(),
                         d_trbf=_ptr(g.get("trbf")), d_features_dc=p_dc, d_features_rest=p_rest, d_shs_res=_ptr(g.get("shs_res")),
                         d_sh_factor=p_fac)
+    camera = _pose_buffers(P, dev) if camera_grads else None
+    if camera is not None and P == 0:
+        camera[0].zero_()
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
@@ -831,9 +875,11 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
 
             def call(phase):
                 _render_call("backward_raw", (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux, absgrad)
+                             args, flags, aux, absgrad, camera)
 
             _run_backward(ar, call, P, geomBuffer, dev)
+    if camera is not None:
+        g["camera"] = _camera_result(camera)
     if keep["motion_res"] is not None:
         g["motion_res"] = g["xyz"]
     return g

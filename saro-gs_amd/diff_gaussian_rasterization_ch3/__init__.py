@@ -34,6 +34,12 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   that render OVERWRITES it with sum over pixels |d loss_pixel / d means2D[:, :2]|, in the units of ``means2D.grad`` (>= its absolute
   value; zero for Gaussians no pixel used).  Nothing is attached to ``means2D``; ``.backward()`` and ``torch.autograd.grad`` fill it
   alike.  A wrong shape / dtype / device / layout raises ``ValueError`` at forward time (include/gsrast.h: GSRAST_RENDER_ABSGRAD).
+* not in the reference: ``forward(..., camera_grads=True)`` (keyword-only, default False; also ``rasterize_gaussians`` and
+  ``GaussianRasterizerRaw``, together with ``return_aux``, ``antialiasing``, ``absgrad`` and a ``GradArena``) -- gradients for the camera:
+  ``raster_settings.viewmatrix``, ``.projmatrix`` and ``.campos`` are differentiated as three independent inputs, each only if it
+  requires grad (gsplat's gradients on ``viewmats``).  A caller that builds ``projmatrix = viewmatrix @ projection`` and
+  ``campos = inverse(viewmatrix)[3, :3]`` from a pose parameter gets that parameter's gradient through autograd.  tanfovx / tanfovy
+  are not differentiated.  When none of the three requires grad the call is the plain one (include/gsrast.h: GSRAST_RENDER_POSEGRAD).
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -78,7 +84,8 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, antialiasing, absgrad):
+                raster_settings, antialiasing, absgrad, *camera):
+        # camera: () or raster_settings' (viewmatrix, projmatrix, campos) once more, as differentiable inputs (_camera_inputs)
         aux = ctx._forward_cls.AUX      # (of the class .apply was called on)
         if aux:
             _no_arena_for_aux()
@@ -97,6 +104,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
         ctx.absgrad = absgrad                      # the caller's [P,2] sink (not a saved tensor: every backward writes it)
+        ctx.camera = bool(camera)                  # the backward also differentiates the camera
         ctx.num_rendered = num_rendered
         ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
         ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
@@ -120,18 +128,19 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_out_color is None:      # a loss that reaches this node through depth (or the aux outputs) only: the reference sees a zero colour gradient (REF:88)
             grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=means3D.device)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
+         grad_scales, grad_rotations, *grad_camera) = _C.rasterize_gaussians_backward(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
             geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad,
+            **({"camera_grads": True} if ctx.camera else {}))
         ctx.gs_backwards += 1
         # one gradient per forward input, in input order; absent optionals get None
         def opt(g, x):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None)
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None) + _camera_grads_out(ctx, rs, grad_camera, 11)
 
 
 class _RasterizeGaussiansAux(_RasterizeGaussians):
@@ -139,22 +148,41 @@ class _RasterizeGaussiansAux(_RasterizeGaussians):
     AUX = True
 
 
+def _camera_inputs(raster_settings, camera_grads: bool) -> tuple:
+    """What camera_grads=True adds to the autograd node's inputs: the settings' (viewmatrix, projmatrix, campos) if any of them requires
+    grad, else nothing -- the node, its arguments and its launches are then the plain call's."""
+    cam = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
+    if camera_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+        return cam
+    return ()
+
+
+def _camera_grads_out(ctx, rs, grad_camera, first: int) -> tuple:
+    """The node's gradients for its camera inputs (input `first` onwards): () without them, else each tensor's gradient in its own shape
+    and dtype, None for one that does not require grad."""
+    if not ctx.camera:
+        return ()
+    return tuple(g.reshape(t.shape).to(t.dtype) if ctx.needs_input_grad[first + k] else None
+                 for k, (g, t) in enumerate(zip(grad_camera[0], (rs.viewmatrix, rs.projmatrix, rs.campos))))
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_aux=False, *, antialiasing: bool = False, absgrad: Optional[torch.Tensor] = None):
+                        raster_settings, return_aux=False, *, antialiasing: bool = False, absgrad: Optional[torch.Tensor] = None,
+                        camera_grads: bool = False):
     """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha; `antialiasing` (not in the
     reference): the opacity-compensated 2-D filter; `absgrad` (not in the reference): the [P,2] sink of the absolute screen-space
-    gradient (module docstring)."""
+    gradient; `camera_grads` (not in the reference): gradients for raster_settings' viewmatrix / projmatrix / campos (module docstring)."""
     fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
     if absgrad is not None:
         _C.check_absgrad(absgrad, int(means3D.shape[0]), means3D.device)
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad)
+                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad, *_camera_inputs(raster_settings, bool(camera_grads)))
 
 
 def _antialiasing_of(render_options: dict) -> bool:
     """The keyword-only `antialiasing` (default False) of GaussianRasterizer.forward / GaussianRasterizerRaw.forward.  It arrives through
     **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone."""
-    unknown = set(render_options) - {"antialiasing", "absgrad"}
+    unknown = set(render_options) - {"antialiasing", "absgrad", "camera_grads"}
     if unknown:
         raise TypeError(f"forward() got an unexpected keyword argument {sorted(unknown)[0]!r}")
     return bool(render_options.get("antialiasing", False))
@@ -163,6 +191,11 @@ def _antialiasing_of(render_options: dict) -> bool:
 def _absgrad_of(render_options: dict) -> Optional[torch.Tensor]:
     """The keyword-only `absgrad` (default None) of the same two methods, through **render_options like `antialiasing`."""
     return render_options.get("absgrad", None)
+
+
+def _camera_grads_of(render_options: dict) -> bool:
+    """The keyword-only `camera_grads` (default False) of the same two methods, through **render_options like `antialiasing`."""
+    return bool(render_options.get("camera_grads", False))
 
 
 _EMPTY = torch.empty(0)
@@ -202,11 +235,13 @@ class GaussianRasterizer(nn.Module):
             scales if scales is not None else empty,
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
-            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing, absgrad=absgrad)
+            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing, absgrad=absgrad,
+            camera_grads=_camera_grads_of(render_options))
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
     # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so is antialiasing
-    # (default False, through **render_options: _antialiasing_of) and absgrad (default None: _absgrad_of).
+    # (default False, through **render_options: _antialiasing_of), absgrad (default None: _absgrad_of) and camera_grads (default
+    # False: _camera_grads_of).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
 
@@ -220,6 +255,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2D, raster_settings, antialiasing, absgrad, *raw_tensors):
+        # (behind the len(_C.RAW_NAMES) raw tensors: () or the camera's three, as _RasterizeGaussians.forward's *camera)
+        raw_tensors, camera = raw_tensors[:len(_C.RAW_NAMES)], raw_tensors[len(_C.RAW_NAMES):]
         aux = ctx._forward_cls.AUX
         if aux:
             _no_arena_for_aux()
@@ -232,6 +269,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
         ctx.antialiasing = bool(antialiasing)
         ctx.absgrad = absgrad
+        ctx.camera = bool(camera)
         ctx.gs_options = _C.current_options()
         ctx.gs_options["forward_only"] = int(forward_only)
         ctx.gs_backwards = 0
@@ -254,11 +292,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
             rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad)
+            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad,
+            **({"camera_grads": True} if ctx.camera else {}))
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None, None, None) + grads
+        return (g["dL_dmeans2D"], None, None, None) + grads + _camera_grads_out(ctx, rs, (g.get("camera"),), 4 + len(_C.RAW_NAMES))
 
 
 class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
@@ -273,7 +312,7 @@ class GaussianRasterizerRaw(nn.Module):
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
     being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), and the keyword-only
-    `antialiasing=True` (default False) and `absgrad=sink` (default None), as GaussianRasterizer."""
+    `antialiasing=True` (default False), `absgrad=sink` (default None) and `camera_grads=True` (default False), as GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -287,4 +326,5 @@ class GaussianRasterizerRaw(nn.Module):
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
         fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
-        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, *[raw[n] for n in _C.RAW_NAMES])
+        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, *[raw[n] for n in _C.RAW_NAMES],
+                        *_camera_inputs(self.raster_settings, _camera_grads_of(render_options)))

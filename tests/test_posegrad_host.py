@@ -1,0 +1,275 @@
+"""CPU: camera-pose gradients (include/gsrast.h: GSRAST_RENDER_POSEGRAD, gsrast_backward_flags_pose / gsrast_backward_raw_flags_pose;
+`camera_grads=` of the Python package).  tests/posegrad_math.py -- the fp64 renderer with the camera as leaf tensors that
+tests/test_gpu_posegrad.py compares the kernels with -- is pinned to tests/math_renderer.py, satisfies the identities the function
+itself implies and agrees with finite differences; the new symbols are declared, exported and bound, the backward's plan reports the
+decision and every refusal is produced before any device work; the package knows the keyword."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import math_renderer as mr
+import posegrad_math as pm
+import test_gpu_independent as tgi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "gsrast.h")
+
+
+def _case(letter):
+    return next(c for c in tgi.CASES if c["name"].startswith(letter + "_"))
+
+
+def _rel(got, want):
+    return float(np.abs(np.asarray(got) - np.asarray(want)).max()) / max(float(np.abs(np.asarray(want)).max()), 1e-300)
+
+
+# ---- 1. the helper is pinned to the independent renderer ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", tgi.CASES, ids=lambda c: c["name"])
+def test_helper_equals_the_math_renderer_with_constant_cameras(c, scenes):
+    """Colour and every leaf gradient of the six cases, 1e-10 relative (both are fp64 evaluations of one function, written twice)."""
+    r = tgi._reference(scenes, c)
+    sc, cam, names = r["sc"], r["cam"], r["names"]
+    e = pm.evaluate(sc, cam, names, pm.cfg_of(cam, sc, c), c, upstream_grads=(r["g"], None, None))
+    assert np.array_equal(e["out"]["vis"], r["out"]["proj"]["disc"]["vis"])
+    assert _rel(e["out"]["color"].detach().numpy(), r["out"]["color"].detach().numpy()) <= 1e-10
+    assert _rel(e["out"]["alpha"].detach().numpy(), 1.0 - r["out"]["final_T"].detach().numpy()) <= 1e-10
+    for n in names:
+        assert float(np.abs(r["want"][n]).max()) > 0.0
+        assert _rel(e["want"][n], r["want"][n]) <= 1e-10, n
+    # the Gaussians' own terms add up to the camera's gradient
+    for k in pm.CAMERA:
+        assert _rel(e["terms"][k].sum(axis=0), e["want"][k]) <= 1e-10 or not e["want"][k].any()
+
+
+# ---- 2. identities of the function itself ------------------------------------------------------------------------------------------------
+def _translation_sides(want, cam):
+    V, Pm_ = np.asarray(cam["viewmatrix"], np.float64), np.asarray(cam["projmatrix"], np.float64)
+    lhs = want["means3D"].sum(axis=0)
+    rhs = V[:3, :] @ want["viewmatrix"][3, :] + Pm_[:3, :] @ want["projmatrix"][3, :] - want["campos"]
+    return lhs, rhs
+
+
+@pytest.mark.parametrize("aux,aa", [(False, False), (True, True)], ids=["plain", "aux_antialiased"])
+def test_translation_identity(scenes, aux, aa):
+    """Moving every Gaussian by d is moving the camera by -d: sum_i dL/dmeans3D_i[k] = sum_c V[k,c] dV[3,c] + sum_c Pm[k,c] dPm[3,c] - dcampos[k],
+    with SH colours (the campos term), the aux outputs and the anti-aliasing factor."""
+    c = _case("b")
+    sc, cam, names = tgi._case_inputs(scenes, c)
+    e = pm.evaluate(sc, cam, names, pm.cfg_of(cam, sc, c, aa=aa), c, aux=aux)
+    lhs, rhs = _translation_sides(e["want"], cam)
+    assert float(np.abs(e["want"]["campos"]).max()) > 0.0 and float(np.abs(lhs).max()) > 0.0
+    scale = float(np.abs(e["terms"]["viewmatrix"][:, 3, :]).sum())      # (what the sums are made of: they may cancel)
+    assert float(np.abs(lhs - rhs).max()) <= 1e-9 * scale, (lhs, rhs)
+
+
+def test_rotation_identity(scenes):
+    """colors_precomp + cov3D_precomp: rotating the world by I + eps G (G antisymmetric) -- means m @ (I + eps G), covariances
+    (I + eps G)^T S (I + eps G) -- is replacing rows 0-2 of viewmatrix and projmatrix by (I + eps G) @ rows: the two first-order changes
+    of the loss agree for the three generators."""
+    c = _case("d")
+    sc, cam, names = tgi._case_inputs(scenes, c)
+    e = pm.evaluate(sc, cam, names, pm.cfg_of(cam, sc, c), c, aux=True)
+    w = e["want"]
+    V, Pm_ = np.asarray(cam["viewmatrix"], np.float64), np.asarray(cam["projmatrix"], np.float64)
+    m, c6 = np.asarray(sc["means3D"], np.float64), np.asarray(sc["cov3D"], np.float64)
+    S = np.stack([c6[:, 0], c6[:, 1], c6[:, 2], c6[:, 1], c6[:, 3], c6[:, 4], c6[:, 2], c6[:, 4], c6[:, 5]], 1).reshape(-1, 3, 3)
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        G = np.zeros((3, 3)); G[i, j], G[j, i] = 1.0, -1.0
+        dS = G.T @ S + S @ G
+        d6 = np.stack([dS[:, 0, 0], dS[:, 0, 1], dS[:, 0, 2], dS[:, 1, 1], dS[:, 1, 2], dS[:, 2, 2]], 1)
+        scene = float((w["means3D"] * (m @ G)).sum() + (w["cov3D"] * d6).sum())
+        camera = float((w["viewmatrix"][:3] * (G @ V[:3])).sum() + (w["projmatrix"][:3] * (G @ Pm_[:3])).sum())
+        scale = float(np.abs(w["means3D"] * (m @ G)).sum() + np.abs(w["cov3D"] * d6).sum())
+        assert abs(scene) > 1e-6 * scale and abs(scene - camera) <= 1e-9 * scale, (scene, camera)
+
+
+def test_structural_zeros(scenes):
+    """The forward never reads column 3 of viewmatrix or column 2 of projmatrix, and with degree 0 / precomputed colours not campos."""
+    for letter in ("b", "d", "e"):
+        c = _case(letter)
+        sc, cam, names = tgi._case_inputs(scenes, c)
+        e = pm.evaluate(sc, cam, names, pm.cfg_of(cam, sc, c), c)
+        assert not e["want"]["viewmatrix"][:, 3].any() and not e["want"]["projmatrix"][:, 2].any()
+        assert e["want"]["viewmatrix"][:, :3].all() and e["want"]["projmatrix"][:, [0, 1, 3]].all()
+        assert e["want"]["campos"].any() == (c["deg"] > 0)
+
+
+# ---- 3. finite differences ---------------------------------------------------------------------------------------------------------------
+def test_helper_agrees_with_central_finite_differences(scenes):
+    """20 Gaussians, none frustum-clamped, no ambiguous pixel, clamp_grad="true" (the forward differentiated as written): all 35 entries
+    against (L(x + h) - L(x - h)) / 2h in fp64 on the discrete decisions of the unperturbed pass (the function is smooth inside one
+    cell of its decisions; h = 1e-5 would flip some alpha >= 1/255 test otherwise, a jump no derivative describes).  Bar: 1e-6 of the
+    tensor's largest entry -- truncation h^2 f''' / 6 ~ 1e-10 relative and rounding eps |L| / h ~ 1e-11 |L| are both far below it, a
+    missing or halved term far above."""
+    c = dict(P=20, seed=5, W=32, H=32, k=1, V=5, deg=3, smul=1.0, bg=(0.2, 0.1, 0.3))
+    sc = scenes.synth(c["P"], c["seed"], sh_degree=3)
+    sc["bg"] = np.array(c["bg"], np.float32)
+    cam = scenes.camera(c["k"], c["V"], c["W"], c["H"])
+    names = ["means3D", "opacities", "shs", "scales", "rotations"]
+    cfg = pm.cfg_of(cam, sc, c, aa=True)
+    e = pm.evaluate(sc, cam, names, cfg, c, aux=True, clamp_grad="true")
+    assert not e["amb"].any() and not e["out"]["clamped"].any() and e["out"]["vis"].sum() >= 10 and e["out"]["n_live"].max() >= 3
+    t = pm.tensors(sc, names, grad=False)
+    base = [np.asarray(cam[k], np.float64) for k in pm.CAMERA]
+
+    def L(k, idx, h):
+        arrs = [b.copy() for b in base]
+        arrs[k][idx] += h
+        with torch.no_grad():
+            out = pm.render(t, *[torch.as_tensor(a) for a in arrs], cfg, decisions=e["out"]["decisions"], clamp_grad="true")
+            return float(pm.loss_of(out, e["g"], e["gD"], e["gA"]))
+
+    h = 1e-5
+    for k, name in enumerate(pm.CAMERA):
+        want = e["want"][name]
+        fd = np.zeros_like(want)
+        for idx in np.ndindex(want.shape):
+            fd[idx] = (L(k, idx, h) - L(k, idx, -h)) / (2 * h)
+        assert float(np.abs(want).max()) > 0.0
+        assert float(np.abs(fd - want).max()) <= 1e-6 * float(np.abs(want).max()), (name, fd, want)
+
+
+# ---- 4. without a device -----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def L(rast):
+    return rast._C.lib()
+
+
+def test_symbols_are_declared_exported_and_bound(rast, L):
+    src = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    raw = C.CDLL(rast._C.LIB_PATH)
+    for n, sib in (("gsrast_backward_flags_pose", "gsrast_backward_flags_abs"), ("gsrast_backward_raw_flags_pose", "gsrast_backward_raw_flags_abs")):
+        assert re.search(r"\bint\s+" + n + r"\s*\(", text), f"{n} not declared in gsrast.h"
+        assert hasattr(raw, n) and n in rast._C.EXPORTS
+        assert getattr(L, n).argtypes == list(getattr(L, sib).argtypes) + [C.c_void_p, C.c_void_p]      # the _abs symbol + output + scratch
+        assert getattr(L, n).restype is C.c_int
+    assert re.search(r"\bsize_t\s+gsrast_pose_scratch_bytes\s*\(\s*int\s+P\s*\)", text) and "gsrast_pose_scratch_bytes" in rast._C.EXPORTS
+    assert re.search(r"#define\s+GSRAST_RENDER_POSEGRAD\s+0x8u\b", src)
+    assert rast._C.RENDER_POSEGRAD == 8 and rast._C.CAMERA_FLOATS == 35
+    assert L.gsrast_abi_version() == 5      # additive: the version does not move
+    # one 128-byte row per workgroup of the larger grid (128 Gaussians each); the state buffers do not grow with the feature
+    assert [L.gsrast_pose_scratch_bytes(p) for p in (1, 128, 129, 1500)] == [128, 128, 256, 12 * 128]
+    assert L.gsrast_pose_scratch_bytes(0) > 0
+
+
+def _plan_fn(rast):
+    fn = C.CDLL(rast._C.LIB_PATH).gsrast_debug_backward_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(rast._C.OptionsStruct), C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    return fn
+
+
+def test_backward_plan_reports_the_pose_sums(L, rast):
+    _C = rast._C
+    POSE, AUX, AA = _C.RENDER_POSEGRAD, _C.RENDER_AUX, _C.RENDER_ANTIALIAS
+    opts = _C.OptionsStruct()
+    L.gsrast_options_init(C.byref(opts))
+    fn, err = _plan_fn(rast), L.gsrast_last_error
+    SYM, OUT, SCR = 32, 64, 128
+    for kind in (2, 2 | 1, 4 | 8):      # SH dense, SH raw, precomputed colour + covariance
+        for extra in (0, AA, AUX):
+            for phase in (0, 1, 2):
+                opts.backward_phase = phase
+                base = (C.c_int * 7)(1000, 3, 5000, 64, 64, kind | (16 if extra == AUX else 0), 1)
+                full = (C.c_int * 7)(1000, 3, 5000, 64, 64, kind | (16 if extra == AUX else 0) | SYM | OUT | SCR, 1)
+                plain, sym, pose = fn(C.byref(opts), extra, base, None), fn(C.byref(opts), extra, (C.c_int * 7)(*base[:5], base[5] | SYM, 1), None), fn(C.byref(opts), extra | POSE, full, None)
+                assert plain >= 0 and not plain & (1 << 28)
+                assert sym == plain                           # the new symbol without the bit and with NULL pointers IS the old call
+                assert pose == plain | (1 << 28)              # bit 28, and no other decision moves
+    opts.backward_phase = 0
+    # the refusals, one text each, before any device work
+    w = lambda bits: (C.c_int * 7)(1000, 3, 5000, 64, 64, 2 | bits, 1)      # noqa: E731
+    assert fn(C.byref(opts), POSE, w(0), None) == -1 and err() == b"flags: unknown bits"
+    assert fn(C.byref(opts), POSE, w(SYM | SCR), None) == -1 and b"GSRAST_RENDER_POSEGRAD with a NULL dL_dcamera" in err()
+    assert fn(C.byref(opts), POSE, w(SYM | OUT), None) == -1 and b"GSRAST_RENDER_POSEGRAD with a NULL pose_scratch" in err()
+    for bits in (SYM | OUT, SYM | SCR, SYM | OUT | SCR):
+        assert fn(C.byref(opts), 0, w(bits), None) == -1 and b"without GSRAST_RENDER_POSEGRAD" in err()
+    assert fn(C.byref(opts), POSE | 0x10, w(SYM | OUT | SCR), None) == -1 and b"unknown bits" in err()
+
+
+def test_bad_arguments_fail_before_any_device_work(L, rast):
+    """The same refusals through the exported symbols (pointers that would fault if anything touched them)."""
+    _C = rast._C
+    one = C.c_void_p(16)
+    AA, ABS, POSE = _C.RENDER_ANTIALIAS, _C.RENDER_ABSGRAD, _C.RENDER_POSEGRAD
+    opts = _C.OptionsStruct()
+    L.gsrast_options_init(C.byref(opts))
+    o, err = C.byref(opts), L.gsrast_last_error
+
+    def dense(sym, P, flags, *tail):
+        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one,
+                               one, one, one, one, one, None, one, None, one, None, one, one, one, None, None, None, *tail)
+
+    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
+    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
+
+    def raw(sym, P, flags, *tail):
+        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one,
+                               C.byref(gr), None, None, None, *tail)
+
+    for call, name in ((dense, "gsrast_backward_flags"), (raw, "gsrast_backward_raw_flags")):
+        for fl in (POSE, POSE | AA):
+            assert call(name + "_pose", 10, fl, None, None, one) == -1 and b"NULL dL_dcamera" in err()
+            assert call(name + "_pose", 10, fl, None, one, None) == -1 and b"NULL pose_scratch" in err()
+            # every other symbol refuses the bit as an unknown one
+            assert call(name, 10, fl) == -1 and b"unknown bits" in err()
+            assert call(name + "_abs", 10, fl, None) == -1 and b"unknown bits" in err()
+        for fl in (0, AA):
+            assert call(name + "_pose", 10, fl, None, one, one) == -1 and b"without GSRAST_RENDER_POSEGRAD" in err()
+            assert call(name + "_pose", 10, fl, None, one, None) == -1 and b"without GSRAST_RENDER_POSEGRAD" in err()
+        # the _abs rules hold on the new symbols
+        assert call(name + "_pose", 10, POSE | ABS, None, one, one) == -1 and b"NULL dL_dmean2D_abs" in err()
+        assert call(name + "_pose", 10, POSE, one, one, one) == -1 and b"without GSRAST_RENDER_ABSGRAD" in err()
+        assert call(name + "_pose", 10, POSE | 0x10, None, one, one) == -1 and b"unknown bits" in err()
+        # a good combination reaches the ordinary checks (here: the negative P), with and without the bit
+        assert call(name + "_pose", -1, POSE, None, one, one) == -1 and b"POSEGRAD" not in err() and b"unknown bits" not in err()
+        assert call(name + "_pose", -1, 0, None, None, None) == -1 and b"POSEGRAD" not in err()
+        assert call(name + "_pose", 0, 0, None, None, None) == 0      # nothing to do, no device touched
+    # no forward knows the bit
+    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
+    cb = ALLOC(lambda ctx, n: None)
+    rc = L.gsrast_forward_flags(None, o, POSE, cb, None, cb, None, cb, None, 10, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one,
+                                None, one, one, one, 0.5, 0.5, 0, one, one, one, None, None, None)
+    assert rc == -1 and b"unknown bits" in err()
+
+
+def test_the_package_knows_the_keyword(rast):
+    """camera_grads is keyword-only, defaults to False, is rejected nowhere, and without a camera tensor that requires grad adds nothing
+    to the autograd node's inputs.  The settings tuple keeps the reference's 11 fields."""
+    import inspect
+    assert len(rast.GaussianRasterizationSettings._fields) == 11
+    p = inspect.signature(rast.rasterize_gaussians).parameters["camera_grads"]
+    assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is False
+    for fn in (rast._C.rasterize_gaussians_backward, rast._C.rasterize_gaussians_raw_backward):
+        q = inspect.signature(fn).parameters["camera_grads"]
+        assert q.kind is inspect.Parameter.KEYWORD_ONLY and q.default is False
+    for fn in (rast.GaussianRasterizer.forward, rast.GaussianRasterizerRaw.forward):
+        assert fn.__kwdefaults__ == {"return_aux": False}
+    assert rast._camera_grads_of({}) is False and rast._camera_grads_of({"camera_grads": 1}) is True
+    assert rast._antialiasing_of({"camera_grads": True}) is False      # (the check of unknown keywords lets it through)
+    with pytest.raises(TypeError):
+        rast._antialiasing_of({"camera_grad": True})
+    P = 5
+    mk = lambda V: rast.GaussianRasterizationSettings(16, 16, 0.5, 0.5, torch.zeros(3), 1.0, V, torch.eye(4), 0, torch.zeros(3), False)      # noqa: E731
+    rs = mk(torch.eye(4))
+    assert rast._camera_inputs(rs, True) == () and rast._camera_inputs(rs, False) == ()
+    rq = mk(torch.eye(4, requires_grad=True))
+    assert rast._camera_inputs(rq, False) == ()
+    got = rast._camera_inputs(rq, True)
+    assert len(got) == 3 and got[0] is rq.viewmatrix and got[1] is rq.projmatrix and got[2] is rq.campos
+    # through the public entry points the keyword gets as far as the device check (no GPU in this test), in all three places
+    m3, m2, op = torch.zeros((P, 3)), torch.zeros((P, 3)), torch.zeros((P, 1))
+    e = torch.empty(0)
+    for rset in (rs, rq):
+        for kw in (dict(), dict(camera_grads=False), dict(camera_grads=True)):
+            with pytest.raises(RuntimeError, match="GPU"):
+                rast.rasterize_gaussians(m3, m2, e, torch.zeros((P, 3)), op, torch.ones((P, 3)), torch.ones((P, 4)), e, rset, **kw)
+            with pytest.raises(RuntimeError, match="GPU"):
+                rast.GaussianRasterizer(rset)(m3, m2, op, colors_precomp=torch.zeros((P, 3)), scales=torch.ones((P, 3)), rotations=torch.ones((P, 4)), **kw)
+            with pytest.raises(RuntimeError, match="GPU"):
+                rast.GaussianRasterizerRaw(rset)(m3, m2, torch.ones((P, 4)), torch.zeros((P, 3)), op, torch.zeros((P, 1, 3)), torch.zeros((P, 15, 3)), **kw)
