@@ -646,6 +646,38 @@ int gsrast_backward_raw_flags_pose(const gsrast_options* options, unsigned flags
                                    const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs,
                                    float* dL_dcamera /*[35]*/, char* pose_scratch);
 
+/* Per-Gaussian blend-weight statistics of one finished forward (no counterpart in the reference): what importance-pruning schemes build
+ * their masks from -- LightGaussian's hit count and sum of alpha T, RadSplat's max alpha T, Mini-Splatting's dominant-pixel counts.
+ *
+ * Definition.  For one finished forward, take pixel p inside the image and Gaussian i.  i CONTRIBUTES to p when the forward blended it
+ * there: its position in the tile's list in force is below n_contrib[p] and it passed the forward's per-pair tests --
+ *     power <= 0 && power >= threshold;  alpha = min(0.99, opacity * exp(power)) >= 1/255;  T * (1 - alpha) >= 1e-4
+ * (the terminating entry does not contribute).  Its weight is w_ip = alpha_ip * T_ip, T_ip the transmittance in front of it.
+ * m_p = pixel_weights[p] clamped to [0, 1]; without pixel_weights m_p = 1.  A pixel with m_p = 0 counts in no column.  One row per Gaussian:
+ *     col 0  weight_sum   sum over p of m_p * w_ip
+ *     col 1  weight_max   max over pixels with m_p > 0 of w_ip (unweighted)
+ *     col 2  pixel_count  number of pixels with m_p > 0 that i contributes to
+ *     col 3  top_count    number of those pixels where w_ip is the largest of the pixel's contributors (first in list order on a tie)
+ * Gaussians that nobody consumed -- culled, off screen, late under the list cut, or listed behind every pixel's stop -- get a zero row.
+ * It follows that  sum_i col0 = sum_p m_p (1 - T_final[p]),  sum_i col3 = number of pixels with m_p > 0 and at least one contributor,
+ * col1 <= 0.99,  col2 >= col3,  col0 <= col1 * col2.
+ *
+ * The state already carries the opacity the forward blended with (the GSRAST_RENDER_ANTIALIAS compensation included), so the call has no
+ * flags; pass the options (exp_mode) of the forward that filled the state (NULL: the process defaults).  The three state buffers are valid
+ * for this call after the forward that filled them has been enqueued on `stream` and before a backward on them.  The call replays the
+ * blend from that state (csrc/gsrast_contrib.h); every accumulation across waves and tiles is an integer atomic, so the same state gives
+ * the same bits on every run.  weight_sum is accumulated in units of 2^-36 (each 64-pixel partial is truncated to that unit); the two counts
+ * are stored as float32: exact up to 2^24, rounded above.
+ * stats [P][4] float32 is fully overwritten (16-byte aligned).  scratch: gsrast_contrib_scratch_bytes(P) bytes of the caller's (20 bytes
+ * per Gaussian, rounded up like every scratch size here; 16-byte aligned); the call zeroes it itself and leaves it zeroed.
+ * GSRAST_E_ARG before any device work: P < 0 or R < 0, a zero-size image, and with P > 0 a NULL state buffer (binning_buffer only when R > 0),
+ * a NULL stats, a NULL scratch.  P == 0 returns 0 without a launch.  Kernels "contrib_blend" and "contrib_finish" of the profile table. */
+size_t gsrast_contrib_scratch_bytes(int P);
+int gsrast_contrib_stats(const gsrast_options* options, int P, int R, int width, int height,
+                         const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                         const float* pixel_weights /* [H][W] or NULL */, float* stats /* [P][4] */,
+                         char* scratch, void* stream);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

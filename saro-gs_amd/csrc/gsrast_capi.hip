@@ -18,6 +18,7 @@
 #include "gsrast_preprocess.h"
 #include "gsrast_binning.h"
 #include "gsrast_blend.h"
+#include "gsrast_contrib.h"
 #include "gsrast_loss.h"
 #include "gsrast_epilogue.h"
 #include "gsrast_adam.h"
@@ -140,14 +141,15 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
-                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_COUNT };
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_COUNT };
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
                                             "cut_redo" /* list cut: the predicated second binning + blend behind the forward blend, as ONE stage */,
                                             "late_rows_zero" /* list cut: the late Gaussians' zero rows, on the side stream beside the blend backward */,
                                             "grec_zero_touched" /* the consumed Gaussians' gradient records zeroed behind the forward's last blend */,
-                                            "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */ };
+                                            "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */,
+                                            "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -2181,6 +2183,62 @@ int gsrast_touched_rows(int P, const char* geom_buffer, unsigned char* flags, vo
     const GeomLayout GL = geom_layout((size_t)P);
     touched_rows_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, at<unsigned char>(geom_buffer, GL.untouched), at<uint32_t>(geom_buffer, GL.scalars), flags);
     GS_LAUNCHED("touched_rows");
+    return GSRAST_OK;
+}
+
+// ---- per-Gaussian blend-weight statistics of a finished forward (gsrast_contrib.h) ---------------------------------------------------
+namespace {
+struct ContribLayout { size_t sum, max, cnt, top, total; };
+ContribLayout contrib_layout(size_t P)
+{
+    ContribLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    const size_t Pp = P ? P : 1;
+    L.sum = take(Pp * 8); L.max = take(Pp * 4); L.cnt = take(Pp * 4); L.top = take(Pp * 4);      // 20 bytes per Gaussian
+    L.total = o;
+    return L;
+}
+} // namespace
+
+size_t gsrast_contrib_scratch_bytes(int P) { return contrib_layout(P > 0 ? (size_t)P : 0).total; }
+
+int gsrast_contrib_stats(const gsrast_options* options, int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                         const char* image_buffer, const float* pixel_weights, float* stats, char* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0 || R < 0) return fail(GSRAST_E_ARG, "contrib_stats: negative P or R");
+    if (width <= 0 || height <= 0) return fail(GSRAST_E_ARG, "contrib_stats: zero-size image");
+    if (P == 0) return GSRAST_OK;
+    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail(GSRAST_E_ARG, "contrib_stats: NULL state buffer");
+    if (!stats) return fail(GSRAST_E_ARG, "contrib_stats: NULL stats");
+    if (!scratch) return fail(GSRAST_E_ARG, "contrib_stats: NULL scratch");
+    if (((uintptr_t)stats & 15) || ((uintptr_t)scratch & 15)) return fail(GSRAST_E_ARG, "contrib_stats: stats / scratch must be 16-byte aligned");
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "contrib_stats: exp_mode must be 0, 1 or 2");
+    const GeomLayout GL = geom_layout((size_t)P);
+    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const ContribLayout CL = contrib_layout((size_t)P);
+    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
+    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    unsigned long long* const a_sum = at<unsigned long long>(scratch, CL.sum);
+    uint32_t* const a_max = at<uint32_t>(scratch, CL.max); uint32_t* const a_cnt = at<uint32_t>(scratch, CL.cnt); uint32_t* const a_top = at<uint32_t>(scratch, CL.top);
+    GS_HIP(hipMemsetAsync(scratch, 0, CL.total, s));      // (the caller owes nothing: whatever the scratch held)
+    {
+        ProfScope ps(K_CONTRIB_BLEND, s);
+        // the list in force, resolved as the blend backward resolves it: the tile's range (a tile the list cut's completion pass listed again has
+        // its range in the point list's second half) into the point list at offset 0 of the binning buffer
+        pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
+            contrib_blend_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
+                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
+                at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), pixel_weights, a_sum, a_max, a_cnt, a_top);
+        });
+        GS_LAUNCHED("contrib_blend");
+    }
+    {
+        ProfScope ps(K_CONTRIB_FINISH, s);
+        contrib_finish_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, a_sum, a_max, a_cnt, a_top, reinterpret_cast<float4*>(stats));
+        GS_LAUNCHED("contrib_finish");
+    }
     return GSRAST_OK;
 }
 

@@ -45,6 +45,7 @@ EXPORTS = (
     "gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags",
     "gsrast_backward_flags_abs", "gsrast_backward_raw_flags_abs",
     "gsrast_backward_flags_pose", "gsrast_backward_raw_flags_pose", "gsrast_pose_scratch_bytes",
+    "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
 )
 
 # include/gsrast.h: the flags word of the gsrast_*_flags entry points
@@ -189,6 +190,10 @@ def lib() -> C.CDLL:
         getattr(L, name).argtypes = [ci]
     L.gsrast_pose_scratch_bytes.restype = C.c_size_t
     L.gsrast_pose_scratch_bytes.argtypes = [ci]
+    L.gsrast_contrib_scratch_bytes.restype = C.c_size_t
+    L.gsrast_contrib_scratch_bytes.argtypes = [ci]
+    L.gsrast_contrib_stats.restype = ci
+    L.gsrast_contrib_stats.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_binning_bytes.restype = C.c_size_t
     L.gsrast_binning_bytes.argtypes = [ci, ci, ci]
     L.gsrast_image_bytes.restype = C.c_size_t
@@ -751,6 +756,65 @@ def check_absgrad(absgrad: Optional[torch.Tensor], P: int, dev: torch.device) ->
         raise ValueError("absgrad must be contiguous")
     if absgrad.requires_grad:
         raise ValueError("absgrad is a statistic the backward writes, not a differentiable tensor (requires_grad must be False)")
+
+
+def check_contrib(contrib: Optional[torch.Tensor], pixel_weights: Optional[torch.Tensor], P: int, H: int, W: int, dev: torch.device) -> None:
+    """The caller-owned sink of the blend-weight statistics (`contrib=`): a contiguous float32 [P,4] tensor on the render's device (None: not
+    wanted), and its optional per-pixel weights (`pixel_weights=`): a contiguous float32 [H,W] or [1,H,W] tensor on the same device, only legal
+    together with a sink.  ValueError otherwise -- the library gets pointers and would write P * 4 floats / read H * W floats through them."""
+    if contrib is None:
+        if pixel_weights is not None:
+            raise ValueError("pixel_weights is only legal together with contrib")
+        return
+    for name, t, shapes in (("contrib", contrib, ((P, 4),)), ("pixel_weights", pixel_weights, ((H, W), (1, H, W)))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor or None (got {type(t).__name__})")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{name} must be {' or '.join(str(list(x)) for x in shapes)} (got {list(t.shape)})")
+        if t.dtype is not torch.float32:
+            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+        if t.device != dev:
+            raise ValueError(f"{name} must live on {dev} (got {t.device})")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.requires_grad:
+            raise ValueError(f"{name} is not a differentiable tensor (requires_grad must be False)")
+    if contrib.numel() != 0 and contrib.device.type != "meta" and contrib.data_ptr() % 16 != 0:
+        raise ValueError("contrib must be 16-byte aligned (rows of a fresh or row-sliced [*, 4] float32 tensor are)")
+
+
+_contrib_cache: dict = {}
+
+
+def _contrib_scratch(P: int, dev: torch.device) -> torch.Tensor:
+    """The accumulators of gsrast_contrib_stats, kept per device, stream and P (the call zeroes them itself and leaves them zeroed)."""
+    k = (dev.index, int(_stream_of(dev) or 0), P)
+    v = _contrib_cache.get(k)
+    if v is None:
+        if len(_contrib_cache) > 16:
+            _contrib_cache.clear()
+        v = _contrib_cache[k] = torch.empty((int(lib().gsrast_contrib_scratch_bytes(P)),), dtype=torch.uint8, device=dev)
+    return v
+
+
+def contrib_stats(contrib: torch.Tensor, pixel_weights: Optional[torch.Tensor], R: int, W: int, H: int, geomBuffer: torch.Tensor,
+                  binningBuffer: torch.Tensor, imageBuffer: torch.Tensor, *, options: Optional[dict] = None) -> torch.Tensor:
+    """gsrast_contrib_stats (include/gsrast.h) on the state a forward returned: OVERWRITES `contrib` [P,4] with the per-Gaussian rows
+    [weight_sum, weight_max, pixel_count, top_count] on the current stream, behind everything the forward enqueued there.  Valid until a
+    backward runs on the state.  `options`: the per-call options of that forward (default: the calling thread's)."""
+    P = int(contrib.shape[0])
+    dev = _require_gpu(contrib)
+    check_contrib(contrib, pixel_weights, P, int(H), int(W), dev)
+    if P == 0:
+        return contrib
+    with _on_device(dev):
+        rc = lib().gsrast_contrib_stats(C.byref(_options_struct(options=options)), P, int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+                                        _ptr(imageBuffer), _ptr(pixel_weights), contrib.data_ptr(), _contrib_scratch(P, dev).data_ptr(), _stream_of(dev))
+    if rc != 0:
+        raise _err(rc, "gsrast_contrib_stats")
+    return contrib
 
 
 def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, antialiasing: bool):

@@ -40,6 +40,23 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   requires grad (gsplat's gradients on ``viewmats``).  A caller that builds ``projmatrix = viewmatrix @ projection`` and
   ``campos = inverse(viewmatrix)[3, :3]`` from a pose parameter gets that parameter's gradient through autograd.  tanfovx / tanfovy
   are not differentiated.  When none of the three requires grad the call is the plain one (include/gsrast.h: GSRAST_RENDER_POSEGRAD).
+* not in the reference: ``forward(..., contrib=sink)`` (keyword-only, default None; also ``rasterize_gaussians`` and
+  ``GaussianRasterizerRaw``, together with ``return_aux``, ``antialiasing``, ``absgrad``, ``camera_grads`` and a ``GradArena``) -- per-Gaussian
+  blend-weight statistics for importance pruning.  `sink` is a caller-owned contiguous float32 ``[P, 4]`` tensor on the render's device, and THE
+  FORWARD overwrites it, on the current stream, behind everything it enqueued there (also under ``torch.no_grad()``); nothing is attached to
+  the graph.  For one finished forward, take pixel p inside the image and Gaussian i.  i CONTRIBUTES to p when the forward blended it
+  there: its position in the tile's list in force is below n_contrib[p] and it passed the forward's per-pair tests --
+  power <= 0 && power >= threshold;  alpha = min(0.99, opacity * exp(power)) >= 1/255;  T * (1 - alpha) >= 1e-4
+  (the terminating entry does not contribute).  Its weight is w_ip = alpha_ip * T_ip, T_ip the transmittance in front of it.
+  m_p = pixel_weights[p] clamped to [0, 1]; without pixel_weights m_p = 1.  A pixel with m_p = 0 counts in no column.  One row per Gaussian:
+  col 0 ``weight_sum`` = sum over p of m_p * w_ip;  col 1 ``weight_max`` = max over pixels with m_p > 0 of w_ip (unweighted);
+  col 2 ``pixel_count`` = number of pixels with m_p > 0 that i contributes to;  col 3 ``top_count`` = number of those pixels where w_ip is
+  the largest of the pixel's contributors (first in list order on a tie).  Gaussians that nobody consumed -- culled, off screen, late
+  under the list cut, or listed behind every pixel's stop -- get a zero row.  The counts are float32: exact up to 2^24, rounded above.
+  The result is bit-identical from run to run.  ``pixel_weights=w`` (keyword-only, default None; only legal together with ``contrib``): a
+  float32 ``[H, W]`` or ``[1, H, W]`` tensor on the same device, e.g. a loss map or a mask.  A wrong shape / dtype / device / layout raises
+  ``ValueError`` at call time, before any launch.  With ``contrib=None`` nothing is launched or allocated that was not before
+  (include/gsrast.h: gsrast_contrib_stats; fused_densify.ContribStats accumulates the rows over views).
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -84,7 +101,8 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, antialiasing, absgrad, *camera):
+                raster_settings, antialiasing, absgrad, contrib, *camera):
+        # contrib: None or (the [P,4] sink of the blend-weight statistics, its pixel weights or None) -- a tuple, so autograd sees no tensor
         # camera: () or raster_settings' (viewmatrix, projmatrix, campos) once more, as differentiable inputs (_camera_inputs)
         aux = ctx._forward_cls.AUX      # (of the class .apply was called on)
         if aux:
@@ -101,6 +119,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
             rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=aux, antialiasing=antialiasing)
+        if contrib is not None:                    # filled HERE, from the state the call above left: no backward is needed, none is affected
+            _C.contrib_stats(contrib[0], contrib[1], num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
         ctx.raster_settings = rs
         ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
         ctx.absgrad = absgrad                      # the caller's [P,2] sink (not a saved tensor: every backward writes it)
@@ -140,7 +160,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None) + _camera_grads_out(ctx, rs, grad_camera, 11)
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None, None) + _camera_grads_out(ctx, rs, grad_camera, 12)
 
 
 class _RasterizeGaussiansAux(_RasterizeGaussians):
@@ -168,21 +188,24 @@ def _camera_grads_out(ctx, rs, grad_camera, first: int) -> tuple:
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_aux=False, *, antialiasing: bool = False, absgrad: Optional[torch.Tensor] = None,
-                        camera_grads: bool = False):
+                        camera_grads: bool = False, contrib: Optional[torch.Tensor] = None, pixel_weights: Optional[torch.Tensor] = None):
     """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha; `antialiasing` (not in the
     reference): the opacity-compensated 2-D filter; `absgrad` (not in the reference): the [P,2] sink of the absolute screen-space
-    gradient; `camera_grads` (not in the reference): gradients for raster_settings' viewmatrix / projmatrix / campos (module docstring)."""
+    gradient; `camera_grads` (not in the reference): gradients for raster_settings' viewmatrix / projmatrix / campos; `contrib` / `pixel_weights` (not in the reference): the
+    [P,4] sink of the per-Gaussian blend-weight statistics, which the forward overwrites, and its per-pixel weights (module docstring)."""
     fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
     if absgrad is not None:
         _C.check_absgrad(absgrad, int(means3D.shape[0]), means3D.device)
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad, *_camera_inputs(raster_settings, bool(camera_grads)))
+                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad,
+                    _contrib_arg(contrib, pixel_weights, int(means3D.shape[0]), raster_settings, means3D.device),
+                    *_camera_inputs(raster_settings, bool(camera_grads)))
 
 
 def _antialiasing_of(render_options: dict) -> bool:
     """The keyword-only `antialiasing` (default False) of GaussianRasterizer.forward / GaussianRasterizerRaw.forward.  It arrives through
     **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone."""
-    unknown = set(render_options) - {"antialiasing", "absgrad", "camera_grads"}
+    unknown = set(render_options) - {"antialiasing", "absgrad", "camera_grads", "contrib", "pixel_weights"}
     if unknown:
         raise TypeError(f"forward() got an unexpected keyword argument {sorted(unknown)[0]!r}")
     return bool(render_options.get("antialiasing", False))
@@ -196,6 +219,13 @@ def _absgrad_of(render_options: dict) -> Optional[torch.Tensor]:
 def _camera_grads_of(render_options: dict) -> bool:
     """The keyword-only `camera_grads` (default False) of the same two methods, through **render_options like `antialiasing`."""
     return bool(render_options.get("camera_grads", False))
+
+
+def _contrib_arg(contrib, pixel_weights, P: int, raster_settings, device) -> Optional[tuple]:
+    """The keyword-only `contrib` (default None) and `pixel_weights` (default None), checked (ValueError, before anything is launched) and
+    packed for the autograd node: None without a sink, else (sink, weights or None)."""
+    _C.check_contrib(contrib, pixel_weights, P, int(raster_settings.image_height), int(raster_settings.image_width), device)
+    return None if contrib is None else (contrib, pixel_weights)
 
 
 _EMPTY = torch.empty(0)
@@ -236,12 +266,12 @@ class GaussianRasterizer(nn.Module):
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
             self.raster_settings, return_aux=return_aux, antialiasing=antialiasing, absgrad=absgrad,
-            camera_grads=_camera_grads_of(render_options))
+            camera_grads=_camera_grads_of(render_options), contrib=render_options.get("contrib"), pixel_weights=render_options.get("pixel_weights"))
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
     # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so is antialiasing
-    # (default False, through **render_options: _antialiasing_of), absgrad (default None: _absgrad_of) and camera_grads (default
-    # False: _camera_grads_of).
+    # (default False, through **render_options: _antialiasing_of), absgrad (default None: _absgrad_of), camera_grads (default
+    # False: _camera_grads_of), contrib and pixel_weights (default None: _contrib_arg).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
 
@@ -254,7 +284,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     AUX = False
 
     @staticmethod
-    def forward(ctx, means2D, raster_settings, antialiasing, absgrad, *raw_tensors):
+    def forward(ctx, means2D, raster_settings, antialiasing, absgrad, contrib, *raw_tensors):
         # (behind the len(_C.RAW_NAMES) raw tensors: () or the camera's three, as _RasterizeGaussians.forward's *camera)
         raw_tensors, camera = raw_tensors[:len(_C.RAW_NAMES)], raw_tensors[len(_C.RAW_NAMES):]
         aux = ctx._forward_cls.AUX
@@ -266,6 +296,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = _C.rasterize_gaussians_raw(
             rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
             rs.sh_degree, rs.campos, forward_only=forward_only, aux=aux, antialiasing=antialiasing)
+        if contrib is not None:                    # (as _RasterizeGaussians.forward)
+            _C.contrib_stats(contrib[0], contrib[1], num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
         ctx.raster_settings, ctx.num_rendered = rs, num_rendered
         ctx.antialiasing = bool(antialiasing)
         ctx.absgrad = absgrad
@@ -297,7 +329,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.gs_backwards += 1
         shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
         grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None, None, None) + grads + _camera_grads_out(ctx, rs, (g.get("camera"),), 4 + len(_C.RAW_NAMES))
+        return (g["dL_dmeans2D"], None, None, None, None) + grads + _camera_grads_out(ctx, rs, (g.get("camera"),), 5 + len(_C.RAW_NAMES))
 
 
 class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
@@ -312,7 +344,7 @@ class GaussianRasterizerRaw(nn.Module):
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
     being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), and the keyword-only
-    `antialiasing=True` (default False), `absgrad=sink` (default None) and `camera_grads=True` (default False), as GaussianRasterizer."""
+    `antialiasing=True` (default False), `absgrad=sink` (default None), `camera_grads=True` (default False), `contrib=sink` and `pixel_weights=w` (default None), as GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -326,5 +358,6 @@ class GaussianRasterizerRaw(nn.Module):
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
         fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
-        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, *[raw[n] for n in _C.RAW_NAMES],
+        contrib = _contrib_arg(render_options.get("contrib"), render_options.get("pixel_weights"), int(xyz.shape[0]), self.raster_settings, xyz.device)
+        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, contrib, *[raw[n] for n in _C.RAW_NAMES],
                         *_camera_inputs(self.raster_settings, _camera_grads_of(render_options)))

@@ -7,6 +7,8 @@ Mirror of the reference (paths relative to its root):
   scene/saro_gaussian.py:555-640  _prune_optimizer / cat_tensors_to_optimizer / densification_postfix             -> inside both calls
   scene/saro_gaussian.py:577-593  prune_points; :347-356 the every-50-iterations integral prune                    -> prune
   train.py:282-292 + scene/saro_gaussian.py:745-750 add_densification_stats_grad                                   -> DensifyStats.update
+Not in the reference: ContribStats accumulates the rasterizer's per-Gaussian blend-weight statistics (`contrib=sink`) over views and ranks
+them into a keep mask, whose negation is a `prune_mask` for the two calls below (importance pruning: LightGaussian, RadSplat, Mini-Splatting).
 
 One classification pass, one scan and ONE row-moving launch for all groups replace the reference's chain of boolean-mask indexing
 and torch.cat over seven groups and fourteen moment tensors; the only host read-back is the five counts (for the new P).  The result
@@ -73,6 +75,65 @@ class DensifyStats:
                                                       _C._ptr(self.denom), _C._ptr(self.max_radii2D), int(is_mean), _C._stream_of(dev))
         if rc != 0:
             raise _C._err(rc, "gsrast_densify_stats_update")
+
+
+class ContribStats:
+    """The rasterizer's blend-weight statistics (`forward(..., contrib=sink)`, include/gsrast.h: gsrast_contrib_stats) accumulated over views:
+    weight_sum, pixel_count, top_count (summed over the views), weight_max (the maximum over them) and views (in how many views the
+    Gaussian had pixel_count > 0), [P] float32 each.  Plain torch ops on whatever device the sinks live on: this is not a hot path.
+    Storage: `sums` [P,4] = (weight_sum, pixel_count, top_count, views) and `weight_max` [P] -- what view_parallel.reduce_contrib_stats
+    all-reduces with SUM and MAX."""
+    SUM_COLUMNS = ("weight_sum", "pixel_count", "top_count", "views")
+    COLUMNS = SUM_COLUMNS + ("weight_max",)
+
+    def __init__(self, P: int, device):
+        self.device = torch.device(device)
+        self.reset(P)
+
+    def reset(self, P: Optional[int] = None) -> None:
+        """Zeros (at P rows; default: the current P)."""
+        P = self.P if P is None else int(P)
+        self.sums = torch.zeros((P, 4), dtype=torch.float32, device=self.device)
+        self.weight_max = torch.zeros((P,), dtype=torch.float32, device=self.device)
+
+    @property
+    def P(self) -> int:
+        return int(self.weight_max.shape[0])
+
+    weight_sum = property(lambda self: self.sums[:, 0])
+    pixel_count = property(lambda self: self.sums[:, 1])
+    top_count = property(lambda self: self.sums[:, 2])
+    views = property(lambda self: self.sums[:, 3])
+
+    @torch.no_grad()
+    def update(self, sink: torch.Tensor) -> None:
+        """One view's sink [P,4] = [weight_sum, weight_max, pixel_count, top_count] (the rasterizer's columns)."""
+        if tuple(sink.shape) != (self.P, 4) or sink.device != self.device:
+            raise RuntimeError(f"ContribStats.update: the sink must be [{self.P}, 4] on {self.device} (got {list(sink.shape)} on {sink.device})")
+        sink = sink.detach().to(torch.float32)
+        self.sums[:, 0] += sink[:, 0]
+        self.sums[:, 1] += sink[:, 2]
+        self.sums[:, 2] += sink[:, 3]
+        self.sums[:, 3] += (sink[:, 2] > 0).to(torch.float32)
+        torch.maximum(self.weight_max, sink[:, 1], out=self.weight_max)
+
+    def column(self, name: str) -> torch.Tensor:
+        if name not in self.COLUMNS:
+            raise KeyError(f"ContribStats: no column {name!r} (one of {', '.join(self.COLUMNS)})")
+        return getattr(self, name)
+
+    @torch.no_grad()
+    def keep_mask_by_rank(self, column: str, keep_fraction: float) -> torch.Tensor:
+        """bool [P]: True for the ceil(keep_fraction * P) Gaussians with the largest `column`; among equal values the lower index ranks
+        first (a stable sort), so replicated ranks agree.  Its negation is the `prune_mask` of prune() / densify_and_prune()."""
+        if not 0.0 <= float(keep_fraction) <= 1.0:
+            raise ValueError(f"keep_fraction must be in [0, 1] (got {keep_fraction})")
+        P = self.P
+        k = min(P, int(math.ceil(float(keep_fraction) * P)))
+        order = torch.sort(self.column(column), descending=True, stable=True).indices
+        mask = torch.zeros((P,), dtype=torch.bool, device=self.device)
+        mask[order[:k]] = True
+        return mask
 
 
 def _flat_f32(t: torch.Tensor, name: str, P: int, dev: torch.device) -> torch.Tensor:
@@ -226,16 +287,17 @@ def _mask_u8(mask: torch.Tensor, P: int, dev: torch.device) -> torch.Tensor:
 
 
 @torch.no_grad()
-def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras: Iterable[torch.Tensor] = ()):
+def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras: Iterable[torch.Tensor] = (), contrib: Optional[ContribStats] = None):
     """prune_points (scene/saro_gaussian.py:577-593) and the integral prune of update_learning_rate (:347-356): rows with mask != 0
-    leave every group, its moments, `stats` (gathered, NOT reset) and every tensor of `extras` ([P, ...] float32 each, e.g.
-    t_gradient_accum).  The same plan / apply pair with an infinite threshold.  Returns (counts, {group name: new parameter},
-    [new extras])."""
+    leave every group, its moments, `stats` (gathered, NOT reset), `contrib` (a ContribStats: gathered like `stats`, NOT reset -- the
+    survivors keep what the views so far saw of them) and every tensor of `extras` ([P, ...] float32 each, e.g. t_gradient_accum).
+    The same plan / apply pair with an infinite threshold.  Returns (counts, {group name: new parameter}, [new extras])."""
     rows, P = _optimizer_groups(opt, stats.P if stats is not None else None)
     dev = _C._require_gpu(rows[0][1]) if rows else _C._require_gpu(mask)
     m8 = _mask_u8(mask, P, dev)
     moved = [(p, st["exp_avg"] if st else None, st["exp_avg_sq"] if st else None, _C.DENSIFY_COPY) for _, p, st in rows]
-    carried: List[torch.Tensor] = ([stats.xyz_gradient_accum, stats.denom, stats.max_radii2D] if stats is not None else []) + list(extras)
+    carried: List[torch.Tensor] = (([stats.xyz_gradient_accum, stats.denom, stats.max_radii2D] if stats is not None else [])
+                                   + ([contrib.sums, contrib.weight_max] if contrib is not None else []) + list(extras))
     for k, t in enumerate(carried):
         _check_param(t, f"carried tensor {k}", P)
         moved.append((t, None, None, _C.DENSIFY_COPY))
@@ -245,4 +307,7 @@ def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras:
     if stats is not None:
         stats.xyz_gradient_accum, stats.denom, stats.max_radii2D = rest[:3]
         rest = rest[3:]
+    if contrib is not None:
+        contrib.sums, contrib.weight_max = rest[:2]
+        rest = rest[2:]
     return counts, new, rest

@@ -395,6 +395,15 @@ def reduce_densification_stats(point_grad_norm: torch.Tensor, visible_count: tor
         dist.all_reduce(max_radii, op=dist.ReduceOp.MAX)
 
 
+def reduce_contrib_stats(stats, group=None) -> None:
+    """In-place cross-rank reduction of a fused_densify.ContribStats whose views were split over the ranks: one SUM all-reduce of the
+    summed columns (`stats.sums` [P,4]: weight_sum, pixel_count, top_count, views) and one MAX all-reduce of `stats.weight_max`.
+    Afterwards every rank holds the statistics of all views, so keep_mask_by_rank gives every rank the same mask."""
+    if collectives_active():
+        dist.all_reduce(stats.sums, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(stats.weight_max, op=dist.ReduceOp.MAX, group=group)
+
+
 def max_over_ranks(x: float, device: torch.device) -> float:
     if collectives_active():
         t = torch.tensor([x], dtype=torch.float64, device=device)
