@@ -38,8 +38,9 @@
 extern "C" {
 #endif
 
-#define GSRAST_ABI_VERSION 5   /* 5: gsrast_grad_rows_clear / gsrast_grad_rows_add take P (indices received from peers are bounds-checked).  4: gsrast_raw_grads.d_sh_factor (the struct grew), gsrast_sh_grad_combine_rows.  3: gsrast_options.no_list_cut (the struct grew).  2: gsrast_backward OVERWRITES every output array (version 1 accumulated into caller-zeroed arrays like the
-                                    reference); options.forward_only; gsrast_forward_raw / gsrast_backward_raw */
+#define GSRAST_ABI_VERSION 6   /* 6: the render calls beside gsrast_forward / gsrast_backward are gsrast_render_forward / gsrast_render_backward over one versioned call record each
+                                    (fourteen positional render symbols removed).  5: gsrast_grad_rows_clear / gsrast_grad_rows_add take P (indices received from peers are bounds-checked).  4: gsrast_raw_grads.d_sh_factor (the struct grew), gsrast_sh_grad_combine_rows.  3: gsrast_options.no_list_cut (the struct grew).  2: gsrast_backward OVERWRITES every output array (version 1 accumulated into caller-zeroed arrays like the
+                                    reference); options.forward_only; the raw family (gsrast_raw_inputs / gsrast_raw_grads) */
 #define GSRAST_TILE_X 16 /* reference config.h:16 */
 #define GSRAST_TILE_Y 16 /* reference config.h:17 */
 
@@ -213,11 +214,11 @@ int gsrast_debug_export(int P, int R, int width, int height,
  * The reference's Rasterizer::{forward, backward} are stateless statics (rasterizer.h:24-83): any number of host threads
  * may call them on different streams / devices.  The same holds here:
  *   - everything that changes what a call computes or how it is scheduled is a field of gsrast_options, passed per call to
- *     gsrast_forward_ex / gsrast_backward_ex (NULL = a snapshot of the process defaults, taken once at entry);
+ *     gsrast_render_forward / gsrast_render_backward (NULL = a snapshot of the process defaults, taken once at entry);
  *   - the only state that outlives a forward call -- the capacity hints of the speculative launch and the counts of the last
  *     call -- lives in a gsrast_context the caller owns (NULL = a context private to the calling host thread);
  *   - gsrast_last_error() is per host thread.
- * gsrast_forward / gsrast_backward are exactly gsrast_forward_ex(NULL, NULL, ...) / gsrast_backward_ex(NULL, ...).
+ * gsrast_forward / gsrast_backward are exactly gsrast_render_forward(NULL, NULL, ...) / gsrast_render_backward(NULL, ...) on a dense record with flags = 0.
  * gsrast_set_option only edits the process DEFAULTS (plus the process-wide diagnostics "profile", "debug_sync"): callers that
  * want different behaviour on different threads pass a gsrast_options instead. */
 typedef struct gsrast_options {
@@ -311,75 +312,35 @@ int gsrast_policy_event(gsrast_context* ctx, const char* what, int a, int b, int
  * eligible, 15 adaptive radix sort, 16 three passes assumed, 17 the cut pays, 18 the list cut is applied.  ctx NULL = the calling thread's context. */
 int gsrast_debug_forward_plan(gsrast_context* ctx, const gsrast_options* options, unsigned flags, int P, int W, int H, const int* words);
 /* The backward's host-side plan (csrc/gsrast_policy.h: BackwardPlan) WITHOUT a device: what a backward with these options and flags would decide for
- * words[7] = { P, D, R, width, height, (1: a gsrast_backward_raw* call) | (2: SH coefficients) | (4: colors_precomp) | (8: cov3D_precomp) | (16: dL_dacc_depth or
+ * words[7] = { P, D, R, width, height, (1: a GSRAST_FAMILY_RAW record) | (2: SH coefficients) | (4: colors_precomp) | (8: cov3D_precomp) | (16: dL_dacc_depth or
  * dL_dalpha given), 1: the context's side stream can be had }, under the process-wide switches in force (gsrast_set_option).  Returns GSRAST_E_ARG (the
  * backward's own refusal in gsrast_last_error) or the decisions as bits: 0 aux gradients, 1 anti-aliased state, 2 blend phase, 3 per-Gaussian phase, 4 gradient
  * records zero-filled, 5 sh_dir_derivs runs, 6 ... on the side stream, 7 late fill wanted, 8 late fill (late_rows_zero on the side stream), 9 its kernel skipped
  * ("ablate" 3), 10 side stream joined BEHIND preprocess_bwd, 11 the blend backward runs, 12 culled, 13 transposed, 14 its aux instantiation, 15 launch order from
  * the work buckets, 16 from tile_order, 17 sh_factor runs, 18 preprocess_bwd leaves dL_dsh to it, 19 sparse preprocess_bwd, 20 grouped; bits 21-23 pixels per
  * lane (1 / 2 / 4), 24-25 the "ablate" blend kernel (0 / 1 / 2), 26-27 "mutate", 28 pose sums (GSRAST_RENDER_POSEGRAD).  words[5] also takes 32: a
- * gsrast_backward*_flags_pose call, 64: its dL_dcamera given, 128: its pose_scratch given, 256: its dL_dmean2D_abs given -- without 32 the plan stands for a
- * symbol that has none of them.  grids (may be NULL) receives { sh_dir_derivs' grid, preprocess_bwd's grid } (0: not launched). */
+ * record whose struct_size covers the pose fields (all four flag bits known), 64: its dL_dcamera given, 128: its pose_scratch given, 256: its dL_dmean2D_abs
+ * given -- without 32 the plan stands for a GSRAST_BACKWARD_CALL_MIN record, which knows only GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS.  grids (may be NULL) receives { sh_dir_derivs' grid, preprocess_bwd's grid } (0: not launched). */
 int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, const int* words, int* grids);
-int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
-                      gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                      gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                      gsrast_alloc_fn image_alloc, void* image_ctx,
-                      int P, int D, int M, const float* background, int width, int height,
-                      const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                      const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                      const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                      float tan_fovx, float tan_fovy, int prefiltered,
-                      float* out_color, float* out_depth, int* radii, void* stream);
-int gsrast_backward_ex(const gsrast_options* options,
-                       int P, int D, int M, int R, const float* background, int width, int height,
-                       const float* means3D, const float* shs, const float* colors_precomp,
-                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos,
-                       float tan_fovx, float tan_fovy, const int* radii,
-                       char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream);
 
 /* ---- Differentiable alpha and accumulated depth (no counterpart in the reference, whose only depth output is the median depth
  * above, whose gradient it drops) ----
- * gsrast_forward_aux = gsrast_forward_ex that also writes, for every pixel, over the same contributors and the same early stop as the
- * colour:
+ * With GSRAST_RENDER_AUX (the flags and the call records below) the forward also writes, for every pixel, over the same contributors and the
+ * same early stop as the colour:
  *     out_acc_depth [1][H][W] = sum_i alpha_i T_i z_i     z_i = Gaussian i's view-space depth; the background adds nothing; NOT normalised
  *                                                        (expected depth = acc_depth / alpha, left to the caller)
  *     out_alpha     [1][H][W] = 1 - T_final
- * Both must be non-NULL.  Everything else it computes and leaves in the state buffers is what gsrast_forward_ex computes.
- * gsrast_backward_aux = gsrast_backward_ex plus the upstream gradients dL_dacc_depth / dL_dalpha [1][H][W]; either may be NULL (= zero),
- * with both NULL it is gsrast_backward_ex (the options->cull rule below is checked first).  The gradients reach the same outputs as the colour's (means3D through the view-space
+ * Both must be non-NULL.  Everything else it computes and leaves in the state buffers is what the forward without the bit computes.
+ * The backward with the bit takes the upstream gradients dL_dacc_depth / dL_dalpha [1][H][W]; either may be NULL (= zero),
+ * with both NULL it is the backward without the bit (the options->cull rule below is checked first).  The gradients reach the same outputs as the colour's (means3D through the view-space
  * depth as well, means2D, opacities, scales / rotations or cov3D; the raw leaves on the raw pair) with the colour's conventions (the 0.99
  * clamp passes gradients through).  The backward rebuilds the depth recurrence from final_T and n_contrib back to front, as the colour's:
- * it needs nothing of the forward's aux outputs, so an aux backward on the state of a plain gsrast_forward_ex is valid.  With
+ * it needs nothing of the forward's aux outputs, so an aux backward on the state of a forward without the bit is valid.  With
  * options->backward_phase, pass the same two pointers to both phases.
- * gsrast_forward_raw_aux / gsrast_backward_raw_aux: the same for the raw pair below.
+ * The same holds for the raw family below.
  * Only the default culled blend kernels have the aux outputs: options->cull == 0 (and, forward, fwd_pixels_per_lane != 0) return
  * GSRAST_E_ARG.  The aux backward always runs the one-pixel-per-lane transposed blend backward, whatever bwd_pixels_per_lane says (the
  * automatic choice would take two pixels per lane from 8 192 tiles, 4K images, on).  Argument errors return before any device work. */
-int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
-                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                       gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                       gsrast_alloc_fn image_alloc, void* image_ctx,
-                       int P, int D, int M, const float* background, int width, int height,
-                       const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                       float tan_fovx, float tan_fovy, int prefiltered,
-                       float* out_color, float* out_depth, int* radii, void* stream,
-                       float* out_acc_depth, float* out_alpha);
-int gsrast_backward_aux(const gsrast_options* options,
-                        int P, int D, int M, int R, const float* background, int width, int height,
-                        const float* means3D, const float* shs, const float* colors_precomp,
-                        const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                        const float* viewmatrix, const float* projmatrix, const float* campos,
-                        float tan_fovx, float tan_fovy, const int* radii,
-                        char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                        const float* dL_dacc_depth, const float* dL_dalpha);
 
 /* Process defaults of the options above (and process-wide diagnostics): "exp_mode" 0 = fixed-sequence exp (bit-reproducible vs the CPU oracle), 1 = libm-grade
  * expf, 2 = hardware v_exp_f32;  "profile" = bit mask of kernel ids (gsrast_profile_kernel_name) whose launches are bracketed
@@ -450,13 +411,13 @@ int gsrast_activate_backward(int P, const float* rotation, const float* rot_res,
                              void* stream);
 
 /* ---- rank 3 as SURVEY.md 8f wrote it: the epilogue FUSED INTO the per-Gaussian kernels (K1 / K7) ----
- * gsrast_forward_raw / gsrast_backward_raw are gsrast_forward_ex / gsrast_backward_ex taking the model's RAW leaves
+ * A GSRAST_FAMILY_RAW call record (below) is a render call taking the model's RAW leaves
  * (scene/saro_gaussian.py:306-319: _xyz, _rotation, _scaling, _opacity, _features_dc, _features_rest) and the optional deformation
  * residuals of get_deformation (:807-847) instead of activated attributes: the activations above run in registers inside
  * preprocess_fwd / preprocess_color, the chain rule inside preprocess_bwd, and the [P][M][3] coefficient tensor
  * (cat(dc, rest) + residual: 192 B / Gaussian written by the model and re-read by the rasterizer, and back) is never materialised.
- * The rasterizer's outputs and state are bit-identical to gsrast_activate_forward followed by gsrast_forward_ex.
- * The reference-shaped entry points are untouched; this pair is additional.  M in {4, 16}; rotation, features_dc, features_rest,
+ * The rasterizer's outputs and state are bit-identical to gsrast_activate_forward followed by the dense forward.
+ * The reference-shaped entry points are untouched; this family is additional.  M in {4, 16}; rotation, features_dc, features_rest,
  * shs_res and the matching gradient arrays 16-byte aligned.  NULL = absent optional residual. */
 typedef struct gsrast_raw_inputs {
     const float* xyz;             /* [P][3]  _xyz */
@@ -486,41 +447,10 @@ typedef struct gsrast_raw_grads {   /* every array is fully overwritten */
                                      completes them with gsrast_sh_grad_combine_rows after the exchange); not together with shs_res / d_shs_res, whose
                                      gradient every rank needs whole for its own view */
 } gsrast_raw_grads;
-int gsrast_forward_raw(gsrast_context* ctx, const gsrast_options* options,
-                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                       gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                       gsrast_alloc_fn image_alloc, void* image_ctx,
-                       int P, int D, int M, const float* background, int width, int height,
-                       const gsrast_raw_inputs* inputs, float scale_modifier,
-                       const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                       float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream);
-int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                        const gsrast_raw_inputs* inputs, float scale_modifier,
-                        const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                        const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                        const float* dL_dpix, const gsrast_raw_grads* grads, void* stream);
-/* the raw pair with the aux outputs / gradients (gsrast_forward_aux / gsrast_backward_aux above) */
-int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
-                           gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                           gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                           gsrast_alloc_fn image_alloc, void* image_ctx,
-                           int P, int D, int M, const float* background, int width, int height,
-                           const gsrast_raw_inputs* inputs, float scale_modifier,
-                           const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                           float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
-                           float* out_acc_depth, float* out_alpha);
-int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                            const gsrast_raw_inputs* inputs, float scale_modifier,
-                            const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                            const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                            const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
-                            const float* dL_dacc_depth, const float* dL_dalpha);
 
-/* ---- Render flags: one family of entry points for every combination of the optional render features ----
- * gsrast_forward_flags / gsrast_backward_flags take gsrast_forward_ex's / gsrast_backward_ex's arguments, a flags word behind the options,
- * and the aux arrays of gsrast_forward_aux / gsrast_backward_aux at the end; the _raw_flags pair is the same for the raw pair.
- *   flags = 0                        exactly gsrast_forward_ex / gsrast_backward_ex (the aux pointers are ignored)
- *   GSRAST_RENDER_AUX                exactly gsrast_forward_aux / gsrast_backward_aux (the same rules: outputs non-NULL, gradients either NULL)
+/* ---- Render flags: the `flags` word of a call record (below) selects every combination of the optional render features ----
+ *   flags = 0                        the plain render (the aux pointers are ignored)
+ *   GSRAST_RENDER_AUX                the aux outputs / gradients above (outputs non-NULL, gradients either NULL)
  *   GSRAST_RENDER_ANTIALIAS          the 2-D Mip filter of Mip-Splatting (Yu et al., CVPR 2024), upstream 3DGS's `antialiasing`: every
  *                                    Gaussian's 2-D covariance keeps the 0.3 px^2 dilation, and its opacity is scaled by
  *                                        comp = sqrt(max(0.000025, rho)),   rho = det(cov2D) / det(cov2D + 0.3 I)     (cov2D before the dilation)
@@ -531,45 +461,9 @@ int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, 
  * The backward must get the same GSRAST_RENDER_ANTIALIAS bit as the forward that filled the state (the state does not record it).  With
  * options->backward_phase, pass the same flags to both phases.
  * GSRAST_E_ARG before any device work: unknown bits; GSRAST_RENDER_AUX with options->cull == 0; forward, GSRAST_RENDER_AUX with a NULL aux output.
- * Every gsrast_forward* / gsrast_backward* symbol of this header is an adapter over these: one set of checks, one error text per condition. */
+ * One set of checks, one error text per condition, whichever entry point the call came through. */
 #define GSRAST_RENDER_AUX        0x1u
 #define GSRAST_RENDER_ANTIALIAS  0x2u
-int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                         gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                         gsrast_alloc_fn image_alloc, void* image_ctx,
-                         int P, int D, int M, const float* background, int width, int height,
-                         const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                         const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                         const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                         float tan_fovx, float tan_fovy, int prefiltered,
-                         float* out_color, float* out_depth, int* radii, void* stream,
-                         float* out_acc_depth, float* out_alpha);
-int gsrast_backward_flags(const gsrast_options* options, unsigned flags,
-                          int P, int D, int M, int R, const float* background, int width, int height,
-                          const float* means3D, const float* shs, const float* colors_precomp,
-                          const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                          const float* viewmatrix, const float* projmatrix, const float* campos,
-                          float tan_fovx, float tan_fovy, const int* radii,
-                          char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                          float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                          const float* dL_dacc_depth, const float* dL_dalpha);
-int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx,
-                             gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                             gsrast_alloc_fn image_alloc, void* image_ctx,
-                             int P, int D, int M, const float* background, int width, int height,
-                             const gsrast_raw_inputs* inputs, float scale_modifier,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
-                             float* out_acc_depth, float* out_alpha);
-int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                              const gsrast_raw_inputs* inputs, float scale_modifier,
-                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                              const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
-                              const float* dL_dacc_depth, const float* dL_dalpha);
 
 /* ---- Absolute screen-space gradient: the densification statistic of AbsGS (Ye et al., 2024), gsplat's `absgrad` ----
  * dL_dmean2D[i] is the SIGNED sum over pixels of each pixel's gradient with respect to Gaussian i's projected centre: a large Gaussian
@@ -580,30 +474,14 @@ int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int
  * dL_dmean2D_abs[i][k] >= |dL_dmean2D[i][k]|, with equality when every pixel pulls the same way.  [P][2] floats, fully overwritten like every
  * other output: zero for every Gaussian whose dL_dmean2D row is zero because no pixel consumed it.  Densification thresholds for it are the
  * caller's choice and are higher than for the signed gradient (AbsGS: about 2x).
- * gsrast_backward_flags_abs / gsrast_backward_raw_flags_abs are gsrast_backward_flags / gsrast_backward_raw_flags with the sink as one more
- * trailing argument; without the bit (and with a NULL sink) they ARE those calls.  The bit belongs to these two symbols: every other
- * backward symbol, and every forward, refuses it as an unknown bit (mask it off the flags word given to the forward).  With
+ * The sink is the field dL_dmean2D_abs of gsrast_backward_call; without the bit (and with a NULL sink) the call is the one without the
+ * field.  The bit belongs to backward records whose struct_size covers that field: a shorter record, and every forward, refuses it as an
+ * unknown bit (mask it off the flags word given to the forward).  With
  * options->backward_phase, pass the bit and the sink to both phases.  No other output changes with it.
- * GSRAST_E_ARG before any device work, one text each: the bit with a NULL sink; a sink without the bit; the bit on a symbol without a sink
- * (unknown bit); the bit where the transposed blend backward would not run (options->cull == 0, the ablation kernels) -- the rule of
+ * GSRAST_E_ARG before any device work, one text each: the bit with a NULL sink; a sink without the bit; the bit on a record too short for
+ * the sink (unknown bit); the bit where the transposed blend backward would not run (options->cull == 0, the ablation kernels) -- the rule of
  * GSRAST_RENDER_AUX.  Like GSRAST_RENDER_AUX it selects the transposed blend backward whatever the pixels per lane say. */
 #define GSRAST_RENDER_ABSGRAD    0x4u
-int gsrast_backward_flags_abs(const gsrast_options* options, unsigned flags,
-                              int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp,
-                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                              const float* viewmatrix, const float* projmatrix, const float* campos,
-                              float tan_fovx, float tan_fovy, const int* radii,
-                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                              const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs);
-int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                                  const gsrast_raw_inputs* inputs, float scale_modifier,
-                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                                  const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                                  const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
-                                  const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs);
 
 /* ---- Camera-pose gradients: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos (gsplat's gradients on `viewmats`; the pose-optimising 3DGS forks) ----
  * viewmatrix [4][4], projmatrix [4][4] and campos [3] are three INDEPENDENT inputs, as they are passed: a caller that composes them
@@ -620,31 +498,104 @@ int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags,
  * Every workgroup of the per-Gaussian backward reduces its Gaussians' terms and writes one row of partial sums to pose_scratch
  * (gsrast_pose_scratch_bytes(P) bytes, 16-byte aligned, the caller's; no state buffer grows); a one-workgroup kernel adds the rows in a fixed order
  * in fp64.  No atomics: the same gradient records give the same bits.  No other output changes with the bit.
- * gsrast_backward_flags_pose / gsrast_backward_raw_flags_pose are the _flags_abs symbols with two more trailing arguments; without the bit (and
- * with both NULL) they ARE those calls.  The bit belongs to these two symbols: every other backward symbol, and every forward, refuses it as an
+ * dL_dcamera and pose_scratch are the last two fields of gsrast_backward_call; without the bit (and with both NULL) the call is the one
+ * without them.  The bit belongs to backward records whose struct_size covers them: a shorter record, and every forward, refuses it as an
  * unknown bit.  With options->backward_phase, pass the bit and both pointers to both phases: dL_dcamera is written by phase 2 (or by phase 0).
- * GSRAST_E_ARG before any device work, one text each: the bit on a symbol without the arguments ("flags: unknown bits"); the bit with a NULL dL_dcamera;
+ * GSRAST_E_ARG before any device work, one text each: the bit on a record too short for the fields ("flags: unknown bits"); the bit with a NULL dL_dcamera;
  * the bit with a NULL pose_scratch; dL_dcamera or pose_scratch without the bit. */
 #define GSRAST_RENDER_POSEGRAD   0x8u
 size_t gsrast_pose_scratch_bytes(int P);
-int gsrast_backward_flags_pose(const gsrast_options* options, unsigned flags,
-                               int P, int D, int M, int R, const float* background, int width, int height,
-                               const float* means3D, const float* shs, const float* colors_precomp,
-                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                               const float* viewmatrix, const float* projmatrix, const float* campos,
-                               float tan_fovx, float tan_fovy, const int* radii,
-                               char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                               float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                               const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs,
-                               float* dL_dcamera /*[35]*/, char* pose_scratch);
-int gsrast_backward_raw_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                                   const gsrast_raw_inputs* inputs, float scale_modifier,
-                                   const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                                   const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                                   const float* dL_dpix, const gsrast_raw_grads* grads, void* stream,
-                                   const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs,
-                                   float* dL_dcamera /*[35]*/, char* pose_scratch);
+
+/* ---- The render calls: one versioned call record per direction ----
+ * Every render feature is a FIELD of these records and a bit of `flags`, not a symbol.  gsrast_render_forward / gsrast_render_backward take
+ * the per-call options and context (Reentrancy, above) and one record; gsrast_forward / gsrast_backward at the top are the same calls on a
+ * dense record with flags = 0, NULL options and NULL context.  The fields have the meaning of the equally named arguments of that pair.
+ *   family  GSRAST_FAMILY_DENSE: the dense arrays (and the dense gradient outputs); `raw` / `raw_grads` must be NULL.
+ *           GSRAST_FAMILY_RAW:   `raw` (and `raw_grads`); the dense arrays and dense gradient outputs must be NULL, prefiltered 0.
+ * How the records grow.  The caller sets struct_size = sizeof(the record) of the header it was compiled against.  A record is accepted when
+ * GSRAST_*_CALL_MIN <= struct_size <= sizeof of the library's own; the library copies struct_size bytes into a zeroed record of its own, so
+ * fields the caller's header did not have are NULL.  A flag bit whose fields lie beyond struct_size is an UNKNOWN bit, refused like any
+ * other ("flags: unknown bits").  A later feature appends its fields behind the earlier ones; nothing in front ever moves.
+ * GSRAST_E_ARG before any device work: a NULL `call`, a struct_size outside that range, an unknown family, a pointer of the other family. */
+#define GSRAST_FAMILY_DENSE 0
+#define GSRAST_FAMILY_RAW   1
+typedef struct gsrast_forward_call {
+    size_t struct_size;      /* sizeof(gsrast_forward_call) of the header the caller was compiled against */
+    unsigned flags;          /* GSRAST_RENDER_* */
+    int family;              /* GSRAST_FAMILY_* */
+    gsrast_alloc_fn geometry_alloc; void* geometry_ctx;
+    gsrast_alloc_fn binning_alloc; void* binning_ctx;
+    gsrast_alloc_fn image_alloc; void* image_ctx;
+    int P, D, M;
+    const float* background;
+    int width, height;
+    const float* means3D;
+    const float* shs;
+    const float* colors_precomp;
+    const float* opacities;
+    const float* scales;
+    const float* rotations;
+    const float* cov3D_precomp;
+    const gsrast_raw_inputs* raw;
+    float scale_modifier;
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* cam_pos;
+    float tan_fovx, tan_fovy;
+    int prefiltered;
+    float* out_color;
+    float* out_depth;
+    int* radii;
+    void* stream;
+    float* out_acc_depth;    /* GSRAST_RENDER_AUX */
+    float* out_alpha;
+} gsrast_forward_call;
+typedef struct gsrast_backward_call {
+    size_t struct_size;      /* sizeof(gsrast_backward_call) of the header the caller was compiled against */
+    unsigned flags;          /* GSRAST_RENDER_* */
+    int family;              /* GSRAST_FAMILY_* */
+    int P, D, M, R;
+    const float* background;
+    int width, height;
+    const float* means3D;
+    const float* shs;
+    const float* colors_precomp;
+    const float* scales;
+    const float* rotations;
+    const float* cov3D_precomp;
+    const gsrast_raw_inputs* raw;
+    float scale_modifier;
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* campos;
+    float tan_fovx, tan_fovy;
+    const int* radii;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    const float* dL_dpix;
+    float* dL_dmean2D;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;
+    float* dL_dsh;
+    float* dL_dscale;
+    float* dL_drot;
+    const gsrast_raw_grads* raw_grads;
+    void* stream;
+    const float* dL_dacc_depth;   /* GSRAST_RENDER_AUX */
+    const float* dL_dalpha;       /* GSRAST_BACKWARD_CALL_MIN ends here */
+    float* dL_dmean2D_abs;        /* GSRAST_RENDER_ABSGRAD; GSRAST_BACKWARD_CALL_ABS ends here */
+    float* dL_dcamera;            /* GSRAST_RENDER_POSEGRAD: [35] */
+    char* pose_scratch;
+} gsrast_backward_call;
+#define GSRAST_FORWARD_CALL_MIN  sizeof(gsrast_forward_call)
+#define GSRAST_BACKWARD_CALL_MIN offsetof(gsrast_backward_call, dL_dmean2D_abs)
+#define GSRAST_BACKWARD_CALL_ABS offsetof(gsrast_backward_call, dL_dcamera)
+int gsrast_render_forward(gsrast_context* ctx, const gsrast_options* options, const gsrast_forward_call* call);
+int gsrast_render_backward(const gsrast_options* options, const gsrast_backward_call* call);
 
 /* Per-Gaussian blend-weight statistics of one finished forward (no counterpart in the reference): what importance-pruning schemes build
  * their masks from -- LightGaussian's hit count and sum of alpha T, RadSplat's max alpha T, Mini-Splatting's dominant-pixel counts.

@@ -845,8 +845,8 @@ int gsrast_debug_backward_plan(const gsrast_options* options, unsigned flags, co
     if (!options || !words) return fail(GSRAST_E_ARG, "debug_backward_plan: NULL argument");
     const int in = words[5];
     BackwardInputs bi{ flags, words[0], words[1], words[2], words[3], words[4], (in & 1) != 0, (in & 2) != 0, (in & 4) != 0, (in & 8) != 0, (in & 16) != 0 };
-    bi.pose_symbol = (in & 32) != 0; bi.pose_out = (in & 64) != 0; bi.pose_scratch = (in & 128) != 0;
-    bi.abs_symbol = bi.pose_symbol; bi.abs_sink = (in & 256) != 0;      // (a _pose symbol has the _abs symbol's sink argument too)
+    bi.known_flags = backward_known_flags((in & 32) ? sizeof(gsrast_backward_call) : GSRAST_BACKWARD_CALL_MIN);
+    bi.pose_out = (in & 64) != 0; bi.pose_scratch = (in & 128) != 0; bi.abs_sink = (in & 256) != 0;
     BackwardPlan p = plan_backward(*options, bi, snapshot_switches());
     if (p.refusal) return fail(GSRAST_E_ARG, p.refusal);
     p.side_answer(p.wants_side() && words[6] != 0);
@@ -953,19 +953,7 @@ static const char* raw_inputs_check(int P, int M, const gsrast_raw_inputs* in)
     return nullptr;
 }
 
-// Everything a forward is called with: every exported gsrast_forward* fills one of these from its positional arguments.
-// raw_family: the call came through a gsrast_forward_raw* symbol -- `raw` replaces the dense inputs (which stay null), prefiltered is 0.
 extern "C++" { namespace {      // (C++ linkage: a member template lives here)
-struct FwdCall {
-    gsrast_alloc_fn geometry_alloc; void* geometry_ctx; gsrast_alloc_fn binning_alloc; void* binning_ctx; gsrast_alloc_fn image_alloc; void* image_ctx;
-    int P, D, M; const float* background; int width, height;
-    const float *means3D, *shs, *colors_precomp, *opacities, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
-    const float *viewmatrix, *projmatrix, *cam_pos; float tan_fovx, tan_fovy; int prefiltered;
-    float *out_color, *out_depth; int* radii; void* stream;
-    bool raw_family; const gsrast_raw_inputs* raw;
-    unsigned flags; float *out_acc_depth, *out_alpha;      // GSRAST_RENDER_*; the aux outputs are looked at only with GSRAST_RENDER_AUX
-};
-
 // ---- the two binning kernels with long argument lists: one record each, filled by name, the positional list written once ----
 struct BucketSortArgs {      // depth_bucket_sort_kernel
     const uint4* slab; const uint32_t* gcount; uint32_t nb; const uint32_t* bkey; uint32_t *border, *bwincl; uint4* binfo; uint32_t* bwsum;
@@ -997,8 +985,9 @@ bool trace_on() { static const bool on = getenv("GSRAST_TRACE") != nullptr; retu
 
 // One forward call's state and its stages (forward_impl below is the order they run in).  Every stage that launches is told its stream
 // -- `stream` is the caller's and is never re-aimed -- and, where it has one, its predicate word.
+// c: the call's record (include/gsrast.h: gsrast_forward_call).  Raw family: `raw` replaces the dense inputs (which are null), prefiltered is 0.
 struct ForwardRun {
-    gsrast_context* const ctx; const FwdCall& c; const gsrast_options o; const std::chrono::steady_clock::time_point t_entry; const hipStream_t stream;
+    gsrast_context* const ctx; const gsrast_forward_call& c; const gsrast_options o; const std::chrono::steady_clock::time_point t_entry; const hipStream_t stream;
     ForwardPlan plan;
     const float *means3D, *shs, *opacities, *scales, *rotations;      // as the kernels see them (raw family: the model's leaves)
     const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{};
@@ -1033,7 +1022,7 @@ struct ForwardRun {
     uint32_t counts[12] = { 0 }; uint32_t nQ1 = 0;
     std::chrono::steady_clock::time_point t0, t1;
 
-    ForwardRun(gsrast_context* ctx_, const gsrast_options* options, const FwdCall& c_, std::chrono::steady_clock::time_point t)
+    ForwardRun(gsrast_context* ctx_, const gsrast_options* options, const gsrast_forward_call& c_, std::chrono::steady_clock::time_point t)
         : ctx(ctx_ ? ctx_ : thread_context()), c(c_), o(options ? *options : snapshot_defaults()), t_entry(t), stream((hipStream_t)c_.stream),
           means3D(c_.means3D), shs(c_.shs), opacities(c_.opacities), scales(c_.scales), rotations(c_.rotations) {}
 
@@ -1041,12 +1030,13 @@ struct ForwardRun {
     int check_and_plan(hipStream_t s)
     {
         P = c.P; W = c.width; H = c.height;
-        plan = plan_forward(o, PlanInputs{ c.flags, P, W, H, c.D, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr), c.colors_precomp != nullptr,
+        const bool raw_family = c.family == GSRAST_FAMILY_RAW;
+        plan = plan_forward(o, PlanInputs{ c.flags, P, W, H, c.D, (raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr), c.colors_precomp != nullptr,
                                            ctx->bucket_skip.load(), ctx->R_hint.load(), ctx->last_Q.load(), ctx->depth_short.load() != 0 }, snapshot_switches());
         if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
         if (plan.aux) { out_acc_depth = c.out_acc_depth; out_alpha = c.out_alpha; }
         if (plan.aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward: NULL acc_depth / alpha output");
-        if (c.raw_family) {
+        if (raw_family) {
             rawin = c.raw;
             if (const char* e = raw_inputs_check(P, c.M, rawin)) return fail(GSRAST_E_ARG, e);
             means3D = rawin->xyz; shs = rawin->features_dc /* "there are SH coefficients" */; opacities = rawin->opacity_logit; scales = rawin->scaling; rotations = rawin->rotation;
@@ -1316,7 +1306,7 @@ struct ForwardRun {
             const int cgrid = (P + PCC_IDS - 1) / PCC_IDS;
             if (rawin) preprocess_color_compact_kernel<true><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, nullptr, nullptr, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
             else preprocess_color_compact_kernel<false><<<cgrid, 64 * PCC_WAVES, 0, cs>>>(P, D, M, means3D, sh_in, colors_precomp, raw, cam_pos, rec2, cl, sA, sB, sC, skip, pred);
-        } else if (rawin) {        // (gsrast_forward_raw has checked M and the alignment of the three SH arrays)
+        } else if (rawin) {        // (raw_inputs_check has checked M and the alignment of the three SH arrays)
             if (M * 3 == PP_SH_MAX) preprocess_color_kernel<PP_SH_MAX, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
             else preprocess_color_kernel<0, true><<<grid, PP_THREADS, 0, cs>>>(P, D, M, means3D, nullptr, raw, cam_pos, rec2, cl, gz, sA, sB, sC, pred);
         } else if (staged && M * 3 == PP_SH_MAX)
@@ -1668,10 +1658,10 @@ struct ForwardRun {
 // The one forward.  Dense: the inputs are the activated arrays.  Raw family: means3D / opacities / scales / rotations are the model's raw
 // leaves, shs a non-null placeholder, and the per-Gaussian kernels run as their RAW instantiations.
 // checks -> plan -> preprocess -> sort -> speculative binning + blend -> read-back -> (sort redo) -> accept, completion pass, or exact redo
-static int forward_impl(gsrast_context* ctx, const gsrast_options* options, const FwdCall& c)
+static int forward_impl(gsrast_context* ctx, const gsrast_options* options, const gsrast_forward_call& c)
 {
     const auto t_entry = std::chrono::steady_clock::now();
-    RoctxRange range_fwd(c.raw_family ? "gsrast_forward_raw" : "gsrast_forward");
+    RoctxRange range_fwd(c.family == GSRAST_FAMILY_RAW ? "gsrast_forward" "_raw" : "gsrast_forward");      // (the range names are the ones profiles have always been read by)
     ForwardRun r(ctx, options, c, t_entry);
     const hipStream_t s = r.stream;
     int rc = r.check_and_plan(s);
@@ -1691,46 +1681,30 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     return r.finish(s, R);
 }
 
-// ---- the exported forwards: adapters that fill a FwdCall (include/gsrast.h: gsrast_forward = _ex(NULL, NULL) = _flags(0), _aux = _flags(AUX)) ----
-int gsrast_forward_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                         gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                         void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                         const float* background, int width, int height, const float* means3D, const float* shs,
-                         const float* colors_precomp, const float* opacities, const float* scales,
-                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                         const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                         float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                         float* out_acc_depth, float* out_alpha)
+// A call record as the library sees it: struct_size bytes of the caller's in a zeroed record of its own, so that fields the caller's header
+// did not have are null (include/gsrast.h: how the records grow).  The refusals of the record itself, before any check of its contents.
+static const char* take_record(void* own, size_t own_size, const void* call, size_t min_size)
 {
-    return forward_impl(ctx, options, FwdCall{ geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, false, nullptr, flags, out_acc_depth, out_alpha });
+    if (!call) return "call record: NULL";
+    size_t n;
+    memcpy(&n, call, sizeof n);      // (struct_size is the first field of both records)
+    if (n < min_size || n > own_size) return "call record: struct_size is not one this library knows";
+    memset(own, 0, own_size);
+    memcpy(own, call, n);
+    return nullptr;
 }
+static bool family_known(int family) { return family == GSRAST_FAMILY_DENSE || family == GSRAST_FAMILY_RAW; }
 
-int gsrast_forward_raw_flags(gsrast_context* ctx, const gsrast_options* options, unsigned flags,
-                             gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                             gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
-                             const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                             float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
-                             float* out_acc_depth, float* out_alpha)
+// ---- the exported forwards: the record call, and the reference-shaped positional one that fills a record by name ----
+int gsrast_render_forward(gsrast_context* ctx, const gsrast_options* options, const gsrast_forward_call* call)
 {
-    return forward_impl(ctx, options, FwdCall{ geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix, projmatrix, cam_pos,
-                        tan_fovx, tan_fovy, 0, out_color, out_depth, radii, stream, true, in, flags, out_acc_depth, out_alpha });
-}
-
-int gsrast_forward_ex(gsrast_context* ctx, const gsrast_options* options,
-                      gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                      void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                      const float* background, int width, int height, const float* means3D, const float* shs,
-                      const float* colors_precomp, const float* opacities, const float* scales,
-                      float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                      const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                      float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream)
-{
-    return gsrast_forward_flags(ctx, options, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, nullptr);
+    gsrast_forward_call c;
+    if (const char* e = take_record(&c, sizeof c, call, GSRAST_FORWARD_CALL_MIN)) return fail(GSRAST_E_ARG, e);
+    if (!family_known(c.family)) return fail(GSRAST_E_ARG, "call record: unknown family");
+    if (c.family == GSRAST_FAMILY_DENSE ? c.raw != nullptr
+                                        : c.means3D || c.shs || c.colors_precomp || c.opacities || c.scales || c.rotations || c.cov3D_precomp || c.prefiltered)
+        return fail(GSRAST_E_ARG, "call record: dense family with raw set, or raw family with a dense input / prefiltered set");
+    return forward_impl(ctx, options, c);
 }
 
 int gsrast_forward(gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
@@ -1741,45 +1715,16 @@ int gsrast_forward(gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_al
                    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                    float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream)
 {
-    return gsrast_forward_flags(nullptr, nullptr, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, nullptr, nullptr);
-}
-
-int gsrast_forward_aux(gsrast_context* ctx, const gsrast_options* options,
-                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc,
-                       void* binning_ctx, gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M,
-                       const float* background, int width, int height, const float* means3D, const float* shs,
-                       const float* colors_precomp, const float* opacities, const float* scales,
-                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, int* radii, void* stream,
-                       float* out_acc_depth, float* out_alpha)
-{
-    return gsrast_forward_flags(ctx, options, GSRAST_RENDER_AUX, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                                means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
-                                tan_fovx, tan_fovy, prefiltered, out_color, out_depth, radii, stream, out_acc_depth, out_alpha);
-}
-
-int gsrast_forward_raw(gsrast_context* ctx, const gsrast_options* options,
-                       gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                       gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
-                       const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                       float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream)
-{
-    return gsrast_forward_raw_flags(ctx, options, 0, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                                    in, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, radii, stream, nullptr, nullptr);
-}
-
-int gsrast_forward_raw_aux(gsrast_context* ctx, const gsrast_options* options,
-                           gsrast_alloc_fn geometry_alloc, void* geometry_ctx, gsrast_alloc_fn binning_alloc, void* binning_ctx,
-                           gsrast_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
-                           const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                           float tan_fovx, float tan_fovy, float* out_color, float* out_depth, int* radii, void* stream,
-                           float* out_acc_depth, float* out_alpha)
-{
-    return gsrast_forward_raw_flags(ctx, options, GSRAST_RENDER_AUX, geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background, width, height,
-                                    in, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, radii, stream, out_acc_depth, out_alpha);
+    gsrast_forward_call c{};
+    c.struct_size = sizeof c; c.family = GSRAST_FAMILY_DENSE;
+    c.geometry_alloc = geometry_alloc; c.geometry_ctx = geometry_ctx; c.binning_alloc = binning_alloc; c.binning_ctx = binning_ctx;
+    c.image_alloc = image_alloc; c.image_ctx = image_ctx;
+    c.P = P; c.D = D; c.M = M; c.background = background; c.width = width; c.height = height;
+    c.means3D = means3D; c.shs = shs; c.colors_precomp = colors_precomp; c.opacities = opacities; c.scales = scales;
+    c.rotations = rotations; c.cov3D_precomp = cov3D_precomp; c.scale_modifier = scale_modifier;
+    c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.cam_pos = cam_pos; c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
+    c.prefiltered = prefiltered; c.out_color = out_color; c.out_depth = out_depth; c.radii = radii; c.stream = stream;
+    return forward_impl(nullptr, nullptr, c);
 }
 
 int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_res, const float* rotation,
@@ -2365,28 +2310,13 @@ int gsrast_sh_grad_combine_union(int P, int D, int M, int N, const float* means3
     return GSRAST_OK;
 }
 
-// Everything a backward is called with: every exported gsrast_backward* fills one of these from its positional arguments.
-// raw_family: the call came through a gsrast_backward_raw* symbol -- `raw` / `raw_grads` replace the dense inputs and gradient outputs (which stay null).
-namespace {
-struct BwdCall {
-    int P, D, M, R; const float* background; int width, height;
-    const float *means3D, *shs, *colors_precomp, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
-    const float *viewmatrix, *projmatrix, *campos; float tan_fovx, tan_fovy; const int* radii;
-    char *geom_buffer, *binning_buffer, *image_buffer; const float* dL_dpix;
-    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot; void* stream;
-    bool raw_family; const gsrast_raw_inputs* raw; const gsrast_raw_grads* raw_grads;
-    unsigned flags; const float *dL_dacc_depth, *dL_dalpha;      // GSRAST_RENDER_*; the aux gradients are looked at only with GSRAST_RENDER_AUX
-    bool abs_symbol = false; float* dL_dmean2D_abs = nullptr;    // a *_flags_abs symbol; its [P][2] sink (GSRAST_RENDER_ABSGRAD)
-    bool pose_symbol = false; float* dL_dcamera = nullptr; char* pose_scratch = nullptr;      // a *_flags_pose symbol; its [35] output and scratch (GSRAST_RENDER_POSEGRAD)
-};
-} // namespace
-
 // One backward call's state and its stages (backward_impl below is the order they run in).  What the call does is decided once, by
 // plan_backward (gsrast_policy.h), from one snapshot of the options and the process-wide switches; the stages only check pointers and enqueue.
-// Raw family: the dense arrays are the model's raw leaves and their gradients, taken from the two structs in check_and_plan.
+// c: the call's record (include/gsrast.h: gsrast_backward_call).  Raw family: `raw` / `raw_grads` replace the dense inputs and gradient outputs (null in
+// the record): the dense pointers become the model's raw leaves and their gradients, taken from the two structs in check_and_plan.
 namespace {
 struct BackwardRun {
-    BwdCall c;      // (a copy: the raw family's leaves and gradient arrays take the dense pointers' places)
+    gsrast_backward_call c; const bool raw_family;      // (a copy: the raw family's leaves and gradient arrays take the dense pointers' places)
     gsrast_options o; const hipStream_t s;
     BackwardPlan plan;
     const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{}; RawGrads rawg{};
@@ -2399,18 +2329,18 @@ struct BackwardRun {
         ~SideJoinGuard() { if (side && !joined) (void)hipStreamSynchronize(side->stream); }
     } fork;
 
-    BackwardRun(const gsrast_options* options, const BwdCall& c_) : c(c_), o(options ? *options : snapshot_defaults()), s((hipStream_t)c_.stream) {}
+    BackwardRun(const gsrast_options* options, const gsrast_backward_call& c_) : c(c_), raw_family(c_.family == GSRAST_FAMILY_RAW), o(options ? *options : snapshot_defaults()), s((hipStream_t)c_.stream) {}
 
     // ---- the plan, and the checks every entry point shares (before any device work) ----
     int check_and_plan()
     {
         const int P = c.P, M = c.M;
-        if (c.raw_family) o.sh_grad_factors = (c.raw_grads && c.raw_grads->d_sh_factor) ? 1 : 0;      // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
-        plan = plan_backward(o, BackwardInputs{ c.flags, P, c.D, c.R, c.width, c.height, c.raw_family, (c.raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr),
+        if (raw_family) o.sh_grad_factors = (c.raw_grads && c.raw_grads->d_sh_factor) ? 1 : 0;      // the SH leaves' gradient leaves as its [P][3] factor (multi-GPU exchange)
+        plan = plan_backward(o, BackwardInputs{ c.flags, P, c.D, c.R, c.width, c.height, raw_family, (raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr),
                                                 c.colors_precomp != nullptr, c.cov3D_precomp != nullptr, c.dL_dacc_depth != nullptr || c.dL_dalpha != nullptr,
-                                                c.abs_symbol, c.dL_dmean2D_abs != nullptr, c.pose_symbol, c.dL_dcamera != nullptr, c.pose_scratch != nullptr }, snapshot_switches());
+                                                backward_known_flags(c.struct_size), c.dL_dmean2D_abs != nullptr, c.dL_dcamera != nullptr, c.pose_scratch != nullptr }, snapshot_switches());
         if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
-        if (c.raw_family) {
+        if (raw_family) {
             rawin = c.raw;
             const gsrast_raw_grads* const out = c.raw_grads;
             if (const char* e = raw_inputs_check(P, M, rawin)) return fail(GSRAST_E_ARG, e);
@@ -2586,9 +2516,9 @@ struct BackwardRun {
 
 // The one backward: checks -> plan -> zero-fill -> [fork: direction derivatives, zero rows] -> blend backward -> factor -> join and
 // per-Gaussian backward, in the order the plan says
-static int backward_impl(const gsrast_options* options, const BwdCall& c)
+static int backward_impl(const gsrast_options* options, const gsrast_backward_call& c)
 {
-    RoctxRange range_bwd(c.raw_family ? "gsrast_backward_raw" : "gsrast_backward");
+    RoctxRange range_bwd(c.family == GSRAST_FAMILY_RAW ? "gsrast_backward" "_raw" : "gsrast_backward");
     BackwardRun r(options, c);
     int rc = r.check_and_plan();
     if (rc == GSRAST_OK && c.P == 0 && r.plan.pose && r.o.backward_phase != 1 && hipMemsetAsync(c.dL_dcamera, 0, POSE_OUT * sizeof(float), r.s) != hipSuccess)
@@ -2601,102 +2531,17 @@ static int backward_impl(const gsrast_options* options, const BwdCall& c)
     return r.plan.join_late ? r.join() : GSRAST_OK;
 }
 
-// ---- the exported backwards: adapters that fill a BwdCall (include/gsrast.h: gsrast_backward = _ex(NULL) = _flags(0), _aux = _flags(AUX),
-// _flags = _flags_abs without the sink: GSRAST_RENDER_ABSGRAD is refused there) ----
-int gsrast_backward_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                              float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                              const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                              float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                              const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                              const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs)
+// ---- the exported backwards: the record call, and the reference-shaped positional one that fills a record by name ----
+int gsrast_render_backward(const gsrast_options* options, const gsrast_backward_call* call)
 {
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
-                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha, true, dL_dmean2D_abs });
-}
-
-int gsrast_backward_raw_flags_abs(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                                  const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                                  float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                                  const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
-                                  float* dL_dmean2D_abs)
-{
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha,
-                                           true, dL_dmean2D_abs });
-}
-
-// _flags_abs = _flags_pose without the camera's output: GSRAST_RENDER_POSEGRAD is refused there
-int gsrast_backward_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                               const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                               float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                               const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                               float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                               const float* dL_dacc_depth, const float* dL_dalpha, float* dL_dmean2D_abs, float* dL_dcamera, char* pose_scratch)
-{
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
-                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha, true, dL_dmean2D_abs, true, dL_dcamera, pose_scratch });
-}
-
-int gsrast_backward_raw_flags_pose(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                                   const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                                   float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                                   const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha,
-                                   float* dL_dmean2D_abs, float* dL_dcamera, char* pose_scratch)
-{
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha,
-                                           true, dL_dmean2D_abs, true, dL_dcamera, pose_scratch });
-}
-
-// One row of POSE_ROW floats per workgroup of the per-Gaussian backward, sized for its larger grid (the plain form: PP_THREADS Gaussians each)
-size_t gsrast_pose_scratch_bytes(int P) { return P > 0 ? (((size_t)P + PP_THREADS - 1) / PP_THREADS) * POSE_ROW * sizeof(float) : (size_t)POSE_ROW * sizeof(float); }
-
-int gsrast_backward_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                          const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                          float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                          float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                          const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                          float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                          const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream,
-                                           false, nullptr, nullptr, flags, dL_dacc_depth, dL_dalpha });
-}
-
-int gsrast_backward_raw_flags(const gsrast_options* options, unsigned flags, int P, int D, int M, int R, const float* background, int width, int height,
-                              const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                              float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                              const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    return backward_impl(options, BwdCall{ P, D, M, R, background, width, height, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr,
-                                           viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, true, in, out, flags, dL_dacc_depth, dL_dalpha });
-}
-
-int gsrast_backward_ex(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                       const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                       const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream)
-{
-    return gsrast_backward_flags(options, 0, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
+    gsrast_backward_call c;
+    if (const char* e = take_record(&c, sizeof c, call, GSRAST_BACKWARD_CALL_MIN)) return fail(GSRAST_E_ARG, e);
+    if (!family_known(c.family)) return fail(GSRAST_E_ARG, "call record: unknown family");
+    if (c.family == GSRAST_FAMILY_DENSE ? c.raw || c.raw_grads
+                                        : c.means3D || c.shs || c.colors_precomp || c.scales || c.rotations || c.cov3D_precomp || c.dL_dmean2D || c.dL_dconic ||
+                                          c.dL_dopacity || c.dL_dcolor || c.dL_dmean3D || c.dL_dcov3D || c.dL_dsh || c.dL_dscale || c.dL_drot)
+        return fail(GSRAST_E_ARG, "call record: dense family with raw / raw_grads set, or raw family with a dense input / gradient output set");
+    return backward_impl(options, c);
 }
 
 int gsrast_backward(int P, int D, int M, int R, const float* background, int width, int height,
@@ -2707,42 +2552,19 @@ int gsrast_backward(int P, int D, int M, int R, const float* background, int wid
                     const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream)
 {
-    return gsrast_backward_flags(nullptr, 0, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, nullptr, nullptr);
+    gsrast_backward_call c{};
+    c.struct_size = GSRAST_BACKWARD_CALL_MIN; c.family = GSRAST_FAMILY_DENSE;
+    c.P = P; c.D = D; c.M = M; c.R = R; c.background = background; c.width = width; c.height = height;
+    c.means3D = means3D; c.shs = shs; c.colors_precomp = colors_precomp; c.scales = scales; c.rotations = rotations; c.cov3D_precomp = cov3D_precomp;
+    c.scale_modifier = scale_modifier; c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.campos = campos; c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
+    c.radii = radii; c.geom_buffer = geom_buffer; c.binning_buffer = binning_buffer; c.image_buffer = image_buffer; c.dL_dpix = dL_dpix;
+    c.dL_dmean2D = dL_dmean2D; c.dL_dconic = dL_dconic; c.dL_dopacity = dL_dopacity; c.dL_dcolor = dL_dcolor; c.dL_dmean3D = dL_dmean3D;
+    c.dL_dcov3D = dL_dcov3D; c.dL_dsh = dL_dsh; c.dL_dscale = dL_dscale; c.dL_drot = dL_drot; c.stream = stream;
+    return backward_impl(nullptr, c);
 }
 
-int gsrast_backward_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                        const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                        float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                        const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                        float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                        const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, void* stream,
-                        const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    return gsrast_backward_flags(options, GSRAST_RENDER_AUX, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream, dL_dacc_depth, dL_dalpha);
-}
-
-int gsrast_backward_raw(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                        const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                        float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                        const float* dL_dpix, const gsrast_raw_grads* out, void* stream)
-{
-    return gsrast_backward_raw_flags(options, 0, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                                     radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, nullptr, nullptr);
-}
-
-int gsrast_backward_raw_aux(const gsrast_options* options, int P, int D, int M, int R, const float* background, int width, int height,
-                            const gsrast_raw_inputs* in, float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
-                            float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                            const float* dL_dpix, const gsrast_raw_grads* out, void* stream, const float* dL_dacc_depth, const float* dL_dalpha)
-{
-    return gsrast_backward_raw_flags(options, GSRAST_RENDER_AUX, P, D, M, R, background, width, height, in, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                                     radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, out, stream, dL_dacc_depth, dL_dalpha);
-}
+// One row of POSE_ROW floats per workgroup of the per-Gaussian backward, sized for its larger grid (the plain form: PP_THREADS Gaussians each)
+size_t gsrast_pose_scratch_bytes(int P) { return P > 0 ? (((size_t)P + PP_THREADS - 1) / PP_THREADS) * POSE_ROW * sizeof(float) : (size_t)POSE_ROW * sizeof(float); }
 
 int gsrast_debug_export(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
                         const char* image_buffer, float* depths, float* means2D, float* cov3D, float* conic_opacity,

@@ -230,9 +230,14 @@ inline ForwardPlan plan_forward(const gsrast_options& o, const PlanInputs& in, c
 // switches (plan_backward).  Whether the context's side stream could be had is the one second-phase answer (side_answer).
 // tests/test_policy.py reads the plan through gsrast_debug_backward_plan.
 struct BackwardInputs { unsigned flags; int P, D, R, W, H; bool raw_family, sh, colors_precomp, cov3D_precomp, aux_grads /* dL_dacc_depth or dL_dalpha is given */;
-                        bool abs_symbol = false /* the call came through a symbol that has a dL_dmean2D_abs argument */, abs_sink = false /* ... and it is not NULL */;
-                        // the call came through a gsrast_backward*_flags_pose symbol; its dL_dcamera / pose_scratch argument is not NULL
-                        bool pose_symbol = false, pose_out = false, pose_scratch = false; };
+                        unsigned known_flags = GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS;      // backward_known_flags(the record's struct_size)
+                        bool abs_sink = false, pose_out = false, pose_scratch = false; };        // dL_dmean2D_abs / dL_dcamera / pose_scratch is not NULL
+// The flag bits a backward record of struct_size bytes knows: a bit whose fields lie beyond struct_size is an unknown bit (include/gsrast.h)
+inline unsigned backward_known_flags(size_t struct_size)
+{
+    return GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS | (struct_size >= GSRAST_BACKWARD_CALL_ABS ? GSRAST_RENDER_ABSGRAD : 0u) |
+           (struct_size >= sizeof(gsrast_backward_call) ? GSRAST_RENDER_POSEGRAD : 0u);
+}
 // Which blend backward runs.  transposed: blend_bwd_cull_t_kernel<.., aux, abs>; ablate 1 / 2: blend_bwd_kernel<0, 4, ablate> (experiments), else 0
 struct BlendBwdPick { int ppl = 1; bool cull = false, transposed = false, aux = false; int ablate = 0; bool abs = false; };
 struct BackwardPlan {
@@ -274,11 +279,11 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     p.abs = (in.flags & GSRAST_RENDER_ABSGRAD) != 0;
     p.pose = (in.flags & GSRAST_RENDER_POSEGRAD) != 0;
     p.pick.cull = culled_blend(o, true);
-    // (GSRAST_RENDER_POSEGRAD is a known bit only where the symbol has its arguments: everywhere else it is an unknown bit like any other)
-    if (in.flags & ~(unsigned)(GSRAST_RENDER_AUX | GSRAST_RENDER_ANTIALIAS | GSRAST_RENDER_ABSGRAD | (in.pose_symbol ? GSRAST_RENDER_POSEGRAD : 0u))) p.refusal = "flags: unknown bits";
+    // (GSRAST_RENDER_ABSGRAD on a record without its sink is refused further down, where it always was, with a text of its own)
+    if (in.flags & ~(in.known_flags | GSRAST_RENDER_ABSGRAD)) p.refusal = "flags: unknown bits";
     else if (!options_valid(o)) p.refusal = "backward: bad option value";
     else if (aux_flag && !p.pick.cull) p.refusal = "backward: acc_depth / alpha gradients need the culled blend kernels (options.cull != 0)";
-    else if (p.abs && !in.abs_symbol) p.refusal = "flags: unknown bits (GSRAST_RENDER_ABSGRAD is known only to the gsrast_backward*_flags_abs symbols, which have its sink)";
+    else if (p.abs && !(in.known_flags & GSRAST_RENDER_ABSGRAD)) p.refusal = "flags: unknown bits (GSRAST_RENDER_ABSGRAD is known only to a call record whose struct_size covers dL_dmean2D_abs)";
     else if (p.abs && !in.abs_sink) p.refusal = "backward: GSRAST_RENDER_ABSGRAD with a NULL dL_dmean2D_abs";
     else if (!p.abs && in.abs_sink) p.refusal = "backward: dL_dmean2D_abs without GSRAST_RENDER_ABSGRAD";
     else if (p.abs && (!p.pick.cull || g.ablate == 1 || g.ablate == 2))

@@ -48,7 +48,7 @@ __device__ __forceinline__ Cam load_cam(const CamArgs& a)
     return c;
 }
 
-// ---- raw-parameter entry points (gsrast_forward_raw / gsrast_backward_raw) ------------------------------
+// ---- raw-parameter entry points (GSRAST_FAMILY_RAW call records) --------- ------------------------------
 // SaRO-GS hands the rasterizer ACTIVATED attributes: exp(_scaling), normalize(_rotation), sigmoid(_opacity) * trbf,
 // cat(_features_dc, _features_rest) + residuals (scene/saro_gaussian.py:807-847, activations :39-47) -- a [P,16,3] tensor written
 // by the model and re-read here, and the reverse in the backward.  With RAW = true the per-Gaussian kernels take the model's
@@ -676,9 +676,9 @@ preprocess_color_compact_kernel(int P, int D, int M, const float* __restrict__ m
 #define GSRAST_PF_THREADS 256      // (1024-thread blocks shorten the depth-range reduction of the bucket scatter by 2 us, but beside the colour kernel they wait for whole-CU wave slots: 43 -> 107 us)
 #endif
 constexpr int PF_THREADS = GSRAST_PF_THREADS;
-// RAW (gsrast_forward_raw): means3D / scales / rotations / opacities are the model's _xyz / _scaling / _rotation / _opacity leaves
+// RAW (a GSRAST_FAMILY_RAW forward): means3D / scales / rotations / opacities are the model's _xyz / _scaling / _rotation / _opacity leaves
 // and `raw` carries the optional residuals; the activations happen right behind the loads (RawArgs above).
-// AA (gsrast_forward_flags with GSRAST_RENDER_ANTIALIAS): the opacity is scaled by aa_comp right behind the covariance; everything
+// AA (a forward with GSRAST_RENDER_ANTIALIAS): the opacity is scaled by aa_comp right behind the covariance; everything
 // downstream takes o_eff.  A template parameter, so that the plain instantiations keep their code (and registers) as they were.
 template <bool RAW, bool AA = false>
 __global__ void __launch_bounds__(PF_THREADS)
@@ -1054,7 +1054,7 @@ sh_dir_derivs_kernel(int P, int D, int M, const float* __restrict__ means3D, con
 
 // K6 + K7 fused.  Every output row is written exactly once (zeros for culled Gaussians), so the
 // caller does not have to zero-fill the five output arrays.  dL/dsh leaves through LDS (coalesced).
-// RAW (gsrast_backward_raw): means3D / scales / rotations are the model's leaves as in preprocess_fwd_kernel<true>; the chain rule
+// RAW (a GSRAST_FAMILY_RAW backward): means3D / scales / rotations are the model's leaves as in preprocess_fwd_kernel<true>; the chain rule
 // through the activations (epilogue_small_bwd_kernel's expressions) is applied before the stores: dL_dmeans3D = d_xyz (= d_motion_res),
 // dL_dscale = d_scaling, dL_drot = d_rotation, dL_dopacity = d_opacity_logit, plus RawGrads (d_rot_res, d_trbf, the SH leaves).
 // (Measured and dropped with the list cut: not even READING the gradient record of a Gaussian the forward's scatter marked late --
@@ -1065,10 +1065,10 @@ sh_dir_derivs_kernel(int P, int D, int M, const float* __restrict__ means3D, con
 // at 1 M).  Measured and dropped: not writing those rows either, the arrays zero-filled by a kernel on the side stream under the blend
 // backward -- preprocess_bwd 229 -> 130 us at 3 M, but the fill's 700 MB slowed the VALU-bound blend backward by 45 us and the extra
 // launches cost the small scenes 10-50 us: no better than this at 3 M, worse everywhere else.
-// AA (gsrast_backward_flags with GSRAST_RENDER_ANTIALIAS; the state must come from an anti-aliased forward): the record's dL/do_eff = g
+// AA (a backward with GSRAST_RENDER_ANTIALIAS; the state must come from an anti-aliased forward): the record's dL/do_eff = g
 // becomes dL/do = g * comp, and g * o_eff * 0.5 * d(ln rho)/d(c00, c01, c11) joins dL/d(a, b, c) in front of the covariance chain (zero on
 // the floor).  o_eff is the forward's rec1.y.  Every output is still linear in the record: the SPARSE shortcut holds.
-// POSE (gsrast_backward_flags_pose with GSRAST_RENDER_POSEGRAD): the gradient of the camera.  viewmatrix, projmatrix and campos are three
+// POSE (a backward with GSRAST_RENDER_POSEGRAD): the gradient of the camera.  viewmatrix, projmatrix and campos are three
 // independent inputs in the row-vector storage t = [mean, 1] @ viewmatrix, hom = [mean, 1] @ projmatrix; every Gaussian adds POSE_TERMS sums:
 //   dV[r][c]  += mean_r dt_c, dV[3][c] += dt_c (c < 3; dt = dtx, dty, dtz below, the aux depth term included) and, through the rotation inside
 //                T = J W, dV[r][c] += sum_j J[j][c] dT[j][r] (the frustum-clamped entries of J constants, as everywhere in this backward);
@@ -1107,7 +1107,7 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       // the bits' place -- "no pixel consumed this Gaussian", a superset of "culled or late" that needs no pose table
                       const unsigned long long* __restrict__ late_bits = nullptr, const uint32_t* __restrict__ cut_scalars = nullptr,
                       const unsigned char* __restrict__ untouched = nullptr,
-                      // aux (gsrast_backward_aux): float 9 of the record (gr2.y) is dL/d(view-space z) from the blend backward's acc_depth
+                      // aux (GSRAST_RENDER_AUX): float 9 of the record (gr2.y) is dL/d(view-space z) from the blend backward's acc_depth
                       // gradient -- added to the projection chain's own; 0: the record's nine sums only, exactly as without it
                       int aux = 0,
                       const float4* __restrict__ rec1 = nullptr /* AA: GeomLayout::rec1 of the forward, whose .y is o_eff */,

@@ -23,7 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsrast_hip.so")
 
 NUM_CHANNELS = 3  # reference config.h:15
-ABI_VERSION = 5   # include/gsrast.h: GSRAST_ABI_VERSION this binding was written against
+ABI_VERSION = 6   # include/gsrast.h: GSRAST_ABI_VERSION this binding was written against
 
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 _lib: Optional[C.CDLL] = None
@@ -40,19 +40,16 @@ EXPORTS = (
     "gsrast_knn_scratch_bytes", "gsrast_knn3_mean_dist2",
     "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event", "gsrast_debug_forward_plan", "gsrast_debug_backward_plan",
-    "gsrast_forward_ex", "gsrast_backward_ex", "gsrast_forward_raw", "gsrast_backward_raw", "gsrast_alloc_prealloc",
-    "gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux",
-    "gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags",
-    "gsrast_backward_flags_abs", "gsrast_backward_raw_flags_abs",
-    "gsrast_backward_flags_pose", "gsrast_backward_raw_flags_pose", "gsrast_pose_scratch_bytes",
+    "gsrast_render_forward", "gsrast_render_backward", "gsrast_alloc_prealloc", "gsrast_pose_scratch_bytes",
     "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
 )
 
-# include/gsrast.h: the flags word of the gsrast_*_flags entry points
+# include/gsrast.h: the flags word of a call record
 RENDER_AUX = 0x1
 RENDER_ANTIALIAS = 0x2
-RENDER_ABSGRAD = 0x4      # the two gsrast_backward*_flags_abs symbols only (and their _pose siblings)
-RENDER_POSEGRAD = 0x8     # the two gsrast_backward*_flags_pose symbols only
+RENDER_ABSGRAD = 0x4      # backward records whose struct_size covers dL_dmean2D_abs
+RENDER_POSEGRAD = 0x8     # backward records whose struct_size covers dL_dcamera / pose_scratch
+FAMILY_DENSE, FAMILY_RAW = 0, 1
 CAMERA_FLOATS = 35        # dL_dcamera: dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
 
 
@@ -64,8 +61,8 @@ class OptionsStruct(C.Structure):
                 ("forward_only", C.c_int), ("no_order_hint", C.c_int), ("dense_backward", C.c_int), ("no_list_cut", C.c_int)]
 
 
-# Per-call options are kept PER HOST THREAD on the Python side and travel with every call (gsrast_forward_ex /
-# gsrast_backward_ex): two threads rendering on two streams with different options never see each other's settings.
+# Per-call options are kept PER HOST THREAD on the Python side and travel with every call (gsrast_render_forward /
+# gsrast_render_backward): two threads rendering on two streams with different options never see each other's settings.
 PER_CALL_OPTIONS = ("exp_mode", "binning", "tile_clip", "cull", "lpt", "speculative", "fwd_pixels_per_lane", "bwd_pixels_per_lane", "side_stream", "depth_sort", "forward_only", "no_order_hint", "dense_backward", "no_list_cut")
 _OPTION_DEFAULTS = dict(exp_mode=0, binning=0, tile_clip=1, cull=1, lpt=1, speculative=1, fwd_pixels_per_lane=0, bwd_pixels_per_lane=0, side_stream=1, depth_sort=0, forward_only=0, no_order_hint=0, dense_backward=0, no_list_cut=0)
 _OPTION_RANGE = dict(exp_mode=(0, 1, 2), binning=(0, 1), depth_sort=(0, 1), fwd_pixels_per_lane=(0, 1, 2, 4), bwd_pixels_per_lane=(0, 1, 2, 4))
@@ -124,6 +121,26 @@ class RawGradsStruct(C.Structure):
                                           "d_features_dc", "d_features_rest", "d_shs_res", "d_sh_factor")]
 
 
+_fields = lambda *groups: [(n, t) for t, names in groups for n in names.split()]  # noqa: E731  ([(name, ctype), ...] from (ctype, "name name ...") groups)
+
+
+class ForwardCallStruct(C.Structure):
+    """gsrast_forward_call (include/gsrast.h)."""
+    _fields_ = _fields((C.c_size_t, "struct_size"), (C.c_uint, "flags"), (C.c_int, "family"), (_ALLOC_FN, "geometry_alloc"), (C.c_void_p, "geometry_ctx"), (_ALLOC_FN, "binning_alloc"),
+                       (C.c_void_p, "binning_ctx"), (_ALLOC_FN, "image_alloc"), (C.c_void_p, "image_ctx"), (C.c_int, "P D M"), (C.c_void_p, "background"), (C.c_int, "width height"),
+                       (C.c_void_p, "means3D shs colors_precomp opacities scales rotations cov3D_precomp"), (C.POINTER(RawInputsStruct), "raw"), (C.c_float, "scale_modifier"),
+                       (C.c_void_p, "viewmatrix projmatrix cam_pos"), (C.c_float, "tan_fovx tan_fovy"), (C.c_int, "prefiltered"), (C.c_void_p, "out_color out_depth radii stream out_acc_depth out_alpha"))
+
+
+class BackwardCallStruct(C.Structure):
+    """gsrast_backward_call (include/gsrast.h); GSRAST_BACKWARD_CALL_MIN ends in front of dL_dmean2D_abs, GSRAST_BACKWARD_CALL_ABS in front of dL_dcamera."""
+    _fields_ = _fields((C.c_size_t, "struct_size"), (C.c_uint, "flags"), (C.c_int, "family"), (C.c_int, "P D M R"), (C.c_void_p, "background"), (C.c_int, "width height"),
+                       (C.c_void_p, "means3D shs colors_precomp scales rotations cov3D_precomp"), (C.POINTER(RawInputsStruct), "raw"), (C.c_float, "scale_modifier"),
+                       (C.c_void_p, "viewmatrix projmatrix campos"), (C.c_float, "tan_fovx tan_fovy"), (C.c_void_p, "radii geom_buffer binning_buffer image_buffer dL_dpix"),
+                       (C.c_void_p, "dL_dmean2D dL_dconic dL_dopacity dL_dcolor dL_dmean3D dL_dcov3D dL_dsh dL_dscale dL_drot"), (C.POINTER(RawGradsStruct), "raw_grads"),
+                       (C.c_void_p, "stream dL_dacc_depth dL_dalpha dL_dmean2D_abs dL_dcamera pose_scratch"))
+
+
 class AdamGroupStruct(C.Structure):
     """gsrast_adam_group (include/gsrast.h)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
@@ -157,23 +174,11 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     vp, ci, cf = C.c_void_p, C.c_int, C.c_float
     opt = C.POINTER(OptionsStruct)
-    fwd = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]
-    bwd = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    fwd_raw = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf, vp, vp, vp, vp]
-    bwd_raw = [ci, ci, ci, ci, vp, ci, ci, C.POINTER(RawInputsStruct), cf, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, C.POINTER(RawGradsStruct), vp]
-    # every render family: the legacy symbol without options, the plain one, _aux (+ the two [1,H,W] arrays: outputs / upstream gradients,
-    # NULL = zero) and _flags (the flags word behind the options) -- the one this binding calls (_render_call)
-    for family, legacy, plain, head, args in (("forward", "gsrast_forward", "_ex", [vp, opt], fwd), ("backward", "gsrast_backward", "_ex", [opt], bwd),
-                                              ("forward_raw", None, "", [vp, opt], fwd_raw), ("backward_raw", None, "", [opt], bwd_raw)):
-        table = [("gsrast_" + family + plain, head + args), ("gsrast_" + family + "_aux", head + args + [vp, vp]),
-                 ("gsrast_" + family + "_flags", head + [C.c_uint] + args + [vp, vp])]
-        if family.startswith("backward"):      # + the [P,2] sink of GSRAST_RENDER_ABSGRAD
-            table.append(("gsrast_" + family + "_flags_abs", head + [C.c_uint] + args + [vp, vp, vp]))
-            # + the [35] output and the scratch of GSRAST_RENDER_POSEGRAD
-            table.append(("gsrast_" + family + "_flags_pose", head + [C.c_uint] + args + [vp, vp, vp, vp, vp]))
-        for name, types in table + ([(legacy, args)] if legacy else []):
-            getattr(L, name).restype = ci
-            getattr(L, name).argtypes = types
+    # the render calls: the reference-shaped positional pair, and the pair over one call record each (the one this binding calls: _render_call)
+    L.gsrast_forward.restype = L.gsrast_backward.restype = L.gsrast_render_forward.restype = L.gsrast_render_backward.restype = ci      # (ctypes' default, spelled out)
+    L.gsrast_forward.argtypes = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]
+    L.gsrast_backward.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf] + [vp] * 15
+    L.gsrast_render_forward.argtypes, L.gsrast_render_backward.argtypes = [vp, opt, C.POINTER(ForwardCallStruct)], [opt, C.POINTER(BackwardCallStruct)]
     L.gsrast_options_init.restype = None
     L.gsrast_options_init.argtypes = [C.POINTER(OptionsStruct)]
     L.gsrast_context_create.restype = vp
@@ -531,22 +536,19 @@ class _Arena:
             self.callbacks = None
 
 
-def _render_call(family: str, head: tuple, args: tuple, flags: int, aux: tuple, absgrad: Optional[torch.Tensor] = None,
+def _render_call(entry: str, head: tuple, rec, flags: int, absgrad: Optional[torch.Tensor] = None,
                  camera: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> int:
-    """The one native render call: gsrast_<family>_flags(*head, flags, *args, *aux) for family "forward" / "backward" / "forward_raw" /
-    "backward_raw" (flags = 0 is exactly the _ex / _raw call, include/gsrast.h).  Returns its result (forward: the number of rendered
-    instances), raises on an error code.  `absgrad` (backward families): the [P,2] sink of GSRAST_RENDER_ABSGRAD -- the _flags_abs
-    symbol with the bit set; None: the _flags symbol, as before the sink existed.  `camera` (backward families): (the [35] output, the
-    scratch) of GSRAST_RENDER_POSEGRAD (_pose_buffers) -- the _flags_pose symbol with the bit set; None: the call as before it existed."""
-    name = "gsrast_" + family + "_flags"
+    """The one native render call: gsrast_render_forward / gsrast_render_backward (`entry`) on the call record `rec`, whose inputs the caller has filled
+    by name (include/gsrast.h).  Returns its result (forward: the number of rendered instances), raises on an error code.  Backward: `absgrad`, the [P,2] sink
+    of GSRAST_RENDER_ABSGRAD; `camera`, (the [35] output, the scratch) of GSRAST_RENDER_POSEGRAD (_pose_buffers); either sets its bit and its fields."""
+    if absgrad is not None:
+        flags, rec.dL_dmean2D_abs = flags | RENDER_ABSGRAD, absgrad.data_ptr()
     if camera is not None:
-        name, aux = name + "_pose", (*aux, None if absgrad is None else absgrad.data_ptr(), camera[0].data_ptr(), camera[1].data_ptr())
-        flags |= RENDER_POSEGRAD | (0 if absgrad is None else RENDER_ABSGRAD)
-    elif absgrad is not None:
-        name, flags, aux = name + "_abs", flags | RENDER_ABSGRAD, (*aux, absgrad.data_ptr())
-    rc = getattr(lib(), name)(*head, flags, *args, *aux)
+        flags, rec.dL_dcamera, rec.pose_scratch = flags | RENDER_POSEGRAD, camera[0].data_ptr(), camera[1].data_ptr()
+    rec.struct_size, rec.flags = C.sizeof(rec), flags
+    rc = getattr(lib(), entry)(*head, rec)
     if rc < 0:
-        raise _err(rc, name)
+        raise _err(rc, entry)
     return rc
 
 
@@ -555,7 +557,7 @@ _pose_cache: dict = {}
 
 def _pose_buffers(P: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
     """(the [35] float32 output, the scratch) of a backward with GSRAST_RENDER_POSEGRAD, kept per device, stream and P: both are fully
-    overwritten by every such backward, and the backward hands autograd a copy of the output."""
+    overwritten by every such backward (zeroed here for P = 0, which makes no call), and the backward hands autograd a copy of the output."""
     k = (dev.index, int(_stream_of(dev) or 0), P)
     v = _pose_cache.get(k)
     if v is None:
@@ -563,6 +565,8 @@ def _pose_buffers(P: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor
             _pose_cache.clear()
         v = _pose_cache[k] = (torch.empty((CAMERA_FLOATS,), dtype=torch.float32, device=dev),
                               torch.empty((int(lib().gsrast_pose_scratch_bytes(P)),), dtype=torch.uint8, device=dev))
+    if P == 0:
+        v[0].zero_()
     return v
 
 
@@ -572,9 +576,10 @@ def _camera_result(camera: Optional[Tuple[torch.Tensor, torch.Tensor]]):
     return g[:16].view(4, 4), g[16:32].view(4, 4), g[32:]
 
 
-def _forward(family: str, dev: torch.device, P: int, H: int, W: int, inputs: tuple, forward_only: bool, aux: bool, antialiasing: bool):
-    """What the dense and the raw forward share: the outputs, the state arena, the call (`inputs`: the symbol's arguments between the
-    allocators and out_color) and the return tuple."""
+def _forward(rec: ForwardCallStruct, dev: torch.device, forward_only: bool, aux: bool, antialiasing: bool):
+    """What the dense and the raw forward share: the outputs, the state arena, the call (`rec`: the record with the family's inputs
+    filled in) and the return tuple."""
+    P, H, W = rec.P, rec.height, rec.width
     o = dict(dtype=torch.float32, device=dev)
     out_color, out_depth = torch.empty((NUM_CHANNELS, H, W), **o), torch.empty((1, H, W), **o)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
@@ -582,11 +587,11 @@ def _forward(family: str, dev: torch.device, P: int, H: int, W: int, inputs: tup
     arena = _Arena.acquire(dev)
     try:
         with _on_device(dev):
-            rendered = _render_call(
-                family, (_current_context(), C.byref(_options_struct(forward_only=forward_only))),       # context: the innermost `with Context()` of the calling thread, else the thread's own
-                (*arena.forward_allocators(P, W, H), *inputs, out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), _stream_of(dev)),
-                (RENDER_AUX if aux else 0) | (RENDER_ANTIALIAS if antialiasing else 0),
-                (aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None))
+            (rec.geometry_alloc, rec.geometry_ctx, rec.binning_alloc, rec.binning_ctx, rec.image_alloc, rec.image_ctx) = arena.forward_allocators(P, W, H)
+            rec.out_color, rec.out_depth, rec.radii, rec.stream = out_color.data_ptr(), out_depth.data_ptr(), _ptr(radii), _stream_of(dev)
+            rec.out_acc_depth, rec.out_alpha = (aux_out[0].data_ptr(), aux_out[1].data_ptr()) if aux else (None, None)
+            rendered = _render_call("gsrast_render_forward", (_current_context(), _options_struct(forward_only=forward_only)),       # context: the innermost `with Context()` of the calling thread, else the thread's own
+                                    rec, (RENDER_AUX if aux else 0) | (RENDER_ANTIALIAS if antialiasing else 0))
         return (rendered, out_color, radii, arena.tensor(0), arena.tensor(1), arena.tensor(2), out_depth) + aux_out
     finally:
         arena.close()       # break the arena <-> callback cycle now, not whenever the cyclic GC runs
@@ -613,10 +618,11 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     scales, rotations, cov3D_precomp = f(scales, "scales"), f(rotations, "rotations"), f(cov3D_precomp, "cov3D_precomp")
     viewmatrix, projmatrix, sh, campos = f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(sh, "shs"), f(campos, "campos")
     M = int(sh.shape[1]) if sh.numel() != 0 else 0  # rasterize_points.cu:83-87
-    inputs = (P, int(degree), M, background.data_ptr(), W, H, means3D.data_ptr(), _ptr(sh), _ptr(colors), opacity.data_ptr(),
-              _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(),
-              projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)))
-    return _forward("forward", dev, P, H, W, inputs, forward_only, aux, antialiasing)
+    rec = ForwardCallStruct(family=FAMILY_DENSE, P=P, D=int(degree), M=M, background=background.data_ptr(), width=W, height=H, means3D=means3D.data_ptr(), shs=_ptr(sh),
+                            colors_precomp=_ptr(colors), opacities=opacity.data_ptr(), scales=_ptr(scales), rotations=_ptr(rotations), cov3D_precomp=_ptr(cov3D_precomp),
+                            scale_modifier=float(scale_modifier), viewmatrix=viewmatrix.data_ptr(), projmatrix=projmatrix.data_ptr(), cam_pos=_ptr(campos),
+                            tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), prefiltered=int(bool(prefiltered)))
+    return _forward(rec, dev, forward_only, aux, antialiasing)
 
 
 def _claim_grad_arena(fits, P: int, campos: torch.Tensor, degree: int, no_factors: Optional[str] = None) -> Optional["GradArena"]:
@@ -644,7 +650,7 @@ def _claim_grad_arena(fits, P: int, campos: torch.Tensor, degree: int, no_factor
 
 def _run_backward(ar: Optional["GradArena"], call, P: int, geomBuffer: torch.Tensor, dev: torch.device) -> None:
     """call(phase) enqueues the native backward (0: all of it).  In factor mode the touched rows are exported first and, with a
-    factor-ready hook, the backward runs in two phases around it."""
+    factor-ready hook, the backward runs in two phases around it: on one call record, only the options differ."""
     factors = ar is not None and ar.sh_factors
     if factors:
         # which rows this view can touch is known since the forward's blend (its untouched bits): exported BEFORE the backward
@@ -717,24 +723,19 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dscales = out("scales", (P, 3), not use_sr)
     dL_drotations = out("rotations", (P, 4), not use_sr)
     camera = _pose_buffers(P, dev) if camera_grads else None
-    if camera is not None and P == 0:
-        camera[0].zero_()
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
-            args = (P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                    _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
-                    _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii_c),
-                    _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dL_dout_color),
-                    dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), _ptr(dL_dcolors),
-                    dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscales.data_ptr(),
-                    dL_drotations.data_ptr(), _stream_of(dev))
-
-            def call(phase):      # options travel per call: no process-wide switch is flipped
-                _render_call("backward", (C.byref(_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux, absgrad, camera)
-
-            _run_backward(ar, call, P, geomBuffer, dev)
+            rec = BackwardCallStruct(
+                family=FAMILY_DENSE, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, means3D=_ptr(means3D), shs=_ptr(sh),
+                colors_precomp=_ptr(colors), scales=_ptr(scales), rotations=_ptr(rotations), cov3D_precomp=_ptr(cov3D_precomp), scale_modifier=float(scale_modifier),
+                viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=_ptr(radii_c),
+                geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dpix=_ptr(dL_dout_color),
+                dL_dmean2D=dL_dmeans2D.data_ptr(), dL_dopacity=dL_dopacity.data_ptr(), dL_dcolor=_ptr(dL_dcolors), dL_dmean3D=dL_dmeans3D.data_ptr(), dL_dcov3D=_ptr(dL_dcov3D),
+                dL_dsh=ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscale=dL_dscales.data_ptr(), dL_drot=dL_drotations.data_ptr(), stream=_stream_of(dev),
+                dL_dacc_depth=aux[0], dL_dalpha=aux[1])
+            _run_backward(ar, lambda phase: _render_call(      # options travel per call: no process-wide switch is flipped
+                "gsrast_render_backward", (_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera), P, geomBuffer, dev)
     grads = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     return grads if camera is None else grads + (_camera_result(camera),)
 
@@ -833,7 +834,7 @@ def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device,
     return flags | RENDER_AUX, (_ptr(keep[0]), _ptr(keep[1])), keep
 
 
-# ---- raw-parameter entry points (include/gsrast.h: gsrast_forward_raw / gsrast_backward_raw; no counterpart in the reference's _C) ----
+# ---- raw-parameter entry points (include/gsrast.h: GSRAST_FAMILY_RAW records; no counterpart in the reference's _C) ----
 RAW_NAMES = ("xyz", "motion_res", "rotation", "rot_res", "scaling", "opacity_logit", "trbf", "features_dc", "features_rest", "shs_res")
 
 
@@ -873,9 +874,9 @@ def rasterize_gaussians_raw(background, raw: dict, scale_modifier, viewmatrix, p
     st, keep, M = _raw_struct(raw, dev, P)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, viewmatrix, projmatrix, campos = f(background, "bg"), f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(campos, "campos")
-    inputs = (P, int(degree), M, _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-              float(tan_fovx), float(tan_fovy))
-    return _forward("forward_raw", dev, P, H, W, inputs, forward_only, aux, antialiasing)
+    rec = ForwardCallStruct(family=FAMILY_RAW, P=P, D=int(degree), M=M, background=_ptr(background), width=W, height=H, raw=C.pointer(st), scale_modifier=float(scale_modifier),
+                            viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), cam_pos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy))
+    return _forward(rec, dev, forward_only, aux, antialiasing)
 
 
 def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
@@ -927,21 +928,16 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                         d_trbf=_ptr(g.get("trbf")), d_features_dc=p_dc, d_features_rest=p_rest, d_shs_res=_ptr(g.get("shs_res")),
                         d_sh_factor=p_fac)
     camera = _pose_buffers(P, dev) if camera_grads else None
-    if camera is not None and P == 0:
-        camera[0].zero_()
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
-            args = (P, int(degree), M, int(R),
-                    _ptr(background), W, H, C.byref(st), float(scale_modifier), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                    float(tan_fovx), float(tan_fovy), _ptr(radii_c), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
-                    _ptr(dL_dout_color), C.byref(gs), _stream_of(dev))
-
-            def call(phase):
-                _render_call("backward_raw", (C.byref(_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase)),),
-                             args, flags, aux, absgrad, camera)
-
-            _run_backward(ar, call, P, geomBuffer, dev)
+            rec = BackwardCallStruct(
+                family=FAMILY_RAW, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, raw=C.pointer(st), scale_modifier=float(scale_modifier),
+                viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=_ptr(radii_c),
+                geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dpix=_ptr(dL_dout_color), raw_grads=C.pointer(gs),
+                stream=_stream_of(dev), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
+            _run_backward(ar, lambda phase: _render_call(
+                "gsrast_render_backward", (_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera), P, geomBuffer, dev)
     if camera is not None:
         g["camera"] = _camera_result(camera)
     if keep["motion_res"] is not None:

@@ -22,7 +22,7 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
 * not in the reference: ``forward(..., return_aux=True)`` (also ``rasterize_gaussians`` and ``GaussianRasterizerRaw``) returns
   ``(color, radii, depth, acc_depth[1,H,W], alpha[1,H,W])`` -- alpha = 1 - T_final and the accumulated depth
   sum_i alpha_i T_i z_i (not normalised: expected depth = acc_depth / alpha), both differentiable like the colour
-  (include/gsrast.h: gsrast_forward_aux / gsrast_backward_aux).  The median ``depth`` keeps the reference's zero gradient.
+  (include/gsrast.h: GSRAST_RENDER_AUX).  The median ``depth`` keeps the reference's zero gradient.
 * not in the reference: ``forward(..., antialiasing=True)`` (keyword-only, default False; also ``rasterize_gaussians`` and
   ``GaussianRasterizerRaw``, and together with ``return_aux``) -- upstream 3DGS's ``antialiasing``, the 2-D Mip filter of
   Mip-Splatting: each Gaussian's opacity is scaled by sqrt(det cov2D / det(cov2D + 0.3 I)) so that the 0.3 px^2 dilation does not

@@ -1,10 +1,10 @@
-"""CPU: the absolute screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD, gsrast_backward_flags_abs /
-gsrast_backward_raw_flags_abs; `absgrad=` of the Python package) -- the fp64 reference of tests/absgrad_math.py checks itself, the new
-symbols are declared, bound and refuse bad arguments before any device work, the package refuses a bad sink at forward time, and the
-densification plumbing (view_parallel.distributed_step, fused_densify.DensifyStats.update) carries the statistic."""
+"""CPU: the absolute screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD, dL_dmean2D_abs of gsrast_backward_call;
+`absgrad=` of the Python package) -- the fp64 reference of tests/absgrad_math.py checks itself, the backward records refuse bad
+arguments before any device work, the package refuses a bad sink at forward time, and the densification plumbing
+(view_parallel.distributed_step, fused_densify.DensifyStats.update) carries the statistic.  (The records' layout and the flag values:
+tests/test_capi_abi.py.)"""
 import ctypes as C
 import os
-import re
 import socket
 import sys
 
@@ -15,9 +15,9 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import absgrad_math as am
+import capi_records as cr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsrast.h")
 
 
 @pytest.fixture(scope="module")
@@ -70,76 +70,57 @@ def test_symmetric_gaussian_has_no_signed_gradient_but_an_absolute_one(scenes):
 
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
-def test_symbols_are_declared_exported_and_bound(rast, L):
-    src = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n, sib in (("gsrast_backward_flags_abs", "gsrast_backward_flags"), ("gsrast_backward_raw_flags_abs", "gsrast_backward_raw_flags")):
-        assert re.search(r"\bint\s+" + n + r"\s*\(", text), f"{n} not declared in gsrast.h"
-        assert hasattr(raw, n) and n in rast._C.EXPORTS
-        assert getattr(L, n).argtypes == list(getattr(L, sib).argtypes) + [C.c_void_p]      # the sibling's arguments + the sink
-        assert getattr(L, n).restype is C.c_int
-    assert re.search(r"#define\s+GSRAST_RENDER_ABSGRAD\s+0x4u\b", src)
-    assert rast._C.RENDER_ABSGRAD == 4
-    assert L.gsrast_abi_version() == 5      # additive: the version does not move
-
-
 def test_bad_arguments_fail_before_any_device_work(L, rast):
     _C = rast._C
-    one = C.c_void_p(16)
+    one = cr.ONE
     AUX, AA, ABS = _C.RENDER_AUX, _C.RENDER_ANTIALIAS, _C.RENDER_ABSGRAD
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))
-    o = C.byref(opts)
-    err = L.gsrast_last_error
 
-    def dense(sym, P, flags, *tail):
-        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one,
-                               one, one, one, one, one, None, one, None, one, None, one, one, one, None, None, None, *tail)
+    def call(family, size, P, flags, sink=None):      # size "abs": the record truncated just behind the sink; "min": a record without it
+        return cr.call(cr.backward(P, flags, family, size=size, dL_dmean2D_abs=sink), opts)
 
-    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
-
-    def raw(sym, P, flags, *tail):
-        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one,
-                               C.byref(gr), None, None, None, *tail)
-
-    for call, name in ((dense, "gsrast_backward_flags"), (raw, "gsrast_backward_raw_flags")):
+    for family in ("dense", "raw"):
         for fl in (ABS, ABS | AA):
             # the bit with a NULL sink
-            assert call(name + "_abs", 10, fl, None) == -1 and b"NULL dL_dmean2D_abs" in err()
-            # the bit on a symbol that has no sink: an unknown bit there
-            assert call(name, 10, fl) == -1 and b"unknown bits" in err() and b"_flags_abs" in err()
+            rc, err = call(family, "abs", 10, fl)
+            assert rc == -1 and b"NULL dL_dmean2D_abs" in err
+            # the bit on a record that has no sink: an unknown bit there
+            rc, err = call(family, "min", 10, fl)
+            assert rc == -1 and b"unknown bits" in err and b"dL_dmean2D_abs" in err
         # a sink without the bit
         for fl in (0, AA):
-            assert call(name + "_abs", 10, fl, one) == -1 and b"without GSRAST_RENDER_ABSGRAD" in err()
-        # unknown bits stay unknown on the new symbols
-        assert call(name + "_abs", 10, ABS | 0x8, one) == -1 and b"unknown bits" in err()
+            rc, err = call(family, "abs", 10, fl, one)
+            assert rc == -1 and b"without GSRAST_RENDER_ABSGRAD" in err
+        # unknown bits stay unknown on the longer record
+        rc, err = call(family, "abs", 10, ABS | 0x8, one)
+        assert rc == -1 and b"unknown bits" in err
         # the bit where the transposed blend backward would not run: cull = 0 (GSRAST_RENDER_AUX's rule), the ablation kernels
         opts.cull = 0
-        assert call(name + "_abs", 10, ABS, one) == -1 and b"transposed" in err() and b"cull" in err()
+        rc, err = call(family, "abs", 10, ABS, one)
+        assert rc == -1 and b"transposed" in err and b"cull" in err
         L.gsrast_options_init(C.byref(opts))
         for abl in (1, 2):
             _C.set_option("ablate", abl)
             try:
-                assert call(name + "_abs", 10, ABS, one) == -1 and b"transposed" in err()
+                rc, err = call(family, "abs", 10, ABS, one)
+                assert rc == -1 and b"transposed" in err
             finally:
                 _C.set_option("ablate", 0)
         # a good combination reaches the ordinary checks (here: the negative P), with and without the bit
-        assert call(name + "_abs", -1, ABS, one) == -1 and b"ABSGRAD" not in err() and b"unknown bits" not in err()
-        assert call(name + "_abs", -1, 0, None) == -1 and b"ABSGRAD" not in err()
+        rc, err = call(family, "abs", -1, ABS, one)
+        assert rc == -1 and b"ABSGRAD" not in err and b"unknown bits" not in err
+        rc, err = call(family, "abs", -1, 0)
+        assert rc == -1 and b"ABSGRAD" not in err
         # P = 0: nothing to do, no device touched
-        assert call(name + "_abs", 0, ABS, one) == 0
+        assert call(family, "abs", 0, ABS, one)[0] == 0
     # the forward has no use for the bit: mask it off (include/gsrast.h)
-    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-    cb = ALLOC(lambda ctx, n: None)
-    rc = L.gsrast_forward_flags(None, o, ABS, cb, None, cb, None, cb, None, 10, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one,
-                                None, one, one, one, 0.5, 0.5, 0, one, one, one, None, None, None)
-    assert rc == -1 and b"unknown bits" in err()
+    rc, err = cr.call(cr.forward(10, ABS), opts)
+    assert rc == -1 and b"unknown bits" in err
 
 
 def test_backward_plan_takes_the_transposed_kernel_only_for_the_new_symbols(L, rast):
-    """gsrast_debug_backward_plan stands for a symbol without a sink: it refuses the bit, and plans every other call as before."""
+    """gsrast_debug_backward_plan (without 32 in words[5]) stands for a record without a sink: it refuses the bit, and plans every other call as before."""
     _C = rast._C
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))

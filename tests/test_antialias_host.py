@@ -1,20 +1,17 @@
-"""CPU: the anti-aliased rendering (include/gsrast.h: GSRAST_RENDER_ANTIALIAS and the gsrast_*_flags entry points) -- declared,
-exported and bound; argument errors refused before any device work; `antialiasing` keyword-only and False by default on every Python
-surface; the fp64 helper the GPU tests measure against (tests/aa_math.py)."""
+"""CPU: the anti-aliased rendering (include/gsrast.h: GSRAST_RENDER_ANTIALIAS, the `flags` word of the call records) -- argument
+errors refused before any device work; `antialiasing` keyword-only and False by default on every Python surface; the fp64 helper the
+GPU tests measure against (tests/aa_math.py).  (The records' layout and the flag values: tests/test_capi_abi.py.)"""
 import ctypes as C
 import inspect
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsrast.h")
-FLAGS = ("gsrast_forward_flags", "gsrast_backward_flags", "gsrast_forward_raw_flags", "gsrast_backward_raw_flags")
-SIBLINGS = ("gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux")
+import capi_records as cr
+
+ONE = cr.ONE
 
 
 @pytest.fixture(scope="module")
@@ -22,142 +19,113 @@ def L(rast):
     return rast._C.lib()
 
 
-def test_flags_symbols_are_declared_exported_and_bound(rast, L):
-    src = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n, sib in zip(FLAGS, SIBLINGS):
-        assert re.search(r"\bint\s+" + n + r"\s*\(", text), f"{n} not declared in gsrast.h"
-        assert hasattr(raw, n), f"{n} not exported"
-        assert n in rast._C.EXPORTS
-        # the aux sibling's arguments with an unsigned flags word behind the options
-        at = 2 if "forward" in n else 1
-        want = list(getattr(L, sib).argtypes)
-        assert getattr(L, n).argtypes == want[:at] + [C.c_uint] + want[at:], n
-        assert getattr(L, n).restype is C.c_int
-    assert re.search(r"#define\s+GSRAST_RENDER_AUX\s+0x1u\b", src)
-    assert re.search(r"#define\s+GSRAST_RENDER_ANTIALIAS\s+0x2u\b", src)
-    assert (rast._C.RENDER_AUX, rast._C.RENDER_ANTIALIAS) == (1, 2)
-    assert L.gsrast_abi_version() == 5
+def _fwd(P, opts, flags, acc, alpha, family="dense"):
+    return cr.call(cr.forward(P, flags, family, out_acc_depth=acc, out_alpha=alpha), opts)
 
 
-def _fwd(L, cb, P, one, opts, flags, acc, alpha):
-    return L.gsrast_forward_flags(None, opts, flags, cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one,
-                                  None, one, one, one, 0.5, 0.5, 0, one, one, one, None, acc, alpha)
-
-
-def _bwd(L, P, one, opts, flags, dacc=None, dal=None):
-    return L.gsrast_backward_flags(opts, flags, P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one,
-                                   one, one, one, one, one, None, one, None, one, None, one, one, one, None, dacc, dal)
+def _bwd(P, opts, flags, dacc=None, dal=None, family="dense"):      # (the record of a caller that knows the flags word and nothing later)
+    return cr.call(cr.backward(P, flags, family, size="min", dL_dacc_depth=dacc, dL_dalpha=dal), opts)
 
 
 def test_flags_entry_points_refuse_bad_arguments_before_any_device_work(L, rast):
     _C = rast._C
-    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-    cb = ALLOC(lambda ctx, n: None)      # an allocation would fail: a refusal that got that far would say "allocation"
-    one = C.c_void_p(16)
     AUX, AA = _C.RENDER_AUX, _C.RENDER_ANTIALIAS
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))
-    o = C.byref(opts)
     # unknown bits, alone and next to known ones
     for bad in (0x4, 0x80000000, AA | 0x8, AUX | AA | 0x10):
-        assert _fwd(L, cb, 10, one, o, bad, one, one) == -1 and b"unknown bits" in L.gsrast_last_error(), bad
-        assert _bwd(L, 10, one, o, bad) == -1 and b"unknown bits" in L.gsrast_last_error(), bad
+        rc, err = _fwd(10, opts, bad, ONE, ONE)
+        assert rc == -1 and b"unknown bits" in err, bad
+        rc, err = _bwd(10, opts, bad)
+        assert rc == -1 and b"unknown bits" in err, bad
     # AUX with a NULL aux output (AA or not)
     for fl in (AUX, AUX | AA):
-        for a, b in ((None, one), (one, None), (None, None)):
-            assert _fwd(L, cb, 10, one, o, fl, a, b) == -1 and b"NULL acc_depth / alpha" in L.gsrast_last_error()
+        for a, b in ((None, ONE), (ONE, None), (None, None)):
+            rc, err = _fwd(10, opts, fl, a, b)
+            assert rc == -1 and b"NULL acc_depth / alpha" in err
     # AUX with cull = 0, forward and backward
     opts.cull = 0
     for fl in (AUX, AUX | AA):
-        assert _fwd(L, cb, 10, one, o, fl, one, one) == -1 and b"cull" in L.gsrast_last_error()
-        assert _bwd(L, 10, one, o, fl, one, None) == -1 and b"cull" in L.gsrast_last_error()
-        assert _bwd(L, 10, one, o, fl) == -1 and b"cull" in L.gsrast_last_error()
+        for rc, err in (_fwd(10, opts, fl, ONE, ONE), _bwd(10, opts, fl, ONE, None), _bwd(10, opts, fl)):
+            assert rc == -1 and b"cull" in err
     # (AA alone does not need the culled kernels: it reaches the ordinary argument checks -- here the negative P)
-    assert _fwd(L, cb, -1, one, o, AA, None, None) == -1 and b"bad P" in L.gsrast_last_error()
+    rc, err = _fwd(-1, opts, AA, None, None)
+    assert rc == -1 and b"bad P" in err
     L.gsrast_options_init(C.byref(opts))
-    assert _fwd(L, cb, -1, one, o, AA, None, None) == -1
-    assert _bwd(L, -1, one, o, AA) == -1
-    # the raw pair
-    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    fr = lambda P, fl, a, b: L.gsrast_forward_raw_flags(None, o, fl, cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, C.byref(ins),   # noqa: E731
-                                                        1.0, one, one, one, 1.0, 1.0, one, one, one, None, a, b)
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
-    br = lambda P, fl, a=None, b=None: L.gsrast_backward_raw_flags(o, fl, P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one,   # noqa: E731
-                                                                   1.0, 1.0, one, one, one, one, one, C.byref(gr), None, a, b)
-    assert fr(10, 0x4, one, one) == -1 and b"unknown bits" in L.gsrast_last_error()
-    assert br(10, 0x4) == -1 and b"unknown bits" in L.gsrast_last_error()
-    assert fr(10, AUX | AA, None, one) == -1 and b"NULL acc_depth / alpha" in L.gsrast_last_error()
-    assert fr(-1, AA, None, None) == -1
-    assert br(-1, AA) == -1
+    assert _fwd(-1, opts, AA, None, None)[0] == -1
+    assert _bwd(-1, opts, AA)[0] == -1
+    # the raw family
+    fr = lambda P, fl, a, b: _fwd(P, opts, fl, a, b, "raw")                  # noqa: E731
+    br = lambda P, fl, a=None, b=None: _bwd(P, opts, fl, a, b, "raw")        # noqa: E731
+    for rc, err in (fr(10, 0x4, ONE, ONE), br(10, 0x4)):
+        assert rc == -1 and b"unknown bits" in err
+    rc, err = fr(10, AUX | AA, None, ONE)
+    assert rc == -1 and b"NULL acc_depth / alpha" in err
+    assert fr(-1, AA, None, None)[0] == -1
+    assert br(-1, AA)[0] == -1
     opts.cull = 0
-    assert fr(10, AUX, one, one) == -1 and b"cull" in L.gsrast_last_error()
-    assert br(10, AUX | AA, one, None) == -1 and b"cull" in L.gsrast_last_error()
+    for rc, err in (fr(10, AUX, ONE, ONE), br(10, AUX | AA, ONE, None)):
+        assert rc == -1 and b"cull" in err
     L.gsrast_options_init(C.byref(opts))
 
 
 def test_every_render_symbol_is_an_adapter_over_one_path(L, rast):
-    """The same bad argument through every symbol of a family that can express it: the same return code and the same
-    gsrast_last_error() text, forward and backward, dense (_ex, _aux, _flags) and raw (_raw, _raw_aux, _raw_flags).  All of these return
-    before any device work (the allocators would fail: a refusal that got that far would say "allocation")."""
+    """The same bad argument through every way of a family that can express it: the same return code and the same gsrast_last_error()
+    text, forward and backward, dense and raw -- the backward record at each of its three sizes ("min": what a caller compiled before the
+    absgrad sink passes, "abs": before the pose fields, "full"), and for the dense family with flags = 0 the positional gsrast_forward /
+    gsrast_backward (which take no options: the process defaults).  All of these return before any device work (the allocators would
+    fail: a refusal that got that far would say "allocation")."""
     _C = rast._C
-    cb = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)(lambda ctx, n: None)
-    one = C.c_void_p(16)
+    one = C.c_void_p(ONE)
     AUX = _C.RENDER_AUX
     opts = _C.OptionsStruct()
-    o = C.byref(opts)
-    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
-    body = {      # the arguments between the options (+ flags) and the aux pair, as a function of P
-        "forward": lambda P: (cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one, None, one, one, one,
-                              0.5, 0.5, 0, one, one, one, None),
-        "backward": lambda P: (P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one, one, one, one,
-                               one, one, None, one, None, one, None, one, one, one, None),
-        "forward_raw": lambda P: (cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0,
-                                  one, one, one, None),
-        "backward_raw": lambda P: (P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one,
-                                   C.byref(gr), None),
-    }
 
-    def outcomes(family, P, flags, a, b):
-        """(symbol, return code, error text) of every symbol of the family that can express (flags, aux pair)."""
-        head = (None, o) if family.startswith("forward") else (o,)
-        plain = "gsrast_" + family + ("" if family.endswith("raw") else "_ex")
-        calls = [("gsrast_" + family + "_flags", head + (flags,) + body[family](P) + (a, b))]
-        if flags == AUX:
-            calls.append(("gsrast_" + family + "_aux", head + body[family](P) + (a, b)))
-        if flags == 0:
-            calls.append((plain, head + body[family](P)))
-        out = []
-        for name, args in calls:
-            rc = getattr(L, name)(*args)
-            out.append((name, rc, L.gsrast_last_error()))
+    def positional(family, P):
+        if family == "forward":
+            rc = L.gsrast_forward(cr.NO_ALLOC, None, cr.NO_ALLOC, None, cr.NO_ALLOC, None, P, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one, None,
+                                  one, one, one, 0.5, 0.5, 0, one, one, one, None)
+        else:
+            rc = L.gsrast_backward(P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one, one, one, one,
+                                   one, one, None, one, None, one, None, one, one, one, None)
+        return ("gsrast_" + family, rc, L.gsrast_last_error())
+
+    def outcomes(family, P, flags, a, b, with_positional=False):
+        """(way, return code, error text) of every way of the family that can express (flags, aux pair)."""
+        direction, _, raw = family.partition("_")
+        kind = "raw" if raw else "dense"
+        if direction == "forward":
+            recs = [("record", cr.forward(P, flags, kind, out_acc_depth=a, out_alpha=b))]
+        else:
+            recs = [(size, cr.backward(P, flags, kind, size=size, dL_dacc_depth=a, dL_dalpha=b)) for size in ("min", "abs", "full")]
+        out = [(way,) + cr.call(rec, opts) for way, rec in recs]
+        if with_positional and not raw:
+            out.append(positional(direction, P))
         return out
 
-    def same(results, n_symbols, needle):
-        assert len(results) == n_symbols, results
+    def same(results, n_ways, needle):
+        assert len(results) == n_ways, results
         assert {r[1] for r in results} == {-1}, results
         assert len({r[2] for r in results}) == 1, results
         assert needle in results[0][2], results
 
     for family in ("forward", "backward", "forward_raw", "backward_raw"):
-        L.gsrast_options_init(o)
-        # P = -1: through all three (plain and _flags with flags = 0, _aux and _flags with AUX)
+        L.gsrast_options_init(C.byref(opts))
+        n = 1 if family.startswith("forward") else 3      # the records of the family
+        # P = -1: flags = 0 (the positional call too) and AUX
         sizes = b"bad P" if family.startswith("forward") else b"bad sizes"
-        plain = outcomes(family, -1, 0, None, None)
-        auxed = outcomes(family, -1, AUX, one, one)
-        same(plain + auxed, 4, sizes)
-        # an unknown flag bit: _flags alone can express it
-        same(outcomes(family, 10, 0x4, one, one), 1, b"unknown bits")
-        # forward, AUX with a NULL aux output: _aux and _flags
+        plain = outcomes(family, -1, 0, None, None, with_positional=True)
+        auxed = outcomes(family, -1, AUX, ONE, ONE)
+        same(plain + auxed, 2 * n + (0 if family.endswith("raw") else 1), sizes)
+        # an unknown flag bit
+        same(outcomes(family, 10, 0x10, ONE, ONE), n, b"unknown bits")
+        # forward, AUX with a NULL aux output
         if family.startswith("forward"):
-            for a, b in ((None, one), (one, None), (None, None)):
-                same(outcomes(family, 10, AUX, a, b), 2, b"NULL acc_depth / alpha")
-        # AUX with cull = 0: _aux and _flags
+            for a, b in ((None, ONE), (ONE, None), (None, None)):
+                same(outcomes(family, 10, AUX, a, b), n, b"NULL acc_depth / alpha")
+        # AUX with cull = 0
         opts.cull = 0
-        same(outcomes(family, 10, AUX, one, one), 2, b"cull")
-    L.gsrast_options_init(o)
+        same(outcomes(family, 10, AUX, ONE, ONE), n, b"cull")
+    L.gsrast_options_init(C.byref(opts))
 
 
 def test_antialiasing_is_keyword_only_and_false_by_default_on_every_surface(rast):

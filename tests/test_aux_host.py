@@ -1,15 +1,14 @@
-"""CPU: the differentiable alpha / accumulated-depth outputs (include/gsrast.h: gsrast_forward_aux, gsrast_backward_aux and the raw
-pair) -- declared, exported and bound; argument errors refused before any device work; the Python surfaces default to the plain path."""
+"""CPU: the differentiable alpha / accumulated-depth outputs (include/gsrast.h: GSRAST_RENDER_AUX; out_acc_depth / out_alpha of
+gsrast_forward_call, dL_dacc_depth / dL_dalpha of gsrast_backward_call, either family) -- argument errors refused before any device
+work; the Python surfaces default to the plain path.  (The records' layout: tests/test_capi_abi.py.)"""
 import ctypes as C
 import inspect
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsrast.h")
-AUX = ("gsrast_forward_aux", "gsrast_backward_aux", "gsrast_forward_raw_aux", "gsrast_backward_raw_aux")
+import capi_records as cr
+
+ONE = cr.ONE
 
 
 @pytest.fixture(scope="module")
@@ -17,68 +16,45 @@ def L(rast):
     return rast._C.lib()
 
 
-def test_aux_symbols_are_declared_exported_and_listed(rast, L):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n in AUX:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", text), f"{n} not declared in gsrast.h"
-        assert hasattr(raw, n), f"{n} not exported"
-        assert n in rast._C.EXPORTS
-    # each takes its sibling's arguments + the two [1,H,W] arrays
-    for n, sib in zip(AUX, ("gsrast_forward_ex", "gsrast_backward_ex", "gsrast_forward_raw", "gsrast_backward_raw")):
-        assert getattr(L, n).argtypes == getattr(L, sib).argtypes + [C.c_void_p, C.c_void_p]
-    assert L.gsrast_abi_version() == 5
-
-
-def _fwd_args(L, cb, P, one):
-    return (None, None, cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one, None,
-            one, one, one, 0.5, 0.5, 0, one, one, one, None)
-
-
-def _bwd_args(P, one, opts=None):
-    return (opts, P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one, one, one, one, one,
-            one, None, one, None, one, None, one, one, one, None)
-
-
 def test_aux_entry_points_refuse_bad_arguments_before_any_device_work(L, rast):
     _C = rast._C
-    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-    cb = ALLOC(lambda ctx, n: None)      # an allocation would fail: a refusal that got that far would say "allocation"
-    one = C.c_void_p(16)
+    AUX = _C.RENDER_AUX
     # negative P
-    assert L.gsrast_forward_aux(*_fwd_args(L, cb, -1, one), one, one) == -1
-    assert L.gsrast_backward_aux(*_bwd_args(-1, one), one, one) == -1
+    assert cr.call(cr.forward(-1, AUX, out_acc_depth=ONE, out_alpha=ONE))[0] == -1
+    assert cr.call(cr.backward(-1, AUX, dL_dacc_depth=ONE, dL_dalpha=ONE))[0] == -1
     # NULL aux outputs
-    for a, b in ((None, one), (one, None), (None, None)):
-        assert L.gsrast_forward_aux(*_fwd_args(L, cb, 10, one), a, b) == -1
-        assert b"NULL acc_depth / alpha" in L.gsrast_last_error()
+    for a, b in ((None, ONE), (ONE, None), (None, None)):
+        rc, err = cr.call(cr.forward(10, AUX, out_acc_depth=a, out_alpha=b))
+        assert rc == -1 and b"NULL acc_depth / alpha" in err
     # cull = 0
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))
     opts.cull = 0
-    args = list(_fwd_args(L, cb, 10, one)); args[1] = C.byref(opts)
-    assert L.gsrast_forward_aux(*args, one, one) == -1 and b"cull" in L.gsrast_last_error()
-    assert L.gsrast_backward_aux(*_bwd_args(10, one, C.byref(opts)), one, None) == -1 and b"cull" in L.gsrast_last_error()
-    assert L.gsrast_backward_aux(*_bwd_args(10, one, C.byref(opts)), None, one) == -1 and b"cull" in L.gsrast_last_error()
+    fwd = cr.forward(10, AUX, out_acc_depth=ONE, out_alpha=ONE)
+    rc, err = cr.call(fwd, opts)
+    assert rc == -1 and b"cull" in err
+    for a, b in ((ONE, None), (None, ONE)):
+        rc, err = cr.call(cr.backward(10, AUX, dL_dacc_depth=a, dL_dalpha=b), opts)
+        assert rc == -1 and b"cull" in err
     # a forced pixels-per-lane forward selects the un-culled kernel, which has no aux outputs
     L.gsrast_options_init(C.byref(opts))
     opts.fwd_pixels_per_lane = 2
-    args[1] = C.byref(opts)
-    assert L.gsrast_forward_aux(*args, one, one) == -1 and b"cull" in L.gsrast_last_error()
-    # the raw pair
+    rc, err = cr.call(fwd, opts)
+    assert rc == -1 and b"cull" in err
+    # the raw family
     L.gsrast_options_init(C.byref(opts))
-    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    fr = lambda P, o: (None, o, cb, None, cb, None, cb, None, P, 3, 16, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0,   # noqa: E731
-                       one, one, one, None)
-    assert L.gsrast_forward_raw_aux(*fr(-1, C.byref(opts)), one, one) == -1
-    assert L.gsrast_forward_raw_aux(*fr(10, C.byref(opts)), None, one) == -1 and b"NULL acc_depth / alpha" in L.gsrast_last_error()
+    fr = lambda P, a, b: cr.call(cr.forward(P, AUX, "raw", out_acc_depth=a, out_alpha=b), opts)      # noqa: E731
+    br = lambda P, a, b: cr.call(cr.backward(P, AUX, "raw", dL_dacc_depth=a, dL_dalpha=b), opts)     # noqa: E731
+    assert fr(-1, ONE, ONE)[0] == -1
+    rc, err = fr(10, None, ONE)
+    assert rc == -1 and b"NULL acc_depth / alpha" in err
     opts.cull = 0
-    assert L.gsrast_forward_raw_aux(*fr(10, C.byref(opts)), one, one) == -1 and b"cull" in L.gsrast_last_error()
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
-    br = lambda P, o: (o, P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one, C.byref(gr), None)  # noqa: E731
-    assert L.gsrast_backward_raw_aux(*br(10, C.byref(opts)), one, None) == -1 and b"cull" in L.gsrast_last_error()
+    rc, err = fr(10, ONE, ONE)
+    assert rc == -1 and b"cull" in err
+    rc, err = br(10, ONE, None)
+    assert rc == -1 and b"cull" in err
     L.gsrast_options_init(C.byref(opts))
-    assert L.gsrast_backward_raw_aux(*br(-1, C.byref(opts)), one, one) == -1
+    assert br(-1, ONE, ONE)[0] == -1
 
 
 def test_return_aux_defaults_to_false_on_every_surface(rast):

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import capi_records as cr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gsrast.h")
 
@@ -28,8 +30,108 @@ def test_header_and_library_agree(rast, L):
     for n in names:
         assert hasattr(raw, n), f"{n} declared in gsrast.h but not exported"
     assert sorted(rast._C.EXPORTS) == names
-    assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 5
-    assert re.search(r"#define GSRAST_ABI_VERSION 5\b", open(HEADER).read())
+    assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
+    assert re.search(r"#define GSRAST_ABI_VERSION 6\b", open(HEADER).read())
+    render = [n for n in names if re.fullmatch(r"gsrast_(render_)?(forward|backward)\w*", n)]
+    assert render == ["gsrast_backward", "gsrast_forward", "gsrast_render_backward", "gsrast_render_forward"]      # four render entry points, no more
+
+
+C_TYPES = {"size_t": C.c_size_t, "unsigned": C.c_uint, "int": C.c_int, "float": C.c_float, "gsrast_alloc_fn": None, "void*": C.c_void_p, "const float*": C.c_void_p,
+           "float*": C.c_void_p, "const int*": C.c_void_p, "int*": C.c_void_p, "char*": C.c_void_p, "const gsrast_raw_inputs*": "RawInputsStruct",
+           "const gsrast_raw_grads*": "RawGradsStruct"}
+
+
+def declared_fields(struct):
+    """[(name, C type)] of `typedef struct <struct> { ... } <struct>;` as include/gsrast.h declares it, in order."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct + ";", text, flags=re.S).group(1)
+    out = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        ctype, names = re.fullmatch(r"([\w ]+?\*?)\s*(\w+(?:\s*,\s*\w+)*)", decl).groups()
+        out += [(n.strip(), ctype.strip()) for n in names.split(",")]
+    return out
+
+
+def test_call_records_match_the_header(rast, L):
+    """The two call records (include/gsrast.h: how the records grow) as the binding declares them: the same fields, in the same order, of
+    the same C types; the prefixes a caller of an earlier header passes end where the header says; the flag bits and families have the
+    header's values.  Every render feature is a field and a bit here -- the header declares no symbol for any of them."""
+    _C = rast._C
+    src = open(HEADER).read()
+    for struct, cls in (("gsrast_forward_call", _C.ForwardCallStruct), ("gsrast_backward_call", _C.BackwardCallStruct)):
+        want = declared_fields(struct)
+        assert [n for n, _ in want] == [n for n, _ in cls._fields_], struct
+        for (name, ctype), (_, bound) in zip(want, cls._fields_):
+            expect = C_TYPES[ctype]
+            expect = _C._ALLOC_FN if expect is None else C.POINTER(getattr(_C, expect)) if isinstance(expect, str) else expect
+            assert bound is expect, (struct, name, ctype, bound)
+        assert want[0] == ("struct_size", "size_t") and want[1] == ("flags", "unsigned") and want[2] == ("family", "int")
+    B = _C.BackwardCallStruct
+    names = [n for n, _ in B._fields_]
+    # MIN: everything up to the aux gradients; then the absgrad sink; then the two pose fields, which end the record
+    assert re.search(r"#define GSRAST_BACKWARD_CALL_MIN offsetof\(gsrast_backward_call, dL_dmean2D_abs\)", src)
+    assert re.search(r"#define GSRAST_BACKWARD_CALL_ABS offsetof\(gsrast_backward_call, dL_dcamera\)", src)
+    assert re.search(r"#define GSRAST_FORWARD_CALL_MIN  sizeof\(gsrast_forward_call\)", src)
+    assert names[-5:] == ["dL_dacc_depth", "dL_dalpha", "dL_dmean2D_abs", "dL_dcamera", "pose_scratch"]
+    assert cr.SIZES == dict(min=B.dL_dmean2D_abs.offset, abs=B.dL_dcamera.offset, full=C.sizeof(B))
+    assert cr.SIZES["min"] + 8 == cr.SIZES["abs"] and cr.SIZES["abs"] + 16 == cr.SIZES["full"]
+    assert [n for n, _ in _C.ForwardCallStruct._fields_][-2:] == ["out_acc_depth", "out_alpha"]
+    for name, value in (("RENDER_AUX", 1), ("RENDER_ANTIALIAS", 2), ("RENDER_ABSGRAD", 4), ("RENDER_POSEGRAD", 8)):
+        assert re.search(r"#define\s+GSRAST_" + name + r"\s+" + hex(value) + r"u\b", src) and getattr(_C, name) == value
+    for name, value in (("FAMILY_DENSE", 0), ("FAMILY_RAW", 1)):
+        assert re.search(r"#define\s+GSRAST_" + name + r"\s+" + str(value) + r"\b", src) and getattr(_C, name) == value
+    for fn, args in ((L.gsrast_render_forward, [C.c_void_p, C.POINTER(_C.OptionsStruct), C.POINTER(_C.ForwardCallStruct)]),
+                     (L.gsrast_render_backward, [C.POINTER(_C.OptionsStruct), C.POINTER(B)])):
+        assert fn.argtypes == args and fn.restype is C.c_int
+
+
+def test_call_records_are_refused_by_size_family_and_unknown_bits(L, rast):
+    """The refusals of the record itself, all before any device work (every pointer in these records is 16)."""
+    _C = rast._C
+    AUX, AA, ABS, POSE = _C.RENDER_AUX, _C.RENDER_ANTIALIAS, _C.RENDER_ABSGRAD, _C.RENDER_POSEGRAD
+    # a NULL record
+    assert L.gsrast_render_forward(None, None, None) == -1 and b"call record: NULL" in L.gsrast_last_error()
+    assert L.gsrast_render_backward(None, None) == -1 and b"call record: NULL" in L.gsrast_last_error()
+    # struct_size 0, MIN - 1, sizeof + 8 (the record behind it is never read past what this library knows)
+    F = C.sizeof(_C.ForwardCallStruct)
+    for size in (0, F - 1, F + 8):
+        rc, err = cr.call(cr.forward(size=size))
+        assert rc == -1 and b"struct_size" in err, size
+    for size in (0, cr.SIZES["min"] - 1, cr.SIZES["full"] + 8):
+        for family in ("dense", "raw"):
+            rc, err = cr.call(cr.backward(family=family, size=size))
+            assert rc == -1 and b"struct_size" in err, size
+    # every size in between is a record (here: refused for its P, not for its size)
+    for size in ("min", cr.SIZES["min"] + 4, "abs", "full"):
+        rc, err = cr.call(cr.backward(-1, size=size))
+        assert rc == -1 and b"bad sizes" in err, size
+    # an unknown family; a dense record with `raw` set, a raw record with a dense input set
+    for make in (cr.forward, cr.backward):
+        rec = make()
+        rec.family = 2
+        rc, err = cr.call(rec)
+        assert rc == -1 and b"unknown family" in err
+        rc, err = cr.call(make(raw=cr.RAW_INPUTS))
+        assert rc == -1 and b"call record: dense family with raw" in err
+        rc, err = cr.call(make(family="raw", means3D=cr.ONE))
+        assert rc == -1 and b"raw family with a dense input" in err
+    rc, err = cr.call(cr.backward(raw_grads=cr.RAW_GRADS))
+    assert rc == -1 and b"call record: dense family with raw" in err
+    rc, err = cr.call(cr.backward(family="raw", dL_dmean3D=cr.ONE))
+    assert rc == -1 and b"raw family with a dense input" in err
+    rc, err = cr.call(cr.forward(family="raw", prefiltered=1))
+    assert rc == -1 and b"prefiltered" in err
+    # a flag bit whose fields lie beyond struct_size is an unknown bit; P = -1 on each of those records is refused for its size, not its flags
+    for family in ("dense", "raw"):
+        for size, flags in (("min", ABS), ("min", POSE), ("min", ABS | AA), ("abs", POSE), ("abs", POSE | AUX), ("full", 0x10), ("full", POSE | 0x10)):
+            rc, err = cr.call(cr.backward(10, flags, family, size=size))
+            assert rc == -1 and b"unknown bits" in err, (family, size, flags)
+            rc, err = cr.call(cr.backward(-1, 0, family, size=size))
+            assert rc == -1 and b"bad sizes" in err and b"ABSGRAD" not in err and b"POSEGRAD" not in err and b"unknown bits" not in err
+    for flags in (ABS, POSE, 0x10):
+        for family in ("dense", "raw"):
+            rc, err = cr.call(cr.forward(10, flags, family))
+            assert rc == -1 and b"unknown bits" in err
 
 
 def test_no_torch_or_cxx_types_in_the_boundary():
@@ -104,31 +206,21 @@ def test_widened_rows_reject_bad_arguments_without_a_device(rast, L):
 
 
 def test_raw_entry_points_reject_bad_arguments_before_any_device_work(L, rast):
-    """gsrast_forward_raw / gsrast_backward_raw validate their pointer sets on the host (no GPU needed for the refusals)."""
+    """GSRAST_FAMILY_RAW records: the pointer sets are validated on the host (no GPU needed for the refusals)."""
     _C = rast._C
-    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-    cb = ALLOC(lambda ctx, n: None)
-    one = C.c_void_p(16)
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))
     assert opts.forward_only == 0 and opts.tile_clip == 1
-    ins = _C.RawInputsStruct()
-    rc = L.gsrast_forward_raw(None, C.byref(opts), cb, None, cb, None, cb, None, 10, 3, 16, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, None)
-    assert rc < 0 and b"raw" in L.gsrast_last_error()
-    ok = dict(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    ins = _C.RawInputsStruct(**ok)
-    rc = L.gsrast_forward_raw(None, C.byref(opts), cb, None, cb, None, cb, None, 10, 3, 9, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, None)
-    assert rc < 0 and b"M must be" in L.gsrast_last_error()
-    ins = _C.RawInputsStruct(**dict(ok, features_rest=20))
-    rc = L.gsrast_forward_raw(None, C.byref(opts), cb, None, cb, None, cb, None, 10, 3, 16, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, None)
-    assert rc < 0 and b"aligned" in L.gsrast_last_error()
-    ins = _C.RawInputsStruct(**ok)
-    gr = _C.RawGradsStruct()
-    rc = L.gsrast_backward_raw(C.byref(opts), 10, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one, C.byref(gr), None)
-    assert rc < 0 and b"NULL required gradient" in L.gsrast_last_error()
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_shs_res=16)
-    rc = L.gsrast_backward_raw(C.byref(opts), 10, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one, C.byref(gr), None)
-    assert rc < 0 and b"d_shs_res" in L.gsrast_last_error()
+    rc, err = cr.call(cr.forward(family="raw", raw={}), opts)
+    assert rc < 0 and b"raw" in err
+    rc, err = cr.call(cr.forward(family="raw", M=9), opts)
+    assert rc < 0 and b"M must be" in err
+    rc, err = cr.call(cr.forward(family="raw", raw=dict(cr.RAW_INPUTS, features_rest=20)), opts)
+    assert rc < 0 and b"aligned" in err
+    rc, err = cr.call(cr.backward(family="raw", raw_grads={}), opts)
+    assert rc < 0 and b"NULL required gradient" in err
+    rc, err = cr.call(cr.backward(family="raw", raw_grads=dict(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_shs_res=16)), opts)
+    assert rc < 0 and b"d_shs_res" in err
 
 
 def test_prealloc_callback_hands_out_what_fits_and_nothing_else():

@@ -61,7 +61,7 @@ def test_new_symbols_are_declared_and_exported(rast):
         assert n in rast._C.EXPORTS and hasattr(raw, n), n
         assert getattr(L, n).argtypes is not None
     assert "gsrast_densify_group" in text
-    assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 5
+    assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
     assert C.sizeof(rast._C.DensifyGroupStruct) == 6 * C.sizeof(C.c_void_p) + 2 * C.sizeof(C.c_int)
     b = [L.gsrast_densify_scratch_bytes(p) for p in (-1, 0, 1, 70001, 3_000_000)]
     assert b[0] == b[1] > 0 and all(y >= x for x, y in zip(b, b[1:])) and all(x % 256 == 0 for x in b)

@@ -713,7 +713,7 @@ def test_grad_arena_contract(scenes, rast, gpu):
 
 
 def test_two_threads_two_streams_different_options(orc, scenes, rast, gpu):
-    """The C ABI is reentrant (include/gsrast.h, gsrast_forward_ex / gsrast_backward_ex): two host threads on two streams, each
+    """The C ABI is reentrant (include/gsrast.h, gsrast_render_forward / gsrast_render_backward): two host threads on two streams, each
     with its OWN options (thread A: the reference's literal lists + instance-level binning + 2 pixels per lane in the backward;
     thread B: product defaults), interleaved for many iterations, reproduce their single-threaded results bit for bit (forward)
     and within the float-atomic band (backward)."""

@@ -1,4 +1,4 @@
-"""-m gpu: the raw-parameter entry points (include/gsrast.h: gsrast_forward_raw / gsrast_backward_raw, module GaussianRasterizerRaw) --
+"""-m gpu: the raw-parameter entry points (include/gsrast.h: GSRAST_FAMILY_RAW call records, module GaussianRasterizerRaw) --
 SURVEY.md 8f rank 3 as written: the activation / deformation epilogue of scene/saro_gaussian.py:807-847 (activations :39-47) fused
 into the per-Gaussian kernels, the [P,16,3] coefficient tensor never materialised.
 

@@ -1,4 +1,4 @@
-"""-m gpu: anti-aliased rendering (antialiasing=True; include/gsrast.h: GSRAST_RENDER_ANTIALIAS, the gsrast_*_flags entry points).
+"""-m gpu: anti-aliased rendering (antialiasing=True; include/gsrast.h: GSRAST_RENDER_ANTIALIAS, the flags word of the call records).
 
     o_eff = o * comp,   comp = sqrt(max(0.000025, det cov2D / det(cov2D + 0.3 I)))      (cov2D before the dilation)
 
@@ -91,15 +91,14 @@ def _cov6(sc):
 
 
 # ---- 1. the default path ------------------------------------------------------------------------------------------------------------------
-def test_default_path_and_flags_zero_are_todays_calls(scenes, rast, gpu, monkeypatch):
-    """antialiasing=False is today's call; gsrast_*_flags with 0 / AUX is gsrast_*_ex / _aux: outputs bitwise, gradients within the
-    plain backward's own run-to-run spread (its float atomics)."""
+def test_default_path_and_flags_zero_are_todays_calls(scenes, rast, gpu):
+    """antialiasing=False is today's call, with the flags word 0 / AUX: outputs bitwise, gradients within the plain backward's own
+    run-to-run spread (its float atomics)."""
     P, W, H = 100_000, 800, 800
     sc, cam, rs = _setup(scenes, rast, gpu, P, W, H)
     g = _t(scenes.upstream_grad(H, W, 1), gpu)
     rng = np.random.default_rng(2)
     gD, gA = _t(rng.normal(size=(1, H, W)) / (H * W), gpu), _t(rng.normal(size=(1, H, W)) / (H * W), gpu)
-    L = rast._C.lib()
 
     def run(aux, kw):
         t = _leaves(sc, gpu); m2 = torch.zeros((P, 3), device=gpu, requires_grad=True)
@@ -112,17 +111,7 @@ def test_default_path_and_flags_zero_are_todays_calls(scenes, rast, gpu, monkeyp
 
     for aux in (False, True):
         base, base2 = run(aux, {}), run(aux, {})
-        runs = [run(aux, dict(antialiasing=False))]
-        fwd = (L.gsrast_forward_flags, L.gsrast_backward_flags)
-        flag = rast._C.RENDER_AUX if aux else 0
-        with monkeypatch.context() as mp:      # today's entry points answered by the flags family
-            if aux:
-                mp.setattr(L, "gsrast_forward_aux", lambda *a: fwd[0](a[0], a[1], flag, *a[2:]))
-                mp.setattr(L, "gsrast_backward_aux", lambda *a: fwd[1](a[0], flag, *a[1:]))
-            else:
-                mp.setattr(L, "gsrast_forward_ex", lambda *a: fwd[0](a[0], a[1], 0, *a[2:], None, None))
-                mp.setattr(L, "gsrast_backward_ex", lambda *a: fwd[1](a[0], 0, *a[1:], None, None))
-            runs.append(run(aux, {}))
+        runs = [run(aux, dict(antialiasing=False)), run(aux, {})]
         for out, gr, m in runs:
             for k in range(len(out)):
                 assert np.array_equal(_bits(out[k]), _bits(base[0][k])), (aux, k)

@@ -1,5 +1,5 @@
-"""-m gpu: the differentiable alpha and accumulated-depth outputs (return_aux=True; include/gsrast.h: gsrast_forward_aux /
-gsrast_backward_aux and the raw pair).
+"""-m gpu: the differentiable alpha and accumulated-depth outputs (return_aux=True; include/gsrast.h: GSRAST_RENDER_AUX,
+both families).
 
     acc_depth = sum_i alpha_i T_i z_i     alpha = 1 - T_final
 

@@ -1,7 +1,7 @@
-"""CPU: camera-pose gradients (include/gsrast.h: GSRAST_RENDER_POSEGRAD, gsrast_backward_flags_pose / gsrast_backward_raw_flags_pose;
+"""CPU: camera-pose gradients (include/gsrast.h: GSRAST_RENDER_POSEGRAD, dL_dcamera / pose_scratch of gsrast_backward_call;
 `camera_grads=` of the Python package).  tests/posegrad_math.py -- the fp64 renderer with the camera as leaf tensors that
 tests/test_gpu_posegrad.py compares the kernels with -- is pinned to tests/math_renderer.py, satisfies the identities the function
-itself implies and agrees with finite differences; the new symbols are declared, exported and bound, the backward's plan reports the
+itself implies and agrees with finite differences; the scratch size is declared, exported and bound, the backward's plan reports the
 decision and every refusal is produced before any device work; the package knows the keyword."""
 import ctypes as C
 import os
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import math_renderer as mr
+import capi_records as cr
 import posegrad_math as pm
 import test_gpu_independent as tgi
 
@@ -140,18 +141,11 @@ def L(rast):
 
 
 def test_symbols_are_declared_exported_and_bound(rast, L):
-    src = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n, sib in (("gsrast_backward_flags_pose", "gsrast_backward_flags_abs"), ("gsrast_backward_raw_flags_pose", "gsrast_backward_raw_flags_abs")):
-        assert re.search(r"\bint\s+" + n + r"\s*\(", text), f"{n} not declared in gsrast.h"
-        assert hasattr(raw, n) and n in rast._C.EXPORTS
-        assert getattr(L, n).argtypes == list(getattr(L, sib).argtypes) + [C.c_void_p, C.c_void_p]      # the _abs symbol + output + scratch
-        assert getattr(L, n).restype is C.c_int
+    """(The record's pose fields and the flag's value: tests/test_capi_abi.py.)"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     assert re.search(r"\bsize_t\s+gsrast_pose_scratch_bytes\s*\(\s*int\s+P\s*\)", text) and "gsrast_pose_scratch_bytes" in rast._C.EXPORTS
-    assert re.search(r"#define\s+GSRAST_RENDER_POSEGRAD\s+0x8u\b", src)
-    assert rast._C.RENDER_POSEGRAD == 8 and rast._C.CAMERA_FLOATS == 35
-    assert L.gsrast_abi_version() == 5      # additive: the version does not move
+    assert hasattr(C.CDLL(rast._C.LIB_PATH), "gsrast_pose_scratch_bytes")
+    assert rast._C.CAMERA_FLOATS == 35
     # one 128-byte row per workgroup of the larger grid (128 Gaussians each); the state buffers do not grow with the feature
     assert [L.gsrast_pose_scratch_bytes(p) for p in (1, 128, 129, 1500)] == [128, 128, 256, 12 * 128]
     assert L.gsrast_pose_scratch_bytes(0) > 0
@@ -179,7 +173,7 @@ def test_backward_plan_reports_the_pose_sums(L, rast):
                 full = (C.c_int * 7)(1000, 3, 5000, 64, 64, kind | (16 if extra == AUX else 0) | SYM | OUT | SCR, 1)
                 plain, sym, pose = fn(C.byref(opts), extra, base, None), fn(C.byref(opts), extra, (C.c_int * 7)(*base[:5], base[5] | SYM, 1), None), fn(C.byref(opts), extra | POSE, full, None)
                 assert plain >= 0 and not plain & (1 << 28)
-                assert sym == plain                           # the new symbol without the bit and with NULL pointers IS the old call
+                assert sym == plain                           # the longer record without the bit and with NULL pointers IS the shorter one's call
                 assert pose == plain | (1 << 28)              # bit 28, and no other decision moves
     opts.backward_phase = 0
     # the refusals, one text each, before any device work
@@ -193,49 +187,46 @@ def test_backward_plan_reports_the_pose_sums(L, rast):
 
 
 def test_bad_arguments_fail_before_any_device_work(L, rast):
-    """The same refusals through the exported symbols (pointers that would fault if anything touched them)."""
+    """The same refusals through the exported entry point (pointers that would fault if anything touched them)."""
     _C = rast._C
-    one = C.c_void_p(16)
+    one = cr.ONE
     AA, ABS, POSE = _C.RENDER_ANTIALIAS, _C.RENDER_ABSGRAD, _C.RENDER_POSEGRAD
     opts = _C.OptionsStruct()
     L.gsrast_options_init(C.byref(opts))
-    o, err = C.byref(opts), L.gsrast_last_error
 
-    def dense(sym, P, flags, *tail):
-        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, one, one, None, one, 1.0, one, None, one, one, one, 0.5, 0.5, one,
-                               one, one, one, one, one, None, one, None, one, None, one, one, one, None, None, None, *tail)
+    def call(family, size, P, flags, sink=None, camera=None, scratch=None):
+        return cr.call(cr.backward(P, flags, family, size=size, dL_dmean2D_abs=sink, dL_dcamera=camera, pose_scratch=scratch), opts)
 
-    ins = _C.RawInputsStruct(xyz=16, rotation=16, scaling=16, opacity_logit=16, features_dc=16, features_rest=16)
-    gr = _C.RawGradsStruct(dL_dmean2D=16, d_xyz=16, d_rotation=16, d_scaling=16, d_opacity_logit=16, d_features_dc=16, d_features_rest=16)
-
-    def raw(sym, P, flags, *tail):
-        return getattr(L, sym)(o, flags, P, 3, 16, 5, one, 64, 64, C.byref(ins), 1.0, one, one, one, 1.0, 1.0, one, one, one, one, one,
-                               C.byref(gr), None, None, None, *tail)
-
-    for call, name in ((dense, "gsrast_backward_flags"), (raw, "gsrast_backward_raw_flags")):
+    for family in ("dense", "raw"):
         for fl in (POSE, POSE | AA):
-            assert call(name + "_pose", 10, fl, None, None, one) == -1 and b"NULL dL_dcamera" in err()
-            assert call(name + "_pose", 10, fl, None, one, None) == -1 and b"NULL pose_scratch" in err()
-            # every other symbol refuses the bit as an unknown one
-            assert call(name, 10, fl) == -1 and b"unknown bits" in err()
-            assert call(name + "_abs", 10, fl, None) == -1 and b"unknown bits" in err()
+            rc, err = call(family, "full", 10, fl, None, None, one)
+            assert rc == -1 and b"NULL dL_dcamera" in err
+            rc, err = call(family, "full", 10, fl, None, one, None)
+            assert rc == -1 and b"NULL pose_scratch" in err
+            # every shorter record refuses the bit as an unknown one
+            for size in ("min", "abs"):
+                rc, err = call(family, size, 10, fl)
+                assert rc == -1 and b"unknown bits" in err
         for fl in (0, AA):
-            assert call(name + "_pose", 10, fl, None, one, one) == -1 and b"without GSRAST_RENDER_POSEGRAD" in err()
-            assert call(name + "_pose", 10, fl, None, one, None) == -1 and b"without GSRAST_RENDER_POSEGRAD" in err()
-        # the _abs rules hold on the new symbols
-        assert call(name + "_pose", 10, POSE | ABS, None, one, one) == -1 and b"NULL dL_dmean2D_abs" in err()
-        assert call(name + "_pose", 10, POSE, one, one, one) == -1 and b"without GSRAST_RENDER_ABSGRAD" in err()
-        assert call(name + "_pose", 10, POSE | 0x10, None, one, one) == -1 and b"unknown bits" in err()
+            for scratch in (one, None):
+                rc, err = call(family, "full", 10, fl, None, one, scratch)
+                assert rc == -1 and b"without GSRAST_RENDER_POSEGRAD" in err
+        # the absgrad rules hold on the full record
+        rc, err = call(family, "full", 10, POSE | ABS, None, one, one)
+        assert rc == -1 and b"NULL dL_dmean2D_abs" in err
+        rc, err = call(family, "full", 10, POSE, one, one, one)
+        assert rc == -1 and b"without GSRAST_RENDER_ABSGRAD" in err
+        rc, err = call(family, "full", 10, POSE | 0x10, None, one, one)
+        assert rc == -1 and b"unknown bits" in err
         # a good combination reaches the ordinary checks (here: the negative P), with and without the bit
-        assert call(name + "_pose", -1, POSE, None, one, one) == -1 and b"POSEGRAD" not in err() and b"unknown bits" not in err()
-        assert call(name + "_pose", -1, 0, None, None, None) == -1 and b"POSEGRAD" not in err()
-        assert call(name + "_pose", 0, 0, None, None, None) == 0      # nothing to do, no device touched
+        rc, err = call(family, "full", -1, POSE, None, one, one)
+        assert rc == -1 and b"POSEGRAD" not in err and b"unknown bits" not in err
+        rc, err = call(family, "full", -1, 0)
+        assert rc == -1 and b"POSEGRAD" not in err
+        assert call(family, "full", 0, 0)[0] == 0      # nothing to do, no device touched
     # no forward knows the bit
-    ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-    cb = ALLOC(lambda ctx, n: None)
-    rc = L.gsrast_forward_flags(None, o, POSE, cb, None, cb, None, cb, None, 10, 3, 16, one, 64, 64, one, one, None, one, one, 1.0, one,
-                                None, one, one, one, 0.5, 0.5, 0, one, one, one, None, None, None)
-    assert rc == -1 and b"unknown bits" in err()
+    rc, err = cr.call(cr.forward(10, POSE), opts)
+    assert rc == -1 and b"unknown bits" in err
 
 
 def test_the_package_knows_the_keyword(rast):

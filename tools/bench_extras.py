@@ -432,7 +432,7 @@ def iteration_row(rast, scenes, dev, P, W, H, deg):
     rc = raw()
     opt_c = fused_adam.GaussianAdam([{"params": [rc[k]], "lr": lr[k] * inv if k != "f_rest" else lr[k], "name": k} for k in rc], eps=1e-15)
 
-    def fused():        # the epilogue INSIDE the per-Gaussian kernels (gsrast_forward_raw / gsrast_backward_raw)
+    def fused():        # the epilogue INSIDE the per-Gaussian kernels (GSRAST_FAMILY_RAW call records)
         color, _, _ = raster_raw(rc["xyz"], m2, rc["rotation"], rc["scaling"], rc["opacity"], rc["f_dc"], rc["f_rest"])
         loss = fused_loss.l1_dssim_loss(color, gt, 0.2)
         opt_c.zero_grad(); m2.grad = None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Where the host's time goes in ONE per-call synchronised step (bench.py's headline protocol), development helper:
    python tools/sync_probe.py [P=3e6] [poses=8] [steps=200] [option=value ...]
-Wraps the two C entry points the step goes through (gsrast_forward_flags / gsrast_backward_flags: the ones the binding calls) and prints medians of: Python before the forward's C call, the forward's C call
+Wraps the two C entry points the step goes through (gsrast_render_forward / gsrast_render_backward: the ones the binding calls) and prints medians of: Python before the forward's C call, the forward's C call
 (launches + the spin for the instance counts), Python between the two C calls (autograd), the backward's C call, and from the
 backward's return to the end of torch.cuda.synchronize()."""
 import os
@@ -36,8 +36,8 @@ class Wrap:
         return r
 
 
-L.gsrast_forward_flags = Wrap(L.gsrast_forward_flags, "fwd")
-L.gsrast_backward_flags = Wrap(L.gsrast_backward_flags, "bwd")
+L.gsrast_render_forward = Wrap(L.gsrast_render_forward, "fwd")
+L.gsrast_render_backward = Wrap(L.gsrast_render_backward, "bwd")
 dev = torch.device("cuda:0")
 wl = bench.Workload(rast, scenes, P, 1920, 1080, 3, 0, V, dev, poses=V)
 rows = []
