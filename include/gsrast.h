@@ -629,6 +629,40 @@ int gsrast_contrib_stats(const gsrast_options* options, int P, int R, int width,
                          const float* pixel_weights /* [H][W] or NULL */, float* stats /* [P][4] */,
                          char* scratch, void* stream);
 
+/* Per-Gaussian feature vectors blended with the weights of one finished forward, and the gradients of that blend (no counterpart in the
+ * reference; gsplat renders `colors` of any width): semantic / language features, decoder features, motion, normals, uncertainty.
+ *
+ * Definition.  Pair (pixel p, Gaussian i) CONTRIBUTES exactly as defined for gsrast_contrib_stats above; its weight is w_ip = alpha_ip T_ip,
+ * with the opacity the state carries (the GSRAST_RENDER_ANTIALIAS compensation included).
+ *     feature_map[c][p] = sum over contributing i of w_ip * features[i][c]          (no background term: composite with 1 - alpha of
+ *                                                                                    GSRAST_RENDER_AUX if one is wanted)
+ * features is [P][C] row-major float32, feature_map [C][H][W] planar; 1 <= C <= GSRAST_FEATURES_MAX_C.  Every pixel of the map is written,
+ * 0 where nothing contributes.  The calls have no flags; of the options only exp_mode is read (pass the forward's; NULL: the process
+ * defaults).  Both replay the blend from the state (csrc/gsrast_features.h), in passes of up to 32 channels.
+ *
+ * gsrast_features_forward is valid once the render forward that filled the three state buffers has been enqueued on `stream`.
+ *
+ * gsrast_features_backward takes dL_dfeature_map [C][H][W] and
+ *   - OVERWRITES dL_dfeatures [P][C]:  dL/dfeatures[i][c] = sum_p w_ip dL_dfeature_map[c][p]  (rows of Gaussians nobody consumed: exactly 0);
+ *   - ADDS the map's part of the screen-space mean, conic and opacity gradient sums to floats 0-5 of the Gaussians' gradient records
+ *     inside geom_buffer, in the units the blend backward writes them (dL/dalpha_ip = T_ip sum_c dL_dfeature_map[c][p] (features[i][c] - A_c),
+ *     A_c the blend behind i; the 0.99 clamp passes gradients through).  Nothing else of the record is touched.
+ * It is therefore valid only BETWEEN a gsrast_render_backward with options.backward_phase = 1 and one with backward_phase = 2 on the same
+ * state and stream: the window in which the records exist and have not been consumed.  The second call's mean, covariance, opacity, scale,
+ * rotation (and GSRAST_RENDER_POSEGRAD camera) gradients then include the feature map's loss; dL_dmean2D_abs (GSRAST_RENDER_ABSGRAD) does not.
+ *
+ * GSRAST_E_ARG before any device work: C outside 1..GSRAST_FEATURES_MAX_C, P < 0 or R < 0, a zero-size image, and with P > 0 a NULL state
+ * buffer (binning_buffer only when R > 0); a NULL features, feature_map, dL_dfeature_map or dL_dfeatures; a bad exp_mode.  P == 0: the
+ * forward writes a zero map, the backward nothing; neither launches a kernel.  Kernels "features_fwd" and "features_bwd" of the profile table. */
+#define GSRAST_FEATURES_MAX_C 64
+int gsrast_features_forward(const gsrast_options* options, int P, int R, int C, int width, int height,
+                            const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                            const float* features /* [P][C] */, float* feature_map /* [C][H][W] */, void* stream);
+int gsrast_features_backward(const gsrast_options* options, int P, int R, int C, int width, int height,
+                             char* geom_buffer /* gradient records: floats 0-5 are ADDED to */, const char* binning_buffer, const char* image_buffer,
+                             const float* features /* [P][C] */, const float* dL_dfeature_map /* [C][H][W] */,
+                             float* dL_dfeatures /* [P][C], overwritten */, void* stream);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

@@ -19,6 +19,7 @@
 #include "gsrast_binning.h"
 #include "gsrast_blend.h"
 #include "gsrast_contrib.h"
+#include "gsrast_features.h"
 #include "gsrast_loss.h"
 #include "gsrast_epilogue.h"
 #include "gsrast_adam.h"
@@ -141,7 +142,7 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
-                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_COUNT };
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_COUNT };
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
@@ -149,7 +150,8 @@ const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "sca
                                             "late_rows_zero" /* list cut: the late Gaussians' zero rows, on the side stream beside the blend backward */,
                                             "grec_zero_touched" /* the consumed Gaussians' gradient records zeroed behind the forward's last blend */,
                                             "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */,
-                                            "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */ };
+                                            "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */,
+                                            "features_fwd", "features_bwd" /* csrc/gsrast_features.h: gsrast_features_forward / _backward (one entry per call: all its passes) */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -2183,6 +2185,85 @@ int gsrast_contrib_stats(const gsrast_options* options, int P, int R, int width,
         ProfScope ps(K_CONTRIB_FINISH, s);
         contrib_finish_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, a_sum, a_max, a_cnt, a_top, reinterpret_cast<float4*>(stats));
         GS_LAUNCHED("contrib_finish");
+    }
+    return GSRAST_OK;
+}
+
+// ---- per-Gaussian feature vectors through the blend of a finished forward, and back (gsrast_features.h) ------------------------------
+namespace {
+// What the two calls refuse alike, before any device work (one text each); fwd: the text names features_forward, else features_backward
+const char* features_refusal(bool fwd, int P, int R, int C, int width, int height)
+{
+    if (C < 1 || C > GSRAST_FEATURES_MAX_C) return fwd ? "features_forward: C must be 1..64" : "features_backward: C must be 1..64";
+    if (P < 0 || R < 0) return fwd ? "features_forward: negative P or R" : "features_backward: negative P or R";
+    if (width <= 0 || height <= 0) return fwd ? "features_forward: zero-size image" : "features_backward: zero-size image";
+    return nullptr;
+}
+// The chunk of the pass that starts at channel c0: the smallest instantiated width that holds what is left, 32 at most
+inline int features_chunk(int C, int c0) { const int rem = C - c0; return rem > 16 ? 32 : rem > 8 ? 16 : rem > 4 ? 8 : 4; }
+} // namespace
+
+int gsrast_features_forward(const gsrast_options* options, int P, int R, int C, int width, int height, const char* geom_buffer,
+                            const char* binning_buffer, const char* image_buffer, const float* features, float* feature_map, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = features_refusal(true, P, R, C, width, height)) return fail(GSRAST_E_ARG, e);
+    if (!feature_map) return fail(GSRAST_E_ARG, "features_forward: NULL feature_map");
+    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer))) return fail(GSRAST_E_ARG, "features_forward: NULL state buffer");
+    if (P > 0 && !features) return fail(GSRAST_E_ARG, "features_forward: NULL features");
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "features_forward: exp_mode must be 0, 1 or 2");
+    // (no Gaussian, or no instance: nothing was blended)
+    if (P == 0 || R == 0) { GS_HIP(hipMemsetAsync(feature_map, 0, (size_t)C * (size_t)width * (size_t)height * sizeof(float), s)); return GSRAST_OK; }
+    const GeomLayout GL = geom_layout((size_t)P);
+    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
+    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    ProfScope ps(K_FEATURES_FWD, s);
+    for (int c0 = 0; c0 < C;) {
+        const int ch = features_chunk(C, c0);
+        // the list in force, resolved as gsrast_contrib_stats resolves it
+        pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { pick_int<4, 8, 16, 32>(ch, [&](auto chunk) {
+            features_fwd_kernel<decltype(mode)::value, decltype(chunk)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
+                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
+                at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), features, C, c0, feature_map);
+        }); });
+        GS_LAUNCHED("features_fwd");
+        c0 += ch;
+    }
+    return GSRAST_OK;
+}
+
+int gsrast_features_backward(const gsrast_options* options, int P, int R, int C, int width, int height, char* geom_buffer,
+                             const char* binning_buffer, const char* image_buffer, const float* features, const float* dL_dfeature_map,
+                             float* dL_dfeatures, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = features_refusal(false, P, R, C, width, height)) return fail(GSRAST_E_ARG, e);
+    if (!dL_dfeature_map) return fail(GSRAST_E_ARG, "features_backward: NULL dL_dfeature_map");
+    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer))) return fail(GSRAST_E_ARG, "features_backward: NULL state buffer");
+    if (P > 0 && !features) return fail(GSRAST_E_ARG, "features_backward: NULL features");
+    if (P > 0 && !dL_dfeatures) return fail(GSRAST_E_ARG, "features_backward: NULL dL_dfeatures");
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "features_backward: exp_mode must be 0, 1 or 2");
+    if (P == 0) return GSRAST_OK;
+    GS_HIP(hipMemsetAsync(dL_dfeatures, 0, (size_t)P * (size_t)C * sizeof(float), s));
+    if (R == 0) return GSRAST_OK;             // (no instance: nothing was blended)
+    const GeomLayout GL = geom_layout((size_t)P);
+    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
+    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    ProfScope ps(K_FEATURES_BWD, s);
+    for (int c0 = 0; c0 < C;) {
+        const int ch = features_chunk(C, c0);
+        pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { pick_int<4, 8, 16, 32>(ch, [&](auto chunk) {
+            features_bwd_kernel<decltype(mode)::value, decltype(chunk)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
+                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
+                at<float>(image_buffer, IL.final_T), at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), features, C, c0, dL_dfeature_map,
+                at<float>(geom_buffer, GL.grec), dL_dfeatures);
+        }); });
+        GS_LAUNCHED("features_bwd");
+        c0 += ch;
     }
     return GSRAST_OK;
 }

@@ -42,6 +42,7 @@ EXPORTS = (
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event", "gsrast_debug_forward_plan", "gsrast_debug_backward_plan",
     "gsrast_render_forward", "gsrast_render_backward", "gsrast_alloc_prealloc", "gsrast_pose_scratch_bytes",
     "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
+    "gsrast_features_forward", "gsrast_features_backward",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -50,6 +51,7 @@ RENDER_ANTIALIAS = 0x2
 RENDER_ABSGRAD = 0x4      # backward records whose struct_size covers dL_dmean2D_abs
 RENDER_POSEGRAD = 0x8     # backward records whose struct_size covers dL_dcamera / pose_scratch
 FAMILY_DENSE, FAMILY_RAW = 0, 1
+FEATURES_MAX_C = 64       # include/gsrast.h: GSRAST_FEATURES_MAX_C
 CAMERA_FLOATS = 35        # dL_dcamera: dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
 
 
@@ -199,6 +201,9 @@ def lib() -> C.CDLL:
     L.gsrast_contrib_scratch_bytes.argtypes = [ci]
     L.gsrast_contrib_stats.restype = ci
     L.gsrast_contrib_stats.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_features_forward.restype = L.gsrast_features_backward.restype = ci
+    L.gsrast_features_forward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.gsrast_features_backward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_binning_bytes.restype = C.c_size_t
     L.gsrast_binning_bytes.argtypes = [ci, ci, ci]
     L.gsrast_image_bytes.restype = C.c_size_t
@@ -672,7 +677,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                  first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                  dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                 absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False):
+                                 absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
@@ -683,7 +688,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     both phases of a two-phase backward).  `absgrad`: a [P,2] sink (check_absgrad) that the call overwrites with the absolute
     screen-space gradient (include/gsrast.h: GSRAST_RENDER_ABSGRAD); it is no gradient of anything and never lives in a GradArena.
     `camera_grads`: the tuple continues with ``(dL_dviewmatrix[4,4], dL_dprojmatrix[4,4], dL_dcampos[3])`` (include/gsrast.h:
-    GSRAST_RENDER_POSEGRAD); without it the call and its result are what they were before the flag existed."""
+    GSRAST_RENDER_POSEGRAD); without it the call and its result are what they were before the flag existed.
+    `features`: (features [P,C], dL_dfeature_map [C,H,W]) of a feature map rendered from this state (features_forward) whose gradient is
+    not zero -- the backward then runs in two phases around gsrast_features_backward, every returned gradient includes the map's loss
+    (`absgrad` does not) and the tuple ends with ``dL_dfeatures[P,C]`` (behind the camera's); without it the call is what it was."""
     dev = _require_gpu(means3D)
     P = int(means3D.shape[0])
     check_absgrad(absgrad, P, dev)
@@ -723,6 +731,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dscales = out("scales", (P, 3), not use_sr)
     dL_drotations = out("rotations", (P, 4), not use_sr)
     camera = _pose_buffers(P, dev) if camera_grads else None
+    between, dL_dfeatures = _features_between(features, ar, P, int(R), W, H, geomBuffer, binningBuffer, imageBuffer, options, dev)
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
@@ -734,10 +743,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 dL_dmean2D=dL_dmeans2D.data_ptr(), dL_dopacity=dL_dopacity.data_ptr(), dL_dcolor=_ptr(dL_dcolors), dL_dmean3D=dL_dmeans3D.data_ptr(), dL_dcov3D=_ptr(dL_dcov3D),
                 dL_dsh=ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscale=dL_dscales.data_ptr(), dL_drot=dL_drotations.data_ptr(), stream=_stream_of(dev),
                 dL_dacc_depth=aux[0], dL_dalpha=aux[1])
-            _run_backward(ar, lambda phase: _render_call(      # options travel per call: no process-wide switch is flipped
-                "gsrast_render_backward", (_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera), P, geomBuffer, dev)
+            call = lambda phase: _render_call(      # noqa: E731  (options travel per call: no process-wide switch is flipped)
+                "gsrast_render_backward", (_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera)
+            if between is None:
+                _run_backward(ar, call, P, geomBuffer, dev)
+            else:
+                _run_backward_around(call, between)
     grads = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    return grads if camera is None else grads + (_camera_result(camera),)
+    grads = grads if camera is None else grads + (_camera_result(camera),)
+    return grads if features is None else grads + (dL_dfeatures,)
 
 
 def check_absgrad(absgrad: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
@@ -818,6 +832,80 @@ def contrib_stats(contrib: torch.Tensor, pixel_weights: Optional[torch.Tensor], 
     return contrib
 
 
+def check_features(features: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
+    """The per-Gaussian feature vectors of `features=`: a contiguous float32 [P, C] tensor on the render's device, 1 <= C <= FEATURES_MAX_C
+    (None: not wanted).  It may require grad.  ValueError otherwise -- the library gets a pointer and would read P * C floats through it."""
+    if features is None:
+        return
+    if not isinstance(features, torch.Tensor):
+        raise ValueError(f"features must be a tensor or None (got {type(features).__name__})")
+    if features.ndim != 2 or int(features.shape[0]) != P:
+        raise ValueError(f"features must be [{P}, C] (got {list(features.shape)})")
+    if not 1 <= int(features.shape[1]) <= FEATURES_MAX_C:
+        raise ValueError(f"features must have 1..{FEATURES_MAX_C} channels (got {int(features.shape[1])})")
+    if features.dtype is not torch.float32:
+        raise ValueError(f"features must be float32 (got {features.dtype})")
+    if features.device != dev:
+        raise ValueError(f"features must live on {dev} (got {features.device})")
+    if not features.is_contiguous():
+        raise ValueError("features must be contiguous")
+
+
+def no_arena_for_features() -> None:
+    if _grad_arena is not None:
+        raise RuntimeError("features= is not supported with a GradArena installed (multi-GPU / view_parallel training): the arena drives the "
+                           "backward's two phases itself; uninstall it with _C.set_grad_arena(None) for renders that need a feature map")
+
+
+def features_forward(features: torch.Tensor, R: int, W: int, H: int, geomBuffer: torch.Tensor, binningBuffer: torch.Tensor,
+                     imageBuffer: torch.Tensor, *, options: Optional[dict] = None) -> torch.Tensor:
+    """gsrast_features_forward (include/gsrast.h) on the state a forward returned: feature_map [C,H,W] = sum_i alpha_i T_i features[i], over
+    the forward's own contributors, on the current stream behind everything the forward enqueued there.  `options`: the per-call options
+    of that forward (default: the calling thread's)."""
+    P = int(features.shape[0])
+    dev = _require_gpu(features)
+    check_features(features, P, dev)
+    Cn = int(features.shape[1])
+    out = torch.empty((Cn, int(H), int(W)), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib().gsrast_features_forward(C.byref(_options_struct(options=options)), P, int(R), Cn, int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+                                           _ptr(imageBuffer), _ptr(features), out.data_ptr(), _stream_of(dev))
+    if rc != 0:
+        raise _err(rc, "gsrast_features_forward")
+    return out
+
+
+def _run_backward_around(call, between) -> None:
+    """The backward of a render whose feature map has a gradient (never with an arena: _features_between): the two phases of call(phase)
+    around between(), on one call record -- only the options differ."""
+    call(1)                      # blend backward: the gradient records exist
+    between()                    # gsrast_features_backward adds the feature map's part to them
+    call(2)                      # the per-Gaussian backward consumes them
+
+
+def _features_between(features: Optional[tuple], ar, P: int, R: int, W: int, H: int, geomBuffer, binningBuffer, imageBuffer, options, dev):
+    """(what a backward with `features` = (features, dL_dfeature_map) runs between its two phases, the dL_dfeatures [P,C] it fills); (None,
+    None) without.  The call (gsrast_features_backward) adds the map's part to the gradient records phase 1 left and phase 2 consumes."""
+    if features is None:
+        return None, None
+    if ar is not None:
+        raise RuntimeError("a feature map's gradient cannot be served with a GradArena claimed by this backward")
+    feats, dL_dmap = features
+    check_features(feats, P, dev)
+    Cn = int(feats.shape[1])
+    if tuple(dL_dmap.shape) != (Cn, H, W):
+        raise RuntimeError(f"dL_dfeature_map must be [{Cn},{H},{W}] (got {list(dL_dmap.shape)})")
+    dL_dmap = _dev_f32(dL_dmap, "dL_dfeature_map", dev)
+    dL_dfeatures = torch.empty((P, Cn), dtype=torch.float32, device=dev)
+
+    def between():
+        rc = lib().gsrast_features_backward(C.byref(_options_struct(options=options)), P, R, Cn, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
+                                            _ptr(imageBuffer), _ptr(feats), dL_dmap.data_ptr(), _ptr(dL_dfeatures), _stream_of(dev))
+        if rc != 0:
+            raise _err(rc, "gsrast_features_backward")
+    return between, dL_dfeatures
+
+
 def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, antialiasing: bool):
     """A backward's (flags, (dL/dacc_depth, dL/dalpha) pointers, the tensors they point into): each gradient a contiguous fp32 [1,H,W]
     device tensor or None = zero; GSRAST_RENDER_AUX when either is given."""
@@ -883,11 +971,12 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                      first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                      dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                     absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False) -> dict:
+                                     absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
     rasterize_gaussians_backward; `antialiasing`, `absgrad`: as rasterize_gaussians_backward; `camera_grads`: also "camera", the
-    (dL_dviewmatrix, dL_dprojmatrix, dL_dcampos) of rasterize_gaussians_backward."""
+    (dL_dviewmatrix, dL_dprojmatrix, dL_dcampos) of rasterize_gaussians_backward; `features`: as rasterize_gaussians_backward, the result
+    then has "features" (dL_dfeatures [P,C])."""
     dev = _require_gpu(raw["xyz"])
     P = int(raw["xyz"].shape[0])
     check_absgrad(absgrad, P, dev)
@@ -928,6 +1017,9 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                         d_trbf=_ptr(g.get("trbf")), d_features_dc=p_dc, d_features_rest=p_rest, d_shs_res=_ptr(g.get("shs_res")),
                         d_sh_factor=p_fac)
     camera = _pose_buffers(P, dev) if camera_grads else None
+    between, dL_dfeatures = _features_between(features, ar, P, int(R), W, H, geomBuffer, binningBuffer, imageBuffer, options, dev)
+    if features is not None:
+        g["features"] = dL_dfeatures
     if P != 0:
         with _on_device(dev):
             radii_c = radii.contiguous()
@@ -936,8 +1028,12 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                 viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=_ptr(radii_c),
                 geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dpix=_ptr(dL_dout_color), raw_grads=C.pointer(gs),
                 stream=_stream_of(dev), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
-            _run_backward(ar, lambda phase: _render_call(
-                "gsrast_render_backward", (_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera), P, geomBuffer, dev)
+            call = lambda phase: _render_call(      # noqa: E731
+                "gsrast_render_backward", (_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera)
+            if between is None:
+                _run_backward(ar, call, P, geomBuffer, dev)
+            else:
+                _run_backward_around(call, between)
     if camera is not None:
         g["camera"] = _camera_result(camera)
     if keep["motion_res"] is not None:
