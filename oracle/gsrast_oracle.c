@@ -4,13 +4,15 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing under saro-gs_amd/ may import, link or call this file.
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, as the checker.
  *
- * PARITY PINNING STATUS: "parity unpinned" against a RUNNING reference -- pinned piecewise against everything reachable.
- *   The reference implementation of this path exists only as CUDA (.cu) sources that include
- *   <cuda.h>, "cuda_runtime.h", <cooperative_groups.h> and <cub/cub.cuh>; none of those headers
- *   exist in this image and the reference ships no tests or golden vectors for the path
- *   (SURVEY.md section 4).  It is therefore unbuildable here (no oracle/_ref) and this file is an independent
- *   restatement of the published algorithm, following the reference file:line cited at every
- *   function.  What pins it (DESIGN.md section 5 has the table):
+ * PARITY PINNING STATUS: pinned against the RUNNING reference kernels on eight small edge scenes, piecewise against everything else
+ *   reachable.  The reference implementation of this path exists only as CUDA (.cu) sources and ships no tests or golden vectors
+ *   (SURVEY.md section 4); this file is an independent restatement of the published algorithm, following the reference
+ *   file:line cited at every function.  What pins it (DESIGN.md section 5 has the table):
+ *     - against the reference's OWN KERNELS (RST/forward.cu, backward.cu, rasterizer_impl.cu compiled for gfx950 by
+ *       oracle/ref_build.py into oracle/_ref/, run on the MI355X): depths, means2D, cov3D, conic, rgb, clamp flags, tile counts,
+ *       sorted keys, point list and tile ranges BIT FOR BIT, the blend and all nine gradient arrays within the fp32 bars, on the six
+ *       edge cases of tests/edge_scenes.py and the two of tests/contrib_math.py -> tests/test_gpu_reference_kernels.py (-m gpu);
+ *       three of the cases recorded as tests/golden/ref_kernel_vectors.npz      -> tests/test_oracle_ref_kernels.py (every machine);
  *     - against the reference's OWN Python, imported by tests/golden/make_golden.py: SH colour (utils/sh_utils.py eval_sh), the
  *       camera-matrix conventions and the point projection (utils/graphics_utils.py, scene/cameras.py), cov3D -- packing,
  *       quaternion convention, R S S^T R^T, scale_modifier (utils/general_utils.py build_scaling_rotation / strip_symmetric as
@@ -20,7 +22,8 @@
  *       median depth, and ALL hand-derived backward formulas (this file's gradients equal autograd's to 1e-7 relative)
  *                                                                                      -> tests/test_oracle_independent.py;
  *     - finite differences of the forward reproduce the backward                      -> tests/test_oracle_grad.py.
- *   Not pinnable here: that the CUDA binary evaluates these formulas in exactly this association (FMA contraction).
+ *   Not pinned: full-size scenes against the reference's kernels, and nvcc's own code generation (its FMA contraction: the
+ *   reference kernels above are compiled by hipcc with -ffp-contract=off, as this file is).
  *
  * RST = /root/reference/submodules/gaussian_rasterization_ch3/cuda_rasterizer
  *

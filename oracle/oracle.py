@@ -2,9 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
 leg; never by the product package under saro-gs_amd/.  See the C file's header for what the
-oracle restates and for its pinning status (no running reference here; SH colour, camera conventions, point projection
-and cov3D pinned against the reference's own Python, everything else -- including every backward formula -- against an
-independent torch-autograd derivation, tests/test_oracle_independent.py).
+oracle restates and for its pinning status (forward intermediates, lists, blend and every backward tensor pinned against the
+reference's own kernels run on the MI355X, on eight small edge scenes -- oracle/ref_build.py, tests/test_gpu_reference_kernels.py,
+tests/test_oracle_ref_kernels.py; SH colour, camera conventions, point projection and cov3D against the reference's own Python;
+every formula against an independent torch-autograd derivation, tests/test_oracle_independent.py).
 """
 from __future__ import annotations
 

@@ -1,0 +1,4 @@
+// Forwarding header of the reference-kernel build (oracle/ref_build.py): the name the reference sources include, served by ROCm.
+#pragma once
+#include <hipcub/hipcub.hpp>
+namespace cub = hipcub;

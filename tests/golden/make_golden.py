@@ -11,6 +11,14 @@
 2. oracle_scene_*.npz -- small seeded scenes with the ORACLE's outputs (fp32 build for the
    bit-exact quantities, fp64 build for the gradients).  They guard against oracle drift and give
    the GPU tests a fixture that does not depend on the oracle library being rebuilt.
+3. ref_kernel_vectors.npz -- what the REFERENCE's own kernels wrote (oracle/_ref/libref_rasterizer.so, oracle/ref_build.py) for three of
+   the edge cases: outputs, intermediates, lists and all nine gradient arrays.  Needs the MI355X and the built library, not the tree:
+
+       python tests/golden/make_golden.py refkernels [OUT.npz]
+
+   It pins oracle/gsrast_oracle.c to reference-written numbers on every machine (tests/test_oracle_ref_kernels.py).  The inputs are
+   not stored: they regenerate from the cases' seeds, and their SHA-256 is recorded so that a drifted generator is told apart from a
+   drifted oracle.  Only data the kernels wrote is stored -- no reference source.
 """
 import importlib.util
 import os
@@ -115,6 +123,47 @@ def oracle_scenes():
         path = os.path.join(HERE, f"oracle_scene_{tag}.npz")
         np.savez_compressed(path, **d)
         print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def input_digest(packed, name):
+    """SHA-256 over one case's input arrays as tests/ref_kernels.pack_case lays them out."""
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(k for k in packed if k.startswith(name + "/")):
+        a = np.ascontiguousarray(packed[k])
+        h.update(k.encode() + str(a.dtype).encode() + str(a.shape).encode() + a.tobytes())
+    return h.hexdigest()
+
+
+def ref_kernel_vectors(out_path=None):
+    """Runs tests/ref_kernels.py once, as a child process, on ref_compare.GOLDEN_CASES and keeps everything it wrote."""
+    import subprocess
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_compare as rc
+    import ref_kernels
+    from oracle import ref_build
+    hashes = ref_build.source_hashes()
+    assert hashes is not None and os.path.exists(ref_kernels.LIB_PATH), "build oracle/_ref first (oracle/ref_build.py, needs the reference tree)"
+    names = list(rc.GOLDEN_CASES)
+    packed = {"names": np.array(names)}
+    for n in names:
+        t = rc.truth(n)
+        packed.update(ref_kernels.pack_case(n, t["r"]["sc"], t["r"]["cam"], t["c"]["deg"], t["r"]["g"]))
+    with tempfile.TemporaryDirectory() as d:
+        np.savez(os.path.join(d, "in.npz"), **packed)
+        subprocess.run([sys.executable, ref_kernels.__file__, os.path.join(d, "in.npz"), os.path.join(d, "out.npz")], check=True, timeout=180)
+        res = ref_kernels.unpack(np.load(os.path.join(d, "out.npz")), names)
+    out = {"names": np.array(names), "source_files": np.array(sorted(hashes)), "source_sha256": np.array([hashes[k] for k in sorted(hashes)])}
+    for n in names:
+        out[f"{n}/g_seed"] = np.int64(rc.truth(n)["r"]["g_seed"])
+        out[f"{n}/input_sha256"] = np.array(input_digest(packed, n))
+        out.update({f"{n}/{k}": v for k, v in res[n].items()})
+    path = out_path or os.path.join(HERE, "ref_kernel_vectors.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    assert size <= os.path.getsize(os.path.join(HERE, "oracle_scene_b.npz")), size      # no larger than the largest fixture there
+    print("wrote", path, size // 1024, "KiB")
 
 
 def _load_with_placeholders(name, path, absent, cuda_to_cpu=False):
@@ -240,6 +289,9 @@ def loss_vectors():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "focal":        # only the (round 3) focal fixture; the others stay as committed
         ref_focal_vectors()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "refkernels":   # only the reference-kernel fixture (MI355X); the others stay as committed
+        ref_kernel_vectors(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if os.path.isdir(REF):
         ref_python_vectors()
