@@ -557,19 +557,26 @@ def _render_call(entry: str, head: tuple, rec, flags: int, absgrad: Optional[tor
     return rc
 
 
+def _per_stream(cache: dict, P: int, dev: torch.device, make):
+    """cache's entry for (device, current stream, P), made by make() on its first use: scratch that one call at a time owns on its stream."""
+    k = (dev.index, int(_stream_of(dev) or 0), P)
+    v = cache.get(k)
+    if v is None:
+        if len(cache) > 16:
+            cache.clear()
+        v = cache[k] = make()
+    return v
+
+
 _pose_cache: dict = {}
+_contrib_cache: dict = {}
 
 
 def _pose_buffers(P: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
     """(the [35] float32 output, the scratch) of a backward with GSRAST_RENDER_POSEGRAD, kept per device, stream and P: both are fully
     overwritten by every such backward (zeroed here for P = 0, which makes no call), and the backward hands autograd a copy of the output."""
-    k = (dev.index, int(_stream_of(dev) or 0), P)
-    v = _pose_cache.get(k)
-    if v is None:
-        if len(_pose_cache) > 16:
-            _pose_cache.clear()
-        v = _pose_cache[k] = (torch.empty((CAMERA_FLOATS,), dtype=torch.float32, device=dev),
-                              torch.empty((int(lib().gsrast_pose_scratch_bytes(P)),), dtype=torch.uint8, device=dev))
+    v = _per_stream(_pose_cache, P, dev, lambda: (torch.empty((CAMERA_FLOATS,), dtype=torch.float32, device=dev),
+                                                  torch.empty((int(lib().gsrast_pose_scratch_bytes(P)),), dtype=torch.uint8, device=dev)))
     if P == 0:
         v[0].zero_()
     return v
@@ -672,6 +679,30 @@ def _run_backward(ar: Optional["GradArena"], call, P: int, geomBuffer: torch.Ten
         call(0)
 
 
+def _backward(rec: BackwardCallStruct, flags: int, ar: Optional["GradArena"], sh_grad_factors: bool, dev: torch.device, radii: torch.Tensor,
+              geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imageBuffer: torch.Tensor, options: Optional[dict], first_backward: bool,
+              absgrad: Optional[torch.Tensor], camera_grads: bool, features: Optional[tuple]):
+    """What the dense and the raw backward share behind their outputs (`rec`: the record with the family's inputs and outputs filled in; the
+    forward's state, the stream and the keyword-driven fields are filled here): the pose buffers, the feature map's step between the phases,
+    the call -- through _run_backward, or around that step -- and the results the keywords add: ((dL_dviewmatrix, dL_dprojmatrix,
+    dL_dcampos) or None, dL_dfeatures or None)."""
+    P = rec.P
+    camera = _pose_buffers(P, dev) if camera_grads else None
+    between, dL_dfeatures = _features_between(features, ar, P, rec.R, rec.width, rec.height, geomBuffer, binningBuffer, imageBuffer, options, dev)
+    if P != 0:
+        with _on_device(dev):
+            radii = radii.contiguous()
+            rec.radii, rec.geom_buffer, rec.binning_buffer, rec.image_buffer = _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer)
+            rec.stream = _stream_of(dev)
+            call = lambda phase: _render_call(      # noqa: E731  (options travel per call: no process-wide switch is flipped)
+                "gsrast_render_backward", (_options_struct(sh_grad_factors=sh_grad_factors, options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera)
+            if between is None:
+                _run_backward(ar, call, P, geomBuffer, dev)
+            else:
+                _run_backward_around(call, between)
+    return (None if camera is None else _camera_result(camera)), dL_dfeatures
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
@@ -730,47 +761,44 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     factors = ar is not None and ar.sh_factors      # dL_dsh is then only valid after sh_grad_combine(): the kernel writes this view's factor
     dL_dscales = out("scales", (P, 3), not use_sr)
     dL_drotations = out("rotations", (P, 4), not use_sr)
-    camera = _pose_buffers(P, dev) if camera_grads else None
-    between, dL_dfeatures = _features_between(features, ar, P, int(R), W, H, geomBuffer, binningBuffer, imageBuffer, options, dev)
-    if P != 0:
-        with _on_device(dev):
-            radii_c = radii.contiguous()
-            rec = BackwardCallStruct(
-                family=FAMILY_DENSE, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, means3D=_ptr(means3D), shs=_ptr(sh),
-                colors_precomp=_ptr(colors), scales=_ptr(scales), rotations=_ptr(rotations), cov3D_precomp=_ptr(cov3D_precomp), scale_modifier=float(scale_modifier),
-                viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=_ptr(radii_c),
-                geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dpix=_ptr(dL_dout_color),
-                dL_dmean2D=dL_dmeans2D.data_ptr(), dL_dopacity=dL_dopacity.data_ptr(), dL_dcolor=_ptr(dL_dcolors), dL_dmean3D=dL_dmeans3D.data_ptr(), dL_dcov3D=_ptr(dL_dcov3D),
-                dL_dsh=ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscale=dL_dscales.data_ptr(), dL_drot=dL_drotations.data_ptr(), stream=_stream_of(dev),
-                dL_dacc_depth=aux[0], dL_dalpha=aux[1])
-            call = lambda phase: _render_call(      # noqa: E731  (options travel per call: no process-wide switch is flipped)
-                "gsrast_render_backward", (_options_struct(sh_grad_factors=factors, options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera)
-            if between is None:
-                _run_backward(ar, call, P, geomBuffer, dev)
-            else:
-                _run_backward_around(call, between)
+    rec = BackwardCallStruct(
+        family=FAMILY_DENSE, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, means3D=_ptr(means3D), shs=_ptr(sh),
+        colors_precomp=_ptr(colors), scales=_ptr(scales), rotations=_ptr(rotations), cov3D_precomp=_ptr(cov3D_precomp), scale_modifier=float(scale_modifier),
+        viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy),
+        dL_dpix=_ptr(dL_dout_color), dL_dmean2D=_ptr(dL_dmeans2D), dL_dopacity=_ptr(dL_dopacity), dL_dcolor=_ptr(dL_dcolors), dL_dmean3D=_ptr(dL_dmeans3D), dL_dcov3D=_ptr(dL_dcov3D),
+        dL_dsh=ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscale=_ptr(dL_dscales), dL_drot=_ptr(dL_drotations), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
+    grad_camera, dL_dfeatures = _backward(rec, flags, ar, factors, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features)
     grads = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    grads = grads if camera is None else grads + (_camera_result(camera),)
+    grads = grads if grad_camera is None else grads + (grad_camera,)
     return grads if features is None else grads + (dL_dfeatures,)
+
+
+def _check_tensor(name: str, t, shapes: tuple, dev: torch.device, no_grad: Optional[str] = None, channels: Optional[tuple] = None) -> None:
+    """The one ladder of check_absgrad / check_contrib / check_features: `t` is a contiguous float32 tensor on `dev` in one of `shapes`
+    (an extent of None, printed as C: any -- then within `channels` = (lowest, highest)); `no_grad`: it must not require grad, and why.
+    ValueError otherwise."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor or None (got {type(t).__name__})")
+    if not any(len(s) == t.ndim and all(w is None or w == int(n) for w, n in zip(s, t.shape)) for s in shapes):
+        want = " or ".join("[" + ", ".join("C" if w is None else str(w) for w in s) + "]" for s in shapes)
+        raise ValueError(f"{name} must be {want} (got {list(t.shape)})")
+    if channels is not None and not channels[0] <= int(t.shape[-1]) <= channels[1]:
+        raise ValueError(f"{name} must have {channels[0]}..{channels[1]} channels (got {int(t.shape[-1])})")
+    if t.dtype is not torch.float32:
+        raise ValueError(f"{name} must be float32 (got {t.dtype})")
+    if t.device != dev:
+        raise ValueError(f"{name} must live on {dev} (got {t.device})")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if no_grad is not None and t.requires_grad:
+        raise ValueError(f"{name} {no_grad} (requires_grad must be False)")
 
 
 def check_absgrad(absgrad: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
     """The caller-owned sink of the absolute screen-space gradient: a contiguous float32 [P,2] tensor on the render's device (None: not
     wanted).  ValueError otherwise -- the library gets a pointer and would write P * 2 floats through it."""
-    if absgrad is None:
-        return
-    if not isinstance(absgrad, torch.Tensor):
-        raise ValueError(f"absgrad must be a tensor or None (got {type(absgrad).__name__})")
-    if tuple(absgrad.shape) != (P, 2):
-        raise ValueError(f"absgrad must be [{P}, 2] (got {list(absgrad.shape)})")
-    if absgrad.dtype is not torch.float32:
-        raise ValueError(f"absgrad must be float32 (got {absgrad.dtype})")
-    if absgrad.device != dev:
-        raise ValueError(f"absgrad must live on {dev} (got {absgrad.device})")
-    if not absgrad.is_contiguous():
-        raise ValueError("absgrad must be contiguous")
-    if absgrad.requires_grad:
-        raise ValueError("absgrad is a statistic the backward writes, not a differentiable tensor (requires_grad must be False)")
+    if absgrad is not None:
+        _check_tensor("absgrad", absgrad, ((P, 2),), dev, no_grad="is a statistic the backward writes, not a differentiable tensor")
 
 
 def check_contrib(contrib: Optional[torch.Tensor], pixel_weights: Optional[torch.Tensor], P: int, H: int, W: int, dev: torch.device) -> None:
@@ -782,36 +810,15 @@ def check_contrib(contrib: Optional[torch.Tensor], pixel_weights: Optional[torch
             raise ValueError("pixel_weights is only legal together with contrib")
         return
     for name, t, shapes in (("contrib", contrib, ((P, 4),)), ("pixel_weights", pixel_weights, ((H, W), (1, H, W)))):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a tensor or None (got {type(t).__name__})")
-        if tuple(t.shape) not in shapes:
-            raise ValueError(f"{name} must be {' or '.join(str(list(x)) for x in shapes)} (got {list(t.shape)})")
-        if t.dtype is not torch.float32:
-            raise ValueError(f"{name} must be float32 (got {t.dtype})")
-        if t.device != dev:
-            raise ValueError(f"{name} must live on {dev} (got {t.device})")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if t.requires_grad:
-            raise ValueError(f"{name} is not a differentiable tensor (requires_grad must be False)")
+        if t is not None:
+            _check_tensor(name, t, shapes, dev, no_grad="is not a differentiable tensor")
     if contrib.numel() != 0 and contrib.device.type != "meta" and contrib.data_ptr() % 16 != 0:
         raise ValueError("contrib must be 16-byte aligned (rows of a fresh or row-sliced [*, 4] float32 tensor are)")
 
 
-_contrib_cache: dict = {}
-
-
 def _contrib_scratch(P: int, dev: torch.device) -> torch.Tensor:
     """The accumulators of gsrast_contrib_stats, kept per device, stream and P (the call zeroes them itself and leaves them zeroed)."""
-    k = (dev.index, int(_stream_of(dev) or 0), P)
-    v = _contrib_cache.get(k)
-    if v is None:
-        if len(_contrib_cache) > 16:
-            _contrib_cache.clear()
-        v = _contrib_cache[k] = torch.empty((int(lib().gsrast_contrib_scratch_bytes(P)),), dtype=torch.uint8, device=dev)
-    return v
+    return _per_stream(_contrib_cache, P, dev, lambda: torch.empty((int(lib().gsrast_contrib_scratch_bytes(P)),), dtype=torch.uint8, device=dev))
 
 
 def contrib_stats(contrib: torch.Tensor, pixel_weights: Optional[torch.Tensor], R: int, W: int, H: int, geomBuffer: torch.Tensor,
@@ -835,20 +842,8 @@ def contrib_stats(contrib: torch.Tensor, pixel_weights: Optional[torch.Tensor], 
 def check_features(features: Optional[torch.Tensor], P: int, dev: torch.device) -> None:
     """The per-Gaussian feature vectors of `features=`: a contiguous float32 [P, C] tensor on the render's device, 1 <= C <= FEATURES_MAX_C
     (None: not wanted).  It may require grad.  ValueError otherwise -- the library gets a pointer and would read P * C floats through it."""
-    if features is None:
-        return
-    if not isinstance(features, torch.Tensor):
-        raise ValueError(f"features must be a tensor or None (got {type(features).__name__})")
-    if features.ndim != 2 or int(features.shape[0]) != P:
-        raise ValueError(f"features must be [{P}, C] (got {list(features.shape)})")
-    if not 1 <= int(features.shape[1]) <= FEATURES_MAX_C:
-        raise ValueError(f"features must have 1..{FEATURES_MAX_C} channels (got {int(features.shape[1])})")
-    if features.dtype is not torch.float32:
-        raise ValueError(f"features must be float32 (got {features.dtype})")
-    if features.device != dev:
-        raise ValueError(f"features must live on {dev} (got {features.device})")
-    if not features.is_contiguous():
-        raise ValueError("features must be contiguous")
+    if features is not None:
+        _check_tensor("features", features, ((P, None),), dev, channels=(1, FEATURES_MAX_C))
 
 
 def no_arena_for_features() -> None:
@@ -1016,26 +1011,16 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                         d_scaling=g["scaling"].data_ptr(), d_rot_res=_ptr(g.get("rot_res")), d_opacity_logit=g["opacity_logit"].data_ptr(),
                         d_trbf=_ptr(g.get("trbf")), d_features_dc=p_dc, d_features_rest=p_rest, d_shs_res=_ptr(g.get("shs_res")),
                         d_sh_factor=p_fac)
-    camera = _pose_buffers(P, dev) if camera_grads else None
-    between, dL_dfeatures = _features_between(features, ar, P, int(R), W, H, geomBuffer, binningBuffer, imageBuffer, options, dev)
+    rec = BackwardCallStruct(
+        family=FAMILY_RAW, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, raw=C.pointer(st), scale_modifier=float(scale_modifier),
+        viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy),
+        dL_dpix=_ptr(dL_dout_color), raw_grads=C.pointer(gs), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
+    # (sh_grad_factors stays off: a raw factor call is told by d_sh_factor in its gradient record)
+    grad_camera, dL_dfeatures = _backward(rec, flags, ar, False, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features)
     if features is not None:
         g["features"] = dL_dfeatures
-    if P != 0:
-        with _on_device(dev):
-            radii_c = radii.contiguous()
-            rec = BackwardCallStruct(
-                family=FAMILY_RAW, P=P, D=int(degree), M=M, R=int(R), background=_ptr(background), width=W, height=H, raw=C.pointer(st), scale_modifier=float(scale_modifier),
-                viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=_ptr(radii_c),
-                geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dpix=_ptr(dL_dout_color), raw_grads=C.pointer(gs),
-                stream=_stream_of(dev), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
-            call = lambda phase: _render_call(      # noqa: E731
-                "gsrast_render_backward", (_options_struct(options=options, grads_zeroed=first_backward, backward_phase=phase),), rec, flags, absgrad, camera)
-            if between is None:
-                _run_backward(ar, call, P, geomBuffer, dev)
-            else:
-                _run_backward_around(call, between)
-    if camera is not None:
-        g["camera"] = _camera_result(camera)
+    if grad_camera is not None:
+        g["camera"] = grad_camera
     if keep["motion_res"] is not None:
         g["motion_res"] = g["xyz"]
     return g

@@ -108,21 +108,105 @@ def _no_arena_for_aux():
                            "uninstall it with _C.set_grad_arena(None) for renders that need acc_depth / alpha")
 
 
+class _Request(NamedTuple):
+    """What one render was asked for besides its inputs: `return_aux` and the keyword-only render options, parsed and checked once
+    (_parse_request) and handed to the autograd node as ONE argument -- a tuple, so autograd sees no tensor in it."""
+    return_aux: bool                            # two more outputs (acc_depth, alpha), two more incoming gradients
+    antialiasing: bool                          # the backward must know how the state was filled
+    absgrad: Optional[torch.Tensor]             # the caller's [P,2] sink (not a saved tensor: every backward writes it)
+    contrib: Optional[torch.Tensor]             # the [P,4] sink of the blend-weight statistics, which the forward overwrites
+    pixel_weights: Optional[torch.Tensor]       # its per-pixel weights (only legal with `contrib`)
+    camera: bool                                # the backward also differentiates the camera
+
+
+_RENDER_OPTIONS = frozenset(("antialiasing", "absgrad", "camera_grads", "contrib", "pixel_weights", "features"))
+
+
+def _parse_request(raster_settings, P: int, device, return_aux: bool = False, **render_options):
+    """(the _Request, the four fixed trailing inputs of the autograd node) of one render of P Gaussians on `device`: the one place that reads
+    `return_aux` and the keyword-only `antialiasing` (default False), `absgrad` (None), `camera_grads` (False), `contrib` (None),
+    `pixel_weights` (None) and `features` (None).  GaussianRasterizer.forward / GaussianRasterizerRaw.forward take them through
+    **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone.  In this order: an
+    unknown keyword is a TypeError; a bad sink, bad weights or bad features a ValueError, before anything is launched; `return_aux` or
+    `features` with a GradArena installed a RuntimeError.  The trailing inputs are (features, viewmatrix, projmatrix, campos), None where
+    unused: the settings' three camera tensors once more, as differentiable inputs, if camera_grads is true and any of them requires grad --
+    else the record's `camera` is False and the node, its arguments and its launches are the plain call's."""
+    if not _RENDER_OPTIONS.issuperset(render_options):
+        raise TypeError(f"forward() got an unexpected keyword argument {sorted(set(render_options) - _RENDER_OPTIONS)[0]!r}")
+    get = render_options.get
+    absgrad, contrib, pixel_weights, features = get("absgrad"), get("contrib"), get("pixel_weights"), get("features")
+    if absgrad is not None:
+        _C.check_absgrad(absgrad, P, device)
+    _C.check_contrib(contrib, pixel_weights, P, int(raster_settings.image_height), int(raster_settings.image_width), device)
+    if features is not None:
+        _C.check_features(features, P, device)
+        _C.no_arena_for_features()
+    if return_aux:
+        _no_arena_for_aux()
+    cam = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
+    camera = bool(get("camera_grads", False)) and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam)
+    req = _Request(bool(return_aux), bool(get("antialiasing", False)), absgrad, contrib, pixel_weights, camera)
+    return req, (features,) + (cam if camera else (None, None, None))
+
+
+def _after_forward(ctx, rs, req: _Request, features, state, *family_saved):
+    """What both nodes do with what their family's _C.rasterize_gaussians* returned (`state`): the statistics and the feature map of the
+    request, what the backward must remember, and the outputs (color, radii, depth[, acc_depth, alpha][, feature_map]).  Saved, in this
+    fixed layout: radii, the three state buffers, features (None without), then the family's own tensors (None for an absent one)."""
+    num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = state
+    if req.contrib is not None:                # filled HERE, from the state the call above left: no backward is needed, none is affected
+        _C.contrib_stats(req.contrib, req.pixel_weights, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
+    # features: one more output, one more incoming gradient, one more saved tensor
+    feat_out = () if features is None else (_C.features_forward(features, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf),)
+    ctx.raster_settings, ctx.req, ctx.num_rendered = rs, req, num_rendered
+    ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
+    ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
+    ctx.gs_backwards = 0                       # backwards run on this state (retain_graph): only the first finds zeroed records
+    ctx.save_for_backward(radii, geom_buf, bin_buf, img_buf, features, *family_saved)
+    # depth stays "differentiable" as in the reference (REF:85-88: it is returned by the Function, its incoming gradient is ignored): a
+    # loss built from depth alone runs a backward that yields zero gradients there, and does here (round 6; rounds 1-5 marked it
+    # non-differentiable, which raised instead).  radii is int32: never differentiable.
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)     # no zero-filled [1,H,W] / [P] gradients for the two outputs nothing flows through
+    return (color, radii, depth, *aux_out, *feat_out)
+
+
+def _before_backward(ctx, grad_out_color, grad_aux: tuple):
+    """What both nodes do in front of their family's _C.*_backward: (the colour's gradient, (radii, geom_buf, bin_buf, img_buf), the
+    family's saved tensors, the call's keyword arguments) from the incoming gradients and the layout _after_forward saved."""
+    req, rs = ctx.req, ctx.raster_settings
+    radii, geom_buf, bin_buf, img_buf, features, *family_saved = ctx.saved_tensors
+    grad_aux, grad_map = (grad_aux[:-1], grad_aux[-1]) if features is not None else (grad_aux, None)      # (None = zero: today's call)
+    grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
+    if grad_out_color is None:      # a loss that reaches this node through depth (or the aux outputs) only: the reference sees a zero colour gradient (REF:88)
+        grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=radii.device)
+    kw = dict(options=ctx.gs_options, first_backward=ctx.gs_backwards == 0, dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha,
+              antialiasing=req.antialiasing, absgrad=req.absgrad)
+    if req.camera:                  # (without: the call is the plain one, as before the keyword existed)
+        kw["camera_grads"] = True
+    if grad_map is not None:
+        kw["features"] = (features, grad_map)
+    return grad_out_color, (radii, geom_buf, bin_buf, img_buf), family_saved, kw
+
+
+def _optional_grads(ctx, first: int, grad_features, grad_camera) -> tuple:
+    """The node's gradients for its four fixed trailing inputs (input `first` onwards): dL_dfeatures or None, then each camera tensor's
+    gradient in its own shape and dtype -- None for one that does not require grad, and for all three without req.camera."""
+    rs = ctx.raster_settings
+    if not ctx.req.camera:
+        return (grad_features, None, None, None)
+    return (grad_features,) + tuple(g.reshape(t.shape).to(t.dtype) if ctx.needs_input_grad[first + 1 + k] else None
+                                    for k, (g, t) in enumerate(zip(grad_camera, (rs.viewmatrix, rs.projmatrix, rs.campos))))
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Opaque-state autograd node: forward saves the three state buffers the native library
-    filled, backward hands them back (REF:42-132).  AUX (the subclass below): two more outputs, two more incoming gradients."""
-    AUX = False
+    filled, backward hands them back (REF:42-132).  `req`: the render's _Request; behind it the four fixed optional differentiable
+    inputs (_parse_request), None where unused."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, antialiasing, absgrad, contrib, *camera):
-        # camera: behind () or (features,) -- the [P,C] per-Gaussian vectors of `features=`, one more differentiable input (_split_features)
-        features, camera = _split_features(camera)
-        # contrib: None or (the [P,4] sink of the blend-weight statistics, its pixel weights or None) -- a tuple, so autograd sees no tensor
-        # camera: () or raster_settings' (viewmatrix, projmatrix, campos) once more, as differentiable inputs (_camera_inputs)
-        aux = ctx._forward_cls.AUX      # (of the class .apply was called on)
-        if aux:
-            _no_arena_for_aux()
+                raster_settings, req, features, viewmatrix, projmatrix, campos):
         rs = raster_settings
         ar = _C._grad_arena
         if ar is not None and ar.sh_factors and sh.numel() != 0 and sh.requires_grad and not sh.is_leaf:
@@ -131,95 +215,31 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise RuntimeError("GradArena(sh_factors=True) needs the rasterizer's `shs` to be a leaf tensor; for "
                                "cat(features_dc, features_rest) or shs + residual use GradArena(sh_factors=False) + "
                                "view_parallel.allreduce_mean_inplace")
-        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = _C.rasterize_gaussians(
+        state = _C.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=aux, antialiasing=antialiasing)
-        if contrib is not None:                    # filled HERE, from the state the call above left: no backward is needed, none is affected
-            _C.contrib_stats(contrib[0], contrib[1], num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
-        feat_out = () if features is None else (_C.features_forward(features, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf),)
-        ctx.features = features is not None        # one more output, one more incoming gradient, one more saved tensor
-        ctx.raster_settings = rs
-        ctx.antialiasing = bool(antialiasing)      # the backward must know how the state was filled
-        ctx.absgrad = absgrad                      # the caller's [P,2] sink (not a saved tensor: every backward writes it)
-        ctx.camera = bool(camera)                  # the backward also differentiates the camera
-        ctx.num_rendered = num_rendered
-        ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
-        ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
-        ctx.gs_backwards = 0                       # backwards run on this state (retain_graph): only the first finds zeroed records
+            rs.sh_degree, rs.campos, rs.prefiltered, forward_only=not any(ctx.needs_input_grad), aux=req.return_aux, antialiasing=req.antialiasing)
         # opacities are not saved: the state buffer keeps them next to the conic (REF:84)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-                              geom_buf, bin_buf, img_buf, *(() if features is None else (features,)))
-        # depth stays "differentiable" as in the reference (REF:85-88: it is returned by the Function, its incoming gradient is ignored): a
-        # loss built from depth alone runs a backward that yields zero gradients there, and does here (round 6; rounds 1-5 marked it
-        # non-differentiable, which raised instead).  radii is int32: never differentiable.
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)     # no zero-filled [1,H,W] / [P] gradients for the two outputs nothing flows through
-        return (color, radii, depth, *aux_out, *feat_out)
+        return _after_forward(ctx, rs, req, features, state, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, _grad_depth, *grad_aux):
-        grad_aux, grad_map = (grad_aux[:-1], grad_aux[-1]) if ctx.features else (grad_aux, None)      # (None = zero: today's call)
-        grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
         rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-         geom_buf, bin_buf, img_buf, *features) = ctx.saved_tensors
-        if grad_out_color is None:      # a loss that reaches this node through depth (or the aux outputs) only: the reference sees a zero colour gradient (REF:88)
-            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=means3D.device)
+        grad_out_color, (radii, geom_buf, bin_buf, img_buf), (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh), kw = \
+            _before_backward(ctx, grad_out_color, grad_aux)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations, *grad_camera) = _C.rasterize_gaussians_backward(
+         grad_scales, grad_rotations, *more) = _C.rasterize_gaussians_backward(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
-            geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad,
-            **({"camera_grads": True} if ctx.camera else {}), **({"features": (features[0], grad_map)} if grad_map is not None else {}))
+            geom_buf, ctx.num_rendered, bin_buf, img_buf, **kw)
         ctx.gs_backwards += 1
-        grad_features = (grad_camera.pop() if grad_map is not None else None,) if ctx.features else ()
+        grad_features = more.pop() if "features" in kw else None
         # one gradient per forward input, in input order; absent optionals get None
         def opt(g, x):
             return g if x.numel() != 0 else None
         return (grad_means3D, grad_means2D, opt(grad_sh, sh), opt(grad_colors_precomp, colors_precomp),
                 grad_opacities, opt(grad_scales, scales), opt(grad_rotations, rotations),
-                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None, None, None) + grad_features + _camera_grads_out(ctx, rs, grad_camera, 12 + len(grad_features))
-
-
-class _RasterizeGaussiansAux(_RasterizeGaussians):
-    """_RasterizeGaussians with the two aux outputs: returns (color, radii, depth, acc_depth, alpha)."""
-    AUX = True
-
-
-def _split_features(tail: tuple):
-    """(features or None, the camera's inputs) of what an autograd node finds behind its fixed inputs: () | (features,) | the camera's
-    three (_camera_inputs) | (features,) + the camera's three.  Without `features=` the node's inputs are what they were before it existed."""
-    return (tail[0], tail[1:]) if len(tail) in (1, 4) else (None, tail)
-
-
-def _features_arg(features, P: int, device) -> tuple:
-    """The keyword-only `features` (default None), checked (ValueError before anything is launched; RuntimeError with a GradArena installed)
-    and packed for the autograd node: () without it, else (features,)."""
-    if features is None:
-        return ()
-    _C.check_features(features, P, device)
-    _C.no_arena_for_features()
-    return (features,)
-
-
-def _camera_inputs(raster_settings, camera_grads: bool) -> tuple:
-    """What camera_grads=True adds to the autograd node's inputs: the settings' (viewmatrix, projmatrix, campos) if any of them requires
-    grad, else nothing -- the node, its arguments and its launches are then the plain call's."""
-    cam = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
-    if camera_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
-        return cam
-    return ()
-
-
-def _camera_grads_out(ctx, rs, grad_camera, first: int) -> tuple:
-    """The node's gradients for its camera inputs (input `first` onwards): () without them, else each tensor's gradient in its own shape
-    and dtype, None for one that does not require grad."""
-    if not ctx.camera:
-        return ()
-    return tuple(g.reshape(t.shape).to(t.dtype) if ctx.needs_input_grad[first + k] else None
-                 for k, (g, t) in enumerate(zip(grad_camera[0], (rs.viewmatrix, rs.projmatrix, rs.campos))))
+                opt(grad_cov3Ds_precomp, cov3Ds_precomp), None, None) + _optional_grads(ctx, 10, grad_features, more[0] if more else None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -231,39 +251,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     gradient; `camera_grads` (not in the reference): gradients for raster_settings' viewmatrix / projmatrix / campos; `contrib` / `pixel_weights` (not in the reference): the
     [P,4] sink of the per-Gaussian blend-weight statistics, which the forward overwrites, and its per-pixel weights (module docstring);
     `features` (not in the reference): [P,C] per-Gaussian vectors, the result ends with their blend feature_map[C,H,W] (module docstring)."""
-    fn = _RasterizeGaussiansAux if return_aux else _RasterizeGaussians
-    if absgrad is not None:
-        _C.check_absgrad(absgrad, int(means3D.shape[0]), means3D.device)
-    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                    cov3Ds_precomp, raster_settings, bool(antialiasing), absgrad,
-                    _contrib_arg(contrib, pixel_weights, int(means3D.shape[0]), raster_settings, means3D.device),
-                    *_features_arg(features, int(means3D.shape[0]), means3D.device), *_camera_inputs(raster_settings, bool(camera_grads)))
-
-
-def _antialiasing_of(render_options: dict) -> bool:
-    """The keyword-only `antialiasing` (default False) of GaussianRasterizer.forward / GaussianRasterizerRaw.forward.  It arrives through
-    **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone."""
-    unknown = set(render_options) - {"antialiasing", "absgrad", "camera_grads", "contrib", "pixel_weights", "features"}
-    if unknown:
-        raise TypeError(f"forward() got an unexpected keyword argument {sorted(unknown)[0]!r}")
-    return bool(render_options.get("antialiasing", False))
-
-
-def _absgrad_of(render_options: dict) -> Optional[torch.Tensor]:
-    """The keyword-only `absgrad` (default None) of the same two methods, through **render_options like `antialiasing`."""
-    return render_options.get("absgrad", None)
-
-
-def _camera_grads_of(render_options: dict) -> bool:
-    """The keyword-only `camera_grads` (default False) of the same two methods, through **render_options like `antialiasing`."""
-    return bool(render_options.get("camera_grads", False))
-
-
-def _contrib_arg(contrib, pixel_weights, P: int, raster_settings, device) -> Optional[tuple]:
-    """The keyword-only `contrib` (default None) and `pixel_weights` (default None), checked (ValueError, before anything is launched) and
-    packed for the autograd node: None without a sink, else (sink, weights or None)."""
-    _C.check_contrib(contrib, pixel_weights, P, int(raster_settings.image_height), int(raster_settings.image_width), device)
-    return None if contrib is None else (contrib, pixel_weights)
+    req, optional = _parse_request(raster_settings, int(means3D.shape[0]), means3D.device, return_aux, antialiasing=antialiasing, absgrad=absgrad,
+                                   camera_grads=camera_grads, contrib=contrib, pixel_weights=pixel_weights, features=features)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, req, *optional)
 
 
 _EMPTY = torch.empty(0)
@@ -284,7 +274,7 @@ class GaussianRasterizer(nn.Module):
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
                 rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *, return_aux: bool = False,
                 **render_options):
-        antialiasing, absgrad = _antialiasing_of(render_options), _absgrad_of(render_options)
+        req, optional = _parse_request(self.raster_settings, int(means3D.shape[0]), means3D.device, return_aux, **render_options)
         have_sh, have_rgb = shs is not None, colors_precomp is not None
         if have_sh == have_rgb:
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -295,7 +285,7 @@ class GaussianRasterizer(nn.Module):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
 
         empty = _EMPTY          # absent optional input, like the reference's torch.Tensor([]) (REF:173-183); one shared CPU tensor: nobody writes it
-        return rasterize_gaussians(
+        return _RasterizeGaussians.apply(
             means3D, means2D,
             shs if have_sh else empty,
             colors_precomp if have_rgb else empty,
@@ -303,14 +293,11 @@ class GaussianRasterizer(nn.Module):
             scales if scales is not None else empty,
             rotations if rotations is not None else empty,
             cov3D_precomp if have_cov else empty,
-            self.raster_settings, return_aux=return_aux, antialiasing=antialiasing, absgrad=absgrad,
-            camera_grads=_camera_grads_of(render_options), contrib=render_options.get("contrib"), pixel_weights=render_options.get("pixel_weights"),
-            features=render_options.get("features"))
+            self.raster_settings, req, *optional)
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
-    # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so is antialiasing
-    # (default False, through **render_options: _antialiasing_of), absgrad (default None: _absgrad_of), camera_grads (default
-    # False: _camera_grads_of), contrib and pixel_weights (default None: _contrib_arg), features (default None: _features_arg).
+    # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so are antialiasing, absgrad,
+    # camera_grads, contrib, pixel_weights and features, which arrive through **render_options (names and defaults: _parse_request).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
 
@@ -318,67 +305,29 @@ class GaussianRasterizer(nn.Module):
 # ---- raw-parameter module (no counterpart in the reference: SURVEY.md 8f rank 3 as written -- the activation / deformation epilogue
 # of scene/saro_gaussian.py:807-847 fused into the per-Gaussian kernels) -------------------------------------------------------------
 class _RasterizeGaussiansRaw(torch.autograd.Function):
-    """Inputs in _C.RAW_NAMES order (absent residuals: None) + means2D (the gradient sink of REF:42) + the settings + antialiasing.
-    AUX: as _RasterizeGaussians."""
-    AUX = False
+    """means2D (the gradient sink of REF:42) + the settings + the render's _Request + the inputs in _C.RAW_NAMES order (absent residuals:
+    None) + the four fixed optional differentiable inputs, as _RasterizeGaussians."""
 
     @staticmethod
-    def forward(ctx, means2D, raster_settings, antialiasing, absgrad, contrib, *raw_tensors):
-        # (behind the len(_C.RAW_NAMES) raw tensors: () or the camera's three, as _RasterizeGaussians.forward's *camera)
-        raw_tensors, (features, camera) = raw_tensors[:len(_C.RAW_NAMES)], _split_features(raw_tensors[len(_C.RAW_NAMES):])      # (features: as _RasterizeGaussians.forward)
-        aux = ctx._forward_cls.AUX
-        if aux:
-            _no_arena_for_aux()
+    def forward(ctx, means2D, raster_settings, req, *inputs):
+        *raw_tensors, features, viewmatrix, projmatrix, campos = inputs
         rs = raster_settings
-        raw = dict(zip(_C.RAW_NAMES, raw_tensors))
-        forward_only = not any(ctx.needs_input_grad)
-        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = _C.rasterize_gaussians_raw(
-            rs.bg, raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-            rs.sh_degree, rs.campos, forward_only=forward_only, aux=aux, antialiasing=antialiasing)
-        if contrib is not None:                    # (as _RasterizeGaussians.forward)
-            _C.contrib_stats(contrib[0], contrib[1], num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
-        feat_out = () if features is None else (_C.features_forward(features, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf),)
-        ctx.features = features is not None
-        ctx.raster_settings, ctx.num_rendered = rs, num_rendered
-        ctx.antialiasing = bool(antialiasing)
-        ctx.absgrad = absgrad
-        ctx.camera = bool(camera)
-        ctx.gs_options = _C.current_options()
-        ctx.gs_options["forward_only"] = int(forward_only)
-        ctx.gs_backwards = 0
-        ctx.present = tuple(t is not None for t in raw_tensors)
-        ctx.save_for_backward(*[t for t in raw_tensors if t is not None], *(() if features is None else (features,)), radii, geom_buf, bin_buf, img_buf)
-        ctx.mark_non_differentiable(radii)      # (depth: as _RasterizeGaussians -- differentiable in name, its gradient ignored)
-        ctx.set_materialize_grads(False)
-        return (color, radii, depth, *aux_out, *feat_out)
+        state = _C.rasterize_gaussians_raw(
+            rs.bg, dict(zip(_C.RAW_NAMES, raw_tensors)), rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
+            rs.sh_degree, rs.campos, forward_only=not any(ctx.needs_input_grad), aux=req.return_aux, antialiasing=req.antialiasing)
+        return _after_forward(ctx, rs, req, features, state, *raw_tensors)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, _grad_depth, *grad_aux):
-        grad_aux, grad_map = (grad_aux[:-1], grad_aux[-1]) if ctx.features else (grad_aux, None)      # (None = zero: today's call)
-        grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
         rs = ctx.raster_settings
-        saved = list(ctx.saved_tensors)
-        img_buf, bin_buf, geom_buf, radii = saved.pop(), saved.pop(), saved.pop(), saved.pop()
-        features = saved.pop() if ctx.features else None
-        it = iter(saved)
-        raw = {n: (next(it) if here else None) for n, here in zip(_C.RAW_NAMES, ctx.present)}
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((_C.NUM_CHANNELS, rs.image_height, rs.image_width), device=radii.device)
+        grad_out_color, (radii, geom_buf, bin_buf, img_buf), raw_tensors, kw = _before_backward(ctx, grad_out_color, grad_aux)
+        raw = dict(zip(_C.RAW_NAMES, raw_tensors))
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, raw, radii, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree,
-            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, options=ctx.gs_options, first_backward=ctx.gs_backwards == 0,
-            dL_dacc_depth=grad_acc_depth, dL_dalpha=grad_alpha, antialiasing=ctx.antialiasing, absgrad=ctx.absgrad,
-            **({"camera_grads": True} if ctx.camera else {}), **({"features": (features, grad_map)} if grad_map is not None else {}))
+            rs.campos, geom_buf, ctx.num_rendered, bin_buf, img_buf, **kw)
         ctx.gs_backwards += 1
-        grad_features = (g.get("features"),) if ctx.features else ()
-        shapes = {n: (None if raw[n] is None else raw[n].shape) for n in _C.RAW_NAMES}
-        grads = tuple(None if raw[n] is None else g[n].reshape(shapes[n]) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
-        return (g["dL_dmeans2D"], None, None, None, None) + grads + grad_features + _camera_grads_out(ctx, rs, (g.get("camera"),), 5 + len(_C.RAW_NAMES) + len(grad_features))
-
-
-class _RasterizeGaussiansRawAux(_RasterizeGaussiansRaw):
-    """_RasterizeGaussiansRaw with the two aux outputs."""
-    AUX = True
+        grads = tuple(None if raw[n] is None else g[n].reshape(raw[n].shape) if g[n].is_contiguous() else g[n] for n in _C.RAW_NAMES)
+        return (g["dL_dmeans2D"], None, None) + grads + _optional_grads(ctx, 3 + len(_C.RAW_NAMES), g.get("features"), g.get("camera"))
 
 
 class GaussianRasterizerRaw(nn.Module):
@@ -396,12 +345,7 @@ class GaussianRasterizerRaw(nn.Module):
 
     def forward(self, xyz, means2D, rotation, scaling, opacity, features_dc, features_rest, motion_residual=None, rot_residual=None,
                 trbfoutput=None, shs_residual=None, *, return_aux: bool = False, **render_options):
-        antialiasing, absgrad = _antialiasing_of(render_options), _absgrad_of(render_options)
-        if absgrad is not None:
-            _C.check_absgrad(absgrad, int(xyz.shape[0]), xyz.device)
+        req, optional = _parse_request(self.raster_settings, int(xyz.shape[0]), xyz.device, return_aux, **render_options)
         raw = dict(xyz=xyz, motion_res=motion_residual, rotation=rotation, rot_res=rot_residual, scaling=scaling, opacity_logit=opacity,
                    trbf=trbfoutput, features_dc=features_dc, features_rest=features_rest, shs_res=shs_residual)
-        fn = _RasterizeGaussiansRawAux if return_aux else _RasterizeGaussiansRaw
-        contrib = _contrib_arg(render_options.get("contrib"), render_options.get("pixel_weights"), int(xyz.shape[0]), self.raster_settings, xyz.device)
-        return fn.apply(means2D, self.raster_settings, antialiasing, absgrad, contrib, *[raw[n] for n in _C.RAW_NAMES],
-                        *_features_arg(render_options.get("features"), int(xyz.shape[0]), xyz.device), *_camera_inputs(self.raster_settings, _camera_grads_of(render_options)))
+        return _RasterizeGaussiansRaw.apply(means2D, self.raster_settings, req, *[raw[n] for n in _C.RAW_NAMES], *optional)

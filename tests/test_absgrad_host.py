@@ -162,7 +162,7 @@ def test_python_refuses_a_bad_sink_at_forward_time(rast):
         assert fn.__kwdefaults__ == {"return_aux": False}
     with pytest.raises(TypeError):
         rast.GaussianRasterizer(rs)(m3, m2, op, colors_precomp=torch.zeros((P, 3)), scales=torch.ones((P, 3)), rotations=torch.ones((P, 4)), abs_grad=good)
-    assert rast._absgrad_of({}) is None and rast._absgrad_of({"absgrad": good}) is good
+    assert rast._parse_request(rs, P, cpu)[0].absgrad is None and rast._parse_request(rs, P, cpu, absgrad=good)[0].absgrad is good
 
 
 # ---- densification plumbing ---------------------------------------------------------------------------------------------------------

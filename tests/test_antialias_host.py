@@ -136,12 +136,13 @@ def test_antialiasing_is_keyword_only_and_false_by_default_on_every_surface(rast
     for cls in (rast.GaussianRasterizer, rast.GaussianRasterizerRaw):
         ps = inspect.signature(cls.forward, follow_wrapped=False).parameters
         assert "antialiasing" not in ps
-    assert rast._antialiasing_of({}) is False
-    assert rast._antialiasing_of({"antialiasing": True}) is True
-    with pytest.raises(TypeError, match="unexpected keyword argument 'antialias'"):
-        rast._antialiasing_of({"antialias": True})
-    # ... reached before anything touches a tensor: a typo fails on a CPU machine too, and a positional value has no slot to land in
     rs = rast.GaussianRasterizationSettings(8, 8, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 0, torch.zeros(3), False)
+    cpu = torch.device("cpu")
+    assert rast._parse_request(rs, 1, cpu)[0].antialiasing is False
+    assert rast._parse_request(rs, 1, cpu, antialiasing=True)[0].antialiasing is True
+    with pytest.raises(TypeError, match="unexpected keyword argument 'antialias'"):
+        rast._parse_request(rs, 1, cpu, antialias=True)
+    # ... reached before anything touches a tensor: a typo fails on a CPU machine too, and a positional value has no slot to land in
     with pytest.raises(TypeError, match="antialias"):
         rast.GaussianRasterizer(rs)(torch.zeros(1, 3), torch.zeros(1, 3), torch.ones(1, 1), colors_precomp=torch.zeros(1, 3),
                                     cov3D_precomp=torch.zeros(1, 6), antialias=True)

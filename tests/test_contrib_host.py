@@ -154,6 +154,14 @@ def test_python_refuses_a_bad_sink_or_bad_weights_at_call_time(rast):
         assert fn.__kwdefaults__ == {"return_aux": False}
     with pytest.raises(TypeError):
         rast.GaussianRasterizer(rs)(m3, m2, op, colors_precomp=torch.zeros((P, 3)), scales=torch.ones((P, 3)), rotations=torch.ones((P, 4)), contribs=good)
+    # the one parser: every default, and the sink and its weights as given
+    req, slots = rast._parse_request(rs, P, cpu)
+    assert req == (False, False, None, None, None, False) and req._fields == ("return_aux", "antialiasing", "absgrad", "contrib", "pixel_weights", "camera")
+    assert slots == (None, None, None, None)
+    req, _ = rast._parse_request(rs, P, cpu, return_aux=True, contrib=good, pixel_weights=gw)
+    assert req.return_aux is True and req.contrib is good and req.pixel_weights is gw
+    with pytest.raises(ValueError, match="only legal"):
+        rast._parse_request(rs, P, cpu, pixel_weights=gw)
 
 
 # ---- accumulation over views ----------------------------------------------------------------------------------------------------------

@@ -112,10 +112,18 @@ def test_python_refuses_bad_features_at_call_time(rast):
         assert fn.__kwdefaults__ == {"return_aux": False}
     with pytest.raises(TypeError):
         rast.GaussianRasterizer(rs)(m3, m2, op, colors_precomp=torch.zeros((P, 3)), scales=torch.ones((P, 3)), rotations=torch.ones((P, 4)), feature=good)
-    # what the node finds behind its fixed inputs
-    cam = (torch.eye(4), torch.eye(4), torch.zeros(3))
-    assert rast._split_features(()) == (None, ()) and rast._split_features(cam) == (None, cam)
-    assert rast._split_features((good,)) == (good, ()) and rast._split_features((good,) + cam) == (good, cam)
+    with pytest.raises(TypeError, match="unexpected keyword argument 'feature'"):
+        rast._parse_request(rs, P, cpu, feature=good)
+    # what the node finds in its four fixed trailing slots (features, viewmatrix, projmatrix, campos): None where unused
+    rq = rs._replace(viewmatrix=torch.eye(4, requires_grad=True))
+    cam = (rq.viewmatrix, rq.projmatrix, rq.campos)
+    for feats in (None, good):
+        kw = {} if feats is None else dict(features=feats)
+        for settings, camera_grads in ((rs, False), (rs, True), (rq, False)):
+            req, slots = rast._parse_request(settings, P, cpu, camera_grads=camera_grads, **kw)
+            assert req.camera is False and len(slots) == 4 and slots[0] is feats and slots[1:] == (None, None, None)
+        req, slots = rast._parse_request(rq, P, cpu, camera_grads=True, **kw)
+        assert req.camera is True and len(slots) == 4 and slots[0] is feats and all(a is b for a, b in zip(slots[1:], cam))
 
 
 def test_reference_with_three_channels_is_the_colour_render(scenes):

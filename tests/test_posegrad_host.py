@@ -241,18 +241,20 @@ def test_the_package_knows_the_keyword(rast):
         assert q.kind is inspect.Parameter.KEYWORD_ONLY and q.default is False
     for fn in (rast.GaussianRasterizer.forward, rast.GaussianRasterizerRaw.forward):
         assert fn.__kwdefaults__ == {"return_aux": False}
-    assert rast._camera_grads_of({}) is False and rast._camera_grads_of({"camera_grads": 1}) is True
-    assert rast._antialiasing_of({"camera_grads": True}) is False      # (the check of unknown keywords lets it through)
-    with pytest.raises(TypeError):
-        rast._antialiasing_of({"camera_grad": True})
-    P = 5
+    P, cpu = 5, torch.device("cpu")
     mk = lambda V: rast.GaussianRasterizationSettings(16, 16, 0.5, 0.5, torch.zeros(3), 1.0, V, torch.eye(4), 0, torch.zeros(3), False)      # noqa: E731
-    rs = mk(torch.eye(4))
-    assert rast._camera_inputs(rs, True) == () and rast._camera_inputs(rs, False) == ()
-    rq = mk(torch.eye(4, requires_grad=True))
-    assert rast._camera_inputs(rq, False) == ()
-    got = rast._camera_inputs(rq, True)
-    assert len(got) == 3 and got[0] is rq.viewmatrix and got[1] is rq.projmatrix and got[2] is rq.campos
+    rs, rq = mk(torch.eye(4)), mk(torch.eye(4, requires_grad=True))
+    request = lambda settings, **kw: rast._parse_request(settings, P, cpu, **kw)      # noqa: E731  ((the record, the node's four trailing inputs))
+    assert request(rq)[0].camera is False and request(rq, camera_grads=1)[0].camera is True
+    assert request(rq, camera_grads=True)[0].antialiasing is False      # (the check of unknown keywords lets it through)
+    with pytest.raises(TypeError):
+        request(rq, camera_grad=True)
+    # no settings tensor requires grad: no camera request, whatever camera_grads says -- the plain call
+    for settings, flag in ((rs, True), (rs, False), (rq, False)):
+        req, slots = request(settings, camera_grads=flag)
+        assert req.camera is False and slots == (None, None, None, None)
+    req, got = request(rq, camera_grads=True)
+    assert req.camera is True and len(got) == 4 and got[0] is None and got[1] is rq.viewmatrix and got[2] is rq.projmatrix and got[3] is rq.campos
     # through the public entry points the keyword gets as far as the device check (no GPU in this test), in all three places
     m3, m2, op = torch.zeros((P, 3)), torch.zeros((P, 3)), torch.zeros((P, 1))
     e = torch.empty(0)
