@@ -663,6 +663,50 @@ int gsrast_features_backward(const gsrast_options* options, int P, int R, int C,
                              const float* features /* [P][C] */, const float* dL_dfeature_map /* [C][H][W] */,
                              float* dL_dfeatures /* [P][C], overwritten */, void* stream);
 
+/* The depth-distortion map of one finished forward, and its gradients (no counterpart in the reference): the distortion loss of Mip-NeRF 360
+ * that gsplat renders as render_distort (`distloss`) and 2DGS carries in its rasterizer -- the regulariser against floaters and
+ * semi-transparent shells.
+ *
+ * Definition.  Pair (pixel p, Gaussian i) CONTRIBUTES exactly as defined for gsrast_contrib_stats above; its weight is w_i = alpha_i T_i, with
+ * the opacity the state carries (the GSRAST_RENDER_ANTIALIAS compensation included); z_i is the view-space depth the state carries (the
+ * value acc_depth of GSRAST_RENDER_AUX sums): raw view-space z, gsplat's convention, no near / far or NDC mapping.
+ *     distort[p] = sum_i sum_j w_i w_j |z_i - z_j|                   (over the contributors of p; no background term)
+ *                = 2 sum_i w_i (z_i A_{i-1} - D_{i-1}),   A_{i-1} = sum_{j<i} w_j,   D_{i-1} = sum_{j<i} w_j z_j
+ * The second line is what the kernel evaluates, in list order; it equals the first because every tile list is in non-decreasing z (ties
+ * contribute 0 either way).  The quantity does not change under z -> z - z0, and it is evaluated on depths RELATIVE to a tile-uniform z0,
+ * the depth of the tile's first listed Gaussian, so that z_i A - D does not cancel against the scene's distance from the camera; the fp32
+ * accuracy the tests hold the map to is measured on that association.  Every pixel of the map [H][W] is written, 0 with fewer than two
+ * contributors.  The calls have no flags; of the options only exp_mode is read (pass the forward's; NULL: the process defaults).  Both
+ * replay the blend from the state (csrc/gsrast_distort.h).
+ *
+ * gsrast_distortion_forward is valid once the render forward that filled the three state buffers has been enqueued on `stream`.  It also
+ * writes moments [2][H][W] = (A_N, D_N), each pixel's totals over all its contributors, D_N relative to the same z0: the backward goes back
+ * to front and cannot recover them.  z0 itself is not stored: both calls read it from the head of the tile's list.  The caller keeps
+ * moments (2 * H * W floats) for the backward.
+ *
+ * gsrast_distortion_backward takes moments and g = dL_ddistort [H][W].  With the sums over the contributors k > i behind a pair,
+ * SA = sum w_k, SD = sum w_k z_k, SG = sum G_k w_k:
+ *     dL/dz_i = 2 g w_i (A_{i-1} - SA)              G_i = dL/dw_i = 2 g (z_i A_{i-1} - D_{i-1} + SD - z_i SA)
+ *     dL/dalpha_i = T_i G_i - SG / (1 - alpha_i)    A_{i-1} = A_N - SA - w_i      D_{i-1} = D_N - SD - w_i z_i
+ *   - ADDS the screen-space mean, conic and opacity gradient sums that follow from dL/dalpha to floats 0-5 of the Gaussians' gradient
+ *     records inside geom_buffer, in the units the blend backward writes them (the 0.99 clamp passes gradients through);
+ *   - ADDS sum_p dL/dz_i to float 9 of the record, the dL/d(view-space z) that the per-Gaussian backward consumes only under
+ *     GSRAST_RENDER_AUX with a non-NULL aux gradient: a caller without aux gradients passes that flag and a zero dL_dacc_depth on both
+ *     phases.  Nothing else of the record is touched.
+ * It is therefore valid only BETWEEN a gsrast_render_backward with options.backward_phase = 1 and one with backward_phase = 2 on the same
+ * state and stream, like gsrast_features_backward; the two may both run there, in either order: they only add.  dL_dmean2D_abs
+ * (GSRAST_RENDER_ABSGRAD) does not include the map's loss.
+ *
+ * GSRAST_E_ARG before any device work: P < 0 or R < 0, a zero-size image, with P > 0 a NULL state buffer (binning_buffer only when R > 0),
+ * a NULL distort_map or moments (forward; backward with P > 0: moments or dL_ddistort), a bad exp_mode.  P == 0: the forward writes a zero
+ * map (and zero moments), the backward nothing; neither launches a kernel.  Kernels "distort_fwd" and "distort_bwd" of the profile table. */
+int gsrast_distortion_forward(const gsrast_options* options, int P, int R, int width, int height,
+                              const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                              float* distort_map /* [H][W] */, float* moments /* [2][H][W], saved for the backward */, void* stream);
+int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int width, int height,
+                               char* geom_buffer /* gradient records: floats 0-5 and 9 are ADDED to */, const char* binning_buffer, const char* image_buffer,
+                               const float* moments /* [2][H][W] */, const float* dL_ddistort /* [H][W] */, void* stream);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

@@ -20,6 +20,7 @@
 #include "gsrast_blend.h"
 #include "gsrast_contrib.h"
 #include "gsrast_features.h"
+#include "gsrast_distort.h"
 #include "gsrast_loss.h"
 #include "gsrast_epilogue.h"
 #include "gsrast_adam.h"
@@ -142,7 +143,7 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
-                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_COUNT };
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_COUNT };
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
@@ -151,7 +152,8 @@ const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "sca
                                             "grec_zero_touched" /* the consumed Gaussians' gradient records zeroed behind the forward's last blend */,
                                             "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */,
                                             "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */,
-                                            "features_fwd", "features_bwd" /* csrc/gsrast_features.h: gsrast_features_forward / _backward (one entry per call: all its passes) */ };
+                                            "features_fwd", "features_bwd" /* csrc/gsrast_features.h: gsrast_features_forward / _backward (one entry per call: all its passes) */,
+                                            "distort_fwd", "distort_bwd" /* csrc/gsrast_distort.h: gsrast_distortion_forward / _backward */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -2265,6 +2267,68 @@ int gsrast_features_backward(const gsrast_options* options, int P, int R, int C,
         GS_LAUNCHED("features_bwd");
         c0 += ch;
     }
+    return GSRAST_OK;
+}
+
+// ---- the depth-distortion map of a finished forward, and back (gsrast_distort.h) -------------------------------------------------------
+namespace {
+// What the two calls refuse alike, before any device work (one text each); fwd: the text names distortion_forward, else distortion_backward
+const char* distortion_refusal(bool fwd, const gsrast_options* options, int P, int R, int width, int height, const void* geom, const void* binning, const void* image,
+                               const void* map_or_grad, const void* moments)
+{
+    if (P < 0 || R < 0) return fwd ? "distortion_forward: negative P or R" : "distortion_backward: negative P or R";
+    if (width <= 0 || height <= 0) return fwd ? "distortion_forward: zero-size image" : "distortion_backward: zero-size image";
+    if (P > 0 && (!geom || !image || (R > 0 && !binning))) return fwd ? "distortion_forward: NULL state buffer" : "distortion_backward: NULL state buffer";
+    if ((fwd || P > 0) && !map_or_grad) return fwd ? "distortion_forward: NULL distort_map" : "distortion_backward: NULL dL_ddistort";
+    if ((fwd || P > 0) && !moments) return fwd ? "distortion_forward: NULL moments" : "distortion_backward: NULL moments";
+    const int mode = options ? options->exp_mode : snapshot_defaults().exp_mode;
+    if (mode < 0 || mode > 2) return fwd ? "distortion_forward: exp_mode must be 0, 1 or 2" : "distortion_backward: exp_mode must be 0, 1 or 2";
+    return nullptr;
+}
+} // namespace
+
+int gsrast_distortion_forward(const gsrast_options* options, int P, int R, int width, int height, const char* geom_buffer,
+                              const char* binning_buffer, const char* image_buffer, float* distort_map, float* moments, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = distortion_refusal(true, options, P, R, width, height, geom_buffer, binning_buffer, image_buffer, distort_map, moments)) return fail(GSRAST_E_ARG, e);
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    const size_t N = (size_t)width * (size_t)height;
+    // (no Gaussian, or no instance: nothing was blended)
+    if (P == 0 || R == 0) { GS_HIP(hipMemsetAsync(distort_map, 0, N * sizeof(float), s)); GS_HIP(hipMemsetAsync(moments, 0, 2 * N * sizeof(float), s)); return GSRAST_OK; }
+    const GeomLayout GL = geom_layout((size_t)P);
+    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
+    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    ProfScope ps(K_DISTORT_FWD, s);
+    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
+        distort_fwd_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
+            at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
+            at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), distort_map, moments);
+    });
+    GS_LAUNCHED("distort_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int width, int height, char* geom_buffer,
+                               const char* binning_buffer, const char* image_buffer, const float* moments, const float* dL_ddistort, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = distortion_refusal(false, options, P, R, width, height, geom_buffer, binning_buffer, image_buffer, dL_ddistort, moments)) return fail(GSRAST_E_ARG, e);
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (P == 0 || R == 0) return GSRAST_OK;      // (no Gaussian, or no instance: nothing was blended, nothing is added)
+    const GeomLayout GL = geom_layout((size_t)P);
+    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
+    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    ProfScope ps(K_DISTORT_BWD, s);
+    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
+        distort_bwd_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
+            at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
+            at<float>(image_buffer, IL.final_T), at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), moments, dL_ddistort,
+            at<float>(geom_buffer, GL.grec));
+    });
+    GS_LAUNCHED("distort_bwd");
     return GSRAST_OK;
 }
 

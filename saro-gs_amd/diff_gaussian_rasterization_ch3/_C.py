@@ -43,6 +43,7 @@ EXPORTS = (
     "gsrast_render_forward", "gsrast_render_backward", "gsrast_alloc_prealloc", "gsrast_pose_scratch_bytes",
     "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
     "gsrast_features_forward", "gsrast_features_backward",
+    "gsrast_distortion_forward", "gsrast_distortion_backward",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -204,6 +205,9 @@ def lib() -> C.CDLL:
     L.gsrast_features_forward.restype = L.gsrast_features_backward.restype = ci
     L.gsrast_features_forward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.gsrast_features_backward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_distortion_forward.restype = L.gsrast_distortion_backward.restype = ci
+    L.gsrast_distortion_forward.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.gsrast_distortion_backward.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.gsrast_binning_bytes.restype = C.c_size_t
     L.gsrast_binning_bytes.argtypes = [ci, ci, ci]
     L.gsrast_image_bytes.restype = C.c_size_t
@@ -681,14 +685,15 @@ def _run_backward(ar: Optional["GradArena"], call, P: int, geomBuffer: torch.Ten
 
 def _backward(rec: BackwardCallStruct, flags: int, ar: Optional["GradArena"], sh_grad_factors: bool, dev: torch.device, radii: torch.Tensor,
               geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imageBuffer: torch.Tensor, options: Optional[dict], first_backward: bool,
-              absgrad: Optional[torch.Tensor], camera_grads: bool, features: Optional[tuple]):
+              absgrad: Optional[torch.Tensor], camera_grads: bool, features: Optional[tuple], distortion: Optional[tuple] = None):
     """What the dense and the raw backward share behind their outputs (`rec`: the record with the family's inputs and outputs filled in; the
-    forward's state, the stream and the keyword-driven fields are filled here): the pose buffers, the feature map's step between the phases,
-    the call -- through _run_backward, or around that step -- and the results the keywords add: ((dL_dviewmatrix, dL_dprojmatrix,
+    forward's state, the stream and the keyword-driven fields are filled here): the pose buffers, the feature map's and the distortion map's
+    steps between the phases, the call -- through _run_backward, or around that step -- and the results the keywords add: ((dL_dviewmatrix, dL_dprojmatrix,
     dL_dcampos) or None, dL_dfeatures or None)."""
     P = rec.P
     camera = _pose_buffers(P, dev) if camera_grads else None
     between, dL_dfeatures = _features_between(features, ar, P, rec.R, rec.width, rec.height, geomBuffer, binningBuffer, imageBuffer, options, dev)
+    between = _distortion_between(distortion, between, ar, P, rec.R, rec.width, rec.height, geomBuffer, binningBuffer, imageBuffer, options, dev)
     if P != 0:
         with _on_device(dev):
             radii = radii.contiguous()
@@ -708,7 +713,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                  first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                  dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                 absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None):
+                                 absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None,
+                                 distortion: Optional[tuple] = None):
     """Backward.  Mirrors RasterizeGaussiansBackwardCUDA (rasterize_points.cu:117-194): returns
     ``(dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4])``.  `options` (not in the reference): the per-call options to use
@@ -722,11 +728,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     GSRAST_RENDER_POSEGRAD); without it the call and its result are what they were before the flag existed.
     `features`: (features [P,C], dL_dfeature_map [C,H,W]) of a feature map rendered from this state (features_forward) whose gradient is
     not zero -- the backward then runs in two phases around gsrast_features_backward, every returned gradient includes the map's loss
-    (`absgrad` does not) and the tuple ends with ``dL_dfeatures[P,C]`` (behind the camera's); without it the call is what it was."""
+    (`absgrad` does not) and the tuple ends with ``dL_dfeatures[P,C]`` (behind the camera's); without it the call is what it was.
+    `distortion`: (moments [2,H,W], dL_ddistort [H,W]) of a distortion map rendered from this state (distortion_forward) whose gradient is
+    not zero -- the backward runs in two phases around gsrast_distortion_backward (beside the feature map's step, if any), with
+    GSRAST_RENDER_AUX and a zero dL_dacc_depth of its own when no aux gradient is given (the per-Gaussian phase then consumes dL/dz); every
+    returned gradient includes the map's loss (`absgrad` does not), the tuple is unchanged."""
     dev = _require_gpu(means3D)
     P = int(means3D.shape[0])
     check_absgrad(absgrad, P, dev)
     H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])  # rasterize_points.cu:141-142
+    dL_dacc_depth = _distortion_aux(distortion, dL_dacc_depth, dL_dalpha, H, W, dev, options)
     flags, aux, _keep = _backward_flags(dL_dacc_depth, dL_dalpha, H, W, dev, antialiasing)
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, means3D, colors = f(background, "bg"), f(means3D, "means3D"), f(colors, "colors_precomp")
@@ -767,7 +778,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy),
         dL_dpix=_ptr(dL_dout_color), dL_dmean2D=_ptr(dL_dmeans2D), dL_dopacity=_ptr(dL_dopacity), dL_dcolor=_ptr(dL_dcolors), dL_dmean3D=_ptr(dL_dmeans3D), dL_dcov3D=_ptr(dL_dcov3D),
         dL_dsh=ar.factor.data_ptr() if factors else _ptr(dL_dsh), dL_dscale=_ptr(dL_dscales), dL_drot=_ptr(dL_drotations), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
-    grad_camera, dL_dfeatures = _backward(rec, flags, ar, factors, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features)
+    grad_camera, dL_dfeatures = _backward(rec, flags, ar, factors, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features,
+                                          distortion)
     grads = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     grads = grads if grad_camera is None else grads + (grad_camera,)
     return grads if features is None else grads + (dL_dfeatures,)
@@ -901,6 +913,64 @@ def _features_between(features: Optional[tuple], ar, P: int, R: int, W: int, H: 
     return between, dL_dfeatures
 
 
+def no_arena_for_distortion() -> None:
+    if _grad_arena is not None:
+        raise RuntimeError("distortion= is not supported with a GradArena installed (multi-GPU / view_parallel training): the arena drives the "
+                           "backward's two phases itself; uninstall it with _C.set_grad_arena(None) for renders that need a distortion map")
+
+
+def distortion_forward(P: int, R: int, W: int, H: int, geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imageBuffer: torch.Tensor,
+                       dev: torch.device, *, options: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gsrast_distortion_forward (include/gsrast.h) on the state a forward of P Gaussians returned: (distort_map [H,W] = sum_ij w_i w_j
+    |z_i - z_j| over the forward's own contributors, moments [2,H,W] for distortion's backward), on the current stream behind everything the
+    forward enqueued there.  `options`: the per-call options of that forward (default: the calling thread's)."""
+    out = torch.empty((int(H), int(W)), dtype=torch.float32, device=dev)
+    moments = torch.empty((2, int(H), int(W)), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib().gsrast_distortion_forward(C.byref(_options_struct(options=options)), int(P), int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+                                             _ptr(imageBuffer), out.data_ptr(), moments.data_ptr(), _stream_of(dev))
+    if rc != 0:
+        raise _err(rc, "gsrast_distortion_forward")
+    return out, moments
+
+
+def _distortion_aux(distortion: Optional[tuple], dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, options: Optional[dict]):
+    """The dL_dacc_depth of a backward: the caller's -- or, with `distortion` and no aux gradient at all, a zero one of the call's own, so that
+    the record carries GSRAST_RENDER_AUX and the per-Gaussian phase reads float 9 of the gradient records (dL/dz).  That plan needs the
+    culled blend kernels, and options.cull is the only switch the backward's plan reads for that (gsrast_policy.h: culled_blend(o, true) is
+    cull != 0), so its refusal is raised here, under the keyword's name, before the library would refuse "acc_depth / alpha gradients"."""
+    if distortion is None:
+        return dL_dacc_depth
+    if int((_thread_options() if options is None else options).get("cull", 1)) == 0:
+        raise RuntimeError("distortion=True: the gradient of the distortion map needs the culled blend kernels (options.cull != 0)")
+    if dL_dacc_depth is None and dL_dalpha is None:
+        return torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+    return dL_dacc_depth
+
+
+def _distortion_between(distortion: Optional[tuple], between, ar, P: int, R: int, W: int, H: int, geomBuffer, binningBuffer, imageBuffer, options, dev):
+    """What a backward runs between its two phases: `between` (the feature map's step, or None) and, with `distortion` = (moments,
+    dL_ddistort), gsrast_distortion_backward -- it adds the map's part to the gradient records phase 1 left and phase 2 consumes (floats
+    0-5, and dL/dz in float 9).  The two only add: their order does not matter."""
+    if distortion is None:
+        return between
+    if ar is not None:
+        raise RuntimeError("a distortion map's gradient cannot be served with a GradArena claimed by this backward")
+    moments, dL_dmap = distortion
+    if tuple(moments.shape) != (2, H, W) or dL_dmap.numel() != H * W:
+        raise RuntimeError(f"distortion: moments must be [2,{H},{W}] and dL_ddistort [{H},{W}] (got {list(moments.shape)}, {list(dL_dmap.shape)})")
+    moments, dL_dmap = _dev_f32(moments, "moments", dev), _dev_f32(dL_dmap, "dL_ddistort", dev)
+
+    def both():
+        if between is not None:
+            between()
+        rc = lib().gsrast_distortion_backward(C.byref(_options_struct(options=options)), P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
+                                              _ptr(imageBuffer), moments.data_ptr(), dL_dmap.data_ptr(), _stream_of(dev))
+        if rc != 0:
+            raise _err(rc, "gsrast_distortion_backward")
+    return both
+
+
 def _backward_flags(dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, antialiasing: bool):
     """A backward's (flags, (dL/dacc_depth, dL/dalpha) pointers, the tensors they point into): each gradient a contiguous fp32 [1,H,W]
     device tensor or None = zero; GSRAST_RENDER_AUX when either is given."""
@@ -966,12 +1036,13 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, *, options: Optional[dict] = None,
                                      first_backward: bool = False, dL_dacc_depth: Optional[torch.Tensor] = None,
                                      dL_dalpha: Optional[torch.Tensor] = None, antialiasing: bool = False,
-                                     absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None) -> dict:
+                                     absgrad: Optional[torch.Tensor] = None, camera_grads: bool = False, features: Optional[tuple] = None,
+                                     distortion: Optional[tuple] = None) -> dict:
     """Gradients of the raw leaves: dict with dL_dmeans2D [P,3], xyz (= motion_res), rotation, scaling, opacity_logit [P,1], features_dc,
     features_rest, and -- when the residual was given -- rot_res [P,7], trbf [P,1], shs_res [P,M,3].  `dL_dacc_depth` / `dL_dalpha`: as
     rasterize_gaussians_backward; `antialiasing`, `absgrad`: as rasterize_gaussians_backward; `camera_grads`: also "camera", the
     (dL_dviewmatrix, dL_dprojmatrix, dL_dcampos) of rasterize_gaussians_backward; `features`: as rasterize_gaussians_backward, the result
-    then has "features" (dL_dfeatures [P,C])."""
+    then has "features" (dL_dfeatures [P,C]); `distortion`: as rasterize_gaussians_backward."""
     dev = _require_gpu(raw["xyz"])
     P = int(raw["xyz"].shape[0])
     check_absgrad(absgrad, P, dev)
@@ -980,6 +1051,7 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
     f = lambda t, n: _dev_f32(t, n, dev)  # noqa: E731
     background, viewmatrix, projmatrix, campos = f(background, "bg"), f(viewmatrix, "viewmatrix"), f(projmatrix, "projmatrix"), f(campos, "campos")
     dL_dout_color = f(dL_dout_color, "dL_dout_color")
+    dL_dacc_depth = _distortion_aux(distortion, dL_dacc_depth, dL_dalpha, H, W, dev, options)
     flags, aux, _keep = _backward_flags(dL_dacc_depth, dL_dalpha, H, W, dev, antialiasing)
     o = dict(dtype=torch.float32, device=dev)
     ar = _claim_grad_arena(      # (else: the bucket of another call shape)
@@ -1016,7 +1088,8 @@ def rasterize_gaussians_raw_backward(background, raw: dict, radii, scale_modifie
         viewmatrix=_ptr(viewmatrix), projmatrix=_ptr(projmatrix), campos=_ptr(campos), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy),
         dL_dpix=_ptr(dL_dout_color), raw_grads=C.pointer(gs), dL_dacc_depth=aux[0], dL_dalpha=aux[1])
     # (sh_grad_factors stays off: a raw factor call is told by d_sh_factor in its gradient record)
-    grad_camera, dL_dfeatures = _backward(rec, flags, ar, False, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features)
+    grad_camera, dL_dfeatures = _backward(rec, flags, ar, False, dev, radii, geomBuffer, binningBuffer, imageBuffer, options, first_backward, absgrad, camera_grads, features,
+                                          distortion)
     if features is not None:
         g["features"] = dL_dfeatures
     if grad_camera is not None:

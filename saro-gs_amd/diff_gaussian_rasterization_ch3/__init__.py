@@ -71,6 +71,20 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   ``RuntimeError`` (the arena drives the two phases itself).  Under ``torch.no_grad()`` it is forward only.  A wrong shape / dtype /
   device / layout / C raises ``ValueError`` at call time, before any launch.  With ``features=None`` nothing is launched or allocated
   that was not before and the autograd node is the same (include/gsrast.h: gsrast_features_forward / gsrast_features_backward).
+* not in the reference: ``forward(..., distortion=True)`` (keyword-only, default False; also ``rasterize_gaussians`` and
+  ``GaussianRasterizerRaw``, together with ``return_aux``, ``antialiasing``, ``camera_grads``, ``contrib`` and ``features``) -- the
+  depth-distortion map of Mip-NeRF 360 (gsplat's ``distloss`` / ``render_distort``, 2DGS's distortion term), the regulariser against
+  floaters and semi-transparent shells.  The returned tuple gets ``distort_map[H, W]`` APPENDED as its LAST element (behind
+  ``feature_map`` when both are asked for):  distort_map[p] = sum_i sum_j w_ip w_jp |z_i - z_j|  over the Gaussians the forward blended at
+  p (the contributors defined under ``contrib``), w = alpha T with the opacity the render used, z the raw view-space depth that
+  ``acc_depth`` sums (no near / far or NDC mapping, no background term); a pixel with fewer than two contributors reads 0.  The map is
+  differentiable: ``means2D.grad``, ``opacities.grad``, the geometry leaves and the camera gradients of ``camera_grads=True`` include its
+  loss, through the weights and through z (the backward runs the blend phase, adds the map's terms to the per-Gaussian gradient records
+  -- beside the feature map's, if any -- and runs the per-Gaussian phase).  ``absgrad`` stays a statistic of the colour and the aux
+  outputs only.  With a ``GradArena`` installed ``distortion=True`` raises ``RuntimeError``.  Under ``torch.no_grad()`` it is forward only.
+  Its gradient needs the culled blend kernels (``options.cull != 0``, the default): ``RuntimeError`` otherwise.  With
+  ``distortion=False`` nothing is launched or allocated that was not before (include/gsrast.h: gsrast_distortion_forward /
+  gsrast_distortion_backward).
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -110,25 +124,35 @@ def _no_arena_for_aux():
 
 class _Request(NamedTuple):
     """What one render was asked for besides its inputs: `return_aux` and the keyword-only render options, parsed and checked once
-    (_parse_request) and handed to the autograd node as ONE argument -- a tuple, so autograd sees no tensor in it."""
+    (_parse_request) and handed to the autograd node as ONE argument -- a tuple, so autograd sees no tensor in it.
+    `distortion` is NOT one of the six fields (tests pin them as a tuple): it is a class attribute, False here and True in the subclass
+    _DistortionRequest, so equality, repr and _asdict do not show it -- compare type(req) or req.distortion; _replace / _make keep the type."""
     return_aux: bool                            # two more outputs (acc_depth, alpha), two more incoming gradients
     antialiasing: bool                          # the backward must know how the state was filled
     absgrad: Optional[torch.Tensor]             # the caller's [P,2] sink (not a saved tensor: every backward writes it)
     contrib: Optional[torch.Tensor]             # the [P,4] sink of the blend-weight statistics, which the forward overwrites
     pixel_weights: Optional[torch.Tensor]       # its per-pixel weights (only legal with `contrib`)
     camera: bool                                # the backward also differentiates the camera
+    distortion = False                          # (no field: _DistortionRequest)
 
 
-_RENDER_OPTIONS = frozenset(("antialiasing", "absgrad", "camera_grads", "contrib", "pixel_weights", "features"))
+class _DistortionRequest(_Request):
+    """A _Request that also asks for the depth-distortion map: one more output (distort_map, the last), one more incoming gradient, one more
+    saved tensor.  The record keeps its six fields; the bit travels in the record's type."""
+    __slots__ = ()
+    distortion = True
+
+
+_RENDER_OPTIONS = frozenset(("antialiasing", "absgrad", "camera_grads", "contrib", "pixel_weights", "features", "distortion"))
 
 
 def _parse_request(raster_settings, P: int, device, return_aux: bool = False, **render_options):
     """(the _Request, the four fixed trailing inputs of the autograd node) of one render of P Gaussians on `device`: the one place that reads
     `return_aux` and the keyword-only `antialiasing` (default False), `absgrad` (None), `camera_grads` (False), `contrib` (None),
-    `pixel_weights` (None) and `features` (None).  GaussianRasterizer.forward / GaussianRasterizerRaw.forward take them through
+    `pixel_weights` (None), `features` (None) and `distortion` (False).  GaussianRasterizer.forward / GaussianRasterizerRaw.forward take them through
     **render_options: those methods' keyword defaults (__kwdefaults__) are published as {"return_aux": False} alone.  In this order: an
-    unknown keyword is a TypeError; a bad sink, bad weights or bad features a ValueError, before anything is launched; `return_aux` or
-    `features` with a GradArena installed a RuntimeError.  The trailing inputs are (features, viewmatrix, projmatrix, campos), None where
+    unknown keyword is a TypeError; a bad sink, bad weights, bad features or a `distortion` that is no bool a ValueError, before anything is
+    launched; `return_aux`, `features` or `distortion` with a GradArena installed a RuntimeError.  The trailing inputs are (features, viewmatrix, projmatrix, campos), None where
     unused: the settings' three camera tensors once more, as differentiable inputs, if camera_grads is true and any of them requires grad --
     else the record's `camera` is False and the node, its arguments and its launches are the plain call's."""
     if not _RENDER_OPTIONS.issuperset(render_options):
@@ -141,41 +165,53 @@ def _parse_request(raster_settings, P: int, device, return_aux: bool = False, **
     if features is not None:
         _C.check_features(features, P, device)
         _C.no_arena_for_features()
+    distortion = get("distortion", False)
+    if not isinstance(distortion, bool):
+        raise ValueError(f"distortion must be True or False (got {type(distortion).__name__})")
+    if distortion:
+        _C.no_arena_for_distortion()
     if return_aux:
         _no_arena_for_aux()
     cam = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
     camera = bool(get("camera_grads", False)) and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam)
-    req = _Request(bool(return_aux), bool(get("antialiasing", False)), absgrad, contrib, pixel_weights, camera)
+    req = (_DistortionRequest if distortion else _Request)(bool(return_aux), bool(get("antialiasing", False)), absgrad, contrib, pixel_weights, camera)
     return req, (features,) + (cam if camera else (None, None, None))
 
 
 def _after_forward(ctx, rs, req: _Request, features, state, *family_saved):
     """What both nodes do with what their family's _C.rasterize_gaussians* returned (`state`): the statistics and the feature map of the
-    request, what the backward must remember, and the outputs (color, radii, depth[, acc_depth, alpha][, feature_map]).  Saved, in this
-    fixed layout: radii, the three state buffers, features (None without), then the family's own tensors (None for an absent one)."""
+    request, what the backward must remember, and the outputs (color, radii, depth[, acc_depth, alpha][, feature_map][, distort_map]).  Saved,
+    in this fixed layout: radii, the three state buffers, features (None without), the distortion map's moments (None without), then the
+    family's own tensors (None for an absent one)."""
     num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth, *aux_out = state
     if req.contrib is not None:                # filled HERE, from the state the call above left: no backward is needed, none is affected
         _C.contrib_stats(req.contrib, req.pixel_weights, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf)
     # features: one more output, one more incoming gradient, one more saved tensor
     feat_out = () if features is None else (_C.features_forward(features, num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf),)
+    # distortion: one more output (the last), one more incoming gradient, one more saved tensor (the moments its backward reads)
+    dist_out, moments = (), None
+    if req.distortion:
+        dmap, moments = _C.distortion_forward(int(radii.shape[0]), num_rendered, rs.image_width, rs.image_height, geom_buf, bin_buf, img_buf, color.device)
+        dist_out = (dmap,)
     ctx.raster_settings, ctx.req, ctx.num_rendered = rs, req, num_rendered
     ctx.gs_options = _C.current_options()      # the backward runs on autograd's thread: it must use THIS thread's options
     ctx.gs_options["forward_only"] = int(not any(ctx.needs_input_grad))   # (a backward then cannot happen; kept consistent anyway)
     ctx.gs_backwards = 0                       # backwards run on this state (retain_graph): only the first finds zeroed records
-    ctx.save_for_backward(radii, geom_buf, bin_buf, img_buf, features, *family_saved)
+    ctx.save_for_backward(radii, geom_buf, bin_buf, img_buf, features, moments, *family_saved)
     # depth stays "differentiable" as in the reference (REF:85-88: it is returned by the Function, its incoming gradient is ignored): a
     # loss built from depth alone runs a backward that yields zero gradients there, and does here (round 6; rounds 1-5 marked it
     # non-differentiable, which raised instead).  radii is int32: never differentiable.
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)     # no zero-filled [1,H,W] / [P] gradients for the two outputs nothing flows through
-    return (color, radii, depth, *aux_out, *feat_out)
+    return (color, radii, depth, *aux_out, *feat_out, *dist_out)
 
 
 def _before_backward(ctx, grad_out_color, grad_aux: tuple):
     """What both nodes do in front of their family's _C.*_backward: (the colour's gradient, (radii, geom_buf, bin_buf, img_buf), the
     family's saved tensors, the call's keyword arguments) from the incoming gradients and the layout _after_forward saved."""
     req, rs = ctx.req, ctx.raster_settings
-    radii, geom_buf, bin_buf, img_buf, features, *family_saved = ctx.saved_tensors
+    radii, geom_buf, bin_buf, img_buf, features, moments, *family_saved = ctx.saved_tensors
+    grad_aux, grad_dist = (grad_aux[:-1], grad_aux[-1]) if req.distortion else (grad_aux, None)           # (None = zero: today's call)
     grad_aux, grad_map = (grad_aux[:-1], grad_aux[-1]) if features is not None else (grad_aux, None)      # (None = zero: today's call)
     grad_acc_depth, grad_alpha = grad_aux or (None, None)      # (None = zero; both None: the plain backward)
     if grad_out_color is None:      # a loss that reaches this node through depth (or the aux outputs) only: the reference sees a zero colour gradient (REF:88)
@@ -186,6 +222,8 @@ def _before_backward(ctx, grad_out_color, grad_aux: tuple):
         kw["camera_grads"] = True
     if grad_map is not None:
         kw["features"] = (features, grad_map)
+    if grad_dist is not None:
+        kw["distortion"] = (moments, grad_dist)
     return grad_out_color, (radii, geom_buf, bin_buf, img_buf), family_saved, kw
 
 
@@ -245,14 +283,17 @@ class _RasterizeGaussians(torch.autograd.Function):
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_aux=False, *, antialiasing: bool = False, absgrad: Optional[torch.Tensor] = None,
                         camera_grads: bool = False, contrib: Optional[torch.Tensor] = None, pixel_weights: Optional[torch.Tensor] = None,
-                        features: Optional[torch.Tensor] = None):
+                        features: Optional[torch.Tensor] = None, distortion: bool = False):
     """Functional form (REF:17-39).  `return_aux` (not in the reference): also acc_depth and alpha; `antialiasing` (not in the
     reference): the opacity-compensated 2-D filter; `absgrad` (not in the reference): the [P,2] sink of the absolute screen-space
     gradient; `camera_grads` (not in the reference): gradients for raster_settings' viewmatrix / projmatrix / campos; `contrib` / `pixel_weights` (not in the reference): the
     [P,4] sink of the per-Gaussian blend-weight statistics, which the forward overwrites, and its per-pixel weights (module docstring);
-    `features` (not in the reference): [P,C] per-Gaussian vectors, the result ends with their blend feature_map[C,H,W] (module docstring)."""
+    `features` (not in the reference): [P,C] per-Gaussian vectors, the result ends with their blend feature_map[C,H,W] (module docstring);
+    `distortion` (not in the reference): the result ends with the depth-distortion map distort_map[H,W], behind feature_map (module docstring);
+    `absgrad` stays a statistic of the colour and the aux outputs only."""
     req, optional = _parse_request(raster_settings, int(means3D.shape[0]), means3D.device, return_aux, antialiasing=antialiasing, absgrad=absgrad,
-                                   camera_grads=camera_grads, contrib=contrib, pixel_weights=pixel_weights, features=features)
+                                   camera_grads=camera_grads, contrib=contrib, pixel_weights=pixel_weights, features=features,
+                                   distortion=distortion)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, req, *optional)
 
 
@@ -297,7 +338,7 @@ class GaussianRasterizer(nn.Module):
 
     # Introspection shows the reference's signature (REF:163-165: drop-in callers -- and tests/test_api_host.py -- compare it);
     # return_aux is this package's keyword-only extension, default False (forward.__kwdefaults__), and so are antialiasing, absgrad,
-    # camera_grads, contrib, pixel_weights and features, which arrive through **render_options (names and defaults: _parse_request).
+    # camera_grads, contrib, pixel_weights, features and distortion, which arrive through **render_options (names and defaults: _parse_request).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
 
@@ -337,7 +378,7 @@ class GaussianRasterizerRaw(nn.Module):
     opacities = sigmoid(opacity) * trbfoutput, shs = cat(features_dc, features_rest) + shs_residual (scene/saro_gaussian.py:807-847) --
     outputs bit-identical to fused_epilogue.activate_gaussians followed by GaussianRasterizer, without the activated tensors ever
     being written.  Gradients flow to every tensor given.  `return_aux=True`: (color, radii, depth, acc_depth, alpha), and the keyword-only
-    `antialiasing=True` (default False), `absgrad=sink` (default None), `camera_grads=True` (default False), `contrib=sink` and `pixel_weights=w` (default None), `features=F` (default None), as GaussianRasterizer."""
+    `antialiasing=True` (default False), `absgrad=sink` (default None), `camera_grads=True` (default False), `contrib=sink` and `pixel_weights=w` (default None), `features=F` (default None), `distortion=True` (default False), as GaussianRasterizer."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
