@@ -720,6 +720,17 @@ typedef struct gsrast_adam_group {
 } gsrast_adam_group;
 int gsrast_adam_step(int n_groups, const gsrast_adam_group* groups /* host array */, double beta1, double beta2, double eps,
                      int step /* 1-based */, void* stream);   /* betas in fp64: (1 - 0.999f) would be off by 1.3e-5 relative */
+/* The same step for the rows a view saw -- what upstream 3DGS ships as SparseGaussianAdam(params, visibility, N), gsplat as SelectiveAdam and
+ * PyTorch as torch.optim.SparseAdam.  visible: [rows] on the device, visible_elem_bytes 1 (bool / uint8: non-zero = visible) or 4 (int32:
+ * > 0 = visible, so that a render's radii can be passed as it is).  A visible row gets exactly gsrast_adam_step's update (an all-true mask
+ * reproduces it bit for bit); an invisible row keeps param, exp_avg and exp_avg_sq bit for bit, and neither its grad nor its lr_rows entry is
+ * read (NaN / Inf there reach nothing).  `step` is the caller's one global count: it advances with every step, masked or not, so a row first
+ * seen late is bias-corrected with the global t, not as if it were its first step (torch.optim.SparseAdam's and gsplat's choice).
+ * One launch (profile name "adam_step_visible"): a wave takes 64 consecutive rows of a group and leaves at once when none is visible.
+ * Refused before any device call (gsrast_last_error): what gsrast_adam_step refuses, visible_elem_bytes other than 1 or 4, rows < 0, a group
+ * whose rows differ from `rows` or whose width exceeds 2^24, NULL visible with rows > 0.  rows == 0 or no groups: nothing is launched. */
+int gsrast_adam_step_visible(int n_groups, const gsrast_adam_group* groups /* host array */, const void* visible, int visible_elem_bytes /* 1 or 4 */,
+                             long long rows, double beta1, double beta2, double eps, int step /* 1-based */, void* stream);
 
 /* ---- densification: clone / split / prune of every per-Gaussian array with its Adam moments, on the device ----
  * Replaces scene/saro_gaussian.py:705-736 densify_pruneclone with :685-701 densify_and_clone, :646-682 densify_and_splitv2,

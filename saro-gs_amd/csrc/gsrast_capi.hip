@@ -143,7 +143,7 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
-                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_COUNT };
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_ADAM_VISIBLE, K_COUNT };
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
@@ -153,7 +153,8 @@ const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "sca
                                             "densify_classify", "densify_scan", "densify_apply", "densify_stats_update" /* csrc/gsrast_densify.h */,
                                             "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */,
                                             "features_fwd", "features_bwd" /* csrc/gsrast_features.h: gsrast_features_forward / _backward (one entry per call: all its passes) */,
-                                            "distort_fwd", "distort_bwd" /* csrc/gsrast_distort.h: gsrast_distortion_forward / _backward */ };
+                                            "distort_fwd", "distort_bwd" /* csrc/gsrast_distort.h: gsrast_distortion_forward / _backward */,
+                                            "adam_step_visible" /* csrc/gsrast_adam.h: gsrast_adam_step_visible */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -1799,6 +1800,40 @@ int gsrast_adam_step(int n_groups, const gsrast_adam_group* groups, double beta1
     a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)step)));
     adam_step_kernel<<<(unsigned)blocks, ADAM_THREADS, 0, s>>>(a);
     GS_LAUNCHED("adam_step");
+    return GSRAST_OK;
+}
+
+int gsrast_adam_step_visible(int n_groups, const gsrast_adam_group* groups, const void* visible, int visible_elem_bytes, long long rows,
+                             double beta1, double beta2, double eps, int step, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(GSRAST_E_ARG, "adam_step_visible: bad arguments (at most 8 groups, step >= 1, betas in [0, 1))");
+    if (visible_elem_bytes != 1 && visible_elem_bytes != 4) return fail(GSRAST_E_ARG, "adam_step_visible: visible_elem_bytes must be 1 or 4");
+    if (rows < 0 || rows > 0x7FFFFFFFll) return fail(GSRAST_E_ARG, "adam_step_visible: rows out of range");
+    if (rows > 0 && !visible) return fail(GSRAST_E_ARG, "adam_step_visible: NULL visible");
+    AdamArgs a{};
+    const unsigned long long per_group = ((unsigned long long)rows + ADAM_VIS_ROWS_PER_BLOCK - 1) / ADAM_VIS_ROWS_PER_BLOCK;      // (<= 2^23 blocks per group: the grid cannot overflow)
+    unsigned long long blocks = 0;
+    for (int k = 0; k < n_groups; k++) {
+        const gsrast_adam_group& g = groups[k];
+        if (g.rows < 0 || g.width < 1 || (unsigned)g.width > ADAM_VIS_MAX_WIDTH) return fail(GSRAST_E_ARG, "adam_step_visible: bad group shape");
+        if (g.rows != rows) return fail(GSRAST_E_ARG, "adam_step_visible: a group's rows differ from the mask's length");
+        if (rows && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)) return fail(GSRAST_E_ARG, "adam_step_visible: NULL tensor");
+        if (rows == 0) continue;
+        AdamGroup& o = a.grp[a.n_groups++];
+        o.p = g.param; o.g = g.grad; o.m = g.exp_avg; o.v = g.exp_avg_sq; o.lr_rows = g.lr_rows; o.lr = g.lr; o.width = (unsigned)g.width;
+        o.n = (unsigned long long)rows * (unsigned long long)g.width; o.first_block = blocks; o.n_blocks = per_group;
+        blocks += per_group;
+    }
+    if (blocks == 0) return GSRAST_OK;
+    a.b1 = (float)beta1; a.b2 = (float)beta2; a.eps = (float)eps;
+    a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+    a.inv_bc1 = (float)(1.0 / (1.0 - std::pow(beta1, (double)step)));
+    a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)step)));
+    ProfScope ps(K_ADAM_VISIBLE, s);
+    adam_step_visible_kernel<<<(unsigned)blocks, ADAM_THREADS, 0, s>>>(a, visible, visible_elem_bytes, (unsigned)rows);
+    GS_LAUNCHED("adam_step_visible");
     return GSRAST_OK;
 }
 

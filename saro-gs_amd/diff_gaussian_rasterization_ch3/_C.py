@@ -35,7 +35,7 @@ EXPORTS = (
     "gsrast_get_option", "gsrast_profile_kernel_count", "gsrast_profile_kernel_name",
     "gsrast_profile_collect", "gsrast_profile_read", "gsrast_profile_reset", "gsrast_last_error",
     "gsrast_abi_version", "gsrast_loss_scratch_bytes", "gsrast_loss_forward", "gsrast_loss_backward",
-    "gsrast_sh_grad_combine", "gsrast_sh_grad_combine_rows", "gsrast_sh_grad_combine_union", "gsrast_rows_pack", "gsrast_rows_unpack", "gsrast_grad_rows_pack", "gsrast_grad_rows_clear", "gsrast_grad_rows_add", "gsrast_touched_rows", "gsrast_activate_forward", "gsrast_activate_backward", "gsrast_adam_step",
+    "gsrast_sh_grad_combine", "gsrast_sh_grad_combine_rows", "gsrast_sh_grad_combine_union", "gsrast_rows_pack", "gsrast_rows_unpack", "gsrast_grad_rows_pack", "gsrast_grad_rows_clear", "gsrast_grad_rows_add", "gsrast_touched_rows", "gsrast_activate_forward", "gsrast_activate_backward", "gsrast_adam_step", "gsrast_adam_step_visible",
     "gsrast_densify_scratch_bytes", "gsrast_densify_plan", "gsrast_densify_apply", "gsrast_densify_stats_update",
     "gsrast_knn_scratch_bytes", "gsrast_knn3_mean_dist2",
     "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
@@ -260,6 +260,8 @@ def lib() -> C.CDLL:
     L.gsrast_knn3_mean_dist2.argtypes = [ci, vp, vp, vp, vp]
     L.gsrast_adam_step.restype = ci
     L.gsrast_adam_step.argtypes = [ci, C.POINTER(AdamGroupStruct), C.c_double, C.c_double, C.c_double, ci, vp]
+    L.gsrast_adam_step_visible.restype = ci
+    L.gsrast_adam_step_visible.argtypes = [ci, C.POINTER(AdamGroupStruct), vp, ci, C.c_longlong, C.c_double, C.c_double, C.c_double, ci, vp]
     L.gsrast_densify_scratch_bytes.restype = C.c_size_t
     L.gsrast_densify_scratch_bytes.argtypes = [ci]
     L.gsrast_densify_plan.restype = ci

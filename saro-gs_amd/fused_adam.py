@@ -9,10 +9,14 @@ Mirror of how the reference drives its optimizer (/root/reference/scene/saro_gau
 `step()`, `zero_grad()`, `state`), accepts a float or a [P] / [P,1] tensor as a group's 'lr', and updates every group in ONE
 kernel (`gsrast_adam_step`).  amsgrad / maximize / weight_decay are not supported (the reference does not use them for
 these groups).  GPU tensors only; no fallback.
+
+`step(visibility=mask)` steps only the rows a view saw (`gsrast_adam_step_visible`): what upstream 3DGS ships as
+`SparseGaussianAdam`, gsplat as `SelectiveAdam`, PyTorch as `torch.optim.SparseAdam`.  The mask is a render's `radii` (int32,
+> 0 = visible) as it is, or a bool / uint8 tensor such as `view_parallel.distributed_step`'s `"visibility_filter"`.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List
+from typing import Dict, Iterable, List, Optional
 
 import torch
 
@@ -45,17 +49,38 @@ class GaussianAdam:
                 p.grad.zero_()
 
     @torch.no_grad()
-    def step(self) -> None:
-        L = _C.lib()
+    def step(self, *, visibility: Optional[torch.Tensor] = None) -> None:
+        """One Adam step of every group that has a gradient.
+
+        visibility=None: the dense step.  Otherwise a [P] or [P, 1] tensor on the parameters' device that selects rows: torch.bool /
+        torch.uint8 (non-zero = visible) or torch.int32 (> 0 = visible: a render's `radii`).  A visible row gets exactly the dense
+        update; a row that is not visible keeps its parameter and both moments bit for bit, and neither its gradient nor its
+        per-row learning rate is read (NaN / Inf there reach nothing).  Every group's row count must equal the mask's length.
+
+        The step count t of the bias corrections is the optimizer's one global count: it increases by one on every call, masked or
+        not, an all-false mask included (torch.optim.SparseAdam's and gsplat's choice).  A row first seen late is therefore NOT
+        bias-corrected as if that were its step 1."""
+        mask = None
+        if visibility is not None:
+            if not isinstance(visibility, torch.Tensor) or visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
+                raise RuntimeError("GaussianAdam: visibility must be a torch.bool, torch.uint8 or torch.int32 tensor "
+                                   f"(got {getattr(visibility, 'dtype', type(visibility))})")
+            if visibility.dim() not in (1, 2) or (visibility.dim() == 2 and visibility.shape[1] != 1):
+                raise RuntimeError(f"GaussianAdam: visibility must have shape [P] or [P, 1] (got {tuple(visibility.shape)})")
+            mask = visibility.detach().reshape(-1).contiguous()
         arr = (_C.AdamGroupStruct * len(self.param_groups))()
         n, keep, dev = 0, [], None
         for g in self.param_groups:
             p = g["params"][0]
             if p.grad is None:
                 continue
+            if mask is not None and (int(p.shape[0]) if p.dim() > 0 else 1) != mask.numel():
+                raise RuntimeError(f"GaussianAdam: group {g.get('name')} has {int(p.shape[0]) if p.dim() > 0 else 1} rows, the visibility mask {mask.numel()} entries")
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("GaussianAdam: parameters must be contiguous float32 GPU tensors (no CPU fallback)")
             dev = p.device
+            if mask is not None and mask.device != dev:
+                raise RuntimeError(f"GaussianAdam: the visibility mask lives on {mask.device}, the parameters on {dev}")
             st = self.state.get(p)
             if st is None:
                 st = self.state[p] = {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
@@ -80,7 +105,13 @@ class GaussianAdam:
         self._step += 1
         if n == 0:
             return
+        L = _C.lib()
         with torch.cuda.device(dev):
-            rc = L.gsrast_adam_step(n, arr, self.betas[0], self.betas[1], self.eps, self._step, torch.cuda.current_stream(dev).cuda_stream)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if mask is None:
+                rc, what = L.gsrast_adam_step(n, arr, self.betas[0], self.betas[1], self.eps, self._step, stream), "gsrast_adam_step"
+            else:
+                rc, what = L.gsrast_adam_step_visible(n, arr, mask.data_ptr(), 4 if mask.dtype == torch.int32 else 1, mask.numel(),
+                                                      self.betas[0], self.betas[1], self.eps, self._step, stream), "gsrast_adam_step_visible"
         if rc != 0:
-            raise _C._err(rc, "gsrast_adam_step")
+            raise _C._err(rc, what)
