@@ -775,6 +775,59 @@ int gsrast_densify_apply(int P, int N, const char* scratch, const unsigned* coun
 int gsrast_densify_stats_update(int P, const float* grad, const float* visibility_count, const float* radii,
                                 float* accum, float* denom, float* max_radii, int grad_is_mean, void* stream);
 
+/* ---- MCMC densification: relocate dead Gaussians, grow to a cap, position noise -- gsplat's MCMCStrategy on the device ----
+ * Replaces gsplat/strategy/ops.py relocate, sample_add and inject_noise_to_position, and gsplat/relocation.py compute_relocation
+ * (N_MAX = 51), with the optimizer surgery that goes with the first two.  Row layout: every array is [P][width] fp32, row i = Gaussian i.
+ *
+ * gsrast_mcmc_plan -- the multinomial's weights (relocate: opacities[alive]; sample_add: opacities.flatten()).  o_i =
+ * sigmoid(opacity_logit[i]); row i is dead when o_i <= min_opacity or dead_src[i] != 0 (dead_src [P] bytes or NULL); weights_out[i] =
+ * q_i = 0 for a dead row, max(1, floor(o_i * 2^24)) for an alive one (uint32 [P]).  counts[4] (device) = { n_dead, n_alive, W_lo, W_hi },
+ * W = sum q_i in 64 bits.  The growth step plans with min_opacity = 0 and no dead_src: every row with o_i > 0 has weight.  The prefixes
+ * of q and of the dead flag (two-level scans, no atomics) stay in scratch (>= gsrast_mcmc_scratch_bytes(P, n)) for the calls below.
+ *
+ * gsrast_mcmc_sample -- torch.multinomial(weights, n, replacement=True) as integer arithmetic: draws[n] int64 in [0, 2^62) (the
+ * caller's torch.randint), draw j targets t_j = floor(draws[j] * W / 2^62) and selects the smallest i whose inclusive prefix of q
+ * exceeds t_j; a zero-weight row is never selected.  src_out[n] int32 (-1 when W = 0); the draws per source (bincount) stay in scratch
+ * and are copied to count_out [P] uint32 when it is not NULL.  Exact: the same q and draws give the same src on every run and rank.
+ *
+ * gsrast_mcmc_relocate -- relocate's index assignments, in place (groups: dst / dst_m / dst_v are the arrays; src / src_m / src_v NULL
+ * or equal to them).  For every source s with count[s] > 0, from the PRE-call values:  r = min(count + 1, 51);  o' = 1 - (1 - o)^(1/r);
+ * denom = sum_{i=1..r} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) o'^(k+1);  s' = (o / denom) exp(scaling);  o' clamped to
+ * [min_opacity, 1 - FLT_EPSILON];  stored: logit(o'), log(s').  denom is accumulated in fp64 (gsplat: fp32) -- the one deliberate
+ * difference.  The j-th dead row in index order (j < n <= n_dead) becomes a bit copy of row src[j] in every group, except that the
+ * OPACITY (width 1) and SCALING (width 3) groups take the source's new values; row src[j] takes them too; exp_avg / exp_avg_sq of every
+ * group become 0 at the sampled sources; a dead row keeps its own moments (as the 3DGS-MCMC code and gsplat leave them).  Every row has
+ * one writer.  counts_host: the plan's counts as read back.
+ *
+ * gsrast_mcmc_grow -- sample_add: dst [P + n][width].  Rows [0, P) are bit copies of src with their moments, except that sampled sources
+ * carry the new opacity and scaling (computed as above); row P + j is a copy of the updated row src[j] with zero moments.  Nothing in
+ * the source arrays is written.  counts_host may be NULL (then W is not checked).
+ *
+ * gsrast_mcmc_noise -- inject_noise_to_position, one launch, in place:  xyz[i] += Sigma_i (noise[i] * gate_i * scale [* row_scale[i]]),
+ * Sigma_i = R(q / |q|) diag(exp(scaling))^2 R(q / |q|)^T over rotation [P][4] raw (r, x, y, z; 16-byte aligned), gate_i = 1 / (1 +
+ * exp(-k ((1 - o_i) - x0))) (gsplat: k = 100, x0 = 0.995).  noise [P][3]: the caller's randn; row_scale [P] or NULL; scale: the caller's
+ * xyz_lr * noise_lr.
+ *
+ * Groups: gsrast_densify_group, at most 16, width in [1, 64], moments optional; roles GSRAST_MCMC_*, exactly one OPACITY and one SCALING
+ * group when n > 0.  Refused before any device call (gsrast_last_error): P < 0 or n < 0, P + n > 2^31 - 1, min_opacity outside [0, 1),
+ * more than 16 groups, a width outside [1, 64], an OPACITY group of width != 1 or a SCALING group of width != 3, NULL required pointers,
+ * counts that are not a plan's for this P, n > n_dead (relocate), n > 0 with W = 0.  Profile names: "mcmc_plan" (weights + scan),
+ * "mcmc_sample", "mcmc_apply" (values + apply), "mcmc_noise".  Deterministic: no floating-point atomics; P = 0 and n = 0 are valid. */
+#define GSRAST_MCMC_COPY 0
+#define GSRAST_MCMC_OPACITY 1
+#define GSRAST_MCMC_SCALING 2
+size_t gsrast_mcmc_scratch_bytes(int P, int n /* today's layout depends on P only */);
+int gsrast_mcmc_plan(int P, const float* opacity_logit, const unsigned char* dead_src /* NULL */, float min_opacity, unsigned* weights_out /* [P] */,
+                     char* scratch, unsigned* counts /* device [4] */, void* stream);
+int gsrast_mcmc_sample(int P, int n, const long long* draws /* [n] in [0, 2^62) */, char* scratch, int* src_out /* [n] */,
+                       unsigned* count_out /* [P] or NULL */, void* stream);
+int gsrast_mcmc_relocate(int P, int n, const int* src /* [n] */, char* scratch, const unsigned* counts_host /* [4], as read back */, float min_opacity,
+                         int n_groups /* <= 16 */, const gsrast_densify_group* groups /* host array */, void* stream);
+int gsrast_mcmc_grow(int P, int n, const int* src /* [n] */, char* scratch, const unsigned* counts_host /* [4] or NULL */, float min_opacity,
+                     int n_groups /* <= 16 */, const gsrast_densify_group* groups /* host array */, void* stream);
+int gsrast_mcmc_noise(int P, float* xyz, const float* rotation, const float* scaling, const float* opacity_logit, const float* noise /* [P][3] */,
+                      const float* row_scale /* [P] or NULL */, float scale, float k, float x0, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

@@ -25,6 +25,7 @@
 #include "gsrast_epilogue.h"
 #include "gsrast_adam.h"
 #include "gsrast_densify.h"
+#include "gsrast_mcmc.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include "gsrast_exchange.h"
@@ -143,7 +144,9 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 // ---- per-kernel device timing (option "profile") -------------------------------------------
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
-                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_ADAM_VISIBLE, K_COUNT };
+                K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_ADAM_VISIBLE,
+                K_MCMC_PLAN, K_MCMC_SAMPLE, K_MCMC_APPLY, K_MCMC_NOISE, K_COUNT };
+static_assert(K_COUNT <= 32, "option \"profile\" is one 32-bit word: a bit per kernel id");
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
@@ -154,7 +157,9 @@ const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "sca
                                             "contrib_blend", "contrib_finish" /* csrc/gsrast_contrib.h: gsrast_contrib_stats */,
                                             "features_fwd", "features_bwd" /* csrc/gsrast_features.h: gsrast_features_forward / _backward (one entry per call: all its passes) */,
                                             "distort_fwd", "distort_bwd" /* csrc/gsrast_distort.h: gsrast_distortion_forward / _backward */,
-                                            "adam_step_visible" /* csrc/gsrast_adam.h: gsrast_adam_step_visible */ };
+                                            "adam_step_visible" /* csrc/gsrast_adam.h: gsrast_adam_step_visible */,
+                                            "mcmc_plan" /* csrc/gsrast_mcmc.h: gsrast_mcmc_plan (weights + scan) */, "mcmc_sample" /* gsrast_mcmc_sample */,
+                                            "mcmc_apply" /* gsrast_mcmc_relocate / _grow (values + apply) */, "mcmc_noise" /* gsrast_mcmc_noise */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -1927,6 +1932,154 @@ int gsrast_densify_stats_update(int P, const float* grad, const float* visibilit
     ProfScope ps(K_DENSIFY_STATS, s);
     densify_stats_update_kernel<<<(unsigned)(((size_t)P + 255) / 256), 256, 0, s>>>(P, grad, visibility_count, radii, accum, denom, max_radii, grad_is_mean ? 1 : 0);
     GS_LAUNCHED("densify_stats_update");
+    return GSRAST_OK;
+}
+
+// ---- MCMC densification (gsrast_mcmc.h) ----------------------------------------------------------------------------
+// scratch: header = counts (4 words) | in-run weight prefix per row | dead byte per row | workgroup weight sums (64 bit) and dead sums,
+//          scanned in place by the plan | draws per source | the sources' new values [P][4]
+namespace {
+struct McmcLayout { size_t hdr, run_prefix, dead, wg_weight, wg_dead, count, vals, total; uint32_t nb; };
+McmcLayout mcmc_layout(size_t P)
+{
+    McmcLayout L; size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    const size_t Pp = P ? P : 1;
+    L.nb = (uint32_t)((P + MC_RUN - 1) / MC_RUN);
+    const size_t nbp = L.nb ? L.nb : 1;
+    L.hdr = take(MC_HDR_WORDS * 4); L.run_prefix = take(Pp * 4); L.dead = take(Pp); L.wg_weight = take(nbp * 8); L.wg_dead = take(nbp * 4);
+    L.count = take(Pp * 4); L.vals = take(Pp * 16);
+    L.total = o + 256;
+    return L;
+}
+// what relocate and grow share: the argument checks, the values pass and the apply launch
+int mcmc_apply(const char* who, bool grow, int P, int n, const int* src, char* scratch, const unsigned* counts_host, float min_opacity,
+               int n_groups, const gsrast_densify_group* groups, hipStream_t s)
+{
+    char msg[160];
+    auto refuse = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(GSRAST_E_ARG, msg); };
+    if (P < 0 || n < 0) return refuse("negative P / n");
+    if ((long long)P + (long long)n > 0x7FFFFFFFll) return refuse("P + n exceeds 2^31 - 1");
+    if (!(min_opacity >= 0.0f && min_opacity < 1.0f)) return refuse("min_opacity must be in [0, 1)");
+    if (n_groups < 0 || n_groups > MC_MAX_GROUPS) return refuse("at most 16 groups");
+    if (!scratch || (n_groups > 0 && !groups) || (n > 0 && !src)) return refuse("NULL scratch / groups / src");
+    if (!grow && !counts_host) return refuse("NULL counts");
+    if (P == 0 && n > 0) return refuse("n > 0 draws from an empty model");
+    if (counts_host) {
+        const unsigned long long W = (unsigned long long)counts_host[2] | ((unsigned long long)counts_host[3] << 32);
+        if ((unsigned long long)counts_host[0] + counts_host[1] != (unsigned long long)P || W > ((unsigned long long)counts_host[1] << 24) || (counts_host[1] > 0 && W < counts_host[1]))
+            return refuse("counts are not those of a plan for this P");
+        if (n > 0 && W == 0) return refuse("n > 0 draws from a total weight of 0 (no alive row)");
+        if (!grow && (unsigned)n > counts_host[0]) return refuse("n exceeds the number of dead rows");
+    }
+    McApplyArgs a{};
+    const float *opacity = nullptr, *scaling = nullptr;
+    for (int k = 0; k < n_groups; k++) {
+        const gsrast_densify_group& g = groups[k];
+        if (g.width < 1 || g.width > MC_MAX_WIDTH) return refuse("group width must be in [1, 64]");
+        if (g.role != GSRAST_MCMC_COPY && g.role != GSRAST_MCMC_OPACITY && g.role != GSRAST_MCMC_SCALING) return refuse("unknown group role");
+        if (g.role == GSRAST_MCMC_OPACITY && g.width != 1) return refuse("the opacity role needs width 1");
+        if (g.role == GSRAST_MCMC_SCALING && g.width != 3) return refuse("the scaling role needs width 3");
+        if ((g.role == GSRAST_MCMC_OPACITY && opacity) || (g.role == GSRAST_MCMC_SCALING && scaling)) return refuse("more than one opacity / scaling group");
+        if (grow) {
+            if ((g.src_m && !g.dst_m) || (g.src_v && !g.dst_v) || (g.dst_m && !g.src_m) || (g.dst_v && !g.src_v)) return refuse("src_m / src_v and dst_m / dst_v go together");
+            if ((P > 0 && !g.src) || (P + n > 0 && !g.dst)) return refuse("NULL src / dst");
+        } else {
+            if ((g.src && g.src != g.dst) || (g.src_m && g.src_m != g.dst_m) || (g.src_v && g.src_v != g.dst_v)) return refuse("in place: src / src_m / src_v must be NULL or equal dst / dst_m / dst_v");
+            if (P > 0 && !g.dst) return refuse("NULL dst");
+        }
+        a.grp[k] = grow ? McGroup{ g.src, g.src_m, g.src_v, g.dst, g.dst_m, g.dst_v, g.width, g.role }
+                        : McGroup{ g.dst, g.dst_m, g.dst_v, g.dst, g.dst_m, g.dst_v, g.width, g.role };
+        if (g.role == GSRAST_MCMC_OPACITY) opacity = a.grp[k].src;
+        if (g.role == GSRAST_MCMC_SCALING) scaling = a.grp[k].src;
+    }
+    if (n > 0 && P > 0 && (!opacity || !scaling)) return refuse("one opacity and one scaling group are required");
+    if (P == 0 || n_groups == 0 || (!grow && n == 0)) return GSRAST_OK;
+    const McmcLayout L = mcmc_layout((size_t)P);
+    a.n_groups = n_groups; a.P = P; a.n = n; a.src = src;
+    a.count = at<uint32_t>(scratch, L.count); a.vals = at<float>(scratch, L.vals);
+    a.dead = at<unsigned char>(scratch, L.dead); a.wg_dead = at<uint32_t>(scratch, L.wg_dead);
+    ProfScope ps(K_MCMC_APPLY, s);
+    if (n > 0) {
+        mcmc_values_kernel<<<L.nb, MC_RUN, 0, s>>>(P, a.count, opacity, scaling, min_opacity, at<float>(scratch, L.vals));
+        GS_LAUNCHED("mcmc_values");
+    }
+    if (grow) {
+        mcmc_apply_kernel<true><<<(unsigned)(((size_t)P + (size_t)n + MC_RUN - 1) / MC_RUN), MC_RUN, 0, s>>>(a);
+        GS_LAUNCHED("mcmc_grow");
+    } else {
+        mcmc_apply_kernel<false><<<L.nb, MC_RUN, 0, s>>>(a);
+        GS_LAUNCHED("mcmc_relocate");
+    }
+    return GSRAST_OK;
+}
+}
+size_t gsrast_mcmc_scratch_bytes(int P, int n) { (void)n; return mcmc_layout(P > 0 ? (size_t)P : 0).total; }
+
+int gsrast_mcmc_plan(int P, const float* opacity_logit, const unsigned char* dead_src, float min_opacity, unsigned* weights_out,
+                     char* scratch, unsigned* counts, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "mcmc_plan: negative P");
+    if (!(min_opacity >= 0.0f && min_opacity < 1.0f)) return fail(GSRAST_E_ARG, "mcmc_plan: min_opacity must be in [0, 1)");
+    if (!scratch || !counts) return fail(GSRAST_E_ARG, "mcmc_plan: NULL scratch / counts");
+    if (P > 0 && (!opacity_logit || !weights_out)) return fail(GSRAST_E_ARG, "mcmc_plan: NULL opacity_logit / weights_out");
+    const McmcLayout L = mcmc_layout((size_t)P);
+    ProfScope ps(K_MCMC_PLAN, s);
+    if (L.nb) {
+        mcmc_weights_kernel<<<L.nb, MC_RUN, 0, s>>>(P, opacity_logit, dead_src, min_opacity, weights_out, at<uint32_t>(scratch, L.run_prefix),
+                                                   at<unsigned char>(scratch, L.dead), at<unsigned long long>(scratch, L.wg_weight), at<uint32_t>(scratch, L.wg_dead));
+        GS_LAUNCHED("mcmc_weights");
+    }
+    mcmc_scan_kernel<<<1, MC_RUN, 0, s>>>(at<unsigned long long>(scratch, L.wg_weight), at<uint32_t>(scratch, L.wg_dead), L.nb, (uint32_t)P,
+                                          at<uint32_t>(scratch, L.hdr), counts);
+    GS_LAUNCHED("mcmc_scan");
+    return GSRAST_OK;
+}
+
+int gsrast_mcmc_sample(int P, int n, const long long* draws, char* scratch, int* src_out, unsigned* count_out, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0 || n < 0) return fail(GSRAST_E_ARG, "mcmc_sample: negative P / n");
+    if (!scratch) return fail(GSRAST_E_ARG, "mcmc_sample: NULL scratch");
+    if (n > 0 && (!draws || !src_out)) return fail(GSRAST_E_ARG, "mcmc_sample: NULL draws / src_out");
+    if (P == 0 && n == 0) return GSRAST_OK;
+    const McmcLayout L = mcmc_layout((size_t)P);
+    uint32_t* count = at<uint32_t>(scratch, L.count);
+    ProfScope ps(K_MCMC_SAMPLE, s);
+    if (P > 0) GS_HIP(hipMemsetAsync(count, 0, (size_t)P * 4, s));
+    if (n > 0) {
+        mcmc_sample_kernel<<<(unsigned)(((size_t)n + MC_RUN - 1) / MC_RUN), MC_RUN, 0, s>>>(P, n, draws, at<uint32_t>(scratch, L.hdr), at<unsigned long long>(scratch, L.wg_weight),
+                                                                                          L.nb, at<uint32_t>(scratch, L.run_prefix), src_out, count);
+        GS_LAUNCHED("mcmc_sample");
+    }
+    if (count_out && P > 0) GS_HIP(hipMemcpyAsync(count_out, count, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
+    return GSRAST_OK;
+}
+
+int gsrast_mcmc_relocate(int P, int n, const int* src, char* scratch, const unsigned* counts_host, float min_opacity, int n_groups,
+                         const gsrast_densify_group* groups, void* stream)
+{
+    return mcmc_apply("mcmc_relocate", false, P, n, src, scratch, counts_host, min_opacity, n_groups, groups, (hipStream_t)stream);
+}
+
+int gsrast_mcmc_grow(int P, int n, const int* src, char* scratch, const unsigned* counts_host, float min_opacity, int n_groups,
+                     const gsrast_densify_group* groups, void* stream)
+{
+    return mcmc_apply("mcmc_grow", true, P, n, src, scratch, counts_host, min_opacity, n_groups, groups, (hipStream_t)stream);
+}
+
+int gsrast_mcmc_noise(int P, float* xyz, const float* rotation, const float* scaling, const float* opacity_logit, const float* noise,
+                      const float* row_scale, float scale, float k, float x0, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "mcmc_noise: negative P");
+    if (P == 0) return GSRAST_OK;
+    if (!xyz || !rotation || !scaling || !opacity_logit || !noise) return fail(GSRAST_E_ARG, "mcmc_noise: NULL pointer");
+    if (((uintptr_t)rotation & 15) != 0) return fail(GSRAST_E_ARG, "mcmc_noise: rotation must be 16-byte aligned");
+    ProfScope ps(K_MCMC_NOISE, s);
+    mcmc_noise_kernel<<<(unsigned)(((size_t)P + MC_RUN - 1) / MC_RUN), MC_RUN, 0, s>>>(P, xyz, reinterpret_cast<const float4*>(rotation), scaling, opacity_logit, noise, row_scale, scale, k, x0);
+    GS_LAUNCHED("mcmc_noise");
     return GSRAST_OK;
 }
 

@@ -44,6 +44,7 @@ EXPORTS = (
     "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
     "gsrast_features_forward", "gsrast_features_backward",
     "gsrast_distortion_forward", "gsrast_distortion_backward",
+    "gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -157,6 +158,7 @@ class DensifyGroupStruct(C.Structure):
 
 
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2      # include/gsrast.h: GSRAST_DENSIFY_*
+MCMC_COPY, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2           # include/gsrast.h: GSRAST_MCMC_* (the role of a gsrast_densify_group in the mcmc calls)
 
 
 class PlaneStruct(C.Structure):
@@ -270,6 +272,13 @@ def lib() -> C.CDLL:
     L.gsrast_densify_apply.argtypes = [ci, ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp, vp, vp, vp]
     L.gsrast_densify_stats_update.restype = ci
     L.gsrast_densify_stats_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.gsrast_mcmc_scratch_bytes.restype = C.c_size_t
+    L.gsrast_mcmc_scratch_bytes.argtypes = [ci, ci]
+    L.gsrast_mcmc_plan.restype = L.gsrast_mcmc_sample.restype = L.gsrast_mcmc_relocate.restype = L.gsrast_mcmc_grow.restype = L.gsrast_mcmc_noise.restype = ci
+    L.gsrast_mcmc_plan.argtypes = [ci, vp, vp, cf, vp, vp, vp, vp]
+    L.gsrast_mcmc_sample.argtypes = [ci, ci, vp, vp, vp, vp, vp]
+    L.gsrast_mcmc_relocate.argtypes = L.gsrast_mcmc_grow.argtypes = [ci, ci, vp, vp, C.POINTER(C.c_uint), cf, ci, C.POINTER(DensifyGroupStruct), vp]
+    L.gsrast_mcmc_noise.argtypes = [ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp]
     L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
     L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
     L.gsrast_hexplane_forward.restype = ci

@@ -16,6 +16,15 @@ is the reference's layout row for row:
   [ originals !split && !pruned | clones | split copy 0 | copy 1 | ... ]      (every part in index order)
 and is bit-identical from run to run and from rank to rank (no atomics), so replicated models stay replicated.
 
+The second policy, 3DGS-MCMC as gsplat's MCMCStrategy runs it (include/gsrast.h: gsrast_mcmc_*, csrc/gsrast_mcmc.h), sits beside it:
+  gsplat/strategy/ops.py relocate + gsplat/relocation.py compute_relocation                                        -> mcmc_relocate
+  gsplat/strategy/ops.py sample_add                                                                                -> mcmc_grow
+  gsplat/strategy/ops.py inject_noise_to_position                                                                  -> mcmc_inject_noise
+  MCMCStrategy.step_post_backward's refine branch (relocate, then add)                                             -> mcmc_refine
+A fixed budget (`cap_max`), no gradient thresholds, dead Gaussians re-used instead of pruned.  The multinomial is integer arithmetic on
+fixed-point weights, so the same draws select the same rows on every rank.  Two stated deviations from gsplat: compute_relocation's
+alternating sum runs in fp64, and a model with no alive row is a no-op where torch.multinomial would raise.
+
 What stays the caller's: `reset_opacity`; the integral `get_intergral() < min_intergral` (it needs the hex-plane model) and the colmap
 `z < 4.5` rule -- both arrive here as `prune_mask`; per-row `lr` tensors of the old P (GaussianAdam.step raises on a mismatch) and the
 `view_parallel.StepBucket`, which is rebuilt after P changed.  GPU tensors only; no fallback.
@@ -311,3 +320,167 @@ def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras:
         contrib.sums, contrib.weight_max = rest[:2]
         rest = rest[2:]
     return counts, new, rest
+
+
+# ---- 3DGS-MCMC ------------------------------------------------------------------------------------------------------------------
+DRAW_RANGE = 1 << 62      # draws are int64 in [0, DRAW_RANGE): draw d targets floor(d * W / 2^62) of the total weight W
+
+
+def _mcmc_moved(opt, names: Dict[str, str], extras: Iterable[torch.Tensor]):
+    """(rows, P, device, the opacity parameter, [(tensor, exp_avg, exp_avg_sq, role)] of every group and extra)."""
+    rows, P = _optimizer_groups(opt)
+    by_name = {g.get("name"): p for g, p, _ in rows}
+    for role in ("scaling", "opacity"):
+        if names.get(role) not in by_name:
+            raise RuntimeError(f"fused_densify: no group named {names.get(role)!r} (names[{role!r}])")
+    scaling, opacity = by_name[names["scaling"]], by_name[names["opacity"]]
+    if _rows_width(scaling) != 3 or _rows_width(opacity) != 1:
+        raise RuntimeError("fused_densify: scaling / opacity must be [P,3] / [P,1]")
+    dev = _C._require_gpu(opacity)
+    role_of = {id(scaling): _C.MCMC_SCALING, id(opacity): _C.MCMC_OPACITY}
+    moved = [(p, st["exp_avg"] if st else None, st["exp_avg_sq"] if st else None, role_of.get(id(p), _C.MCMC_COPY)) for _, p, st in rows]
+    for k, t in enumerate(extras):
+        _check_param(t, f"extra tensor {k}", P)
+        moved.append((t, None, None, _C.MCMC_COPY))
+    if len(moved) > MAX_GROUPS:
+        raise RuntimeError(f"fused_densify: {len(moved)} arrays to move, at most {MAX_GROUPS} per launch")
+    return rows, P, dev, opacity, moved
+
+
+def _mcmc_plan(P: int, dev: torch.device, opacity: torch.Tensor, dead_u8: Optional[torch.Tensor], min_opacity: float, n: int = 0):
+    """gsrast_mcmc_plan and the read-back of its counts (the one synchronisation).  Returns (scratch, weights [P] int32, the four words,
+    n_dead, n_alive, W)."""
+    L = _C.lib()
+    scratch = torch.empty(int(L.gsrast_mcmc_scratch_bytes(P, n)), dtype=torch.uint8, device=dev)
+    weights = torch.empty(P, dtype=torch.int32, device=dev)
+    counts_dev = torch.empty(4, dtype=torch.int32, device=dev)
+    rc = L.gsrast_mcmc_plan(P, _C._ptr(opacity), _C._ptr(dead_u8), float(min_opacity), _C._ptr(weights), scratch.data_ptr(), counts_dev.data_ptr(), _C._stream_of(dev))
+    if rc != 0:
+        raise _C._err(rc, "gsrast_mcmc_plan")
+    host = [int(v) & 0xFFFFFFFF for v in counts_dev.cpu().tolist()]
+    return scratch, weights, host, host[0], host[1], host[2] | (host[3] << 32)
+
+
+def _mcmc_sample(P: int, n: int, dev: torch.device, scratch: torch.Tensor, generator, draws: Optional[torch.Tensor]) -> torch.Tensor:
+    """n draws (torch.randint on the device unless given) -> src [n] int32."""
+    if draws is None:
+        draws = torch.randint(0, DRAW_RANGE, (n,), generator=generator, device=dev, dtype=torch.int64)
+    else:
+        if tuple(draws.shape) != (n,) or draws.dtype != torch.int64 or draws.device != dev:
+            raise RuntimeError(f"fused_densify: draws must be int64 [{n}] on {dev} (got {draws.dtype} {tuple(draws.shape)} on {draws.device})")
+        draws = draws.contiguous()
+    src = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = _C.lib().gsrast_mcmc_sample(P, n, _C._ptr(draws), scratch.data_ptr(), _C._ptr(src), None, _C._stream_of(dev))
+    if rc != 0:
+        raise _C._err(rc, "gsrast_mcmc_sample")
+    return src
+
+
+def _check_min_opacity(min_opacity: float) -> float:
+    if not 0.0 <= float(min_opacity) < 1.0:
+        raise ValueError(f"min_opacity must be in [0, 1) (got {min_opacity})")
+    return float(min_opacity)
+
+
+@torch.no_grad()
+def mcmc_relocate(opt, *, min_opacity: float = 0.005, dead_mask: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                  draws: Optional[torch.Tensor] = None, extras: Iterable[torch.Tensor] = (), names: Dict[str, str] = DEFAULT_NAMES) -> Dict[str, int]:
+    """gsplat's relocate (strategy/ops.py) on `opt`'s per-Gaussian groups, in place: a row is dead where sigmoid(opacity) <= min_opacity or
+    dead_mask (bool / uint8 [P]) is set; the j-th dead row in index order becomes a copy of an alive row sampled with probability
+    proportional to its opacity, both get compute_relocation's opacity and scale for the number of copies, the sampled sources' Adam
+    moments become zero and the dead rows keep theirs.  draws: int64 [n_dead] in [0, 2^62), drawn with torch.randint(..., generator=) on
+    the device unless given.  extras: [P, ...] float32 tensors without moments, copied like any other group.  The parameters stay the
+    same leaf objects and opt.state keeps its keys.  No dead row, or no alive row (where torch.multinomial would raise): nothing changes.
+    Returns dict(n_dead, n_alive, n_relocated)."""
+    min_opacity = _check_min_opacity(min_opacity)
+    rows, P, dev, opacity, moved = _mcmc_moved(opt, names, extras)
+    dead_u8 = _mask_u8(dead_mask, P, dev) if dead_mask is not None else None
+    with _C._on_device(dev):
+        scratch, _, host, n_dead, n_alive, _W = _mcmc_plan(P, dev, opacity, dead_u8, min_opacity)
+        counts = dict(n_dead=n_dead, n_alive=n_alive, n_relocated=0)
+        if n_dead == 0 or n_alive == 0:
+            return counts
+        src = _mcmc_sample(P, n_dead, dev, scratch, generator, draws)
+        arr = (_C.DensifyGroupStruct * len(moved))()
+        for a, (t, m, v, role) in zip(arr, moved):
+            a.dst, a.dst_m, a.dst_v, a.width, a.role = _C._ptr(t), _C._ptr(m), _C._ptr(v), _rows_width(t), role
+        rc = _C.lib().gsrast_mcmc_relocate(P, n_dead, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr, _C._stream_of(dev))
+        if rc != 0:
+            raise _C._err(rc, "gsrast_mcmc_relocate")
+    counts["n_relocated"] = n_dead
+    return counts
+
+
+@torch.no_grad()
+def mcmc_grow(opt, *, cap_max: int, growth: float = 1.05, min_opacity: float = 0.005, generator: Optional[torch.Generator] = None,
+              draws: Optional[torch.Tensor] = None, extras: Iterable[torch.Tensor] = (), names: Dict[str, str] = DEFAULT_NAMES):
+    """gsplat's sample_add (strategy/ops.py): n = max(0, min(cap_max, int(growth * P)) - P) rows are appended, copies of rows sampled with
+    probability proportional to opacity (every row: sample_add samples from opacities.flatten()); a sampled row and its copies get
+    compute_relocation's opacity (clamped to [min_opacity, 1 - eps]) and scale.  The first P rows keep their moments, the new rows start
+    from zero.  Every group's params[0] becomes a fresh leaf (as densify_and_prune installs them; GaussianAdam's step count goes on);
+    n = 0 returns without installing anything.  draws: int64 [n] in [0, 2^62).  Returns (dict(n_added, P), {group name: parameter},
+    [extras at the new P])."""
+    min_opacity = _check_min_opacity(min_opacity)
+    extras = list(extras)
+    rows, P, dev, opacity, moved = _mcmc_moved(opt, names, extras)
+    n = max(0, min(int(cap_max), int(float(growth) * P)) - P)
+    if n == 0:
+        return dict(n_added=0, P=P), {g.get("name"): p for g, p, _ in rows}, extras
+    with _C._on_device(dev):
+        scratch, _, host, _, _, W = _mcmc_plan(P, dev, opacity, None, 0.0, n)
+        if W == 0:
+            raise RuntimeError("fused_densify: mcmc_grow on a model whose every opacity is 0: nothing to sample from")
+        src = _mcmc_sample(P, n, dev, scratch, generator, draws)
+        arr = (_C.DensifyGroupStruct * len(moved))()
+        out = []
+        for a, (t, m, v, role) in zip(arr, moved):
+            shape = (P + n,) + tuple(t.shape[1:])
+            dst = torch.empty(shape, dtype=torch.float32, device=dev)
+            dm = torch.empty(shape, dtype=torch.float32, device=dev) if m is not None else None
+            dv = torch.empty(shape, dtype=torch.float32, device=dev) if v is not None else None
+            a.src, a.src_m, a.src_v, a.dst, a.dst_m, a.dst_v = _C._ptr(t), _C._ptr(m), _C._ptr(v), _C._ptr(dst), _C._ptr(dm), _C._ptr(dv)
+            a.width, a.role = _rows_width(t), role
+            out.append((dst, dm, dv))
+        rc = _C.lib().gsrast_mcmc_grow(P, n, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr, _C._stream_of(dev))
+        if rc != 0:
+            raise _C._err(rc, "gsrast_mcmc_grow")
+    new = _install(opt, rows, out[: len(rows)])
+    return dict(n_added=n, P=P + n), new, [r[0] for r in out[len(rows):]]
+
+
+@torch.no_grad()
+def mcmc_inject_noise(xyz: torch.Tensor, rotation: torch.Tensor, scaling: torch.Tensor, opacity: torch.Tensor, *, scale: float,
+                      row_scale: Optional[torch.Tensor] = None, k: float = 100.0, x0: float = 0.995,
+                      generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> None:
+    """gsplat's inject_noise_to_position (strategy/ops.py), one launch, `xyz` updated in place:
+      xyz += Sigma (noise * gate * scale [* row_scale]),  Sigma = R(q / |q|) diag(exp(scaling))^2 R^T,  gate = 1 / (1 + exp(-k ((1 - sigmoid(opacity)) - x0)))
+    over the raw parameters xyz [P,3], rotation [P,4] (r, x, y, z), scaling [P,3], opacity [P,1].  scale: the caller's xyz_lr * noise_lr;
+    row_scale [P]: a per-Gaussian factor on it (per-row learning rates).  noise [P,3]: torch.randn(..., generator=) on the device unless given."""
+    P = int(xyz.shape[0])
+    for t, name, w in ((xyz, "xyz", 3), (rotation, "rotation", 4), (scaling, "scaling", 3), (opacity, "opacity", 1)):
+        _check_param(t, name, P)
+        if _rows_width(t) != w:
+            raise RuntimeError(f"fused_densify: {name} must have {w} floats per Gaussian (got {tuple(t.shape)})")
+    dev = _C._require_gpu(xyz)
+    if noise is None:
+        noise = torch.randn((P, 3), generator=generator, device=dev, dtype=torch.float32)
+    else:
+        if tuple(noise.shape) != (P, 3) or noise.device != dev:
+            raise RuntimeError(f"fused_densify: noise must be [{P}, 3] on {dev}, got {tuple(noise.shape)} on {noise.device}")
+        noise = noise.to(torch.float32).contiguous()
+    rs = _flat_f32(row_scale, "row_scale", P, dev) if row_scale is not None else None
+    with _C._on_device(dev):
+        rc = _C.lib().gsrast_mcmc_noise(P, _C._ptr(xyz), _C._ptr(rotation), _C._ptr(scaling), _C._ptr(opacity), _C._ptr(noise), _C._ptr(rs),
+                                        float(scale), float(k), float(x0), _C._stream_of(dev))
+    if rc != 0:
+        raise _C._err(rc, "gsrast_mcmc_noise")
+
+
+def mcmc_refine(opt, *, cap_max: int, min_opacity: float = 0.005, growth: float = 1.05, generator: Optional[torch.Generator] = None,
+                names: Dict[str, str] = DEFAULT_NAMES):
+    """MCMCStrategy's refine step in gsplat's order: mcmc_relocate, then mcmc_grow (whose weights see the relocated opacities).
+    Returns (dict(n_dead, n_alive, n_relocated, n_added, P), {group name: parameter})."""
+    counts = mcmc_relocate(opt, min_opacity=min_opacity, generator=generator, names=names)
+    grown, new, _ = mcmc_grow(opt, cap_max=cap_max, growth=growth, min_opacity=min_opacity, generator=generator, names=names)
+    counts.update(grown)
+    return counts, new
