@@ -828,6 +828,39 @@ int gsrast_mcmc_grow(int P, int n, const int* src /* [n] */, char* scratch, cons
 int gsrast_mcmc_noise(int P, float* xyz, const float* rotation, const float* scaling, const float* opacity_logit, const float* noise /* [P][3] */,
                       const float* row_scale /* [P] or NULL */, float scale, float k, float x0, void* stream);
 
+/* ---- fused 3-layer MLP: the deformation heads between the residual-field lookup and the rasterizer ----
+ * y = [sigmoid] (W3 relu(W2 relu(W1 [x | x_tail] + b1) + b2) + b3) over N rows, fp32 on the f32-input matrix instruction; replaces the
+ * nn.Sequential(Linear, ReLU, Linear, ReLU, Linear[, Sigmoid]) heads motion_mlp / rot_mlp / shs_mlp / opacity_mlp of scene/saro_gaussian.py.
+ * x [N][d_x], x_tail [N][d_tail] (read behind x's columns, no gradient; NULL when d_tail = 0), weights in nn.Linear's [out][in] layout,
+ * y [N][d_out]; all contiguous fp32 device pointers.  The hidden activations never reach global memory: the backward recomputes them.
+ * Shapes: 1 <= d_x, d_tail >= 0, d_x + d_tail <= 64; h1, h2 in {32, 64, 96, 128}; 1 <= d_out <= 64; n >= 0.  Anything else is refused
+ * (GSRAST_E_ARG, gsrast_last_error) before any device call, as are NULL required pointers; there is no other path.
+ *
+ * gsrast_mlp3_forward  writes y.  No scratch.
+ * gsrast_mlp3_backward reads x, x_tail, dy [N][d_out] and, for the sigmoid head, y; writes the gradients whose pointer is not NULL:
+ *   dx [N][d_x], dw1 [h1][d_in], db1, dw2 [h2][h1], db2, dw3 [d_out][h2], db3 (each OVERWRITTEN; with n = 0 they are 0).  Each workgroup
+ *   keeps its share of the weight gradients in registers over all of its row tiles, stores it to scratch (>= gsrast_mlp3_scratch_bytes,
+ *   a function of the workgroup count and the widths, never of n) and a second launch sums the shares in workgroup order: no
+ *   floating-point atomics, bit-identical results for the same workgroup count.  scratch may be NULL when no weight gradient is wanted.
+ * workgroups: 0 = the library's default for the device (forward two per CU, backward one per CU: what their LDS images admit); a call never
+ * launches more workgroups than it has 64-row tiles.
+ * The backward is one kernel issued as a chain of ceil(n / (512 x workgroups)) launches on `stream` (no accumulator sums more than 512
+ * rows in fp32): 8 at n = 1 M on 256 workgroups; a forced small workgroup count with a large n means that many launches.
+ * A NaN pre-activation stays NaN through the ReLUs, as torch.relu.
+ * Profile names: "mlp_fwd", "mlp_bwd" (ids behind the 32 bits of option "profile": timed when the option is -1). */
+typedef struct {
+    int n, d_x, d_tail, h1, h2, d_out;
+    int sigmoid;                /* 1: the head ends in a Sigmoid */
+    const float *x, *x_tail;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    float* y;                   /* forward: out; backward: in (sigmoid head only) */
+    const float* dy;            /* backward only, as everything below */
+    float *dx, *dw1, *db1, *dw2, *db2, *dw3, *db3;      /* NULL: not wanted, not computed */
+} gsrast_mlp3;
+size_t gsrast_mlp3_scratch_bytes(const gsrast_mlp3* d /* dims only */, int workgroups);      /* 0: the dims are refused (gsrast_last_error) */
+int gsrast_mlp3_forward(const gsrast_mlp3* d, int workgroups, void* stream);
+int gsrast_mlp3_backward(const gsrast_mlp3* d, int workgroups, char* scratch, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

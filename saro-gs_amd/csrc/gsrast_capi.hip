@@ -26,6 +26,7 @@
 #include "gsrast_adam.h"
 #include "gsrast_densify.h"
 #include "gsrast_mcmc.h"
+#include "gsrast_mlp.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include "gsrast_exchange.h"
@@ -145,8 +146,9 @@ int fail(int code, const char* what, hipError_t e = hipSuccess)
 enum KernelId { K_PREPROCESS_FWD, K_SORT_DEPTH, K_SCAN_TILES, K_EMIT, K_SORT_TILE, K_RANGES, K_BLEND_FWD,
                 K_BLEND_BWD, K_PREPROCESS_BWD, K_MARK_VISIBLE, K_LOSS_FWD, K_LOSS_BWD, K_COLOR, K_SH_DERIVS, K_CUT_REDO, K_LATE_ZERO, K_GREC_ZERO,
                 K_DENSIFY_CLASSIFY, K_DENSIFY_SCAN, K_DENSIFY_APPLY, K_DENSIFY_STATS, K_CONTRIB_BLEND, K_CONTRIB_FINISH, K_FEATURES_FWD, K_FEATURES_BWD, K_DISTORT_FWD, K_DISTORT_BWD, K_ADAM_VISIBLE,
-                K_MCMC_PLAN, K_MCMC_SAMPLE, K_MCMC_APPLY, K_MCMC_NOISE, K_COUNT };
-static_assert(K_COUNT <= 32, "option \"profile\" is one 32-bit word: a bit per kernel id");
+                K_MCMC_PLAN, K_MCMC_SAMPLE, K_MCMC_APPLY, K_MCMC_NOISE, K_MLP_FWD, K_MLP_BWD, K_COUNT };
+// option "profile" is one 32-bit word, a bit per kernel id: ids 0 .. 31 have a bit of their own, the ids behind them are timed when the word is -1 (all)
+static_assert(K_MCMC_NOISE == 31, "the ids with a bit of their own");
 const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "scan_tiles", "emit_instances",
                                             "sort_tile", "tile_ranges", "blend_fwd", "blend_bwd",
                                             "preprocess_bwd", "mark_visible", "loss_fwd", "loss_bwd", "preprocess_color", "sh_dir_derivs",
@@ -159,7 +161,8 @@ const char* const kKernelNames[K_COUNT] = { "preprocess_fwd", "sort_depth", "sca
                                             "distort_fwd", "distort_bwd" /* csrc/gsrast_distort.h: gsrast_distortion_forward / _backward */,
                                             "adam_step_visible" /* csrc/gsrast_adam.h: gsrast_adam_step_visible */,
                                             "mcmc_plan" /* csrc/gsrast_mcmc.h: gsrast_mcmc_plan (weights + scan) */, "mcmc_sample" /* gsrast_mcmc_sample */,
-                                            "mcmc_apply" /* gsrast_mcmc_relocate / _grow (values + apply) */, "mcmc_noise" /* gsrast_mcmc_noise */ };
+                                            "mcmc_apply" /* gsrast_mcmc_relocate / _grow (values + apply) */, "mcmc_noise" /* gsrast_mcmc_noise */,
+                                            "mlp_fwd" /* csrc/gsrast_mlp.h: gsrast_mlp3_forward */, "mlp_bwd" /* gsrast_mlp3_backward (the kernel + the partial-sum reduction) */ };
 thread_local int t_prof_off = 0;      // > 0: the stages below are part of an enclosing one (cut_redo) and not recorded on their own
 struct Pending { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -191,7 +194,7 @@ struct RoctxRange {
 
 struct ProfScope {
     int id; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on; RoctxRange range;
-    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_), on(((g_opt.profile.load() >> id_) & 1) != 0 && (t_prof_off == 0 || id_ == K_CUT_REDO)), range(kKernelNames[id_])
+    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_), on((id_ < 32 ? ((g_opt.profile.load() >> id_) & 1) != 0 : g_opt.profile.load() == -1) && (t_prof_off == 0 || id_ == K_CUT_REDO)), range(kKernelNames[id_])
     {
         if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
     }
@@ -2080,6 +2083,115 @@ int gsrast_mcmc_noise(int P, float* xyz, const float* rotation, const float* sca
     ProfScope ps(K_MCMC_NOISE, s);
     mcmc_noise_kernel<<<(unsigned)(((size_t)P + MC_RUN - 1) / MC_RUN), MC_RUN, 0, s>>>(P, xyz, reinterpret_cast<const float4*>(rotation), scaling, opacity_logit, noise, row_scale, scale, k, x0);
     GS_LAUNCHED("mcmc_noise");
+    return GSRAST_OK;
+}
+
+// ---- fused 3-layer MLP (gsrast_mlp.h) -------------------------------------------------------------------------------
+namespace {
+int mlp3_default_workgroups()      // one workgroup per CU (its LDS images leave room for one)
+{
+    static const int n = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        return cus;
+    }();
+    return n;
+}
+// the checks every entry point shares; 0 or the refusal's code
+int mlp3_check(const char* who, const gsrast_mlp3* d, int workgroups)
+{
+    char msg[160];
+    auto refuse = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(GSRAST_E_ARG, msg); };
+    if (!d) return refuse("NULL descriptor");
+    if (d->n < 0) return refuse("negative N");
+    if (workgroups < 0 || workgroups > 65535) return refuse("workgroups must be in [0, 65535]");
+    if (d->d_x < 1 || d->d_tail < 0) return refuse("D_x must be >= 1 and D_tail >= 0");
+    if ((long long)d->d_x + d->d_tail > MLP_MAX_IO) return refuse("D_in = D_x + D_tail must be in [1, 64]");
+    for (int h : { d->h1, d->h2 }) if (h != 32 && h != 64 && h != 96 && h != 128) return refuse("H1 and H2 must be one of 32, 64, 96, 128");
+    if (d->d_out < 1 || d->d_out > MLP_MAX_IO) return refuse("D_out must be in [1, 64]");
+    if (d->sigmoid != 0 && d->sigmoid != 1) return refuse("sigmoid must be 0 or 1");
+    if (!d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->w3 || !d->b3) return refuse("NULL weight / bias pointer");
+    if (d->n > 0 && (!d->x || (d->d_tail > 0 && !d->x_tail))) return refuse("NULL x / x_tail");
+    return GSRAST_OK;
+}
+Mlp3Args mlp3_args(const gsrast_mlp3* d)
+{
+    Mlp3Args a{};
+    a.n = d->n; a.d_x = d->d_x; a.d_tail = d->d_tail; a.d_in = d->d_x + d->d_tail; a.h1 = d->h1; a.h2 = d->h2; a.d_out = d->d_out; a.sigmoid = d->sigmoid;
+    a.x = d->x; a.x_tail = d->x_tail; a.w1 = d->w1; a.b1 = d->b1; a.w2 = d->w2; a.b2 = d->b2; a.w3 = d->w3; a.b3 = d->b3;
+    a.y = d->y; a.dy = d->dy; a.dx = d->dx;
+    return a;
+}
+int mlp3_grid(const gsrast_mlp3* d, int workgroups, int per_cu)      // never more workgroups than tiles; default: per_cu workgroups per CU
+{
+    const long long tiles = ((long long)d->n + MLP_TR - 1) / MLP_TR;
+    return (int)std::min<long long>(workgroups ? workgroups : per_cu * mlp3_default_workgroups(), tiles);
+}
+}  // namespace
+
+size_t gsrast_mlp3_scratch_bytes(const gsrast_mlp3* d, int workgroups)
+{
+    gsrast_mlp3 probe{};
+    if (d) { probe = *d; probe.n = 0; }
+    static const float one = 0.0f;
+    probe.w1 = probe.b1 = probe.w2 = probe.b2 = probe.w3 = probe.b3 = &one;      // (only the dims are looked at)
+    if (mlp3_check("mlp3_scratch_bytes", d ? &probe : nullptr, workgroups) != GSRAST_OK) return 0;
+    const size_t g = workgroups ? (size_t)workgroups : (size_t)mlp3_default_workgroups();
+    return align256(g * mlp3_param_floats(d->d_x + d->d_tail, d->h1, d->h2, d->d_out) * 4) + 256;
+}
+
+int gsrast_mlp3_forward(const gsrast_mlp3* d, int workgroups, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mlp3_check("mlp3_forward", d, workgroups)) return rc;
+    if (d->n > 0 && !d->y) return fail(GSRAST_E_ARG, "mlp3_forward: NULL y");
+    if (d->n == 0) return GSRAST_OK;
+    const Mlp3Args a = mlp3_args(d);
+    const size_t lds = (size_t)(((a.d_in + 7) & ~7) + a.h1 + a.h2) * MLP_LD * 4;
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp3_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MLP_FWD_LDS);
+    if (attr != hipSuccess) return fail(GSRAST_E_DEVICE, "mlp3_forward: hipFuncSetAttribute", attr);
+    ProfScope ps(K_MLP_FWD, s);
+    mlp3_fwd_kernel<<<mlp3_grid(d, workgroups, 2), MLP_THREADS, lds, s>>>(a);      // (its LDS images leave room for two per CU up to D_in = 48)
+    GS_LAUNCHED("mlp3_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_mlp3_backward(const gsrast_mlp3* d, int workgroups, char* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mlp3_check("mlp3_backward", d, workgroups)) return rc;
+    if (d->n > 0 && !d->dy) return fail(GSRAST_E_ARG, "mlp3_backward: NULL dy");
+    if (d->n > 0 && d->sigmoid && !d->y) return fail(GSRAST_E_ARG, "mlp3_backward: the sigmoid head needs y");
+    Mlp3Args a = mlp3_args(d);
+    a.need = (d->dx ? MLP_NEED_DX : 0) | (d->dw1 || d->db1 ? MLP_NEED_L1 : 0) | (d->dw2 || d->db2 ? MLP_NEED_L2 : 0) | (d->dw3 || d->db3 ? MLP_NEED_L3 : 0);
+    if (a.need == 0) return GSRAST_OK;
+    const bool params = (a.need & ~MLP_NEED_DX) != 0;
+    if (params && !scratch) return fail(GSRAST_E_ARG, "mlp3_backward: NULL scratch");
+    a.partial = reinterpret_cast<float*>(scratch);
+    const int grid = mlp3_grid(d, workgroups, 1);
+    ProfScope ps(K_MLP_BWD, s);
+    if (grid > 0) {
+        const size_t lds = (size_t)(2 * MLP_MAX_IO + a.h1 + std::max(a.h1, a.h2) + a.h2) * MLP_LD * 4;
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp3_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MLP_BWD_LDS);
+        if (attr != hipSuccess) return fail(GSRAST_E_DEVICE, "mlp3_backward: hipFuncSetAttribute", attr);
+        const long long tiles = ((long long)d->n + MLP_TR - 1) / MLP_TR, per_launch = (long long)grid * MLP_FLUSH_TILES;
+        for (a.tile0 = 0; a.tile0 < tiles; a.tile0 += per_launch) {      // (gsrast_mlp.h: no accumulator chain longer than 512 rows)
+            a.tile_end = std::min(tiles, a.tile0 + per_launch);
+            a.add = a.tile0 > 0;
+            mlp3_bwd_kernel<<<(unsigned)std::min<long long>(grid, a.tile_end - a.tile0), MLP_THREADS, lds, s>>>(a);
+            GS_LAUNCHED("mlp3_bwd");
+        }
+    }
+    if (params) {      // (N = 0: no partial, every wanted gradient is written as 0)
+        Mlp3Reduce r{};
+        r.partial = a.partial; r.n_partials = grid; r.total = (unsigned)mlp3_param_floats(a.d_in, a.h1, a.h2, a.d_out);
+        const unsigned sizes[6] = { (unsigned)(a.h1 * a.d_in), (unsigned)a.h1, (unsigned)(a.h2 * a.h1), (unsigned)a.h2, (unsigned)(a.d_out * a.h2), (unsigned)a.d_out };
+        float* const outs[6] = { d->dw1, d->db1, d->dw2, d->db2, d->dw3, d->db3 };
+        unsigned end = 0;
+        for (int k = 0; k < 6; k++) { end += sizes[k]; r.seg_end[k] = end; r.out[k] = outs[k]; }
+        mlp3_reduce_kernel<<<(r.total + 255) / 256, 256, 0, s>>>(r);
+        GS_LAUNCHED("mlp3_reduce");
+    }
     return GSRAST_OK;
 }
 

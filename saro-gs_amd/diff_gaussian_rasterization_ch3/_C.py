@@ -45,6 +45,7 @@ EXPORTS = (
     "gsrast_features_forward", "gsrast_features_backward",
     "gsrast_distortion_forward", "gsrast_distortion_backward",
     "gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise",
+    "gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -159,6 +160,12 @@ class DensifyGroupStruct(C.Structure):
 
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2      # include/gsrast.h: GSRAST_DENSIFY_*
 MCMC_COPY, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2           # include/gsrast.h: GSRAST_MCMC_* (the role of a gsrast_densify_group in the mcmc calls)
+
+
+class Mlp3Struct(C.Structure):
+    """gsrast_mlp3 (include/gsrast.h): the dims, the sigmoid flag and the pointers of one fused 3-layer head."""
+    _fields_ = ([(k, C.c_int) for k in ("n", "d_x", "d_tail", "h1", "h2", "d_out", "sigmoid")]
+                + [(k, C.c_void_p) for k in ("x", "x_tail", "w1", "b1", "w2", "b2", "w3", "b3", "y", "dy", "dx", "dw1", "db1", "dw2", "db2", "dw3", "db3")])
 
 
 class PlaneStruct(C.Structure):
@@ -279,6 +286,11 @@ def lib() -> C.CDLL:
     L.gsrast_mcmc_sample.argtypes = [ci, ci, vp, vp, vp, vp, vp]
     L.gsrast_mcmc_relocate.argtypes = L.gsrast_mcmc_grow.argtypes = [ci, ci, vp, vp, C.POINTER(C.c_uint), cf, ci, C.POINTER(DensifyGroupStruct), vp]
     L.gsrast_mcmc_noise.argtypes = [ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp]
+    L.gsrast_mlp3_scratch_bytes.restype = C.c_size_t
+    L.gsrast_mlp3_scratch_bytes.argtypes = [C.POINTER(Mlp3Struct), ci]
+    L.gsrast_mlp3_forward.restype = L.gsrast_mlp3_backward.restype = ci
+    L.gsrast_mlp3_forward.argtypes = [C.POINTER(Mlp3Struct), ci, vp]
+    L.gsrast_mlp3_backward.argtypes = [C.POINTER(Mlp3Struct), ci, vp, vp]
     L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
     L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
     L.gsrast_hexplane_forward.restype = ci
