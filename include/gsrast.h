@@ -400,7 +400,8 @@ int gsrast_loss_backward(int C, int H, int W, const float* img, const float* gt,
  * motion_res, rot_res ([P][7]), trbf and shs_res may each be NULL (static stage: plain activations).
  * backward: upstream d_rot [P][4], d_scale [P][3], d_opacity [P] (NULL = zero) -> d_rotation [P][4], d_scaling [P][3],
  * d_rot_res [P][7] (NULL ok), d_opacity_logit [P], d_trbf [P] (NULL ok).  The other gradients need no kernel:
- * d_xyz = d_motion_res = d_motion; d_features_dc / d_features_rest are slices of d_shs, d_shs_res = d_shs. */
+ * d_xyz = d_motion_res = d_motion; d_features_dc / d_features_rest are slices of d_shs, d_shs_res = d_shs.
+ * rotation, rot, d_rot and d_rotation are accessed as float4: GSRAST_E_ARG unless they are 16-byte aligned. */
 int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_res, const float* rotation,
                             const float* rot_res, const float* scaling, const float* opacity_logit, const float* trbf,
                             const float* features_dc, const float* features_rest, const float* shs_res,

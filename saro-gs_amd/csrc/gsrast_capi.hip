@@ -1750,6 +1750,7 @@ int gsrast_activate_forward(int P, int M, const float* xyz, const float* motion_
     if (P == 0) return GSRAST_OK;
     if (!xyz || !rotation || !scaling || !opacity_logit || !features_dc || (M > 1 && !features_rest) ||
         !motion || !rot || !scale || !opacity || !shs) return fail(GSRAST_E_ARG, "activate_forward: NULL required pointer");
+    if (((uintptr_t)rotation | (uintptr_t)rot) & 15) return fail(GSRAST_E_ARG, "activate_forward: rotation / rot must be 16-byte aligned");
     epilogue_small_fwd_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, xyz, motion_res, rotation, rot_res, scaling, opacity_logit, trbf,
                                                              motion, rot, scale, opacity);
     GS_LAUNCHED("epilogue_small_fwd");
@@ -1775,6 +1776,8 @@ int gsrast_activate_backward(int P, const float* rotation, const float* rot_res,
     if (P == 0) return GSRAST_OK;
     if (!rotation || !scale || !opacity_logit || !d_rotation || !d_scaling || !d_opacity_logit)
         return fail(GSRAST_E_ARG, "activate_backward: NULL required pointer");
+    if (((uintptr_t)rotation | (uintptr_t)d_rot | (uintptr_t)d_rotation) & 15)
+        return fail(GSRAST_E_ARG, "activate_backward: rotation / d_rot / d_rotation must be 16-byte aligned");
     epilogue_small_bwd_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, rotation, rot_res, scale, opacity_logit, trbf, d_rot, d_scale, d_opacity,
                                                              d_rotation, d_scaling, d_rot_res, d_opacity_logit, d_trbf);
     GS_LAUNCHED("epilogue_small_bwd");

@@ -27,6 +27,15 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _c16(t: Optional[torch.Tensor]):
+    """Contiguous float32 at a 16-byte aligned address (the kernels read quaternions as float4): a contiguous view that starts
+    elsewhere inside a larger buffer is copied."""
+    if t is None:
+        return None
+    t = t.contiguous().float()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, motion_res, rotation, rot_res, scaling, opacity, trbf, f_dc, f_rest, shs_res):
@@ -34,7 +43,7 @@ class _Activate(torch.autograd.Function):
             raise RuntimeError("fused_epilogue: tensors must be on a GPU (HIP) device; there is no CPU fallback")
         dev = xyz.device
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
-        xyz, motion_res, rotation, rot_res, scaling = c(xyz), c(motion_res), c(rotation), c(rot_res), c(scaling)
+        xyz, motion_res, rotation, rot_res, scaling = c(xyz), c(motion_res), _c16(rotation), c(rot_res), c(scaling)
         opacity, trbf, f_dc, f_rest, shs_res = c(opacity), c(trbf), c(f_dc), c(f_rest), c(shs_res)
         P = int(xyz.shape[0])
         M = 1 + int(f_rest.shape[1])
@@ -65,7 +74,7 @@ class _Activate(torch.autograd.Function):
         P = int(rotation.shape[0])
         o = dict(dtype=torch.float32, device=dev)
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
-        d_rot, d_scale, d_opa = c(d_rot), c(d_scale), c(d_opa)
+        d_rot, d_scale, d_opa = _c16(d_rot), c(d_scale), c(d_opa)
         g_rotation, g_scaling, g_logit = torch.empty((P, 4), **o), torch.empty((P, 3), **o), torch.empty((P, 1), **o)
         g_rres = torch.empty((P, 7), **o) if has_rres else None
         g_trbf = torch.empty((P, 1), **o) if has_trbf else None
@@ -88,6 +97,15 @@ def activate_gaussians(xyz: torch.Tensor, rotation: torch.Tensor, scaling: torch
                        trbfoutput: Optional[torch.Tensor] = None, shs_residual: Optional[torch.Tensor] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """Returns (motion [P,3], rot [P,4], scale [P,3], opacity [P,1], shs [P,M,3]) -- the `means3D, rotations, scales,
-    opacities, shs` arguments of GaussianRasterizer -- differentiable w.r.t. every input."""
+    opacities, shs` arguments of GaussianRasterizer -- differentiable w.r.t. every input.
+
+    Outputs that take no part in a backward pass (their upstream gradient is None) count as zero upstream.  What an input that none
+    of the used outputs depends on then receives: `rotation`, `scaling`, `opacity`, `rot_residual` and `trbfoutput` always get a
+    tensor from the one backward kernel, exact zeros where nothing reaches them; `xyz`, `motion_residual`, `features_dc`,
+    `features_rest` and `shs_residual` are views of the upstream gradient itself and get None (`.grad` stays None) when `motion`,
+    respectively `shs`, is unused.
+
+    `rotation` (and the upstream gradient of `rot`) is read as float4: a contiguous tensor that does not start on a 16-byte boundary,
+    such as a view into a larger buffer, is copied first."""
     return _Activate.apply(xyz, motion_residual, rotation, rot_residual, scaling, opacity, trbfoutput, features_dc,
                            features_rest, shs_residual)
