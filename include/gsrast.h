@@ -862,6 +862,41 @@ size_t gsrast_mlp3_scratch_bytes(const gsrast_mlp3* d /* dims only */, int workg
 int gsrast_mlp3_forward(const gsrast_mlp3* d, int workgroups, void* stream);
 int gsrast_mlp3_backward(const gsrast_mlp3* d, int workgroups, char* scratch, void* stream);
 
+/* ---- temporal lifespan: the gate between the opacity head and the other heads, and Eq. 22's integral ----
+ * What makes the model 4-D (scene/saro_gaussian.py: get_deformation :782-795, get_deformation_eval :871-881, get_intergral :761-777 and the
+ * top of update_learning_rate :345-356).  All arrays fp32 [P] device pointers unless noted:  head = the opacity head's output after its
+ * Sigmoid;  center = the raw _temporal_pos, read as c = center, or c = sigmoid(center) with sigmoid_center = 1 (args.sigmoid_tcenter);
+ * min_scale = min_interval / duration in (0, 1].
+ *   L = (1 - min_scale) (1 - head) + min_scale;   d = t - c;   state = exp(-4 (d / L)^2)
+ *
+ * gsrast_temporal_gate_forward writes lifespan = L, state and, where their pointer is not NULL:
+ *   time_emb [P][2 multires + 1] = [d, sin d, cos d, sin 2d, cos 2d, ..., sin 2^(multires-1) d, cos 2^(multires-1) d]  (the reference's
+ *   Embedder: include_input, log-sampled exact powers of two, sin before cos; multires in [0, 8]; 16-byte aligned: stored as float4);
+ *   dead [P] u8 = !(state > dead_threshold)  (a NaN row is dead).  One launch.
+ * gsrast_temporal_gate_backward recomputes L, d and state from head and center (the forward saves nothing) and writes, where their pointer
+ *   is not NULL (each OVERWRITTEN):  with u = d / L,  g_L = d_lifespan + d_state (8 u^2 state / L)  and  g_d = d_state (-8 u state / L):
+ *   d_head = -(1 - min_scale) g_L,  d_center = -g_d [x c (1 - c) under sigmoid_center].  d_lifespan / d_state NULL: zeros.  The time
+ *   embedding carries no gradient (the reference detaches it).  A state that underflowed to 0 gives gradient 0.  One launch, no atomics.
+ * gsrast_temporal_integral writes
+ *   integral = I = L (sqrt(pi) / 2) (Q(2 sqrt2 (end - c) / L) - Q(2 sqrt2 (start - c) / L)),  Q(x) = 1 / (1 + exp(-(a1 x^3 + a2 x))),
+ *   a1 = 0.070565902, a2 = 1.5976 (the reference's 1 - 1 / (1 + e^z) written as a sigmoid: no cancellation for very negative z);
+ *   dead [P] u8 = !(I > min_integral);  stats (device int[2], zeroed by the call) = { the float bits of the largest I over the valid rows,
+ *   the number of valid rows } (integer atomics: exact and order-free);  inv [P] (NULL: not wanted) = I_max / I on a valid row, 0 on a
+ *   dead one -- the reference's (1/I) / min(1/I) with one rounding less.  No valid row: inv all zeros.  Two launches.
+ * P = 0 returns 0 without a launch (and without touching stats).  Refused (GSRAST_E_ARG, gsrast_last_error) before any device call:
+ * negative P, a NULL required pointer, multires outside [0, 8], sigmoid_center other than 0 / 1, min_scale outside (0, 1], a non-finite t /
+ * start / end, end < start, a negative or non-finite min_integral, a time_emb that is not 16-byte aligned.  No floating-point atomics;
+ * the launches have no entry in the profile table. */
+int gsrast_temporal_gate_forward(int P, int multires, int sigmoid_center, float t, float min_scale, float dead_threshold, const float* head,
+                                 const float* center, float* lifespan, float* state, float* time_emb /* NULL ok */, unsigned char* dead /* NULL ok */,
+                                 void* stream);
+int gsrast_temporal_gate_backward(int P, int sigmoid_center, float t, float min_scale, const float* head, const float* center,
+                                  const float* d_lifespan /* NULL = 0 */, const float* d_state /* NULL = 0 */, float* d_head /* NULL ok */,
+                                  float* d_center /* NULL ok */, void* stream);
+int gsrast_temporal_integral(int P, int sigmoid_center, float start, float end, float min_scale, float min_integral, const float* head,
+                             const float* center, float* integral, unsigned char* dead, float* inv /* NULL ok */, int* stats /* device [2] */,
+                             void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

@@ -27,6 +27,7 @@
 #include "gsrast_densify.h"
 #include "gsrast_mcmc.h"
 #include "gsrast_mlp.h"
+#include "gsrast_temporal.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include "gsrast_exchange.h"
@@ -2089,9 +2090,75 @@ int gsrast_mcmc_noise(int P, float* xyz, const float* rotation, const float* sca
     return GSRAST_OK;
 }
 
+// ---- temporal lifespan (gsrast_temporal.h) --------------------------------------------------------------------------
+// Not in the profile kernel-name table: tools/temporal_overhead.py times these calls with device events of its own.
+namespace {
+// the refusals the three entry points share; 0 or GSRAST_E_ARG
+int temporal_check(const char* who, int P, int sigmoid_center, float min_scale)
+{
+    char msg[160];
+    auto refuse = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(GSRAST_E_ARG, msg); };
+    if (P < 0) return refuse("negative P");
+    if (sigmoid_center != 0 && sigmoid_center != 1) return refuse("sigmoid_center must be 0 or 1");
+    if (!(min_scale > 0.0f && min_scale <= 1.0f)) return refuse("min_scale must be in (0, 1]");
+    return GSRAST_OK;
+}
+unsigned temporal_grid(int P) { return (unsigned)(((size_t)P + TP_RUN - 1) / TP_RUN); }
+}  // namespace
+
+int gsrast_temporal_gate_forward(int P, int multires, int sigmoid_center, float t, float min_scale, float dead_threshold, const float* head,
+                                 const float* center, float* lifespan, float* state, float* time_emb, unsigned char* dead, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = temporal_check("temporal_gate_forward", P, sigmoid_center, min_scale)) return rc;
+    if (multires < 0 || multires > TP_MAX_MULTIRES) return fail(GSRAST_E_ARG, "temporal_gate_forward: multires must be in [0, 8]");
+    if (!std::isfinite(t)) return fail(GSRAST_E_ARG, "temporal_gate_forward: t must be finite");
+    if (P == 0) return GSRAST_OK;
+    if (!head || !center || !lifespan || !state) return fail(GSRAST_E_ARG, "temporal_gate_forward: NULL required pointer");
+    if (((uintptr_t)time_emb & 15) != 0) return fail(GSRAST_E_ARG, "temporal_gate_forward: time_emb must be 16-byte aligned");
+    const size_t lds = time_emb ? (size_t)TP_RUN * (2 * multires + 1) * 4 : 0;
+    temporal_gate_fwd_kernel<<<temporal_grid(P), TP_RUN, lds, s>>>(P, multires, sigmoid_center, t, min_scale, dead_threshold, head, center, lifespan, state, time_emb, dead);
+    GS_LAUNCHED("temporal_gate_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_temporal_gate_backward(int P, int sigmoid_center, float t, float min_scale, const float* head, const float* center, const float* d_lifespan,
+                                  const float* d_state, float* d_head, float* d_center, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = temporal_check("temporal_gate_backward", P, sigmoid_center, min_scale)) return rc;
+    if (!std::isfinite(t)) return fail(GSRAST_E_ARG, "temporal_gate_backward: t must be finite");
+    if (P == 0) return GSRAST_OK;
+    if (!head || !center) return fail(GSRAST_E_ARG, "temporal_gate_backward: NULL required pointer");
+    if (!d_head && !d_center) return GSRAST_OK;
+    temporal_gate_bwd_kernel<<<temporal_grid(P), TP_RUN, 0, s>>>(P, sigmoid_center, t, min_scale, head, center, d_lifespan, d_state, d_head, d_center);
+    GS_LAUNCHED("temporal_gate_bwd");
+    return GSRAST_OK;
+}
+
+int gsrast_temporal_integral(int P, int sigmoid_center, float start, float end, float min_scale, float min_integral, const float* head, const float* center,
+                             float* integral, unsigned char* dead, float* inv, int* stats, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = temporal_check("temporal_integral", P, sigmoid_center, min_scale)) return rc;
+    if (!std::isfinite(start) || !std::isfinite(end)) return fail(GSRAST_E_ARG, "temporal_integral: start and end must be finite");
+    if (end < start) return fail(GSRAST_E_ARG, "temporal_integral: end < start");
+    if (!(min_integral >= 0.0f) || !std::isfinite(min_integral)) return fail(GSRAST_E_ARG, "temporal_integral: min_integral must be finite and >= 0 (the maximum is taken on the bits of positive floats)");
+    if (P == 0) return GSRAST_OK;
+    if (!head || !center || !integral || !dead || !stats) return fail(GSRAST_E_ARG, "temporal_integral: NULL required pointer");
+    GS_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int), s));
+    temporal_integral_kernel<<<std::min(temporal_grid(P), (unsigned)TP_INTEGRAL_WGS), TP_RUN, 0, s>>>(P, sigmoid_center, start, end, min_scale, min_integral, head, center, integral, dead, stats);
+    GS_LAUNCHED("temporal_integral");
+    if (inv) {      // (a launch of its own: the maximum must exist before the division)
+        temporal_inv_kernel<<<temporal_grid(P), TP_RUN, 0, s>>>(P, integral, dead, stats, inv);
+        GS_LAUNCHED("temporal_inv");
+    }
+    return GSRAST_OK;
+}
+
 // ---- fused 3-layer MLP (gsrast_mlp.h) -------------------------------------------------------------------------------
 namespace {
-int mlp3_default_workgroups()      // one workgroup per CU (its LDS images leave room for one)
+int mlp3_default_workgroups()     // one workgroup per CU (its LDS images leave room for one)
 {
     static const int n = [] {
         int dev = 0, cus = 0;

@@ -46,6 +46,7 @@ EXPORTS = (
     "gsrast_distortion_forward", "gsrast_distortion_backward",
     "gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise",
     "gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward",
+    "gsrast_temporal_gate_forward", "gsrast_temporal_gate_backward", "gsrast_temporal_integral",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -291,6 +292,10 @@ def lib() -> C.CDLL:
     L.gsrast_mlp3_forward.restype = L.gsrast_mlp3_backward.restype = ci
     L.gsrast_mlp3_forward.argtypes = [C.POINTER(Mlp3Struct), ci, vp]
     L.gsrast_mlp3_backward.argtypes = [C.POINTER(Mlp3Struct), ci, vp, vp]
+    L.gsrast_temporal_gate_forward.restype = L.gsrast_temporal_gate_backward.restype = L.gsrast_temporal_integral.restype = ci
+    L.gsrast_temporal_gate_forward.argtypes = [ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_temporal_gate_backward.argtypes = [ci, ci, cf, cf, vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_temporal_integral.argtypes = [ci, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
     L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
     L.gsrast_hexplane_forward.restype = ci

@@ -25,8 +25,9 @@ A fixed budget (`cap_max`), no gradient thresholds, dead Gaussians re-used inste
 fixed-point weights, so the same draws select the same rows on every rank.  Two stated deviations from gsplat: compute_relocation's
 alternating sum runs in fp64, and a model with no alive row is a no-op where torch.multinomial would raise.
 
-What stays the caller's: `reset_opacity`; the integral `get_intergral() < min_intergral` (it needs the hex-plane model) and the colmap
-`z < 4.5` rule -- both arrive here as `prune_mask`; per-row `lr` tensors of the old P (GaussianAdam.step raises on a mismatch) and the
+What stays the caller's: `reset_opacity` and the colmap `z < 4.5` rule, which arrives here as `prune_mask`.  The integral prune
+`get_intergral() <= min_intergral` is `fused_temporal.temporal_prune` (the integral and its mask on the device from the opacity head's
+output, then `prune` below with `inv_intergral` carried along); per-row `lr` tensors of the old P (GaussianAdam.step raises on a mismatch) and the
 `view_parallel.StepBucket`, which is rebuilt after P changed.  GPU tensors only; no fallback.
 """
 from __future__ import annotations
