@@ -1,6 +1,7 @@
 // gsrast_common.h -- shared constants, HBM state layout and wave64 helpers (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gsrast_host.h"       // (Carver: the layouts' offsets)
 #include <stdint.h>
 #include <stddef.h>
 
@@ -213,7 +214,7 @@ static inline int cut_cell_shift(size_t gx, size_t gy)      // 1, 2, 3, or 0 = n
 // prediction is verified like a remembered cut (the blend flags a tile whose cut list ended before it saturated, the completion pass lists
 // it again), so it can only cost time; every reported pass raises tau_req.  Depth bins: TAU_BINS equal steps of the depth KEY (float bits:
 // piecewise linear in log depth) over the key range [lo, hi] the context has learned from its forwards (the occupied range padded by an
-// eighth, gsrast_capi.hip: learn_depth_range) -- the depth histogram's own bins are powers of two of key steps and cover up to twice
+// eighth, gsrast_policy.h: DepthRange::learn) -- the depth histogram's own bins are powers of two of key steps and cover up to twice
 // that range, too coarse here: a tile's cut lands on a bin's FAR edge, so a bin's width is what the prediction gives away.  The last
 // bin also takes everything behind hi and has no far edge (no cut there).
 #ifndef GSRAST_TAU_BINS
@@ -269,53 +270,51 @@ static inline size_t scan_tmp_elems(size_t n)
 
 static inline GeomLayout geom_layout(size_t P)
 {
-    GeomLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    GeomLayout L; Carver c;
     size_t Pp = P ? P : 1;
-    if (REC_STRIDE == 4) { L.rec0 = take(Pp * 64); L.rec1 = L.rec0 + 16; L.rec2 = L.rec0 + 32; }      // one 64-byte record per Gaussian: {rec0, rec1, rec2, -}
-    else { L.rec0 = take(Pp * 16); L.rec1 = take(Pp * 16); L.rec2 = take(Pp * 16); }
-    L.cov3D = take(Pp * 24); L.clamped = take(Pp); L.tiles = take(Pp * 4); L.rect = take(Pp * 8); L.binrec = take(Pp * 32);
-    L.keyA = take(Pp * 4); L.keyB = take(Pp * 4); L.valA = take(Pp * 4); L.valB = take(Pp * 4);
-    L.offsets = take(Pp * 4); L.woffsets = take(Pp * 4);
+    if (REC_STRIDE == 4) { L.rec0 = c.take(Pp * 64); L.rec1 = L.rec0 + 16; L.rec2 = L.rec0 + 32; }      // one 64-byte record per Gaussian: {rec0, rec1, rec2, -}
+    else { L.rec0 = c.take(Pp * 16); L.rec1 = c.take(Pp * 16); L.rec2 = c.take(Pp * 16); }
+    L.cov3D = c.take(Pp * 24); L.clamped = c.take(Pp); L.tiles = c.take(Pp * 4); L.rect = c.take(Pp * 8); L.binrec = c.take(Pp * 32);
+    L.keyA = c.take(Pp * 4); L.keyB = c.take(Pp * 4); L.valA = c.take(Pp * 4); L.valB = c.take(Pp * 4);
+    L.offsets = c.take(Pp * 4); L.woffsets = c.take(Pp * 4);
     size_t hist_n = 256 * rs_blocks_n(Pp, GSRAST_DEPTH_ITEMS);
-    L.hist = take(hist_n * 4);
+    L.hist = c.take(hist_n * 4);
     size_t st = scan_tmp_elems(hist_n) > scan_tmp_elems(Pp) ? scan_tmp_elems(hist_n) : scan_tmp_elems(Pp);
-    L.scan_tmp = take(st * 4);
-    L.scalars = take(256);
-    L.grec = take(Pp * GREC * 4);
-    L.keyC = take(Pp * 4); L.valC = take(Pp * 4);                               // third buffer pair of the adaptive depth sort
-    L.sort_minmax = take(2 * rs_blocks_n(Pp, GSRAST_DEPTH_ITEMS) * 4);
-    L.shdA = take(Pp * 16); L.shdB = take(Pp * 16); L.shdC = take(Pp * 4);
+    L.scan_tmp = c.take(st * 4);
+    L.scalars = c.take(256);
+    L.grec = c.take(Pp * GREC * 4);
+    L.keyC = c.take(Pp * 4); L.valC = c.take(Pp * 4);                               // third buffer pair of the adaptive depth sort
+    L.sort_minmax = c.take(2 * rs_blocks_n(Pp, GSRAST_DEPTH_ITEMS) * 4);
+    L.shdA = c.take(Pp * 16); L.shdB = c.take(Pp * 16); L.shdC = c.take(Pp * 4);
     // bucket depth sort (gsrast_binning.h): sampled depth histogram of preprocess_fwd and its running sum, bucket counters, slabs
-    L.zhist = take(ZH_COPIES * ZH_BINS * 4);
+    L.zhist = c.take(ZH_COPIES * ZH_BINS * 4);
     {
         const size_t nb = Pp >= BUCKET_SORT_MIN_P ? depth_buckets_host(Pp) : 0;
-        L.bk_count = take(nb * 8 * 4);                       // [8 XCDs][nb]
-        L.bk_ccount = take(8 * 256 * 4);                     // [8 XCDs][256 coarse buckets] (two-launch scatter, gsrast_binning.h); contiguous with bk_count: nb * 32 bytes is a multiple of 256
-        L.bk_slab = take(nb * GSRAST_BK_CAP * 16);           // [nb][8][CAP / 8] {key, id, width, tiles}
-        L.bk_order = take(nb * GSRAST_BK_CAP * 4); L.bk_wincl = take(nb * GSRAST_BK_CAP * 4);
-        L.bk_info = take(nb * 16); L.bk_base = take(nb * 4); L.bk_key = take((nb + 1) * 4);
-        L.bk_order_e = take(nb * GSRAST_BK_CAP * 4); L.bk_wincl_e = take(nb * GSRAST_BK_CAP * 4); L.bk_info_e = take(nb * 16); L.bk_base_e = take(nb * 4);
+        L.bk_count = c.take(nb * 8 * 4);                       // [8 XCDs][nb]
+        L.bk_ccount = c.take(8 * 256 * 4);                     // [8 XCDs][256 coarse buckets] (two-launch scatter, gsrast_binning.h); contiguous with bk_count: nb * 32 bytes is a multiple of 256
+        L.bk_slab = c.take(nb * GSRAST_BK_CAP * 16);           // [nb][8][CAP / 8] {key, id, width, tiles}
+        L.bk_order = c.take(nb * GSRAST_BK_CAP * 4); L.bk_wincl = c.take(nb * GSRAST_BK_CAP * 4);
+        L.bk_info = c.take(nb * 16); L.bk_base = c.take(nb * 4); L.bk_key = c.take((nb + 1) * 4);
+        L.bk_order_e = c.take(nb * GSRAST_BK_CAP * 4); L.bk_wincl_e = c.take(nb * GSRAST_BK_CAP * 4); L.bk_info_e = c.take(nb * 16); L.bk_base_e = c.take(nb * 4);
     }
-    L.color_skip = take(((Pp + 63) / 64) * 8 + 256);
-    L.cand_bits = take(((Pp + 63) / 64) * 8 + 256);
-    L.skip2 = take(((Pp + 63) / 64) * 8 + 256);
-    L.untouched = take(Pp + 256);            // (one BYTE per Gaussian: the blend marks with plain stores)
-    L.total = o + 256;
+    L.color_skip = c.take(((Pp + 63) / 64) * 8 + 256);
+    L.cand_bits = c.take(((Pp + 63) / 64) * 8 + 256);
+    L.skip2 = c.take(((Pp + 63) / 64) * 8 + 256);
+    L.untouched = c.take(Pp + 256);            // (one BYTE per Gaussian: the blend marks with plain stores)
+    L.total = c.o + 256;
     return L;
 }
 static inline BinLayout bin_layout(size_t R)
 {
-    BinLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    BinLayout L; Carver c;
     size_t Rp = R ? R : 1;
     // valA first: the sorted Gaussian ids (point_list) always end at offset 0, so the backward needs
     // neither the instance count nor the capacity the buffer was sized for
-    L.valA = take(Rp * 4); L.valB = take(Rp * 4); L.keyA = take(Rp * 4); L.keyB = take(Rp * 4);
+    L.valA = c.take(Rp * 4); L.valB = c.take(Rp * 4); L.keyA = c.take(Rp * 4); L.keyB = c.take(Rp * 4);
     size_t hist_n = 256 * rs_blocks(Rp);
-    L.hist = take(hist_n * 4);
-    L.scan_tmp = take(scan_tmp_elems(hist_n) * 4);
-    L.total = o + 256;
+    L.hist = c.take(hist_n * 4);
+    L.scan_tmp = c.take(scan_tmp_elems(hist_n) * 4);
+    L.total = c.o + 256;
     return L;
 }
 // Run-compressed binning (gsrast_binning.h): capR = instance capacity, capQ = column-run capacity.
@@ -335,35 +334,33 @@ struct RunBinLayout {
 };
 static inline RunBinLayout runbin_layout(size_t capR, size_t capQ)
 {
-    RunBinLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    RunBinLayout L; Carver c;
     if (!capR) capR = 1;
     if (!capQ) capQ = 1;
-    L.point_list = take(2 * capR * 4);      // (second half: the lists of the tiles the completion pass of the list cut lists again, below)
-    L.rkeyA = take(capQ * 2); L.rkeyB = take(capQ * 2); L.rvalA = take(capQ * 8); L.rvalB = take(capQ * 8);
-    L.hist_x = take(256 * rs_blocks_n(capQ, GSRAST_RUN_SORT_ITEMS) * 4);
-    L.hist_y = take(256 * ((capQ + RUNS_PER_BLOCK - 1) / RUNS_PER_BLOCK) * 4);
-    L.scan_tmp = take((scan_tmp_elems(capQ) + 512) * 4);
-    L.total = o + 256;
+    L.point_list = c.take(2 * capR * 4);      // (second half: the lists of the tiles the completion pass of the list cut lists again, below)
+    L.rkeyA = c.take(capQ * 2); L.rkeyB = c.take(capQ * 2); L.rvalA = c.take(capQ * 8); L.rvalB = c.take(capQ * 8);
+    L.hist_x = c.take(256 * rs_blocks_n(capQ, GSRAST_RUN_SORT_ITEMS) * 4);
+    L.hist_y = c.take(256 * ((capQ + RUNS_PER_BLOCK - 1) / RUNS_PER_BLOCK) * 4);
+    L.scan_tmp = c.take((scan_tmp_elems(capQ) + 512) * 4);
+    L.total = c.o + 256;
     return L;
 }
 
 static inline ImgLayout img_layout(size_t W, size_t H)
 {
-    ImgLayout L; size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
+    ImgLayout L; Carver c;
     size_t N = W * H ? W * H : 1;
     size_t T = ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y);
     if (!T) T = 1;
-    L.final_T = take(N * 4); L.n_contrib = take(N * 4); L.ranges = take(T * 8); L.tile_max = take(T * 4);
-    L.order_fwd = take(T * 4); L.order_bwd = take(T * 4);
+    L.final_T = c.take(N * 4); L.n_contrib = c.take(N * 4); L.ranges = c.take(T * 8); L.tile_max = c.take(T * 4);
+    L.order_fwd = c.take(T * 4); L.order_bwd = c.take(T * 4);
     const size_t Tg = xcd_group_tiles_host((W + TILE_X - 1) / TILE_X, (H + TILE_Y - 1) / TILE_Y);      // list capacity of one (group, bucket)
-    L.bucket_cnt = take(((XCD_GROUPS + 1) * WORK_BUCKETS + GATE_WORDS) * 4);   // forward: per XCD group; backward: one global set; + the completion pass's gate counters (gsrast_blend.h, GateArgs), zeroed with them
-    L.bucket_list = take(T <= BUCKET_MAX_TILES ? (XCD_GROUPS * WORK_BUCKETS * (Tg ? Tg : 1) + WORK_BUCKETS * T) * 2 : 0);
-    L.zcut_used = take(T * 4);
-    L.tile_flags = take(T);
-    L.tau_hist = take((size_t)TAU_COPIES * T * TAU_BINS * 4);
-    L.total = o + 256;
+    L.bucket_cnt = c.take(((XCD_GROUPS + 1) * WORK_BUCKETS + GATE_WORDS) * 4);   // forward: per XCD group; backward: one global set; + the completion pass's gate counters (gsrast_blend.h, GateArgs), zeroed with them
+    L.bucket_list = c.take(T <= BUCKET_MAX_TILES ? (XCD_GROUPS * WORK_BUCKETS * (Tg ? Tg : 1) + WORK_BUCKETS * T) * 2 : 0);
+    L.zcut_used = c.take(T * 4);
+    L.tile_flags = c.take(T);
+    L.tau_hist = c.take((size_t)TAU_COPIES * T * TAU_BINS * 4);
+    L.total = c.o + 256;
     return L;
 }
 // key bits / radix passes needed to sort tile ids < T

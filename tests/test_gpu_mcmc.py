@@ -322,6 +322,28 @@ def test_noise_from_the_generator_and_on_parameters(gpu):
     assert torch.equal(outs[0], outs[1]) and not torch.equal(outs[0].cpu(), case["params"]["xyz"])
 
 
+def test_noise_records_into_the_one_profile_table(rast, gpu):
+    """The library has one timer table, whichever translation unit a call is compiled in: with the profile bit of mcmc_noise set (and no
+    other), one mcmc_inject_noise shows as one launch of "mcmc_noise" in profile_read(), and the renderer's preprocess_fwd shows none."""
+    import fused_densify
+    _C = rast._C
+    P = 256
+    gen = torch.Generator().manual_seed(9)
+    xyz, rot, scaling, logit = (torch.randn(P, w, generator=gen).to(gpu) for w in (3, 4, 3, 1))
+    bit = list(_C.profile_read()).index("mcmc_noise")
+    assert bit == 31
+    _C.set_option("profile", -(1 << 31))        # bit 31 alone, as the 32-bit word the option is
+    try:
+        _C.profile_reset()
+        fused_densify.mcmc_inject_noise(xyz, rot, scaling, logit, scale=1.0, noise=torch.randn(P, 3, generator=gen).to(gpu))
+        prof = _C.profile_read()
+        assert prof["mcmc_noise"][1] == 1 and prof["mcmc_noise"][0] > 0.0
+        assert prof["preprocess_fwd"][1] == 0
+    finally:
+        _C.set_option("profile", 0)
+        _C.profile_reset()
+
+
 # ---- determinism and composition ----------------------------------------------------------------------------------------------
 def _state(opt):
     out = []

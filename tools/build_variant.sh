@@ -4,6 +4,8 @@ set -e
 name=$1; shift
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_variants
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-  -munsafe-fp-atomics -fno-slp-vectorize -Wall -Wno-unused-function "$@" saro-gs_amd/csrc/gsrast_capi.hip -o gpurun_variants/lib_$name.so
+lib() {      # the variant's path; sources and flags are those of saro-gs_amd/build.py
 echo gpurun_variants/lib_$name.so
+}
+python3 saro-gs_amd/build.py --force --out "$(lib)" "$@" > /dev/null
+lib

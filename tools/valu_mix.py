@@ -2,23 +2,20 @@
 """Static VALU instruction mix of the blend kernels' per-(wave, instance) loop, priced with the MEASURED issue cost of each
 instruction class (profiles/r02_valu_calib.json, tools/valu_calib.hip) -> profiles/<tag>_valu_mix.json (tag = argv[1], default r04).
 
-    python tools/valu_mix.py            # compiles csrc/gsrast_capi.hip with -save-temps into a temp dir, no GPU needed
+    python tools/valu_mix.py            # compiles the library's units (saro-gs_amd/build.py: its sources, its flags) with -save-temps into a temp dir, no GPU needed
 
 bench.py uses `avg_cycles_per_valu_inst` of a kernel to turn its SQ_INSTS_VALU count into SIMD issue cycles; the per-pair
 figures say where the cycles of one evaluated (wave, instance) pair go.  The loop region is the code between the `s_ff1_i32_b64`
 that picks the next surviving instance and the batch's closing `s_barrier`; both sides of every branch inside it are counted
 once (a static mix, not a trace)."""
+import importlib.util
 import json
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "saro-gs_amd", "csrc", "gsrast_capi.hip")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-munsafe-fp-atomics",
-         "-fno-slp-vectorize"]      # = saro-gs_amd/build.py
 KERNELS = {"blend_bwd_cull_t_kernel": r"^_ZN6gsrast23blend_bwd_cull_t_kernelILi0E", "blend_bwd_cull_kernel": r"^_ZN6gsrast21blend_bwd_cull_kernelILi0ELi1E",
            "blend_fwd_cull_kernel": r"^_ZN6gsrast21blend_fwd_cull_kernelILi0E"}
 
@@ -60,9 +57,10 @@ def main():
     calib = json.load(open(os.path.join(ROOT, "profiles", "r02_valu_calib.json")))
     cost = cost_table(calib)
     with tempfile.TemporaryDirectory() as td:
-        subprocess.check_call(["hipcc"] + FLAGS + ["-save-temps", "-c", SRC, "-o", os.path.join(td, "x.o")], cwd=td,
-                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(os.path.join(td, "gsrast_capi-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+        spec = importlib.util.spec_from_file_location("gsrast_build", os.path.join(ROOT, "saro-gs_amd", "build.py"))
+        build = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(build)
+        asm = [line for path in build.assembly(td) for line in open(path).read().splitlines()]
     out = {"cycles_per_wave_instruction": {k: round(v, 3) for k, v in cost.items()}, "calibration": "profiles/r02_valu_calib.json (8 waves per SIMD)",
            "kernels": {}}
     for name, pat in KERNELS.items():
