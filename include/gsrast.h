@@ -862,6 +862,20 @@ size_t gsrast_mlp3_scratch_bytes(const gsrast_mlp3* d /* dims only */, int workg
 int gsrast_mlp3_forward(const gsrast_mlp3* d, int workgroups, void* stream);
 int gsrast_mlp3_backward(const gsrast_mlp3* d, int workgroups, char* scratch, void* stream);
 
+/* The same head with the arithmetic chosen per call.  GSRAST_MLP_FP32 IS the three calls above (same code, same bits, same scratch size).
+ * GSRAST_MLP_BF16 runs the products on the bf16 matrix instruction with fp32 accumulation (csrc/gsrast_mlp_bf16.h states the rounding model:
+ * x, the weights, both hidden activations and the three back-propagated gradients are rounded to bfloat16, round-to-nearest-even, where a
+ * product reads them; biases, bias add, ReLU, Sigmoid, y and every gradient written are fp32; bias gradients sum the unrounded values; the
+ * weight gradients are the fp32 master weights', straight-through).  Tensors stay fp32 on both sides, the weights are converted inside each
+ * launch and no bf16 copy outlives the call.  Same shapes, refusals, scratch size, launch chain (at most 512 rows per accumulator, tiles of
+ * 128 rows), run-to-run bits for one workgroup count and profile names as fp32.  fp32 denormals: unspecified.
+ * Any other precision is GSRAST_E_ARG ("precision ...") before any device call. */
+#define GSRAST_MLP_FP32 0
+#define GSRAST_MLP_BF16 1
+size_t gsrast_mlp3_scratch_bytes_p(const gsrast_mlp3* d /* dims only */, int precision, int workgroups);
+int gsrast_mlp3_forward_p(const gsrast_mlp3* d, int precision, int workgroups, void* stream);
+int gsrast_mlp3_backward_p(const gsrast_mlp3* d, int precision, int workgroups, char* scratch, void* stream);
+
 /* ---- temporal lifespan: the gate between the opacity head and the other heads, and Eq. 22's integral ----
  * What makes the model 4-D (scene/saro_gaussian.py: get_deformation :782-795, get_deformation_eval :871-881, get_intergral :761-777 and the
  * top of update_learning_rate :345-356).  All arrays fp32 [P] device pointers unless noted:  head = the opacity head's output after its

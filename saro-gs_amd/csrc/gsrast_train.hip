@@ -8,6 +8,7 @@
 #include "gsrast_densify.h"
 #include "gsrast_mcmc.h"
 #include "gsrast_mlp.h"
+#include "gsrast_mlp_bf16.h"
 #include "gsrast_temporal.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
@@ -519,6 +520,91 @@ int gsrast_mlp3_backward(const gsrast_mlp3* d, int workgroups, char* scratch, vo
             a.add = a.tile0 > 0;
             mlp3_bwd_kernel<<<(unsigned)std::min<long long>(grid, a.tile_end - a.tile0), MLP_THREADS, lds, s>>>(a);
             GS_LAUNCHED("mlp3_bwd");
+        }
+    }
+    if (params) {      // (N = 0: no partial, every wanted gradient is written as 0)
+        Mlp3Reduce r{};
+        r.partial = a.partial; r.n_partials = grid; r.total = (unsigned)mlp3_param_floats(a.d_in, a.h1, a.h2, a.d_out);
+        const unsigned sizes[6] = { (unsigned)(a.h1 * a.d_in), (unsigned)a.h1, (unsigned)(a.h2 * a.h1), (unsigned)a.h2, (unsigned)(a.d_out * a.h2), (unsigned)a.d_out };
+        float* const outs[6] = { d->dw1, d->db1, d->dw2, d->db2, d->dw3, d->db3 };
+        unsigned end = 0;
+        for (int k = 0; k < 6; k++) { end += sizes[k]; r.seg_end[k] = end; r.out[k] = outs[k]; }
+        mlp3_reduce_kernel<<<(r.total + 255) / 256, 256, 0, s>>>(r);
+        GS_LAUNCHED("mlp3_reduce");
+    }
+    return GSRAST_OK;
+}
+
+// ---- the same head with the precision chosen per call (gsrast_mlp_bf16.h); GSRAST_MLP_FP32 IS the calls above ----
+namespace {
+int mlp3_precision_check(const char* who, int precision)
+{
+    if (precision != GSRAST_MLP_FP32 && precision != GSRAST_MLP_BF16) return refuse(who, "precision must be GSRAST_MLP_FP32 (0) or GSRAST_MLP_BF16 (1)");
+    return GSRAST_OK;
+}
+// the kernels with the hidden widths of the reference's heads (128 / 128, 128 / 64) compiled in, or the general one
+typedef void (*mlp3_bf16_kernel_t)(const Mlp3Args);
+mlp3_bf16_kernel_t mlp3_bf16_pick(const gsrast_mlp3* d, mlp3_bf16_kernel_t both128, mlp3_bf16_kernel_t second64, mlp3_bf16_kernel_t general)
+{
+    return d->h1 == 128 && d->h2 == 128 ? both128 : d->h1 == 128 && d->h2 == 64 ? second64 : general;
+}
+int mlp3_bf16_grid(const gsrast_mlp3* d, int workgroups, int per_cu)
+{
+    const long long tiles = ((long long)d->n + MLPB_ROWS - 1) / MLPB_ROWS;
+    return (int)std::min<long long>(workgroups ? workgroups : per_cu * mlp3_default_workgroups(), tiles);
+}
+}  // namespace
+
+size_t gsrast_mlp3_scratch_bytes_p(const gsrast_mlp3* d, int precision, int workgroups)
+{
+    if (mlp3_precision_check("mlp3_scratch_bytes", precision) != GSRAST_OK) return 0;
+    return gsrast_mlp3_scratch_bytes(d, workgroups);      // (bf16: the same slabs, one per workgroup, the same default count)
+}
+
+int gsrast_mlp3_forward_p(const gsrast_mlp3* d, int precision, int workgroups, void* stream)
+{
+    if (int rc = mlp3_precision_check("mlp3_forward", precision)) return rc;
+    if (precision == GSRAST_MLP_FP32) return gsrast_mlp3_forward(d, workgroups, stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mlp3_check("mlp3_forward", d, workgroups)) return rc;
+    if (d->n > 0 && !d->y) return fail(GSRAST_E_ARG, "mlp3_forward: NULL y");
+    if (d->n == 0) return GSRAST_OK;
+    const Mlp3Args a = mlp3_args(d);
+    const auto kernel = mlp3_bf16_pick(d, &mlp3_bf16_fwd_kernel<4, 4>, &mlp3_bf16_fwd_kernel<4, 2>, &mlp3_bf16_fwd_kernel<0, 0>);
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MLPB_FWD_LDS);
+    if (attr != hipSuccess) return fail(GSRAST_E_DEVICE, "mlp3_forward: hipFuncSetAttribute", attr);
+    ProfScope ps(K_MLP_FWD, s);
+    kernel<<<mlp3_bf16_grid(d, workgroups, 2), MLP_THREADS, MLPB_FWD_LDS, s>>>(a);
+    GS_LAUNCHED("mlp3_bf16_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_mlp3_backward_p(const gsrast_mlp3* d, int precision, int workgroups, char* scratch, void* stream)
+{
+    if (int rc = mlp3_precision_check("mlp3_backward", precision)) return rc;
+    if (precision == GSRAST_MLP_FP32) return gsrast_mlp3_backward(d, workgroups, scratch, stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mlp3_check("mlp3_backward", d, workgroups)) return rc;
+    if (d->n > 0 && !d->dy) return fail(GSRAST_E_ARG, "mlp3_backward: NULL dy");
+    if (d->n > 0 && d->sigmoid && !d->y) return fail(GSRAST_E_ARG, "mlp3_backward: the sigmoid head needs y");
+    Mlp3Args a = mlp3_args(d);
+    a.need = (d->dx ? MLP_NEED_DX : 0) | (d->dw1 || d->db1 ? MLP_NEED_L1 : 0) | (d->dw2 || d->db2 ? MLP_NEED_L2 : 0) | (d->dw3 || d->db3 ? MLP_NEED_L3 : 0);
+    if (a.need == 0) return GSRAST_OK;
+    const bool params = (a.need & ~MLP_NEED_DX) != 0;
+    if (params && !scratch) return fail(GSRAST_E_ARG, "mlp3_backward: NULL scratch");
+    a.partial = reinterpret_cast<float*>(scratch);
+    const int grid = mlp3_bf16_grid(d, workgroups, 1);
+    ProfScope ps(K_MLP_BWD, s);
+    if (grid > 0) {
+        const auto kernel = mlp3_bf16_pick(d, &mlp3_bf16_bwd_kernel<4, 4>, &mlp3_bf16_bwd_kernel<4, 2>, &mlp3_bf16_bwd_kernel<0, 0>);
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MLPB_BWD_LDS);
+        if (attr != hipSuccess) return fail(GSRAST_E_DEVICE, "mlp3_backward: hipFuncSetAttribute", attr);
+        const long long tiles = ((long long)d->n + MLPB_ROWS - 1) / MLPB_ROWS, per_launch = (long long)grid * MLPB_FLUSH_TILES;
+        for (a.tile0 = 0; a.tile0 < tiles; a.tile0 += per_launch) {      // (gsrast_mlp_bf16.h: no accumulator chain longer than 512 rows)
+            a.tile_end = std::min(tiles, a.tile0 + per_launch);
+            a.add = a.tile0 > 0;
+            kernel<<<(unsigned)std::min<long long>(grid, a.tile_end - a.tile0), MLP_THREADS, MLPB_BWD_LDS, s>>>(a);
+            GS_LAUNCHED("mlp3_bf16_bwd");
         }
     }
     if (params) {      // (N = 0: no partial, every wanted gradient is written as 0)

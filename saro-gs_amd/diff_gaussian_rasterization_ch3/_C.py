@@ -46,6 +46,7 @@ EXPORTS = (
     "gsrast_distortion_forward", "gsrast_distortion_backward",
     "gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise",
     "gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward",
+    "gsrast_mlp3_scratch_bytes_p", "gsrast_mlp3_forward_p", "gsrast_mlp3_backward_p",
     "gsrast_temporal_gate_forward", "gsrast_temporal_gate_backward", "gsrast_temporal_integral",
 )
 
@@ -161,6 +162,9 @@ class DensifyGroupStruct(C.Structure):
 
 DENSIFY_COPY, DENSIFY_XYZ, DENSIFY_SCALING = 0, 1, 2      # include/gsrast.h: GSRAST_DENSIFY_*
 MCMC_COPY, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2           # include/gsrast.h: GSRAST_MCMC_* (the role of a gsrast_densify_group in the mcmc calls)
+
+
+MLP_FP32, MLP_BF16 = 0, 1                                  # include/gsrast.h: GSRAST_MLP_* (the precision of the gsrast_mlp3_*_p calls)
 
 
 class Mlp3Struct(C.Structure):
@@ -292,6 +296,11 @@ def lib() -> C.CDLL:
     L.gsrast_mlp3_forward.restype = L.gsrast_mlp3_backward.restype = ci
     L.gsrast_mlp3_forward.argtypes = [C.POINTER(Mlp3Struct), ci, vp]
     L.gsrast_mlp3_backward.argtypes = [C.POINTER(Mlp3Struct), ci, vp, vp]
+    L.gsrast_mlp3_scratch_bytes_p.restype = C.c_size_t
+    L.gsrast_mlp3_scratch_bytes_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci]
+    L.gsrast_mlp3_forward_p.restype = L.gsrast_mlp3_backward_p.restype = ci
+    L.gsrast_mlp3_forward_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci, vp]
+    L.gsrast_mlp3_backward_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci, vp, vp]
     L.gsrast_temporal_gate_forward.restype = L.gsrast_temporal_gate_backward.restype = L.gsrast_temporal_integral.restype = ci
     L.gsrast_temporal_gate_forward.argtypes = [ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_temporal_gate_backward.argtypes = [ci, ci, cf, cf, vp, vp, vp, vp, vp, vp, vp]

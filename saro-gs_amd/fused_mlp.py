@@ -1,16 +1,17 @@
 """The deformation heads as one fused kernel each way: Linear -> ReLU -> Linear -> ReLU -> Linear [-> Sigmoid] on the HIP library
-(csrc/gsrast_mlp.h: fp32 on the f32-input matrix instruction, hidden activations kept on chip, recomputed by the backward).
+(csrc/gsrast_mlp.h: fp32 on the f32-input matrix instruction, hidden activations kept on chip, recomputed by the backward), or, with
+precision="bf16", on the bf16 matrix instruction with fp32 accumulation (csrc/gsrast_mlp_bf16.h states what is rounded where).
 
 Stands where the reference's four nn.Sequential heads stand (scene/saro_gaussian.py:104-110: motion_mlp, rot_mlp, shs_mlp: 32 + 9 -> 128
 -> 128 -> 3 / 7 / 48; opacity_mlp: 32 -> 128 -> 64 -> 1 with a Sigmoid), which it evaluates over all Gaussians once or twice per view:
 
-  fused_mlp3(x, w1, b1, w2, b2, w3, b3, x_tail=None, sigmoid_out=False)      the autograd function
-  FusedMLP3 / FusedMLP3.from_sequential(seq)                                 a module holding the Sequential's own Linear layers
-  convert_heads(model)                                                       swaps a model's four head attributes in place
+  fused_mlp3(x, w1, b1, w2, b2, w3, b3, x_tail=None, sigmoid_out=False, precision="fp32")      the autograd function
+  FusedMLP3 / FusedMLP3.from_sequential(seq, precision="fp32")               a module holding the Sequential's own Linear layers
+  convert_heads(model, precision="fp32")                                     swaps a model's four head attributes in place
 
 `x_tail` [N, D_tail] is read behind x's columns without a cat and receives no gradient: the reference's
 `torch.cat((hexplane_feature, time_emb.detach()), 1)`.  Supported: D_x + D_tail <= 64, hidden widths in {32, 64, 96, 128}, D_out <= 64,
-fp32.  There is no CPU / PyTorch fallback: without libgsrast_hip.so and GPU tensors this raises, as do other shapes."""
+fp32 tensors at either precision (the bf16 path converts inside its kernels and keeps no bf16 copy).  There is no CPU / PyTorch fallback: without libgsrast_hip.so and GPU tensors this raises, as do other shapes."""
 import ctypes as C
 from typing import Optional
 
@@ -23,6 +24,14 @@ from diff_gaussian_rasterization_ch3 import _C as _lib
 HEAD_NAMES = ("motion_mlp", "rot_mlp", "shs_mlp", "opacity_mlp")
 HIDDEN_WIDTHS = (32, 64, 96, 128)
 MAX_IO = 64
+PRECISIONS = {"fp32": _lib.MLP_FP32, "bf16": _lib.MLP_BF16}
+
+
+def _precision(precision) -> int:
+    """include/gsrast.h's GSRAST_MLP_* of "fp32" / "bf16", or a ValueError (no device needed)."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"fused_mlp3: precision must be one of {tuple(PRECISIONS)}, got {precision!r}")
+    return PRECISIONS[precision]
 
 
 def _check_shapes(x, w1, b1, w2, b2, w3, b3, x_tail):
@@ -63,7 +72,7 @@ def _desc(N, d_x, d_tail, h1, h2, d_out, sigmoid, **ptrs):
 
 class _FusedMLP3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, x_tail, w1, b1, w2, b2, w3, b3, sigmoid_out, workgroups):
+    def forward(ctx, x, x_tail, w1, b1, w2, b2, w3, b3, sigmoid_out, workgroups, precision):
         dims = _check_shapes(x, w1, b1, w2, b2, w3, b3, x_tail)
         if not x.is_cuda:
             raise RuntimeError("fused_mlp3: tensors must be on a GPU (HIP) device; there is no CPU fallback")
@@ -79,10 +88,10 @@ class _FusedMLP3Fn(torch.autograd.Function):
         y = torch.empty((dims[0], dims[5]), dtype=torch.float32, device=dev)
         d = _desc(*dims, sigmoid_out, x=xs, x_tail=ts, w1=ws[0], b1=ws[1], w2=ws[2], b2=ws[3], w3=ws[4], b3=ws[5], y=y)
         with torch.cuda.device(dev):
-            rc = L.gsrast_mlp3_forward(C.byref(d), int(workgroups), torch.cuda.current_stream(dev).cuda_stream)
+            rc = L.gsrast_mlp3_forward_p(C.byref(d), int(precision), int(workgroups), torch.cuda.current_stream(dev).cuda_stream)
         if rc != 0:
-            raise _lib._err(rc, "gsrast_mlp3_forward")
-        ctx.dims, ctx.sigmoid, ctx.workgroups, ctx.has_tail = dims, bool(sigmoid_out), int(workgroups), ts is not None
+            raise _lib._err(rc, "gsrast_mlp3_forward_p")
+        ctx.dims, ctx.sigmoid, ctx.workgroups, ctx.has_tail, ctx.precision = dims, bool(sigmoid_out), int(workgroups), ts is not None, int(precision)
         # the hidden activations are not kept: x, the tail, the parameters, and y for the sigmoid's derivative
         ctx.save_for_backward(xs, ts if ts is not None else xs.new_empty(0), *ws, y if sigmoid_out else xs.new_empty(0))
         return y
@@ -108,38 +117,41 @@ class _FusedMLP3Fn(torch.autograd.Function):
                   y=y if ctx.sigmoid else None, dy=dy, **g)
         scratch = None
         if any(k != "dx" for k in g):
-            nbytes = L.gsrast_mlp3_scratch_bytes(C.byref(d), ctx.workgroups)      # workgroups x parameters: independent of N
+            nbytes = L.gsrast_mlp3_scratch_bytes_p(C.byref(d), ctx.precision, ctx.workgroups)      # workgroups x parameters: independent of N
             if nbytes == 0:
-                raise _lib._err(-1, "gsrast_mlp3_scratch_bytes")
+                raise _lib._err(-1, "gsrast_mlp3_scratch_bytes_p")
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         if g:
             with torch.cuda.device(dev):
-                rc = L.gsrast_mlp3_backward(C.byref(d), ctx.workgroups, scratch.data_ptr() if scratch is not None else None,
-                                            torch.cuda.current_stream(dev).cuda_stream)
+                rc = L.gsrast_mlp3_backward_p(C.byref(d), ctx.precision, ctx.workgroups, scratch.data_ptr() if scratch is not None else None,
+                                              torch.cuda.current_stream(dev).cuda_stream)
             if rc != 0:
-                raise _lib._err(rc, "gsrast_mlp3_backward")
-        return (g.get("dx"), None, g.get("dw1"), g.get("db1"), g.get("dw2"), g.get("db2"), g.get("dw3"), g.get("db3"), None, None)
+                raise _lib._err(rc, "gsrast_mlp3_backward_p")
+        return (g.get("dx"), None, g.get("dw1"), g.get("db1"), g.get("dw2"), g.get("db2"), g.get("dw3"), g.get("db3"), None, None, None)
 
 
 def fused_mlp3(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, *,
-               x_tail: Optional[torch.Tensor] = None, sigmoid_out: bool = False, workgroups: int = 0) -> torch.Tensor:
+               x_tail: Optional[torch.Tensor] = None, sigmoid_out: bool = False, workgroups: int = 0, precision: str = "fp32") -> torch.Tensor:
     """[sigmoid](relu(relu([x | x_tail] w1^T + b1) w2^T + b2) w3^T + b3).  Gradients go to x and the six parameters (each only when it
     requires one), never to x_tail.  `workgroups` = 0 is the library's choice for the device; the weight gradients are bit-identical from run
-    to run for the same count."""
-    return _FusedMLP3Fn.apply(x, x_tail, w1, b1, w2, b2, w3, b3, bool(sigmoid_out), int(workgroups))
+    to run for the same count.  `precision` = "bf16" runs the products on the bf16 matrix instruction with fp32 accumulation (inputs, weights,
+    hidden activations and back-propagated gradients rounded to bfloat16 where a product reads them); every tensor stays fp32 and the
+    gradients are the fp32 parameters', as under autocast."""
+    return _FusedMLP3Fn.apply(x, x_tail, w1, b1, w2, b2, w3, b3, bool(sigmoid_out), int(workgroups), _precision(precision))
 
 
 class FusedMLP3(nn.Module):
     """Drop-in for nn.Sequential(Linear, ReLU, Linear, ReLU, Linear[, Sigmoid]).  The three Linear layers are children named "0", "2", "4"
     like the Sequential's, so the state_dict keys (0.weight, 0.bias, 2.weight, ...), the order of parameters() and -- through
     from_sequential -- the Parameter objects themselves are the Sequential's: checkpoints, optimizer groups and flat gradient buckets built
-    from the Sequential keep working."""
+    from the Sequential keep working.  `precision` ("fp32" / "bf16") is a plain attribute: not a parameter, not a buffer, not in the state_dict."""
 
-    def __init__(self, d_in: int, h1: int, h2: int, d_out: int, sigmoid_out: bool = False):
+    def __init__(self, d_in: int, h1: int, h2: int, d_out: int, sigmoid_out: bool = False, precision: str = "fp32"):
         super().__init__()
-        self._adopt(nn.Linear(d_in, h1), nn.Linear(h1, h2), nn.Linear(h2, d_out), sigmoid_out)
+        self._adopt(nn.Linear(d_in, h1), nn.Linear(h1, h2), nn.Linear(h2, d_out), sigmoid_out, precision)
 
-    def _adopt(self, l1: nn.Linear, l2: nn.Linear, l3: nn.Linear, sigmoid_out: bool) -> None:
+    def _adopt(self, l1: nn.Linear, l2: nn.Linear, l3: nn.Linear, sigmoid_out: bool, precision: str = "fp32") -> None:
+        _precision(precision)
         for l in (l1, l2, l3):
             if l.bias is None:
                 raise ValueError("FusedMLP3: every Linear needs its bias")
@@ -153,9 +165,10 @@ class FusedMLP3(nn.Module):
         self.add_module("2", l2)
         self.add_module("4", l3)
         self.sigmoid_out = bool(sigmoid_out)
+        self.precision = precision
 
     @classmethod
-    def from_sequential(cls, seq: nn.Sequential) -> "FusedMLP3":
+    def from_sequential(cls, seq: nn.Sequential, precision: str = "fp32") -> "FusedMLP3":
         """The fused module over `seq`'s own Linear layers (same Parameter objects).  Any other structure raises."""
         if not isinstance(seq, nn.Sequential):
             raise ValueError("FusedMLP3.from_sequential: not an nn.Sequential")
@@ -166,28 +179,31 @@ class FusedMLP3(nn.Module):
                              + ", ".join(type(m).__name__ for m in mods))
         self = cls.__new__(cls)
         nn.Module.__init__(self)
-        self._adopt(mods[0], mods[2], mods[4], sigmoid_out)
+        self._adopt(mods[0], mods[2], mods[4], sigmoid_out, precision)
         self.train(seq.training)
         return self
 
     def forward(self, x: torch.Tensor, x_tail: Optional[torch.Tensor] = None) -> torch.Tensor:
         l1, l2, l3 = self._modules["0"], self._modules["2"], self._modules["4"]
-        return fused_mlp3(x, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, x_tail=x_tail, sigmoid_out=self.sigmoid_out)
+        return fused_mlp3(x, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, x_tail=x_tail, sigmoid_out=self.sigmoid_out,
+                          precision=self.precision)
 
     def extra_repr(self) -> str:
-        return f"sigmoid_out={self.sigmoid_out}"
+        return f"sigmoid_out={self.sigmoid_out}, precision={self.precision}"
 
 
-def convert_heads(model, names=HEAD_NAMES):
+def convert_heads(model, names=HEAD_NAMES, precision="fp32"):
     """Swap `model`'s deformation heads for FusedMLP3 in place, where the attribute exists and is a Sequential of the fused structure and
-    widths; returns the names converted.  The parameters stay the same objects, so an optimizer built before the call stays valid."""
+    widths; returns the names converted.  The parameters stay the same objects, so an optimizer built before the call stays valid.  `precision` is
+    given to every head converted."""
+    _precision(precision)
     done = []
     for name in names:
         seq = getattr(model, name, None)
         if not isinstance(seq, nn.Sequential):
             continue
         try:
-            fused = FusedMLP3.from_sequential(seq)
+            fused = FusedMLP3.from_sequential(seq, precision)
         except ValueError:
             continue
         setattr(model, name, fused)
