@@ -705,6 +705,31 @@ void launch_blend_bwd(int exp_mode, const BlendBwdPick& k, uint32_t grid, hipStr
     });
 }
 
+// ---- the replays of a finished forward (gsrast_replay.h): what their five launches take from the forward's state -----------------------
+struct ReplayLaunch {
+    int W, H, gx; uint32_t T; unsigned grid;      // one workgroup per tile, the grid padded to xcd_tile's eight bands
+    // the list in force, resolved as the blend backward resolves it: the tile's range (a tile the list cut's completion pass listed again has
+    // its range in the point list's second half) into the point list at offset 0 of the binning buffer
+    const uint2* ranges; const uint32_t* point_list;
+    const float4 *rec0, *rec1; const float* final_T; const uint32_t *n_contrib, *tile_max;
+    size_t grec;                                  // GeomLayout::grec: where the two backwards add
+    ReplayLaunch(int P, int width, int height, const char* geom, const char* binning, const char* image)
+    {
+        const GeomLayout GL = geom_layout((size_t)P);
+        const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+        W = width; H = height; gx = (width + TILE_X - 1) / TILE_X;
+        T = (uint32_t)gx * (uint32_t)((height + TILE_Y - 1) / TILE_Y); grid = ((T + 7) / 8) * 8;
+        ranges = at<uint2>(image, IL.ranges); point_list = at<uint32_t>(binning, 0);
+        rec0 = at<float4>(geom, GL.rec0); rec1 = at<float4>(geom, GL.rec1); grec = GL.grec;
+        final_T = at<float>(image, IL.final_T); n_contrib = at<uint32_t>(image, IL.n_contrib); tile_max = at<uint32_t>(image, IL.tile_max);
+    }
+    // the kernels' common leading arguments, then the kernel's own
+    template <class K, class... A> void front_to_back(K kernel, hipStream_t s, A... own) const
+    { kernel<<<grid, 256, 0, s>>>(ranges, point_list, W, H, gx, T, rec0, rec1, n_contrib, tile_max, own...); }
+    template <class K, class... A> void back_to_front(K kernel, hipStream_t s, A... own) const
+    { kernel<<<grid, 256, 0, s>>>(ranges, point_list, W, H, gx, T, rec0, rec1, final_T, n_contrib, tile_max, own...); }
+};
+
 } // namespace
 
 extern "C" {
@@ -1754,23 +1779,14 @@ int gsrast_contrib_stats(const gsrast_options* options, int P, int R, int width,
     if (((uintptr_t)stats & 15) || ((uintptr_t)scratch & 15)) return fail(GSRAST_E_ARG, "contrib_stats: stats / scratch must be 16-byte aligned");
     const gsrast_options o = options ? *options : snapshot_defaults();
     if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "contrib_stats: exp_mode must be 0, 1 or 2");
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
     const ContribLayout CL = contrib_layout((size_t)P);
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
-    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
     unsigned long long* const a_sum = at<unsigned long long>(scratch, CL.sum);
     uint32_t* const a_max = at<uint32_t>(scratch, CL.max); uint32_t* const a_cnt = at<uint32_t>(scratch, CL.cnt); uint32_t* const a_top = at<uint32_t>(scratch, CL.top);
     GS_HIP(hipMemsetAsync(scratch, 0, CL.total, s));      // (the caller owes nothing: whatever the scratch held)
     {
         ProfScope ps(K_CONTRIB_BLEND, s);
-        // the list in force, resolved as the blend backward resolves it: the tile's range (a tile the list cut's completion pass listed again has
-        // its range in the point list's second half) into the point list at offset 0 of the binning buffer
-        pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
-            contrib_blend_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
-                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
-                at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), pixel_weights, a_sum, a_max, a_cnt, a_top);
-        });
+        pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { L.front_to_back(contrib_blend_kernel<decltype(mode)::value>, s, pixel_weights, a_sum, a_max, a_cnt, a_top); });
         GS_LAUNCHED("contrib_blend");
     }
     {
@@ -1807,18 +1823,12 @@ int gsrast_features_forward(const gsrast_options* options, int P, int R, int C, 
     if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "features_forward: exp_mode must be 0, 1 or 2");
     // (no Gaussian, or no instance: nothing was blended)
     if (P == 0 || R == 0) { GS_HIP(hipMemsetAsync(feature_map, 0, (size_t)C * (size_t)width * (size_t)height * sizeof(float), s)); return GSRAST_OK; }
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
-    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
     ProfScope ps(K_FEATURES_FWD, s);
     for (int c0 = 0; c0 < C;) {
         const int ch = features_chunk(C, c0);
-        // the list in force, resolved as gsrast_contrib_stats resolves it
         pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { pick_int<4, 8, 16, 32>(ch, [&](auto chunk) {
-            features_fwd_kernel<decltype(mode)::value, decltype(chunk)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
-                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
-                at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), features, C, c0, feature_map);
+            L.front_to_back(features_fwd_kernel<decltype(mode)::value, decltype(chunk)::value>, s, features, C, c0, feature_map);
         }); });
         GS_LAUNCHED("features_fwd");
         c0 += ch;
@@ -1841,18 +1851,12 @@ int gsrast_features_backward(const gsrast_options* options, int P, int R, int C,
     if (P == 0) return GSRAST_OK;
     GS_HIP(hipMemsetAsync(dL_dfeatures, 0, (size_t)P * (size_t)C * sizeof(float), s));
     if (R == 0) return GSRAST_OK;             // (no instance: nothing was blended)
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
-    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
     ProfScope ps(K_FEATURES_BWD, s);
     for (int c0 = 0; c0 < C;) {
         const int ch = features_chunk(C, c0);
         pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { pick_int<4, 8, 16, 32>(ch, [&](auto chunk) {
-            features_bwd_kernel<decltype(mode)::value, decltype(chunk)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
-                at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
-                at<float>(image_buffer, IL.final_T), at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), features, C, c0, dL_dfeature_map,
-                at<float>(geom_buffer, GL.grec), dL_dfeatures);
+            L.back_to_front(features_bwd_kernel<decltype(mode)::value, decltype(chunk)::value>, s, features, C, c0, dL_dfeature_map, at<float>(geom_buffer, L.grec), dL_dfeatures);
         }); });
         GS_LAUNCHED("features_bwd");
         c0 += ch;
@@ -1886,16 +1890,9 @@ int gsrast_distortion_forward(const gsrast_options* options, int P, int R, int w
     const size_t N = (size_t)width * (size_t)height;
     // (no Gaussian, or no instance: nothing was blended)
     if (P == 0 || R == 0) { GS_HIP(hipMemsetAsync(distort_map, 0, N * sizeof(float), s)); GS_HIP(hipMemsetAsync(moments, 0, 2 * N * sizeof(float), s)); return GSRAST_OK; }
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
-    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
     ProfScope ps(K_DISTORT_FWD, s);
-    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
-        distort_fwd_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
-            at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
-            at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), distort_map, moments);
-    });
+    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { L.front_to_back(distort_fwd_kernel<decltype(mode)::value>, s, distort_map, moments); });
     GS_LAUNCHED("distort_fwd");
     return GSRAST_OK;
 }
@@ -1907,17 +1904,9 @@ int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int 
     if (const char* e = distortion_refusal(false, options, P, R, width, height, geom_buffer, binning_buffer, image_buffer, dL_ddistort, moments)) return fail(GSRAST_E_ARG, e);
     const gsrast_options o = options ? *options : snapshot_defaults();
     if (P == 0 || R == 0) return GSRAST_OK;      // (no Gaussian, or no instance: nothing was blended, nothing is added)
-    const GeomLayout GL = geom_layout((size_t)P);
-    const ImgLayout IL = img_layout((size_t)width, (size_t)height);
-    const int gx = (width + TILE_X - 1) / TILE_X, gy = (height + TILE_Y - 1) / TILE_Y;
-    const uint32_t T = (uint32_t)gx * (uint32_t)gy;
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
     ProfScope ps(K_DISTORT_BWD, s);
-    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) {
-        distort_bwd_kernel<decltype(mode)::value><<<((T + 7) / 8) * 8, 256, 0, s>>>(
-            at<uint2>(image_buffer, IL.ranges), at<uint32_t>(binning_buffer, 0), width, height, gx, T, at<float4>(geom_buffer, GL.rec0), at<float4>(geom_buffer, GL.rec1),
-            at<float>(image_buffer, IL.final_T), at<uint32_t>(image_buffer, IL.n_contrib), at<uint32_t>(image_buffer, IL.tile_max), moments, dL_ddistort,
-            at<float>(geom_buffer, GL.grec));
-    });
+    pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { L.back_to_front(distort_bwd_kernel<decltype(mode)::value>, s, moments, dL_ddistort, at<float>(geom_buffer, L.grec)); });
     GS_LAUNCHED("distort_bwd");
     return GSRAST_OK;
 }

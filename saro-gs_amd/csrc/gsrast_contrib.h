@@ -1,18 +1,14 @@
 // gsrast_contrib.h -- per-Gaussian blend-weight statistics of one finished forward (include/gsrast.h: gsrast_contrib_stats).
 //
-// For a pixel p inside the image and a Gaussian i, i CONTRIBUTES to p when the forward blended it there: its position in the tile's list in
-// force is below n_contrib[p] and it passed the forward's per-pair tests (power <= 0 && power >= threshold; alpha = min(0.99, opacity
-// exp(power)) >= 1/255; T (1 - alpha) >= 1e-4 -- the terminating entry does not contribute).  Its weight is w = alpha T, T the transmittance
-// in front of it.  m_p = pixel_weights[p] clamped to [0, 1] (1 without weights); a pixel with m_p = 0 counts in no column.  One row per
-// Gaussian:  [ sum_p m_p w,  max over pixels with m_p > 0 of w,  number of pixels with m_p > 0 it contributes to,  number of those pixels
-// whose largest w is this Gaussian's (first in list order on a tie) ].
+// Contribution is the replay invariant of gsrast_replay.h; the weight of a contributing pair is w = alpha T.  m_p = pixel_weights[p] clamped to
+// [0, 1] (1 without weights); a pixel with m_p = 0 counts in no column.  One row per Gaussian:  [ sum_p m_p w,  max over pixels with
+// m_p > 0 of w,  number of pixels with m_p > 0 it contributes to,  number of those pixels whose largest w is this Gaussian's (first in list
+// order on a tie) ].
 //
-// contrib_blend_kernel replays blend_fwd_cull_kernel (gsrast_blend.h) from the state it left behind: the same geometry (one tile per
-// workgroup, four wave64, each an 8 x 8 block), the same staging, the same wave-level culling (strip_may_touch), the same arithmetic
-// (gs_power, gs_exp<EXPMODE, true>, the forward's association) and the same nested tests, so that every pixel's T is the forward's bit for
-// bit at every step.  What the forward decided by carrying `alive` lanes it decides from the stored n_contrib: a lane looks at list positions
-// below its own n_contrib, a wave at those below its block's maximum, the workgroup at those below tile_max -- at every such position the
-// forward's lane was alive, so the replayed pair sees the operands the forward saw.  rec2 (the colour) is not staged: no statistic reads it.
+// contrib_blend_kernel walks front to back with a body of its own, line for line replay_front_to_back's, in which a pixel with m_p = 0 looks
+// at no list position, every lane takes part in the per-pair reductions below and a batch is retired behind a third barrier: written as a
+// visitor of that walker it measured 1 - 2 % slower on the MI355X (DESIGN_LOG.md), so a change to the walker's tests or arithmetic has to be
+// made here as well.
 //
 // Accumulation is integer and commutative from the first cross-wave step on, so the result is bit-identical from run to run:
 //   * per surviving (wave, staged slot): the masked sum m w by a fixed-order DPP reduction (wave_sum_to_lane63), the maximum of w by the same
@@ -24,6 +20,9 @@
 //     non-negative: their bit patterns order like their values) and one 32-bit atomicAdd of the count;
 //   * each lane keeps its pixel's best (w, Gaussian) in registers and adds 1 to that Gaussian's top count at the end.
 // contrib_finish_kernel turns the 20 bytes of accumulators per Gaussian into the float32 row and clears them.
+//
+// Resources (gfx950, tools/kernel_resources.sh contrib_; scratch 0), exp_mode 0 | 1 | 2:
+//   contrib_blend_kernel:  VGPR 65 | 65 | 65,  LDS 21504 B  ->  seven waves per SIMD, by the registers (512 / 72) and by LDS (160 KiB / 21504 B) alike
 #pragma once
 #include "gsrast_common.h"
 #include "gsrast_blend.h"

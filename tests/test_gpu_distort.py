@@ -164,6 +164,51 @@ def test_with_features_the_gradients_are_the_sum_of_both_losses(rast, gpu):
         assert (np.abs(rd["r64"]["grads"][n]).reshape(tol.shape) > 100 * tol).any() and (np.abs(rf["r64"]["grads"][n]).reshape(tol.shape) > 100 * tol).any(), n
 
 
+@pytest.mark.parametrize("exp_mode", [1, 2])
+def test_with_features_in_the_other_exp_modes(exp_mode, rast, gpu):
+    """Device against device under exp_mode 1 / 2 (the fp64 references belong to mode 0 and only scale the gradient bar): the map beside 19
+    feature channels is the map alone, bit for bit and from run to run; the gradients of the three-part loss of the test above are the sum
+    of the feature-and-colour loss's and the distortion loss's; one launch of each of the four kernels."""
+    _C = rast._C
+    rf, rd = fm.reference("a", 19), dm.reference("a", "plain", colour_loss=False)
+    g = dict(rd["r64"]["g"], g0=rf["r64"]["g0"])
+    sc, cam = rd["sc"], rd["cam"]
+    _C.set_option("exp_mode", exp_mode)
+    try:
+        _C.set_option("profile", -1)
+        try:
+            _C.profile_reset()
+            both = _render(rast, gpu, sc, cam, F=rf["F"], g=g, g1=rf["r64"]["g1"])
+            prof = _C.profile_read()
+        finally:
+            _C.set_option("profile", 0)
+            _C.profile_reset()
+        again = _render(rast, gpu, sc, cam, F=rf["F"])
+        alone = _render(rast, gpu, sc, cam)
+        feat = _render(rast, gpu, sc, cam, F=rf["F"], g=dict(g0=g["g0"]), g1=rf["r64"]["g1"])
+        dist = _render(rast, gpu, sc, cam, F=rf["F"], g=dict(gd=g["gd"]), colour_loss=False)
+    finally:
+        _C.set_option("exp_mode", 0)
+    assert all(prof[k][1] == 1 for k in ("features_fwd", "features_bwd", "distort_fwd", "distort_bwd"))
+    assert not torch.isnan(both["map"]).any() and float(both["map"].detach().max()) > 0
+    assert torch.equal(both["map"], alone["map"]) and torch.equal(both["map"], again["map"]) and torch.equal(both["fmap"], again["fmap"])
+    assert not dist["grads"]["features"].any()
+    worst = ("", 0.0)
+    for n in both["grads"]:
+        s = feat["grads"][n] + dist["grads"][n]
+        w64 = rf["r64"]["grads"][n] + (rd["r64"]["grads"][n] if n in rd["r64"]["grads"] else 0.0)
+        w32 = rf["r32"]["grads"][n] + (rd["r32"]["grads"][n] if n in rd["r32"]["grads"] else 0.0)
+        tol = grad_tol(w64.reshape(s.shape), w32.reshape(s.shape))
+        ratio = float((np.abs(both["grads"][n] - s) / np.maximum(tol, 1e-300)).max())
+        worst = max(worst, (n, ratio), key=lambda x: x[1])
+        assert np.abs(feat["grads"][n]).max() > 0 or n == "shs", n
+        assert (np.abs(both["grads"][n] - s) <= tol).all(), (n, ratio)
+    print(f"exp_mode {exp_mode}: features + distortion, worst gradient |both - (feat + dist)| / bar {worst[1]:.3f} ({worst[0]})")
+    for n in ("means2D", "opacities", "means3D"):      # neither part is negligible: overwriting instead of adding would show
+        tol = grad_tol(rd["r64"]["grads"][n].reshape(both["grads"][n].shape))
+        assert (np.abs(both["grads"][n] - feat["grads"][n]) > 100 * tol).any() and (np.abs(both["grads"][n] - dist["grads"][n]) > 100 * tol).any(), n
+
+
 def test_camera_gradients_of_a_distortion_only_loss(rast, gpu):
     """viewmatrix.grad / projmatrix.grad of sum distort gd against the restated renderer with the camera as leaves, fp64; bar grad_tol(want, its
     float32 evaluation).  The path through z (float 9 of the records -> the per-Gaussian backward's dV) is the new part."""

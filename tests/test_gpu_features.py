@@ -152,6 +152,34 @@ def test_three_channels_are_the_colour_path(name, rast, gpu):
     print(f"case {name}: features vs colors_precomp, worst gradient |h - c| / bar {worst[1]:.3f} ({worst[0]})")
 
 
+@pytest.mark.parametrize("exp_mode", [1, 2])
+def test_three_channels_are_the_colour_path_in_the_other_exp_modes(exp_mode, rast, gpu):
+    """The device-against-device half of the test above with both renders under exp_mode 1 / 2: the replay's alpha and T are the forward's
+    own in every mode, so the bars stand as they are and every pixel is compared (the fp64 reference and its ambiguity mask belong to mode 0
+    and serve as the gradient bar's scale only)."""
+    r = fm.reference("a", 3, colour_loss=False)
+    r64, r32 = r["r64"], r["r32"]
+    rast._C.set_option("exp_mode", exp_mode)
+    try:
+        h = _render(rast, gpu, r["sc"], r["cam"], r["F"], g1=r64["g1"])
+        c = _render(rast, gpu, r["sc"], r["cam"], None, precomp=r["F"], bg=np.zeros(3, np.float32), g0=r64["g1"])
+    finally:
+        rast._C.set_option("exp_mode", 0)
+    a, rr = MAP_BAR
+    m, col = _np(h["map"]), _np(c["out"][0])
+    tol = 4.0 * (a * np.abs(col).max() + rr * np.abs(col))
+    print(f"exp_mode {exp_mode}: features vs colors_precomp, map worst |h - c| / bar {float((np.abs(m - col) / tol).max()):.3f}")
+    assert not np.isnan(m).any() and np.abs(col).max() > 0 and (np.abs(m - col) <= tol).all()
+    worst = ("", 0.0)
+    for n, k in (("means3D", "means3D"), ("means2D", "means2D"), ("opacities", "opacities"), ("scales", "scales"), ("rotations", "rotations"), ("features", "shs")):
+        tol = grad_tol(r64["grads"][n], r32["grads"][n])
+        ratio = float((np.abs(h["grads"][n] - c["grads"][k]) / tol).max())
+        worst = max(worst, (n, ratio), key=lambda x: x[1])
+        assert np.abs(h["grads"][n]).max() > 0, n
+        assert (np.abs(h["grads"][n] - c["grads"][k]) <= tol).all(), (n, ratio)
+    print(f"exp_mode {exp_mode}: features vs colors_precomp, worst gradient |h - c| / bar {worst[1]:.3f} ({worst[0]})")
+
+
 # ---- 3. additivity: the records are added to, not overwritten --------------------------------------------------------------------------------
 def test_colour_and_feature_gradients_add(rast, gpu):
     r = fm.reference("a", 19)
