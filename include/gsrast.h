@@ -927,10 +927,15 @@ int gsrast_knn3_mean_dist2(int P, const float* points, float* mean_dist2, char* 
  *   plane      channel-last level 0 [H][W][C] fp32 (hexplane.py:35 layout); u = pts[n][cu], v = pts[n][cv] in [0,1]
  *              texture coordinates; bias = min(levels[n][cu], levels[n][cv]) (hexplane.py:46)
  *   features   [N][F]; plane p adds its C channels at features[n][out_offset .. out_offset + C); planes sharing an
- *              out_offset (the six planes of a scale) must be adjacent in the array and are summed in array order
- *   C          power of two in [4, 64]; D = floats per pts / levels row (4 in the reference)
+ *              out_offset (the six planes of a scale) must be adjacent in the array and are summed in array order; two
+ *              blocks are equal or disjoint (GSRAST_E_ARG otherwise).  Columns of a row that no block covers are left
+ *              UNWRITTEN by the forward (the caller zeroes them if it reads them) and are not read by the backward
+ *   C          power of two in [4, 64]; D = floats per pts / levels row (4 in the reference); F = floats per feature row,
+ *              a multiple of 4, up to 24 blocks wide (the reference's 4 scales of 32 channels: F = 128)
  *   scratch    >= gsrast_hexplane_scratch_bytes() bytes (mip stacks: built by every forward call, as the op does; gradient
- *              stacks and the sorted (plane, point) pairs of the backward)
+ *              stacks and the sorted (plane, point) pairs of the backward).  That call is not given F: it checks what does
+ *              not depend on the row width and returns 0, with its reason in gsrast_last_error(), when a descriptor is
+ *              refused; whether a block fits its row is checked by forward / backward
  * backward: grad_tex of every plane is overwritten with dL/dtex; d_pts / d_levels [N][D] optional (the reference detaches
  * both, scene/saro_gaussian.py:780); mips_built != 0 says scratch still holds the forward's stacks of these textures.
  * All pointers inside gsrast_plane and the tensor arguments are device pointers; `planes` itself is a host array. */

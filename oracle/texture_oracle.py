@@ -26,6 +26,11 @@ Published algorithm, as restated here:
   * gradients: to the texels of both levels (then pulled down the stack to level 0, the transpose of the box average),
     to uv (bilinear slope * extent, 0 where clamped), to the bias (sum_c dy_c (b_c - a_c) where f > 0)
 
+Beside the fp64 restatement the same functions give, for the tests' per-element bars, an fp32 restatement (dtype=np.float32; the
+texel gradient summed in a chosen point order) and the ABSOLUTE COMPANION (absolute=True: every term replaced by its absolute
+value, the size of what was summed into each element); interpolate_ms_features covers the summed-scales and space | time
+layouts and returns d_pts / d_levels as well.
+
 The structure (box-average pyramid, border-clamped half-texel-centred bilinear, level lerp) is pinned against torch's own
 `avg_pool2d` + `grid_sample(padding_mode='border', align_corners=False)` + autograd in tests/test_oracle_texture.py.
 """
@@ -46,83 +51,106 @@ def mip_sizes(W, H, max_mip_level):
     return sizes
 
 
-def build_mips(tex, max_mip_level):
-    """tex [H, W, C] -> list of levels (fp64)."""
-    tex = np.asarray(tex, np.float64)
+def build_mips(tex, max_mip_level, dtype=np.float64):
+    """tex [H, W, C] -> list of levels, every operation in `dtype`."""
+    T = np.dtype(dtype).type
+    tex = np.asarray(tex, dtype)
     H, W, _ = tex.shape
     out = [tex]
     for (w, h) in mip_sizes(W, H, max_mip_level)[1:]:
         p = out[-1]
         ph, pw = p.shape[:2]
         if pw > 1 and ph > 1:
-            n = 0.25 * (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2])
+            n = T(0.25) * (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2])
         elif pw > 1:
-            n = 0.5 * (p[:, 0::2] + p[:, 1::2])
+            n = T(0.5) * (p[:, 0::2] + p[:, 1::2])
         else:
-            n = 0.5 * (p[0::2] + p[1::2])
-        assert n.shape[:2] == (h, w)
+            n = T(0.5) * (p[0::2] + p[1::2])
+        assert n.shape[:2] == (h, w) and n.dtype == tex.dtype
         out.append(n)
     return out
 
 
-def pull_down(dmips):
+def pull_down(dmips, dtype=np.float64):
     """Transpose of build_mips: gradient of all levels -> gradient of level 0."""
-    d = [np.array(x, np.float64) for x in dmips]
+    T = np.dtype(dtype).type
+    d = [np.array(x, dtype) for x in dmips]
     for l in range(len(d) - 1, 0, -1):
         g, p = d[l], d[l - 1]
         ph, pw = p.shape[:2]
         if pw > 1 and ph > 1:
             for dy, dx in itertools.product((0, 1), (0, 1)):
-                p[dy::2, dx::2] += 0.25 * g
+                p[dy::2, dx::2] += T(0.25) * g
         elif pw > 1:
-            p[:, 0::2] += 0.5 * g
-            p[:, 1::2] += 0.5 * g
+            p[:, 0::2] += T(0.5) * g
+            p[:, 1::2] += T(0.5) * g
         else:
-            p[0::2] += 0.5 * g
-            p[1::2] += 0.5 * g
+            p[0::2] += T(0.5) * g
+            p[1::2] += T(0.5) * g
     return d[0]
 
 
 def _level_terms(uv, w, h):
-    u = uv[:, 0] * w - 0.5
-    v = uv[:, 1] * h - 0.5
-    u = np.minimum(np.maximum(u, 0.0), w - 1.0)
-    v = np.minimum(np.maximum(v, 0.0), h - 1.0)
+    T = uv.dtype.type
+    u = uv[:, 0] * T(w) - T(0.5)
+    v = uv[:, 1] * T(h) - T(0.5)
+    u = np.minimum(np.maximum(u, T(0.0)), T(w - 1.0))
+    v = np.minimum(np.maximum(v, T(0.0)), T(h - 1.0))
     cu = (u == 0.0) | (u == w - 1.0)
     cv = (v == 0.0) | (v == h - 1.0)
     iu0 = np.floor(u).astype(np.int64)
     iv0 = np.floor(v).astype(np.int64)
     iu1 = iu0 + np.where(cu, 0, 1)
     iv1 = iv0 + np.where(cv, 0, 1)
-    return iu0, iu1, iv0, iv1, u - iu0, v - iv0
+    return iu0, iu1, iv0, iv1, u - iu0.astype(uv.dtype), v - iv0.astype(uv.dtype)
 
 
-def _levels(bias, n_levels):
-    fl = np.minimum(np.maximum(np.asarray(bias, np.float64), 0.0), float(n_levels))
+def _levels(bias, n_levels, dtype=np.float64):
+    T = np.dtype(dtype).type
+    fl = np.minimum(np.maximum(np.asarray(bias, dtype), T(0.0)), T(n_levels))
     l0 = np.floor(fl).astype(np.int64)
     two = fl > 0.0
     l1 = np.where(two, np.minimum(l0 + 1, n_levels), 0)
-    f = np.where(two, fl - l0, 0.0)
+    f = np.where(two, fl - l0.astype(dtype), T(0.0))
     return l0, l1, f
 
 
-def texture(tex, uv, bias, max_mip_level, dy=None):
-    """tex [H,W,C], uv [N,2], bias [N] -> out [N,C]; with dy [N,C] also (dtex [H,W,C], duv [N,2], dbias [N])."""
-    mips = build_mips(tex, max_mip_level)
-    uv = np.asarray(uv, np.float64)
+def texture(tex, uv, bias, max_mip_level, dy=None, dtype=np.float64, order=None, absolute=False):
+    """tex [H,W,C], uv [N,2], bias [N] -> out [N,C]; with dy [N,C] also (dtex [H,W,C], duv [N,2], dbias [N]).
+
+    dtype     every operation in that type (np.float32: the same arithmetic as a plain fp32 program would do it; the texel
+              gradient is then summed point by point in fp32, in the order of `order`)
+    order     a permutation of the points: the order in which their contributions reach the texel gradient (nothing else
+              depends on it; outputs per point come back in the caller's order)
+    absolute  the ABSOLUTE COMPANION: the same formulas with every term replaced by its absolute value.  All interpolation
+              weights are non-negative, so out is the lookup of |tex| and dtex is the texel gradient of |dy|; a texel
+              difference b - a becomes |b| + |a| in the uv slopes and in the bias gradient.  It is the size s_i of what
+              was summed into element i: an fp32 evaluation errs by a small multiple of 2^-24 s_i, whatever cancelled."""
+    if order is not None:
+        order = np.asarray(order)
+        inv = np.empty_like(order)
+        inv[order] = np.arange(order.size)
+        r = texture(tex, np.asarray(uv)[order], np.asarray(bias)[order], max_mip_level, None if dy is None else np.asarray(dy)[order],
+                    dtype=dtype, absolute=absolute)
+        return r[inv] if dy is None else (r[0][inv], r[1], r[2][inv], r[3][inv])
+    T = np.dtype(dtype).type
+    if absolute:
+        tex = np.abs(np.asarray(tex, dtype))
+    mips = build_mips(tex, max_mip_level, dtype)
+    uv = np.asarray(uv, dtype)
     N, C = uv.shape[0], mips[0].shape[2]
-    l0, l1, f = _levels(bias, len(mips) - 1)
-    out = np.zeros((N, C))
+    l0, l1, f = _levels(bias, len(mips) - 1, dtype)
+    sgn = T(1.0) if absolute else T(-1.0)        # a difference b - a is b + sgn * a
     want = dy is not None
     if want:
-        dy = np.asarray(dy, np.float64)
+        dy = np.asarray(dy, dtype)
+        if absolute:
+            dy = np.abs(dy)
         dm = [np.zeros_like(m) for m in mips]
-        duv = np.zeros((N, 2))
-        dbias = np.zeros(N)
+        duv = np.zeros((N, 2), dtype)
     vals = {}
     for which, lv in ((0, l0), (1, l1)):
-        B = np.zeros((N, C))
-        slope = np.zeros((N, 2))
+        B = np.zeros((N, C), dtype)
         for l in np.unique(lv):
             sel = np.nonzero(lv == l)[0] if which == 0 else np.nonzero((lv == l) & (f > 0.0))[0]
             if sel.size == 0:
@@ -136,52 +164,77 @@ def texture(tex, uv, bias, max_mip_level, dy=None):
             bot = a01 + (a11 - a01) * fu_
             B[sel] = top + (bot - top) * fv_
             if want:
-                wl = (1.0 - f[sel]) if which == 0 else f[sel]
+                one = T(1.0)
+                wl = (one - f[sel]) if which == 0 else f[sel]
                 g = dy[sel] * wl[:, None]
-                np.add.at(dm[l], (iv0, iu0), g * (1 - fu_) * (1 - fv_))
-                np.add.at(dm[l], (iv0, iu1), g * fu_ * (1 - fv_))
-                np.add.at(dm[l], (iv1, iu0), g * (1 - fu_) * fv_)
+                np.add.at(dm[l], (iv0, iu0), g * (one - fu_) * (one - fv_))
+                np.add.at(dm[l], (iv0, iu1), g * fu_ * (one - fv_))
+                np.add.at(dm[l], (iv1, iu0), g * (one - fu_) * fv_)
                 np.add.at(dm[l], (iv1, iu1), g * fu_ * fv_)
-                dBdu = ((a10 - a00) * (1 - fv_) + (a11 - a01) * fv_) * w
-                dBdv = ((a01 - a00) * (1 - fu_) + (a11 - a10) * fu_) * h
-                duv[sel, 0] += (g * dBdu).sum(1)
-                duv[sel, 1] += (g * dBdv).sum(1)
+                # a clamped axis has i1 == i0: its difference is 0 (and stays 0 in the absolute companion)
+                dx0, dx1 = np.where(iu1 != iu0, 1, 0).astype(dtype)[:, None], np.where(iv1 != iv0, 1, 0).astype(dtype)[:, None]
+                dBdu = (dx0 * (a10 + sgn * a00) * (one - fv_) + dx0 * (a11 + sgn * a01) * fv_) * T(w)
+                dBdv = (dx1 * (a01 + sgn * a00) * (one - fu_) + dx1 * (a11 + sgn * a10) * fu_) * T(h)
+                duv[sel, 0] += (g * dBdu).sum(1, dtype=dtype)
+                duv[sel, 1] += (g * dBdv).sum(1, dtype=dtype)
         vals[which] = B
     two = (f > 0.0)[:, None]
     out = np.where(two, vals[0] + f[:, None] * (vals[1] - vals[0]), vals[0])
     if not want:
         return out
-    dbias = np.where(f > 0.0, (dy * (vals[1] - vals[0])).sum(1), 0.0)
-    return out, pull_down(dm), duv, dbias
+    dbias = np.where(f > 0.0, (dy * (vals[1] + sgn * vals[0])).sum(1, dtype=dtype), T(0.0))
+    return out, pull_down(dm, dtype), duv, dbias
 
 
 PLANES = list(itertools.combinations(range(4), 2))      # scene/hexplane.py:105-107: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
 
 
-def interpolate_ms_features(pts, ms_grids, levels, dy=None):
-    """scene/hexplane.py:95-139 with concat_features=True, concat_planes=False (the values ScaleAwareResField fixes,
-    :168-169).  pts [N,4] in texture coordinates, ms_grids[scale][plane] = [C, H, W] (the parameter's layout without its
-    leading 1), levels [N,4].  Returns features [N, sum C]; with dy also the per-grid gradients (same nesting)."""
-    pts = np.asarray(pts, np.float64)
-    levels = np.asarray(levels, np.float64)
-    feats, dgrids = [], []
-    off = 0
-    for grids in ms_grids:
-        C = grids[0].shape[0]
-        acc = np.zeros((pts.shape[0], C))
+def field_layout(n_scales, C, concat_features=True, concat_planes=False):
+    """(feature width, offsets[scale][plane]) of scene/hexplane.py:95-139: the six planes of a scale are summed into one
+    block (concat_planes: planes 0, 1, 3 = space into one block, 2, 4, 5 = those with the time axis into the next, :121-125);
+    the scales' blocks are concatenated (concat_features) or summed."""
+    groups = [[0, 1, 3], [2, 4, 5]] if concat_planes else [list(range(len(PLANES)))]
+    per_scale = C * len(groups)
+    offs = [[(s * per_scale if concat_features else 0) + next(gi for gi, g in enumerate(groups) if ci in g) * C
+             for ci in range(len(PLANES))] for s in range(n_scales)]
+    return (per_scale * n_scales if concat_features else per_scale), offs
+
+
+def interpolate_ms_features(pts, ms_grids, levels, dy=None, concat_features=True, concat_planes=False, dtype=np.float64, order=None,
+                            absolute=False):
+    """scene/hexplane.py:95-139; the defaults concat_features=True, concat_planes=False are the values ScaleAwareResField
+    fixes (:168-169).  pts [N,4] in texture coordinates, ms_grids[scale][plane] = [C, H, W] (the parameter's layout without
+    its leading 1), levels [N,4].  Returns features [N, F]; with dy [N, F] also the per-grid gradients (same nesting) and
+    d_pts [N,4], d_levels [N,4]: sums over the planes that share a column; a plane's bias is min(levels[cu], levels[cv]), so
+    its bias gradient goes to the smaller of the two level columns, to cu on a tie (what torch.min does).
+    dtype / order / absolute: as in texture()."""
+    T = np.dtype(dtype).type
+    pts = np.asarray(pts, dtype)
+    levels = np.asarray(levels, dtype)
+    N = pts.shape[0]
+    C = ms_grids[0][0].shape[0]
+    F, offs = field_layout(len(ms_grids), C, concat_features, concat_planes)
+    f = np.zeros((N, F), dtype)
+    dgrids = []
+    d_pts, d_levels = np.zeros((N, 4), dtype), np.zeros((N, 4), dtype)
+    for s, grids in enumerate(ms_grids):
         dg = []
         for ci, comb in enumerate(PLANES):
-            tex = np.transpose(np.asarray(grids[ci], np.float64), (1, 2, 0))          # hexplane.py:35 permute(0,2,3,1)
-            bias = levels[:, list(comb)].min(axis=1)                                    # hexplane.py:46
-            mm = 7 if 3 not in comb else 0                                              # hexplane.py:55, :117
+            cu, cv = comb
+            off = offs[s][ci]
+            tex = np.transpose(np.asarray(grids[ci], dtype), (1, 2, 0))                # hexplane.py:35 permute(0,2,3,1)
+            bias = np.minimum(levels[:, cu], levels[:, cv])                            # hexplane.py:46
+            mm = 7 if 3 not in comb else 0                                             # hexplane.py:55, :117
             if dy is None:
-                acc = acc + texture(tex, pts[:, list(comb)], bias, mm)
-            else:
-                o, dt, _, _ = texture(tex, pts[:, list(comb)], bias, mm, dy[:, off:off + C])
-                acc = acc + o
-                dg.append(np.transpose(dt, (2, 0, 1)))
-        feats.append(acc)
+                f[:, off:off + C] += texture(tex, pts[:, [cu, cv]], bias, mm, dtype=dtype, absolute=absolute)
+                continue
+            o, dt, duv, db = texture(tex, pts[:, [cu, cv]], bias, mm, np.asarray(dy)[:, off:off + C], dtype=dtype, order=order, absolute=absolute)
+            f[:, off:off + C] += o
+            dg.append(np.transpose(dt, (2, 0, 1)))
+            d_pts[:, cu] += duv[:, 0]
+            d_pts[:, cv] += duv[:, 1]
+            to_v = levels[:, cv] < levels[:, cu]
+            d_levels[:, cu] += np.where(to_v, T(0.0), db)
+            d_levels[:, cv] += np.where(to_v, db, T(0.0))
         dgrids.append(dg)
-        off += C
-    f = np.concatenate(feats, axis=1)
-    return f if dy is None else (f, dgrids)
+    return f if dy is None else (f, dgrids, d_pts, d_levels)

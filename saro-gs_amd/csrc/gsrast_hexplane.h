@@ -455,7 +455,7 @@ hex_grad_uv_kernel(HexArgs a, const float* __restrict__ pts, const float* __rest
         float du0, dv0, du1 = 0.0f, dv1 = 0.0f;
         hex_slopes(lv0, hex_tap(u, v, w0, h0), q4, q, w0, h0, g, va, du0, dv0);
         float db = 0.0f;
-        if (L.two) {
+        if (L.f > 0.0f) {                                       // an integral level is a single level: no second fetch, no bias gradient (as the op)
             const int w1 = hex_extent(P.W, L.l1), h1 = hex_extent(P.H, L.l1);
             const float4* lv1 = reinterpret_cast<const float4*>(L.l1 ? P.mips + (size_t)hex_level_offset(P.W, P.H, L.l1) * a.C : P.tex);
             hex_slopes(lv1, hex_tap(u, v, w1, h1), q4, q, w1, h1, g, vb, du1, dv1);

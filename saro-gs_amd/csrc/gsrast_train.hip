@@ -680,19 +680,27 @@ int hex_levels(int W, int H, int limit)
     }
     return l;
 }
+// F < 0: the caller does not know the row width (gsrast_hexplane_scratch_bytes); everything that needs none is still checked
 const char* hex_check(int n_planes, const gsrast_plane* planes, int C, int D, int F)
 {
     if (n_planes < 1 || n_planes > HEX_MAX_PLANES || !planes) return "hexplane: 1..24 planes";
     if (C < 4 || C > 64 || (C & (C - 1))) return "hexplane: channels must be a power of two in [4, 64]";
-    if (D < 2 || D > 8 || F < C || (F & 3)) return "hexplane: 2..8 coordinates per point, feature rows a multiple of 4 floats";
+    if (D < 2 || D > 8 || (F >= 0 && (F < C || (F & 3)))) return "hexplane: 2..8 coordinates per point, feature rows a multiple of 4 floats";
     for (int p = 0; p < n_planes; p++) {
         const gsrast_plane& g = planes[p];
         if (g.W < 1 || g.H < 1 || (long long)g.W * g.H > (1ll << 26)) return "hexplane: bad plane extent";
         if (g.cu < 0 || g.cu >= D || g.cv < 0 || g.cv >= D) return "hexplane: coordinate column outside the point row";
         if (g.max_mip_level < 0) return "hexplane: negative max_mip_level";
-        if (g.out_offset < 0 || (g.out_offset & 3) || g.out_offset + C > F) return "hexplane: feature block outside the row";
+        if (g.out_offset < 0 || (g.out_offset & 3) || (F >= 0 && g.out_offset > F - C)) return "hexplane: feature block outside the row";
         if (hex_levels(g.W, g.H, g.max_mip_level) < 0) return "hexplane: a mip level has an odd extent > 1 (limit max_mip_level)";
         if (hex_levels(g.W, g.H, g.max_mip_level) >= HEX_MAX_LEVELS) return "hexplane: too many mip levels";
+        // the forward sums a block in registers over ADJACENT planes and stores it once: an equal offset further back, or a block
+        // that covers part of another, would be overwritten, and the backward would differentiate a sum that was never formed
+        for (int q = 0; q < p; q++) {
+            const int o = planes[q].out_offset;
+            if (o == g.out_offset ? planes[p - 1].out_offset != g.out_offset : (o < g.out_offset + C && g.out_offset < o + C))
+                return "hexplane: planes sharing a feature block must be adjacent, and blocks must be equal or disjoint";
+        }
     }
     return nullptr;
 }
@@ -752,7 +760,9 @@ int hex_build_mips(const HexArgs& a, hipStream_t s)
 
 size_t gsrast_hexplane_scratch_bytes(int n_planes, const gsrast_plane* planes, int C, int N)
 {
-    if (N < 0 || hex_check(n_planes, planes, C, 8, 64)) return 0;
+    // no row width is passed: whether a block fits its row is for forward / backward to say.  0 = refused, gsrast_last_error() has the text
+    if (N < 0) { fail(GSRAST_E_ARG, "hexplane_scratch_bytes: bad size"); return 0; }
+    if (const char* e = hex_check(n_planes, planes, C, 8, -1)) { fail(GSRAST_E_ARG, e); return 0; }
     return hex_layout(n_planes, planes, C, (size_t)N).total;
 }
 

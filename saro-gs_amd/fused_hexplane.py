@@ -62,10 +62,13 @@ class _HexplaneFn(torch.autograd.Function):
         ps = _PlaneSet(texs, cols, max_mips, offsets)
         nbytes = L.gsrast_hexplane_scratch_bytes(ps.n, ps.arr, Cn, N)
         if nbytes == 0:
-            L.gsrast_hexplane_forward(0, D, Cn, F, ps.n, ps.arr, None, None, None, None, None)     # sets the error text
-            raise _lib._err(-1, "gsrast_hexplane_scratch_bytes")
+            raise _lib._err(-1, "gsrast_hexplane_scratch_bytes")       # (the call left its reason in gsrast_last_error)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        out = torch.empty((N, F), dtype=torch.float32, device=dev)
+        # the kernel writes the planes' blocks only: columns no block covers are zero-filled here, and only when there are any
+        # (the field's blocks tile its row, so that path stays one launch)
+        covered = sorted(set(int(o) for o in offsets))
+        tiled = covered == list(range(0, F, Cn))
+        out = (torch.empty if tiled else torch.zeros)((N, F), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             rc = L.gsrast_hexplane_forward(N, D, Cn, F, ps.n, ps.arr, p.data_ptr() if N else None, lv.data_ptr() if N else None,
                                            out.data_ptr() if N else None, scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
@@ -109,7 +112,8 @@ def texture_planes(pts: torch.Tensor, levels: torch.Tensor, grids: Sequence[torc
                    max_mips: Sequence[int], offsets: Sequence[int], feature_width: int) -> torch.Tensor:
     """General entry: plane i samples grids[i] ([1,C,H,W]) at (pts[:, cols[i][0]], pts[:, cols[i][1]]) with the bias
     min(levels[:, cols[i]]) and adds its C channels at features[:, offsets[i]:offsets[i]+C].  Planes sharing an offset must
-    be adjacent."""
+    be adjacent and two blocks are equal or disjoint (the library refuses anything else); columns of the feature_width
+    that no plane covers are 0."""
     return _HexplaneFn.apply(pts, levels, tuple(tuple(c) for c in cols), tuple(max_mips), tuple(offsets), int(feature_width), *grids)
 
 
