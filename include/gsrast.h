@@ -911,6 +911,44 @@ int gsrast_temporal_integral(int P, int sigmoid_center, float start, float end, 
                              const float* center, float* integral, unsigned char* dead, float* inv /* NULL ok */, int* stats /* device [2] */,
                              void* stream);
 
+/* ---- bilateral-grid colour correction between the render and the loss (gsplat's lib_bilagrid `slice`; 3DGS "exposure" = 1 x 1 x 1) ----
+ * grid [12][L][GH][GW] (one camera's grid, PyTorch's [C, D, H, W] order), image / out / dL_dout / dL_dimage [3][H][W]; all contiguous
+ * fp32 device pointers.  image is the crop at (x0, y0) of a full_W x full_H frame (a whole frame: x0 = y0 = 0, full = W x H).
+ * Per pixel (px, py):   x = (x0 + px + 0.5) / full_W,   y = (y0 + py + 0.5) / full_H,   gray = 0.299 r + 0.587 g + 0.114 b,
+ *   u = x (GW - 1),  v = y (GH - 1),  t = clamp(gray, 0, 1) (L - 1);   A[12] = the trilinear interpolation of the 12 channels at (u, v, t)
+ *   -- torch.nn.functional.grid_sample(grid[None], 2 (x, y, gray) - 1, "bilinear", "border", align_corners=True); an axis of one vertex
+ *   has the single index 0 --;   out_c = A[4c] r + A[4c+1] g + A[4c+2] b + A[4c+3]   (A read as a row-major 3 x 4 matrix).
+ * gsrast_bilagrid_forward writes out.  One launch, no scratch.
+ * gsrast_bilagrid_backward recomputes the weights and A from grid and image (the forward saves nothing) and writes, where their pointer is
+ *   not NULL (each OVERWRITTEN; both NULL is refused):
+ *   dL_dimage: through the matrix product and through gray (the t coordinate) as torch's autograd gives it: slope 0 where gray is
+ *              outside (0, 1) or L = 1; x and y carry no gradient;
+ *   dL_dgrid:  through the trilinear weights, by a gather: one workgroup per vertex column (gx, gy) and slab of its pixel rectangle, one
+ *              writer per element, NO floating-point atomics; with more than one slab a second launch sums the slabs' partials (scratch,
+ *              >= gsrast_bilagrid_scratch_bytes; may be NULL when dL_dgrid is) in slab order: bit-identical from run to run for a given
+ *              slab count.  A vertex no pixel reaches gets exactly 0.
+ *   splits: 0 = the library's choice (a function of the descriptor alone); > 0 forces that many slabs per vertex column.
+ * A NaN / Inf pixel stays in its own output pixel and in the at most 8 x 12 grid-gradient entries it touches.
+ * gsrast_bilagrid_tv: grids [N][12][L][GH][GW];  tv = sum over the axes GW, GH, L of the mean, over every element pair along that axis
+ *   (all n, channels and positions), of the squared forward difference; an axis of one vertex contributes 0.  loss_out (device float;
+ *   NULL: not wanted): one launch, fixed-order fp64 partial sums.  dL_dgrids (NULL: not wanted; OVERWRITTEN) = *upstream x d tv / d grids
+ *   (upstream: device pointer to one float, NULL = 1): one launch, one writer per element.
+ * Refused (GSRAST_E_ARG, gsrast_last_error) before any device call: a NULL descriptor or required pointer, GW / GH outside [1, 64], L
+ * outside [1, 16], W or H < 1, a frame side outside [1, 32768], a window outside the frame, splits outside [0, 1024], N outside
+ * [1, 2048], both outputs NULL.  fp32 only.  The launches have no entry in the profile table. */
+typedef struct {
+    int GW, GH, L;              /* the grid */
+    int W, H;                   /* the image (crop) */
+    int x0, y0, full_W, full_H; /* where the crop lies in its frame */
+    int splits;                 /* backward: slabs per vertex column; 0 = the library's choice */
+} gsrast_bilagrid;
+size_t gsrast_bilagrid_scratch_bytes(const gsrast_bilagrid* d);      /* 0: the descriptor is refused (gsrast_last_error) */
+int gsrast_bilagrid_forward(const gsrast_bilagrid* d, const float* grid, const float* image, float* out, void* stream);
+int gsrast_bilagrid_backward(const gsrast_bilagrid* d, const float* grid, const float* image, const float* dL_dout,
+                             float* dL_dimage /* NULL ok */, float* dL_dgrid /* NULL ok */, char* scratch, void* stream);
+int gsrast_bilagrid_tv(int N, int GW, int GH, int L, const float* grids, float* loss_out /* NULL ok */, const float* upstream /* NULL = 1 */,
+                       float* dL_dgrids /* NULL ok */, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

@@ -10,6 +10,7 @@
 #include "gsrast_mlp.h"
 #include "gsrast_mlp_bf16.h"
 #include "gsrast_temporal.h"
+#include "gsrast_bilagrid.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include <algorithm>
@@ -424,6 +425,107 @@ int gsrast_temporal_integral(int P, int sigmoid_center, float start, float end, 
     if (inv) {      // (a launch of its own: the maximum must exist before the division)
         temporal_inv_kernel<<<temporal_grid(P), TP_RUN, 0, s>>>(P, integral, dead, stats, inv);
         GS_LAUNCHED("temporal_inv");
+    }
+    return GSRAST_OK;
+}
+
+// ---- bilateral-grid colour correction (gsrast_bilagrid.h) -----------------------------------------------------------
+// Not in the profile kernel-name table: tools/bilagrid_overhead.py times these calls with device events of its own.
+// scratch: `splits` slabs of 12 L GH GW floats when a vertex column has more than one slab, nothing otherwise
+namespace {
+int bilagrid_check(const char* who, const gsrast_bilagrid* d)
+{
+    if (!d) return refuse(who, "NULL descriptor");
+    if (d->GW < 1 || d->GW > BG_MAX_G || d->GH < 1 || d->GH > BG_MAX_G) return refuse(who, "GW and GH must be in [1, 64]");
+    if (d->L < 1 || d->L > BG_MAX_L) return refuse(who, "L must be in [1, 16]");
+    if (d->W < 1 || d->H < 1) return refuse(who, "W and H must be >= 1");
+    if (d->full_W < 1 || d->full_H < 1 || d->full_W > BG_MAX_FRAME || d->full_H > BG_MAX_FRAME) return refuse(who, "full_W and full_H must be in [1, 32768]");
+    if (d->x0 < 0 || d->y0 < 0 || (long long)d->x0 + d->W > d->full_W || (long long)d->y0 + d->H > d->full_H) return refuse(who, "the window must lie inside the frame");
+    if (d->splits < 0 || d->splits > BG_MAX_SPLITS) return refuse(who, "splits must be in [0, 1024] (0: the library's choice)");
+    return GSRAST_OK;
+}
+// slabs per vertex column: as asked, or enough for about 2048 workgroups while a slab keeps at least four pixel rows (one per wave).
+// A function of the descriptor alone, never of the device.
+int bilagrid_splits(const gsrast_bilagrid* d)
+{
+    if (d->splits > 0) return d->splits;
+    const int want = (2048 + d->GW * d->GH - 1) / (d->GW * d->GH);
+    const int rows = d->GH == 1 ? d->H : std::min(d->H, 2 * ((d->full_H + d->GH - 2) / (d->GH - 1)) + 4);      // of a vertex's rectangle, at most
+    return std::max(1, std::min(want, rows / 4));
+}
+BgArgs bilagrid_args(const gsrast_bilagrid* d) { return BgArgs{ d->GW, d->GH, d->L, d->W, d->H, d->x0, d->y0, d->full_W, d->full_H }; }
+size_t bilagrid_floats(const gsrast_bilagrid* d) { return (size_t)12 * d->L * d->GH * d->GW; }
+#define BILAGRID_PIXEL_GRID(d) dim3((unsigned)(((d)->W + 63) / 64), (unsigned)(((d)->H + 3) / 4))      /* a wave per 64 pixels of a row, four rows per workgroup */
+}  // namespace
+
+size_t gsrast_bilagrid_scratch_bytes(const gsrast_bilagrid* d)
+{
+    if (bilagrid_check("bilagrid_scratch_bytes", d) != GSRAST_OK) return 0;
+    const int splits = bilagrid_splits(d);
+    return (splits > 1 ? align256((size_t)splits * bilagrid_floats(d) * 4) : 0) + 256;
+}
+
+int gsrast_bilagrid_forward(const gsrast_bilagrid* d, const float* grid, const float* image, float* out, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = bilagrid_check("bilagrid_forward", d)) return rc;
+    if (!grid || !image || !out) return fail(GSRAST_E_ARG, "bilagrid_forward: NULL required pointer");
+    bilagrid_fwd_kernel<<<BILAGRID_PIXEL_GRID(d), BG_THREADS, bg_pixel_lds(d->L), s>>>(bilagrid_args(d), grid, image, out);
+    GS_LAUNCHED("bilagrid_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_bilagrid_backward(const gsrast_bilagrid* d, const float* grid, const float* image, const float* dL_dout, float* dL_dimage,
+                             float* dL_dgrid, char* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = bilagrid_check("bilagrid_backward", d)) return rc;
+    if (!grid || !image || !dL_dout) return fail(GSRAST_E_ARG, "bilagrid_backward: NULL required pointer");
+    if (!dL_dimage && !dL_dgrid) return fail(GSRAST_E_ARG, "bilagrid_backward: dL_dimage and dL_dgrid are both NULL");
+    const int splits = bilagrid_splits(d);
+    if (dL_dgrid && splits > 1 && !scratch) return fail(GSRAST_E_ARG, "bilagrid_backward: NULL scratch");
+    const BgArgs a = bilagrid_args(d);
+    if (dL_dimage) {
+        bilagrid_bwd_pixel_kernel<<<BILAGRID_PIXEL_GRID(d), BG_THREADS, bg_pixel_lds(d->L), s>>>(a, grid, image, dL_dout, dL_dimage);
+        GS_LAUNCHED("bilagrid_bwd_pixel");
+    }
+    if (dL_dgrid) {
+        float* const dst = splits > 1 ? reinterpret_cast<float*>(scratch) : dL_dgrid;
+        const dim3 g((unsigned)(d->GW * d->GH), (unsigned)splits);
+        pick_int<1, 2, 4, 8, 16>(d->L <= 1 ? 1 : d->L <= 2 ? 2 : d->L <= 4 ? 4 : d->L <= 8 ? 8 : 16, [&](auto lt) {
+            bilagrid_bwd_grid_kernel<decltype(lt)::value><<<g, BG_THREADS, 0, s>>>(a, splits, image, dL_dout, dst);
+        });
+        GS_LAUNCHED("bilagrid_bwd_grid");
+        if (splits > 1) {
+            const unsigned n = (unsigned)bilagrid_floats(d);
+            bilagrid_reduce_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, splits, dst, dL_dgrid);
+            GS_LAUNCHED("bilagrid_reduce");
+        }
+    }
+    return GSRAST_OK;
+}
+
+int gsrast_bilagrid_tv(int N, int GW, int GH, int L, const float* grids, float* loss_out, const float* upstream, float* dL_dgrids, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (N < 1 || N > BG_TV_MAX_N) return fail(GSRAST_E_ARG, "bilagrid_tv: N must be in [1, 2048]");
+    if (GW < 1 || GW > BG_MAX_G || GH < 1 || GH > BG_MAX_G) return fail(GSRAST_E_ARG, "bilagrid_tv: GW and GH must be in [1, 64]");
+    if (L < 1 || L > BG_MAX_L) return fail(GSRAST_E_ARG, "bilagrid_tv: L must be in [1, 16]");
+    if (!grids) return fail(GSRAST_E_ARG, "bilagrid_tv: NULL required pointer");
+    if (!loss_out && !dL_dgrids) return fail(GSRAST_E_ARG, "bilagrid_tv: loss_out and dL_dgrids are both NULL");
+    const unsigned n = (unsigned)N * 12u * (unsigned)(L * GH * GW);      // (< 2^31: N <= 2048, 12 L GH GW <= 786432)
+    const double rows = (double)N * 12.0;
+    const auto inv = [](double pairs) { return pairs > 0.0 ? 1.0 / pairs : 0.0; };
+    const BgTvCounts cnt{ inv(rows * L * GH * (GW - 1)), inv(rows * L * (GH - 1) * GW), inv(rows * (L - 1) * GH * GW) };
+    if (loss_out) {
+        const int rows_step = BG_TV_THREADS / GW;
+        const BgTvStep step{ BG_TV_THREADS % GW, rows_step % GH, (rows_step / GH) % L };
+        bilagrid_tv_kernel<<<1, BG_TV_THREADS, 0, s>>>(n, GW, GH, L, step, cnt, grids, loss_out);
+        GS_LAUNCHED("bilagrid_tv");
+    }
+    if (dL_dgrids) {
+        bilagrid_tv_grad_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, GW, GH, L, cnt, grids, upstream, dL_dgrids);
+        GS_LAUNCHED("bilagrid_tv_grad");
     }
     return GSRAST_OK;
 }

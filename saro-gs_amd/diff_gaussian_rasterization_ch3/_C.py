@@ -48,6 +48,7 @@ EXPORTS = (
     "gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward",
     "gsrast_mlp3_scratch_bytes_p", "gsrast_mlp3_forward_p", "gsrast_mlp3_backward_p",
     "gsrast_temporal_gate_forward", "gsrast_temporal_gate_backward", "gsrast_temporal_integral",
+    "gsrast_bilagrid_scratch_bytes", "gsrast_bilagrid_forward", "gsrast_bilagrid_backward", "gsrast_bilagrid_tv",
 )
 
 # include/gsrast.h: the flags word of a call record
@@ -171,6 +172,11 @@ class Mlp3Struct(C.Structure):
     """gsrast_mlp3 (include/gsrast.h): the dims, the sigmoid flag and the pointers of one fused 3-layer head."""
     _fields_ = ([(k, C.c_int) for k in ("n", "d_x", "d_tail", "h1", "h2", "d_out", "sigmoid")]
                 + [(k, C.c_void_p) for k in ("x", "x_tail", "w1", "b1", "w2", "b2", "w3", "b3", "y", "dy", "dx", "dw1", "db1", "dw2", "db2", "dw3", "db3")])
+
+
+class BilagridStruct(C.Structure):
+    """gsrast_bilagrid (include/gsrast.h): the grid, the image (crop), where it lies in its frame, and the backward's slab count."""
+    _fields_ = [(k, C.c_int) for k in ("GW", "GH", "L", "W", "H", "x0", "y0", "full_W", "full_H", "splits")]
 
 
 class PlaneStruct(C.Structure):
@@ -305,6 +311,12 @@ def lib() -> C.CDLL:
     L.gsrast_temporal_gate_forward.argtypes = [ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_temporal_gate_backward.argtypes = [ci, ci, cf, cf, vp, vp, vp, vp, vp, vp, vp]
     L.gsrast_temporal_integral.argtypes = [ci, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_bilagrid_scratch_bytes.restype = C.c_size_t
+    L.gsrast_bilagrid_scratch_bytes.argtypes = [C.POINTER(BilagridStruct)]
+    L.gsrast_bilagrid_forward.restype = L.gsrast_bilagrid_backward.restype = L.gsrast_bilagrid_tv.restype = ci
+    L.gsrast_bilagrid_forward.argtypes = [C.POINTER(BilagridStruct), vp, vp, vp, vp]
+    L.gsrast_bilagrid_backward.argtypes = [C.POINTER(BilagridStruct), vp, vp, vp, vp, vp, vp, vp]
+    L.gsrast_bilagrid_tv.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
     L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
     L.gsrast_hexplane_forward.restype = ci
