@@ -770,6 +770,16 @@ int gsrast_densify_plan(int P, int N /* 1..4 */, const float* accum, const float
 int gsrast_densify_apply(int P, int N, const char* scratch, const unsigned* counts_host /* [5], as read back */, int n_groups /* <= 16 */,
                          const gsrast_densify_group* groups /* host array */, const float* rotation /* [P][4] raw */, const float* scaling,
                          const float* noise /* [N * n_split_all][3]; NULL allowed when n_split == 0 */, void* stream);
+/* The transpose of a prune-only apply: dst [P][width] <- src [n_kept][width] on the rows the plan kept, +0.0f on every other row.
+ * Same P, scratch and read-back counts as the gsrast_densify_plan that made them.  With gsrast_densify_apply over COPY groups it is the
+ * differentiable row selection of fused_densify.RowSelection: each call is the other's vector-Jacobian product.  One launch for up to
+ * 16 groups, one writer per element, no atomics, nothing read from a row the plan dropped; P = 0 launches nothing, n_kept = 0 zero-fills
+ * every dst.  Refused before any device call (gsrast_last_error): P < 0; for P > 0 a NULL scratch, counts_host or groups; n_groups outside
+ * [0, 16]; a width outside [1, 64]; a role other than GSRAST_DENSIFY_COPY; any moment pointer; a NULL src while n_kept > 0; a NULL dst;
+ * counts that are not a prune-only plan's (n_clone, n_split or n_split_all != 0, counts[4] != counts[0]); n_kept > P.  It has no
+ * profile name of its own. */
+int gsrast_densify_scatter(int P, const char* scratch, const unsigned* counts_host /* [5] */, int n_groups /* <= 16 */,
+                           const gsrast_densify_group* groups /* host array */, void* stream);
 /* The per-iteration statistics of train.py:282-292 + add_densification_stats_grad (scene/saro_gaussian.py:745-750), one launch:
  * where visibility_count[i] > 0:  accum[i] += grad_is_mean ? grad[i] : grad[i] / visibility_count[i];  denom[i] += 1;
  * max_radii[i] = max(max_radii[i], radii[i]) (both NULL: skipped).  Other rows are untouched.  All arrays fp32 [P]. */

@@ -198,6 +198,54 @@ densify_apply_kernel(DnApplyArgs a)
     }
 }
 
+// The transpose of a prune-only apply (gsrast_densify_scatter): the same workgroup-to-run mapping and the same LDS scan, but the walk is over
+// the DESTINATION's run x width floats: a kept row loads its floats from row s_keep of the compact source (survivors keep index order, so a
+// run reads one contiguous span), every other element stores +0.0f.  One writer per element, nothing read from an unselected row.
+constexpr uint32_t DN_NO_ROW = 0xFFFFFFFFu;
+constexpr int DN_SCATTER_UNROLL = 4;
+__global__ void __launch_bounds__(DN_RUN)
+densify_scatter_kernel(DnApplyArgs a)
+{
+    __shared__ DnCount wsum[4];
+    __shared__ uint32_t s_keep[DN_RUN];                                  // the kept row, or DN_NO_ROW
+    const uint32_t blk = blockIdx.x;
+    const size_t first = (size_t)blk * DN_RUN;
+    const int run = (int)((size_t)a.P - first < (size_t)DN_RUN ? (size_t)a.P - first : (size_t)DN_RUN);
+    {
+        const unsigned char c = (int)threadIdx.x < run ? a.cls[first + threadIdx.x] : (unsigned char)0;
+        DnCount tot;
+        const DnCount ex = dn_block_excl_scan(dn_of(c), &tot, wsum);
+        const uint32_t row = a.sums[blk] + ex.kept;
+        s_keep[threadIdx.x] = ((c & DN_KEEP) && row < a.n_kept) ? row : DN_NO_ROW;      // (row < n_kept: always, for the scratch of this plan)
+    }
+    __syncthreads();
+    for (int gi = 0; gi < a.n_groups; gi++) {
+        const DnGroup G = a.grp[gi];
+        const int w = G.width, total = run * w, qstep = DN_RUN / w, rstep = DN_RUN % w;
+        int r = (int)threadIdx.x / w, c = (int)threadIdx.x % w;
+        // four elements per turn, the loads in front of the stores: src and dst may alias as far as the compiler knows, so a load behind a
+        // store waits for it, and one load in flight per wave leaves the kernel bound by latency
+        for (int e = threadIdx.x; e < total; e += DN_SCATTER_UNROLL * DN_RUN) {
+            float v[DN_SCATTER_UNROLL];
+            size_t o[DN_SCATTER_UNROLL];
+#pragma unroll
+            for (int u = 0; u < DN_SCATTER_UNROLL; u++) {
+                v[u] = 0.0f;
+                o[u] = (first + r) * (size_t)w + c;
+                if (e + u * DN_RUN < total) {                            // (behind the run's end r may pass DN_RUN: nothing is read there)
+                    const uint32_t row = s_keep[r];
+                    if (row != DN_NO_ROW) v[u] = G.src[(size_t)row * w + c];
+                }
+                r += qstep; c += rstep;
+                if (c >= w) { c -= w; r++; }
+            }
+#pragma unroll
+            for (int u = 0; u < DN_SCATTER_UNROLL; u++)
+                if (e + u * DN_RUN < total) G.dst[o[u]] = v[u];
+        }
+    }
+}
+
 // train.py:282-292 + add_densification_stats_grad (scene/saro_gaussian.py:745-750), where visibility_count[i] > 0:
 //   accum += grad_is_mean ? grad[i] : grad[i] / visibility_count[i];  denom += 1;  max_radii = max(max_radii, radii)
 __global__ void __launch_bounds__(256)

@@ -206,6 +206,37 @@ int gsrast_densify_apply(int P, int N, const char* scratch, const unsigned* coun
     return GSRAST_OK;
 }
 
+int gsrast_densify_scatter(int P, const char* scratch, const unsigned* counts_host, int n_groups, const gsrast_densify_group* groups, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "densify_scatter: negative P");
+    if (n_groups < 0 || n_groups > DN_MAX_GROUPS) return fail(GSRAST_E_ARG, "densify_scatter: at most 16 groups");
+    if (P > 0 && (!scratch || !counts_host || !groups)) return fail(GSRAST_E_ARG, "densify_scatter: NULL scratch / counts / groups");
+    if (P == 0) return GSRAST_OK;
+    const unsigned n_kept = counts_host[0];
+    if (counts_host[1] || counts_host[2] || counts_host[3] || counts_host[4] != n_kept)
+        return fail(GSRAST_E_ARG, "densify_scatter: counts are not those of a prune-only plan (clones or split copies have no transpose)");
+    if (n_kept > (unsigned)P) return fail(GSRAST_E_ARG, "densify_scatter: n_kept exceeds P");
+    DnApplyArgs a{};
+    for (int k = 0; k < n_groups; k++) {
+        const gsrast_densify_group& g = groups[k];
+        if (g.width < 1 || g.width > DN_MAX_WIDTH) return fail(GSRAST_E_ARG, "densify_scatter: group width must be in [1, 64]");
+        if (g.role != GSRAST_DENSIFY_COPY) return fail(GSRAST_E_ARG, "densify_scatter: only the COPY role has a transpose");
+        if (g.src_m || g.src_v || g.dst_m || g.dst_v) return fail(GSRAST_E_ARG, "densify_scatter: moments are not scattered (src_m / src_v / dst_m / dst_v must be NULL)");
+        if (n_kept > 0 && !g.src) return fail(GSRAST_E_ARG, "densify_scatter: NULL src while n_kept > 0");
+        if (!g.dst) return fail(GSRAST_E_ARG, "densify_scatter: NULL dst");
+        a.grp[k] = DnGroup{ g.src, nullptr, nullptr, g.dst, nullptr, nullptr, g.width, g.role };
+    }
+    if (n_groups == 0) return GSRAST_OK;
+    const DensifyLayout L = densify_layout((size_t)P);
+    a.n_groups = n_groups; a.P = P; a.N = 1;
+    a.n_kept = n_kept; a.p_new = n_kept; a.nb = L.nb;
+    a.cls = at<unsigned char>(scratch, L.cls); a.sums = at<uint32_t>(scratch, L.sums);
+    densify_scatter_kernel<<<L.nb, DN_RUN, 0, s>>>(a);      // (no timer of its own: the profile table is the plan's and the apply's)
+    GS_LAUNCHED("densify_scatter");
+    return GSRAST_OK;
+}
+
 int gsrast_densify_stats_update(int P, const float* grad, const float* visibility_count, const float* radii,
                                 float* accum, float* denom, float* max_radii, int grad_is_mean, void* stream)
 {

@@ -36,7 +36,7 @@ EXPORTS = (
     "gsrast_profile_collect", "gsrast_profile_read", "gsrast_profile_reset", "gsrast_last_error",
     "gsrast_abi_version", "gsrast_loss_scratch_bytes", "gsrast_loss_forward", "gsrast_loss_backward",
     "gsrast_sh_grad_combine", "gsrast_sh_grad_combine_rows", "gsrast_sh_grad_combine_union", "gsrast_rows_pack", "gsrast_rows_unpack", "gsrast_grad_rows_pack", "gsrast_grad_rows_clear", "gsrast_grad_rows_add", "gsrast_touched_rows", "gsrast_activate_forward", "gsrast_activate_backward", "gsrast_adam_step", "gsrast_adam_step_visible",
-    "gsrast_densify_scratch_bytes", "gsrast_densify_plan", "gsrast_densify_apply", "gsrast_densify_stats_update",
+    "gsrast_densify_scratch_bytes", "gsrast_densify_plan", "gsrast_densify_apply", "gsrast_densify_scatter", "gsrast_densify_stats_update",
     "gsrast_knn_scratch_bytes", "gsrast_knn3_mean_dist2",
     "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
     "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event", "gsrast_debug_forward_plan", "gsrast_debug_backward_plan",
@@ -288,6 +288,8 @@ def lib() -> C.CDLL:
     L.gsrast_densify_plan.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp]
     L.gsrast_densify_apply.restype = ci
     L.gsrast_densify_apply.argtypes = [ci, ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp, vp, vp, vp]
+    L.gsrast_densify_scatter.restype = ci
+    L.gsrast_densify_scatter.argtypes = [ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp]
     L.gsrast_densify_stats_update.restype = ci
     L.gsrast_densify_stats_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp]
     L.gsrast_mcmc_scratch_bytes.restype = C.c_size_t

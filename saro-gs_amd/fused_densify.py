@@ -16,6 +16,10 @@ is the reference's layout row for row:
   [ originals !split && !pruned | clones | split copy 0 | copy 1 | ... ]      (every part in index order)
 and is bit-identical from run to run and from rank to rank (no atomics), so replicated models stay replicated.
 
+Not in the reference either: `select_rows` / `RowSelection` keep a prune-only plan beyond its apply and make the row move differentiable --
+`gather` ([P, ...] -> [n, ...], gsrast_densify_apply) and `scatter` ([n, ...] -> [P, ...] with zeros elsewhere, gsrast_densify_scatter), each the
+other's backward -- so that a training step runs the deformation heads, and optionally the rasterizer, on the rows alive at the view's time.
+
 The second policy, 3DGS-MCMC as gsplat's MCMCStrategy runs it (include/gsrast.h: gsrast_mcmc_*, csrc/gsrast_mcmc.h), sits beside it:
   gsplat/strategy/ops.py relocate + gsplat/relocation.py compute_relocation                                        -> mcmc_relocate
   gsplat/strategy/ops.py sample_add                                                                                -> mcmc_grow
@@ -38,6 +42,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from diff_gaussian_rasterization_ch3 import _C
 
@@ -165,6 +170,22 @@ def _check_param(p: torch.Tensor, name: str, P: int) -> None:
         raise RuntimeError(f"fused_densify: {name} has {tuple(p.shape)}, expected {P} rows")
 
 
+def _plan(P: int, dev: torch.device, N: int, plan_args: dict) -> Tuple[torch.Tensor, List[int]]:
+    """gsrast_densify_plan and the read-back of its five counts (the one synchronisation).  Returns (scratch, the counts as host words):
+    together they are the plan, which any number of gsrast_densify_apply / gsrast_densify_scatter calls with the same P and N may use."""
+    L = _C.lib()
+    scratch = torch.empty(int(L.gsrast_densify_scratch_bytes(P)), dtype=torch.uint8, device=dev)
+    counts_dev = torch.empty(5, dtype=torch.int32, device=dev)
+    with _C._on_device(dev):
+        rc = L.gsrast_densify_plan(P, N, plan_args.get("accum"), plan_args.get("denom"), plan_args.get("grad_scale"), plan_args.get("scaling"),
+                                   plan_args.get("opacity"), plan_args.get("prune_src"), float(plan_args["thr"]), float(plan_args.get("tau", 0.0)),
+                                   float(plan_args.get("min_opacity", 0.0)), scratch.data_ptr(), counts_dev.data_ptr(), _C._stream_of(dev))
+        if rc != 0:
+            raise _C._err(rc, "gsrast_densify_plan")
+        host = [int(v) & 0xFFFFFFFF for v in counts_dev.cpu().tolist()]
+    return scratch, host
+
+
 def _run(P: int, dev: torch.device, N: int, plan_args: dict, moved: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], int]],
          rotation: Optional[torch.Tensor], scaling: Optional[torch.Tensor], generator, noise: Optional[torch.Tensor]):
     """plan -> read the counts back (the one synchronisation) -> noise -> allocate -> apply.  `moved`: (src, exp_avg, exp_avg_sq, role) per
@@ -172,16 +193,9 @@ def _run(P: int, dev: torch.device, N: int, plan_args: dict, moved: Sequence[Tup
     if len(moved) > MAX_GROUPS:
         raise RuntimeError(f"fused_densify: {len(moved)} arrays to move, at most {MAX_GROUPS} per launch")
     L = _C.lib()
-    scratch = torch.empty(int(L.gsrast_densify_scratch_bytes(P)), dtype=torch.uint8, device=dev)
-    counts_dev = torch.empty(5, dtype=torch.int32, device=dev)
+    scratch, host = _plan(P, dev, N, plan_args)
     with _C._on_device(dev):
         stream = _C._stream_of(dev)
-        rc = L.gsrast_densify_plan(P, N, plan_args.get("accum"), plan_args.get("denom"), plan_args.get("grad_scale"), plan_args.get("scaling"),
-                                   plan_args.get("opacity"), plan_args.get("prune_src"), float(plan_args["thr"]), float(plan_args.get("tau", 0.0)),
-                                   float(plan_args.get("min_opacity", 0.0)), scratch.data_ptr(), counts_dev.data_ptr(), stream)
-        if rc != 0:
-            raise _C._err(rc, "gsrast_densify_plan")
-        host = [int(v) & 0xFFFFFFFF for v in counts_dev.cpu().tolist()]
         counts = dict(zip(COUNT_NAMES, host))
         n_all, P_new = counts["n_split_all"], counts["P"]
         if noise is None:
@@ -321,6 +335,174 @@ def prune(opt, mask: torch.Tensor, stats: Optional[DensifyStats] = None, extras:
         contrib.sums, contrib.weight_max = rest[:2]
         rest = rest[2:]
     return counts, new, rest
+
+
+# ---- differentiable row selection -------------------------------------------------------------------------------------------------
+_MOVABLE = (torch.float32, torch.int32)
+
+
+def _check_mask(mask, P: Optional[int], name: str) -> int:
+    """The refusals of a row mask that need no device: a bool / uint8 [P] or [P, 1] tensor (P: the expected length, None: any).  Returns P."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"fused_densify: {name} must be a bool or uint8 tensor (got {getattr(mask, 'dtype', type(mask).__name__)})")
+    if mask.dim() not in (1, 2) or (mask.dim() == 2 and int(mask.shape[1]) != 1):
+        raise RuntimeError(f"fused_densify: {name} must be [P] or [P, 1] (got {tuple(mask.shape)})")
+    if P is not None and int(mask.shape[0]) != P:
+        raise RuntimeError(f"fused_densify: {name} has {int(mask.shape[0])} entries, expected {P} rows")
+    return int(mask.shape[0])
+
+
+def _check_movable(tensors: Sequence[torch.Tensor], rows: int, dev: torch.device, what: str) -> None:
+    """What one gsrast_densify_apply / gsrast_densify_scatter launch can move, refused before it: at most 16 contiguous float32 / int32 tensors of
+    `rows` rows and 1 ... 64 four-byte elements per row, on `dev`."""
+    if len(tensors) > MAX_GROUPS:
+        raise RuntimeError(f"fused_densify: {len(tensors)} tensors to {what}, at most {MAX_GROUPS} per call")
+    for k, x in enumerate(tensors):
+        if not isinstance(x, torch.Tensor) or x.dtype not in _MOVABLE:
+            raise RuntimeError(f"fused_densify: {what}: tensor {k} must be float32 or int32 (got {getattr(x, 'dtype', type(x).__name__)})")
+        if x.dim() < 1 or int(x.shape[0]) != rows:
+            raise RuntimeError(f"fused_densify: {what}: tensor {k} has {tuple(x.shape)}, expected {rows} rows")
+        if not 1 <= int(math.prod(x.shape[1:])) <= 64:
+            raise RuntimeError(f"fused_densify: {what}: tensor {k} has {tuple(x.shape)}: 1 ... 64 four-byte elements per row")
+        if not x.is_contiguous():
+            raise RuntimeError(f"fused_densify: {what}: tensor {k} must be contiguous")
+        if x.device != dev:
+            raise RuntimeError(f"fused_densify: {what}: tensor {k} must live on {dev} (got {x.device}); there is no CPU fallback")
+
+
+class RowSelection:
+    """A prune-only plan that outlives its apply: which `count` of `P` rows are kept, as the scratch and the host counts of one
+    gsrast_densify_plan.  Immutable; `gather` and `scatter` may be called any number of times, in any order, each ONE launch for all its tensors:
+        a_n, b_n = sel.gather(a, b)      # [P, ...] -> [count, ...], the kept rows in index order (x[mask]);            backward = scatter
+        r_P, = sel.scatter(r_n)          # [count, ...] -> [P, ...], +0.0 on every other row (zeros.index_copy(0, rows)); backward = gather
+    At most 16 tensors per call, each contiguous with 1 ... 64 four-byte elements per row on the selection's device.  float32 tensors are
+    differentiable (once: a double backward raises); int32 tensors (radii, row numbers) are moved as bits and are non-differentiable; anything
+    else raises before a launch.  The backward launches only for the tensors that need a gradient and received one.  Both work under
+    torch.no_grad(), and with count = 0 or P = 0.  With a `GradArena` installed, gathering a leaf that requires a gradient raises (a render of
+    the gathered rows does not fit the arena: the leaf's gradient would miss the exchanged bucket), as `features=` does there.
+    Made by `select_rows` or `fused_temporal.temporal_rows`."""
+    __slots__ = ("P", "count", "device", "_scratch", "_counts", "_rows")
+
+    def __init__(self, P: int, device: torch.device, scratch: Optional[torch.Tensor], counts: Sequence[int]):
+        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731
+        set_("P", int(P)); set_("count", int(counts[0])); set_("device", torch.device(device))
+        set_("_scratch", scratch); set_("_counts", (C.c_uint * 5)(*counts)); set_("_rows", None)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("RowSelection is immutable")
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """int32 [count], ascending: the kept row numbers (an arange moved through the plan, built on first use)."""
+        if self._rows is None:
+            with torch.no_grad():
+                object.__setattr__(self, "_rows", _move_rows(self, [torch.arange(self.P, dtype=torch.int32, device=self.device)], True)[0])
+        return self._rows
+
+    @property
+    def mask(self) -> torch.Tensor:
+        """bool [P]: True on the kept rows."""
+        m = torch.zeros(self.P, dtype=torch.bool, device=self.device)
+        m[self.rows.long()] = True
+        return m
+
+    def gather(self, *tensors: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        if _C._grad_arena is not None and torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.is_leaf and x.requires_grad for x in tensors):
+            raise RuntimeError("RowSelection.gather of a leaf that requires a gradient is not supported with a GradArena installed (multi-GPU / "
+                               "view_parallel training): a render of the gathered rows does not fit the arena, so the leaf's gradient would arrive "
+                               "outside the bucket the exchange reduces; gather only the heads' inputs there, or uninstall it with _C.set_grad_arena(None)")
+        _check_movable(tensors, self.P, self.device, "gather")
+        return _GatherRows.apply(self, *tensors) if tensors else ()
+
+    def scatter(self, *tensors: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        _check_movable(tensors, self.count, self.device, "scatter")
+        return _ScatterRows.apply(self, *tensors) if tensors else ()
+
+
+def _move_rows(sel: RowSelection, tensors: Sequence[torch.Tensor], compact: bool) -> List[torch.Tensor]:
+    """One launch over `sel`'s plan for all of `tensors` (checked by the caller): gsrast_densify_apply ([P, ...] -> [count, ...]) when `compact`,
+    else gsrast_densify_scatter ([count, ...] -> [P, ...]).  Nothing to write: no launch."""
+    P, n, dev = sel.P, sel.count, sel.device
+    rows_out = n if compact else P
+    out = [torch.empty((rows_out,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in tensors]
+    if rows_out == 0 or not tensors:
+        return out
+    arr = (_C.DensifyGroupStruct * len(tensors))()
+    for a, src, dst in zip(arr, tensors, out):
+        a.src, a.dst, a.width, a.role = _C._ptr(src), _C._ptr(dst), _rows_width(src), _C.DENSIFY_COPY
+    L = _C.lib()
+    with _C._on_device(dev):
+        if compact:
+            rc = L.gsrast_densify_apply(P, 1, sel._scratch.data_ptr(), sel._counts, len(tensors), arr, None, None, None, _C._stream_of(dev))
+        else:
+            rc = L.gsrast_densify_scatter(P, sel._scratch.data_ptr(), sel._counts, len(tensors), arr, _C._stream_of(dev))
+    if rc != 0:
+        raise _C._err(rc, "gsrast_densify_apply" if compact else "gsrast_densify_scatter")
+    return out
+
+
+def _move_rows_backward(ctx, grads, compact: bool):
+    """The transposed move of the upstream gradients that exist and are needed, in one launch; None for the others."""
+    sel = ctx.sel
+    todo = [k for k, g in enumerate(grads) if g is not None and ctx.needs_input_grad[k + 1]]
+    gs = []
+    for k in todo:
+        g = grads[k]
+        if g.device != sel.device or g.dtype != torch.float32:
+            raise RuntimeError(f"fused_densify: an upstream gradient is {g.dtype} on {g.device}, expected float32 on {sel.device}")
+        gs.append(g.contiguous())
+    res: List[Optional[torch.Tensor]] = [None] * (1 + len(grads))
+    for k, r in zip(todo, _move_rows(sel, gs, compact)):
+        res[k + 1] = r
+    return tuple(res)
+
+
+def _move_rows_forward(ctx, sel, tensors, compact: bool):
+    out = _move_rows(sel, [x.detach() for x in tensors], compact)
+    ctx.sel = sel
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(*[o for o in out if o.dtype != torch.float32])
+    return tuple(out)
+
+
+class _GatherRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sel, *tensors):
+        return _move_rows_forward(ctx, sel, tensors, True)
+
+    @staticmethod
+    @once_differentiable      # (the kernels are not differentiable themselves: a double backward raises)
+    def backward(ctx, *grads):
+        return _move_rows_backward(ctx, grads, False)
+
+
+class _ScatterRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sel, *tensors):
+        return _move_rows_forward(ctx, sel, tensors, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _move_rows_backward(ctx, grads, True)
+
+
+def _select_dead_u8(dead_u8: torch.Tensor, P: int, dev: torch.device) -> RowSelection:
+    """The prune-only plan over `dead_u8` (uint8 [P] on `dev`, != 0: the row is dropped).  The count is the one read-back."""
+    scratch, host = _plan(P, dev, 1, dict(thr=math.inf, prune_src=_C._ptr(dead_u8)))
+    return RowSelection(P, dev, scratch, host)
+
+
+def select_rows(*, keep: Optional[torch.Tensor] = None, dead: Optional[torch.Tensor] = None) -> RowSelection:
+    """The selection of the rows with keep != 0, or with dead == 0: exactly one of the two, a bool / uint8 [P] or [P, 1] tensor on the GPU.
+    Two launches (classify, scan) and one read-back, the count; the mask is not needed afterwards."""
+    if (keep is None) == (dead is None):
+        raise ValueError("fused_densify.select_rows: give exactly one of keep= and dead=")
+    mask, name = (keep, "keep") if dead is None else (dead, "dead")
+    P = _check_mask(mask, None, name)
+    dev = _C._require_gpu(mask)
+    flat = mask.detach().reshape(-1)
+    return _select_dead_u8((flat == 0).to(torch.uint8) if dead is None else flat.to(torch.uint8).contiguous(), P, dev)
 
 
 # ---- 3DGS-MCMC ------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@ csrc/gsrast_temporal.h).
 Mirror of the reference (paths relative to its root):
   scene/saro_gaussian.py:782-795  get_deformation: lifespan from the opacity head, distance, survival state, time_emb  -> temporal_gate
   scene/saro_gaussian.py:871-881  get_deformation_eval: state > 0.001 and the boolean index of ten tensors             -> temporal_select
-  scene/saro_gaussian.py:761-777  get_intergral (Eq. 22)                                                               -> temporal_integral
+  (not in the reference)          the same selection in a TRAINING step, differentiable (fused_densify.RowSelection)       -> temporal_rows
+  scene/saro_gaussian.py:761-777  get_intergral (Eq. 22)                                                              -> temporal_integral
   scene/saro_gaussian.py:345-356  update_learning_rate's integral prune and inv_intergral                              -> temporal_prune
 
 With head = the opacity head's output AFTER its Sigmoid ([P,1] or [P]), c = temporal_pos (sigmoid(temporal_pos) under sigmoid_tcenter)
@@ -79,19 +80,18 @@ def _gate_forward(P, dev, h, c, t, min_scale, multires, sig, with_embedding, thr
 
 class _TemporalGate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, head, temporal_pos, t, min_scale, multires, sig, with_embedding):
+    def forward(ctx, head, temporal_pos, t, min_scale, multires, sig, with_embedding, threshold=None):
         P, dev, h, c = _rows(head, temporal_pos)
-        lifespan, state, emb, _ = _gate_forward(P, dev, h, c, t, min_scale, multires, sig, with_embedding, None)
+        lifespan, state, emb, dead = _gate_forward(P, dev, h, c, t, min_scale, multires, sig, with_embedding, threshold)
         ctx.save_for_backward(h, c)
         ctx.args = (t, min_scale, sig, tuple(head.shape), tuple(temporal_pos.shape))
         ctx.set_materialize_grads(False)
-        if emb is not None:
-            ctx.mark_non_differentiable(emb)
-        return lifespan, state, emb
+        ctx.mark_non_differentiable(*[x for x in (emb, dead) if x is not None])
+        return lifespan, state, emb, dead      # (dead: the uint8 [P] of `threshold`, written by the same launch; None without one)
 
     @staticmethod
     @once_differentiable      # (the kernels are not differentiable themselves: a double backward raises)
-    def backward(ctx, d_lifespan, d_state, _d_emb):
+    def backward(ctx, d_lifespan, d_state, _d_emb, _d_dead):
         h, c = ctx.saved_tensors
         t, min_scale, sig, head_shape, pos_shape = ctx.args
         P, dev = int(h.shape[0]), h.device
@@ -110,7 +110,7 @@ class _TemporalGate(torch.autograd.Function):
                                                         _C._ptr(d_head), _C._ptr(d_pos), _C._stream_of(dev))
         if rc != 0:
             raise _C._err(rc, "gsrast_temporal_gate_backward")
-        return d_head, d_pos, None, None, None, None, None
+        return d_head, d_pos, None, None, None, None, None, None
 
 
 def temporal_gate(head: torch.Tensor, temporal_pos: torch.Tensor, timestamp, *, min_scale: float, multires: int = 4,
@@ -120,7 +120,31 @@ def temporal_gate(head: torch.Tensor, temporal_pos: torch.Tensor, timestamp, *, 
     Works under torch.no_grad().  `timestamp`: a Python float; a one-element tensor is converted with float(), which synchronises when it
     lives on the GPU."""
     min_scale, multires = _check_scalars(min_scale, multires)
-    return _TemporalGate.apply(head, temporal_pos, _timestamp(timestamp), min_scale, multires, bool(sigmoid_tcenter), bool(with_embedding))
+    return _TemporalGate.apply(head, temporal_pos, _timestamp(timestamp), min_scale, multires, bool(sigmoid_tcenter), bool(with_embedding))[:3]
+
+
+def temporal_rows(head: torch.Tensor, temporal_pos: torch.Tensor, timestamp, *, min_scale: float, multires: int = 4,
+                  sigmoid_tcenter: bool = False, threshold: float = 0.001, also_dead: Optional[torch.Tensor] = None):
+    """get_deformation_eval's selection for a TRAINING step: the gate with `temporal_gate`'s full-size outputs and autograd, and the
+    `fused_densify.RowSelection` of the rows with state > threshold, taken from the `dead` byte the gate launch itself writes (no second pass
+    over `state`).  Returns (sel, lifespan [P,1], state [P,1], time_emb [P, 2 multires + 1]); one read-back, the count.
+    `sel.gather` / `sel.scatter` then run the heads, and optionally the rasterizer, on the alive rows only, with full-size gradients on the leaves.
+    Exactness: a dropped row has opacity * state <= threshold, and the blend rejects every pair with alpha < 1/255, with or without
+    antialiasing (that factor is <= 1).  So while threshold < 1/255 a dropped row adds nothing to the image and every gradient the render
+    sends back to it is exactly zero: selecting changes no result.  A threshold >= 1/255 makes it an approximation.
+    also_dead: a bool / uint8 [P] or [P, 1] tensor OR-ed into the mask -- the caller's own cull, e.g. the negation of mark_visible on the base
+    positions.  Unlike the lifespan rule that one IS an approximation wherever a head's residual would have moved a culled row into view."""
+    min_scale, multires = _check_scalars(min_scale, multires)
+    t = _timestamp(timestamp)
+    if also_dead is not None:
+        fused_densify._check_mask(also_dead, int(head.shape[0]) if head.dim() else None, "also_dead")
+    lifespan, state, emb, dead = _TemporalGate.apply(head, temporal_pos, t, min_scale, multires, bool(sigmoid_tcenter), True, float(threshold))
+    P, dev = int(dead.shape[0]), dead.device
+    if also_dead is not None:
+        if also_dead.device != dev:
+            raise RuntimeError(f"fused_temporal: also_dead is on {also_dead.device}, head on {dev}")
+        dead = dead | (also_dead.detach().reshape(-1) != 0).to(torch.uint8)
+    return fused_densify._select_dead_u8(dead, P, dev), lifespan, state, emb
 
 
 @torch.no_grad()
