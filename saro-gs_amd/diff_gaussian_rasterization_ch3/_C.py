@@ -28,29 +28,6 @@ ABI_VERSION = 6   # include/gsrast.h: GSRAST_ABI_VERSION this binding was writte
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 _lib: Optional[C.CDLL] = None
 
-# every symbol include/gsrast.h declares (tests check the library exports all of them)
-EXPORTS = (
-    "gsrast_forward", "gsrast_backward", "gsrast_mark_visible", "gsrast_geometry_bytes",
-    "gsrast_binning_bytes", "gsrast_image_bytes", "gsrast_debug_export", "gsrast_set_option",
-    "gsrast_get_option", "gsrast_profile_kernel_count", "gsrast_profile_kernel_name",
-    "gsrast_profile_collect", "gsrast_profile_read", "gsrast_profile_reset", "gsrast_last_error",
-    "gsrast_abi_version", "gsrast_loss_scratch_bytes", "gsrast_loss_forward", "gsrast_loss_backward",
-    "gsrast_sh_grad_combine", "gsrast_sh_grad_combine_rows", "gsrast_sh_grad_combine_union", "gsrast_rows_pack", "gsrast_rows_unpack", "gsrast_grad_rows_pack", "gsrast_grad_rows_clear", "gsrast_grad_rows_add", "gsrast_touched_rows", "gsrast_activate_forward", "gsrast_activate_backward", "gsrast_adam_step", "gsrast_adam_step_visible",
-    "gsrast_densify_scratch_bytes", "gsrast_densify_plan", "gsrast_densify_apply", "gsrast_densify_scatter", "gsrast_densify_stats_update",
-    "gsrast_knn_scratch_bytes", "gsrast_knn3_mean_dist2",
-    "gsrast_hexplane_scratch_bytes", "gsrast_hexplane_forward", "gsrast_hexplane_backward",
-    "gsrast_options_init", "gsrast_context_create", "gsrast_context_destroy", "gsrast_context_query", "gsrast_policy_event", "gsrast_debug_forward_plan", "gsrast_debug_backward_plan",
-    "gsrast_render_forward", "gsrast_render_backward", "gsrast_alloc_prealloc", "gsrast_pose_scratch_bytes",
-    "gsrast_contrib_scratch_bytes", "gsrast_contrib_stats",
-    "gsrast_features_forward", "gsrast_features_backward",
-    "gsrast_distortion_forward", "gsrast_distortion_backward",
-    "gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise",
-    "gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward",
-    "gsrast_mlp3_scratch_bytes_p", "gsrast_mlp3_forward_p", "gsrast_mlp3_backward_p",
-    "gsrast_temporal_gate_forward", "gsrast_temporal_gate_backward", "gsrast_temporal_integral",
-    "gsrast_bilagrid_scratch_bytes", "gsrast_bilagrid_forward", "gsrast_bilagrid_backward", "gsrast_bilagrid_tv",
-)
-
 # include/gsrast.h: the flags word of a call record
 RENDER_AUX = 0x1
 RENDER_ANTIALIAS = 0x2
@@ -185,6 +162,102 @@ class PlaneStruct(C.Structure):
                 ("max_mip_level", C.c_int), ("out_offset", C.c_int)]
 
 
+_vp, _ci, _cf, _cd, _sz, _ll, _u32, _str = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_longlong, C.c_uint32, C.c_char_p
+_opt, _adam, _dens, _mlp, _bila, _plane = (C.POINTER(S) for S in (OptionsStruct, AdamGroupStruct, DensifyGroupStruct, Mlp3Struct, BilagridStruct, PlaneStruct))
+_vpp, _uints = C.POINTER(_vp), C.POINTER(C.c_uint)      # a host array of device pointers; a host array of counts
+
+# name -> (restype, argtypes) of every function include/gsrast.h declares: the one place a signature is written (lib() binds each row;
+# tests/test_capi_abi.py compares every row with its prototype).  A new C entry point is a new row here.
+SIGNATURES = {
+    # the render calls: the reference-shaped positional pair, and the pair over one call record each (the one this binding calls: _render_call)
+    "gsrast_forward": (_ci, (_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _vp, _vp, _vp, _vp)),
+    "gsrast_backward": (_ci, (_ci, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp, _vp, _cf, _cf) + (_vp,) * 15),
+    "gsrast_render_forward": (_ci, (_vp, _opt, C.POINTER(ForwardCallStruct))),
+    "gsrast_render_backward": (_ci, (_opt, C.POINTER(BackwardCallStruct))),
+    "gsrast_mark_visible": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_geometry_bytes": (_sz, (_ci,)),
+    "gsrast_binning_bytes": (_sz, (_ci, _ci, _ci)),
+    "gsrast_image_bytes": (_sz, (_ci, _ci)),
+    "gsrast_pose_scratch_bytes": (_sz, (_ci,)),
+    "gsrast_alloc_prealloc": (_vp, (_vp, _sz)),
+    "gsrast_debug_export": (_ci, (_ci, _ci, _ci, _ci) + (_vp,) * 16),
+    # options, contexts, the host-side plans, profiling
+    "gsrast_options_init": (None, (_opt,)),
+    "gsrast_context_create": (_vp, ()),
+    "gsrast_context_destroy": (None, (_vp,)),
+    "gsrast_context_query": (_ci, (_vp, _str)),
+    "gsrast_policy_event": (_ci, (_vp, _str, _ci, _ci, _ci)),
+    "gsrast_debug_forward_plan": (_ci, (_vp, _opt, C.c_uint, _ci, _ci, _ci, C.POINTER(_ci))),
+    "gsrast_debug_backward_plan": (_ci, (_opt, C.c_uint, C.POINTER(_ci), C.POINTER(_ci))),
+    "gsrast_set_option": (_ci, (_str, _ci)),
+    "gsrast_get_option": (_ci, (_str,)),
+    "gsrast_profile_kernel_count": (_ci, ()),
+    "gsrast_profile_kernel_name": (_str, (_ci,)),
+    "gsrast_profile_collect": (_ci, ()),
+    "gsrast_profile_read": (_ci, (_ci, C.POINTER(_cd), C.POINTER(_ll))),
+    "gsrast_profile_reset": (None, ()),
+    "gsrast_last_error": (_str, ()),
+    "gsrast_abi_version": (_ci, ()),
+    # what runs on a forward's state: blend-weight statistics, feature maps, distortion maps
+    "gsrast_contrib_scratch_bytes": (_sz, (_ci,)),
+    "gsrast_contrib_stats": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_features_forward": (_ci, (_opt, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_features_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_distortion_forward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_distortion_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    # the multi-GPU gradient exchange
+    "gsrast_sh_grad_combine": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _cf, _vp, _vp)),
+    "gsrast_sh_grad_combine_rows": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
+    "gsrast_sh_grad_combine_union": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
+    "gsrast_touched_rows": (_ci, (_ci, _vp, _vp, _vp)),
+    "gsrast_rows_pack": (_ci, (_ll, _vp, _ci, _vpp, C.POINTER(_ci), _vp, _vp)),
+    "gsrast_rows_unpack": (_ci, (_ll, _vp, _ci, _vpp, C.POINTER(_ci), _vp, _vp)),
+    "gsrast_grad_rows_pack": (_ci, (_ci, _vp, _vpp, _vp, _vp, _u32, _vp)),
+    "gsrast_grad_rows_clear": (_ci, (_ci, _vp, _ci, _sz, _u32, _vpp, _ci, _vp, _vp, _vp, _vp)),
+    "gsrast_grad_rows_add": (_ci, (_ci, _vp, _u32, _vpp, _ci, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
+    # loss, epilogue, Adam, k-NN
+    "gsrast_loss_scratch_bytes": (_sz, (_ci, _ci, _ci)),
+    "gsrast_loss_forward": (_ci, (_ci, _ci, _ci, _vp, _vp, _cf, _vp, _vp, _vp)),
+    "gsrast_loss_backward": (_ci, (_ci, _ci, _ci, _vp, _vp, _cf, _vp, _vp, _vp, _vp)),
+    "gsrast_activate_forward": (_ci, (_ci, _ci) + (_vp,) * 16),
+    "gsrast_activate_backward": (_ci, (_ci,) + (_vp,) * 14),
+    "gsrast_adam_step": (_ci, (_ci, _adam, _cd, _cd, _cd, _ci, _vp)),
+    "gsrast_adam_step_visible": (_ci, (_ci, _adam, _vp, _ci, _ll, _cd, _cd, _cd, _ci, _vp)),
+    "gsrast_knn_scratch_bytes": (_sz, (_ci,)),
+    "gsrast_knn3_mean_dist2": (_ci, (_ci, _vp, _vp, _vp, _vp)),
+    # densification: clone / split / prune, and MCMC
+    "gsrast_densify_scratch_bytes": (_sz, (_ci,)),
+    "gsrast_densify_plan": (_ci, (_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp)),
+    "gsrast_densify_apply": (_ci, (_ci, _ci, _vp, _uints, _ci, _dens, _vp, _vp, _vp, _vp)),
+    "gsrast_densify_scatter": (_ci, (_ci, _vp, _uints, _ci, _dens, _vp)),
+    "gsrast_densify_stats_update": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp)),
+    "gsrast_mcmc_scratch_bytes": (_sz, (_ci, _ci)),
+    "gsrast_mcmc_plan": (_ci, (_ci, _vp, _vp, _cf, _vp, _vp, _vp, _vp)),
+    "gsrast_mcmc_sample": (_ci, (_ci, _ci, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_mcmc_relocate": (_ci, (_ci, _ci, _vp, _vp, _uints, _cf, _ci, _dens, _vp)),
+    "gsrast_mcmc_grow": (_ci, (_ci, _ci, _vp, _vp, _uints, _cf, _ci, _dens, _vp)),
+    "gsrast_mcmc_noise": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp)),
+    # the fused MLP heads, the temporal gate, the bilateral grid, the hexplane lookup
+    "gsrast_mlp3_scratch_bytes": (_sz, (_mlp, _ci)),
+    "gsrast_mlp3_forward": (_ci, (_mlp, _ci, _vp)),
+    "gsrast_mlp3_backward": (_ci, (_mlp, _ci, _vp, _vp)),
+    "gsrast_mlp3_scratch_bytes_p": (_sz, (_mlp, _ci, _ci)),
+    "gsrast_mlp3_forward_p": (_ci, (_mlp, _ci, _ci, _vp)),
+    "gsrast_mlp3_backward_p": (_ci, (_mlp, _ci, _ci, _vp, _vp)),
+    "gsrast_temporal_gate_forward": (_ci, (_ci, _ci, _ci, _cf, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_temporal_gate_backward": (_ci, (_ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_temporal_integral": (_ci, (_ci, _ci, _cf, _cf, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_bilagrid_scratch_bytes": (_sz, (_bila,)),
+    "gsrast_bilagrid_forward": (_ci, (_bila, _vp, _vp, _vp, _vp)),
+    "gsrast_bilagrid_backward": (_ci, (_bila, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_bilagrid_tv": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_hexplane_scratch_bytes": (_sz, (_ci, _plane, _ci, _ci)),
+    "gsrast_hexplane_forward": (_ci, (_ci, _ci, _ci, _ci, _ci, _plane, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_hexplane_backward": (_ci, (_ci, _ci, _ci, _ci, _ci, _plane, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp)),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 def lib() -> C.CDLL:
     """Load libgsrast_hip.so (built by saro-gs_amd/build.py / __graft_entry__.build())."""
     global _lib
@@ -195,138 +268,11 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python saro-gs_amd/build.py` "
             "(hipcc --offload-arch=gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
-    vp, ci, cf = C.c_void_p, C.c_int, C.c_float
-    opt = C.POINTER(OptionsStruct)
-    # the render calls: the reference-shaped positional pair, and the pair over one call record each (the one this binding calls: _render_call)
-    L.gsrast_forward.restype = L.gsrast_backward.restype = L.gsrast_render_forward.restype = L.gsrast_render_backward.restype = ci      # (ctypes' default, spelled out)
-    L.gsrast_forward.argtypes = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]
-    L.gsrast_backward.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf] + [vp] * 15
-    L.gsrast_render_forward.argtypes, L.gsrast_render_backward.argtypes = [vp, opt, C.POINTER(ForwardCallStruct)], [opt, C.POINTER(BackwardCallStruct)]
-    L.gsrast_options_init.restype = None
-    L.gsrast_options_init.argtypes = [C.POINTER(OptionsStruct)]
-    L.gsrast_context_create.restype = vp
-    L.gsrast_context_destroy.restype = None
-    L.gsrast_context_destroy.argtypes = [vp]
-    L.gsrast_context_query.restype = ci
-    L.gsrast_context_query.argtypes = [vp, C.c_char_p]
-    L.gsrast_policy_event.restype = ci
-    L.gsrast_policy_event.argtypes = [vp, C.c_char_p, ci, ci, ci]
-    L.gsrast_mark_visible.restype = ci
-    L.gsrast_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
-    for name in ("gsrast_geometry_bytes",):
-        getattr(L, name).restype = C.c_size_t
-        getattr(L, name).argtypes = [ci]
-    L.gsrast_pose_scratch_bytes.restype = C.c_size_t
-    L.gsrast_pose_scratch_bytes.argtypes = [ci]
-    L.gsrast_contrib_scratch_bytes.restype = C.c_size_t
-    L.gsrast_contrib_scratch_bytes.argtypes = [ci]
-    L.gsrast_contrib_stats.restype = ci
-    L.gsrast_contrib_stats.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_features_forward.restype = L.gsrast_features_backward.restype = ci
-    L.gsrast_features_forward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    L.gsrast_features_backward.argtypes = [opt, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_distortion_forward.restype = L.gsrast_distortion_backward.restype = ci
-    L.gsrast_distortion_forward.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    L.gsrast_distortion_backward.argtypes = [opt, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    L.gsrast_binning_bytes.restype = C.c_size_t
-    L.gsrast_binning_bytes.argtypes = [ci, ci, ci]
-    L.gsrast_image_bytes.restype = C.c_size_t
-    L.gsrast_image_bytes.argtypes = [ci, ci]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     global _PREALLOC_CB
     _PREALLOC_CB = _ALLOC_FN(C.cast(L.gsrast_alloc_prealloc, C.c_void_p).value)      # the library's own C callback over pre-allocated memory (no trip into Python)
-    L.gsrast_debug_export.restype = ci
-    L.gsrast_debug_export.argtypes = [ci, ci, ci, ci] + [vp] * 16
-    L.gsrast_set_option.restype = ci
-    L.gsrast_set_option.argtypes = [C.c_char_p, ci]
-    L.gsrast_get_option.restype = ci
-    L.gsrast_get_option.argtypes = [C.c_char_p]
-    L.gsrast_profile_kernel_count.restype = ci
-    L.gsrast_profile_kernel_name.restype = C.c_char_p
-    L.gsrast_profile_kernel_name.argtypes = [ci]
-    L.gsrast_profile_collect.restype = ci
-    L.gsrast_profile_read.restype = ci
-    L.gsrast_profile_read.argtypes = [ci, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
-    L.gsrast_profile_reset.restype = None
-    L.gsrast_loss_scratch_bytes.restype = C.c_size_t
-    L.gsrast_loss_scratch_bytes.argtypes = [ci, ci, ci]
-    L.gsrast_loss_forward.restype = ci
-    L.gsrast_loss_forward.argtypes = [ci, ci, ci, vp, vp, cf, vp, vp, vp]
-    L.gsrast_loss_backward.restype = ci
-    L.gsrast_loss_backward.argtypes = [ci, ci, ci, vp, vp, cf, vp, vp, vp, vp]
-    L.gsrast_sh_grad_combine.restype = ci
-    L.gsrast_sh_grad_combine.argtypes = [ci, ci, ci, ci, vp, vp, C.c_size_t, cf, vp, vp]
-    L.gsrast_touched_rows.restype = ci
-    L.gsrast_touched_rows.argtypes = [ci, vp, vp, vp]
-    L.gsrast_sh_grad_combine_rows.restype = ci
-    L.gsrast_sh_grad_combine_rows.argtypes = [ci, ci, ci, ci, vp, vp, C.c_size_t, ci, vp, cf, vp, vp, vp, vp]
-    for fn in (L.gsrast_rows_pack, L.gsrast_rows_unpack):
-        fn.restype = ci
-        fn.argtypes = [C.c_longlong, vp, ci, C.POINTER(vp), C.POINTER(ci), vp, vp]
-    L.gsrast_grad_rows_pack.restype = ci
-    L.gsrast_grad_rows_pack.argtypes = [ci, vp, C.POINTER(vp), vp, vp, C.c_uint32, vp]
-    L.gsrast_grad_rows_clear.restype = ci
-    L.gsrast_grad_rows_clear.argtypes = [ci, vp, ci, C.c_size_t, C.c_uint32, C.POINTER(vp), ci, vp, vp, vp, vp]
-    L.gsrast_grad_rows_add.restype = ci
-    L.gsrast_grad_rows_add.argtypes = [ci, vp, C.c_uint32, C.POINTER(vp), ci, ci, vp, cf, vp, vp, vp, vp]
-    L.gsrast_sh_grad_combine_union.restype = ci
-    L.gsrast_sh_grad_combine_union.argtypes = [ci, ci, ci, ci, vp, vp, C.c_size_t, ci, vp, cf, vp, vp, vp, vp]
-    L.gsrast_activate_forward.restype = ci
-    L.gsrast_activate_forward.argtypes = [ci, ci] + [vp] * 16
-    L.gsrast_activate_backward.restype = ci
-    L.gsrast_activate_backward.argtypes = [ci] + [vp] * 14
-    L.gsrast_knn_scratch_bytes.restype = C.c_size_t
-    L.gsrast_knn_scratch_bytes.argtypes = [ci]
-    L.gsrast_knn3_mean_dist2.restype = ci
-    L.gsrast_knn3_mean_dist2.argtypes = [ci, vp, vp, vp, vp]
-    L.gsrast_adam_step.restype = ci
-    L.gsrast_adam_step.argtypes = [ci, C.POINTER(AdamGroupStruct), C.c_double, C.c_double, C.c_double, ci, vp]
-    L.gsrast_adam_step_visible.restype = ci
-    L.gsrast_adam_step_visible.argtypes = [ci, C.POINTER(AdamGroupStruct), vp, ci, C.c_longlong, C.c_double, C.c_double, C.c_double, ci, vp]
-    L.gsrast_densify_scratch_bytes.restype = C.c_size_t
-    L.gsrast_densify_scratch_bytes.argtypes = [ci]
-    L.gsrast_densify_plan.restype = ci
-    L.gsrast_densify_plan.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp]
-    L.gsrast_densify_apply.restype = ci
-    L.gsrast_densify_apply.argtypes = [ci, ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp, vp, vp, vp]
-    L.gsrast_densify_scatter.restype = ci
-    L.gsrast_densify_scatter.argtypes = [ci, vp, C.POINTER(C.c_uint), ci, C.POINTER(DensifyGroupStruct), vp]
-    L.gsrast_densify_stats_update.restype = ci
-    L.gsrast_densify_stats_update.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp]
-    L.gsrast_mcmc_scratch_bytes.restype = C.c_size_t
-    L.gsrast_mcmc_scratch_bytes.argtypes = [ci, ci]
-    L.gsrast_mcmc_plan.restype = L.gsrast_mcmc_sample.restype = L.gsrast_mcmc_relocate.restype = L.gsrast_mcmc_grow.restype = L.gsrast_mcmc_noise.restype = ci
-    L.gsrast_mcmc_plan.argtypes = [ci, vp, vp, cf, vp, vp, vp, vp]
-    L.gsrast_mcmc_sample.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-    L.gsrast_mcmc_relocate.argtypes = L.gsrast_mcmc_grow.argtypes = [ci, ci, vp, vp, C.POINTER(C.c_uint), cf, ci, C.POINTER(DensifyGroupStruct), vp]
-    L.gsrast_mcmc_noise.argtypes = [ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp]
-    L.gsrast_mlp3_scratch_bytes.restype = C.c_size_t
-    L.gsrast_mlp3_scratch_bytes.argtypes = [C.POINTER(Mlp3Struct), ci]
-    L.gsrast_mlp3_forward.restype = L.gsrast_mlp3_backward.restype = ci
-    L.gsrast_mlp3_forward.argtypes = [C.POINTER(Mlp3Struct), ci, vp]
-    L.gsrast_mlp3_backward.argtypes = [C.POINTER(Mlp3Struct), ci, vp, vp]
-    L.gsrast_mlp3_scratch_bytes_p.restype = C.c_size_t
-    L.gsrast_mlp3_scratch_bytes_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci]
-    L.gsrast_mlp3_forward_p.restype = L.gsrast_mlp3_backward_p.restype = ci
-    L.gsrast_mlp3_forward_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci, vp]
-    L.gsrast_mlp3_backward_p.argtypes = [C.POINTER(Mlp3Struct), ci, ci, vp, vp]
-    L.gsrast_temporal_gate_forward.restype = L.gsrast_temporal_gate_backward.restype = L.gsrast_temporal_integral.restype = ci
-    L.gsrast_temporal_gate_forward.argtypes = [ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_temporal_gate_backward.argtypes = [ci, ci, cf, cf, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_temporal_integral.argtypes = [ci, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_bilagrid_scratch_bytes.restype = C.c_size_t
-    L.gsrast_bilagrid_scratch_bytes.argtypes = [C.POINTER(BilagridStruct)]
-    L.gsrast_bilagrid_forward.restype = L.gsrast_bilagrid_backward.restype = L.gsrast_bilagrid_tv.restype = ci
-    L.gsrast_bilagrid_forward.argtypes = [C.POINTER(BilagridStruct), vp, vp, vp, vp]
-    L.gsrast_bilagrid_backward.argtypes = [C.POINTER(BilagridStruct), vp, vp, vp, vp, vp, vp, vp]
-    L.gsrast_bilagrid_tv.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]
-    L.gsrast_hexplane_scratch_bytes.restype = C.c_size_t
-    L.gsrast_hexplane_scratch_bytes.argtypes = [ci, C.POINTER(PlaneStruct), ci, ci]
-    L.gsrast_hexplane_forward.restype = ci
-    L.gsrast_hexplane_forward.argtypes = [ci, ci, ci, ci, ci, C.POINTER(PlaneStruct), vp, vp, vp, vp, vp]
-    L.gsrast_hexplane_backward.restype = ci
-    L.gsrast_hexplane_backward.argtypes = [ci, ci, ci, ci, ci, C.POINTER(PlaneStruct), vp, vp, vp, vp, vp, ci, vp, vp]
-    L.gsrast_last_error.restype = C.c_char_p
-    L.gsrast_abi_version.restype = ci
     if L.gsrast_abi_version() != ABI_VERSION:
         raise ImportError("libgsrast_hip.so: ABI version mismatch")
     _lib = L
@@ -437,10 +383,7 @@ def _export_touched(ar: "GradArena", P: int, geomBuffer: torch.Tensor, dev: torc
     t = getattr(ar, "touched", None)
     if t is None or t.numel() != P or t.device != dev:
         t = ar.touched = torch.empty(P, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = lib().gsrast_touched_rows(P, _ptr(geomBuffer), t.data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_touched_rows")
+    launch("gsrast_touched_rows", dev, P, _ptr(geomBuffer), t.data_ptr())
     ar.touched_fresh = True
     ar.touched_seq = getattr(ar, "touched_seq", 0) + 1       # which backward these flags belong to (view_parallel._touched_hook tags its capacity event with it)
 
@@ -525,6 +468,23 @@ class _on_device:
         if self.inner is not None:
             return self.inner.__exit__(*exc)
         return False
+
+
+def launch(name: str, dev: torch.device, *args) -> None:
+    """The library's `name`(*args, stream) -- how every training kernel is launched: `dev` made current if it is not, the stream torch's
+    current one on `dev`; raises _err on a non-zero result.  (Not the render calls: _render_call.)"""
+    with _on_device(dev):
+        rc = getattr(lib(), name)(*args, _stream_of(dev))
+    if rc != 0:
+        raise _err(rc, name)
+
+
+def scratch_bytes(name: str, *args) -> int:
+    """The library's `name`(*args) of the *_scratch_bytes calls whose 0 is a refusal: raises with the reason the call left in gsrast_last_error."""
+    n = getattr(lib(), name)(*args)
+    if n == 0:
+        raise _err(-1, name)
+    return n
 
 
 class _Arena:
@@ -894,11 +854,8 @@ def contrib_stats(contrib: torch.Tensor, pixel_weights: Optional[torch.Tensor], 
     check_contrib(contrib, pixel_weights, P, int(H), int(W), dev)
     if P == 0:
         return contrib
-    with _on_device(dev):
-        rc = lib().gsrast_contrib_stats(C.byref(_options_struct(options=options)), P, int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
-                                        _ptr(imageBuffer), _ptr(pixel_weights), contrib.data_ptr(), _contrib_scratch(P, dev).data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_contrib_stats")
+    launch("gsrast_contrib_stats", dev, C.byref(_options_struct(options=options)), P, int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+         _ptr(imageBuffer), _ptr(pixel_weights), contrib.data_ptr(), _contrib_scratch(P, dev).data_ptr())
     return contrib
 
 
@@ -925,11 +882,8 @@ def features_forward(features: torch.Tensor, R: int, W: int, H: int, geomBuffer:
     check_features(features, P, dev)
     Cn = int(features.shape[1])
     out = torch.empty((Cn, int(H), int(W)), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = lib().gsrast_features_forward(C.byref(_options_struct(options=options)), P, int(R), Cn, int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
-                                           _ptr(imageBuffer), _ptr(features), out.data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_features_forward")
+    launch("gsrast_features_forward", dev, C.byref(_options_struct(options=options)), P, int(R), Cn, int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+         _ptr(imageBuffer), _ptr(features), out.data_ptr())
     return out
 
 
@@ -957,10 +911,8 @@ def _features_between(features: Optional[tuple], ar, P: int, R: int, W: int, H: 
     dL_dfeatures = torch.empty((P, Cn), dtype=torch.float32, device=dev)
 
     def between():
-        rc = lib().gsrast_features_backward(C.byref(_options_struct(options=options)), P, R, Cn, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
-                                            _ptr(imageBuffer), _ptr(feats), dL_dmap.data_ptr(), _ptr(dL_dfeatures), _stream_of(dev))
-        if rc != 0:
-            raise _err(rc, "gsrast_features_backward")
+        launch("gsrast_features_backward", dev, C.byref(_options_struct(options=options)), P, R, Cn, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
+             _ptr(imageBuffer), _ptr(feats), dL_dmap.data_ptr(), _ptr(dL_dfeatures))
     return between, dL_dfeatures
 
 
@@ -977,11 +929,8 @@ def distortion_forward(P: int, R: int, W: int, H: int, geomBuffer: torch.Tensor,
     forward enqueued there.  `options`: the per-call options of that forward (default: the calling thread's)."""
     out = torch.empty((int(H), int(W)), dtype=torch.float32, device=dev)
     moments = torch.empty((2, int(H), int(W)), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = lib().gsrast_distortion_forward(C.byref(_options_struct(options=options)), int(P), int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
-                                             _ptr(imageBuffer), out.data_ptr(), moments.data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_distortion_forward")
+    launch("gsrast_distortion_forward", dev, C.byref(_options_struct(options=options)), int(P), int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
+         _ptr(imageBuffer), out.data_ptr(), moments.data_ptr())
     return out, moments
 
 
@@ -1015,10 +964,8 @@ def _distortion_between(distortion: Optional[tuple], between, ar, P: int, R: int
     def both():
         if between is not None:
             between()
-        rc = lib().gsrast_distortion_backward(C.byref(_options_struct(options=options)), P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
-                                              _ptr(imageBuffer), moments.data_ptr(), dL_dmap.data_ptr(), _stream_of(dev))
-        if rc != 0:
-            raise _err(rc, "gsrast_distortion_backward")
+        launch("gsrast_distortion_backward", dev, C.byref(_options_struct(options=options)), P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer),
+             _ptr(imageBuffer), moments.data_ptr(), dL_dmap.data_ptr())
     return both
 
 
@@ -1161,7 +1108,6 @@ def sh_grad_combine(arena: "GradArena", means3D: torch.Tensor, chunks: torch.Ten
     SH region are written.  The region is kept zero elsewhere from one step to the next: the rows of the previous union are cleared
     first (the whole region once after a dense combine or a fresh arena).  Whoever writes into those .grad tensors in a way that makes
     a zero row non-zero must set arena.sh_rows_known = False."""
-    L = lib()
     P, M = arena.P, arena.M
     if getattr(arena, "raw", False):
         whole, dc, rest = None, arena.take("features_dc", (P, 1, 3), False), arena.take("features_rest", (P, M - 1, 3), False)
@@ -1182,26 +1128,17 @@ def sh_grad_combine(arena: "GradArena", means3D: torch.Tensor, chunks: torch.Ten
             for v in views:
                 v.index_fill_(0, prev, 0.0)
         arena._sh_union, arena.sh_rows_known = idx, True
-        with _on_device(dev):
-            rc = L.gsrast_sh_grad_combine_union(P, int(arena.last_degree), M, int(n_views), means3D.data_ptr(), chunks.data_ptr(),
-                                                int(chunk_stride if chunk_stride is not None else arena.chunk), int(idx.numel()),
-                                                idx.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest),
-                                                _stream_of(dev))
-        if rc != 0:
-            raise _err(rc, "gsrast_sh_grad_combine_union")
+        launch("gsrast_sh_grad_combine_union", dev, P, int(arena.last_degree), M, int(n_views), means3D.data_ptr(), chunks.data_ptr(),
+             int(chunk_stride if chunk_stride is not None else arena.chunk), int(idx.numel()), idx.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest))
         return whole if whole is not None else (dc, rest)
     if idx is not None:                  # (an M the union kernel does not take: the row map form)
         row_of = torch.full((P,), -1, dtype=torch.int32, device=dev)
         row_of[idx] = torch.arange(idx.numel(), dtype=torch.int32, device=dev)
         rows = int(idx.numel())
     arena.sh_rows_known = False
-    with _on_device(dev):
-        rc = L.gsrast_sh_grad_combine_rows(P, int(arena.last_degree), M, int(n_views), means3D.data_ptr(), chunks.data_ptr(),
-                                           int(chunk_stride if chunk_stride is not None else arena.chunk), int(P if rows is None else rows),
-                                           None if row_of is None else row_of.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest),
-                                           _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_sh_grad_combine_rows")
+    launch("gsrast_sh_grad_combine_rows", dev, P, int(arena.last_degree), M, int(n_views), means3D.data_ptr(), chunks.data_ptr(),
+         int(chunk_stride if chunk_stride is not None else arena.chunk), int(P if rows is None else rows),
+         None if row_of is None else row_of.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest))
     return whole if whole is not None else (dc, rest)
 
 
@@ -1214,12 +1151,7 @@ def rows_pack(idx: torch.Tensor, arrays, packed: torch.Tensor, unpack: bool = Fa
         raise ValueError("rows_pack: packed must be a contiguous [n, sum of widths] array, the arrays contiguous")
     ptrs = (C.c_void_p * k)(*[a.data_ptr() for a in arrays])
     wid = (C.c_int * k)(*widths)
-    dev = packed.device
-    with _on_device(dev):
-        fn = lib().gsrast_rows_unpack if unpack else lib().gsrast_rows_pack
-        rc = fn(n, idx.data_ptr(), k, ptrs, wid, packed.data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_rows_pack")
+    launch("gsrast_rows_unpack" if unpack else "gsrast_rows_pack", packed.device, n, idx.data_ptr(), k, ptrs, wid, packed.data_ptr())
     return packed
 
 
@@ -1243,36 +1175,22 @@ def _dense_ptrs(arena: "GradArena"):
 
 def grad_rows_pack(arena: "GradArena", touched: torch.Tensor, rows: torch.Tensor) -> None:
     """This rank's touched gradient rows into rows[1:] (int32 [1 + cap, 16]; rows[0, 0], zeroed by the caller, counts them)."""
-    dev = rows.device
-    with _on_device(dev):
-        rc = lib().gsrast_grad_rows_pack(arena.P, touched.data_ptr(), _dense_ptrs(arena), arena.factor.data_ptr(), rows.data_ptr(),
-                                         int(rows.shape[0]) - 1, _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_grad_rows_pack")
+    launch("gsrast_grad_rows_pack", rows.device, arena.P, touched.data_ptr(), _dense_ptrs(arena), arena.factor.data_ptr(), rows.data_ptr(), int(rows.shape[0]) - 1)
 
 
 def grad_rows_clear(arena: "GradArena", chunks: torch.Tensor, dense: bool, sh: bool) -> None:
     """Zero the rows the chunks (int32 [n, 1 + cap, 16]) name: of the dense arrays and / or of the SH region(s)."""
     n, cap = int(chunks.shape[0]), int(chunks.shape[1]) - 1
     whole, dc, rest = _arena_sh_arrays(arena) if sh else (None, None, None)
-    dev = chunks.device
-    with _on_device(dev):
-        rc = lib().gsrast_grad_rows_clear(arena.P, chunks.data_ptr(), n, (1 + cap) * GRAD_ROW_WORDS, cap, _dense_ptrs(arena) if dense else None, arena.M,
-                                          _ptr(whole), _ptr(dc), _ptr(rest), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_grad_rows_clear")
+    launch("gsrast_grad_rows_clear", chunks.device, arena.P, chunks.data_ptr(), n, (1 + cap) * GRAD_ROW_WORDS, cap, _dense_ptrs(arena) if dense else None, arena.M,
+         _ptr(whole), _ptr(dc), _ptr(rest))
 
 
 def grad_rows_add(arena: "GradArena", chunk: torch.Tensor, means3D: torch.Tensor, scale: float) -> None:
     """One rank's chunk (int32 [1 + cap, 16]) added into the arena: the dense rows and, recombined from the factor, dL/dsh."""
     whole, dc, rest = _arena_sh_arrays(arena)
-    dev = chunk.device
-    with _on_device(dev):
-        rc = lib().gsrast_grad_rows_add(arena.P, chunk.data_ptr(), int(chunk.shape[0]) - 1, _dense_ptrs(arena), int(arena.last_degree), arena.M,
-                                        means3D.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest),
-                                        _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_grad_rows_add")
+    launch("gsrast_grad_rows_add", chunk.device, arena.P, chunk.data_ptr(), int(chunk.shape[0]) - 1, _dense_ptrs(arena), int(arena.last_degree), arena.M,
+         means3D.data_ptr(), float(scale), _ptr(whole), _ptr(dc), _ptr(rest))
 
 
 def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
@@ -1283,11 +1201,7 @@ def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
     if P != 0:
         means3D, viewmatrix, projmatrix = (_dev_f32(t, n, dev) for t, n in
                                            ((means3D, "means3D"), (viewmatrix, "viewmatrix"), (projmatrix, "projmatrix")))
-        with _on_device(dev):
-            rc = lib().gsrast_mark_visible(P, means3D.data_ptr(), viewmatrix.data_ptr(), projmatrix.data_ptr(),
-                                           present.data_ptr(), _stream_of(dev))
-        if rc != 0:
-            raise _err(rc, "gsrast_mark_visible")
+        launch("gsrast_mark_visible", dev, P, means3D.data_ptr(), viewmatrix.data_ptr(), projmatrix.data_ptr(), present.data_ptr())
     return present
 
 
@@ -1437,13 +1351,9 @@ def debug_export(P: int, R: int, W: int, H: int, geomBuffer, binningBuffer, imag
     keep_cov = int(lib().gsrast_get_option(b"debug_state")) != 0
     if not keep_cov:
         del out["cov3D"]
-    with _on_device(dev):
-        rc = lib().gsrast_debug_export(
-            P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), out["depths"].data_ptr(),
-            out["means2D"].data_ptr(), out["cov3D"].data_ptr() if keep_cov else None, out["conic_opacity"].data_ptr(),
-            out["rgb"].data_ptr(), out["clamped"].data_ptr(), out["tiles_touched"].data_ptr(),
-            _ptr(out["keys_sorted"]), _ptr(out["point_list"]), out["ranges"].data_ptr(),
-            out["final_T"].data_ptr(), out["n_contrib"].data_ptr(), _stream_of(dev))
-    if rc != 0:
-        raise _err(rc, "gsrast_debug_export")
+    launch("gsrast_debug_export", dev, P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), out["depths"].data_ptr(),
+         out["means2D"].data_ptr(), out["cov3D"].data_ptr() if keep_cov else None, out["conic_opacity"].data_ptr(),
+         out["rgb"].data_ptr(), out["clamped"].data_ptr(), out["tiles_touched"].data_ptr(),
+         _ptr(out["keys_sorted"]), _ptr(out["point_list"]), out["ranges"].data_ptr(),
+         out["final_T"].data_ptr(), out["n_contrib"].data_ptr())
     return out

@@ -105,13 +105,8 @@ class GaussianAdam:
         self._step += 1
         if n == 0:
             return
-        L = _C.lib()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if mask is None:
-                rc, what = L.gsrast_adam_step(n, arr, self.betas[0], self.betas[1], self.eps, self._step, stream), "gsrast_adam_step"
-            else:
-                rc, what = L.gsrast_adam_step_visible(n, arr, mask.data_ptr(), 4 if mask.dtype == torch.int32 else 1, mask.numel(),
-                                                      self.betas[0], self.betas[1], self.eps, self._step, stream), "gsrast_adam_step_visible"
-        if rc != 0:
-            raise _C._err(rc, what)
+        if mask is None:
+            _C.launch("gsrast_adam_step", dev, n, arr, self.betas[0], self.betas[1], self.eps, self._step)
+        else:
+            _C.launch("gsrast_adam_step_visible", dev, n, arr, mask.data_ptr(), 4 if mask.dtype == torch.int32 else 1, mask.numel(),
+                    self.betas[0], self.betas[1], self.eps, self._step)

@@ -68,11 +68,7 @@ def _descriptor(grid: torch.Tensor, image: torch.Tensor, window, splits: int = 0
 
 def _forward(desc, grid: torch.Tensor, image: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(image)
-    dev = image.device
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_bilagrid_forward(desc, grid.data_ptr(), image.data_ptr(), out.data_ptr(), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_bilagrid_forward")
+    _C.launch("gsrast_bilagrid_forward", image.device, desc, grid.data_ptr(), image.data_ptr(), out.data_ptr())
     return out
 
 
@@ -83,15 +79,8 @@ def _backward(desc, grid: torch.Tensor, image: torch.Tensor, d_out: torch.Tensor
     d_image = torch.empty_like(image) if need_image else None
     scratch = None
     if need_grid:
-        nbytes = _C.lib().gsrast_bilagrid_scratch_bytes(desc)
-        if nbytes == 0:
-            raise _C._err(-1, "gsrast_bilagrid_scratch_bytes")
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_bilagrid_backward(desc, grid.data_ptr(), image.data_ptr(), d_out.data_ptr(), _C._ptr(d_image), _C._ptr(d_grid),
-                                               _C._ptr(scratch), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_bilagrid_backward")
+        scratch = torch.empty((_C.scratch_bytes("gsrast_bilagrid_scratch_bytes", desc),), dtype=torch.uint8, device=dev)
+    _C.launch("gsrast_bilagrid_backward", dev, desc, grid.data_ptr(), image.data_ptr(), d_out.data_ptr(), _C._ptr(d_image), _C._ptr(d_grid), _C._ptr(scratch))
     return d_grid, d_image
 
 
@@ -129,11 +118,8 @@ def _tv_call(grids: torch.Tensor, want_value: bool, upstream: Optional[torch.Ten
     dev = grids.device
     value = torch.empty((), dtype=torch.float32, device=dev) if want_value else None
     d_grids = None if want_value else torch.empty_like(grids)
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_bilagrid_tv(N, GW, GH, L, grids.data_ptr(), value.data_ptr() if want_value else None,
-                                         upstream.data_ptr() if upstream is not None else None, _C._ptr(d_grids), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_bilagrid_tv")
+    _C.launch("gsrast_bilagrid_tv", dev, N, GW, GH, L, grids.data_ptr(), value.data_ptr() if want_value else None,
+            upstream.data_ptr() if upstream is not None else None, _C._ptr(d_grids))
     return value if want_value else d_grids
 
 

@@ -85,11 +85,8 @@ class DensifyStats:
         dev = _C._require_gpu(self.denom)
         f = lambda t, n: _flat_f32(t, n, P, dev)  # noqa: E731
         grad, count, radii = f(grad, "viewspace_point_grad"), f(step_out["visibility_count"], "visibility_count"), f(step_out["radii"], "radii")
-        with _C._on_device(dev):
-            rc = _C.lib().gsrast_densify_stats_update(P, _C._ptr(grad), _C._ptr(count), _C._ptr(radii), _C._ptr(self.xyz_gradient_accum),
-                                                      _C._ptr(self.denom), _C._ptr(self.max_radii2D), int(is_mean), _C._stream_of(dev))
-        if rc != 0:
-            raise _C._err(rc, "gsrast_densify_stats_update")
+        _C.launch("gsrast_densify_stats_update", dev, P, _C._ptr(grad), _C._ptr(count), _C._ptr(radii), _C._ptr(self.xyz_gradient_accum),
+                _C._ptr(self.denom), _C._ptr(self.max_radii2D), int(is_mean))
 
 
 class ContribStats:
@@ -430,14 +427,10 @@ def _move_rows(sel: RowSelection, tensors: Sequence[torch.Tensor], compact: bool
     arr = (_C.DensifyGroupStruct * len(tensors))()
     for a, src, dst in zip(arr, tensors, out):
         a.src, a.dst, a.width, a.role = _C._ptr(src), _C._ptr(dst), _rows_width(src), _C.DENSIFY_COPY
-    L = _C.lib()
-    with _C._on_device(dev):
-        if compact:
-            rc = L.gsrast_densify_apply(P, 1, sel._scratch.data_ptr(), sel._counts, len(tensors), arr, None, None, None, _C._stream_of(dev))
-        else:
-            rc = L.gsrast_densify_scatter(P, sel._scratch.data_ptr(), sel._counts, len(tensors), arr, _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_densify_apply" if compact else "gsrast_densify_scatter")
+    if compact:
+        _C.launch("gsrast_densify_apply", dev, P, 1, sel._scratch.data_ptr(), sel._counts, len(tensors), arr, None, None, None)
+    else:
+        _C.launch("gsrast_densify_scatter", dev, P, sel._scratch.data_ptr(), sel._counts, len(tensors), arr)
     return out
 
 
@@ -533,13 +526,10 @@ def _mcmc_moved(opt, names: Dict[str, str], extras: Iterable[torch.Tensor]):
 def _mcmc_plan(P: int, dev: torch.device, opacity: torch.Tensor, dead_u8: Optional[torch.Tensor], min_opacity: float, n: int = 0):
     """gsrast_mcmc_plan and the read-back of its counts (the one synchronisation).  Returns (scratch, weights [P] int32, the four words,
     n_dead, n_alive, W)."""
-    L = _C.lib()
-    scratch = torch.empty(int(L.gsrast_mcmc_scratch_bytes(P, n)), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(int(_C.lib().gsrast_mcmc_scratch_bytes(P, n)), dtype=torch.uint8, device=dev)
     weights = torch.empty(P, dtype=torch.int32, device=dev)
     counts_dev = torch.empty(4, dtype=torch.int32, device=dev)
-    rc = L.gsrast_mcmc_plan(P, _C._ptr(opacity), _C._ptr(dead_u8), float(min_opacity), _C._ptr(weights), scratch.data_ptr(), counts_dev.data_ptr(), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_mcmc_plan")
+    _C.launch("gsrast_mcmc_plan", dev, P, _C._ptr(opacity), _C._ptr(dead_u8), float(min_opacity), _C._ptr(weights), scratch.data_ptr(), counts_dev.data_ptr())
     host = [int(v) & 0xFFFFFFFF for v in counts_dev.cpu().tolist()]
     return scratch, weights, host, host[0], host[1], host[2] | (host[3] << 32)
 
@@ -553,9 +543,7 @@ def _mcmc_sample(P: int, n: int, dev: torch.device, scratch: torch.Tensor, gener
             raise RuntimeError(f"fused_densify: draws must be int64 [{n}] on {dev} (got {draws.dtype} {tuple(draws.shape)} on {draws.device})")
         draws = draws.contiguous()
     src = torch.empty(n, dtype=torch.int32, device=dev)
-    rc = _C.lib().gsrast_mcmc_sample(P, n, _C._ptr(draws), scratch.data_ptr(), _C._ptr(src), None, _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_mcmc_sample")
+    _C.launch("gsrast_mcmc_sample", dev, P, n, _C._ptr(draws), scratch.data_ptr(), _C._ptr(src), None)
     return src
 
 
@@ -587,9 +575,7 @@ def mcmc_relocate(opt, *, min_opacity: float = 0.005, dead_mask: Optional[torch.
         arr = (_C.DensifyGroupStruct * len(moved))()
         for a, (t, m, v, role) in zip(arr, moved):
             a.dst, a.dst_m, a.dst_v, a.width, a.role = _C._ptr(t), _C._ptr(m), _C._ptr(v), _rows_width(t), role
-        rc = _C.lib().gsrast_mcmc_relocate(P, n_dead, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr, _C._stream_of(dev))
-        if rc != 0:
-            raise _C._err(rc, "gsrast_mcmc_relocate")
+        _C.launch("gsrast_mcmc_relocate", dev, P, n_dead, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr)
     counts["n_relocated"] = n_dead
     return counts
 
@@ -624,9 +610,7 @@ def mcmc_grow(opt, *, cap_max: int, growth: float = 1.05, min_opacity: float = 0
             a.src, a.src_m, a.src_v, a.dst, a.dst_m, a.dst_v = _C._ptr(t), _C._ptr(m), _C._ptr(v), _C._ptr(dst), _C._ptr(dm), _C._ptr(dv)
             a.width, a.role = _rows_width(t), role
             out.append((dst, dm, dv))
-        rc = _C.lib().gsrast_mcmc_grow(P, n, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr, _C._stream_of(dev))
-        if rc != 0:
-            raise _C._err(rc, "gsrast_mcmc_grow")
+        _C.launch("gsrast_mcmc_grow", dev, P, n, _C._ptr(src), scratch.data_ptr(), (C.c_uint * 4)(*host), min_opacity, len(moved), arr)
     new = _install(opt, rows, out[: len(rows)])
     return dict(n_added=n, P=P + n), new, [r[0] for r in out[len(rows):]]
 
@@ -652,11 +636,8 @@ def mcmc_inject_noise(xyz: torch.Tensor, rotation: torch.Tensor, scaling: torch.
             raise RuntimeError(f"fused_densify: noise must be [{P}, 3] on {dev}, got {tuple(noise.shape)} on {noise.device}")
         noise = noise.to(torch.float32).contiguous()
     rs = _flat_f32(row_scale, "row_scale", P, dev) if row_scale is not None else None
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_mcmc_noise(P, _C._ptr(xyz), _C._ptr(rotation), _C._ptr(scaling), _C._ptr(opacity), _C._ptr(noise), _C._ptr(rs),
-                                        float(scale), float(k), float(x0), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_mcmc_noise")
+    _C.launch("gsrast_mcmc_noise", dev, P, _C._ptr(xyz), _C._ptr(rotation), _C._ptr(scaling), _C._ptr(opacity), _C._ptr(noise), _C._ptr(rs),
+            float(scale), float(k), float(x0))
 
 
 def mcmc_refine(opt, *, cap_max: int, min_opacity: float = 0.005, growth: float = 1.05, generator: Optional[torch.Generator] = None,

@@ -54,13 +54,8 @@ class _Activate(torch.autograd.Function):
         o = dict(dtype=torch.float32, device=dev)
         motion, rot, scale = torch.empty((P, 3), **o), torch.empty((P, 4), **o), torch.empty((P, 3), **o)
         opa, shs = torch.empty((P, 1), **o), torch.empty((P, M, 3), **o)
-        with torch.cuda.device(dev):
-            rc = _C.lib().gsrast_activate_forward(
-                P, M, _p(xyz), _p(motion_res), _p(rotation), _p(rot_res), _p(scaling), _p(opacity), _p(trbf), _p(f_dc),
-                _p(f_rest), _p(shs_res), _p(motion), _p(rot), _p(scale), _p(opa), _p(shs),
-                torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _C._err(rc, "gsrast_activate_forward")
+        _C.launch("gsrast_activate_forward", dev, P, M, _p(xyz), _p(motion_res), _p(rotation), _p(rot_res), _p(scaling), _p(opacity), _p(trbf), _p(f_dc),
+                _p(f_rest), _p(shs_res), _p(motion), _p(rot), _p(scale), _p(opa), _p(shs))
         ctx.save_for_backward(rotation, rot_res, scale, opacity, trbf)
         ctx.has = (motion_res is not None, rot_res is not None, trbf is not None, shs_res is not None)
         ctx.set_materialize_grads(False)
@@ -78,12 +73,8 @@ class _Activate(torch.autograd.Function):
         g_rotation, g_scaling, g_logit = torch.empty((P, 4), **o), torch.empty((P, 3), **o), torch.empty((P, 1), **o)
         g_rres = torch.empty((P, 7), **o) if has_rres else None
         g_trbf = torch.empty((P, 1), **o) if has_trbf else None
-        with torch.cuda.device(dev):
-            rc = _C.lib().gsrast_activate_backward(
-                P, _p(rotation), _p(rot_res), _p(scale), _p(opacity), _p(trbf), _p(d_rot), _p(d_scale), _p(d_opa),
-                _p(g_rotation), _p(g_scaling), _p(g_rres), _p(g_logit), _p(g_trbf), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _C._err(rc, "gsrast_activate_backward")
+        _C.launch("gsrast_activate_backward", dev, P, _p(rotation), _p(rot_res), _p(scale), _p(opacity), _p(trbf), _p(d_rot), _p(d_scale), _p(d_opa),
+                _p(g_rotation), _p(g_scaling), _p(g_rres), _p(g_logit), _p(g_trbf))
         g_dc = g_rest = g_sres = None
         if d_shs is not None:           # no kernel: slices / the tensor itself
             g_dc, g_rest = d_shs[:, :1, :], d_shs[:, 1:, :]

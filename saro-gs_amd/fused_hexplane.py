@@ -49,7 +49,6 @@ class _HexplaneFn(torch.autograd.Function):
         dev = pts.device
         if not pts.is_cuda:
             raise RuntimeError("hexplane lookup: tensors must be on a GPU (HIP) device; there is no CPU fallback")
-        L = _lib.lib()
         texs = [_channel_last(g.detach().float()) for g in grids]
         Cn = int(texs[0].shape[2])
         if any(int(t.shape[2]) != Cn for t in texs):
@@ -60,20 +59,14 @@ class _HexplaneFn(torch.autograd.Function):
         if lv.shape != p.shape:
             raise RuntimeError("hexplane lookup: levels must have the shape of pts")
         ps = _PlaneSet(texs, cols, max_mips, offsets)
-        nbytes = L.gsrast_hexplane_scratch_bytes(ps.n, ps.arr, Cn, N)
-        if nbytes == 0:
-            raise _lib._err(-1, "gsrast_hexplane_scratch_bytes")       # (the call left its reason in gsrast_last_error)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(_lib.scratch_bytes("gsrast_hexplane_scratch_bytes", ps.n, ps.arr, Cn, N), dtype=torch.uint8, device=dev)
         # the kernel writes the planes' blocks only: columns no block covers are zero-filled here, and only when there are any
         # (the field's blocks tile its row, so that path stays one launch)
         covered = sorted(set(int(o) for o in offsets))
         tiled = covered == list(range(0, F, Cn))
         out = (torch.empty if tiled else torch.zeros)((N, F), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.gsrast_hexplane_forward(N, D, Cn, F, ps.n, ps.arr, p.data_ptr() if N else None, lv.data_ptr() if N else None,
-                                           out.data_ptr() if N else None, scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _lib._err(rc, "gsrast_hexplane_forward")
+        _lib.launch("gsrast_hexplane_forward", dev, N, D, Cn, F, ps.n, ps.arr, p.data_ptr() if N else None, lv.data_ptr() if N else None,
+                  out.data_ptr() if N else None, scratch.data_ptr())
         ctx.meta = (cols, max_mips, offsets, F, Cn, [tuple(g.shape) for g in grids], [g.dim() for g in grids])
         ctx.save_for_backward(p, lv, scratch, *texs)
         ctx.versions = [g._version for g in grids]
@@ -85,7 +78,6 @@ class _HexplaneFn(torch.autograd.Function):
         cols, max_mips, offsets, F, Cn, shapes, dims = ctx.meta
         p, lv, scratch, *texs = ctx.saved_tensors
         dev = p.device
-        L = _lib.lib()
         N, D = int(p.shape[0]), int(p.shape[1])
         dy = dout.contiguous().float()
         grads = [torch.empty_like(t) for t in texs]
@@ -93,13 +85,8 @@ class _HexplaneFn(torch.autograd.Function):
         need_p, need_l = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         d_pts = torch.empty_like(p) if need_p else None
         d_lv = torch.empty_like(lv) if need_l else None
-        with torch.cuda.device(dev):
-            rc = L.gsrast_hexplane_backward(N, D, Cn, F, ps.n, ps.arr, p.data_ptr() if N else None, lv.data_ptr() if N else None,
-                                            dy.data_ptr() if N else None, d_pts.data_ptr() if need_p and N else None,
-                                            d_lv.data_ptr() if need_l and N else None, 1, scratch.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _lib._err(rc, "gsrast_hexplane_backward")
+        _lib.launch("gsrast_hexplane_backward", dev, N, D, Cn, F, ps.n, ps.arr, p.data_ptr() if N else None, lv.data_ptr() if N else None,
+                  dy.data_ptr() if N else None, d_pts.data_ptr() if need_p and N else None, d_lv.data_ptr() if need_l and N else None, 1, scratch.data_ptr())
         if N == 0:
             if need_p: d_pts.zero_()
             if need_l: d_lv.zero_()

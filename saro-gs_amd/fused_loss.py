@@ -27,14 +27,9 @@ class _L1DSSIM(torch.autograd.Function):
         image = image.contiguous().float()
         gt = gt.contiguous().float()
         Cn, H, W = (int(v) for v in image.shape)
-        L = _C.lib()
-        scratch = torch.empty(L.gsrast_loss_scratch_bytes(Cn, H, W), dtype=torch.uint8, device=image.device)
+        scratch = torch.empty(_C.lib().gsrast_loss_scratch_bytes(Cn, H, W), dtype=torch.uint8, device=image.device)
         out3 = torch.empty(3, dtype=torch.float32, device=image.device)
-        with torch.cuda.device(image.device):
-            rc = L.gsrast_loss_forward(Cn, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), out3.data_ptr(),
-                                       scratch.data_ptr(), torch.cuda.current_stream(image.device).cuda_stream)
-        if rc != 0:
-            raise _C._err(rc, "gsrast_loss_forward")
+        _C.launch("gsrast_loss_forward", image.device, Cn, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), out3.data_ptr(), scratch.data_ptr())
         ctx.save_for_backward(image, gt, scratch)
         ctx.lambda_dssim = float(lambda_dssim)
         ctx.mark_non_differentiable(out3)
@@ -46,12 +41,7 @@ class _L1DSSIM(torch.autograd.Function):
         Cn, H, W = (int(v) for v in image.shape)
         grad = torch.empty_like(image)
         g = grad_loss.contiguous().float().reshape(1)
-        with torch.cuda.device(image.device):
-            rc = _C.lib().gsrast_loss_backward(Cn, H, W, image.data_ptr(), gt.data_ptr(), ctx.lambda_dssim, g.data_ptr(),
-                                               scratch.data_ptr(), grad.data_ptr(),
-                                               torch.cuda.current_stream(image.device).cuda_stream)
-        if rc != 0:
-            raise _C._err(rc, "gsrast_loss_backward")
+        _C.launch("gsrast_loss_backward", image.device, Cn, H, W, image.data_ptr(), gt.data_ptr(), ctx.lambda_dssim, g.data_ptr(), scratch.data_ptr(), grad.data_ptr())
         return grad, None, None
 
 

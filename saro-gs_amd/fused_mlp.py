@@ -79,7 +79,6 @@ class _FusedMLP3Fn(torch.autograd.Function):
         for name, t in (("x_tail", x_tail), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("w3", w3), ("b3", b3)):
             if t is not None and t.device != x.device:      # (a model not yet moved with .to(device): an error text, not a device fault)
                 raise RuntimeError(f"fused_mlp3: {name} is on {t.device}, x on {x.device}; all tensors must be on x's device")
-        L = _lib.lib()
         dev = x.device
         # made contiguous as fused_hexplane does with its inputs (parameters and the lookup's output are contiguous already: no copy)
         xs = x.detach().contiguous()
@@ -87,10 +86,7 @@ class _FusedMLP3Fn(torch.autograd.Function):
         ws = [p.detach().contiguous() for p in (w1, b1, w2, b2, w3, b3)]
         y = torch.empty((dims[0], dims[5]), dtype=torch.float32, device=dev)
         d = _desc(*dims, sigmoid_out, x=xs, x_tail=ts, w1=ws[0], b1=ws[1], w2=ws[2], b2=ws[3], w3=ws[4], b3=ws[5], y=y)
-        with torch.cuda.device(dev):
-            rc = L.gsrast_mlp3_forward_p(C.byref(d), int(precision), int(workgroups), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _lib._err(rc, "gsrast_mlp3_forward_p")
+        _lib.launch("gsrast_mlp3_forward_p", dev, C.byref(d), int(precision), int(workgroups))
         ctx.dims, ctx.sigmoid, ctx.workgroups, ctx.has_tail, ctx.precision = dims, bool(sigmoid_out), int(workgroups), ts is not None, int(precision)
         # the hidden activations are not kept: x, the tail, the parameters, and y for the sigmoid's derivative
         ctx.save_for_backward(xs, ts if ts is not None else xs.new_empty(0), *ws, y if sigmoid_out else xs.new_empty(0))
@@ -101,7 +97,6 @@ class _FusedMLP3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         xs, ts, w1, b1, w2, b2, w3, b3, y = ctx.saved_tensors
         N, d_x, d_tail, h1, h2, d_out = ctx.dims
-        L = _lib.lib()
         dev = xs.device
         need = ctx.needs_input_grad
         if dy.device != dev:
@@ -117,16 +112,10 @@ class _FusedMLP3Fn(torch.autograd.Function):
                   y=y if ctx.sigmoid else None, dy=dy, **g)
         scratch = None
         if any(k != "dx" for k in g):
-            nbytes = L.gsrast_mlp3_scratch_bytes_p(C.byref(d), ctx.precision, ctx.workgroups)      # workgroups x parameters: independent of N
-            if nbytes == 0:
-                raise _lib._err(-1, "gsrast_mlp3_scratch_bytes_p")
+            nbytes = _lib.scratch_bytes("gsrast_mlp3_scratch_bytes_p", C.byref(d), ctx.precision, ctx.workgroups)      # workgroups x parameters: independent of N
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         if g:
-            with torch.cuda.device(dev):
-                rc = L.gsrast_mlp3_backward_p(C.byref(d), ctx.precision, ctx.workgroups, scratch.data_ptr() if scratch is not None else None,
-                                              torch.cuda.current_stream(dev).cuda_stream)
-            if rc != 0:
-                raise _lib._err(rc, "gsrast_mlp3_backward_p")
+            _lib.launch("gsrast_mlp3_backward_p", dev, C.byref(d), ctx.precision, ctx.workgroups, scratch.data_ptr() if scratch is not None else None)
         return (g.get("dx"), None, g.get("dw1"), g.get("db1"), g.get("dw2"), g.get("db2"), g.get("dw3"), g.get("db3"), None, None, None)
 
 

@@ -70,11 +70,8 @@ def _gate_forward(P, dev, h, c, t, min_scale, multires, sig, with_embedding, thr
     lifespan, state = torch.empty((P, 1), **o), torch.empty((P, 1), **o)
     emb = torch.empty((P, 2 * multires + 1), **o) if with_embedding else None
     dead = torch.empty((P,), dtype=torch.uint8, device=dev) if threshold is not None else None
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_temporal_gate_forward(P, multires, int(sig), t, min_scale, 0.0 if threshold is None else float(threshold), _C._ptr(h), _C._ptr(c),
-                                                   _C._ptr(lifespan), _C._ptr(state), _C._ptr(emb), _C._ptr(dead), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_temporal_gate_forward")
+    _C.launch("gsrast_temporal_gate_forward", dev, P, multires, int(sig), t, min_scale, 0.0 if threshold is None else float(threshold), _C._ptr(h), _C._ptr(c),
+            _C._ptr(lifespan), _C._ptr(state), _C._ptr(emb), _C._ptr(dead))
     return lifespan, state, emb, dead
 
 
@@ -105,11 +102,8 @@ class _TemporalGate(torch.autograd.Function):
             grads.append(g)
         d_head = torch.empty(head_shape, dtype=torch.float32, device=dev) if need_head else None
         d_pos = torch.empty(pos_shape, dtype=torch.float32, device=dev) if need_pos else None
-        with _C._on_device(dev):
-            rc = _C.lib().gsrast_temporal_gate_backward(P, int(sig), t, min_scale, _C._ptr(h), _C._ptr(c), _C._ptr(grads[0]), _C._ptr(grads[1]),
-                                                        _C._ptr(d_head), _C._ptr(d_pos), _C._stream_of(dev))
-        if rc != 0:
-            raise _C._err(rc, "gsrast_temporal_gate_backward")
+        _C.launch("gsrast_temporal_gate_backward", dev, P, int(sig), t, min_scale, _C._ptr(h), _C._ptr(c), _C._ptr(grads[0]), _C._ptr(grads[1]),
+                _C._ptr(d_head), _C._ptr(d_pos))
         return d_head, d_pos, None, None, None, None, None, None
 
 
@@ -185,11 +179,8 @@ def temporal_integral(head: torch.Tensor, temporal_pos: torch.Tensor, *, min_sca
     integral, inv = torch.empty((P, 1), dtype=torch.float32, device=dev), torch.empty((P, 1), dtype=torch.float32, device=dev)
     dead = torch.empty((P,), dtype=torch.uint8, device=dev)
     stats = torch.zeros((2,), dtype=torch.int32, device=dev) if P == 0 else torch.empty((2,), dtype=torch.int32, device=dev)
-    with _C._on_device(dev):
-        rc = _C.lib().gsrast_temporal_integral(P, int(bool(sigmoid_tcenter)), float(start), float(end), min_scale, float(min_integral), _C._ptr(h), _C._ptr(c),
-                                               _C._ptr(integral), _C._ptr(dead), _C._ptr(inv), stats.data_ptr(), _C._stream_of(dev))
-    if rc != 0:
-        raise _C._err(rc, "gsrast_temporal_integral")
+    _C.launch("gsrast_temporal_integral", dev, P, int(bool(sigmoid_tcenter)), float(start), float(end), min_scale, float(min_integral), _C._ptr(h), _C._ptr(c),
+            _C._ptr(integral), _C._ptr(dead), _C._ptr(inv), stats.data_ptr())
     return integral, dead, inv, stats
 
 

@@ -18,11 +18,6 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     out = torch.empty((P,), dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
-    L = _lib.lib()
-    scratch = torch.empty(L.gsrast_knn_scratch_bytes(P), dtype=torch.uint8, device=pts.device)
-    with torch.cuda.device(pts.device):
-        rc = L.gsrast_knn3_mean_dist2(P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr(),
-                                      torch.cuda.current_stream(pts.device).cuda_stream)
-    if rc != 0:
-        raise _lib._err(rc, "gsrast_knn3_mean_dist2")
+    scratch = torch.empty(_lib.lib().gsrast_knn_scratch_bytes(P), dtype=torch.uint8, device=pts.device)
+    _lib.launch("gsrast_knn3_mean_dist2", pts.device, P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr())
     return out

@@ -15,7 +15,6 @@ import torch
 import bilagrid_math as bm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ("gsrast_bilagrid_scratch_bytes", "gsrast_bilagrid_forward", "gsrast_bilagrid_backward", "gsrast_bilagrid_tv")
 IMAGES = [(1, 1, None), (7, 5, None), (37, 53, None), (37, 53, (11, 20, 120, 90))]      # (W, H, window)
 # the profile table as it stood before this feature (its last names are pinned by tests/test_mlp_bf16_host.py as well)
 PROFILE_TAIL = ["mcmc_plan", "mcmc_sample", "mcmc_apply", "mcmc_noise", "mlp_fwd", "mlp_bwd"]
@@ -60,18 +59,9 @@ def test_identity_grid_reproduces_the_image_and_has_no_variation(GW, GH, L):
 
 
 def test_symbols_are_declared_exported_and_bound(rast):
+    """(Every symbol declared, exported and bound with the header's types: tests/test_capi_abi.py.)"""
     L = rast._C.lib()
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsrast.h")).read(), flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n in NEW_EXPORTS:
-        assert re.search(r"\b" + n + r"\s*\(", text), n
-        assert n in rast._C.EXPORTS and hasattr(raw, n), n
-        assert getattr(L, n).argtypes is not None, n
-    assert L.gsrast_bilagrid_scratch_bytes.restype is C.c_size_t
-    assert all(getattr(L, n).restype is C.c_int for n in NEW_EXPORTS[1:])
-    assert [len(getattr(L, n).argtypes) for n in NEW_EXPORTS] == [1, 5, 8, 9]
-    assert re.search(r"int\s+GW,\s*GH,\s*L;[^}]*int\s+W,\s*H;[^}]*int\s+x0,\s*y0,\s*full_W,\s*full_H;[^}]*int\s+splits;[^}]*}\s*gsrast_bilagrid\s*;", text)
-    assert [f for f, _ in rast._C.BilagridStruct._fields_] == ["GW", "GH", "L", "W", "H", "x0", "y0", "full_W", "full_H", "splits"]
     assert C.sizeof(rast._C.BilagridStruct) == 40
     assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
     assert re.search(r"#define\s+GSRAST_ABI_VERSION\s+6\b", text)

@@ -1,15 +1,14 @@
 """CPU: the C-ABI shared library loads without a GPU, exports every symbol include/gsrast.h declares,
 and rejects bad arguments before touching a device (no compute calls here)."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+import capi_header as hdr
 import capi_records as cr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsrast.h")
+HEADER = hdr.HEADER
 
 
 @pytest.fixture(scope="module")
@@ -17,39 +16,45 @@ def L(rast):
     return rast._C.lib()
 
 
-def declared_functions():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gsrast_[a-z_0-9]+)\s*\(", text)) - {"gsrast_alloc_fn"})
-
-
 def test_header_and_library_agree(rast, L):
-    names = declared_functions()
-    assert len(names) >= 16
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n), f"{n} declared in gsrast.h but not exported"
-    assert sorted(rast._C.EXPORTS) == names
+    names = sorted(hdr.prototypes())      # (each of them exported and in EXPORTS: the next test)
     assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
     assert re.search(r"#define GSRAST_ABI_VERSION 6\b", open(HEADER).read())
     render = [n for n in names if re.fullmatch(r"gsrast_(render_)?(forward|backward)\w*", n)]
     assert render == ["gsrast_backward", "gsrast_forward", "gsrast_render_backward", "gsrast_render_forward"]      # four render entry points, no more
 
 
-C_TYPES = {"size_t": C.c_size_t, "unsigned": C.c_uint, "int": C.c_int, "float": C.c_float, "gsrast_alloc_fn": None, "void*": C.c_void_p, "const float*": C.c_void_p,
-           "float*": C.c_void_p, "const int*": C.c_void_p, "int*": C.c_void_p, "char*": C.c_void_p, "const gsrast_raw_inputs*": "RawInputsStruct",
-           "const gsrast_raw_grads*": "RawGradsStruct"}
+def test_every_prototype_matches_its_row_of_the_signature_table(rast, L):
+    """include/gsrast.h against _C.SIGNATURES, the one table lib() binds from: the same names, and for each the header's number of
+    arguments, with every argument and the return type of the C type's width and kind (capi_header.allowed; ctypes types compared by
+    identity).  A c_int where the header says long long, a c_float for a double or a defaulted restype for a size_t fails here."""
+    _C = rast._C
+    protos = hdr.prototypes()
+    assert set(protos) == set(_C.SIGNATURES) and len(protos) >= 78
+    raw = C.CDLL(_C.LIB_PATH)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _C.SIGNATURES[name]
+        assert hasattr(raw, name), f"{name} is not exported"
+        assert any(restype is t for t in hdr.allowed(ret, _C)) and (restype is not C.c_char_p or ret == "const char*"), (name, ret, restype)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for k, (ctype, bound) in enumerate(zip(params, argtypes)):
+            assert any(bound is t for t in hdr.allowed(ctype, _C)), (name, k, ctype, bound)
+        fn = getattr(L, name)       # ... and lib() has bound exactly the row
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert _C.EXPORTS == tuple(_C.SIGNATURES)
 
 
-def declared_fields(struct):
-    """[(name, C type)] of `typedef struct <struct> { ... } <struct>;` as include/gsrast.h declares it, in order."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct + ";", text, flags=re.S).group(1)
-    out = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        ctype, names = re.fullmatch(r"([\w ]+?\*?)\s*(\w+(?:\s*,\s*\w+)*)", decl).groups()
-        out += [(n.strip(), ctype.strip()) for n in names.split(",")]
-    return out
+def test_every_struct_matches_the_header(rast):
+    """Every struct the binding declares against its `typedef struct` in include/gsrast.h: the same field names, in the same order, each of
+    the one ctypes type a field of that C type has (capi_header.allowed's first: a typed pointer to a struct, c_void_p for any other)."""
+    _C = rast._C
+    declared = hdr.structs()
+    assert set(declared) == set(hdr.STRUCTS)      # (gsrast_context is opaque: no body, no class)
+    for struct, cls in hdr.STRUCTS.items():
+        want, have = declared[struct], getattr(_C, cls)._fields_
+        assert [n for n, _ in want] == [n for n, _ in have], struct
+        for (name, ctype), (_, bound) in zip(want, have):
+            assert bound is hdr.allowed(ctype, _C)[0] and bound is not C.c_char_p, (struct, name, ctype, bound)
 
 
 def test_call_records_match_the_header(rast, L):
@@ -58,14 +63,8 @@ def test_call_records_match_the_header(rast, L):
     header's values.  Every render feature is a field and a bit here -- the header declares no symbol for any of them."""
     _C = rast._C
     src = open(HEADER).read()
-    for struct, cls in (("gsrast_forward_call", _C.ForwardCallStruct), ("gsrast_backward_call", _C.BackwardCallStruct)):
-        want = declared_fields(struct)
-        assert [n for n, _ in want] == [n for n, _ in cls._fields_], struct
-        for (name, ctype), (_, bound) in zip(want, cls._fields_):
-            expect = C_TYPES[ctype]
-            expect = _C._ALLOC_FN if expect is None else C.POINTER(getattr(_C, expect)) if isinstance(expect, str) else expect
-            assert bound is expect, (struct, name, ctype, bound)
-        assert want[0] == ("struct_size", "size_t") and want[1] == ("flags", "unsigned") and want[2] == ("family", "int")
+    for struct in ("gsrast_forward_call", "gsrast_backward_call"):      # (every field's name, order and type: test_every_struct_matches_the_header)
+        assert hdr.structs()[struct][:3] == [("struct_size", "size_t"), ("flags", "unsigned"), ("family", "int")]
     B = _C.BackwardCallStruct
     names = [n for n, _ in B._fields_]
     # MIN: everything up to the aux gradients; then the absgrad sink; then the two pose fields, which end the record
@@ -229,8 +228,6 @@ def test_prealloc_callback_hands_out_what_fits_and_nothing_else():
     import ctypes as C
     from diff_gaussian_rasterization_ch3 import _C
     L = _C.lib()
-    L.gsrast_alloc_prealloc.restype = C.c_void_p
-    L.gsrast_alloc_prealloc.argtypes = [C.c_void_p, C.c_size_t]
     p = _C.PreallocStruct()
     p.ptr, p.capacity = 0x1000, 4096
     assert L.gsrast_alloc_prealloc(C.addressof(p), 4096) == 0x1000 and p.requested == 4096
@@ -241,3 +238,50 @@ def test_prealloc_callback_hands_out_what_fits_and_nothing_else():
     # the sizes a caller pre-allocates are the ones the forward will ask for: monotone, 256-byte aligned arrays inside
     gb, ib = _C._state_bytes(1000, 640, 480)
     assert gb == L.gsrast_geometry_bytes(1000) and ib == L.gsrast_image_bytes(640, 480) and gb > 0 and ib > 0
+
+
+def test_launch_makes_the_device_current_once_passes_the_stream_last_and_raises_by_name(rast, monkeypatch):
+    """_C.launch over a stand-in library: the device scope is entered exactly once around the call, the stream handle of that device is the
+    last argument, zero returns normally and a non-zero code raises the RuntimeError of _err -- the symbol's name, the code and
+    gsrast_last_error's text.  _C.scratch_bytes: the size, or that error for the 0 of a refusal.  No device is touched."""
+    import torch
+    _C = rast._C
+    log = []
+
+    class Lib:
+        code = 0
+
+        def gsrast_last_error(self):
+            return b"the reason"
+
+        def __getattr__(self, name):
+            return lambda *args: log.append((name, args)) or self.code
+
+    class Scope:
+        def __init__(self, dev):
+            log.append(("scope", dev))
+
+        def __enter__(self):
+            log.append("enter")
+
+        def __exit__(self, *exc):
+            log.append("exit")
+            return False
+
+    fake, dev = Lib(), torch.device("cuda", 1)
+    monkeypatch.setattr(_C, "lib", lambda: fake)
+    monkeypatch.setattr(_C, "_on_device", Scope)
+    monkeypatch.setattr(_C, "_stream_of", lambda d: log.append(("stream", d)) or 0xABC0)
+    assert _C.launch("gsrast_some_kernel", dev, 7, None, 2.5) is None
+    assert log == [("scope", dev), "enter", ("stream", dev), ("gsrast_some_kernel", (7, None, 2.5, 0xABC0)), "exit"]
+    del log[:]
+    fake.code = -3
+    with pytest.raises(RuntimeError) as e:
+        _C.launch("gsrast_some_kernel", dev, 7)
+    assert str(e.value) == "gsrast_some_kernel failed (-3): the reason"
+    assert log == [("scope", dev), "enter", ("stream", dev), ("gsrast_some_kernel", (7, 0xABC0)), "exit"]
+    fake.code = 4096
+    assert _C.scratch_bytes("gsrast_some_scratch_bytes", 1, 2) == 4096 and log[-1] == ("gsrast_some_scratch_bytes", (1, 2))
+    fake.code = 0
+    with pytest.raises(RuntimeError, match=r"gsrast_some_scratch_bytes failed \(-1\): the reason"):
+        _C.scratch_bytes("gsrast_some_scratch_bytes", 1, 2)

@@ -88,12 +88,9 @@ def test_one_gaussian_is_zero_and_two_are_the_closed_form(scenes):
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_exported_and_bound(rast, L):
+    """(Every symbol declared, exported and bound with the header's types: tests/test_capi_abi.py.)"""
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
     for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", text), n
-        assert hasattr(raw, n) and n in rast._C.EXPORTS, n
-        assert getattr(L, n).restype is C.c_int and len(getattr(L, n).argtypes) == 11
         assert not re.fullmatch(r"gsrast_(render_)?(forward|backward)\w*", n)
     assert L.gsrast_abi_version() == 6 and re.search(r"#define\s+GSRAST_ABI_VERSION\s+6\b", text)      # additive: the version does not move
     names = [L.gsrast_profile_kernel_name(k).decode() for k in range(L.gsrast_profile_kernel_count())]

@@ -12,7 +12,6 @@ import torch
 import mcmc_math as mm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ("gsrast_mcmc_scratch_bytes", "gsrast_mcmc_plan", "gsrast_mcmc_sample", "gsrast_mcmc_relocate", "gsrast_mcmc_grow", "gsrast_mcmc_noise")
 OPACITIES = (0.006, 0.1, 0.5, 0.9, 0.99)
 
 
@@ -122,13 +121,9 @@ def test_noise_equals_gsplats_formula():
 
 
 def test_symbols_are_declared_and_exported(rast):
+    """(Every symbol declared, exported and bound with the header's types: tests/test_capi_abi.py.)"""
     L = rast._C.lib()
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsrast.h")).read(), flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n in NEW_EXPORTS:
-        assert re.search(r"\b" + n + r"\s*\(", text), n
-        assert n in rast._C.EXPORTS and hasattr(raw, n), n
-        assert getattr(L, n).argtypes is not None, n
     assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
     names = [L.gsrast_profile_kernel_name(k).decode() for k in range(L.gsrast_profile_kernel_count())]
     for n in ("mcmc_plan", "mcmc_sample", "mcmc_apply", "mcmc_noise"):

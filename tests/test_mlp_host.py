@@ -12,7 +12,6 @@ from torch import nn
 import mlp_math as mm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ("gsrast_mlp3_scratch_bytes", "gsrast_mlp3_forward", "gsrast_mlp3_backward")
 SHAPES = [(32, 9, 128, 128, 3, False), (32, 9, 128, 128, 7, False), (32, 9, 128, 128, 48, False), (32, 0, 128, 64, 1, True),
           (1, 0, 32, 32, 1, False), (64, 0, 128, 128, 64, False), (5, 3, 96, 32, 17, True)]
 
@@ -56,20 +55,13 @@ def test_relu_at_zero_passes_no_gradient():
 
 
 def test_symbols_are_declared_and_exported(rast):
+    """(Every symbol declared, exported and bound with the header's types: tests/test_capi_abi.py.)"""
     L = rast._C.lib()
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsrast.h")).read(), flags=re.S)
-    raw = C.CDLL(rast._C.LIB_PATH)
-    for n in NEW_EXPORTS:
-        assert re.search(r"\b" + n + r"\s*\(", text), n
-        assert n in rast._C.EXPORTS and hasattr(raw, n), n
-        assert getattr(L, n).argtypes is not None, n
     assert L.gsrast_abi_version() == rast._C.ABI_VERSION == 6
     assert re.search(r"#define\s+GSRAST_ABI_VERSION\s+6\b", text)
     names = [L.gsrast_profile_kernel_name(k).decode() for k in range(L.gsrast_profile_kernel_count())]
     assert names[-2:] == ["mlp_fwd", "mlp_bwd"] and names.index("mcmc_noise") == len(names) - 3      # appended: no earlier id moved
-    # the descriptor as the header declares it: 7 ints, 17 pointers
-    body = re.search(r"typedef struct \{([^}]*)\} gsrast_mlp3;", text).group(1)
-    assert [f for f, _ in rast._C.Mlp3Struct._fields_] == re.findall(r"\*?\s*\**(\w+)\s*[,;]", body)
 
 
 def test_refusals_come_before_any_device_call(rast):
