@@ -11,7 +11,7 @@ import torch
 
 import math_renderer as mr
 
-FLOOR = float(np.float32(0.000025))
+FLOOR = mr.AA_FLOOR
 
 
 def comp_of_cov2(a, b, c):
@@ -30,13 +30,6 @@ def comp(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, clamp_
     return comp_of_cov2(*pr["cov2"])
 
 
-def _rot32(q):
-    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                        2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                        2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
-
-
 def comp32(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, clamp_grad="reference"):
     """(comp, rho) in fp32, the kernel's chain: cov3D = (S R)^T (S R), J W Sigma W^T J^T with the frustum clamp, undilated c00 / c11.
     clamp_grad as in comp: "reference" = a clamped t.x / t.y is a constant of the backward, as in the kernel (preprocess_bwd_kernel)."""
@@ -49,7 +42,7 @@ def comp32(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, clam
     p = means3D.to(f)
     t = p @ V[:3, :3] + V[3, :3]
     if cov3D is None:
-        Mx = _rot32(rotations.to(f)) * (scale_modifier * scales.to(f))[:, None, :]      # (the quaternion as given, like the kernel)
+        Mx = mr.rotation_matrix(rotations.to(f)) * (scale_modifier * scales.to(f))[:, None, :]      # (the quaternion as given, like the kernel)
         Sigma = Mx @ Mx.transpose(1, 2)
     else:
         c = cov3D.to(f)

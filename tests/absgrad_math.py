@@ -19,6 +19,7 @@ import torch
 
 import aa_math
 import math_renderer as mr
+from math_renderer import t64
 
 CASES = dict(
     # four tiles, all four 8 x 8 blocks of each
@@ -32,10 +33,6 @@ CASES = dict(
 CASES["d"] = dict(CASES["a"], aux=True)
 CASES["e"] = dict(CASES["a"], aa=True)
 CASES["f"] = dict(CASES["a"], raw=True)
-
-
-def t64(a):
-    return torch.as_tensor(np.asarray(a, np.float64))
 
 
 def case_scene(scenes, c):

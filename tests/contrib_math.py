@@ -1,9 +1,9 @@
 """The per-Gaussian blend-weight statistics (include/gsrast.h: gsrast_contrib_stats; `contrib=sink` of the Python package) in torch --
 a helper of the tests, not a test.
 
-Built on tests/math_renderer.py as it stands: project() gives the screen-space quantities and the discrete decisions (visibility, tile
-rectangles), render() the depth order, final_T and its fp32-ambiguity mask.  Here the per-pair alpha, T and contribution decisions are
-recomputed in render()'s depth order and turned into the [P, 4] table
+Built on tests/math_renderer.py: render() gives the discrete decisions of the projection (visibility, tile rectangles, depth order), final_T
+and its fp32-ambiguity mask; project_gaussians and blend_pairs run again in `dtype` on those lists (`pairs`), and the weights and the
+contribution decisions they return are turned into the [P, 4] table
 
     col 0 weight_sum = sum_p m_p w_ip   col 1 weight_max = max over m_p > 0 of w_ip   col 2 pixel_count   col 3 top_count
 
@@ -11,9 +11,9 @@ with w_ip = alpha_ip T_ip for the pairs the forward blends (listed, power <= 0, 
 m_p = pixel_weights[p] clamped to [0, 1] (1 without weights).  `ambiguous` [H, W] is render()'s own mask OR'd with the pixels whose best
 and second-best w differ by less than 1e-5 relative (a top_count coin flip).
 
-`dtype`: the per-pair part -- and the continuous screen-space quantities it starts from (project_cont: the same formulas as
-math_renderer.project, checked against it in float64) -- run in this dtype; float32 is the fp32 restatement the GPU test's tolerance is
-measured with.  The discrete decisions and the depth order always come from the float64 projection, so both dtypes walk the same lists.
+`dtype`: the per-pair part -- and the continuous screen-space quantities it starts from (project_cont: math_renderer.project_gaussians
+deciding its frustum clamp in `dtype`) -- run in this dtype; float32 is the fp32 evaluation the GPU test's tolerance is measured with.
+Visibility, rectangles and the depth order always come from the float64 projection, so both dtypes walk the same lists.
 
 CASES are the shapes of tests/test_gpu_contrib.py; the seeds were picked on the CPU so that the ambiguous pixels stay under 5 %."""
 import functools
@@ -23,14 +23,11 @@ import torch
 
 import aa_math
 import math_renderer as mr
+from math_renderer import t64
 
 W_IMG, H_IMG = 70, 45      # 5 x 3 tiles, ragged in both axes: 8 x 8 wave blocks lie half outside
 CASES = dict(a=dict(kind="cluster", P=700, seed=2, k=1, V=6), b=dict(kind="sparse", P=2000, seed=4, k=2, V=6))
 TOP_GAP = 1e-5
-
-
-def t64(a):
-    return torch.as_tensor(np.asarray(a, np.float64))
 
 
 def _world(cam, px, py, z):
@@ -89,33 +86,33 @@ def case_scene(scenes, c):
     return sc, cam
 
 
+def _project(means3D, scales, rotations, cam, dtype):
+    t = dict(means3D=means3D.to(dtype), scales=scales.to(dtype), rotations=rotations.to(dtype))
+    return mr.project_gaussians(t, t64(cam["viewmatrix"]).to(dtype), t64(cam["projmatrix"]).to(dtype), None, mr.camera_cfg(cam))
+
+
 def project_cont(means3D, scales, rotations, cam, dtype):
-    """(pix [P,2], conic [P,3] = (A, B, C), cov2 = (a, b, c) dilated) in `dtype`: the formulas of math_renderer.project (EWA projection,
-    frustum clamp, + 0.3 dilation), every operand and operation in `dtype`."""
-    W, H = int(cam["image_width"]), int(cam["image_height"])
-    V = torch.as_tensor(np.asarray(cam["viewmatrix"], np.float64)).to(dtype)
-    Pm = torch.as_tensor(np.asarray(cam["projmatrix"], np.float64)).to(dtype)
-    tanx, tany = mr.F32(cam["tanfovx"]), mr.F32(cam["tanfovy"])
-    fx, fy = W / (2.0 * tanx), H / (2.0 * tany)
-    m, s, q = means3D.to(dtype), scales.to(dtype), rotations.to(dtype)
-    ph = torch.cat([m, torch.ones_like(m[:, :1])], dim=1)
-    t = (ph @ V)[:, :3]
-    hom = ph @ Pm
-    pw = 1.0 / (hom[:, 3] + mr.C_WEPS)
-    ndc = hom[:, :2] * pw[:, None]
-    pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
-    Mx = mr.rotation_matrix(q) * s[:, None, :]
-    Sigma = Mx @ Mx.transpose(1, 2)
-    tz = t[:, 2]
-    txc = torch.clamp(t[:, 0] / tz, -mr.C_LIM * tanx, mr.C_LIM * tanx) * tz
-    tyc = torch.clamp(t[:, 1] / tz, -mr.C_LIM * tany, mr.C_LIM * tany) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], dim=1).reshape(-1, 2, 3)
-    A = J @ V[:3, :3].T
-    cov2 = A @ Sigma @ A.transpose(1, 2)
-    a, b, c2 = cov2[:, 0, 0] + mr.C_DILATE, cov2[:, 0, 1], cov2[:, 1, 1] + mr.C_DILATE
-    det = a * c2 - b * b
-    return pix, torch.stack([c2 / det, -b / det, a / det], dim=1), (a, b, c2)
+    """(pix [P,2], conic [P,3] = (A, B, C), cov2 = (a, b, c) dilated) in `dtype`: math_renderer.project_gaussians deciding in `dtype`
+    (EWA projection, frustum clamp, + 0.3 dilation), every operand and operation in `dtype`."""
+    pr = _project(means3D, scales, rotations, cam, dtype)
+    return pr["pix"], pr["conic"], pr["cov2"]
+
+
+def pairs(sc, cam, dtype=torch.float64, antialiasing=False, render_out=None):
+    """(math_renderer.blend_pairs' result in `dtype` on the float64 render's lists, out = math_renderer.render's result) of one scene."""
+    m, s, q, sh, o = t64(sc["means3D"]), t64(sc["scales"]), t64(sc["rotations"]), t64(sc["shs"]), t64(sc["opacities"])
+    with torch.no_grad():
+        pr = _project(m, s, q, cam, dtype)
+        o_d = o[:, 0].to(dtype)
+        if antialiasing:
+            vidx = torch.as_tensor(mr.project(m, s, q, cam)["disc"]["vis"]).nonzero()[:, 0]
+            comp64, _ = aa_math.comp(m[vidx], s[vidx], q[vidx], cam)
+            o = o[:, 0].index_put((vidx,), o[vidx, 0] * comp64)[:, None]
+            o_d = o_d * aa_math.comp_of_cov2(*pr["cov2"])[0]
+        out = render_out if render_out is not None else mr.render(m, s, q, o, sh, int(sc.get("sh_degree", 3)), cam, sc["bg"])
+        idx = torch.as_tensor(out["order"])                        # visible Gaussians in depth order
+        g = dict(pix=pr["pix"][idx], conic=pr["conic"][idx], o=o_d[idx], z=pr["depth"][idx], col=None, rect=out["proj"]["sorted"]["rect"])
+        return mr.blend_pairs(g, None, pr["W"], pr["H"]), out
 
 
 def contrib(sc, cam, pixel_weights=None, dtype=torch.float64, antialiasing=False, render_out=None):
@@ -123,42 +120,10 @@ def contrib(sc, cam, pixel_weights=None, dtype=torch.float64, antialiasing=False
     pixel_weights: [H,W] array or None.  antialiasing: the opacity is o * comp (tests/aa_math.py).  render_out: a previous call's `out`
     for the same scene and antialiasing (the float64 render is the expensive part and does not depend on dtype or weights)."""
     P = sc["means3D"].shape[0]
-    m, s, q, sh, o = t64(sc["means3D"]), t64(sc["scales"]), t64(sc["rotations"]), t64(sc["shs"]), t64(sc["opacities"])
+    bl, out = pairs(sc, cam, dtype, antialiasing, render_out)
     with torch.no_grad():
-        pr64 = mr.project(m, s, q, cam)
-        vis = torch.as_tensor(pr64["disc"]["vis"])
-        vidx = vis.nonzero()[:, 0]
-        pix_d, conic_d, cov2_d = project_cont(m[vidx], s[vidx], q[vidx], cam, dtype)
-        if dtype == torch.float64:      # the restatement IS math_renderer's projection
-            assert float((pix_d - pr64["pix"][vidx]).abs().max()) < 1e-9 and float((conic_d / pr64["conic"][vidx] - 1.0).abs().max()) < 1e-6
-        if antialiasing:
-            comp64, _ = aa_math.comp(m[vidx], s[vidx], q[vidx], cam)
-            o = o[:, 0].index_put((vidx,), o[vidx, 0] * comp64)[:, None]
-            comp_d, _ = aa_math.comp_of_cov2(*cov2_d)
-            o_d = (t64(sc["opacities"])[vidx, 0].to(dtype) * comp_d)
-        else:
-            o_d = o[vidx, 0].to(dtype)
-        out = render_out if render_out is not None else mr.render(m, s, q, o, sh, int(sc.get("sh_degree", 3)), cam, sc["bg"])
-        W, H = pr64["W"], pr64["H"]
-        idx = torch.as_tensor(out["order"])                        # visible Gaussians in depth order
-        where = torch.full((P,), -1, dtype=torch.int64)
-        where[vidx] = torch.arange(len(vidx))
-        sel = where[idx]
-        pix, conic, od = pix_d[sel], conic_d[sel], o_d[sel]
-        rect = torch.as_tensor(pr64["disc"]["rect"])[idx]
-        ys, xs = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing="ij")
-        px, py = xs.reshape(-1, 1), ys.reshape(-1, 1)
-        tx, ty = torch.div(px, 16, rounding_mode="floor"), torch.div(py, 16, rounding_mode="floor")
-        listed = (tx >= rect[None, :, 0]) & (tx < rect[None, :, 2]) & (ty >= rect[None, :, 1]) & (ty < rect[None, :, 3])
-        dx, dy = pix[None, :, 0] - px, pix[None, :, 1] - py
-        power = -0.5 * (conic[None, :, 0] * dx * dx + conic[None, :, 2] * dy * dy) - conic[None, :, 1] * dx * dy
-        alpha = torch.clamp(od[None, :] * torch.exp(power), max=mr.C_AMAX)
-        ok = listed & (power <= 0.0) & (alpha >= mr.C_AMIN)
-        one_minus = torch.where(ok, 1.0 - alpha, torch.ones_like(alpha))
-        T_incl = torch.cumprod(one_minus, dim=1)
-        T_excl = torch.cat([torch.ones_like(T_incl[:, :1]), T_incl[:, :-1]], dim=1)      # the transmittance in front of the pair
-        live = ok & (T_incl >= mr.C_TMIN)                          # the pair that would push T below 1e-4 ends the pixel
-        w = torch.where(live, alpha * T_excl, torch.zeros_like(alpha)).to(torch.float64)      # [N, K]
+        H, W = out["ambiguous"].shape
+        idx, live, w = torch.as_tensor(out["order"]), bl["live"], bl["w"].to(torch.float64)      # [N, K]
         N, K = w.shape
         mp = torch.ones((N,), dtype=torch.float64) if pixel_weights is None else torch.clamp(t64(pixel_weights).reshape(-1), 0.0, 1.0)
         active = mp > 0.0

@@ -7,8 +7,8 @@ screen-space mean's through render()'s ndc_offset).  Anti-aliasing: the opacity 
 the activations of GaussianRasterizerRaw (means3D = xyz, rotations = normalize(rotation), scales = exp(scaling), opacities =
 sigmoid(opacity), shs = cat(features_dc, features_rest)) in front of it, gradients with respect to the raw leaves.
 
-float32 (`restate32`): the same function evaluated in float32 by tests/posegrad_math.render on the discrete decisions of its own float64
-pass (visibility, rectangles, order, thresholds, clamps) -- what fp32 rounding alone does; the floor of conftest.grad_tol and the measure of
+float32 (`restate32`): the same function -- math_renderer.project_gaussians / blend_pairs, through tests/posegrad_math.render -- in float32
+on the discrete decisions of its own float64 pass (math_renderer's decisions contract) -- what fp32 rounding alone does; the floor of conftest.grad_tol and the measure of
 the map's bar.  Its gradient of the screen-space mean: posegrad_math gives every Gaussian its own copy of projmatrix, hom = [mean, 1] @
 copy, so the copy's gradient row 3 is dL/dhom, and dL/dndc.xy = dL/dhom.xy / p_w -- what an offset added to ndc.xy (means2D) receives.
 
@@ -75,10 +75,7 @@ def _triples(F):
 
 
 def _grads(leaves, extra):
-    z = lambda x: np.zeros(tuple(x.shape)) if x.grad is None else x.grad.double().numpy()      # noqa: E731
-    g = {n: z(x) for n, x in leaves.items()}
-    g.update({n: z(x) for n, x in extra.items()})
-    return g
+    return {n: mr.grad64(x) for n, x in {**leaves, **extra}.items()}
 
 
 def evaluate64(sc, cam, F, aa=False, raw=False, colour_loss=True, feature_loss=True, g=None):
@@ -110,7 +107,7 @@ def evaluate64(sc, cam, F, aa=False, raw=False, colour_loss=True, feature_loss=T
 
 
 def restate32(sc, cam, F, g1, g0, aa=False, raw=False, colour_loss=True, feature_loss=True):
-    """The float32 restatement on its own float64 pass's decisions.  dict(map [C,H,W] float64 numpy, grads {leaf, "features"})."""
+    """The float32 evaluation on its own float64 pass's decisions.  dict(map [C,H,W] float64 numpy, grads {leaf, "features"})."""
     def run(dtype, decisions, grad):
         leaves, d = _leaves(sc, raw, dtype)
         Ft = torch.as_tensor(np.asarray(F, np.float64)).to(dtype).requires_grad_(True)

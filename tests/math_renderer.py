@@ -25,10 +25,19 @@ What is taken from the reference (cited) is only what DEFINES the function being
   * a fifth: dL/dscales is the gradient with respect to scale_modifier * scales -- computeCov3D's backward forms s = mod * scale
     and returns dL/ds (backward.cu:295, :323-325), dropping the chain rule's factor mod.  Invisible at scale_modifier = 1.
 
-Discrete decisions (culling, rectangles, depth order, the alpha / transmittance thresholds) are taken on detached float64
-values; `ambiguous` flags every pixel in which one of those decisions sits within fp32 rounding of its threshold -- the
-caller zeroes the upstream gradient there and skips those pixels, so an fp32 implementation is never asked to reproduce a coin
-flip."""
+One projection (`project_gaussians`) and one pair loop (`blend_pairs`) serve every torch helper of the rasterizer's tests: project() /
+render() here (the camera a dict of constant arrays, float64), posegrad_math.render (the camera as leaf tensors, per-Gaussian terms),
+distort_math, features_math, contrib_math, absgrad_math and aa_math.comp are adapters that add what is theirs -- the median depth and
+the statistics here, the distortion sums, the contribution table.  Both compute in the dtype of their inputs.
+
+The decisions contract.  Everything discrete lives in one flat dict of tensors: of the projection `clx`, `cly`, `sx`, `sy` (frustum
+clamp and its sign), `vis`, `idx` (the visible Gaussians in depth order: view-space z, ties by index), `rect` (their tile rectangles),
+`floor` (anti-aliasing, only with cfg["aa"]) and `colpos` (the colour clamp, only with shs); of the pair loop `listed`, `ok`, `live`.
+decisions=None: the function decides on detached values in its own dtype and returns its part of the dict.  decisions given: it
+replays them, reads only its own keys and writes nothing -- float32 on a float64 pass's decisions is what fp32 rounding alone does to
+the function (the `ref32` of conftest.grad_tol), and a second float64 pass on them is bit-equal to the first.  `ambiguous` flags every
+pixel in which a decision sits within fp32 rounding of its threshold -- the caller zeroes the upstream gradient there and skips those
+pixels, so an fp32 implementation is never asked to reproduce a coin flip."""
 from __future__ import annotations
 
 import math
@@ -40,6 +49,7 @@ PI = math.pi
 # the function's constants are the reference's fp32 literals (0.3f, 0.99f, 1.0f / 255.0f, 0.0001f, 0.0000001f, 0.2f, 1.3f)
 F32 = lambda v: float(np.float32(v))      # noqa: E731
 C_DILATE, C_AMAX, C_AMIN, C_TMIN, C_WEPS, C_NEAR, C_LIM = F32(0.3), F32(0.99), float(np.float32(1.0) / np.float32(255.0)), F32(0.0001), F32(0.0000001), F32(0.2), F32(1.3)
+AA_FLOOR = F32(0.000025)                  # the anti-aliasing factor's floor (tests/aa_math.py)
 # real spherical-harmonics normalisation constants from their closed forms, rounded to fp32 like the kernel's literals
 # (auxiliary.h:22-39 holds them as float)
 SH_C0 = F32(0.5 * math.sqrt(1.0 / PI))
@@ -78,81 +88,18 @@ def rotation_matrix(q: torch.Tensor) -> torch.Tensor:
     return torch.stack(rows, dim=1).reshape(-1, 3, 3)
 
 
-def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc_offset=None, clamp_grad="reference"):
-    """Per-Gaussian screen-space quantities (all differentiable) + the discrete ones (numpy).  clamp_grad: "reference" (the
-    frustum-clamped t.x / t.y enter J as constants, backward.cu:172-176, :262-264) or "true" (the clamp differentiated as written)."""
-    assert clamp_grad in ("reference", "true"), clamp_grad
-    W, H = int(cam["image_width"]), int(cam["image_height"])
-    V = torch.as_tensor(np.asarray(cam["viewmatrix"], np.float64))            # transposed storage: row vector @ V
-    Pm = torch.as_tensor(np.asarray(cam["projmatrix"], np.float64))
-    tanx, tany = F32(cam["tanfovx"]), F32(cam["tanfovy"])      # the entry points take float arguments
-    fx, fy = W / (2.0 * tanx), H / (2.0 * tany)                # rasterizer_impl.cu:222-223
-    ones = torch.ones_like(means3D[:, :1])
-    ph = torch.cat([means3D, ones], dim=1)
-    t = (ph @ V)[:, :3]                                                       # view space
-    hom = ph @ Pm
-    pw = 1.0 / (hom[:, 3] + C_WEPS)
-    ndc = hom[:, :2] * pw[:, None]
-    if ndc_offset is not None:
-        ndc = ndc + ndc_offset                                               # gradient sink for the screen-space mean
-    pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
-    if cov3D is None:
-        R = rotation_matrix(rotations)
-        s_mod = scale_modifier * scales
-        if scale_modifier != 1.0:
-            s_mod = _scale_grad(s_mod, 1.0 / scale_modifier)                   # dL/dscales as the reference's: of mod * scale
-        Mx = R * s_mod[:, None, :]                                            # R @ diag(s)
-        Sigma = Mx @ Mx.transpose(1, 2)
-    else:
-        c = cov3D
-        Sigma = torch.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]], dim=1).reshape(-1, 3, 3)
-    limx, limy = C_LIM * tanx, C_LIM * tany
-    tz = t[:, 2]
-    txc = torch.clamp(t[:, 0] / tz, -limx, limx) * tz
-    tyc = torch.clamp(t[:, 1] / tz, -limy, limy) * tz
-    with torch.no_grad():
-        clx, cly = (t[:, 0] / tz).abs() > limx, (t[:, 1] / tz).abs() > limy
-    if clamp_grad == "reference":
-        # x and y independently: +-lim * t.z as a constant on a clamped axis; elsewhere t.x itself, kept in the form
-        # clamp(t.x / t.z) * t.z so that the two modes are the same expression (bit-equal gradients) on unclamped rows
-        txc = torch.where(clx, txc.detach(), txc)
-        tyc = torch.where(cly, tyc.detach(), tyc)
-    zero = torch.zeros_like(tz)
-    J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], dim=1).reshape(-1, 2, 3)
-    Wr = V[:3, :3].T                                                          # world -> view rotation (math layout)
-    A = J @ Wr
-    cov2 = A @ Sigma @ A.transpose(1, 2)
-    a = cov2[:, 0, 0] + C_DILATE
-    b = cov2[:, 0, 1]
-    c2 = cov2[:, 1, 1] + C_DILATE
-    with torch.no_grad():
-        det0 = a * c2 - b * b
-        reg = det0 * det0 / (det0 * det0 + C_WEPS)
-    ar, br, cr = _scale_grad(a, reg), _scale_grad(b, reg), _scale_grad(c2, reg)
-    det = ar * cr - br * br
-    conic = torch.stack([cr / det, -br / det, ar / det], dim=1)
-    # discrete part
-    with torch.no_grad():
-        mid = 0.5 * (a + c2)
-        lam = mid + torch.sqrt(torch.clamp(mid * mid - det, min=0.1))
-        r_real = 3.0 * torch.sqrt(lam)
-        radius = torch.ceil(r_real)
-        vis = (tz > C_NEAR) & (det != 0.0)
-        gx, gy = (W + 15) // 16, (H + 15) // 16
-        trunc = lambda v: torch.trunc(v)      # noqa: E731  (int) cast
-        x0 = torch.clamp(trunc((pix[:, 0] - radius) / 16.0), 0, gx); x1 = torch.clamp(trunc((pix[:, 0] + radius + 15.0) / 16.0), 0, gx)
-        y0 = torch.clamp(trunc((pix[:, 1] - radius) / 16.0), 0, gy); y1 = torch.clamp(trunc((pix[:, 1] + radius + 15.0) / 16.0), 0, gy)
-        tiles = (x1 - x0) * (y1 - y0)
-        vis = vis & (tiles > 0)
-        # how close the discrete decisions are to flipping under fp32 rounding of their inputs
-        frac = torch.abs(r_real - torch.round(r_real))
-        edge = lambda v: torch.abs(v - torch.round(v))      # noqa: E731
-        rect_margin = torch.minimum(torch.minimum(edge((pix[:, 0] - radius) / 16.0), edge((pix[:, 0] + radius + 15.0) / 16.0)),
-                                    torch.minimum(edge((pix[:, 1] - radius) / 16.0), edge((pix[:, 1] + radius + 15.0) / 16.0)))
-    disc = dict(vis=vis.numpy(), radius=(radius * vis).numpy().astype(np.int64), rect=torch.stack([x0, y0, x1, y1], 1).numpy().astype(np.int64),
-                tiles=(tiles * vis).numpy().astype(np.int64), radius_margin=frac.numpy(), rect_margin=rect_margin.numpy(),
-                clamped=(clx | cly).numpy())
-    return dict(pix=pix, conic=conic, depth=tz, cov2=(a, b, c2), Sigma=Sigma, disc=disc, W=W, H=H)
+def t64(a):
+    return torch.as_tensor(np.asarray(a, np.float64))
+
+
+def grad64(x: torch.Tensor) -> np.ndarray:
+    """x.grad as float64 numpy; zeros where autograd never reached x."""
+    return np.zeros(tuple(x.shape)) if x.grad is None else x.grad.double().numpy()
+
+
+def camera_cfg(cam, **more):
+    """The constants of a camera as project_gaussians takes them: sizes, and the focal tangents as floats like the entry points' arguments."""
+    return dict(W=int(cam["image_width"]), H=int(cam["image_height"]), tanx=F32(cam["tanfovx"]), tany=F32(cam["tanfovy"]), **more)
 
 
 def _scale_grad(x: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
@@ -161,6 +108,196 @@ def _scale_grad(x: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
     if y.requires_grad:
         y.register_hook(lambda g: g * f)
     return y
+
+
+def _own_copies(x, P):
+    e = x.unsqueeze(0).expand((P,) + tuple(x.shape)) * 1.0      # one row per Gaussian, each with its own gradient
+    if e.requires_grad:
+        e.retain_grad()
+    return e
+
+
+def _frustum_clamped(u, tz, lim, D, axis, decide, clamp_grad):
+    """t.x (or t.y) as it enters J: itself, in the form (u / t.z) * t.z, or +-lim * t.z outside 1.3 x the field of view."""
+    r = u / tz
+    if decide:
+        D["cl" + axis], D["s" + axis] = r.detach().abs() > lim, torch.sign(r.detach())
+    c = D["s" + axis].to(u.dtype) * lim * tz
+    return torch.where(D["cl" + axis], c.detach() if clamp_grad == "reference" else c, r * tz)
+
+
+def project_gaussians(t, V, Pm, campos, cfg, *, ndc_offset=None, clamp_grad="reference", per=False, halve=None, decisions=None):
+    """THE projection, in the dtype of its inputs.  t: dict of tensors -- means3D [P,3], (scales, rotations) or cov3D [P,6], and optionally
+    opacities [P,1] and (shs [P,M,3] or rgb [P,3]).  V, Pm [4,4], campos [3] (None without shs): the camera as tensors, leaves or not.
+    cfg: camera_cfg's constants + scale_modifier, deg, aa (each optional).  ndc_offset: the means2D sink added to ndc.xy.  clamp_grad:
+    "reference" (a frustum-clamped t.x / t.y enters J as a constant, backward.cu:172-176, :262-264) or "true".  per: every Gaussian gets its
+    own copy of the three camera tensors ([P,4,4], [P,4,4], [P,3], `per` in the result), whose .grad rows are the Gaussians' terms of the
+    camera's gradient.  halve="JW": the gradient reaching viewmatrix through the rotation inside J W times 0.5 (a wrong reference on purpose).
+    decisions: None = decide here (the module docstring's contract), or an earlier pass's dict.
+    Returns dict(pix [P,2], conic [P,3], depth [P], cov2 = (a, b, c) dilated, Sigma [P,3,3], o [P], col [P,3], col_margin, per, W, H,
+    sorted = the visible Gaussians' (pix, conic, o, col, z, rect) in depth order, decisions, disc = the discrete quantities as numpy (deciding
+    pass only): vis, radius, rect, tiles, radius_margin, rect_margin, clamped)."""
+    assert clamp_grad in ("reference", "true") and halve in (None, "JW"), (clamp_grad, halve)
+    m = t["means3D"]
+    dt, P, W, H = m.dtype, m.shape[0], cfg["W"], cfg["H"]
+    decide = decisions is None
+    D = {} if decide else decisions
+    fx, fy = W / (2.0 * cfg["tanx"]), H / (2.0 * cfg["tany"])                # rasterizer_impl.cu:222-223
+    ph = torch.cat([m, torch.ones_like(m[:, :1])], dim=1)
+    if per:
+        Ve, Pe, Ce = _own_copies(V, P), _own_copies(Pm, P), _own_copies(campos, P)
+        tv = torch.einsum("pr,prc->pc", ph, Ve)[:, :3]
+        hom = torch.einsum("pr,prc->pc", ph, Pe)
+        Wr = Ve[:, :3, :3].transpose(1, 2)
+    else:
+        Ve, Pe, Ce = None, None, campos
+        tv = (ph @ V)[:, :3]                                                  # transposed storage: row vector @ V; view space
+        hom = ph @ Pm
+        Wr = V[:3, :3].T                                                      # world -> view rotation (math layout)
+    pw = 1.0 / (hom[:, 3] + C_WEPS)
+    ndc = hom[:, :2] * pw[:, None]
+    if ndc_offset is not None:
+        ndc = ndc + ndc_offset                                               # gradient sink for the screen-space mean
+    pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
+    if "cov3D" in t:
+        c = t["cov3D"]
+        Sigma = torch.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]], dim=1).reshape(-1, 3, 3)
+    else:
+        mod = cfg.get("scale_modifier", 1.0)
+        s_mod = mod * t["scales"]
+        if mod != 1.0:
+            s_mod = _scale_grad(s_mod, 1.0 / mod)                             # dL/dscales as the reference's: of mod * scale
+        Mx = rotation_matrix(t["rotations"]) * s_mod[:, None, :]              # R @ diag(s)
+        Sigma = Mx @ Mx.transpose(1, 2)
+    tz = tv[:, 2]
+    # (x entirely before y: t.z's gradient is a sum of nearly cancelling terms that autograd adds in reverse order of creation)
+    txc = _frustum_clamped(tv[:, 0], tz, C_LIM * cfg["tanx"], D, "x", decide, clamp_grad)
+    tyc = _frustum_clamped(tv[:, 1], tz, C_LIM * cfg["tany"], D, "y", decide, clamp_grad)
+    zero = torch.zeros_like(tz)
+    J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], dim=1).reshape(-1, 2, 3)
+    if halve == "JW":
+        Wr = _scale_grad(Wr, 0.5)
+    A = J @ Wr
+    cov2 = A @ Sigma @ A.transpose(1, 2)
+    c00, c11 = cov2[:, 0, 0], cov2[:, 1, 1]
+    a, b, c2 = c00 + C_DILATE, cov2[:, 0, 1], c11 + C_DILATE
+    with torch.no_grad():
+        det0 = a * c2 - b * b
+        reg = det0 * det0 / (det0 * det0 + C_WEPS)
+    ar, br, cr = _scale_grad(a, reg), _scale_grad(b, reg), _scale_grad(c2, reg)
+    det = ar * cr - br * br
+    conic = torch.stack([cr / det, -br / det, ar / det], dim=1)
+    disc = None
+    if decide:
+        with torch.no_grad():
+            mid = 0.5 * (a + c2)
+            r_real = 3.0 * torch.sqrt(mid + torch.sqrt(torch.clamp(mid * mid - det, min=0.1)))
+            radius = torch.ceil(r_real)
+            gx, gy = (W + 15) // 16, (H + 15) // 16
+            trunc = torch.trunc                                               # (int) cast
+            x0 = torch.clamp(trunc((pix[:, 0] - radius) / 16.0), 0, gx); x1 = torch.clamp(trunc((pix[:, 0] + radius + 15.0) / 16.0), 0, gx)
+            y0 = torch.clamp(trunc((pix[:, 1] - radius) / 16.0), 0, gy); y1 = torch.clamp(trunc((pix[:, 1] + radius + 15.0) / 16.0), 0, gy)
+            tiles = (x1 - x0) * (y1 - y0)
+            vis = (tz > C_NEAR) & (det != 0.0) & (tiles > 0)
+            # depth order as the 64-bit key sort gives it inside any tile: by view-space z, ties by index (stable)
+            idx = torch.nonzero(vis)[:, 0]
+            idx = idx[torch.as_tensor(np.lexsort((idx.numpy(), tz[idx].numpy())))]
+            rect = torch.stack([x0, y0, x1, y1], 1)
+            D.update(vis=vis, idx=idx, rect=rect[idx])
+            # how close the discrete decisions are to flipping under fp32 rounding of their inputs
+            edge = lambda v: torch.abs(v - torch.round(v))      # noqa: E731
+            rect_margin = torch.minimum(torch.minimum(edge((pix[:, 0] - radius) / 16.0), edge((pix[:, 0] + radius + 15.0) / 16.0)),
+                                        torch.minimum(edge((pix[:, 1] - radius) / 16.0), edge((pix[:, 1] + radius + 15.0) / 16.0)))
+            disc = dict(vis=vis.numpy(), radius=(radius * vis).numpy().astype(np.int64), rect=rect.numpy().astype(np.int64),
+                        tiles=(tiles * vis).numpy().astype(np.int64), radius_margin=edge(r_real).numpy(), rect_margin=rect_margin.numpy(),
+                        clamped=(D["clx"] | D["cly"]).numpy())
+    o = col = col_margin = None
+    if "opacities" in t:
+        o = t["opacities"].reshape(-1)
+        if cfg.get("aa"):                                                     # o * sqrt(max(AA_FLOOR, det(cov2D) / det(cov2D + 0.3 I)))
+            rho = (c00 * c11 - b * b) / (a * c2 - b * b)
+            if decide:
+                D["floor"] = (rho <= AA_FLOOR).detach()
+            o = o * torch.where(D["floor"], torch.full_like(rho, AA_FLOOR ** 0.5), torch.sqrt(torch.where(D["floor"], torch.ones_like(rho), rho)))
+    if "rgb" in t:
+        col, col_margin = t["rgb"], torch.ones((P,), dtype=dt)
+    elif "shs" in t:
+        d = m - Ce
+        raw = sh_colour(int(cfg.get("deg", 0)), t["shs"], d / torch.linalg.norm(d, dim=1, keepdim=True)) + 0.5
+        if decide:
+            D["colpos"] = (raw > 0.0).detach()
+        col = torch.where(D["colpos"], raw, torch.zeros_like(raw))           # max(SH + 0.5, 0)
+        col_margin = raw.detach().abs().min(dim=1).values
+    idx = D["idx"]
+    take = lambda x: None if x is None else x[idx]      # noqa: E731
+    return dict(pix=pix, conic=conic, depth=tz, cov2=(a, b, c2), Sigma=Sigma, o=o, col=col, col_margin=col_margin, per=(Ve, Pe, Ce) if per else None,
+                sorted=dict(pix=pix[idx], conic=conic[idx], o=take(o), col=take(col), z=tz[idx], rect=D["rect"]), decisions=D, disc=disc, W=W, H=H)
+
+
+def clamp_passthrough(alpha: torch.Tensor, hi: float) -> torch.Tensor:
+    return alpha + (torch.clamp(alpha, max=hi) - alpha).detach()
+
+
+def blend_pairs(g, bg, W, H, *, decisions=None, z0_relative=False, fp32_eps=4e-6):
+    """THE pair loop, in the dtype of its inputs.  g: project_gaussians' `sorted` -- Gaussians in depth order (pix [K,2], conic [K,3], o [K],
+    z [K], rect [K,4] tile rectangles, col [K,3] or None); pixels row-major, N = H W.  decisions: None = decide here (listed, ok, live; the
+    module docstring's contract) or an earlier pass's.  z0_relative: `z_rel` is the depth relative to z0, the depth of the first Gaussian
+    listed for the pixel's tile (the kernels' association); otherwise z itself.
+    Returns dict(w [N,K] = alpha T the blending weights, live, ok, listed, T_incl, T_excl, power, alpha_raw [N,K], T_final [N], z_rel,
+    color [3,H,W] (col given), acc_depth [H,W], alpha [H,W], decisions, ambiguous [N] bool (deciding pass: a decision within fp32 rounding
+    of its threshold))."""
+    pix, conic, o, z, col = g["pix"], g["conic"], g["o"], g["z"], g["col"]
+    dt = pix.dtype
+    decide = decisions is None
+    D = {} if decide else decisions
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+    px, py = xs.reshape(-1, 1), ys.reshape(-1, 1)                            # [N, 1]
+    dx, dy = pix[None, :, 0] - px, pix[None, :, 1] - py
+    power = -0.5 * (conic[None, :, 0] * dx * dx + conic[None, :, 2] * dy * dy) - conic[None, :, 1] * dx * dy
+    alpha_raw = o[None, :] * torch.exp(power)
+    alpha = clamp_passthrough(alpha_raw, C_AMAX)
+    if decide:
+        with torch.no_grad():
+            rect = g["rect"]
+            tx, ty = torch.div(px, 16, rounding_mode="floor"), torch.div(py, 16, rounding_mode="floor")
+            D["listed"] = (tx >= rect[None, :, 0]) & (tx < rect[None, :, 2]) & (ty >= rect[None, :, 1]) & (ty < rect[None, :, 3])   # [N, K]
+            D["ok"] = D["listed"] & (power <= 0.0) & (alpha >= C_AMIN)
+    listed, ok = D["listed"], D["ok"]
+    one_minus = torch.where(ok, 1.0 - alpha, torch.ones_like(alpha))
+    T_incl = torch.cumprod(one_minus, dim=1)
+    T_excl = T_incl / one_minus                                              # the transmittance in front of the pair
+    amb_pix = None
+    if decide:
+        with torch.no_grad():
+            # the pair that would push T below 1e-4 ends the pixel: it is finished at the FIRST such pair (T_incl is monotone)
+            D["live"] = ok & (T_incl >= C_TMIN)
+            # ambiguity of the decisions under fp32 rounding (relative eps on alpha and T, absolute on power)
+            scale_q = conic[None, :, 0].abs() * dx * dx + conic[None, :, 2].abs() * dy * dy + 2 * conic[None, :, 1].abs() * (dx * dy).abs()
+            amb = listed & ((power.abs() <= fp32_eps * (1.0 + scale_q)) |
+                            ((power <= 0.0) & ((alpha_raw / C_AMIN - 1.0).abs() <= 8 * fp32_eps * (1.0 + scale_q))))
+            amb = amb | (ok & ((T_incl / C_TMIN - 1.0).abs() <= 64 * fp32_eps))
+            amb_pix = amb.any(dim=1)
+    live = D["live"]
+    w = torch.where(live, alpha * T_excl, torch.zeros_like(alpha))
+    colour = None if col is None else w @ col                                # [N, 3]
+    T_final = torch.where(live, one_minus, torch.ones_like(alpha)).prod(dim=1)
+    if col is not None:
+        colour = (colour + T_final[:, None] * t64(bg).to(dt)[None, :]).T.reshape(3, H, W)
+    z_rel = z[None, :]
+    if z0_relative:
+        with torch.no_grad():
+            z0 = torch.where(listed.any(dim=1), z.detach()[torch.argmax(listed.to(torch.int8), dim=1)], torch.zeros((), dtype=dt))
+        z_rel = z_rel - z0[:, None]
+    return dict(w=w, live=live, ok=ok, listed=listed, T_incl=T_incl, T_excl=T_excl, power=power, alpha_raw=alpha_raw, T_final=T_final, z_rel=z_rel,
+                color=colour, acc_depth=(w @ z).reshape(H, W), alpha=(1.0 - T_final).reshape(H, W), decisions=D, ambiguous=amb_pix)
+
+
+def project(means3D, scales, rotations, cam, scale_modifier=1.0, cov3D=None, ndc_offset=None, clamp_grad="reference", deg=0, **blended):
+    """project_gaussians in float64 for a camera given as a dict of arrays (constants), deciding here.  `blended`: opacities, shs or rgb."""
+    t = dict(means3D=means3D, **blended)
+    t.update(dict(scales=scales, rotations=rotations) if cov3D is None else dict(cov3D=cov3D))
+    return project_gaussians(t, t64(cam["viewmatrix"]), t64(cam["projmatrix"]), t64(cam["campos"]) if "shs" in t else None,
+                             camera_cfg(cam, scale_modifier=scale_modifier, deg=deg), ndc_offset=ndc_offset, clamp_grad=clamp_grad)
 
 
 def _tile_list_max(rect, W, H):
@@ -172,79 +309,28 @@ def _tile_list_max(rect, W, H):
     return int(n.max())
 
 
-def clamp_passthrough(alpha: torch.Tensor, hi: float) -> torch.Tensor:
-    return alpha + (torch.clamp(alpha, max=hi) - alpha).detach()
-
-
 def render(means3D, scales, rotations, opacities, shs, sh_degree, cam, bg, *, colors_precomp=None, cov3D=None,
            scale_modifier=1.0, ndc_offset=None, fp32_eps=4e-6, clamp_grad="reference"):
-    """Returns dict(color [3,H,W], depth [H,W], final_T [H,W], ambiguous [H,W] bool, proj=...).  clamp_grad: see project()."""
-    pr = project(means3D, scales, rotations, cam, scale_modifier, cov3D, ndc_offset, clamp_grad)
-    W, H = pr["W"], pr["H"]
-    vis = torch.as_tensor(pr["disc"]["vis"])
-    if colors_precomp is None:
-        campos = torch.as_tensor(np.asarray(cam["campos"], np.float64))
-        d = means3D - campos
-        d = d / torch.linalg.norm(d, dim=1, keepdim=True)
-        raw = sh_colour(int(sh_degree), shs, d) + 0.5
-        col = torch.clamp(raw, min=0.0)
-        col_margin = raw.detach().abs().min(dim=1).values
-    else:
-        col = colors_precomp
-        col_margin = torch.full((means3D.shape[0],), 1.0, dtype=torch.float64)
-    idx = torch.nonzero(vis)[:, 0]
-    # depth order as the 64-bit key sort gives it inside any tile: by view-space z, ties by index (stable)
-    z = pr["depth"].detach()[idx]
-    order = torch.as_tensor(np.lexsort((idx.numpy(), z.numpy())))
-    idx = idx[order]
-    zs = z[order]
-    gap = (zs[1:] - zs[:-1]).min().item() if len(zs) > 1 else 1.0
-    pix, conic, o = pr["pix"][idx], pr["conic"][idx], opacities.reshape(-1)[idx]
-    colk, depk = col[idx], pr["depth"][idx]
-    rect = torch.as_tensor(pr["disc"]["rect"])[idx]
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
-    px, py = xs.reshape(-1, 1), ys.reshape(-1, 1)                            # [N, 1]
-    tx, ty = torch.div(px, 16, rounding_mode="floor"), torch.div(py, 16, rounding_mode="floor")
-    listed = (tx >= rect[None, :, 0]) & (tx < rect[None, :, 2]) & (ty >= rect[None, :, 1]) & (ty < rect[None, :, 3])   # [N, K]
-    dx = pix[None, :, 0] - px
-    dy = pix[None, :, 1] - py
-    power = -0.5 * (conic[None, :, 0] * dx * dx + conic[None, :, 2] * dy * dy) - conic[None, :, 1] * dx * dy
-    G = torch.exp(power)
-    alpha_raw = o[None, :] * G
-    alpha = clamp_passthrough(alpha_raw, C_AMAX)
+    """Returns dict(color [3,H,W], depth [H,W], final_T [H,W], ambiguous [H,W] bool, proj=...).  clamp_grad: see project_gaussians()."""
+    pr = project(means3D, scales, rotations, cam, scale_modifier, cov3D, ndc_offset, clamp_grad, int(sh_degree), opacities=opacities,
+                 **(dict(shs=shs) if colors_precomp is None else dict(rgb=colors_precomp)))
+    W, H, g, idx = pr["W"], pr["H"], pr["sorted"], pr["decisions"]["idx"]
+    bl = blend_pairs(g, bg, W, H, fp32_eps=fp32_eps)
+    live, T_incl, T_excl = bl["live"], bl["T_incl"], bl["T_excl"]
     with torch.no_grad():
-        ok = listed & (power <= 0.0) & (alpha >= C_AMIN)
-    one_minus = torch.where(ok, 1.0 - alpha, torch.ones_like(alpha))
-    T_incl = torch.cumprod(one_minus, dim=1)
-    T_excl = T_incl / one_minus
-    with torch.no_grad():
-        live = ok & (T_incl >= C_TMIN)                                         # the pair that would push T below 1e-4 ends the pixel
-        # a pixel is finished at the FIRST such pair; later pairs are dropped even though T_incl is monotone anyway
-        # ambiguity of the decisions under fp32 rounding (relative eps on alpha and T, absolute on power)
-        scale_q = (conic[None, :, 0].abs() * dx * dx + conic[None, :, 2].abs() * dy * dy + 2 * conic[None, :, 1].abs() * (dx * dy).abs())
-        amb = listed & ((power.abs() <= fp32_eps * (1.0 + scale_q)) |
-                        ((power <= 0.0) & ((alpha_raw / C_AMIN - 1.0).abs() <= 8 * fp32_eps * (1.0 + scale_q))))
-        amb = amb | (ok & ((T_incl / C_TMIN - 1.0).abs() <= 64 * fp32_eps))
-        T_before_first_dead = T_incl
-        amb_pix = amb.any(dim=1)
-    w = torch.where(live, alpha * T_excl, torch.zeros_like(alpha))          # blending weights
-    colour = w @ colk                                                        # [N, 3]
-    T_final = torch.where(live, one_minus, torch.ones_like(alpha)).prod(dim=1)
-    bgt = torch.as_tensor(np.asarray(bg, np.float64))
-    colour = colour + T_final[:, None] * bgt[None, :]
-    with torch.no_grad():
+        zs = g["z"]
+        gap = (zs[1:] - zs[:-1]).min().item() if len(zs) > 1 else 1.0
         # median depth: the contributing pair at which T crosses 0.5 (forward.cu:368-372); default 15
         T_after = torch.where(live, T_incl, torch.full_like(T_incl, 2.0))
         T_prev = torch.where(live, T_excl, torch.full_like(T_incl, -1.0))
         cross = live & (T_prev > 0.5) & (T_after < 0.5)
         has = cross.any(dim=1)
         first = torch.argmax(cross.to(torch.int8), dim=1)
-        depth = torch.where(has, depk.detach()[first], torch.full((H * W,), 15.0, dtype=torch.float64))
-        amb_pix = amb_pix | ((live & (((T_prev - 0.5).abs() <= 64 * fp32_eps) | ((T_after - 0.5).abs() <= 64 * fp32_eps))).any(dim=1))
-        n_live = live.sum(dim=1)
-    return dict(color=colour.T.reshape(3, H, W), depth=depth.reshape(H, W), final_T=T_final.reshape(H, W),
+        depth = torch.where(has, zs[first], torch.full((H * W,), 15.0, dtype=torch.float64))
+        amb_pix = bl["ambiguous"] | ((live & (((T_prev - 0.5).abs() <= 64 * fp32_eps) | ((T_after - 0.5).abs() <= 64 * fp32_eps))).any(dim=1))
+    return dict(color=bl["color"], depth=depth.reshape(H, W), final_T=bl["T_final"].reshape(H, W),
                 ambiguous=amb_pix.reshape(H, W).numpy(), proj=pr, order=idx.numpy(), min_depth_gap=gap,
-                colour_clamp_margin=col_margin.numpy(), n_live=n_live.reshape(H, W).numpy(),
-                clamped_pairs=int((live & (alpha_raw > C_AMAX)).sum().item()),
-                tile_list_max=_tile_list_max(rect.numpy(), W, H),
-                stopped=((ok & ~live).any(dim=1)).reshape(H, W).numpy())
+                colour_clamp_margin=pr["col_margin"].numpy(), n_live=live.sum(dim=1).reshape(H, W).numpy(),
+                clamped_pairs=int((live & (bl["alpha_raw"] > C_AMAX)).sum().item()),
+                tile_list_max=_tile_list_max(g["rect"].numpy().astype(np.int64), W, H),
+                stopped=((bl["ok"] & ~live).any(dim=1)).reshape(H, W).numpy(), w=bl["w"], live=live)

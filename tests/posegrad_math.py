@@ -1,8 +1,8 @@
 """The renderer with the CAMERA as differentiable input, in torch -- a helper of the tests, not a test.
 
-tests/math_renderer.py turns viewmatrix / projmatrix / campos into constants through numpy; here they are three leaf tensors
-(include/gsrast.h: GSRAST_RENDER_POSEGRAD treats them as three independent inputs) and autograd of the forward below gives their
-gradients.  The conventions are math_renderer's (its docstring): row-vector matrices stored transposed, t = [mean, 1] @ viewmatrix,
+tests/math_renderer.py's render() turns viewmatrix / projmatrix / campos into constants through numpy; here they are three leaf tensors
+(include/gsrast.h: GSRAST_RENDER_POSEGRAD treats them as three independent inputs) given to the same two functions
+(math_renderer.project_gaussians, blend_pairs), and autograd gives their gradients.  The conventions are math_renderer's (its docstring): row-vector matrices stored transposed, t = [mean, 1] @ viewmatrix,
 hom = [mean, 1] @ projmatrix; the 0.99 alpha clamp straight-through; no gradient through the median depth (not rendered here); a
 frustum-clamped t.x / t.y a constant inside J (clamp_grad="reference"; "true" differentiates the clamp as written);
 det^2 / (det^2 + 1e-7) in the conic chain; dL/dscales with respect to scale_modifier * scales.  tanfovx / tanfovy are constants.
@@ -12,9 +12,8 @@ Per-Gaussian contributions: every Gaussian gets its OWN copy of the three camera
 after a backward their .grad rows are the Gaussians' terms of the three sums -- what the tests need to assert non-vacuity and to form
 sum_i |term_i|.
 
-fp32: render(..., decisions=<the fp64 pass's>) evaluates the same expressions in the dtype of its inputs on the discrete decisions
-(visibility, rectangles, order, the alpha / transmittance thresholds, clamps, the anti-aliasing floor) of the fp64 pass -- the `ref32` of
-conftest.grad_tol: what fp32 rounding alone does to these sums.
+fp32: render(..., decisions=<the fp64 pass's>) evaluates the same expressions in the dtype of its inputs on the discrete decisions of the
+fp64 pass (math_renderer's decisions contract) -- the `ref32` of conftest.grad_tol: what fp32 rounding alone does to these sums.
 
 halve: "JW" multiplies the gradient that reaches viewmatrix through the rotation inside T = J W by 0.5 -- a wrong reference on purpose,
 for the test that shows the bar biting."""
@@ -23,15 +22,13 @@ import functools
 import numpy as np
 import torch
 
-import aa_math
 import math_renderer as mr
 
 
 def cfg_of(cam, sc, c=None, aa=False):
     """The constants of a render: sizes, focal tangents, background, SH degree, scale_modifier, anti-aliasing."""
-    return dict(W=int(cam["image_width"]), H=int(cam["image_height"]), tanx=mr.F32(cam["tanfovx"]), tany=mr.F32(cam["tanfovy"]),
-                bg=np.asarray(sc["bg"], np.float64), deg=int(c["deg"]) if c is not None else int(sc.get("sh_degree", 0)),
-                scale_modifier=float(cam.get("scale_modifier", 1.0)), aa=bool(aa))
+    return mr.camera_cfg(cam, bg=np.asarray(sc["bg"], np.float64), deg=int(c["deg"]) if c is not None else int(sc.get("sh_degree", 0)),
+                         scale_modifier=float(cam.get("scale_modifier", 1.0)), aa=bool(aa))
 
 
 def camera_leaves(cam, dtype=torch.float64):
@@ -39,124 +36,16 @@ def camera_leaves(cam, dtype=torch.float64):
     return tuple(torch.as_tensor(np.asarray(cam[k], np.float64)).to(dtype).requires_grad_(True) for k in ("viewmatrix", "projmatrix", "campos"))
 
 
-def _own_copies(x, P):
-    e = x.unsqueeze(0).expand((P,) + tuple(x.shape)) * 1.0      # one row per Gaussian, each with its own gradient
-    if e.requires_grad:
-        e.retain_grad()
-    return e
-
-
-def render(t, V, Pm, C, cfg, decisions=None, clamp_grad="reference", halve=None, fp32_eps=4e-6):
+def render(t, V, Pm, C, cfg, decisions=None, clamp_grad="reference", halve=None, fp32_eps=4e-6, per=True):
     """t: dict of tensors -- means3D [P,3], opacities [P,1] and (shs [P,M,3], scales, rotations) or (rgb [P,3], cov3D [P,6]).
-    Returns dict(color [3,H,W], acc_depth [H,W], alpha [H,W], per=(Ve, Pe, Ce), decisions, ambiguous [H,W], n_live, clamped [P], vis [P])."""
-    assert clamp_grad in ("reference", "true") and halve in (None, "JW")
-    m = t["means3D"]
-    dt, P, W, H = m.dtype, m.shape[0], cfg["W"], cfg["H"]
-    first = decisions is None
-    D = {} if first else decisions
-    Ve, Pe, Ce = _own_copies(V, P), _own_copies(Pm, P), _own_copies(C, P)
-    fx, fy = W / (2.0 * cfg["tanx"]), H / (2.0 * cfg["tany"])
-    ph = torch.cat([m, torch.ones_like(m[:, :1])], dim=1)
-    tv = torch.einsum("pr,prc->pc", ph, Ve)[:, :3]
-    hom = torch.einsum("pr,prc->pc", ph, Pe)
-    pw = 1.0 / (hom[:, 3] + mr.C_WEPS)
-    ndc = hom[:, :2] * pw[:, None]
-    pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
-    if "cov3D" in t:
-        c6 = t["cov3D"]
-        Sigma = torch.stack([c6[:, 0], c6[:, 1], c6[:, 2], c6[:, 1], c6[:, 3], c6[:, 4], c6[:, 2], c6[:, 4], c6[:, 5]], dim=1).reshape(-1, 3, 3)
-    else:
-        s_mod = cfg["scale_modifier"] * t["scales"]
-        if cfg["scale_modifier"] != 1.0:
-            s_mod = mr._scale_grad(s_mod, 1.0 / cfg["scale_modifier"])
-        Mx = mr.rotation_matrix(t["rotations"]) * s_mod[:, None, :]
-        Sigma = Mx @ Mx.transpose(1, 2)
-    limx, limy = mr.C_LIM * cfg["tanx"], mr.C_LIM * cfg["tany"]
-    tz = tv[:, 2]
-    rx, ry = tv[:, 0] / tz, tv[:, 1] / tz
-    if first:
-        with torch.no_grad():
-            D["clx"], D["cly"] = rx.abs() > limx, ry.abs() > limy
-            D["sx"], D["sy"] = torch.sign(rx), torch.sign(ry)
-    cx, cy = D["sx"].to(dt) * limx * tz, D["sy"].to(dt) * limy * tz
-    if clamp_grad == "reference":
-        cx, cy = cx.detach(), cy.detach()
-    txc, tyc = torch.where(D["clx"], cx, rx * tz), torch.where(D["cly"], cy, ry * tz)
-    zero = torch.zeros_like(tz)
-    J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], dim=1).reshape(-1, 2, 3)
-    Wr = Ve[:, :3, :3].transpose(1, 2)
-    if halve == "JW":
-        Wr = mr._scale_grad(Wr, 0.5)
-    A = J @ Wr
-    cov2 = A @ Sigma @ A.transpose(1, 2)
-    c00, c11 = cov2[:, 0, 0], cov2[:, 1, 1]
-    a, b, c2 = c00 + mr.C_DILATE, cov2[:, 0, 1], c11 + mr.C_DILATE
-    with torch.no_grad():
-        det0 = a * c2 - b * b
-        reg = det0 * det0 / (det0 * det0 + mr.C_WEPS)
-    ar, br, cr = mr._scale_grad(a, reg), mr._scale_grad(b, reg), mr._scale_grad(c2, reg)
-    det = ar * cr - br * br
-    conic = torch.stack([cr / det, -br / det, ar / det], dim=1)
-    if first:
-        with torch.no_grad():
-            mid = 0.5 * (a + c2)
-            radius = torch.ceil(3.0 * torch.sqrt(mid + torch.sqrt(torch.clamp(mid * mid - det, min=0.1))))
-            gx, gy = (W + 15) // 16, (H + 15) // 16
-            x0 = torch.clamp(torch.trunc((pix[:, 0] - radius) / 16.0), 0, gx); x1 = torch.clamp(torch.trunc((pix[:, 0] + radius + 15.0) / 16.0), 0, gx)
-            y0 = torch.clamp(torch.trunc((pix[:, 1] - radius) / 16.0), 0, gy); y1 = torch.clamp(torch.trunc((pix[:, 1] + radius + 15.0) / 16.0), 0, gy)
-            vis = (tz > mr.C_NEAR) & (det != 0.0) & ((x1 - x0) * (y1 - y0) > 0)
-            idx = torch.nonzero(vis)[:, 0]
-            z = tz[idx]
-            idx = idx[torch.as_tensor(np.lexsort((idx.numpy(), z.numpy())))]
-            D.update(vis=vis, idx=idx, rect=torch.stack([x0, y0, x1, y1], 1)[idx])
-    idx, rect = D["idx"], D["rect"]
-    o = t["opacities"].reshape(-1)
-    if cfg["aa"]:
-        rho = (c00 * c11 - b * b) / (a * c2 - b * b)
-        if first:
-            D["floor"] = (rho <= aa_math.FLOOR).detach()
-        o = o * torch.where(D["floor"], torch.full_like(rho, aa_math.FLOOR ** 0.5), torch.sqrt(torch.where(D["floor"], torch.ones_like(rho), rho)))
-    if "rgb" in t:
-        col = t["rgb"]
-    else:
-        d = m - Ce
-        raw = mr.sh_colour(cfg["deg"], t["shs"], d / torch.linalg.norm(d, dim=1, keepdim=True)) + 0.5
-        if first:
-            D["colpos"] = (raw > 0.0).detach()
-        col = torch.where(D["colpos"], raw, torch.zeros_like(raw))
-    pixk, conk, ok_o, colk, depk = pix[idx], conic[idx], o[idx], col[idx], tz[idx]
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
-    px, py = xs.reshape(-1, 1), ys.reshape(-1, 1)
-    dx, dy = pixk[None, :, 0] - px, pixk[None, :, 1] - py
-    power = -0.5 * (conk[None, :, 0] * dx * dx + conk[None, :, 2] * dy * dy) - conk[None, :, 1] * dx * dy
-    alpha_raw = ok_o[None, :] * torch.exp(power)
-    alpha = mr.clamp_passthrough(alpha_raw, mr.C_AMAX)
-    amb_pix = None
-    if first:
-        with torch.no_grad():
-            tx, ty = torch.div(px, 16, rounding_mode="floor"), torch.div(py, 16, rounding_mode="floor")
-            listed = (tx >= rect[None, :, 0]) & (tx < rect[None, :, 2]) & (ty >= rect[None, :, 1]) & (ty < rect[None, :, 3])
-            D["ok"] = listed & (power <= 0.0) & (alpha >= mr.C_AMIN)
-    ok = D["ok"]
-    one_minus = torch.where(ok, 1.0 - alpha, torch.ones_like(alpha))
-    T_incl = torch.cumprod(one_minus, dim=1)
-    T_excl = T_incl / one_minus
-    if first:
-        with torch.no_grad():
-            D["live"] = ok & (T_incl >= mr.C_TMIN)
-            # the pixels in which a decision sits within fp32 rounding of its threshold (math_renderer.render's rules; the median
-            # depth's crossing is not rendered here and decides nothing)
-            sq = conk[None, :, 0].abs() * dx * dx + conk[None, :, 2].abs() * dy * dy + 2 * conk[None, :, 1].abs() * (dx * dy).abs()
-            amb = listed & ((power.abs() <= fp32_eps * (1.0 + sq)) | ((power <= 0.0) & ((alpha_raw / mr.C_AMIN - 1.0).abs() <= 8 * fp32_eps * (1.0 + sq))))
-            amb = amb | (ok & ((T_incl / mr.C_TMIN - 1.0).abs() <= 64 * fp32_eps))
-            amb_pix = amb.any(dim=1).reshape(H, W).numpy()
-    live = D["live"]
-    w = torch.where(live, alpha * T_excl, torch.zeros_like(alpha))
-    T_final = torch.where(live, one_minus, torch.ones_like(alpha)).prod(dim=1)
-    colour = w @ colk + T_final[:, None] * torch.as_tensor(cfg["bg"]).to(dt)[None, :]
-    return dict(color=colour.T.reshape(3, H, W), acc_depth=(w @ depk).reshape(H, W), alpha=(1.0 - T_final).reshape(H, W),
-                per=(Ve, Pe, Ce), decisions=D, ambiguous=amb_pix, n_live=live.sum(dim=1).reshape(H, W).numpy(),
-                clamped=((D["clx"] | D["cly"]) & D["vis"]).numpy(), vis=D["vis"].numpy())
+    Returns dict(color [3,H,W], acc_depth [H,W], alpha [H,W], per=(Ve, Pe, Ce) or None, decisions, ambiguous [H,W], n_live, clamped [P], vis [P])."""
+    W, H = cfg["W"], cfg["H"]
+    pr = mr.project_gaussians(t, V, Pm, C, cfg, clamp_grad=clamp_grad, per=per, halve=halve, decisions=decisions)
+    bl = mr.blend_pairs(pr["sorted"], cfg["bg"], W, H, decisions=decisions, fp32_eps=fp32_eps)
+    D = {**pr["decisions"], **bl["decisions"]} if decisions is None else decisions
+    return dict(color=bl["color"], acc_depth=bl["acc_depth"], alpha=bl["alpha"], per=pr["per"], decisions=D,
+                ambiguous=None if decisions is not None else bl["ambiguous"].reshape(H, W).numpy(), w=bl["w"], live=bl["live"],
+                n_live=bl["live"].sum(dim=1).reshape(H, W).numpy(), clamped=((D["clx"] | D["cly"]) & D["vis"]).numpy(), vis=D["vis"].numpy())
 
 
 def tensors(sc, names, dtype=torch.float64, grad=True):
@@ -197,10 +86,9 @@ def evaluate(sc, cam, names, cfg, c, aux=False, dtype=torch.float64, decisions=N
     out = render(t, V, Pm, C, cfg, decisions=decisions, clamp_grad=clamp_grad, halve=halve)
     g, gD, gA = upstream_grads if upstream_grads is not None else upstream(c, cfg, out["ambiguous"], aux)
     loss_of(out, g, gD, gA).backward()
-    z = lambda x: np.zeros(tuple(x.shape)) if x.grad is None else x.grad.double().numpy()      # noqa: E731
-    want = dict(zip(CAMERA, (z(V), z(Pm), z(C))))
-    want.update({n: z(t[n]) for n in names})
-    terms = dict(zip(CAMERA, (z(e) for e in out["per"])))
+    want = dict(zip(CAMERA, (mr.grad64(V), mr.grad64(Pm), mr.grad64(C))))
+    want.update({n: mr.grad64(t[n]) for n in names})
+    terms = dict(zip(CAMERA, (mr.grad64(e) for e in out["per"])))
     return dict(out=out, want=want, terms=terms, g=g, gD=gD, gA=gA, amb=out["ambiguous"])
 
 

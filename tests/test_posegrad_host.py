@@ -41,6 +41,58 @@ def test_helper_equals_the_math_renderer_with_constant_cameras(c, scenes):
         assert _rel(e["terms"][k].sum(axis=0), e["want"][k]) <= 1e-10 or not e["want"][k].any()
 
 
+def test_one_projection_and_one_pair_loop_under_every_helper(scenes):
+    """contrib_math's case a (700 Gaussians, 70 x 45, ragged tiles, frustum-clamped and colour-clamped rows).  (a) project_gaussians +
+    blend_pairs deciding, then replaying their own decisions: bit-equal outputs and leaf gradients; (b) a float32 replay rewrites no decision;
+    (c) the adapters -- mr.render, pm.render without per-Gaussian camera copies, dm.blend, contrib_math's weights -- agree on `live` and on
+    the weights EXACTLY: they are one function now, which the tolerances of the pins above could not say of four copies."""
+    import contrib_math as cm
+    import distort_math as dm
+    sc, cam = cm.case_scene(scenes, cm.CASES["a"])
+    names = ("means3D", "opacities", "shs", "scales", "rotations")
+    cfg = pm.cfg_of(cam, sc)
+    W, H = cfg["W"], cfg["H"]
+    rng = np.random.default_rng(41)
+    maps = ("color", "acc_depth", "alpha")
+    up = [torch.as_tensor(rng.normal(size=s)) for s in ((3, H, W), (H, W), (H, W))]
+    same = lambda a, b: np.array_equal(a.detach().numpy(), b.detach().numpy(), equal_nan=True)      # noqa: E731  (rows behind the camera hold NaN)
+
+    def run(dtype, D):
+        t, cams = pm.tensors(sc, names, dtype), pm.camera_leaves(cam, dtype)
+        pr = mr.project_gaussians(t, *cams, cfg, decisions=D)
+        bl = mr.blend_pairs(pr["sorted"], cfg["bg"], W, H, decisions=D)
+        sum((bl[k] * g.to(dtype)).sum() for k, g in zip(maps, up)).backward()
+        return pr, bl, {n: x.grad for n, x in (*t.items(), *zip(pm.CAMERA, cams))}
+
+    pr0, bl0, g0 = run(torch.float64, None)
+    D = {**pr0["decisions"], **bl0["decisions"]}
+    assert pr0["disc"]["clamped"].any() and not D["colpos"][D["idx"]].all()      # frustum-clamped rows, colour channels clamped at zero
+    assert (D["ok"] & ~D["live"]).any() and (D["listed"] & ~D["ok"]).any()      # pixels ended by the T stop, listed pairs that are skipped
+    held = {k: (v, v.clone()) for k, v in D.items()}
+    pr1, bl1, g1 = run(torch.float64, D)
+    for k in ("pix", "conic", "depth", "o", "col"):
+        assert same(pr0[k], pr1[k]), k
+    for k in maps + ("w", "T_incl", "T_excl", "T_final", "power", "alpha_raw", "live", "ok", "listed"):
+        assert same(bl0[k], bl1[k]), k
+    for n in g0:
+        assert g0[n] is not None and g0[n].any() and same(g0[n], g1[n]), n
+    run(torch.float32, D)
+    assert D.keys() == held.keys()
+    for k, (v, copy) in held.items():
+        assert D[k] is v and torch.equal(v, copy), k
+    with torch.no_grad():
+        t = pm.tensors(sc, names, grad=False)
+        cams = pm.camera_leaves(cam)
+        ref = mr.render(t["means3D"], t["scales"], t["rotations"], t["opacities"], t["shs"], cfg["deg"], cam, sc["bg"])
+        g = dm.project(t, *cams, cfg, {})
+        others = dict(posegrad=pm.render(t, *cams, cfg, per=False), contrib=cm.pairs(sc, cam)[0],
+                      distort=dm.blend(g["pix"], g["conic"], g["o"], g["z"], g["col"], cfg["bg"], g["rect"], W, H))
+    assert ref["live"].any(dim=1).sum() > 0.5 * W * H
+    for n, o in others.items():
+        assert torch.equal(o["live"], ref["live"]) and torch.equal(o["w"], ref["w"]), n
+    assert torch.equal(bl0["w"], ref["w"])
+
+
 # ---- 2. identities of the function itself ------------------------------------------------------------------------------------------------
 def _translation_sides(want, cam):
     V, Pm_ = np.asarray(cam["viewmatrix"], np.float64), np.asarray(cam["projmatrix"], np.float64)
