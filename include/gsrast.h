@@ -959,6 +959,51 @@ int gsrast_bilagrid_backward(const gsrast_bilagrid* d, const float* grid, const 
 int gsrast_bilagrid_tv(int N, int GW, int GH, int L, const float* grids, float* loss_out /* NULL ok */, const float* upstream /* NULL = 1 */,
                        float* dL_dgrids /* NULL ok */, void* stream);
 
+/* ---- the renderer's projection as a call of its own (gsplat's fully_fused_projection; csrc/gsrast_project.h) ----
+ * What the render keeps inside its geometry state, per Gaussian, as differentiable outputs: 2-D supervision on projected centres (point
+ * tracks, optical flow rendered through gsrast_features_forward), screen-size rules for pruning / LOD, statistics on projected quantities.
+ * All arrays contiguous fp32 device pointers unless noted; viewmatrix / projmatrix are 16 floats each in the render calls' transposed
+ * storage; width, height, tanfovx, tanfovy, scale_modifier as gsrast_forward takes them.  Exactly one of (scales [P][3] + rotations [P][4])
+ * and cov3D_precomp [P][6].
+ *
+ * gsrast_project_forward writes every row of
+ *   means2D [P][2]  the pixel centre ((ndc + 1) S - 1) / 2          depths [P]  view-space z
+ *   conics  [P][3]  (c, -b, a) / det of the dilated 2-D covariance  radii  [P]  int32: ceil(3 sqrt(lambda_max)), 0 = culled
+ *   compensation [P]  (GSRAST_PROJECT_ANTIALIAS only) sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))): the factor
+ *                     GSRAST_RENDER_ANTIALIAS multiplies the opacity with
+ * with the expressions of the render's per-Gaussian kernel on the same operands: on a visible row the bits are those of the render's state
+ * (gsrast_debug_export: means2D, depths, conic_opacity[0..2]; opacity * compensation = conic_opacity[3]) and radii equals the render's on
+ * every row.  A row is visible iff view z > 0.2, det != 0 and its 16 x 16 tile rectangle has non-zero area; a culled row (a NaN mean is
+ * one) reads +0.0 in every float output.  One launch, no scratch.
+ * gsrast_project_backward recomputes the forward from the inputs (the forward saves nothing) and writes, where their pointer is not NULL
+ *   (each row OVERWRITTEN; a culled row gets +0.0): dL_dmeans3D [P][3], dL_dscales [P][3], dL_drotations [P][4], dL_dcov3D [P][6], from
+ *   dL_dmeans2D (in pixels), dL_ddepths, dL_dconics, dL_dcompensation (each NULL = zero).  Conventions are the render backward's, so the
+ *   gradients of a render and of a projection of the same leaves add consistently: a frustum-clamped t.x / t.z, t.y / t.z (outside 1.3 x
+ *   the field of view) is a constant of the Jacobian; d conic / d cov2D carries det^2 / (det^2 + 1e-7); dL_dscales is the gradient of
+ *   scale_modifier * scale; the compensation has no gradient where it sits on its floor.  dL_dscales / dL_drotations with cov3D_precomp
+ *   are zeros; dL_dcov3D with scales / rotations is the intermediate.  The camera is not differentiated.  One launch, no atomics.
+ * P = 0 returns 0 without a launch.  Refused (GSRAST_E_ARG, gsrast_last_error) before any device call: a NULL descriptor, P < 0, a
+ * non-positive width / height / tangent, a NULL means3D / viewmatrix / projmatrix, neither or both of (scales + rotations) / cov3D_precomp,
+ * exactly one of scales / rotations, rotations or dL_drotations not 16-byte aligned, unknown flag bits; forward: a NULL means2D / depths /
+ * conics / radii, a NULL compensation with the flag or one without it; backward: dL_dcompensation without the flag, all four gradient
+ * outputs NULL.  The launches have no entry in the profile table. */
+#define GSRAST_PROJECT_ANTIALIAS 1u
+struct gsrast_project {
+    int P, width, height;
+    float tanfovx, tanfovy, scale_modifier;
+    const float *viewmatrix, *projmatrix;
+    const float *means3D, *scales, *rotations, *cov3D_precomp;
+    unsigned flags;
+    float *means2D, *depths, *conics;           /* forward: out (the backward reads none of the five) */
+    int* radii;
+    float* compensation;
+    const float *dL_dmeans2D, *dL_ddepths, *dL_dconics, *dL_dcompensation;      /* backward only, as everything below; NULL = zero */
+    float *dL_dmeans3D, *dL_dscales, *dL_drotations, *dL_dcov3D;                 /* NULL: not wanted, not written */
+};
+typedef struct gsrast_project gsrast_project;
+int gsrast_project_forward(const gsrast_project* d, void* stream);
+int gsrast_project_backward(const gsrast_project* d, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

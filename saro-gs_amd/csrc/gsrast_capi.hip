@@ -24,6 +24,7 @@
 #include "gsrast_contrib.h"
 #include "gsrast_features.h"
 #include "gsrast_distort.h"
+#include "gsrast_project.h"
 #include "gsrast_exchange.h"
 
 #include <algorithm>
@@ -1908,6 +1909,62 @@ int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int 
     ProfScope ps(K_DISTORT_BWD, s);
     pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { L.back_to_front(distort_bwd_kernel<decltype(mode)::value>, s, moments, dL_ddistort, at<float>(geom_buffer, L.grec)); });
     GS_LAUNCHED("distort_bwd");
+    return GSRAST_OK;
+}
+
+// ---- the projection as a call of its own (gsrast_project.h) -----------------------------------------------------------------------------
+namespace {
+// What the two calls refuse alike, before any device work (one text each, behind the call's name)
+const char* project_refusal(const gsrast_project* d)
+{
+    if (!d) return "NULL descriptor";
+    if (d->P < 0) return "negative P";
+    if (d->width <= 0 || d->height <= 0) return "zero-size image";
+    if (!(d->tanfovx > 0.0f) || !(d->tanfovy > 0.0f)) return "tanfovx / tanfovy must be positive";
+    if (!d->means3D) return "NULL means3D";
+    if (!d->viewmatrix || !d->projmatrix) return "NULL viewmatrix / projmatrix";
+    if ((d->scales != nullptr) != (d->rotations != nullptr)) return "scales and rotations go together";
+    if ((d->scales != nullptr) == (d->cov3D_precomp != nullptr)) return "exactly one of (scales, rotations) and cov3D_precomp";
+    if (((uintptr_t)d->rotations & 15) || ((uintptr_t)d->dL_drotations & 15)) return "rotations / dL_drotations must be 16-byte aligned";
+    if (d->flags & ~GSRAST_PROJECT_ANTIALIAS) return "flags: unknown bits";
+    return nullptr;
+}
+} // namespace
+
+int gsrast_project_forward(const gsrast_project* d, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = project_refusal(d)) return refuse("project_forward", e);
+    const bool aa = (d->flags & GSRAST_PROJECT_ANTIALIAS) != 0;
+    if (!d->means2D || !d->depths || !d->conics || !d->radii) return refuse("project_forward", "NULL means2D / depths / conics / radii");
+    if (aa != (d->compensation != nullptr)) return refuse("project_forward", aa ? "NULL compensation with GSRAST_PROJECT_ANTIALIAS" : "compensation without GSRAST_PROJECT_ANTIALIAS");
+    if (d->P == 0) return GSRAST_OK;
+    const CamArgs cam = make_cam(d->viewmatrix, d->projmatrix, nullptr, d->tanfovx, d->tanfovy, d->scale_modifier, d->width, d->height);
+    const unsigned grid = ((unsigned)d->P + PJ_THREADS - 1) / PJ_THREADS;
+    pick_bool(aa, [&](auto AA) {
+        project_fwd_kernel<decltype(AA)::value><<<grid, PJ_THREADS, 0, s>>>(d->P, d->means3D, d->scales, d->rotations, d->cov3D_precomp, cam,
+                                                                                     d->means2D, d->depths, d->conics, d->radii, d->compensation);
+    });
+    GS_LAUNCHED("project_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_project_backward(const gsrast_project* d, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (const char* e = project_refusal(d)) return refuse("project_backward", e);
+    const bool aa = (d->flags & GSRAST_PROJECT_ANTIALIAS) != 0;
+    if (d->dL_dcompensation && !aa) return refuse("project_backward", "dL_dcompensation without GSRAST_PROJECT_ANTIALIAS");
+    if (!d->dL_dmeans3D && !d->dL_dscales && !d->dL_drotations && !d->dL_dcov3D) return refuse("project_backward", "no gradient output");
+    if (d->P == 0) return GSRAST_OK;
+    const CamArgs cam = make_cam(d->viewmatrix, d->projmatrix, nullptr, d->tanfovx, d->tanfovy, d->scale_modifier, d->width, d->height);
+    const unsigned grid = ((unsigned)d->P + PJ_THREADS - 1) / PJ_THREADS;
+    pick_bool(aa && d->dL_dcompensation, [&](auto AA) {      // (without its upstream gradient the compensation adds nothing: the plain kernel)
+        project_bwd_kernel<decltype(AA)::value><<<grid, PJ_THREADS, 0, s>>>(d->P, d->means3D, d->scales, d->rotations, d->cov3D_precomp, cam,
+                                                                                     d->dL_dmeans2D, d->dL_ddepths, d->dL_dconics, d->dL_dcompensation,
+                                                                                     d->dL_dmeans3D, d->dL_dscales, d->dL_drotations, d->dL_dcov3D);
+    });
+    GS_LAUNCHED("project_bwd");
     return GSRAST_OK;
 }
 

@@ -156,6 +156,18 @@ class BilagridStruct(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("GW", "GH", "L", "W", "H", "x0", "y0", "full_W", "full_H", "splits")]
 
 
+PROJECT_ANTIALIAS = 1                                      # include/gsrast.h: GSRAST_PROJECT_ANTIALIAS
+
+
+class ProjectStruct(C.Structure):
+    """gsrast_project (include/gsrast.h): one projection's sizes, camera, inputs, flags, the five outputs, the four upstream gradients and the
+    four gradient outputs.  The two calls take its address (C.addressof)."""
+    _fields_ = ([(k, C.c_int) for k in ("P", "width", "height")] + [(k, C.c_float) for k in ("tanfovx", "tanfovy", "scale_modifier")]
+                + [(k, C.c_void_p) for k in ("viewmatrix", "projmatrix", "means3D", "scales", "rotations", "cov3D_precomp")] + [("flags", C.c_uint)]
+                + [(k, C.c_void_p) for k in ("means2D", "depths", "conics", "radii", "compensation", "dL_dmeans2D", "dL_ddepths", "dL_dconics",
+                                             "dL_dcompensation", "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dcov3D")])
+
+
 class PlaneStruct(C.Structure):
     """gsrast_plane (include/gsrast.h)."""
     _fields_ = [("tex", C.c_void_p), ("grad_tex", C.c_void_p), ("W", C.c_int), ("H", C.c_int), ("cu", C.c_int), ("cv", C.c_int),
@@ -205,6 +217,9 @@ SIGNATURES = {
     "gsrast_features_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
     "gsrast_distortion_forward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
     "gsrast_distortion_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    # the projection as a call of its own (the descriptor: ProjectStruct, passed by address)
+    "gsrast_project_forward": (_ci, (_vp, _vp)),
+    "gsrast_project_backward": (_ci, (_vp, _vp)),
     # the multi-GPU gradient exchange
     "gsrast_sh_grad_combine": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _cf, _vp, _vp)),
     "gsrast_sh_grad_combine_rows": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
