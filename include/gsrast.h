@@ -289,7 +289,7 @@ int gsrast_context_query(const gsrast_context* ctx, const char* name);
  * every pose), "gate_inline_calls".
  *
  * The host-side decisions of a context (csrc/gsrast_policy.h: when the list cut is applied, paused and widened; how the speculative launch is
- * sized) can be driven WITHOUT a device -- a context that never renders touches no GPU.  One event per call, the return value is the
+ * sized; when the bucket depth sort backs off) can be driven WITHOUT a device -- a context that never renders touches no GPU.  One event per call, the return value is the
  * decision (or GSRAST_E_ARG for an unknown event):
  *   "begin"  (a = Gaussians P, b = column runs of the previous forward, c = 1: option list_cut_always) -> 1: the cut pays for this forward; 0: it sits out
  *   "counts" (a = all column runs Q, b = early column runs, c = bit 0: predicted cut depths available, bit 1: some Gaussian was late; P = the last "begin"'s) -> forwards of pause now pending
@@ -297,10 +297,13 @@ int gsrast_context_query(const gsrast_context* ctx, const char* name);
  *   "clean"  (a cut forward behind which no pass was reported) -> the score
  *   "size"   (a = early-run hint, b = capacity in column runs, c = 1: an early set is expected) -> column runs the launches over the cut lists are sized for
  *   "grow"   (a = count) -> the capacity requested for it;   "follow" (a = hint, b = this forward's count, c = shift) -> the next hint
- *   "get"    (a = 0 pause, 1 score, 2 margin x 4, 3 tau_req, 4 tau_force, 5 length of the last fallback pause)
+ *   "get"    (a = 0 pause, 1 score, 2 margin x 4, 3 tau_req, 4 tau_force, 5 length of the last fallback pause; the bucket depth sort's back-off:
+ *            6 "bucket_skip", 7 length of its last pause, 8 bucket-sorted forwards without an overflow since, at most 1024)
+ *   "depth_sort" (a forward's outcome for the bucket depth sort's back-off -- a = 0: it went to the radix sort although the bucket sort was asked for;
+ *            1: bucket-sorted without overflow; 2: a bucket overflowed, b = 1: the depth histogram's table was a learned one that held every key) -> "bucket_skip"
  *   "zrange" (a = first | last << 16 occupied bin of the depth histogram a forward filled with the context's current table) -> the next table's
  *            shift, | 256 if the current table was a learned one that held every key;   "zget" (a = 0 klo / 256, 1 shift, 2 khi / 256)
- *   "reset"  (a fresh policy: tests);   "tau_min" (a = the predicted cut's requirement and its floor: experiments)
+ *   "reset"  (fresh policies, the back-off's included: tests);   "tau_min" (a = the predicted cut's requirement and its floor: experiments)
  * ctx NULL = the calling thread's context. */
 int gsrast_policy_event(gsrast_context* ctx, const char* what, int a, int b, int c);
 /* The forward's host-side plan (csrc/gsrast_policy.h: ForwardPlan) WITHOUT a device: what a forward with these options, flags and shape would decide

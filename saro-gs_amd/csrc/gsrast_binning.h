@@ -190,12 +190,12 @@ __device__ __forceinline__ uint32_t dev_count(uint32_t n, const uint32_t* __rest
 // buffers accordingly (A -> B -> C -> A instead of A -> B -> A -> B -> A): the sorted sequence ends in A either way.
 // RA_ASSUME: the host did not even enqueue the fourth pass, because the previous forward of the same context found a short span
 // (consecutive views of one scene): every kernel then behaves as if the verdict were "short", and the first pass's extra
-// workgroup raises sig[2] when that was wrong -- the host reads it back with the instance counts and repeats the sort with four
+// workgroup raises sig[SIG_WRONG] when that was wrong -- the host reads it back with the instance counts and repeats the sort with four
 // passes (gsrast_forward: the same redo path as an undersized speculative binning buffer).
 enum : int { RA_MINMAX = 1, RA_IN_ALT = 2, RA_SKIP = 4, RA_OUT_ALT = 8, RA_LAST_IF_SHORT = 16, RA_ASSUME = 32 };
-__device__ __forceinline__ bool sort_is_short(const uint32_t* __restrict__ sig, int adapt = 0)      // sig[1] = base, sig[2] = wrong assumption
+__device__ __forceinline__ bool sort_is_short(const uint32_t* __restrict__ sig, int adapt = 0)      // (the three words at scalars + SC_SIG: SIG_BITS, SIG_BASE, SIG_WRONG)
 {
-    return (adapt & RA_ASSUME) || (sig && sig[0] <= 24u);
+    return (adapt & RA_ASSUME) || (sig && sig[SIG_BITS] <= 24u);
 }
 
 template <typename KeyT, int ITEMS>
@@ -212,7 +212,7 @@ radix_hist_kernel(const KeyT* __restrict__ keys, uint32_t n, const uint32_t* __r
     if ((adapt & RA_SKIP) && is_short) return;
     if ((adapt & RA_IN_ALT) && is_short) keys = keys_alt;
     if ((adapt & RA_MINMAX) && threadIdx.x == 0) { s_mm[0] = 0xFFFFFFFFu; s_mm[1] = 0u; }
-    const uint32_t base = sig ? sig[1] : 0u;
+    const uint32_t base = sig ? sig[SIG_BASE] : 0u;
     n = dev_count(n, n_dev);
     const unsigned lane = lane_id(), wave = threadIdx.x >> 6;
     for (int k = threadIdx.x; k < 1024; k += RS_THREADS) (&cnt[0][0])[k] = 0;
@@ -270,9 +270,9 @@ radix_rowscan_kernel(uint32_t* __restrict__ block_hist, uint32_t nblk, uint32_t*
         if (threadIdx.x == 0) {
             const uint32_t b = mm[0] > mm[1] ? 0u : (mm[0] & ~0xFFu);
             const uint32_t span = mm[0] > mm[1] ? 0u : mm[1] - b;
-            sig[0] = span ? 32u - (uint32_t)__builtin_clz(span) : 0u;
-            sig[1] = b;
-            sig[2] = ((adapt & RA_ASSUME) && sig[0] > 24u) ? 1u : 0u;
+            sig[SIG_BITS] = span ? 32u - (uint32_t)__builtin_clz(span) : 0u;
+            sig[SIG_BASE] = b;
+            sig[SIG_WRONG] = ((adapt & RA_ASSUME) && sig[SIG_BITS] > 24u) ? 1u : 0u;
         }
         return;
     }
@@ -317,7 +317,7 @@ radix_scatter_kernel(const KeyT* __restrict__ keys_in, const ValT* __restrict__ 
         if ((adapt & RA_OUT_ALT) && is_short) { keys_out = keys_out_alt; vals_out = vals_out_alt; }
         if ((adapt & RA_LAST_IF_SHORT) && !is_short) gather_rect = nullptr;      // this pass gathers only when it is the last one
     }
-    const uint32_t base = (sig && shift > 0) ? sig[1] : 0u;      // pass one runs before `base` exists and does not need it (low byte of base = 0)
+    const uint32_t base = (sig && shift > 0) ? sig[SIG_BASE] : 0u;      // pass one runs before `base` exists and does not need it (low byte of base = 0)
     n = dev_count(n, n_dev);
     // Ranks -> block-local order in LDS -> coalesced write-out: after the exchange consecutive lanes
     // hold consecutive elements of the same digit, whose global destinations are consecutive too.
@@ -1005,24 +1005,26 @@ __device__ __forceinline__ void depth_bucket_totals(const uint4* __restrict__ bi
     over = __syncthreads_or((int)over) ? 1u : 0u;
     for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) { s_t[threadIdx.x] += s_t[threadIdx.x + st]; s_q[threadIdx.x] += s_q[threadIdx.x + st]; s_qe[threadIdx.x] += s_qe[threadIdx.x + st]; } __syncthreads(); }
     if (threadIdx.x == 0) {
-        scalars[0] = (uint32_t)s_t[0]; scalars[1] = s_q[0]; scalars[3] = (uint32_t)(s_t[0] >> 32); scalars[11] = over;
+        scalars[SC_R_LO] = (uint32_t)s_t[0]; scalars[SC_Q] = s_q[0]; scalars[SC_R_HI] = (uint32_t)(s_t[0] >> 32); scalars[SC_BUCKET_OVER] = over;
         const uint32_t q_early = binfo_e ? s_qe[0] : s_q[0], n_late = binfo_e ? scalars[SC_N_LATE] : 0u;
         scalars[SC_Q_EARLY] = q_early;
-        scalars[SC_EARLY_COUNTS] = (uint32_t)s_t[0]; scalars[SC_EARLY_COUNTS + 1] = q_early; scalars[SC_EARLY_COUNTS + 2] = 0u; scalars[SC_EARLY_COUNTS + 3] = (uint32_t)(s_t[0] >> 32);
+        scalars[SC_EARLY_COUNTS + SC_R_LO] = (uint32_t)s_t[0]; scalars[SC_EARLY_COUNTS + SC_Q] = q_early; scalars[SC_EARLY_COUNTS + SC_LISTED] = 0u; scalars[SC_EARLY_COUNTS + SC_R_HI] = (uint32_t)(s_t[0] >> 32);
         if (host_out) {
             // seven self-validating 64-bit words {value, sequence number}, each ONE relaxed system-scope atomic store: no fence.  (A
             // system-scope release in front of a flag word writes the L2's dirty lines back -- with the colour kernel dirtying lines
             // beside it this workgroup, and with it the whole kernel, lasted until that kernel was done: 35 -> 120 us at 3 M.)
             unsigned long long* h64 = reinterpret_cast<unsigned long long*>(host_out);
-            const uint32_t vals[7] = { (uint32_t)s_t[0], s_q[0], over, (uint32_t)(s_t[0] >> 32), q_early, n_late, scalars[SC_ZBINS] };
+            uint32_t vals[SC_BUCKET_OVER + 1];      // by the words' names; stored in the read-back's order (kReadbackWord)
+            vals[SC_R_LO] = (uint32_t)s_t[0]; vals[SC_Q] = s_q[0]; vals[SC_BUCKET_OVER] = over; vals[SC_R_HI] = (uint32_t)(s_t[0] >> 32);
+            vals[SC_Q_EARLY] = q_early; vals[SC_N_LATE] = n_late; vals[SC_ZBINS] = scalars[SC_ZBINS];
 #pragma unroll
-            for (int k = 0; k < 7; k++)
-                __hip_atomic_store(h64 + k, ((unsigned long long)host_seq << 32) | vals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            for (int k = 0; k < RB_WORDS; k++)
+                __hip_atomic_store(h64 + k, ((unsigned long long)host_seq << 32) | vals[kReadbackWord[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
 __global__ void __launch_bounds__(256)
-depth_bucket_scan_kernel(const uint4* __restrict__ binfo, uint32_t nb, uint32_t* __restrict__ scalars /* [0] R lo, [1] Q, [3] R hi, [11] overflow */)
+depth_bucket_scan_kernel(const uint4* __restrict__ binfo, uint32_t nb, uint32_t* __restrict__ scalars /* SC_R_LO, SC_Q, SC_R_HI, SC_BUCKET_OVER (and the early group) */)
 {
     depth_bucket_totals(binfo, nb, scalars);
 }
@@ -1220,7 +1222,7 @@ emit_column_runs_kernel(int P, const uint32_t* __restrict__ order, const uint32_
             s_t2[threadIdx.x] = ts; s_q2[threadIdx.x] = q;
             __syncthreads();
             for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) { s_t2[threadIdx.x] += s_t2[threadIdx.x + st]; s_q2[threadIdx.x] += s_q2[threadIdx.x + st]; } __syncthreads(); }
-            if (threadIdx.x == 0) { pass2_counts[0] = (uint32_t)s_t2[0]; pass2_counts[1] = s_q2[0]; pass2_counts[2] = 0u; pass2_counts[3] = (uint32_t)(s_t2[0] >> 32); q2 = s_q2[0] ? s_q2[0] : 1u; }
+            if (threadIdx.x == 0) { pass2_counts[SC_R_LO] = (uint32_t)s_t2[0]; pass2_counts[SC_Q] = s_q2[0]; pass2_counts[SC_LISTED] = 0u; pass2_counts[SC_R_HI] = (uint32_t)(s_t2[0] >> 32); q2 = s_q2[0] ? s_q2[0] : 1u; }
         }
         // (the host is told what the pass cost: the candidates' column runs -- a context whose passes keep costing too much pauses the cut)
         if (threadIdx.x == 0 && host_fallback) __hip_atomic_store(host_fallback, ((unsigned long long)host_fb_seq << 32) | (unsigned long long)q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1453,8 +1455,8 @@ tile_ranges_from_runs_body(uint32_t column, const uint16_t* __restrict__ run_key
         // The launch was sized for capacities (Q = capQ).  If the real counts do not fit, the lists are truncated:
         // publish empty ranges (the blend kernels then touch nothing) -- the host sees the same counts and redoes the
         // binning with exact sizes.
-        overflow = counts_dev[1] > Q || counts_dev[3] != 0u || counts_dev[0] > capR;      // uniform
-        if (!overflow) Q = counts_dev[1];
+        overflow = counts_dev[SC_Q] > Q || counts_dev[SC_R_HI] != 0u || counts_dev[SC_R_LO] > capR;      // uniform
+        if (!overflow) Q = counts_dev[SC_Q];
     }
     uint32_t work = 0;
     const bool mine = y < (uint32_t)gy && (!need2 || need2[y * (uint32_t)gx + x] != 0);
@@ -1653,7 +1655,7 @@ rows_and_ranges_kernel(const uint16_t* __restrict__ run_keys, const uint2* __res
 {
     static_assert(RS_THREADS == 256, "one lane per tile row in the ranges part");
     if (pred && *pred == 0u) return;
-    if (blockIdx.x < nblk) run_scatter_rows_body(blockIdx.x, run_vals, Q, counts_dev ? counts_dev + 1 : nullptr, capR, ybits, (uint32_t)gy, hist_scanned, digit_total, nblk, point_list, total_out);
+    if (blockIdx.x < nblk) run_scatter_rows_body(blockIdx.x, run_vals, Q, counts_dev ? counts_dev + SC_Q : nullptr, capR, ybits, (uint32_t)gy, hist_scanned, digit_total, nblk, point_list, total_out);
     else tile_ranges_from_runs_body(blockIdx.x - nblk, run_keys, run_vals, Q, counts_dev, capR, gx, gy, hist_scanned, digit_total, nblk, ranges, bucket_cnt, bucket_list, hints, hint_sel, need2, list_offset, zcut_pred);
 }
 

@@ -5,7 +5,8 @@
 // Built with the flags of build.py (FLAGS), one object per unit, linked into one library.
 //
 // Host side: forward_impl / backward_impl run the stages of one ForwardRun / BackwardRun; what a call does is decided once, at its top, by
-// plan_forward / plan_backward (gsrast_policy.h).  The process-wide words of gsrast_set_option live in one table (kOptions).
+// plan_forward / plan_backward (gsrast_policy.h).  The process-wide words of gsrast_set_option live in one table (kOptions).  What a context
+// owns on a device -- streams, gate, tables, hints -- is one record (DeviceState), which a call resolves once, at its top (current_device).
 // Launch plan of the default path (every launch on the caller's stream except the colour kernel):
 //   forward : preprocess_fwd (geometry; claims the pose's launch-order hint slot) -> depth_bucket_scatter -> depth_bucket_sort
 //             -> [fork: preprocess_color on the context's side stream] -> emit_column_runs (workgroup 0: totals -> pinned host memory,
@@ -310,20 +311,25 @@ struct Readback {     // 64 pinned bytes + one event per (host thread, device); 
     uint32_t fb_seen = 0;   // list cut: sequence number of the last fallback this thread has taken note of (word RB_FALLBACK)
     bool prepared = false;  // read_flag_prepare has run for the forward in progress (the pose-found word is waited for before the counts)
 };
-// 64-bit words of the pinned buffer (128 bytes): 0-6 the counts of depth_bucket_totals, then
-constexpr int RB_FOUND = 7;        // {1 = the pose had a slot in the context's table, sequence number}: preprocess_fwd, at its very start
-constexpr int RB_FALLBACK = 8;     // {1, sequence number of the call}: the predicated second binning of a list-cut forward has run
+// 64-bit words of the pinned buffer (128 bytes): the counts of depth_bucket_totals (kReadbackWord, gsrast_common.h), then RB_FOUND, RB_FALLBACK
 constexpr size_t RB_BYTES = 128;
-constexpr int kMaxDevices = 32;
+constexpr int kCountWords = SC_BUCKET_OVER + 1;      // the words of GeomLayout::scalars a forward's host reads back (ForwardRun::counts): SC_R_LO ... SC_BUCKET_OVER
+static_assert([] { for (int w : kReadbackWord) if (w >= kCountWords) return false; return true; }(), "a read-back word the host's copy has no room for");
+constexpr int kMaxDevices = 32;      // devices a context keeps a record for (DeviceState) and a host thread a read-back buffer: THE bound, spelt nowhere else
 thread_local Readback t_readback[kMaxDevices];     // one per (host thread, device): events belong to a device
-// begin: enqueue the copy + event; finish: spin until it landed.  Work enqueued between the two runs on the GPU while
-// the host waits (speculative launch in gsrast_forward).
-int read_u32_begin(const uint32_t* dev, hipStream_t s, int nwords, Readback** handle)
+// The calling thread's current device, or -1: none (no runtime, or an exotic topology beyond kMaxDevices) -- such a call has no side stream,
+// no gate, no hints, its own tables, and a blocking copy for the read-back.  A render call asks ONCE, at its top.
+int current_device()
 {
     int device = 0;
+    return (hipGetDevice(&device) == hipSuccess && device >= 0 && device < kMaxDevices) ? device : -1;
+}
+// begin: enqueue the copy + event; finish: spin until it landed.  Work enqueued between the two runs on the GPU while
+// the host waits (speculative launch in gsrast_forward).
+int read_u32_begin(int device, const uint32_t* dev, hipStream_t s, int nwords, Readback** handle)
+{
     *handle = nullptr;
-    GS_HIP(hipGetDevice(&device));
-    if (device < 0 || device >= kMaxDevices) return GSRAST_OK;      // exotic topology: finish() does a blocking copy
+    if (device < 0) return GSRAST_OK;      // no device record: finish() does a blocking copy
     Readback& rb = t_readback[device];
     if (!rb.pinned) {
         GS_HIP(hipHostMalloc((void**)&rb.pinned, RB_BYTES, hipHostMallocPortable | hipHostMallocMapped));
@@ -353,10 +359,9 @@ int read_u32_finish(Readback* rb, const uint32_t* dev, hipStream_t s, uint32_t* 
 // into word 15 (depth_bucket_totals).  prepare: the buffer's device alias and this call's sequence number, or nullptr if mapped host
 // memory is not to be had (the caller then uses the copy).  finish: spin on word 15; should it not arrive within two seconds the stream
 // is drained and the counts are copied the slow way (a failed launch surfaces there).
-Readback* read_flag_prepare(uint32_t** dev_alias, uint32_t* seq)
+Readback* read_flag_prepare(int device, uint32_t** dev_alias, uint32_t* seq)
 {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= kMaxDevices) return nullptr;
+    if (device < 0) return nullptr;
     Readback& rb = t_readback[device];
     if (!rb.pinned) {
         if (hipHostMalloc((void**)&rb.pinned, RB_BYTES, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) { rb.pinned = nullptr; return nullptr; }
@@ -371,13 +376,14 @@ Readback* read_flag_prepare(uint32_t** dev_alias, uint32_t* seq)
     *dev_alias = rb.dev_alias; *seq = rb.seq;
     return &rb;
 }
-int read_flag_finish(Readback* rb, const uint32_t* dev, hipStream_t s, uint32_t* out, int nwords)
+int read_flag_finish(Readback* rb, const uint32_t* dev, hipStream_t s, uint32_t* out /* [kCountWords] */)
 {
-    // seven 64-bit words {value, sequence number} (depth_bucket_totals): each is valid as soon as its upper half carries this call's number
+    constexpr int nwords = kCountWords;
+    // RB_WORDS 64-bit words {value, sequence number} (depth_bucket_totals): each is valid as soon as its upper half carries this call's number
     volatile unsigned long long* p = reinterpret_cast<volatile unsigned long long*>(rb->pinned);
     const auto t0 = std::chrono::steady_clock::now();
-    unsigned long long w[7];
-    for (int k = 0; k < 7; k++) {
+    unsigned long long w[RB_WORDS];
+    for (int k = 0; k < RB_WORDS; k++) {
         for (uint64_t spins = 1; (uint32_t)((w[k] = p[k]) >> 32) != rb->seq; spins++) {
             if ((spins & 0xFFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
                 GS_HIP(hipStreamSynchronize(s));
@@ -388,8 +394,7 @@ int read_flag_finish(Readback* rb, const uint32_t* dev, hipStream_t s, uint32_t*
         }
     }
     for (int k = 0; k < nwords; k++) out[k] = 0u;
-    out[0] = (uint32_t)w[0]; out[1] = (uint32_t)w[1]; out[3] = (uint32_t)w[3];       // {R low, Q, overflow verdict, R high}
-    if (nwords > 11) { out[11] = (uint32_t)w[2]; out[SC_Q_EARLY] = (uint32_t)w[4]; out[SC_N_LATE] = (uint32_t)w[5]; out[SC_ZBINS] = (uint32_t)w[6]; }     // (list cut: early column runs, late Gaussians; the depth histogram's occupied bins)
+    for (int k = 0; k < RB_WORDS; k++) out[kReadbackWord[k]] = (uint32_t)w[k];      // (the kernel's own order: one list, gsrast_common.h)
     return GSRAST_OK;
 }
 // the pose-found word of preprocess_fwd (RB_FOUND): 1 / 0, or 0 ("size the launches as for an unknown pose": all column runs, the safe
@@ -405,10 +410,9 @@ bool read_found(Readback* rb)
 }
 // has the device reported a completion pass of the list cut this thread has not taken note of yet (RB_FALLBACK)?  Returns the number
 // of column runs of that pass's candidates (0: nothing new).
-uint32_t take_fallback_event()
+uint32_t take_fallback_event(int device)
 {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= kMaxDevices) return 0u;
+    if (device < 0) return 0u;
     Readback& rb = t_readback[device];
     if (!rb.pinned) return 0u;
     const unsigned long long w = reinterpret_cast<volatile unsigned long long*>(rb.pinned)[RB_FALLBACK];
@@ -417,10 +421,10 @@ uint32_t take_fallback_event()
     rb.fb_seen = sq;
     return (uint32_t)w ? (uint32_t)w : 1u;
 }
-int read_u32(const uint32_t* dev, hipStream_t s, uint32_t* out, int nwords = 1)
+int read_u32(int device, const uint32_t* dev, hipStream_t s, uint32_t* out, int nwords = 1)
 {
     Readback* rb = nullptr;
-    int rc = read_u32_begin(dev, s, nwords, &rb);
+    int rc = read_u32_begin(device, dev, s, nwords, &rb);
     if (rc != GSRAST_OK) return rc;
     return read_u32_finish(rb, dev, s, out, nwords);
 }
@@ -458,6 +462,140 @@ __global__ void chain_done_kernel(const uint32_t* __restrict__ pred_copy, uint32
 {
     if (*pred_copy != 0u) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// ---- what a context owns on ONE device (gsrast_context::dev[current_device()]): every piece created on first use, by the member that hands
+// it out, under the context's mutex `mu`.  A call resolves its record once, at its top, and every stage uses that pointer. ----
+namespace {
+struct DeviceState {
+    SideStream side;                  // the stream the colour kernel runs on beside the sort
+    ChainGate gate;                   // the completion pass's own stream and release words
+    uint32_t* tau = nullptr; size_t tau_words = 0; bool tau_dirty = false;      // the predicted cut's opacity-mass table [TAU_COPIES][T][TAU_BINS] (ImgLayout::tau_hist's twin), kept ZERO between
+                                                                                // forwards: filled by preprocess_fwd, read by tau_cut_kernel, zeroed again by the bucket sort behind it -- no memset launch per forward
+    uint32_t* zhist = nullptr;        // the sampled depth histogram of the bucket depth sort [ZH_COPIES][ZH_BINS] -- filled by preprocess_fwd, read by the
+                                      // scatter, zeroed again by the bucket sort behind it (no memset launch per forward).  Two forwards of one context in flight on two
+                                      // streams mix their samples: the bucket map stays monotone whatever the histogram holds (gsrast_common.h), only the balance suffers
+    struct Hints { HintTable* table = nullptr; uint32_t T = 0; uint64_t used = 0; } hints[4];   // launch-order hints of the forward blend (gsrast_common.h), device memory: one table per image size in use, up to four (train / eval resolutions alternate)
+    uint64_t hints_clock = 0;         // ... and their least-recently-used clock
+
+    // The side stream (lowest priority: its bandwidth-heavy kernels should fill the gaps the critical path leaves, not compete with it for
+    // compute units).  nullptr if it cannot be had.
+    SideStream* side_stream(std::mutex& mu)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        SideStream& x = side;
+        if (!x.stream) {
+            int prio_least = 0, prio_greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+            if (hipStreamCreateWithPriority(&x.stream, hipStreamNonBlocking, prio_least) != hipSuccess) { x.stream = nullptr; return nullptr; }
+            if (hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&x.join2, hipEventDisableTiming) != hipSuccess) {
+                if (x.fork) (void)hipEventDestroy(x.fork);          // all or nothing: the next call tries again
+                if (x.join) (void)hipEventDestroy(x.join);
+                if (x.join2) (void)hipEventDestroy(x.join2);
+                (void)hipStreamDestroy(x.stream);
+                x = SideStream{};
+                return nullptr;
+            }
+        }
+        return &x;
+    }
+    // The completion pass's gate; nullptr if the device cannot wait on a memory word, or once anything about the gate has failed (`failed` latches)
+    ChainGate* chain_gate(std::mutex& mu, int device)
+    {
+        int can = 0;
+        std::lock_guard<std::mutex> lk(mu);
+        ChainGate& g = gate;
+        if (g.failed) return nullptr;
+        if (!g.stream) {
+            g.failed = true;                      // (until everything below has worked)
+            if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess || !can) return nullptr;
+            int prio_least = 0, prio_greatest = 0;      // (lowest priority: the pass's no-ops run beside the backward and must not stand in its workgroups' way)
+            (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+            if (hipMalloc((void**)&g.words, 128 * sizeof(uint32_t)) != hipSuccess) { g.words = nullptr; return nullptr; }
+            if (hipMemset(g.words, 0, 128 * sizeof(uint32_t)) != hipSuccess ||
+                hipStreamCreateWithPriority(&g.stream, hipStreamNonBlocking, prio_least) != hipSuccess) { (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr; }
+            if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(g.stream); (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr; }
+            for (uint32_t k = 0; k < GATE_RING; k++)
+                if (hipEventCreateWithFlags(&g.tail[k], hipEventDisableTiming) != hipSuccess) {
+                    for (uint32_t j = 0; j < k; j++) (void)hipEventDestroy(g.tail[j]);
+                    (void)hipEventDestroy(g.ev); (void)hipStreamDestroy(g.stream); (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr;
+                }
+            g.failed = false;
+        }
+        return &g;
+    }
+    // The hint table for a T-tile image (allocated on first use, cleared when T changes); nullptr if it cannot be had -- the forward
+    // then orders its blend by list length, as a first-seen pose does.
+    HintTable* hint_table(std::mutex& mu, uint32_t T, hipStream_t s)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        // one table per tile count, up to four per device (train and eval resolutions, mixed camera sizes: each keeps its poses); a fifth
+        // size takes over the least recently used table's place (rare: drain, then start over)
+        Hints* hp = nullptr;
+        for (auto& c : hints) if (c.table && c.T == T) hp = &c;
+        if (!hp) {
+            for (auto& c : hints) if (!c.table) { hp = &c; break; }
+            if (!hp) {
+                hp = &hints[0];
+                for (auto& c : hints) if (c.used < hp->used) hp = &c;
+                (void)hipStreamSynchronize(s); (void)hipFree(hp->table); hp->table = nullptr;
+            }
+        }
+        auto& h = *hp;
+        h.used = ++hints_clock;
+        if (!h.table) {
+            if (hipMalloc((void**)&h.table, hint_table_bytes(T)) != hipSuccess) { h.table = nullptr; return nullptr; }
+            h.T = T;
+            if (hipMemsetAsync(h.table, 0, hint_zcut_offset(T), s) != hipSuccess ||
+                hipMemsetAsync(reinterpret_cast<char*>(h.table) + hint_zcut_offset(T), 0xFF, (size_t)HINT_SLOTS * T * 4, s) != hipSuccess) { (void)hipFree(h.table); h.table = nullptr; return nullptr; }
+        }
+        return h.table;
+    }
+    // The depth histogram, zero; nullptr if no memory is to be had (the call then uses its own table and a memset)
+    uint32_t* depth_hist(std::mutex& mu)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!zhist) {
+            uint32_t* z = nullptr;
+            if (hipMalloc((void**)&z, ZH_COPIES * ZH_BINS * sizeof(uint32_t)) == hipSuccess) {
+                if (hipMemset(z, 0, ZH_COPIES * ZH_BINS * sizeof(uint32_t)) == hipSuccess) zhist = z; else (void)hipFree(z);
+            }
+        }
+        return zhist;
+    }
+    // The opacity-mass table of at least `words` words, zero on `s` and marked dirty (the bucket sort that zeroes it again clears the mark);
+    // nullptr if it cannot be had or zeroed (the call then uses its own table and a memset, which reports what is wrong with the stream)
+    uint32_t* mass_table(std::mutex& mu, size_t words, hipStream_t s)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (tau_words < words) {
+            if (tau) { (void)hipFree(tau); tau = nullptr; tau_words = 0; }
+            uint32_t* z = nullptr;
+            if (hipMalloc((void**)&z, words * sizeof(uint32_t)) == hipSuccess) { tau = z; tau_words = words; tau_dirty = true; }
+        }
+        if (!tau) return nullptr;
+        // (a fresh table, or a forward that filled it and never reached its bucket sort: zeroed here)
+        if (tau_dirty && hipMemsetAsync(tau, 0, tau_words * sizeof(uint32_t), s) != hipSuccess) return nullptr;
+        tau_dirty = true;
+        return tau;
+    }
+    // gsrast_context_destroy: the streams are drained before they are destroyed
+    void release()
+    {
+        for (auto& h : hints) if (h.table) (void)hipFree(h.table);
+        if (gate.stream) { (void)hipStreamSynchronize(gate.stream); (void)hipStreamDestroy(gate.stream); }
+        if (gate.ev) (void)hipEventDestroy(gate.ev);
+        for (hipEvent_t e : gate.tail) if (e) (void)hipEventDestroy(e);
+        if (gate.words) (void)hipFree(gate.words);
+        if (zhist) (void)hipFree(zhist);
+        if (tau) (void)hipFree(tau);
+        if (side.stream) { (void)hipStreamSynchronize(side.stream); (void)hipStreamDestroy(side.stream); }
+        if (side.fork) (void)hipEventDestroy(side.fork);
+        if (side.join) (void)hipEventDestroy(side.join);
+        if (side.join2) (void)hipEventDestroy(side.join2);
+    }
+};
+} // namespace
 struct gsrast_context {
     std::atomic<uint32_t> R_hint{0}, Q_hint{0}, last_R{0}, last_Q{0}, last_late{0}, last_Qe{0};
     std::atomic<uint32_t> Qe_hint{0};  // list cut: column runs of the early Gaussians in recent forwards (sizes the launches over the cut lists)
@@ -472,46 +610,12 @@ struct gsrast_context {
     DepthRange zrange;                 // (gsrast_policy.h) klo / shift: the histogram's bins; khi: the range's un-rounded upper end (the predicted cut's bins span [klo, khi])
     std::atomic<uint32_t> last_prologue_ns{0};   // host time of the last forward from entry to the launch of its first kernel (diagnostic: tools/sync_probe.py)
     std::atomic<int> redo_count{0};   // forwards whose speculative launch did not fit and was repeated with exact sizes
-    std::atomic<int> depth_short{0};  // the last forward's depth keys spanned < 2^24: the next one enqueues three sort passes, not four
-    std::atomic<int> bucket_skip{0};  // > 0: a recent forward's bucket depth sort overflowed a bucket; that many forwards go straight to the radix sort
-    std::atomic<int> bucket_backoff{0}, bucket_clean{0};   // length of the last such pause (doubles per overflow), bucket-sorted forwards without one since
-    SideStream side[32];              // per device: the stream the colour kernel runs on beside the sort (created on first use)
-    ChainGate gate[32];               // per device: the completion pass's own stream and release words (created on first use)
-    uint32_t* tau_dev[32] = {}; size_t tau_dev_words[32] = {}; bool tau_dev_dirty[32] = {};      // per device: the predicted cut's opacity-mass table [TAU_COPIES][T][TAU_BINS] (ImgLayout::tau_hist's twin), kept ZERO between
-                                                                                                   // forwards: filled by preprocess_fwd, read by tau_cut_kernel, zeroed again by the bucket sort behind it -- no memset launch per forward
-    uint32_t* zhist_dev[32] = {};     // per device: the sampled depth histogram of the bucket depth sort [ZH_COPIES][ZH_BINS] -- filled by preprocess_fwd, read by the
-                                      // scatter, zeroed again by the bucket sort behind it (no memset launch per forward).  Two forwards of one context in flight on two
-                                      // streams mix their samples: the bucket map stays monotone whatever the histogram holds (gsrast_common.h), only the balance suffers
-    struct Hints { HintTable* table = nullptr; uint32_t T = 0; uint64_t used = 0; } hints[32][4];   // (one table per image size in use, up to four: train / eval resolutions alternate)
-    uint64_t hints_clock = 0;   // per device: launch-order hints of the forward blend (gsrast_common.h), device memory
+    DepthSortPolicy zsort;            // the bucket depth sort's back-off after an overflow ("bucket_skip"), the radix sort's pass-count hint (gsrast_policy.h)
+    DeviceState dev[kMaxDevices];     // per device: streams, gate, tables, hints
     std::mutex mu;
+    DeviceState* device_state(int device) { return device >= 0 ? &dev[device] : nullptr; }      // (device: current_device())
 };
 namespace {
-// The context's side stream on the current device (created on first use, lowest priority: its bandwidth-heavy kernels should fill
-// the gaps the critical path leaves, not compete with it for compute units).  nullptr if it cannot be had.
-SideStream* side_stream_of(gsrast_context* ctx)
-{
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 32) return nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    SideStream& x = ctx->side[device];
-    if (!x.stream) {
-        int prio_least = 0, prio_greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-        if (hipStreamCreateWithPriority(&x.stream, hipStreamNonBlocking, prio_least) != hipSuccess) { x.stream = nullptr; return nullptr; }
-        if (hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&x.join2, hipEventDisableTiming) != hipSuccess) {
-            if (x.fork) (void)hipEventDestroy(x.fork);          // all or nothing: the next call tries again
-            if (x.join) (void)hipEventDestroy(x.join);
-            if (x.join2) (void)hipEventDestroy(x.join2);
-            (void)hipStreamDestroy(x.stream);
-            x = SideStream{};
-            return nullptr;
-        }
-    }
-    return &x;
-}
 // TESTS ONLY (option "mutate"): a backward that is wrong on purpose, so that a test can show its tolerance would catch it (the
 // full-size gradient bar let an all-zero dL/dsh pass).  bit 0: the blend backward of ONE tile -- the image's centre tile -- does not see the 64
 // front-most entries of the tile's list (one staged batch dropped: the tile's range, its pixels' n_contrib and its tile_max are shifted by a
@@ -526,60 +630,6 @@ __global__ void mutate_drop_front_batch_kernel(uint2* ranges, uint32_t* n_contri
     __syncthreads();
     if (px < (uint32_t)W && py < (uint32_t)H) { const size_t pid = (size_t)W * py + px; const uint32_t c = n_contrib[pid]; n_contrib[pid] = c > drop ? c - drop : 0u; }
     if (threadIdx.x == 0) { ranges[tile] = make_uint2(r.x + drop, r.y); const uint32_t m = tile_max[tile]; tile_max[tile] = m > drop ? m - drop : 0u; }
-}
-ChainGate* chain_gate_of(gsrast_context* ctx)
-{
-    int device = 0, can = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 32) return nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ChainGate& g = ctx->gate[device];
-    if (g.failed) return nullptr;
-    if (!g.stream) {
-        g.failed = true;                      // (until everything below has worked)
-        if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess || !can) return nullptr;
-        int prio_least = 0, prio_greatest = 0;      // (lowest priority: the pass's no-ops run beside the backward and must not stand in its workgroups' way)
-        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-        if (hipMalloc((void**)&g.words, 128 * sizeof(uint32_t)) != hipSuccess) { g.words = nullptr; return nullptr; }
-        if (hipMemset(g.words, 0, 128 * sizeof(uint32_t)) != hipSuccess ||
-            hipStreamCreateWithPriority(&g.stream, hipStreamNonBlocking, prio_least) != hipSuccess) { (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr; }
-        if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(g.stream); (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr; }
-        for (uint32_t k = 0; k < GATE_RING; k++)
-            if (hipEventCreateWithFlags(&g.tail[k], hipEventDisableTiming) != hipSuccess) {
-                for (uint32_t j = 0; j < k; j++) (void)hipEventDestroy(g.tail[j]);
-                (void)hipEventDestroy(g.ev); (void)hipStreamDestroy(g.stream); (void)hipFree(g.words); g = ChainGate{}; g.failed = true; return nullptr;
-            }
-        g.failed = false;
-    }
-    return &g;
-}
-// The context's hint table on the current device for a T-tile image (allocated on first use, cleared when T changes); nullptr if
-// it cannot be had -- the forward then orders its blend by list length, as a first-seen pose does.
-HintTable* hints_of(gsrast_context* ctx, uint32_t T, hipStream_t s)
-{
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 32) return nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    // one table per tile count, up to four per device (train and eval resolutions, mixed camera sizes: each keeps its poses); a fifth
-    // size takes over the least recently used table's place (rare: drain, then start over)
-    gsrast_context::Hints* hp = nullptr;
-    for (auto& c : ctx->hints[device]) if (c.table && c.T == T) hp = &c;
-    if (!hp) {
-        for (auto& c : ctx->hints[device]) if (!c.table) { hp = &c; break; }
-        if (!hp) {
-            hp = &ctx->hints[device][0];
-            for (auto& c : ctx->hints[device]) if (c.used < hp->used) hp = &c;
-            (void)hipStreamSynchronize(s); (void)hipFree(hp->table); hp->table = nullptr;
-        }
-    }
-    auto& h = *hp;
-    h.used = ++ctx->hints_clock;
-    if (!h.table) {
-        if (hipMalloc((void**)&h.table, hint_table_bytes(T)) != hipSuccess) { h.table = nullptr; return nullptr; }
-        h.T = T;
-        if (hipMemsetAsync(h.table, 0, hint_zcut_offset(T), s) != hipSuccess ||
-            hipMemsetAsync(reinterpret_cast<char*>(h.table) + hint_zcut_offset(T), 0xFF, (size_t)HINT_SLOTS * T * 4, s) != hipSuccess) { (void)hipFree(h.table); h.table = nullptr; return nullptr; }
-    }
-    return h.table;
 }
 gsrast_context* thread_context()
 {   // deliberately leaked at thread exit -- the host words AND the device pose tables it has grown (12.5 MB per image size at 1080p, include/gsrast.h):
@@ -748,21 +798,7 @@ gsrast_context* gsrast_context_create(void) { return new (std::nothrow) gsrast_c
 void gsrast_context_destroy(gsrast_context* c)
 {
     if (!c) return;
-    for (auto& d : c->hints) for (auto& h : d) if (h.table) (void)hipFree(h.table);
-    for (ChainGate& g : c->gate) {
-        if (g.stream) { (void)hipStreamSynchronize(g.stream); (void)hipStreamDestroy(g.stream); }
-        if (g.ev) (void)hipEventDestroy(g.ev);
-        for (hipEvent_t e : g.tail) if (e) (void)hipEventDestroy(e);
-        if (g.words) (void)hipFree(g.words);
-    }
-    for (uint32_t* z : c->zhist_dev) if (z) (void)hipFree(z);
-    for (uint32_t* z : c->tau_dev) if (z) (void)hipFree(z);
-    for (SideStream& x : c->side) {
-        if (x.stream) { (void)hipStreamSynchronize(x.stream); (void)hipStreamDestroy(x.stream); }
-        if (x.fork) (void)hipEventDestroy(x.fork);
-        if (x.join) (void)hipEventDestroy(x.join);
-        if (x.join2) (void)hipEventDestroy(x.join2);
-    }
+    for (DeviceState& d : c->dev) d.release();
     delete c;
 }
 int gsrast_context_query(const gsrast_context* c, const char* name)
@@ -773,7 +809,7 @@ int gsrast_context_query(const gsrast_context* c, const char* name)
     if (!strcmp(name, "last_runs")) return (int)c->last_Q.load();
     if (!strcmp(name, "last_prologue_ns")) return (int)c->last_prologue_ns.load();
     if (!strcmp(name, "redo_count")) return c->redo_count.load();
-    if (!strcmp(name, "bucket_skip")) return c->bucket_skip.load();
+    if (!strcmp(name, "bucket_skip")) return c->zsort.skip.load();
     if (!strcmp(name, "last_late")) return (int)c->last_late.load();
     if (!strcmp(name, "last_early_runs")) return (int)c->last_Qe.load();
     if (!strcmp(name, "completion_passes")) return (int)c->pol.passes_reported.load();
@@ -781,16 +817,16 @@ int gsrast_context_query(const gsrast_context* c, const char* name)
     if (!strcmp(name, "tau_force")) return c->pol.tau_force.load();
     if (!strcmp(name, "cut_margin_x4")) return c->pol.margin.load();      // the list cut's current margin, in quarters (6 = 1.5 x)
     if (!strcmp(name, "gate_inline_calls")) {     // cut forwards that ran their completion pass inline because the gate's ring was half full
-        int device = 0; if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 32) return 0;
-        return (int)c->gate[device].inline_calls;
+        const int device = current_device();
+        return device < 0 ? 0 : (int)c->dev[device].gate.inline_calls;
     }
     if (!strcmp(name, "cut_pause")) return c->pol.pause.load();      // forwards the list cut still sits out (too little saved, or its lists kept failing)
     if (!strcmp(name, "cut_fallbacks")) {       // a device counter in the hint table of the current device (diagnostic: waits for the device)
-        int device = 0;
-        if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 32) return 0;
+        const int device = current_device();
+        if (device < 0) return 0;
         if (hipDeviceSynchronize() != hipSuccess) return GSRAST_E_DEVICE;
         uint32_t sum = 0;                       // (over the device's tables: one per image size)
-        for (const auto& h : c->hints[device]) {
+        for (const auto& h : c->dev[device].hints) {
             uint32_t v = 0;
             if (h.table && hipMemcpy(&v, &h.table->cut_fallbacks, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return GSRAST_E_DEVICE;
             sum += v;
@@ -818,7 +854,11 @@ int gsrast_policy_event(gsrast_context* c, const char* what, int a, int b, int c
     if (!strcmp(what, "size")) return (int)early_launch_runs((uint32_t)a, (uint32_t)b, c3 != 0);
     if (!strcmp(what, "grow")) return (int)grow_capacity((uint32_t)a);
     if (!strcmp(what, "follow")) return (int)follow_hint((uint32_t)a, (uint32_t)b, c3);
-    if (!strcmp(what, "reset")) { c->pol.~CutPolicy(); new (&c->pol) CutPolicy(); return 0; }      // (tests: a fresh policy, whatever earlier calls left)
+    if (!strcmp(what, "depth_sort")) {      // a forward's outcome for the bucket depth sort's back-off: a = 0 radix (the bucket sort was asked for), 1 clean bucket sort, 2 overflow (b = 1: the table held every key)
+        if (a == 0) c->zsort.radix_forward(); else if (a == 1) c->zsort.clean_forward(); else if (a == 2) (void)c->zsort.overflow(b != 0); else return GSRAST_E_ARG;
+        return c->zsort.skip.load();
+    }
+    if (!strcmp(what, "reset")) { c->pol.~CutPolicy(); new (&c->pol) CutPolicy(); c->zsort.~DepthSortPolicy(); new (&c->zsort) DepthSortPolicy(); return 0; }      // (tests: fresh policies, whatever earlier calls left)
     if (!strcmp(what, "tau_min")) { pol.tau_min = std::max(1, a); pol.tau_req = std::max(1, a); return a; }      // (experiments: the predicted cut's requirement and its floor)
     if (!strcmp(what, "zrange")) {      // a = first | last << 16 occupied bin of a forward that used the context's current table -> the next table's shift (| 256 if that table had held every key)
         const uint32_t k = c->zrange.klo.load(); const int sh = c->zrange.shift.load();
@@ -828,7 +868,8 @@ int gsrast_policy_event(gsrast_context* c, const char* what, int a, int b, int c
     if (!strcmp(what, "zget")) return a == 0 ? (int)(c->zrange.klo.load() >> 8) : a == 1 ? c->zrange.shift.load() : (int)(c->zrange.khi.load() >> 8);      // (keys / 256: they do not fit an int)
     if (!strcmp(what, "get")) {
         switch (a) { case 0: return pol.pause.load(); case 1: return pol.fb_score.load(); case 2: return pol.margin.load(); case 3: return pol.tau_req.load();
-                     case 4: return pol.tau_force.load(); case 5: return pol.fb_pause.load(); default: return GSRAST_E_ARG; }
+                     case 4: return pol.tau_force.load(); case 5: return pol.fb_pause.load();
+                     case 6: return c->zsort.skip.load(); case 7: return c->zsort.backoff.load(); case 8: return c->zsort.clean.load(); default: return GSRAST_E_ARG; }
     }
     return GSRAST_E_ARG;
 }
@@ -995,6 +1036,7 @@ bool trace_on() { static const bool on = getenv("GSRAST_TRACE") != nullptr; retu
 // c: the call's record (include/gsrast.h: gsrast_forward_call).  Raw family: `raw` replaces the dense inputs (which are null), prefiltered is 0.
 struct ForwardRun {
     gsrast_context* const ctx; const gsrast_forward_call& c; const gsrast_options o; const std::chrono::steady_clock::time_point t_entry; const hipStream_t stream;
+    const int device; DeviceState* const dev;      // the calling thread's device (current_device(); indexes t_readback) and the context's record on it; -1 / nullptr: none
     ForwardPlan plan;
     const float *means3D, *shs, *opacities, *scales, *rotations;      // as the kernels see them (raw family: the model's leaves)
     const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{};
@@ -1008,7 +1050,7 @@ struct ForwardRun {
     uint32_t *zcut_used = nullptr, *tau_hist = nullptr, *zhist_call = nullptr; TauBins tau_bins{};
     HintTable* hints = nullptr;
     uint32_t zh_klo = 0, zh_wave_mask = 0; int zh_shift = 0;      // equalised depth buckets: the histogram's bins (range hint of this context), the sampled waves
-    bool zhist_ctx = false; int tau_ctx_device = -1;               // the depth histogram / the opacity-mass table this call fills is the context's (>= 0: on that device)
+    uint32_t *zhist_ctx = nullptr, *tau_ctx = nullptr;             // non-null: the depth histogram / the opacity-mass table this call fills is the context's (DeviceState), zeroed again by the bucket sort
     // Every exit after the fork must order the caller's stream behind the side stream: the colour kernel and the zero-fill write
     // into the geometry buffer, which the caller is free to release (on its stream) as soon as this function has returned -- an error
     // return (allocation failure, overflow, a failed launch) included: those drain the side stream.  The normal path enqueues the
@@ -1024,14 +1066,13 @@ struct ForwardRun {
     Readback *rb_pre = nullptr, *rb_flag = nullptr, *rb = nullptr; uint32_t *pre_alias = nullptr, *flag_alias = nullptr; uint32_t pre_seq = 0, flag_seq = 0;
     // the completion pass's gate (ChainGate): claimed when the cut forward's blend is launched -- its last workgroup is the gate
     ChainGate* gate = nullptr; uint32_t gseq = 0, *gdone = nullptr, *gpred = nullptr;
-    // {instances R (low word), column runs Q, -, R (high word, run-compressed path), ..., [8] significant depth-key bits,
-    //  [9] key base, [10] "three sort passes were assumed and were not enough"}
-    uint32_t counts[12] = { 0 }; uint32_t nQ1 = 0;
+    // the host's copy of the count block's first words, indexed by their names (gsrast_common.h: SC_R_LO ... SC_BUCKET_OVER)
+    uint32_t counts[kCountWords] = { 0 }; uint32_t nQ1 = 0;
     std::chrono::steady_clock::time_point t0, t1;
 
     ForwardRun(gsrast_context* ctx_, const gsrast_options* options, const gsrast_forward_call& c_, std::chrono::steady_clock::time_point t)
         : ctx(ctx_ ? ctx_ : thread_context()), c(c_), o(options ? *options : snapshot_defaults()), t_entry(t), stream((hipStream_t)c_.stream),
-          means3D(c_.means3D), shs(c_.shs), opacities(c_.opacities), scales(c_.scales), rotations(c_.rotations) {}
+          device(current_device()), dev(ctx->device_state(device)), means3D(c_.means3D), shs(c_.shs), opacities(c_.opacities), scales(c_.scales), rotations(c_.rotations) {}
 
     // ---- the plan, and the checks every entry point shares (before any device work or allocator callback) ----
     int check_and_plan(hipStream_t s)
@@ -1039,7 +1080,7 @@ struct ForwardRun {
         P = c.P; W = c.width; H = c.height;
         const bool raw_family = c.family == GSRAST_FAMILY_RAW;
         plan = plan_forward(o, PlanInputs{ c.flags, P, W, H, c.D, (raw_family ? c.raw && c.raw->features_dc : c.shs != nullptr), c.colors_precomp != nullptr,
-                                           ctx->bucket_skip.load(), ctx->R_hint.load(), ctx->last_Q.load(), ctx->depth_short.load() != 0 }, snapshot_switches());
+                                           ctx->zsort.skip.load(), ctx->R_hint.load(), ctx->last_Q.load(), ctx->zsort.depth_short.load() != 0 }, snapshot_switches());
         if (plan.refusal) return fail(GSRAST_E_ARG, plan.refusal);
         if (plan.aux) { out_acc_depth = c.out_acc_depth; out_alpha = c.out_alpha; }
         if (plan.aux && (!out_acc_depth || !out_alpha)) return fail(GSRAST_E_ARG, "forward: NULL acc_depth / alpha output");
@@ -1105,7 +1146,7 @@ struct ForwardRun {
         // it hides (measured: beside the geometry kernel + depth sort +55 us, beside the run emission + run sort +45 / +65 us, beside the
         // LDS-bound run_scatter_rows it starves itself and delays the blend) -- round 2 forked it at entry, the best of those by ~20 us.
         // The 64 B / Gaussian zero-fill of the backward's gradient records follows on the side stream, under the VALU-bound forward blend.
-        if (o.side_stream) fork.side = side_stream_of(ctx);
+        if (o.side_stream && dev) fork.side = dev->side_stream(ctx->mu);
         return GSRAST_OK;
     }
 
@@ -1114,15 +1155,14 @@ struct ForwardRun {
     int begin_policy(hipStream_t s)
     {
         // launch-order hints of the forward blend: per context, device and camera pose (gsrast_common.h)
-        hints = plan.want_hints ? hints_of(ctx, T, s) : nullptr;
+        hints = plan.want_hints && dev ? dev->hint_table(ctx->mu, T, s) : nullptr;
         CutPolicy& pol = ctx->pol;          // (the decisions: gsrast_policy.h)
         if (pol.begin_forward((uint32_t)P)) {     // (what was learned belongs to the scene it was learned on: a context that moves on to a scene of another size starts afresh)
             // keys, stamps, clock: every slot free again, ordered in front of this call's lookup -- of EVERY image size's table of this device (round 6,
             // the other resolutions' tables kept the old scene's cut depths, running maxima that take eight visits to fade)
-            int device = 0;
             std::lock_guard<std::mutex> lk(ctx->mu);
-            if (hints && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32)
-                for (auto& h : ctx->hints[device]) if (h.table) GS_HIP(hipMemsetAsync(h.table, 0, sizeof(HintTable) /* everything in front of work[] */, s));
+            if (hints)      // (a table was handed out: there is a record)
+                for (auto& h : dev->hints) if (h.table) GS_HIP(hipMemsetAsync(h.table, 0, sizeof(HintTable) /* everything in front of work[] */, s));
             ctx->pose_seen.clear(); ctx->Qe_hint = 0; ctx->Qe_hint_tau = 0;
         }
         // The cut does not need the pose table.  With remembered cut depths (a pose the table knows) the first pass lists what lies in front
@@ -1147,7 +1187,7 @@ struct ForwardRun {
         // list cut: the device says at once whether the pose has a slot in the table (RB_FOUND); the launches over the cut lists of a pose
         // that has none -- everything is early -- are sized for all column runs, not for the early runs of recent forwards (a launch
         // that turned out too small cost a first-seen pose a whole second forward: 1.35 instead of 1.05 ms forward-only at 3 M)
-        if (plan.cut) rb_pre = read_flag_prepare(&pre_alias, &pre_seq);
+        if (plan.cut) rb_pre = read_flag_prepare(device, &pre_alias, &pre_seq);
         return GSRAST_OK;
     }
 
@@ -1158,43 +1198,17 @@ struct ForwardRun {
         const int pf_grid = (P + PF_THREADS - 1) / PF_THREADS;
         float* cov_dbg = plan.debug_state ? at<float>(geom, GL.cov3D) : nullptr;     // 24 B / Gaussian nobody but gsrast_debug_export reads
         if (plan.bucket_sort) {      // the context's depth histogram on this device, zeroed again by the bucket sort (no memset launch per forward)
-            uint32_t* zr = nullptr;
-            int device = 0;
-            if (hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32) {
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                if (!ctx->zhist_dev[device]) {
-                    uint32_t* z = nullptr;
-                    if (hipMalloc((void**)&z, ZH_COPIES * ZH_BINS * sizeof(uint32_t)) == hipSuccess) {
-                        if (hipMemset(z, 0, ZH_COPIES * ZH_BINS * sizeof(uint32_t)) == hipSuccess) ctx->zhist_dev[device] = z; else (void)hipFree(z);
-                    }
-                }
-                zr = ctx->zhist_dev[device];
+            zhist_call = zhist_ctx = dev ? dev->depth_hist(ctx->mu) : nullptr;
+            if (!zhist_call) {      // (no context memory to be had: the call's own table and a memset, as before)
+                zhist_call = at<uint32_t>(geom, GL.zhist);
+                GS_HIP(hipMemsetAsync(zhist_call, 0, ZH_COPIES * ZH_BINS * sizeof(uint32_t), s));
             }
-            zhist_ctx = zr != nullptr;
-            if (!zr) {      // (no context memory to be had: the call's own table and a memset, as before)
-                zr = at<uint32_t>(geom, GL.zhist);
-                GS_HIP(hipMemsetAsync(zr, 0, ZH_COPIES * ZH_BINS * sizeof(uint32_t), s));
-            }
-            zhist_call = zr;
         }
         if (tau_hist) {      // the context's opacity-mass table where the bucket sort will zero it again behind tau_cut_kernel; else the call's own and a memset
             const size_t words = (size_t)TAU_COPIES * T * TAU_BINS;
-            int device = 0;
-            if (plan.bucket_sort && zhist_ctx && !plan.debug_state /* (diagnostics read the table back from the image buffer: tools/tau_debug.py) */ && (words & 3) == 0 && words / 4 <= 0xFFFFFFFFull && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 32) {
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                if (ctx->tau_dev_words[device] < words) {
-                    if (ctx->tau_dev[device]) { (void)hipFree(ctx->tau_dev[device]); ctx->tau_dev[device] = nullptr; ctx->tau_dev_words[device] = 0; }
-                    uint32_t* z = nullptr;
-                    if (hipMalloc((void**)&z, words * sizeof(uint32_t)) == hipSuccess) { ctx->tau_dev[device] = z; ctx->tau_dev_words[device] = words; ctx->tau_dev_dirty[device] = true; }
-                }
-                if (ctx->tau_dev[device]) {
-                    tau_hist = ctx->tau_dev[device]; tau_ctx_device = device;
-                    // (a fresh table, or a forward that filled it and never reached its bucket sort: zeroed here)
-                    if (ctx->tau_dev_dirty[device]) GS_HIP(hipMemsetAsync(tau_hist, 0, ctx->tau_dev_words[device] * sizeof(uint32_t), s));
-                    ctx->tau_dev_dirty[device] = true;
-                }
-            }
-            if (tau_ctx_device < 0) GS_HIP(hipMemsetAsync(tau_hist, 0, words * sizeof(uint32_t), s));
+            if (plan.bucket_sort && zhist_ctx && !plan.debug_state /* (diagnostics read the table back from the image buffer: tools/tau_debug.py) */ && (words & 3) == 0 && words / 4 <= 0xFFFFFFFFull)
+                tau_ctx = dev->mass_table(ctx->mu, words, s);
+            if (tau_ctx) tau_hist = tau_ctx; else GS_HIP(hipMemsetAsync(tau_hist, 0, words * sizeof(uint32_t), s));
         }
         const int nzero = plan.bucket_sort ? (int)nbk * BK_XCD + BK_XCD * BK_NBC_MAX : 0;      // (fine counters + the two-launch scatter's coarse ones, contiguous)
         unsigned long long* host_found = rb_pre ? reinterpret_cast<unsigned long long*>(pre_alias) + RB_FOUND : nullptr;
@@ -1241,11 +1255,11 @@ struct ForwardRun {
             // list cut: only the bucket's EARLY Gaussians are sorted (into the early set); the late ones count into bk_info's totals
             BucketSortArgs a = whole_buckets();
             if (plan.cut) { a.border = bk_order_e; a.bwincl = bk_wincl_e; a.binfo = bk_info_e; a.bwsum = bk_base_e; a.binfo_all = bk_info; }
-            a.zero_words = zhist_ctx ? zhist_call : nullptr; a.n_zero_words = ZH_COPIES * ZH_BINS;
-            if (tau_ctx_device >= 0) { a.zero_quads = reinterpret_cast<uint4*>(tau_hist); a.n_zero_quads = (uint32_t)((size_t)TAU_COPIES * T * TAU_BINS / 4); }
+            a.zero_words = zhist_ctx; a.n_zero_words = ZH_COPIES * ZH_BINS;
+            if (tau_ctx) { a.zero_quads = reinterpret_cast<uint4*>(tau_ctx); a.n_zero_quads = (uint32_t)((size_t)TAU_COPIES * T * TAU_BINS / 4); }
             launch_bucket_sort(s, a);
             GS_LAUNCHED("depth_bucket_sort");
-            if (a.zero_quads) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->tau_dev_dirty[tau_ctx_device] = false; }
+            if (a.zero_quads) { std::lock_guard<std::mutex> lk(ctx->mu); dev->tau_dirty = false; }
             totals_pending = true;      // by the run emission's last workgroup, or by depth_bucket_scan_kernel if the host needs them first
             return GSRAST_OK;
         }
@@ -1255,16 +1269,16 @@ struct ForwardRun {
                 GS_LAUNCHED("iota");
             }
             // the last pass also writes rectangle widths (and, for the instance-level binning, tile counts) in depth order
-            const SortAdapt<uint32_t, uint32_t> ad{ at<uint32_t>(geom, GL.keyC), at<uint32_t>(geom, GL.valC), at<uint32_t>(geom, GL.sort_minmax), scalars + 8, assume };
+            const SortAdapt<uint32_t, uint32_t> ad{ at<uint32_t>(geom, GL.keyC), at<uint32_t>(geom, GL.valC), at<uint32_t>(geom, GL.sort_minmax), scalars + SC_SIG, assume };
             int rc = radix_sort<uint32_t, uint32_t, GSRAST_DEPTH_ITEMS>(kA, vA, kB, vB, (uint32_t)P, 32, hist, scan_tmp, s, rect, plan.runbin ? nullptr : offsets, woffsets, nullptr, &ad);
             if (rc != GSRAST_OK) return rc;
         }
         ProfScope ps(K_SCAN_TILES, s);
         if (plan.runbin)   // only the widths are scanned (-> run offsets, Q); num_rendered is just the sum of the tile counts
-            return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s, nullptr, tiles, scalars, scalars + 3);
-        int rc = scan_u32(offsets, nullptr, (uint32_t)P, offsets, true, scan_tmp, scalars, s);
+            return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + SC_Q, s, nullptr, tiles, scalars + SC_R_LO, scalars + SC_R_HI);
+        int rc = scan_u32(offsets, nullptr, (uint32_t)P, offsets, true, scan_tmp, scalars + SC_R_LO, s);
         if (rc != GSRAST_OK) return rc;
-        return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + 1, s);   // column runs
+        return scan_u32(woffsets, nullptr, (uint32_t)P, woffsets, true, scan_tmp, scalars + SC_Q, s);   // column runs
     }
 
     // ---- plan, second phase: the device's word on the pose (written at the very start of preprocess_fwd, long before this point) ----
@@ -1364,7 +1378,7 @@ struct ForwardRun {
         uint16_t *rkA = at<uint16_t>(bin, RL.rkeyA), *rkB = at<uint16_t>(bin, RL.rkeyB);
         uint2 *rvA = at<uint2>(bin, RL.rvalA), *rvB = at<uint2>(bin, RL.rvalB);
         uint32_t *hist_x = at<uint32_t>(bin, RL.hist_x), *hist_y = at<uint32_t>(bin, RL.hist_y), *rscan = at<uint32_t>(bin, RL.scan_tmp), *plist_w = at<uint32_t>(bin, RL.point_list);
-        const uint32_t* Q_dev = counts_dev ? counts_dev + 1 : nullptr;
+        const uint32_t* Q_dev = counts_dev ? counts_dev + SC_Q : nullptr;
         const int xbits = tile_bits((size_t)cam.gx);
         {   ProfScope ps(K_EMIT, s);
             EmitArgs e{};
@@ -1392,7 +1406,7 @@ struct ForwardRun {
             launch_emit(s, e);
             GS_LAUNCHED("emit_column_runs"); }
         if (bucketed && mode != 2) totals_pending = false;
-        if (readback_after_emit) { int rc = read_u32_begin(scalars, s, 12, &rb); if (rc != GSRAST_OK) return rc; }
+        if (readback_after_emit) { int rc = read_u32_begin(device, scalars, s, kCountWords, &rb); if (rc != GSRAST_OK) return rc; }
         const uint32_t nblk = (nQ + RUNS_PER_BLOCK - 1) / RUNS_PER_BLOCK;
         ProfScope ps(K_SORT_TILE, s);
         int rc = radix_sort<uint16_t, uint2, GSRAST_RUN_SORT_ITEMS>(rkA, rvA, rkB, rvB, nQ, xbits, hist_x, rscan, s, nullptr, nullptr, nullptr, Q_dev, nullptr, pred);   // runs by column
@@ -1404,7 +1418,7 @@ struct ForwardRun {
         GS_LAUNCHED("radix_rowscan");
         // the row pass and the tile ranges in one launch (gsrast_binning.h)
         rows_and_ranges_kernel<<<nblk + (uint32_t)cam.gx, RS_THREADS, 0, s>>>(rkA, rvA, nQ, counts_dev, cap, tile_bits((size_t)cam.gy), cam.gx, cam.gy, hist_y, rscan, nblk,
-                                                                             mode == 2 ? plist_w + cap : plist_w, mode == 2 ? scalars + SC_PASS2 + 2 : scalars + 2, ranges,
+                                                                             mode == 2 ? plist_w + cap : plist_w, scalars + (mode == 2 ? SC_PASS2 : 0) + SC_LISTED, ranges,
                                                                              plan.buckets_ok ? bucket_cnt : nullptr, bucket_list, hints, hint_sel, pred,
                                                                              mode == 2 ? tile_flags : nullptr, mode == 2 ? cap : 0u,
                                                                              (mode == 1 && plan.tau_on) ? zcut_used : nullptr);
@@ -1436,7 +1450,7 @@ struct ForwardRun {
     // claims the completion pass's gate for the blend about to be launched; without one (gate == nullptr) the pass runs inline
     void claim_gate()
     {
-        if (!plan.chain_gate || counter_collection_env() || (gate = chain_gate_of(ctx)) == nullptr) return;
+        if (!plan.chain_gate || counter_collection_env() || !dev || (gate = dev->chain_gate(ctx->mu, device)) == nullptr) return;
         std::lock_guard<std::mutex> lk(ctx->mu);
         uint32_t n = gate->seq + 1u; if (n == 0u) n = 1u;
         // the slot of n was last used by n - GATE_RING; it is free once the chain of n - GATE_RING / 2 (enqueued later on the same
@@ -1500,11 +1514,11 @@ struct ForwardRun {
                 GS_LAUNCHED("depth_bucket_scan");
                 totals_pending = false;
             }
-            int rc = read_u32_begin(scalars, s, 12, &rb); if (rc != GSRAST_OK) return rc;
+            int rc = read_u32_begin(device, scalars, s, kCountWords, &rb); if (rc != GSRAST_OK) return rc;
         }
         if (!plan.speculative) return GSRAST_OK;
         const bool late = totals_pending;      // the counts arrive by the emission kernel's own store into pinned memory (no copy enqueued)
-        if (late) { if (rb_pre) { rb_flag = rb_pre; flag_alias = pre_alias; flag_seq = pre_seq; } else rb_flag = read_flag_prepare(&flag_alias, &flag_seq); }
+        if (late) { if (rb_pre) { rb_flag = rb_pre; flag_alias = pre_alias; flag_seq = pre_seq; } else rb_flag = read_flag_prepare(device, &flag_alias, &flag_seq); }
         // (list cut: the sorts over the cut lists are sized for the early runs of recent forwards, not for all runs)
         // (the early set differs from pose to pose -- 0.98 M / 1.29 M column runs at two neighbouring poses of the 3 M cube --, a launch
         // sized too small costs a whole second forward, one sized too large a few empty workgroups: half again as much as the largest of
@@ -1522,38 +1536,29 @@ struct ForwardRun {
     {
         ctx->redo_count++;
         int rc = sort_and_scan(s, false, false);
-        if (rc == GSRAST_OK) rc = read_u32(scalars, s, counts, 12);
+        if (rc == GSRAST_OK) rc = read_u32(device, scalars, s, counts, kCountWords);
         sort_redone = true;
         return rc;
     }
     // ---- the counts arrive; what they say about the depth sort: the histogram's range, the bucket sort's back-off, a sort to be repeated ----
     int absorb_depth_sort(hipStream_t s)
     {
-        { int rc = rb_flag ? read_flag_finish(rb_flag, scalars, s, counts, 12) : read_u32_finish(rb, scalars, s, counts, 12); if (rc != GSRAST_OK) return rc; }
-        if (!plan.bucket_sort && o.depth_sort == 0) dec_to_zero(ctx->bucket_skip);
+        { int rc = rb_flag ? read_flag_finish(rb_flag, scalars, s, counts) : read_u32_finish(rb, scalars, s, counts, kCountWords); if (rc != GSRAST_OK) return rc; }
+        DepthSortPolicy& zs = ctx->zsort;      // (the decisions: gsrast_policy.h)
+        if (!plan.bucket_sort && o.depth_sort == 0) zs.radix_forward();
         if (plan.bucket_sort) {
-            if (counts[11] == 0 && ctx->bucket_clean.load() < 1024 && ++ctx->bucket_clean >= 64) ctx->bucket_backoff = 0;      // the scene changed: forget
-            if (counts[11] != 0) {      // more Gaussians at (nearly) one depth than a bucket holds: sort again with the radix passes
-                const int clean_before = ctx->bucket_clean.exchange(0);
-                // An ISOLATED overflow (32 clean forwards before it: one pose of a cycle whose depth profile has a hard edge inside a
-                // histogram bin, which doubles a few buckets' share and now and then tips one over) costs this one repeat and nothing
-                // else.  Overflows in quick succession start with the radix passes for a while -- exponential back-off: 16 radix forwards,
-                // twice as many after each further one (a scene whose depths pile up for good pays the discarded speculative launch ever
-                // more rarely), capped at 4096 --
-                // ... unless the histogram behind the bucket map was not up to this view (a context's first forward: four bins per octave;
-                // a depth range that has moved out of the table): the range is learned from this call, the next forward tries again at once
-                if (ctx->zrange.learn(counts[SC_ZBINS], zh_klo, zh_shift) && (clean_before < 32 || ctx->bucket_backoff.load() > 0))
-                { const int prev = ctx->bucket_backoff.load(); const int next = prev <= 0 ? 16 : (prev >= 2048 ? 4096 : prev * 2);
-                  ctx->bucket_backoff = next; ctx->bucket_skip = next; }
-                ctx->depth_short = 0;   // the radix path's pass-count hint is stale (not refreshed on the bucket path): assume four passes
+            if (counts[SC_BUCKET_OVER] == 0) zs.clean_forward();
+            else {      // more Gaussians at (nearly) one depth than a bucket holds: sort again with the radix passes
+                // (the histogram's range is learned from this call either way; whether its table was up to the view decides about a pause)
+                zs.overflow(ctx->zrange.learn(counts[SC_ZBINS], zh_klo, zh_shift));
                 int rc = sort_again(s); if (rc != GSRAST_OK) return rc;
-                if (plan.adaptive_sort) ctx->depth_short = counts[8] <= 24u ? 1 : 0;
+                if (plan.adaptive_sort) zs.radix_key_bits(counts[SC_KEY_BITS]);
             }
         } else if (plan.adaptive_sort) {
-            if (plan.assume_short && counts[10] != 0) { int rc = sort_again(s); if (rc != GSRAST_OK) return rc; }      // the scene's depth range widened
-            ctx->depth_short = counts[8] <= 24u ? 1 : 0;
+            if (plan.assume_short && counts[SC_SHORT_WRONG] != 0) { int rc = sort_again(s); if (rc != GSRAST_OK) return rc; }      // the scene's depth range widened
+            zs.radix_key_bits(counts[SC_KEY_BITS]);
         }
-        if (plan.runbin && counts[3] != 0) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
+        if (plan.runbin && counts[SC_R_HI] != 0) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
         return GSRAST_OK;
     }
     // ---- what the counts teach the context: capacity hints, the early set's size, the cut's policy (gsrast_policy.h) ----
@@ -1562,24 +1567,24 @@ struct ForwardRun {
         const auto t2 = std::chrono::steady_clock::now();
         CutPolicy& pol = ctx->pol;
         if (trace_on()) fprintf(stderr, "[gsrast] alloc(spec) %.1f us, readback wait %.1f us, cap %u R %u Q %u%s | cut %d (pays %d: last_Q %u pause %d) late %u Q_early %u nQ1 %u capQ %u bucket_sort %d (over %u) hints %d zh %08x >> %d bins %u-%u\n",
-                               std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(), cap, counts[0], counts[1],
+                               std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(), cap, counts[SC_R_LO], counts[SC_Q],
                                plan.speculative ? " (speculative)" : "", (int)plan.cut, (int)plan.cut_pays, ctx->last_Q.load(), pol.pause.load(), counts[SC_N_LATE], counts[SC_Q_EARLY], nQ1, capQ,
-                               (int)plan.bucket_sort, counts[11], hints ? 1 : 0, zh_klo, zh_shift, counts[SC_ZBINS] & 0xFFFFu, counts[SC_ZBINS] >> 16);
-        if (counts[0] > 0x7FFFFFFFu) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
-        const uint32_t R = counts[0], Q = counts[1];
+                               (int)plan.bucket_sort, counts[SC_BUCKET_OVER], hints ? 1 : 0, zh_klo, zh_shift, counts[SC_ZBINS] & 0xFFFFu, counts[SC_ZBINS] >> 16);
+        if (counts[SC_R_LO] > 0x7FFFFFFFu) return fail(GSRAST_E_OVERFLOW, "forward: more than 2^31-1 instances");
+        const uint32_t R = counts[SC_R_LO], Q = counts[SC_Q];
         if (plan.bucket_sort && !sort_redone) (void)ctx->zrange.learn(counts[SC_ZBINS], zh_klo, zh_shift);
         // capacity hints decay slowly: consecutive calls render different views, a buffer sized for the largest recent one
         // keeps the speculative launch valid
         ctx->R_hint = follow_hint(ctx->R_hint.load(), R, 4); ctx->Q_hint = follow_hint(ctx->Q_hint.load(), Q, 4);
         ctx->last_R = R; ctx->last_Q = Q;
-        ctx->last_late = plan.cut ? counts[SC_N_LATE] : 0u; ctx->last_Qe = plan.cut ? counts[SC_Q_EARLY] : counts[1];
+        ctx->last_late = plan.cut ? counts[SC_N_LATE] : 0u; ctx->last_Qe = plan.cut ? counts[SC_Q_EARLY] : Q;
         // (a cut forward that removed too little to pay for itself; round 5: FOUR in a row before the context sits out)
-        if (plan.cut) pol.forward_counts(plan.tau_on, counts[SC_N_LATE], counts[1], counts[SC_Q_EARLY], (uint32_t)P, plan.list_cut_always);
+        if (plan.cut) pol.forward_counts(plan.tau_on, counts[SC_N_LATE], Q, counts[SC_Q_EARLY], (uint32_t)P, plan.list_cut_always);
         if (plan.cut && plan.speculative && !sort_redone) { std::atomic<uint32_t>& hint = early_hint(); hint = follow_hint(hint.load(), counts[SC_Q_EARLY], 5); }
         // fallbacks of this thread's earlier cut forwards, as the device reported them (everything enqueued before this forward's counts has run)
         // (a completion pass over a few tiles is cheap and expected; its cost grows with the tiles it lists again: one over an eighth of
         // the image counts like rounds 3's whole second forward, smaller ones in proportion)
-        if (const uint32_t q2 = take_fallback_event()) {       // (the column runs of the pass's candidates)
+        if (const uint32_t q2 = take_fallback_event(device)) {       // (the column runs of the pass's candidates)
             const int before = pol.fb_score.load();
             const int pts = pol.completion_pass(q2, ctx->last_Q.load(), (uint32_t)P, plan.list_cut_always, plan.tau_mode);
             if (trace_on()) fprintf(stderr, "[gsrast] completion pass reported: %u column runs of %u, %d points on a score of %d; margin %d / 4, tau_req %d, pause %d\n", q2, ctx->last_Q.load(), pts, before,
@@ -1680,7 +1685,7 @@ static int forward_impl(gsrast_context* ctx, const gsrast_options* options, cons
     if ((rc = r.speculative_buffer(s)) != GSRAST_OK || (rc = r.launch_color(s)) != GSRAST_OK || (rc = r.speculative_launch(s)) != GSRAST_OK) return rc;
     if ((rc = r.absorb_depth_sort(s)) != GSRAST_OK || (rc = r.absorb_counts()) != GSRAST_OK) return rc;
     const ForwardPlan& plan = r.plan;
-    const uint32_t R = r.counts[0], Q = r.counts[1];
+    const uint32_t R = r.counts[SC_R_LO], Q = r.counts[SC_Q];
     const bool early_fits = !plan.cut || r.counts[SC_Q_EARLY] <= r.nQ1;
     if (!(plan.speculative && !r.sort_redone && R <= r.cap && Q <= r.capQ && early_fits)) return r.exact_redo(s, R, Q);
     // everything is already in flight
@@ -2099,6 +2104,7 @@ namespace {
 struct BackwardRun {
     gsrast_backward_call c; const bool raw_family;      // (a copy: the raw family's leaves and gradient arrays take the dense pointers' places)
     gsrast_options o; const hipStream_t s;
+    DeviceState* const dev;      // the calling thread's context's record on its current device (the backward's side stream); nullptr: none
     BackwardPlan plan;
     const gsrast_raw_inputs* rawin = nullptr; RawArgs raw{}; RawGrads rawg{};
     CamArgs cam; GeomLayout GL; ImgLayout IL; char *geom = nullptr, *img = nullptr;
@@ -2110,7 +2116,8 @@ struct BackwardRun {
         ~SideJoinGuard() { if (side && !joined) (void)hipStreamSynchronize(side->stream); }
     } fork;
 
-    BackwardRun(const gsrast_options* options, const gsrast_backward_call& c_) : c(c_), raw_family(c_.family == GSRAST_FAMILY_RAW), o(options ? *options : snapshot_defaults()), s((hipStream_t)c_.stream) {}
+    BackwardRun(const gsrast_options* options, const gsrast_backward_call& c_) : c(c_), raw_family(c_.family == GSRAST_FAMILY_RAW), o(options ? *options : snapshot_defaults()), s((hipStream_t)c_.stream),
+          dev(thread_context()->device_state(current_device())) {}
 
     // ---- the plan, and the checks every entry point shares (before any device work) ----
     int check_and_plan()
@@ -2176,7 +2183,7 @@ struct BackwardRun {
     int fork_derivs()
     {
         if (plan.derivs && rawin) return fail(GSRAST_E_ARG, "backward_raw: the forward was run with forward_only");
-        if (plan.wants_side() && (fork.side = side_stream_of(thread_context()))) { GS_HIP(hipEventRecord(fork.side->fork, s)); GS_HIP(hipStreamWaitEvent(fork.side->stream, fork.side->fork, 0)); }
+        if (plan.wants_side() && dev && (fork.side = dev->side_stream(thread_context()->mu))) { GS_HIP(hipEventRecord(fork.side->fork, s)); GS_HIP(hipStreamWaitEvent(fork.side->stream, fork.side->fork, 0)); }
         plan.side_answer(fork.side != nullptr);
         if (!plan.derivs) return GSRAST_OK;
         const hipStream_t ds = plan.derivs_on_side ? fork.side->stream : s;

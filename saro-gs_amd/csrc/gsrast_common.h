@@ -28,7 +28,7 @@ constexpr int WAVE = 64;            // CDNA4 wavefront
 //   keyA/B   u32[P] x2   depth-sort ping-pong keys        valA/B u32[P] x2   ping-pong values
 //   offsets  u32[P]      inclusive scan of tiles[] in depth order
 //   hist     u32[256*nblk(P)]   radix block histograms    scan_tmp u32[...]  scan partials
-//   scalars  u32[64]     [0] = num_rendered ... [8] = significant bits of the depth keys (adaptive pass count of the depth sort)
+//   scalars  u32[64]     the call's count block: every word has a name (SC_*, HINT_*: the one map further down)
 //   keyC/valC u32[P] x2  third buffer pair of the depth sort, sort_minmax u32[2 nblk]: per-block key minimum / maximum
 //   shdA/B   float4[P] x2, shdC f32[P]   d(colour)/d(view direction) {dx[3], dy[3], dz[3]}, 36 B: written by the forward's colour kernel
 //                        while the SH block is in LDS (round 3; sh_dir_derivs_kernel in the backward for a forward_only state), so that the
@@ -167,16 +167,42 @@ struct HintTable {
     uint32_t clock, cut_fallbacks /* forwards whose cut lists turned out too short and were binned and blended again (diagnostic) */, pad[2];
     // followed by uint16_t work[HINT_SLOTS][T], then (4-byte aligned) uint32_t zcut[HINT_SLOTS][T]
 };
-// A forward's own choice -- {slot, 1 = "the slot held estimates of this pose when the forward began"} -- lives in ITS geometry buffer
-// (scalars[HINT_SEL], [HINT_SEL + 1]), so two forwards of one context in flight on two streams do not read each other's slot.
+// ---- GeomLayout::scalars: every word of a forward's count block, in index order (u32[64]; a word without a name is unused) ------------
+// Kernels and host index the block -- and the host's copy of it, ForwardRun::counts -- by these names only.
+constexpr int SC_R_LO = 0;            // instances (num_rendered), low word
+constexpr int SC_Q = 1;               // column runs
+constexpr int SC_LISTED = 2;          // the range kernel's output: instances rows_and_ranges_kernel wrote (<= R with row clipping)
+constexpr int SC_R_HI = 3;            // instances, high word (run-compressed path): non-zero = more than 2^32-1, refused
+// (the four-word groups at SC_EARLY_COUNTS and SC_PASS2 are laid out like words 0-3: group + SC_R_LO, + SC_Q, + SC_LISTED, + SC_R_HI)
+constexpr int SC_Q_EARLY = 4;         // list cut: column runs of the early Gaussians
+constexpr int SC_N_LATE = 5;          // list cut: late Gaussians (0: the cut was not in force, or everything was listed after all)
+constexpr int SC_UNDONE = 6, SC_REDO_PRED = SC_UNDONE;   // list cut: tiles whose cut list was too short -- the predicate of the second binning + blend
+constexpr int SC_ZBINS = 7;           // first | last << 16 occupied bin of the sampled depth histogram (0xFFFFFFFF: no sample)
+constexpr int SC_SIG = 8;             // the adaptive radix depth sort's three words (SortAdapt::sig points here), by offset:
+constexpr int SIG_BITS = 0, SIG_BASE = 1, SIG_WRONG = 2;
+constexpr int SC_KEY_BITS = SC_SIG + SIG_BITS;        // [8] significant bits of the depth keys (<= 24: three passes do)
+constexpr int SC_KEY_BASE = SC_SIG + SIG_BASE;        // [9] key base (the smallest key with its low byte cleared)
+constexpr int SC_SHORT_WRONG = SC_SIG + SIG_WRONG;    // [10] "three sort passes were assumed and were not enough"
+constexpr int SC_BUCKET_OVER = 11;    // the bucket depth sort's overflow verdict: more Gaussians at (nearly) one depth than a bucket holds
+// A forward's own choice of launch-order hints -- {slot, 1 = "the slot held estimates of this pose when the forward began"} -- lives in ITS geometry
+// buffer (scalars[HINT_SEL], [HINT_SEL + 1]), so two forwards of one context in flight on two streams do not read each other's slot.
 constexpr int HINT_SEL = 16;
+constexpr int SC_EARLY_COUNTS = 20;   // [20..23] {R lo, Q early, -, R hi}: what the launches over the cut lists read on the device
+constexpr int SC_PASS2 = 24;          // [24..27] {instances (tile counts) lo, column runs, listed, hi} of the completion pass's candidates
+constexpr int SC_GATE_COUNT = 28;     // workgroups of the cut forward's blend that have finished (its last one is the completion pass's gate)
 // ... and what the forward blend PUBLISHES into a newly claimed slot once the call's lists exist (round 5: preprocess_fwd's block 0 used to
 // write the key while the kernel's other lookup blocks read the table): scalars[HINT_PUB] = 1 "publish", [+1, +2] the pose's key
 constexpr int HINT_PUB = 32;
-constexpr int SC_GREC_SPARSE = 46;    // scalars: 1 = only the gradient records of the Gaussians whose untouched bit is CLEAR were zeroed (grec_zero_touched_kernel): every
+constexpr int SC_PREFILTER = 44;      // set by preprocess_fwd when a Gaussian is culled although the caller passed prefiltered = 1
+constexpr int SC_TOUCH_VALID = 45;    // 1 = this forward's blend kept GeomLayout::untouched (the backward trusts the bits)
+constexpr int SC_GREC_SPARSE = 46;    // 1 = only the gradient records of the Gaussians whose untouched bit is CLEAR were zeroed (grec_zero_touched_kernel): every
                                       // other record holds whatever the buffer held -- its readers take it for zero (record_is_stale)
-constexpr int SC_TOUCH_VALID = 45;    // scalars: 1 = this forward's blend kept GeomLayout::untouched (the backward trusts the bits)
-constexpr int SC_PREFILTER = 44;      // scalars: set by preprocess_fwd when a Gaussian is culled although the caller passed prefiltered = 1
+// The pinned read-back (depth_bucket_totals stores, the host's read_flag_finish decodes): 64-bit words {value, sequence number}, word k
+// carries scalars[kReadbackWord[k]].  The words behind them belong to other writers:
+constexpr int kReadbackWord[] = { SC_R_LO, SC_Q, SC_BUCKET_OVER, SC_R_HI, SC_Q_EARLY, SC_N_LATE, SC_ZBINS };
+constexpr int RB_WORDS = (int)(sizeof kReadbackWord / sizeof kReadbackWord[0]);
+constexpr int RB_FOUND = 7;        // {1 = the pose had a slot in the context's table, sequence number}: preprocess_fwd, at its very start
+constexpr int RB_FALLBACK = 8;     // {1, sequence number of the call}: the predicated second binning of a list-cut forward has run
 __host__ __device__ inline uint16_t* hint_work(HintTable* h, uint32_t) { return reinterpret_cast<uint16_t*>(h + 1); }
 __host__ __device__ inline const uint16_t* hint_work(const HintTable* h, uint32_t) { return reinterpret_cast<const uint16_t*>(h + 1); }
 static inline size_t hint_zcut_offset(size_t T) { return (sizeof(HintTable) + (size_t)HINT_SLOTS * T * 2 + 255) & ~(size_t)255; }
@@ -236,12 +262,7 @@ __host__ __device__ inline uint32_t tau_bin_far_edge(uint32_t b, const TauBins& 
     return k >= (unsigned long long)ZH_KEY_TOP ? ZCUT_NONE : (uint32_t)k;
 }
 constexpr uint32_t LATE_BIT = 0x80000000u;      // in the width word of a bucket-slab element
-// words of GeomLayout::scalars used by the list cut
-constexpr int SC_ZBINS = 7 /* first | last << 16 occupied bin of the sampled depth histogram (0xFFFFFFFF: no sample) */;
 constexpr int GATE_WORDS = 80;      // 64 first-level counters of finished workgroups + 1 second-level (ImgLayout::bucket_cnt's tail)
-constexpr int SC_GATE_COUNT = 28 /* workgroups of the cut forward's blend that have finished (its last one is the completion pass's gate) */;
-constexpr int SC_PASS2 = 24 /* {instances (tile counts) lo, column runs, -, hi} of the completion pass's candidates */;
-constexpr int SC_Q_EARLY = 4, SC_N_LATE = 5, SC_UNDONE = 6, SC_EARLY_COUNTS = 20 /* {R lo, Q early, -, R hi} */, SC_REDO_PRED = SC_UNDONE /* the predicate of the second binning + blend: some tile's cut list was too short */;
 
 constexpr int RS_THREADS = 256;     // radix sort: 4 waves
 constexpr uint32_t RS_SELF_SCAN_BLOCKS = 64;   // sorts of at most this many blocks skip the row-scan launch (radix_scatter_kernel)

@@ -1,5 +1,5 @@
 // gsrast_policy.h -- the HOST-side decisions of a render call, free of any HIP call: when the list cut is applied, paused and widened, how
-// the speculative launch is sized, how the depth histogram's range follows the scene, which path a call takes (ForwardPlan, BackwardPlan).  gsrast_capi.hip
+// the speculative launch is sized, how the depth histogram's range follows the scene, when the bucket depth sort backs off to the radix passes, which path a call takes (ForwardPlan, BackwardPlan).  gsrast_capi.hip
 // enqueues; this file decides.  Everything here runs on a CPU box: tests/test_policy.py drives it through gsrast_policy_event(),
 // gsrast_debug_forward_plan() and gsrast_debug_backward_plan() (include/gsrast.h), which touch no device.  No result of a call depends on any of it -- only how much work the call enqueues.
 #pragma once
@@ -139,6 +139,34 @@ struct DepthRange {
         klo = (uint32_t)lo; shift = sh; khi = (uint32_t)hi;
         return !was_coarse && !clipped;
     }
+};
+
+// ---- the bucket depth sort's back-off (gsrast_binning.h: a bucket overflowed -- more Gaussians at (nearly) one depth than it holds) ----
+// An ISOLATED overflow (32 clean forwards before it: one pose of a cycle whose depth profile has a hard edge inside a histogram bin, which
+// doubles a few buckets' share and now and then tips one over) costs that forward its repeat and nothing else.  Overflows in quick
+// succession start with the radix passes for a while -- exponential back-off: 16 radix forwards, twice as many after each further one (a
+// scene whose depths pile up for good pays the discarded speculative launch ever more rarely), capped at 4096 -- unless the histogram
+// behind the bucket map was not up to the view (a context's first forward: four bins per octave; a depth range that has moved out of the
+// table): the range is learned from that call, the next forward tries again at once.  64 clean forwards forget the length.
+struct DepthSortPolicy {
+    std::atomic<int> skip{0};         // > 0: that many forwards go straight to the radix sort ("bucket_skip")
+    std::atomic<int> backoff{0}, clean{0};   // length of the last such pause (doubles per overflow), bucket-sorted forwards without an overflow since (saturates at 1024)
+    std::atomic<int> depth_short{0};  // the last radix-sorted forward's depth keys spanned < 2^24: the next one enqueues three sort passes, not four
+    // a forward that went to the radix sort although the caller asked for the bucket sort serves one forward of the pause
+    void radix_forward() { dec_to_zero(skip); }
+    void clean_forward() { if (clean.load() < 1024 && ++clean >= 64) backoff = 0; }      // the scene changed: forget
+    // table_held: the histogram's table was a learned one that held every key (DepthRange::learn's return).  Returns the pause.
+    int overflow(bool table_held)
+    {
+        const int clean_before = clean.exchange(0);
+        if (table_held && (clean_before < 32 || backoff.load() > 0)) {
+            const int prev = backoff.load(), next = prev <= 0 ? 16 : (prev >= 2048 ? 4096 : prev * 2);
+            backoff = next; skip = next;
+        }
+        depth_short = 0;   // the radix path's pass-count hint is stale (not refreshed on the bucket path): assume four passes
+        return skip.load();
+    }
+    void radix_key_bits(uint32_t bits) { depth_short = bits <= 24u ? 1 : 0; }      // after a radix sort with adaptive pass count
 };
 
 // ---- capacities of the speculative launch --------------------------------------------------------------------------------------------

@@ -147,6 +147,23 @@ def test_python_context_handle(scenes, rast, gpu):
             assert all(torch.equal(x, y) for x, y in zip(inner, want_a))
         assert all(torch.equal(x, y) for x, y in zip(got, want_b))
     assert c1.query("last_instances") != c2.query("last_instances")      # two poses, two contexts: each remembers its own last forward
+    # the same two poses under the list cut, so that c1 owns everything a context can own on a device (side stream, pose table, depth histogram,
+    # opacity-mass table, the completion pass's gate) when it is closed; the cut changes no result
+    _C.set_option("list_cut_always", 1)
+    try:
+        with c1:
+            for _ in range(3):
+                cut = [render(rs_a), render(rs_b)]
+                late = c1.query("last_late")
+                _C.set_option("no_list_cut", 1)
+                try:
+                    plain = [render(rs_a), render(rs_b)]
+                finally:
+                    _C.set_option("no_list_cut", 0)
+                assert all(torch.equal(x, y) for got, want in zip(cut, plain) for x, y in zip(got, want))
+            assert late > 0                             # ... and it was in force: Gaussians were left out of the lists
+    finally:
+        _C.set_option("list_cut_always", 0)
     torch.cuda.synchronize()
     c1.close(); c2.close()
     with pytest.raises(RuntimeError):

@@ -189,6 +189,78 @@ def test_depth_range_widens_at_once_and_narrows_slowly(ctx):
     assert prev < wide // 4
 
 
+# ---- the bucket depth sort's back-off (gsrast_policy.h: DepthSortPolicy): "depth_sort" a = RADIX / CLEAN / OVERFLOW, b = 1: the table held every key ----
+RADIX, CLEAN, OVERFLOW = range(3)
+BUCKET_SKIP, BUCKET_BACKOFF, BUCKET_CLEAN = 6, 7, 8
+
+
+def test_an_isolated_bucket_overflow_is_free(ctx):
+    ev = ctx.policy_event
+    for n in (32, 33, 63):          # 32 or more clean forwards before it, no length remembered: this forward's repeat and nothing else
+        for _ in range(n):
+            assert ev("depth_sort", CLEAN) == 0
+        assert ev("depth_sort", OVERFLOW, 1) == 0, n
+        assert ev("get", BUCKET_SKIP) == 0 and ev("get", BUCKET_BACKOFF) == 0 and ev("get", BUCKET_CLEAN) == 0
+
+
+def test_bucket_overflows_in_quick_succession_back_off_and_double(ctx):
+    ev = ctx.policy_event
+    for _ in range(31):
+        ev("depth_sort", CLEAN)
+    assert ev("depth_sort", OVERFLOW, 1) == 16          # fewer than 32 clean forwards before it: 16 radix forwards
+    assert ev("get", BUCKET_SKIP) == 16 and ev("get", BUCKET_BACKOFF) == 16
+    for left in range(15, -1, -1):                      # every radix forward serves one forward of the pause
+        assert ev("depth_sort", RADIX) == left
+    assert ev("depth_sort", RADIX) == 0                 # (never below zero)
+    want = 32
+    for _ in range(12):                                 # every further overflow: twice the remembered length, 4096 at most -- however many clean forwards (< 64) lie between
+        for _ in range(40):
+            ev("depth_sort", CLEAN)
+        assert ev("depth_sort", OVERFLOW, 1) == want
+        assert ev("get", BUCKET_BACKOFF) == want
+        want = min(want * 2, 4096)
+    assert want == 4096 and ev("get", BUCKET_SKIP) == 4096
+
+
+def test_64_clean_forwards_forget_the_back_off_length(ctx):
+    ev = ctx.policy_event
+    assert ev("depth_sort", OVERFLOW, 1) == 16 and ev("depth_sort", OVERFLOW, 1) == 32
+    for _ in range(32):
+        ev("depth_sort", RADIX)
+    assert ev("get", BUCKET_SKIP) == 0 and ev("get", BUCKET_BACKOFF) == 32
+    for k in range(63):
+        ev("depth_sort", CLEAN)
+        assert ev("get", BUCKET_BACKOFF) == 32, k
+    ev("depth_sort", CLEAN)
+    assert ev("get", BUCKET_BACKOFF) == 0 and ev("get", BUCKET_CLEAN) == 64
+    assert ev("depth_sort", OVERFLOW, 1) == 0           # the next isolated overflow is free again
+    assert ev("get", BUCKET_BACKOFF) == 0
+
+
+def test_an_overflow_under_a_table_that_did_not_hold_every_key_never_pauses(ctx):
+    ev = ctx.policy_event
+    for _ in range(5):                                  # b = 0: the histogram was not up to the view; its range is learned, the next forward tries again
+        assert ev("depth_sort", OVERFLOW, 0) == 0
+    assert ev("get", BUCKET_BACKOFF) == 0
+    assert ev("depth_sort", OVERFLOW, 1) == 16          # ... also while a length is remembered and a pause is being served: neither grows
+    assert ev("depth_sort", OVERFLOW, 0) == 16
+    assert ev("get", BUCKET_SKIP) == 16 and ev("get", BUCKET_BACKOFF) == 16 and ev("get", BUCKET_CLEAN) == 0
+
+
+def test_the_clean_count_saturates_and_reset_clears_the_back_off(ctx):
+    ev = ctx.policy_event
+    for _ in range(1100):
+        ev("depth_sort", CLEAN)
+    assert ev("get", BUCKET_CLEAN) == 1024
+    assert ev("depth_sort", OVERFLOW, 1) == 0 and ev("get", BUCKET_CLEAN) == 0
+    assert ev("depth_sort", OVERFLOW, 1) == 16 and ev("depth_sort", CLEAN) == 16
+    assert (ev("get", BUCKET_SKIP), ev("get", BUCKET_BACKOFF), ev("get", BUCKET_CLEAN)) == (16, 16, 1)
+    assert ev("reset") == 0
+    assert (ev("get", BUCKET_SKIP), ev("get", BUCKET_BACKOFF), ev("get", BUCKET_CLEAN)) == (0, 0, 0)
+    with pytest.raises(ValueError):                     # (an unknown outcome is refused)
+        ev("depth_sort", 3)
+
+
 # ---- the forward's plan (gsrast_policy.h: ForwardPlan) through gsrast_debug_forward_plan: what a forward WOULD decide, no device involved ----
 (RUNBIN, BUCKETS, BUCKET_SORT, TWO_LEVEL, CULLED, ORDERED, HINTS, CUT_BASE, TAU_MODE, ZERO_IN_BLEND, ZERO_TOUCHED, UNTOUCHED, CLIP, SH_DERIVS,
  SPECULATIVE, ADAPTIVE, ASSUME_SHORT, PAYS, CUT) = (1 << k for k in range(19))
