@@ -1007,6 +1007,56 @@ typedef struct gsrast_project gsrast_project;
 int gsrast_project_forward(const gsrast_project* d, void* stream);
 int gsrast_project_backward(const gsrast_project* d, void* stream);
 
+/* ---- normal consistency: Gaussian normals, depth-map normals, the fused loss (2DGS, gsplat's 2DGS trainer, GOF, RaDe-GS, PGSR;
+ *      csrc/gsrast_normal.h) ----
+ * All arrays contiguous fp32 device pointers; images are planar [3][H][W] / [H][W]; viewmatrix is 16 floats in the render calls'
+ * transposed storage; tanfovx / tanfovy as the render takes them, passed as doubles.  The inputs are fp32, the expressions are evaluated
+ * in fp64 and every output is rounded once.  One writer per element, NO floating-point atomics: every value and gradient is
+ * bit-identical from run to run.  Every backward recomputes the forward from its inputs (nothing is saved).
+ *
+ * gsrast_gaussian_normals_forward: normals [P][3], the unit normal of each Gaussian in VIEW space, facing the camera (what a render blends
+ *   as gsrast_features_forward's features):  k = argmin(scales[i]) (a tie: the lowest index);  q^ = q / |q|, q = rotations[i] = (w, x, y, z);
+ *   n_world = column k of the rotation matrix of q^ (the direction whose variance in the render's Sigma = R S^2 R^T is s_k^2);
+ *   n = n_world V[:3,:3],  p = [mean, 1] V;  n is negated where n . p > 0 (an exact 0 is left).  |q| = 0 or a non-finite q: n = 0.
+ * gsrast_gaussian_normals_backward: dL_drotations [P][4] (OVERWRITTEN) from dL_dnormals [P][3], through q^; 0 on a row whose normal is 0.
+ *   scales, means3D and the camera get no gradient: the argmin and the sign are piecewise constant, the camera is not differentiated.
+ *   One launch each, one lane per Gaussian.  P = 0 returns 0 without a launch.
+ *
+ * gsrast_depth_normal_forward: normals [3][H][W] of the surface depth [H][W] (view-space z: the render's depth, or acc_depth / alpha):
+ *   u_x = ((2x + 1) / W - 1) tanfovx,  v_y = ((2y + 1) / H - 1) tanfovy   (the inverse of the render's means2D = ((ndc + 1) S - 1) / 2)
+ *   P(x, y) = d(x, y) (u_x, v_y, 1);   a = P(x, y+1) - P(x, y-1),  b = P(x+1, y) - P(x-1, y);   c = a x b,  n = c / |c|
+ *   -- gsplat's / 2DGS's central-difference depth_to_normal; a fronto-parallel plane gives (0, 0, -1): towards the camera.
+ *   n = 0, with a zero gradient: on the one-pixel border (gsplat's zero padding); where any of the four neighbours' depths is not > 0 (an
+ *   uncovered pixel, a NaN); where c . c < 1e-24.  The last two are DEVIATIONS from gsplat, which divides by max(|c|, 1e-12) and has no
+ *   coverage rule.
+ * gsrast_depth_normal_backward: dL_ddepth [H][W] (OVERWRITTEN) from dL_dnormals [3][H][W], by a gather: dL/dd(q) sums over the four pixels
+ *   whose stencil contains q, their cross products recomputed from the depths within the radius-2 diamond around q.
+ *
+ * gsrast_normal_loss_forward: *loss (device float) = (1 / (H W)) sum_p (1 - w_p <N_p, n_p>), n as above and never written to memory,
+ *   N = normal_map [3][H][W] used as given (not normalised: 2DGS's rend_normal), w = weight [H][W] (NULL = 1; e.g. the render's alpha).
+ *   One launch writes one fp64 partial per workgroup into scratch (>= gsrast_normal_loss_scratch_bytes(W, H); 0 = the size is refused),
+ *   one small launch sums them in a fixed order in fp64.
+ * gsrast_normal_loss_backward: *upstream (device float) = dL/dloss;  dL_dnormal_map [3][H][W] = -(upstream / (H W)) w n pointwise, and
+ *   dL_ddepth [H][W] by the gather above with dL/dn_p = -(upstream / (H W)) w_p N_p formed on the fly; each NULL = not wanted, else
+ *   OVERWRITTEN; the weight gets no gradient.  One launch, no scratch.
+ *
+ * Refused (GSRAST_E_ARG, gsrast_last_error) before any device call, one text each: P < 0; W or H < 1; W or H > 32768; a tanfov that is
+ * not finite or <= 0; a NULL required pointer; a backward whose gradient outputs are all NULL; a NULL scratch.  The launches have no
+ * entry in the profile table. */
+int gsrast_gaussian_normals_forward(int P, const float* means3D, const float* scales, const float* rotations, const float* viewmatrix,
+                                    float* normals, void* stream);
+int gsrast_gaussian_normals_backward(int P, const float* means3D, const float* scales, const float* rotations, const float* viewmatrix,
+                                     const float* dL_dnormals, float* dL_drotations, void* stream);
+int gsrast_depth_normal_forward(int W, int H, double tanfovx, double tanfovy, const float* depth, float* normals, void* stream);
+int gsrast_depth_normal_backward(int W, int H, double tanfovx, double tanfovy, const float* depth, const float* dL_dnormals,
+                                 float* dL_ddepth, void* stream);
+size_t gsrast_normal_loss_scratch_bytes(int W, int H);      /* 0: the size is refused (gsrast_last_error) */
+int gsrast_normal_loss_forward(int W, int H, double tanfovx, double tanfovy, const float* normal_map, const float* depth,
+                               const float* weight /* NULL = 1 */, float* loss, char* scratch, void* stream);
+int gsrast_normal_loss_backward(int W, int H, double tanfovx, double tanfovy, const float* normal_map, const float* depth,
+                                const float* weight /* NULL = 1 */, const float* upstream, float* dL_dnormal_map /* NULL ok */,
+                                float* dL_ddepth /* NULL ok */, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

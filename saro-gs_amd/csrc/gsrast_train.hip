@@ -11,6 +11,7 @@
 #include "gsrast_mlp_bf16.h"
 #include "gsrast_temporal.h"
 #include "gsrast_bilagrid.h"
+#include "gsrast_normal.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include <algorithm>
@@ -966,6 +967,103 @@ int gsrast_hexplane_backward(int N, int D, int C, int F, int n_planes, const gsr
         hex_grad_uv_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, s>>>(a, pts, levels, d_features, d_pts, d_levels);
         GS_LAUNCHED("hex_grad_uv");
     }
+    return GSRAST_OK;
+}
+
+// ---- normal consistency (gsrast_normal.h) -----------------------------------------------------------------------------
+// Not in the profile kernel-name table: tools/normal_overhead.py times these calls with device events of its own.
+// scratch of the loss: one fp64 partial per workgroup of the forward
+namespace {
+// the refusals the image calls share; 0 or GSRAST_E_ARG
+int normal_image_check(const char* who, int W, int H, double tanfovx, double tanfovy)
+{
+    if (W < 1 || H < 1) return refuse(who, "W and H must be >= 1");
+    if (W > NM_MAX_SIDE || H > NM_MAX_SIDE) return refuse(who, "W and H must be at most 32768");
+    if (!std::isfinite(tanfovx) || !std::isfinite(tanfovy) || !(tanfovx > 0.0) || !(tanfovy > 0.0)) return refuse(who, "tanfovx and tanfovy must be finite and > 0");
+    return GSRAST_OK;
+}
+#define NORMAL_GRID(W, H) dim3((unsigned)(((W) + NM_TW - 1) / NM_TW), (unsigned)(((H) + NM_TH - 1) / NM_TH))      /* a workgroup per NM_TW x NM_TH pixel tile */
+}  // namespace
+
+int gsrast_gaussian_normals_forward(int P, const float* means3D, const float* scales, const float* rotations, const float* viewmatrix,
+                                    float* normals, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "gaussian_normals_forward: negative P");
+    if (P == 0) return GSRAST_OK;
+    if (!means3D || !scales || !rotations || !viewmatrix || !normals) return fail(GSRAST_E_ARG, "gaussian_normals_forward: NULL required pointer");
+    gaussian_normals_fwd_kernel<<<(unsigned)(((size_t)P + 255) / 256), 256, 0, s>>>(P, means3D, scales, rotations, viewmatrix, normals);
+    GS_LAUNCHED("gaussian_normals_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_gaussian_normals_backward(int P, const float* means3D, const float* scales, const float* rotations, const float* viewmatrix,
+                                     const float* dL_dnormals, float* dL_drotations, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return fail(GSRAST_E_ARG, "gaussian_normals_backward: negative P");
+    if (!dL_drotations) return fail(GSRAST_E_ARG, "gaussian_normals_backward: dL_drotations is NULL (it is the only gradient)");
+    if (P == 0) return GSRAST_OK;
+    if (!means3D || !scales || !rotations || !viewmatrix || !dL_dnormals) return fail(GSRAST_E_ARG, "gaussian_normals_backward: NULL required pointer");
+    gaussian_normals_bwd_kernel<<<(unsigned)(((size_t)P + 255) / 256), 256, 0, s>>>(P, means3D, scales, rotations, viewmatrix, dL_dnormals, dL_drotations);
+    GS_LAUNCHED("gaussian_normals_bwd");
+    return GSRAST_OK;
+}
+
+int gsrast_depth_normal_forward(int W, int H, double tanfovx, double tanfovy, const float* depth, float* normals, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = normal_image_check("depth_normal_forward", W, H, tanfovx, tanfovy)) return rc;
+    if (!depth || !normals) return fail(GSRAST_E_ARG, "depth_normal_forward: NULL required pointer");
+    depth_normal_fwd_kernel<<<NORMAL_GRID(W, H), NM_THREADS, 0, s>>>(nm_image(W, H, tanfovx, tanfovy), depth, normals);
+    GS_LAUNCHED("depth_normal_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_depth_normal_backward(int W, int H, double tanfovx, double tanfovy, const float* depth, const float* dL_dnormals, float* dL_ddepth,
+                                 void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = normal_image_check("depth_normal_backward", W, H, tanfovx, tanfovy)) return rc;
+    if (!depth || !dL_dnormals) return fail(GSRAST_E_ARG, "depth_normal_backward: NULL required pointer");
+    if (!dL_ddepth) return fail(GSRAST_E_ARG, "depth_normal_backward: dL_ddepth is NULL (it is the only gradient)");
+    depth_normal_bwd_kernel<<<NORMAL_GRID(W, H), NM_THREADS, 0, s>>>(nm_image(W, H, tanfovx, tanfovy), depth, dL_dnormals, dL_ddepth);
+    GS_LAUNCHED("depth_normal_bwd");
+    return GSRAST_OK;
+}
+
+size_t gsrast_normal_loss_scratch_bytes(int W, int H)
+{
+    if (normal_image_check("normal_loss_scratch_bytes", W, H, 1.0, 1.0) != GSRAST_OK) return 0;
+    const dim3 g = NORMAL_GRID(W, H);
+    return align256((size_t)g.x * g.y * sizeof(double)) + 256;
+}
+
+int gsrast_normal_loss_forward(int W, int H, double tanfovx, double tanfovy, const float* normal_map, const float* depth, const float* weight,
+                               float* loss, char* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = normal_image_check("normal_loss_forward", W, H, tanfovx, tanfovy)) return rc;
+    if (!normal_map || !depth || !loss) return fail(GSRAST_E_ARG, "normal_loss_forward: NULL required pointer");
+    if (!scratch) return fail(GSRAST_E_ARG, "normal_loss_forward: NULL scratch");
+    const dim3 g = NORMAL_GRID(W, H);
+    double* const partial = reinterpret_cast<double*>(scratch);
+    normal_loss_fwd_kernel<<<g, NM_THREADS, 0, s>>>(nm_image(W, H, tanfovx, tanfovy), normal_map, depth, weight, partial);
+    GS_LAUNCHED("normal_loss_fwd");
+    normal_loss_reduce_kernel<<<1, 256, 0, s>>>(partial, (int)(g.x * g.y), 1.0 / ((double)H * (double)W), loss);
+    GS_LAUNCHED("normal_loss_reduce");
+    return GSRAST_OK;
+}
+
+int gsrast_normal_loss_backward(int W, int H, double tanfovx, double tanfovy, const float* normal_map, const float* depth, const float* weight,
+                                const float* upstream, float* dL_dnormal_map, float* dL_ddepth, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = normal_image_check("normal_loss_backward", W, H, tanfovx, tanfovy)) return rc;
+    if (!normal_map || !depth || !upstream) return fail(GSRAST_E_ARG, "normal_loss_backward: NULL required pointer");
+    if (!dL_dnormal_map && !dL_ddepth) return fail(GSRAST_E_ARG, "normal_loss_backward: dL_dnormal_map and dL_ddepth are both NULL");
+    normal_loss_bwd_kernel<<<NORMAL_GRID(W, H), NM_THREADS, 0, s>>>(nm_image(W, H, tanfovx, tanfovy), normal_map, depth, weight, upstream, dL_dnormal_map, dL_ddepth);
+    GS_LAUNCHED("normal_loss_bwd");
     return GSRAST_OK;
 }
 

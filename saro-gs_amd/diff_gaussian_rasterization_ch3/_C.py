@@ -220,6 +220,14 @@ SIGNATURES = {
     # the projection as a call of its own (the descriptor: ProjectStruct, passed by address)
     "gsrast_project_forward": (_ci, (_vp, _vp)),
     "gsrast_project_backward": (_ci, (_vp, _vp)),
+    # normal consistency: Gaussian normals, depth-map normals, the fused loss
+    "gsrast_gaussian_normals_forward": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_gaussian_normals_backward": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_depth_normal_forward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp)),
+    "gsrast_depth_normal_backward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp)),
+    "gsrast_normal_loss_scratch_bytes": (_sz, (_ci, _ci)),
+    "gsrast_normal_loss_forward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_normal_loss_backward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
     # the multi-GPU gradient exchange
     "gsrast_sh_grad_combine": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _cf, _vp, _vp)),
     "gsrast_sh_grad_combine_rows": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
