@@ -13,7 +13,7 @@
 // pruned or not (the reference draws its samples before it prunes).  No atomics: every count comes from a scan, every destination row
 // has exactly one writer, so the result is the same bits on every run and every rank.
 #pragma once
-#include "gsrast_common.h"
+#include "gsrast_gaussian.h"
 
 namespace gsrast {
 
@@ -121,11 +121,12 @@ __device__ __forceinline__ float dn_split_offset(const float* __restrict__ rotat
     const float norm = sqrtf(r * r + x * x + y * y + z * z);
     r /= norm; x /= norm; y /= norm; z /= norm;
     const float s0 = noise[3 * nrow] * expf(scaling[3 * src]), s1 = noise[3 * nrow + 1] * expf(scaling[3 * src + 1]), s2 = noise[3 * nrow + 2] * expf(scaling[3 * src + 2]);
-    float a, b, d;
-    if (c == 0)      { a = 1.0f - 2.0f * (y * y + z * z); b = 2.0f * (x * y - r * z);        d = 2.0f * (x * z + r * y); }
-    else if (c == 1) { a = 2.0f * (x * y + r * z);        b = 1.0f - 2.0f * (x * x + z * z); d = 2.0f * (y * z - r * x); }
-    else             { a = 2.0f * (x * z - r * y);        b = 2.0f * (y * z + r * x);        d = 1.0f - 2.0f * (x * x + y * y); }
-    return a * s0 + b * s1 + d * s2;
+    const float q[4] = { r, x, y, z };
+    M3 R;
+    quat_to_R(q, R);
+    if (c == 0) return R.m[0][0] * s0 + R.m[0][1] * s1 + R.m[0][2] * s2;
+    if (c == 1) return R.m[1][0] * s0 + R.m[1][1] * s1 + R.m[1][2] * s2;
+    return R.m[2][0] * s0 + R.m[2][1] * s1 + R.m[2][2] * s2;
 }
 
 // A workgroup takes DN_RUN consecutive sources: class and destination rows into LDS, then every group's run x width floats with

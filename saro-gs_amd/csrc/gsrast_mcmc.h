@@ -15,7 +15,7 @@
 // Moments: the sampled sources' exp_avg / exp_avg_sq become 0; a relocated dead row KEEPS its own moments -- the 3DGS-MCMC code and
 // gsplat both reset the optimizer state at the sampled indices only, and this file leaves it that way.
 #pragma once
-#include "gsrast_common.h"
+#include "gsrast_gaussian.h"
 #include <cfloat>
 
 namespace gsrast {
@@ -258,20 +258,20 @@ mcmc_noise_kernel(int P, float* __restrict__ xyz, const float4* __restrict__ rot
     float r = q4.x, x = q4.y, y = q4.z, z = q4.w;
     const float norm = sqrtf(r * r + x * x + y * y + z * z);
     r /= norm; x /= norm; y /= norm; z /= norm;
-    const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - r * z), R02 = 2.0f * (x * z + r * y);
-    const float R10 = 2.0f * (x * y + r * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - r * x);
-    const float R20 = 2.0f * (x * z - r * y), R21 = 2.0f * (y * z + r * x), R22 = 1.0f - 2.0f * (x * x + y * y);
+    const float qn[4] = { r, x, y, z };
+    M3 R;
+    quat_to_R(qn, R);      // R.m[i][j]: row i, column j of build_rotation
     const float one_minus_o = 1.0f / (1.0f + expf(opacity_logit[i]));
     float g = scale / (1.0f + expf(-k * (one_minus_o - x0)));
     if (row_scale) g *= row_scale[i];
     const float v0 = noise[3 * i] * g, v1 = noise[3 * i + 1] * g, v2 = noise[3 * i + 2] * g;
     const float e0 = expf(scaling[3 * i]), e1 = expf(scaling[3 * i + 1]), e2 = expf(scaling[3 * i + 2]);
-    const float t0 = (R00 * v0 + R10 * v1 + R20 * v2) * (e0 * e0);      // diag(s)^2 R^T v
-    const float t1 = (R01 * v0 + R11 * v1 + R21 * v2) * (e1 * e1);
-    const float t2 = (R02 * v0 + R12 * v1 + R22 * v2) * (e2 * e2);
-    xyz[3 * i] += R00 * t0 + R01 * t1 + R02 * t2;
-    xyz[3 * i + 1] += R10 * t0 + R11 * t1 + R12 * t2;
-    xyz[3 * i + 2] += R20 * t0 + R21 * t1 + R22 * t2;
+    const float t0 = (R.m[0][0] * v0 + R.m[1][0] * v1 + R.m[2][0] * v2) * (e0 * e0);      // diag(s)^2 R^T v
+    const float t1 = (R.m[0][1] * v0 + R.m[1][1] * v1 + R.m[2][1] * v2) * (e1 * e1);
+    const float t2 = (R.m[0][2] * v0 + R.m[1][2] * v1 + R.m[2][2] * v2) * (e2 * e2);
+    xyz[3 * i] += R.m[0][0] * t0 + R.m[0][1] * t1 + R.m[0][2] * t2;
+    xyz[3 * i + 1] += R.m[1][0] * t0 + R.m[1][1] * t1 + R.m[1][2] * t2;
+    xyz[3 * i + 2] += R.m[2][0] * t0 + R.m[2][1] * t1 + R.m[2][2] * t2;
 }
 
 } // namespace gsrast

@@ -2,14 +2,15 @@
 // their backward.  One lane per Gaussian; fp32 arithmetic in a fixed evaluation order (the
 // translation unit is built with -ffp-contract=off, FMAs appear only where written) so the
 // integer outputs (radii, tile rectangles, depth key bits) match the CPU oracle bit for bit.
+// The projection row, the covariances and their backward chain are gsrast_gaussian.h's; this file keeps the SH colour, the RAW
+// activations and the kernels.
 //
 // Reference behaviour restated here (RST = reference cuda_rasterizer/):
-//   forward : RST/forward.cu:155-256 preprocessCUDA, :74-113 computeCov2D, :118-152 computeCov3D,
-//             :20-71 computeColorFromSH, RST/auxiliary.h:41-56 ndc2Pix/getRect, :139-164 in_frustum
-//   backward: RST/backward.cu:144-274 computeCov2DCUDA, :346-396 preprocessCUDA,
-//             :278-341 computeCov3D, :20-139 computeColorFromSH   (fused into ONE kernel here)
+//   forward : RST/forward.cu:155-256 preprocessCUDA, :20-71 computeColorFromSH, RST/auxiliary.h:139-164 in_frustum
+//   backward: RST/backward.cu:346-396 preprocessCUDA, :20-139 computeColorFromSH   (fused into ONE kernel here, with
+//             gsrast_gaussian.h's computeCov2DCUDA / computeCov3D)
 #pragma once
-#include "gsrast_common.h"
+#include "gsrast_gaussian.h"
 
 namespace gsrast {
 
@@ -20,33 +21,6 @@ __device__ constexpr float kSH2[5] = { 1.0925484305920792f, -1.0925484305920792f
 __device__ constexpr float kSH3[7] = { -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                        -0.5900435899266435f };
-
-struct Cam {            // per-call constants, passed by value in kernarg (SGPRs)
-    float view[16];     // transposed storage: view[4*c + r] = V[r][c]
-    float proj[16];
-    float campos[3];
-    float tanx, tany, fx, fy, scale_mod;
-    int W, H, gx, gy;
-};
-
-// What the host passes: the three camera arrays stay in HBM (no D2H copy, no sync); every lane
-// reads them through uniform (scalar) loads at kernel entry.
-struct CamArgs {
-    const float* view; const float* proj; const float* campos;
-    float tanx, tany, fx, fy, scale_mod;
-    int W, H, gx, gy;
-};
-__device__ __forceinline__ Cam load_cam(const CamArgs& a)
-{
-    Cam c;
-#pragma unroll
-    for (int k = 0; k < 16; k++) { c.view[k] = a.view[k]; c.proj[k] = a.proj[k]; }
-    if (a.campos) { c.campos[0] = a.campos[0]; c.campos[1] = a.campos[1]; c.campos[2] = a.campos[2]; }
-    else { c.campos[0] = c.campos[1] = c.campos[2] = 0.0f; }
-    c.tanx = a.tanx; c.tany = a.tany; c.fx = a.fx; c.fy = a.fy; c.scale_mod = a.scale_mod;
-    c.W = a.W; c.H = a.H; c.gx = a.gx; c.gy = a.gy;
-    return c;
-}
 
 // ---- raw-parameter entry points (GSRAST_FAMILY_RAW call records) --------- ------------------------------
 // SaRO-GS hands the rasterizer ACTIVATED attributes: exp(_scaling), normalize(_rotation), sigmoid(_opacity) * trbf,
@@ -91,110 +65,6 @@ __device__ __forceinline__ void raw_rot_scale(const RawArgs& r, int i, float4& q
     for (int k = 0; k < 3; k++) s[k] = expf(s[k]);
 }
 __device__ __forceinline__ float raw_sigmoid(float logit) { return 1.0f / (1.0f + expf(-logit)); }
-
-struct M3 { float m[3][3]; };  // m[c][r], column-major like the reference's glm::mat3
-
-__device__ __forceinline__ void xform4x3(const float p[3], const float* M, float o[3])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++) o[r] = M[r] * p[0] + M[4 + r] * p[1] + M[8 + r] * p[2] + M[12 + r];
-}
-__device__ __forceinline__ void xform4x4(const float p[3], const float* M, float o[4])
-{
-#pragma unroll
-    for (int r = 0; r < 4; r++) o[r] = M[r] * p[0] + M[4 + r] * p[1] + M[8 + r] * p[2] + M[12 + r];
-}
-__device__ __forceinline__ float ndc2pix(float v, int S)
-{ // evaluated in double like the reference (1.0 / 0.5 literals), then narrowed
-    return (float)((((double)v + 1.0) * S - 1.0) * 0.5);
-}
-__device__ __forceinline__ void tile_rect(float px, float py, int rad, int gx, int gy, int rmin[2], int rmax[2])
-{
-    int a;
-    a = (int)((px - rad) / TILE_X); a = a > 0 ? a : 0; rmin[0] = gx < a ? gx : a;
-    a = (int)((py - rad) / TILE_Y); a = a > 0 ? a : 0; rmin[1] = gy < a ? gy : a;
-    a = (int)((px + rad + TILE_X - 1) / TILE_X); a = a > 0 ? a : 0; rmax[0] = gx < a ? gx : a;
-    a = (int)((py + rad + TILE_Y - 1) / TILE_Y); a = a > 0 ? a : 0; rmax[1] = gy < a ? gy : a;
-}
-
-__device__ __forceinline__ void quat_to_R(const float q[4], M3& R)
-{
-    const float r = q[0], x = q[1], y = q[2], z = q[3];
-    R.m[0][0] = 1.0f - 2.0f * (y * y + z * z); R.m[0][1] = 2.0f * (x * y - r * z); R.m[0][2] = 2.0f * (x * z + r * y);
-    R.m[1][0] = 2.0f * (x * y + r * z); R.m[1][1] = 1.0f - 2.0f * (x * x + z * z); R.m[1][2] = 2.0f * (y * z - r * x);
-    R.m[2][0] = 2.0f * (x * z - r * y); R.m[2][1] = 2.0f * (y * z + r * x); R.m[2][2] = 1.0f - 2.0f * (x * x + y * y);
-}
-// Sigma = (S R)^T (S R), upper triangle; M = S*R returned for the backward.
-__device__ __forceinline__ void cov3d_from_scale_rot(const float s_in[3], float mod, const float q[4], float c6[6], M3& M)
-{
-    M3 R; quat_to_R(q, R);
-    const float s[3] = { mod * s_in[0], mod * s_in[1], mod * s_in[2] };
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++) M.m[c][r] = s[r] * R.m[c][r];
-#define GS_SIG(c, r) (M.m[r][0] * M.m[c][0] + M.m[r][1] * M.m[c][1] + M.m[r][2] * M.m[c][2])
-    c6[0] = GS_SIG(0, 0); c6[1] = GS_SIG(0, 1); c6[2] = GS_SIG(0, 2);
-    c6[3] = GS_SIG(1, 1); c6[4] = GS_SIG(1, 2); c6[5] = GS_SIG(2, 2);
-#undef GS_SIG
-}
-
-// a, b, c: the screen-space covariance with the 0.3 px^2 dilation (b = c01); c00, c11: its diagonal BEFORE the dilation, for the
-// anti-aliasing filter (aa_rho below) -- not recovered as a - 0.3f, which would add a rounding error to the quantity that cancels.
-// (Dead in the plain kernels: nothing reads them there.)
-struct Cov2D { float t[3]; float txtz, tytz, limx, limy; M3 T, Wm, V; float a, b, c; float c00, c11; };
-
-__device__ __forceinline__ void cov2d_eval(const float mean[3], const Cam& cam, const float c6[6], Cov2D& o)
-{
-    float t[3];
-    xform4x3(mean, cam.view, t);
-    o.limx = 1.3f * cam.tanx; o.limy = 1.3f * cam.tany;
-    o.txtz = t[0] / t[2]; o.tytz = t[1] / t[2];
-    float cx = o.txtz < -o.limx ? -o.limx : o.txtz; cx = o.limx < cx ? o.limx : cx;
-    float cy = o.tytz < -o.limy ? -o.limy : o.tytz; cy = o.limy < cy ? o.limy : cy;
-    t[0] = cx * t[2]; t[1] = cy * t[2];
-    o.t[0] = t[0]; o.t[1] = t[1]; o.t[2] = t[2];
-    const float J00 = cam.fx / t[2], J02 = -(cam.fx * t[0]) / (t[2] * t[2]);
-    const float J11 = cam.fy / t[2], J12 = -(cam.fy * t[1]) / (t[2] * t[2]);
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++) o.Wm.m[c][r] = cam.view[4 * r + c];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        o.T.m[0][r] = o.Wm.m[0][r] * J00 + o.Wm.m[2][r] * J02;
-        o.T.m[1][r] = o.Wm.m[1][r] * J11 + o.Wm.m[2][r] * J12;
-        o.T.m[2][r] = 0.0f;
-    }
-    o.V.m[0][0] = c6[0]; o.V.m[0][1] = c6[1]; o.V.m[0][2] = c6[2];
-    o.V.m[1][0] = c6[1]; o.V.m[1][1] = c6[3]; o.V.m[1][2] = c6[4];
-    o.V.m[2][0] = c6[2]; o.V.m[2][1] = c6[4]; o.V.m[2][2] = c6[5];
-    float A[3][2];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-            A[k][r] = o.T.m[r][0] * o.V.m[0][k] + o.T.m[r][1] * o.V.m[1][k] + o.T.m[r][2] * o.V.m[2][k];
-    const float c00 = A[0][0] * o.T.m[0][0] + A[1][0] * o.T.m[0][1] + A[2][0] * o.T.m[0][2];
-    const float c01 = A[0][1] * o.T.m[0][0] + A[1][1] * o.T.m[0][1] + A[2][1] * o.T.m[0][2];
-    const float c11 = A[0][1] * o.T.m[1][0] + A[1][1] * o.T.m[1][1] + A[2][1] * o.T.m[1][2];
-    o.a = c00 + 0.3f; o.b = c01; o.c = c11 + 0.3f;
-    o.c00 = c00; o.c11 = c11;
-}
-
-// ---- anti-aliasing: the 2-D Mip filter of Mip-Splatting (Yu et al., CVPR 2024), as upstream 3DGS's `antialiasing` ----------------
-// The 0.3 px^2 dilation above widens every footprint; with AA the opacity is scaled by the ratio of the two footprints' areas so that a
-// small or distant Gaussian keeps its energy:  rho = det(cov2D) / det(cov2D + 0.3 I),  comp = sqrt(max(AA_FLOOR, rho)),  o_eff = o * comp.
-// o_eff replaces o in every downstream use (rec1.y, the skip threshold, the predicted cut's mass); conic, radius and tiles do not change.
-// det_h is the forward's `det` (the backward's `denom`): the same expression on the same operands.  rho <= 0 (fp32 cancellation of a
-// needle) lands on the floor, where the covariance term of the backward is zero.
-constexpr float AA_FLOOR = 0.000025f;      // upstream's literal
-__device__ __forceinline__ float aa_rho(const Cov2D& cv, float det_h)
-{
-    const float det_cov = cv.c00 * cv.c11 - cv.b * cv.b;
-    return det_cov / det_h;
-}
-__device__ __forceinline__ float aa_comp(float rho) { return sqrtf(fmaxf(AA_FLOOR, rho)); }
 
 // colour before clamping (SH + 0.5); sh points at this Gaussian's [M][3] block
 __device__ __forceinline__ void sh_to_rgb(int deg, const float pos[3], const float campos[3], const float* __restrict__ sh, float out[3])
@@ -782,12 +652,8 @@ preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __r
     float tau_mass = 0.0f; int tau_tile = -1;          // predicted cut (gsrast_common.h): this Gaussian's opacity mass and the tile of its centre
     if (i < P) {
 
-    float ph[4], pv[3];
-    xform4x4(p, cam.proj, ph);
-    const float pw = 1.0f / (ph[3] + 0.0000001f);
-    const float pp0 = ph[0] * pw, pp1 = ph[1] * pw;
-    xform4x3(p, cam.view, pv);
-    if (pv[2] > 0.2f) {
+    ProjHead hd;
+    if (project_head(p, cam, hd)) {
         float c6[6];
         if (cov3D_precomp) {
 #pragma unroll
@@ -802,76 +668,64 @@ preprocess_fwd_kernel(int P, const float* __restrict__ means3D, const float* __r
             }
         }
         Cov2D cv;
-        cov2d_eval(p, cam, c6, cv);
-        const float det = cv.a * cv.c - cv.b * cv.b;
-        if (det != 0.0f) {
-            const float det_inv = 1.0f / det;
-            const float con0 = cv.c * det_inv, con1 = -cv.b * det_inv, con2 = cv.a * det_inv;
-            const float mid = 0.5f * (cv.a + cv.c);
-            float disc = mid * mid - det; disc = disc < 0.1f ? 0.1f : disc;
-            const float l1 = mid + sqrtf(disc), l2 = mid - sqrtf(disc);
-            const float lmax = l1 < l2 ? l2 : l1;
-            const float my_radius = ceilf(3.0f * sqrtf(lmax));
-            const float px = ndc2pix(pp0, cam.W), py = ndc2pix(pp1, cam.H);
-            const int rad = (int)my_radius;
-            int rmin[2], rmax[2];
-            tile_rect(px, py, rad, cam.gx, cam.gy, rmin, rmax);
+        ProjRow row;
+        if (project_row<AA>(p, hd, c6, cam, cv, row)) {
+            const float px = row.px, py = row.py, con0 = row.con0, con1 = row.con1, con2 = row.con2, det = row.det;
+            int* rmin = row.rmin; int* rmax = row.rmax;      // (clip_rect narrows them)
             const int area = (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]);
-            if (area != 0) {
-                const float op = AA ? op_in * aa_comp(aa_rho(cv, det)) : op_in;
-                // Conservative pre-test for the blend kernels: power < thr  ==>  op*exp(power) < 1/255
-                // with a 2% margin, so skipping the exp for such pairs never changes a decision.
-                // (clamped at -80 so that exp() is only ever evaluated on [-80, 0]: gs_exp<., BOUNDED>)
-                const float thr = op > 0.0f ? fmaxf(logf(1.0f / (255.0f * op)) - 0.02f, -80.0f) : 1.0f;
-                rec0[(size_t)REC_STRIDE * i] = make_float4(px, py, con0, con1);      // (non-temporal stores here, measured: the kernel +10 us, its readers -12: nothing)
-                rec1[(size_t)REC_STRIDE * i] = make_float4(con2, op, pv[2], thr);
-                rad_out = rad; ntiles = (uint32_t)area;
-                key = __float_as_uint(pv[2]);
-                if (tau_hist && px >= 0.0f && py >= 0.0f && px < (float)cam.W && py < (float)cam.H) {
-                    tau_tile = ((int)py >> 4) * cam.gx + ((int)px >> 4);
-                    // the Gaussian's OPTICAL-DEPTH mass: integral over the plane of -ln(1 - a(x)), a(x) = o exp(-q(x) / 2)  =  2 pi sqrt(det cov2D) Li2(o),
-                    // Li2 the dilogarithm, here its series cut after six terms (a lower bound: the estimate stays conservative)
-                    const float oc = fminf(op, 0.99f);
-                    const float li2 = oc * (1.0f + oc * (0.25f + oc * (0.111111f + oc * (0.0625f + oc * (0.04f + oc * 0.0277778f)))));
-                    // ... but never more than it can lay on ONE tile (its peak over all 256 pixels): a Gaussian wider than a tile hands the tile of
-                    // its centre that much and its neighbours nothing, which only lowers their estimates
-                    tau_mass = fminf(li2 * 6.28318531f * sqrtf(fmaxf(det, 0.0f)), -logf(1.0f - oc) * 256.0f);
-                }
-                if (clip_rect) {
-                    // Bounding box of the ellipse the alpha >= 1/255 pixels lie in (same construction and margins as the
-                    // per-column clipping in emit_column_runs_kernel, gsrast_binning.h): whole tile columns / rows of the
-                    // 3-sigma square that it cannot reach produce no column runs at all.  tiles[] (-> num_rendered) keeps
-                    // the reference's count.
-                    const float DX = fmaxf(fabsf(px - 16.0f * (float)rmin[0]), fabsf(16.0f * (float)rmax[0] - px));
-                    const float DY = fmaxf(fabsf(py - 16.0f * (float)rmin[1]), fabsf(16.0f * (float)rmax[1] - py));
-                    const float Mb = (fabsf(con0) + fabsf(con1)) * DX * DX + (fabsf(con2) + fabsf(con1)) * DY * DY;
-                    const double t = (double)(-thr + 1e-6f * Mb);
-                    const double a = (double)con0, b = (double)con1, c = (double)con2;
-                    const double dd = a * c - b * b;
-                    if (!(t >= 0.0)) { rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
-                    else if (dd > 0.0 && a > 0.0 && c > 0.0) {
-                        const double ex[2] = { sqrt(2.0 * t * c / dd), sqrt(2.0 * t * a / dd) };   // half extents in x, y
-                        const double ctr[2] = { (double)px, (double)py };
-                        const int lim[2] = { cam.W - 1, cam.H - 1 };
+            const float op = AA ? op_in * row.comp : op_in;
+            // Conservative pre-test for the blend kernels: power < thr  ==>  op*exp(power) < 1/255
+            // with a 2% margin, so skipping the exp for such pairs never changes a decision.
+            // (clamped at -80 so that exp() is only ever evaluated on [-80, 0]: gs_exp<., BOUNDED>)
+            const float thr = op > 0.0f ? fmaxf(logf(1.0f / (255.0f * op)) - 0.02f, -80.0f) : 1.0f;
+            rec0[(size_t)REC_STRIDE * i] = make_float4(px, py, con0, con1);      // (non-temporal stores here, measured: the kernel +10 us, its readers -12: nothing)
+            rec1[(size_t)REC_STRIDE * i] = make_float4(con2, op, hd.t[2], thr);
+            rad_out = row.rad; ntiles = (uint32_t)area;
+            key = __float_as_uint(hd.t[2]);
+            if (tau_hist && px >= 0.0f && py >= 0.0f && px < (float)cam.W && py < (float)cam.H) {
+                tau_tile = ((int)py >> 4) * cam.gx + ((int)px >> 4);
+                // the Gaussian's OPTICAL-DEPTH mass: integral over the plane of -ln(1 - a(x)), a(x) = o exp(-q(x) / 2)  =  2 pi sqrt(det cov2D) Li2(o),
+                // Li2 the dilogarithm, here its series cut after six terms (a lower bound: the estimate stays conservative)
+                const float oc = fminf(op, 0.99f);
+                const float li2 = oc * (1.0f + oc * (0.25f + oc * (0.111111f + oc * (0.0625f + oc * (0.04f + oc * 0.0277778f)))));
+                // ... but never more than it can lay on ONE tile (its peak over all 256 pixels): a Gaussian wider than a tile hands the tile of
+                // its centre that much and its neighbours nothing, which only lowers their estimates
+                tau_mass = fminf(li2 * 6.28318531f * sqrtf(fmaxf(det, 0.0f)), -logf(1.0f - oc) * 256.0f);
+            }
+            if (clip_rect) {
+                // Bounding box of the ellipse the alpha >= 1/255 pixels lie in (same construction and margins as the
+                // per-column clipping in emit_column_runs_kernel, gsrast_binning.h): whole tile columns / rows of the
+                // 3-sigma square that it cannot reach produce no column runs at all.  tiles[] (-> num_rendered) keeps
+                // the reference's count.
+                const float DX = fmaxf(fabsf(px - 16.0f * (float)rmin[0]), fabsf(16.0f * (float)rmax[0] - px));
+                const float DY = fmaxf(fabsf(py - 16.0f * (float)rmin[1]), fabsf(16.0f * (float)rmax[1] - py));
+                const float Mb = (fabsf(con0) + fabsf(con1)) * DX * DX + (fabsf(con2) + fabsf(con1)) * DY * DY;
+                const double t = (double)(-thr + 1e-6f * Mb);
+                const double a = (double)con0, b = (double)con1, c = (double)con2;
+                const double dd = a * c - b * b;
+                if (!(t >= 0.0)) { rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
+                else if (dd > 0.0 && a > 0.0 && c > 0.0) {
+                    const double ex[2] = { sqrt(2.0 * t * c / dd), sqrt(2.0 * t * a / dd) };   // half extents in x, y
+                    const double ctr[2] = { (double)px, (double)py };
+                    const int lim[2] = { cam.W - 1, cam.H - 1 };
 #pragma unroll
-                        for (int ax = 0; ax < 2; ax++) {
-                            if (!(ex[ax] < 1e30)) continue;
-                            const double plo = ceil(ctr[ax] - ex[ax] - 1e-3), phi = floor(ctr[ax] + ex[ax] + 1e-3);
-                            const int tlo = max(rmin[ax], (int)fmax(plo, 0.0) >> 4);
-                            const int thi = min(rmax[ax] - 1, (int)fmin(phi, (double)lim[ax]) >> 4);
-                            if (phi < 0.0 || plo > (double)lim[ax] || thi < tlo) { rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
-                            else { rmin[ax] = tlo; rmax[ax] = thi + 1; }
-                        }
+                    for (int ax = 0; ax < 2; ax++) {
+                        if (!(ex[ax] < 1e30)) continue;
+                        const double plo = ceil(ctr[ax] - ex[ax] - 1e-3), phi = floor(ctr[ax] + ex[ax] + 1e-3);
+                        const int tlo = max(rmin[ax], (int)fmax(plo, 0.0) >> 4);
+                        const int thi = min(rmax[ax] - 1, (int)fmin(phi, (double)lim[ax]) >> 4);
+                        if (phi < 0.0 || plo > (double)lim[ax] || thi < tlo) { rmax[0] = rmin[0]; rmax[1] = rmin[1]; }
+                        else { rmin[ax] = tlo; rmax[ax] = thi + 1; }
                     }
                 }
-                rc = make_uint2((uint32_t)rmin[0] | ((uint32_t)rmin[1] << 16), (uint32_t)rmax[0] | ((uint32_t)rmax[1] << 16));
-                // everything the binning needs about this Gaussian in ONE 32-byte record (it is gathered in depth order)
-                // (null under the list cut: the emission then gathers the few Gaussians it lists from rec0 / rec1 / rect, and 32 bytes per
-                // Gaussian stay unwritten)
-                if (binrec) {
-                    binrec[2 * (size_t)i] = make_float4(px, py, con0, con1);
-                    binrec[2 * (size_t)i + 1] = make_float4(con2, thr, __uint_as_float(rc.x), __uint_as_float(rc.y));
-                }
+            }
+            rc = make_uint2((uint32_t)rmin[0] | ((uint32_t)rmin[1] << 16), (uint32_t)rmax[0] | ((uint32_t)rmax[1] << 16));
+            // everything the binning needs about this Gaussian in ONE 32-byte record (it is gathered in depth order)
+            // (null under the list cut: the emission then gathers the few Gaussians it lists from rec0 / rec1 / rect, and 32 bytes per
+            // Gaussian stay unwritten)
+            if (binrec) {
+                binrec[2 * (size_t)i] = make_float4(px, py, con0, con1);
+                binrec[2 * (size_t)i + 1] = make_float4(con2, thr, __uint_as_float(rc.x), __uint_as_float(rc.y));
             }
         }
     }
@@ -901,12 +755,9 @@ mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __res
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    struct { float view[16]; } cam;
-#pragma unroll
-    for (int k = 0; k < 16; k++) cam.view[k] = view[k];
     const float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
     float pv[3];
-    xform4x3(p, cam.view, pv);
+    xform4x3(p, view, pv);
     present[i] = pv[2] > 0.2f ? 1 : 0;
 }
 
@@ -1268,15 +1119,9 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     }
     Cov2D cv;
     cov2d_eval(mean, cam, c6, cv);
-    const float xgm = (cv.txtz < -cv.limx || cv.txtz > cv.limx) ? 0.0f : 1.0f;
-    const float ygm = (cv.tytz < -cv.limy || cv.tytz > cv.limy) ? 0.0f : 1.0f;
-    const float a = cv.a, b = cv.b, c = cv.c;
-    const float dcx = dcon.x, dcy = dcon.y, dcz = dcon.w;
-    const float denom = a * c - b * b;
-    float dL_da = 0, dL_db = 0, dL_dc = 0;
-    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-    const M3& T = cv.T; const M3& V = cv.V; const M3& Wm = cv.Wm;
+    const float denom = cv.a * cv.c - cv.b * cv.b;
     bool aa_on = false;          // AA: rho above the floor -- the covariance term is live
+    float aa_w = 0.0f;           //     g o_eff d(comp)/d(c00, c01, c11) = g o_eff 0.5 d(ln rho)/d(.): the weight of d(ln rho)
     if (AA) {
         const float rho = aa_rho(cv, denom);
         const float go = gr1.y * aa_comp(rho);          // dL/do = dL/do_eff * comp
@@ -1285,63 +1130,18 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
             if (rawg.d_trbf) rawg.d_trbf[i] = go * raw_sg;
         } else dL_dopacity[i] = go;
         aa_on = rho > AA_FLOOR;
+        if (aa_on) aa_w = gr1.y * rec1[(size_t)REC_STRIDE * i].y * 0.5f;          // o_eff: the forward's
     }
-    float dcov[6];
-    if (denom2inv != 0) {
-        dL_da = denom2inv * (-c * c * dcx + 2.0f * b * c * dcy + (denom - a * c) * dcz);
-        dL_dc = denom2inv * (-a * a * dcz + 2.0f * a * b * dcy + (denom - a * c) * dcx);
-        dL_db = denom2inv * 2.0f * (b * c * dcx - (denom + 2.0f * b * b) * dcy + a * b * dcz);
-        if (AA && aa_on) {      // + g o_eff d(comp)/d(c00, c01, c11) = g o_eff 0.5 d(ln rho)/d(.)  (b: the scalar c01, as dL_db)
-            const float w = gr1.y * rec1[(size_t)REC_STRIDE * i].y * 0.5f;
-            const float icov = 1.0f / (cv.c00 * cv.c11 - b * b), ih = 1.0f / denom;
-            dL_da = dL_da + w * (cv.c11 * icov - c * ih);
-            dL_dc = dL_dc + w * (cv.c00 * icov - a * ih);
-            dL_db = dL_db + w * (2.0f * b * ih - 2.0f * b * icov);
-        }
-        dcov[0] = (T.m[0][0] * T.m[0][0] * dL_da + T.m[0][0] * T.m[1][0] * dL_db + T.m[1][0] * T.m[1][0] * dL_dc);
-        dcov[3] = (T.m[0][1] * T.m[0][1] * dL_da + T.m[0][1] * T.m[1][1] * dL_db + T.m[1][1] * T.m[1][1] * dL_dc);
-        dcov[5] = (T.m[0][2] * T.m[0][2] * dL_da + T.m[0][2] * T.m[1][2] * dL_db + T.m[1][2] * T.m[1][2] * dL_dc);
-        dcov[1] = 2.0f * T.m[0][0] * T.m[0][1] * dL_da + (T.m[0][0] * T.m[1][1] + T.m[0][1] * T.m[1][0]) * dL_db + 2.0f * T.m[1][0] * T.m[1][1] * dL_dc;
-        dcov[2] = 2.0f * T.m[0][0] * T.m[0][2] * dL_da + (T.m[0][0] * T.m[1][2] + T.m[0][2] * T.m[1][0]) * dL_db + 2.0f * T.m[1][0] * T.m[1][2] * dL_dc;
-        dcov[4] = 2.0f * T.m[0][2] * T.m[0][1] * dL_da + (T.m[0][1] * T.m[1][2] + T.m[0][2] * T.m[1][1]) * dL_db + 2.0f * T.m[1][1] * T.m[1][2] * dL_dc;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 6; k++) dcov[k] = 0.0f;
-    }
+    // the record carries half the gradient of the stored middle conic (dcon.y), and dL/d(view z) only with aux: the accumulated
+    // depth's z is the view-space z itself (uniform)
+    ProjGrad pg;
+    project_backward(mean, cam, cv, denom, dcon.x, dcon.y, dcon.w, AA && aa_on, aa_w, g2x, g2y, aux != 0, gr2.y, pg);
+    const float* dcov = pg.dcov;
+    float* dmean = pg.dmean;
     if (dL_dcov3D) {     // only a caller that passed cov3D_precomp wants it: with scales / rotations it is an intermediate
 #pragma unroll
         for (int k = 0; k < 6; k++) dL_dcov3D[6 * (size_t)i + k] = dcov[k];
     }
-    float dT[2][3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float r0 = T.m[0][0] * V.m[k][0] + T.m[0][1] * V.m[k][1] + T.m[0][2] * V.m[k][2];
-        const float r1 = T.m[1][0] * V.m[k][0] + T.m[1][1] * V.m[k][1] + T.m[1][2] * V.m[k][2];
-        dT[0][k] = 2.0f * r0 * dL_da + r1 * dL_db;
-        dT[1][k] = 2.0f * r1 * dL_dc + r0 * dL_db;
-    }
-    const float dJ00 = Wm.m[0][0] * dT[0][0] + Wm.m[0][1] * dT[0][1] + Wm.m[0][2] * dT[0][2];
-    const float dJ02 = Wm.m[2][0] * dT[0][0] + Wm.m[2][1] * dT[0][1] + Wm.m[2][2] * dT[0][2];
-    const float dJ11 = Wm.m[1][0] * dT[1][0] + Wm.m[1][1] * dT[1][1] + Wm.m[1][2] * dT[1][2];
-    const float dJ12 = Wm.m[2][0] * dT[1][0] + Wm.m[2][1] * dT[1][1] + Wm.m[2][2] * dT[1][2];
-    const float tz = 1.0f / cv.t[2], tz2 = tz * tz, tz3 = tz2 * tz;
-    const float dtx = xgm * -cam.fx * tz2 * dJ02;
-    const float dty = ygm * -cam.fy * tz2 * dJ12;
-    float dtz = -cam.fx * tz2 * dJ00 - cam.fy * tz2 * dJ11 + (2.0f * cam.fx * cv.t[0]) * tz3 * dJ02 + (2.0f * cam.fy * cv.t[1]) * tz3 * dJ12;
-    if (aux) dtz += gr2.y;          // the accumulated depth's z is the view-space z itself (uniform branch)
-    float dmean[3] = { cam.view[0] * dtx + cam.view[1] * dty + cam.view[2] * dtz,
-                       cam.view[4] * dtx + cam.view[5] * dty + cam.view[6] * dtz,
-                       cam.view[8] * dtx + cam.view[9] * dty + cam.view[10] * dtz };
-    // mean gradient through the perspective projection of the 2D mean
-    float mh[4];
-    xform4x4(mean, cam.proj, mh);
-    const float mw = 1.0f / (mh[3] + 0.0000001f);
-    const float* pj = cam.proj;
-    const float mul1 = (pj[0] * mean[0] + pj[4] * mean[1] + pj[8] * mean[2] + pj[12]) * mw * mw;
-    const float mul2 = (pj[1] * mean[0] + pj[5] * mean[1] + pj[9] * mean[2] + pj[13]) * mw * mw;
-    dmean[0] += (pj[0] * mw - pj[3] * mul1) * g2x + (pj[1] * mw - pj[3] * mul2) * g2y;
-    dmean[1] += (pj[4] * mw - pj[7] * mul1) * g2x + (pj[5] * mw - pj[7] * mul2) * g2y;
-    dmean[2] += (pj[8] * mw - pj[11] * mul1) * g2x + (pj[9] * mw - pj[11] * mul2) * g2y;
     float ddir[3] = { 0.f, 0.f, 0.f };          // POSE: what sh_backward adds to dmean
     if (shs) {
         const float ddx[3] = { sdA.x, sdA.y, sdA.z }, ddy[3] = { sdA.w, sdB.x, sdB.y }, ddz[3] = { sdB.z, sdB.w, sdC };
@@ -1356,7 +1156,9 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
             for (int k = ncoef * 3; k < M * 3; k++) dsh[k] = 0.0f;
         }
     }
-    if (POSE) {
+    if (POSE) {      // from the chain's own intermediates
+        const float tz = pg.tz, tz2 = pg.tz2, dtx = pg.dtx, dty = pg.dty, dtz = pg.dtz, mw = pg.mw;
+        const float* mh = pg.mh; const float (*dT)[3] = pg.dT;
         const float J00 = cam.fx * tz, J11 = cam.fy * tz, J02 = -(cam.fx * cv.t[0]) * tz2, J12 = -(cam.fy * cv.t[1]) * tz2;      // (cv.t: clamped)
         const float dh0 = g2x * mw, dh1 = g2y * mw, dh3 = -(mh[0] * g2x + mh[1] * g2y) * (mw * mw);
 #pragma unroll
@@ -1373,40 +1175,16 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
 #pragma unroll
     for (int k = 0; k < 3; k++) dL_dmeans3D[3 * (size_t)i + k] = dmean[k];
     if (scales) {
-        M3 R;
-        quat_to_R(q, R);
         const float sm[3] = { cam.scale_mod * s[0], cam.scale_mod * s[1], cam.scale_mod * s[2] };
-        M3 dSig, M2, dM;
-        dSig.m[0][0] = dcov[0]; dSig.m[0][1] = 0.5f * dcov[1]; dSig.m[0][2] = 0.5f * dcov[2];
-        dSig.m[1][0] = 0.5f * dcov[1]; dSig.m[1][1] = dcov[3]; dSig.m[1][2] = 0.5f * dcov[4];
-        dSig.m[2][0] = 0.5f * dcov[2]; dSig.m[2][1] = 0.5f * dcov[4]; dSig.m[2][2] = dcov[5];
-#pragma unroll
-        for (int cc = 0; cc < 3; cc++)
-#pragma unroll
-            for (int rr = 0; rr < 3; rr++) M2.m[cc][rr] = 2.0f * Mm.m[cc][rr];
-#pragma unroll
-        for (int cc = 0; cc < 3; cc++)
-#pragma unroll
-            for (int rr = 0; rr < 3; rr++)
-                dM.m[cc][rr] = M2.m[0][rr] * dSig.m[cc][0] + M2.m[1][rr] * dSig.m[cc][1] + M2.m[2][rr] * dSig.m[cc][2];
-        // Rt[k][j] = R[j][k], dMt[k][j] = dM[j][k]
         float ds[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) ds[k] = R.m[0][k] * dM.m[0][k] + R.m[1][k] * dM.m[1][k] + R.m[2][k] * dM.m[2][k];
+        float4 dq;
+        cov3d_backward(q, sm, Mm, dcov, ds, dq);
         if (RAW) {      // d(scaling + residual) = d_scale * scale
 #pragma unroll
             for (int k = 0; k < 3; k++) ds[k] = ds[k] * s[k];
         }
 #pragma unroll
         for (int k = 0; k < 3; k++) dL_dscale[3 * (size_t)i + k] = ds[k];
-#define D_(cc, rr) (dM.m[rr][cc] * sm[cc])
-        const float r = q[0], x = q[1], y = q[2], z = q[3];
-        float4 dq;
-        dq.x = 2.0f * z * (D_(0, 1) - D_(1, 0)) + 2.0f * y * (D_(2, 0) - D_(0, 2)) + 2.0f * x * (D_(1, 2) - D_(2, 1));
-        dq.y = 2.0f * y * (D_(1, 0) + D_(0, 1)) + 2.0f * z * (D_(2, 0) + D_(0, 2)) + 2.0f * r * (D_(1, 2) - D_(2, 1)) - 4.0f * x * (D_(2, 2) + D_(1, 1));
-        dq.z = 2.0f * x * (D_(1, 0) + D_(0, 1)) + 2.0f * r * (D_(2, 0) - D_(0, 2)) + 2.0f * z * (D_(1, 2) + D_(2, 1)) - 4.0f * y * (D_(2, 2) + D_(0, 0));
-        dq.w = 2.0f * r * (D_(0, 1) - D_(1, 0)) + 2.0f * x * (D_(2, 0) + D_(0, 2)) + 2.0f * y * (D_(1, 2) + D_(2, 1)) - 4.0f * z * (D_(1, 1) + D_(0, 0));
-#undef D_
         if (RAW) {      // d(rotation + residual) = (g - y <y, g>) / |x|,  y = x / |x|  (|x| < eps: the clamp is not differentiated)
             const float4 g = dq;
             const float nn = sqrtf(raw_x.x * raw_x.x + raw_x.y * raw_x.y + raw_x.z * raw_x.z + raw_x.w * raw_x.w);
