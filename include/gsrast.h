@@ -711,6 +711,31 @@ int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int 
                                char* geom_buffer /* gradient records: floats 0-5 and 9 are ADDED to */, const char* binning_buffer, const char* image_buffer,
                                const float* moments /* [2][H][W] */, const float* dL_ddistort /* [H][W] */, void* stream);
 
+/* Which Gaussians a pixel sees, and with what weight: each pixel's first or heaviest K contributors of one finished forward (no counterpart
+ * in the reference; the per-pixel id output many forks of it add, gsplat's rasterize_to_indices_in_range): picking the Gaussian under a
+ * cursor, finding the floater that spoils a pixel, lifting 2-D masks or labels by vote, visibility lists for editing.
+ *
+ * Definition.  Pair (pixel p, Gaussian i) CONTRIBUTES exactly as defined for gsrast_contrib_stats above; its weight is w = alpha * T, with
+ * the opacity the state carries (the GSRAST_RENDER_ANTIALIAS compensation included).  For pixel p let c_1 ... c_n be its contributors in
+ * blend order (the order of the tile's list: front to back).
+ *     count[p] = n
+ *     order = 0 ("weight")  slots 0 ... min(K, n) - 1 hold the contributors with the largest w, descending; on equal w the one earlier in
+ *                           blend order comes first.  This is the top_count rule of gsrast_contrib_stats: slot 0 is that call's "top"
+ *                           Gaussian of the pixel.
+ *     order = 1 ("depth")   slots 0 ... min(K, n) - 1 hold c_1 ... c_min(K, n).
+ * Unused slots hold id = -1 and weight = +0.0.  Ids are the caller's row numbers 0 ... P - 1.  Nothing is differentiable.
+ * ids [K][H][W] int32, weights [K][H][W] float32 and count [H][W] int32 (may be NULL: not wanted) are planar and fully overwritten;
+ * 1 <= K <= 16.  The call has no flags; of the options only exp_mode is read (pass the forward's; NULL: the process defaults).  It replays
+ * the blend from the state (csrc/gsrast_topk.h), so every w is the forward's own, bit for bit; there are no atomics and every output
+ * element has one writer: the same state gives the same bits on every run.  The three state buffers are valid for this call after the
+ * forward that filled them has been enqueued on `stream` and before a backward on them.
+ * GSRAST_E_ARG before any device work, each with a text of its own: P < 0 or R < 0, a zero-size image, K outside 1..16, order outside
+ * {0, 1}, a bad exp_mode, with P > 0 and R > 0 a NULL state buffer, a NULL ids, a NULL weights.  P == 0 or R == 0 (nothing was blended)
+ * reads no state: one small launch fills the outputs with -1 / +0.0 / 0.  The launches are not in the profile table. */
+int gsrast_pixel_contributors(const gsrast_options* options, int P, int R, int width, int height,
+                              const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                              int K, int order, int32_t* ids, float* weights, int32_t* count /* may be NULL */, void* stream);
+
 /* ---- "next" row, rank 4 (third item): Adam step of the per-Gaussian parameter groups with a PER-ROW learning rate ----
  * Replaces torch.optim.Adam(l, lr=0.0, eps=1e-15, fused=True) for the groups of scene/saro_gaussian.py:306-323 whose
  * 'lr' update_learning_rate (:345-398) sets to lr * inv_intergral, a [P,1] tensor.  One launch for up to 8 groups:

@@ -25,6 +25,7 @@
 #include "gsrast_contrib.h"
 #include "gsrast_features.h"
 #include "gsrast_distort.h"
+#include "gsrast_topk.h"
 #include "gsrast_project.h"
 #include "gsrast_exchange.h"
 
@@ -1914,6 +1915,34 @@ int gsrast_distortion_backward(const gsrast_options* options, int P, int R, int 
     ProfScope ps(K_DISTORT_BWD, s);
     pick_int<0, 1, 2>(o.exp_mode, [&](auto mode) { L.back_to_front(distort_bwd_kernel<decltype(mode)::value>, s, moments, dL_ddistort, at<float>(geom_buffer, L.grec)); });
     GS_LAUNCHED("distort_bwd");
+    return GSRAST_OK;
+}
+
+// ---- each pixel's first or heaviest K contributors of a finished forward (gsrast_topk.h) -------------------------------------------------
+int gsrast_pixel_contributors(const gsrast_options* options, int P, int R, int width, int height, const char* geom_buffer,
+                              const char* binning_buffer, const char* image_buffer, int K, int order, int32_t* ids, float* weights,
+                              int32_t* count, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0 || R < 0) return fail(GSRAST_E_ARG, "pixel_contributors: negative P or R");
+    if (width <= 0 || height <= 0) return fail(GSRAST_E_ARG, "pixel_contributors: zero-size image");
+    if (K < 1 || K > TOPK_MAX) return fail(GSRAST_E_ARG, "pixel_contributors: K must be 1..16");
+    if (order != 0 && order != 1) return fail(GSRAST_E_ARG, "pixel_contributors: order must be 0 (weight) or 1 (depth)");
+    const gsrast_options o = options ? *options : snapshot_defaults();
+    if (o.exp_mode < 0 || o.exp_mode > 2) return fail(GSRAST_E_ARG, "pixel_contributors: exp_mode must be 0, 1 or 2");
+    if (P > 0 && R > 0 && (!geom_buffer || !image_buffer || !binning_buffer)) return fail(GSRAST_E_ARG, "pixel_contributors: NULL state buffer");
+    if (!ids) return fail(GSRAST_E_ARG, "pixel_contributors: NULL ids");
+    if (!weights) return fail(GSRAST_E_ARG, "pixel_contributors: NULL weights");
+    if (P == 0 || R == 0) {                       // (no Gaussian, or no instance: nothing was blended, no state is read)
+        const size_t pixels = (size_t)width * (size_t)height, slots = pixels * (size_t)K;
+        const size_t groups = (slots + 255) / 256;
+        topk_fill_kernel<<<(unsigned)(groups < 4096 ? groups : 4096), 256, 0, s>>>(slots, pixels, ids, weights, count);
+        GS_LAUNCHED("topk_fill");
+        return GSRAST_OK;
+    }
+    const ReplayLaunch L(P, width, height, geom_buffer, binning_buffer, image_buffer);
+    launch_pixel_topk(L, o.exp_mode, s, K, order, ids, weights, count);
+    GS_LAUNCHED("pixel_topk");
     return GSRAST_OK;
 }
 

@@ -1,5 +1,5 @@
-// gsrast_replay.h -- the blend of one finished forward, walked again: what gsrast_contrib.h, gsrast_features.h and gsrast_distort.h share
-// (contrib_blend_kernel and features_fwd_kernel share the invariant and keep a body of their own: their headers say why).
+// gsrast_replay.h -- the blend of one finished forward, walked again: what gsrast_contrib.h, gsrast_features.h, gsrast_distort.h and
+// gsrast_topk.h share (contrib_blend_kernel and features_fwd_kernel share the invariant and keep a body of their own: their headers say why).
 //
 // THE REPLAY INVARIANT.  A pair (pixel p, Gaussian i) CONTRIBUTES when the forward blended it: i's position in the tile's list in force is
 // below n_contrib[p] and the pair passes the forward's nested tests (power <= 0 && power >= threshold; alpha = min(0.99, o exp(power)) >=
@@ -73,15 +73,26 @@ __device__ __forceinline__ bool replay_pixel(ReplayPixel& p, const uint2* __rest
     return true;
 }
 
+// The staged Gaussians' ids beside s0 / s1: 1 KiB of LDS that only an instantiation with IDS has
+template <bool IDS, uint32_t FB>
+__device__ __forceinline__ uint32_t* replay_staged_ids()
+{
+    if constexpr (IDS) { __shared__ uint32_t sid[FB]; return sid; }
+    else return nullptr;
+}
+
 // pair(w, b) is called in the lanes whose pixel blended the pair: w = alpha T, T in front of the pair; b its rec1.  A batch is two phases,
 // staging and walk; the barrier that separates a batch's walk from the next batch's staging sits in front of the staging.
-template <int EXPMODE, class Pair>
+// IDS (opt-in, compile time): the batch's Gaussian ids are staged too and the visitor is pair(w, b, id); without it nothing of that is
+// compiled and an instantiation is what it was before the switch existed.
+template <int EXPMODE, bool IDS = false, class Pair>
 __device__ __forceinline__ void replay_front_to_back(const ReplayPixel& p, const uint32_t* __restrict__ point_list,
                                                      const float4* __restrict__ rec0, const float4* __restrict__ rec1, Pair&& pair)
 {
     constexpr uint32_t FB = 256;                  // instances staged per batch (the forward's)
     __shared__ float4 s0[FB];
     __shared__ float4 s1[FB];
+    uint32_t* const sid = replay_staged_ids<IDS, FB>();
     const uint32_t t = p.t, n = p.n, last = p.last;
     const unsigned lane = p.lane;
     const uint32_t wave_last = replay_wave_last(last);
@@ -92,6 +103,7 @@ __device__ __forceinline__ void replay_front_to_back(const ReplayPixel& p, const
         if (i < n) {
             const uint32_t g = point_list[p.range.x + i];
             s0[t] = rec0[(size_t)REC_STRIDE * g]; s1[t] = rec1[(size_t)REC_STRIDE * g];
+            if constexpr (IDS) sid[t] = g;
         }
         __syncthreads();
         const uint32_t cnt = (n - base) < FB ? (n - base) : FB;
@@ -124,7 +136,8 @@ __device__ __forceinline__ void replay_front_to_back(const ReplayPixel& p, const
                 const uint64_t m_upd = m_contrib & ~__builtin_amdgcn_ballot_w64(test_T < 0.0001f);
                 if (m_upd == 0ull) continue;
                 if (__builtin_amdgcn_inverse_ballot_w64(m_upd)) {
-                    pair(alpha * T, b);
+                    if constexpr (IDS) pair(alpha * T, b, sid[j]);
+                    else pair(alpha * T, b);
                     T = test_T;
                 }
             }

@@ -217,6 +217,7 @@ SIGNATURES = {
     "gsrast_features_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
     "gsrast_distortion_forward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
     "gsrast_distortion_backward": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_pixel_contributors": (_ci, (_opt, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp)),
     # the projection as a call of its own (the descriptor: ProjectStruct, passed by address)
     "gsrast_project_forward": (_ci, (_vp, _vp)),
     "gsrast_project_backward": (_ci, (_vp, _vp)),
@@ -955,6 +956,64 @@ def distortion_forward(P: int, R: int, W: int, H: int, geomBuffer: torch.Tensor,
     launch("gsrast_distortion_forward", dev, C.byref(_options_struct(options=options)), int(P), int(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer),
          _ptr(imageBuffer), out.data_ptr(), moments.data_ptr())
     return out, moments
+
+
+TOPK_MAX = 16                                              # include/gsrast.h: gsrast_pixel_contributors takes 1 <= K <= 16
+TOPK_ORDERS = {"weight": 0, "depth": 1}
+
+
+def _gaussians_of_state(geomBuffer: torch.Tensor) -> int:
+    """A number of Gaussians whose geometry buffer has this one's size (0 for an empty one).  Every array of that buffer grows with P and is
+    rounded up on its own, so two P of one total size have one layout: whichever is found addresses the state like the forward's own P."""
+    nbytes = int(geomBuffer.numel())
+    if nbytes == 0:
+        return 0
+    size = lib().gsrast_geometry_bytes
+    lo, hi = 1, 1
+    while int(size(hi)) < nbytes:
+        lo, hi = hi, hi * 2
+        if hi > 1 << 30:
+            raise ValueError("pixel_contributors: geomBuffer is no forward's geometry buffer (too large)")
+    while lo < hi:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if int(size(mid)) >= nbytes else (mid + 1, hi)
+    if int(size(lo)) != nbytes:
+        raise ValueError(f"pixel_contributors: geomBuffer is no forward's geometry buffer ({nbytes} bytes)")
+    return lo
+
+
+def check_pixel_contributors(K, order) -> int:
+    """The C call's `order` (0 weight, 1 depth) of a query for K slots per pixel; ValueError for a K outside 1..TOPK_MAX or no int, and for
+    an order that is neither "weight" nor "depth" (nor the C call's 0 / 1)."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= TOPK_MAX:
+        raise ValueError(f"pixel_contributors: K must be an int in 1..{TOPK_MAX} (got {K!r})")
+    if isinstance(order, str) and order in TOPK_ORDERS:
+        return TOPK_ORDERS[order]
+    if not isinstance(order, bool) and isinstance(order, int) and order in (0, 1):
+        return order
+    raise ValueError(f"pixel_contributors: order must be 'weight' or 'depth' (got {order!r})")
+
+
+def pixel_contributors(K: int, order, R: int, W: int, H: int, geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imageBuffer: torch.Tensor, *,
+                       options: Optional[dict] = None, with_count: bool = True, P: Optional[int] = None):
+    """gsrast_pixel_contributors (include/gsrast.h) on the state any forward returned, dense or raw family: (ids [K,H,W] int32, weights
+    [K,H,W] float32, count [H,W] int32 or None without `with_count`) -- each pixel's heaviest (order "weight" / 0: descending, slot 0 the
+    `top` Gaussian of contrib_stats) or first (order "depth" / 1: blend order) K contributors, -1 / +0.0 in unused slots, and how many
+    contributors it has in all.  On the current stream, behind everything the forward enqueued there; valid until a backward runs on the
+    state.  Nothing is differentiable.  `options`: the per-call options of that forward (default: the calling thread's); `P`: that
+    forward's number of Gaussians (default: recovered from the geometry buffer's size)."""
+    order = check_pixel_contributors(K, order)
+    dev = _require_gpu(imageBuffer)
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"pixel_contributors: the image must not be empty (got {W} x {H})")
+    P = _gaussians_of_state(geomBuffer) if P is None else int(P)
+    ids = torch.empty((K, H, W), dtype=torch.int32, device=dev)
+    weights = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    count = torch.empty((H, W), dtype=torch.int32, device=dev) if with_count else None
+    launch("gsrast_pixel_contributors", dev, C.byref(_options_struct(options=options)), P, int(R), W, H, _ptr(geomBuffer), _ptr(binningBuffer),
+           _ptr(imageBuffer), K, order, ids.data_ptr(), weights.data_ptr(), None if count is None else count.data_ptr())
+    return ids, weights, count
 
 
 def _distortion_aux(distortion: Optional[tuple], dL_dacc_depth, dL_dalpha, H: int, W: int, dev: torch.device, options: Optional[dict]):

@@ -85,6 +85,11 @@ diff_gaussian_rasterization_ch3/__init__.py (cited below as REF:line):
   Its gradient needs the culled blend kernels (``options.cull != 0``, the default): ``RuntimeError`` otherwise.  With
   ``distortion=False`` nothing is launched or allocated that was not before (include/gsrast.h: gsrast_distortion_forward /
   gsrast_distortion_backward).
+* not in the reference: ``pixel_contributors(means3D, opacities, scales, rotations, raster_settings=rs, K=8, order="weight")`` -- a call of
+  its own, not a ``forward`` keyword: each pixel's heaviest (``order="weight"``) or first (``order="depth"``) K contributing Gaussians,
+  their weights alpha T and the pixel's number of contributors, as ``PixelContributors(ids[K,H,W] int32, weights[K,H,W], count[H,W]
+  int32, color, depth, radii)``; 1 <= K <= 16, unused slots hold -1 / +0.0.  One forward-only render and one replay of its blend; nothing
+  is differentiable (include/gsrast.h: gsrast_pixel_contributors; the function's docstring has the definition).
 
 The compute is in ``libgsrast_hip.so`` (hand-written HIP kernels behind the C ABI of
 ``include/gsrast.h``), reached through ``_C`` (ctypes).  There is no CPU / PyTorch fallback.
@@ -99,7 +104,7 @@ import torch.nn as nn
 
 from . import _C
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "pixel_contributors", "PixelContributors"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -341,6 +346,80 @@ class GaussianRasterizer(nn.Module):
     # camera_grads, contrib, pixel_weights, features and distortion, which arrive through **render_options (names and defaults: _parse_request).
     forward.__signature__ = inspect.Signature([q for q in inspect.signature(forward).parameters.values()
                                                if q.name not in ("return_aux", "render_options")])
+
+
+# ---- which Gaussians a pixel sees (no counterpart in the reference; include/gsrast.h: gsrast_pixel_contributors) ---------------------------
+class PixelContributors(NamedTuple):
+    """What pixel_contributors returns; every tensor is detached."""
+    ids: torch.Tensor          # [K,H,W] int32: rows of the inputs, -1 in an unused slot
+    weights: torch.Tensor      # [K,H,W] float32: alpha T of the pair, +0.0 in an unused slot
+    count: torch.Tensor        # [H,W] int32: all of the pixel's contributors, also those beyond K
+    color: torch.Tensor        # [3,H,W], depth [1,H,W], radii [P] int32: the render the query ran on
+    depth: torch.Tensor
+    radii: torch.Tensor
+
+
+def _check_query_inputs(given: list, device) -> None:
+    """pixel_contributors' own ladder over (name, tensor, shapes): every one a float32 tensor in one of its `shapes` (None: any extent), then
+    every one on `device`, a GPU; ValueError otherwise."""
+    for name, t, shapes in given:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"pixel_contributors: {name} must be a tensor (got {type(t).__name__})")
+        if not any(len(s) == t.ndim and all(w is None or w == int(n) for w, n in zip(s, t.shape)) for s in shapes):
+            want = " or ".join("[" + ", ".join("M" if w is None else str(w) for w in s) + "]" for s in shapes)
+            raise ValueError(f"pixel_contributors: {name} must be {want} (got {list(t.shape)})")
+        if t.dtype is not torch.float32:
+            raise ValueError(f"pixel_contributors: {name} must be float32 (got {t.dtype})")
+    for name, t, _ in given:
+        if not t.is_cuda:
+            raise ValueError(f"pixel_contributors: {name} must live on a GPU (got {t.device}): there is no CPU fallback")
+        if t.device != device:
+            raise ValueError(f"pixel_contributors: {name} must live on {device} (got {t.device})")
+
+
+def pixel_contributors(means3D, opacities, scales=None, rotations=None, *, raster_settings, K: int = 8, order: str = "weight",
+                       shs=None, colors_precomp=None, cov3D_precomp=None, antialiasing: bool = False) -> PixelContributors:
+    """Which Gaussians each pixel sees, and with what weight: PixelContributors(ids [K,H,W] int32, weights [K,H,W], count [H,W] int32,
+    color, depth, radii) of one view (gsplat's rasterize_to_indices_in_range, the per-pixel id output many forks of the reference add):
+    picking the Gaussian under a cursor, finding the floater that spoils a pixel, lifting 2-D masks or labels by vote, visibility lists.
+
+    A pair (pixel, Gaussian) contributes as defined under ``contrib`` in the module docstring; its weight is w = alpha T with the opacity
+    the render used (anti-aliasing compensation included).  ``count`` is the number of a pixel's contributors.  ``order="weight"``: slots
+    0 .. min(K, count) - 1 hold the contributors with the largest w, descending, on equal w the one earlier in blend order first -- slot 0
+    is the Gaussian ``contrib``'s top_count counts for the pixel.  ``order="depth"``: the slots hold the first min(K, count) contributors
+    in blend order (front to back).  Unused slots hold id -1 and weight +0.0; ids are rows of the inputs; 1 <= K <= 16.
+
+    The call runs one forward-only render under ``torch.no_grad()`` -- of ``shs`` or ``colors_precomp`` if one is given (the returned
+    colour is then a plain forward's), else of zero colours -- and the query on its state.  Inputs that require grad are accepted; nothing
+    is differentiable and every output is detached; a ``GradArena`` may be installed.  The result is bit-identical from run to run.
+    ``ValueError`` before any launch: a K outside 1..16, an order other than "weight" / "depth", a tensor on the CPU, a wrong shape or dtype,
+    both or neither of (scales, rotations) and cov3D_precomp, both shs and colors_precomp."""
+    rs = raster_settings
+    _C.check_pixel_contributors(K, order)
+    if not isinstance(means3D, torch.Tensor) or means3D.ndim != 2 or means3D.shape[1] != 3:
+        raise ValueError("pixel_contributors: means3D must be a [P, 3] tensor")
+    P, dev = int(means3D.shape[0]), means3D.device
+    H, W = int(rs.image_height), int(rs.image_width)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"pixel_contributors: the image must not be empty (got {W} x {H})")
+    if (scales is None) != (rotations is None) or (scales is None) == (cov3D_precomp is None):
+        raise ValueError("pixel_contributors: give exactly one of the (scales, rotations) pair and cov3D_precomp")
+    if shs is not None and colors_precomp is not None:
+        raise ValueError("pixel_contributors: give at most one of shs and colors_precomp")
+    given = [("means3D", means3D, ((P, 3),)), ("opacities", opacities, ((P, 1), (P,))), ("scales", scales, ((P, 3),)), ("rotations", rotations, ((P, 4),)),
+             ("cov3D_precomp", cov3D_precomp, ((P, 6),)), ("shs", shs, ((P, None, 3),)), ("colors_precomp", colors_precomp, ((P, 3),)),
+             ("raster_settings.bg", rs.bg, ((3,),)), ("raster_settings.viewmatrix", rs.viewmatrix, ((4, 4),)),
+             ("raster_settings.projmatrix", rs.projmatrix, ((4, 4),)), ("raster_settings.campos", rs.campos, ((3,), (1, 3)))]
+    _check_query_inputs([g for g in given if g[1] is not None or g[0] in ("means3D", "opacities")], dev)
+    with torch.no_grad():
+        det = lambda t: _EMPTY if t is None else t.detach()      # noqa: E731  (absent optional input: GaussianRasterizer.forward's)
+        colors = torch.zeros((P, 3), dtype=torch.float32, device=dev) if shs is None and colors_precomp is None else det(colors_precomp)
+        num_rendered, color, radii, geom_buf, bin_buf, img_buf, depth = _C.rasterize_gaussians(
+            rs.bg, means3D.detach(), colors, opacities.detach().reshape(P, 1), det(scales), det(rotations), rs.scale_modifier, det(cov3D_precomp),
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, det(shs), rs.sh_degree, rs.campos, rs.prefiltered,
+            forward_only=True, antialiasing=bool(antialiasing))
+        ids, weights, count = _C.pixel_contributors(K, order, num_rendered, W, H, geom_buf, bin_buf, img_buf, P=P)
+    return PixelContributors(ids, weights, count, color, depth, radii)
 
 
 # ---- raw-parameter module (no counterpart in the reference: SURVEY.md 8f rank 3 as written -- the activation / deformation epilogue
