@@ -2228,7 +2228,8 @@ struct BackwardRun {
     }
     // List cut (gsrast_common.h): the zero rows of the Gaussians the forward left out are written on the side stream, beside the blend
     // backward; preprocess_bwd then neither reads nor writes them.  Both kernels check on the device that the forward's cut was in force
-    // and held.  Only where it pays for the two events (large scenes), with the sparse per-Gaussian backward, in a one-phase call.
+    // and held.  Only where it pays for the two events (large scenes), with the sparse per-Gaussian backward, in the call that runs it
+    // (a one-phase call, or phase 2 of two: a backward with a feature or distortion gradient takes the grouped form like any other).
     int fork_zero_rows()
     {
         if (!plan.late_fill) return GSRAST_OK;

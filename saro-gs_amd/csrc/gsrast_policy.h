@@ -277,7 +277,7 @@ struct BackwardPlan {
     bool use_sh = false, use_sr = false;              // colours from SH coefficients; covariances from scales + rotations
     bool zero_records = false;                        // the gradient records are zero-filled (the caller does not vouch for them, or the forward was told no backward would follow)
     bool derivs = false, derivs_side_wanted = false;  // sh_dir_derivs runs (a forward_only state); ... beside the blend backward
-    bool late_fill_wanted = false;                    // the untouched Gaussians' zero rows beside the blend backward: one-phase sparse call, large scene (or list_cut_always)
+    bool late_fill_wanted = false;                    // the untouched Gaussians' zero rows beside the blend backward (phase 2 of two: beside preprocess_bwd): sparse call with the per-Gaussian backward, large scene (or list_cut_always)
     bool skip_zero_rows = false, join_in_front = false;   // experiments only (ablate 3: late fill without its kernel; 5: the join never moves behind preprocess_bwd)
     bool blend = false, from_buckets = false, tile_order = false;     // the blend backward runs (R > 0); its launch order from the forward's work buckets / from tile_order_kernel
     BlendBwdPick pick; uint32_t T = 0; int P = 0;
@@ -325,7 +325,8 @@ inline BackwardPlan plan_backward(const gsrast_options& o, const BackwardInputs&
     p.zero_records = p.do_blend && (!o.grads_zeroed || o.forward_only);
     p.derivs = p.do_blend && p.use_sh && in.D > 0 && o.forward_only;
     p.derivs_side_wanted = p.derivs && o.side_stream && in.R > 0;
-    p.late_fill_wanted = p.do_blend && p.do_geom && in.R > 0 && !o.dense_backward && o.side_stream && (in.P >= g.late_fill_min_p || g.list_cut_always);
+    // (with the per-Gaussian backward: a one-phase call, or phase 2 of two -- whose side stream then carries the zero rows beside preprocess_bwd alone)
+    p.late_fill_wanted = p.do_geom && in.R > 0 && !o.dense_backward && o.side_stream && (in.P >= g.late_fill_min_p || g.list_cut_always);
     p.skip_zero_rows = g.ablate == 3; p.join_in_front = g.ablate == 5;
     p.T = (uint32_t)((in.W + TILE_X - 1) / TILE_X) * (uint32_t)((in.H + TILE_Y - 1) / TILE_Y);
     // Pixels per lane, measured on MI355X (profiles/): with per-wave accumulator slices the backward is within 2 % for 1, 2 and 4 at 1080p

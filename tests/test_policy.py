@@ -436,7 +436,7 @@ def test_backward_plan_of_the_default_path(bplan):
 
 def test_backward_plan_late_fill_conditions(bplan):
     lost = B_LATE_FILL_WANTED | B_LATE_FILL | B_JOIN_LATE | B_GROUPED
-    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(backward_phase=2), dict(R=0), dict(P=749_999)):
+    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(R=0), dict(P=749_999)):
         v = bplan(**kw)
         assert not v & lost, kw
         assert bool(v & B_SPARSE) == ("dense_backward" not in kw)
@@ -445,13 +445,22 @@ def test_backward_plan_late_fill_conditions(bplan):
     assert bplan(P=750_000) & lost == lost
     assert bplan(P=749_999, switches=dict(late_fill_min_p=0)) & lost == lost
     assert bplan(P=1000, switches=dict(list_cut_always=1)) & lost == lost      # regained
-    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(backward_phase=2), dict(R=0)):
+    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(backward_phase=1), dict(R=0)):
         assert not bplan(P=1000, switches=dict(list_cut_always=1), **kw) & lost, kw
-    # the phases
+    # the phases: the zero rows and the grouped form belong to the call that runs the per-Gaussian backward -- phase 2 of two (a backward with a
+    # feature or distortion gradient) as well as the one-phase call, under the same conditions
     v = bplan(backward_phase=1)
     assert v & B_DO_BLEND and v & B_BLEND and v & B_ZERO_RECORDS and not v & B_DO_GEOM and bplan.grids == (0, 0)
     v = bplan(backward_phase=2)
     assert v & B_DO_GEOM and not v & (B_DO_BLEND | B_BLEND | B_ZERO_RECORDS | B_BUCKETS | B_SH_FACTOR)
+    assert v & lost == lost and v & B_SPARSE and bplan.grids == (0, (3_000_000 + 1023) // 1024)
+    assert bplan(P=749_999, backward_phase=2, switches=dict(late_fill_min_p=0)) & lost == lost
+    assert bplan(P=1000, backward_phase=2, switches=dict(list_cut_always=1)) & lost == lost
+    for kw in (dict(dense_backward=1), dict(side_stream=0), dict(R=0), dict(P=749_999)):
+        v = bplan(backward_phase=2, **kw)
+        assert not v & lost and bplan.grids[1] == (kw.get("P", 3_000_000) + 127) // 128, kw
+    v = bplan(backward_phase=2, side=0)      # no side stream to be had: wanted, not had, the ungrouped sparse kernel
+    assert v & B_LATE_FILL_WANTED and v & B_SPARSE and not v & (B_LATE_FILL | B_GROUPED | B_JOIN_LATE)
     v = bplan(R=0)
     assert v & B_DO_BLEND and v & B_ZERO_RECORDS and not v & (B_BLEND | B_BUCKETS | B_TILE_ORDER)
 
