@@ -1082,6 +1082,47 @@ int gsrast_normal_loss_backward(int W, int H, double tanfovx, double tanfovy, co
                                 const float* weight /* NULL = 1 */, const float* upstream, float* dL_dnormal_map /* NULL ok */,
                                 float* dL_ddepth /* NULL ok */, void* stream);
 
+/* ---- Mip-Splatting's 3-D smoothing filter (Yu et al., CVPR 2024): the camera sweep and the fused activation (csrc/gsrast_filter3d.h) ----
+ * The companion of GSRAST_RENDER_ANTIALIAS (the 2-D screen-space filter): every Gaussian's size is bounded below by the highest sampling
+ * rate at which any training camera sees it.  All arrays contiguous fp32 device pointers.
+ *
+ * table [C][16], one row per camera: floats 0-8 R = viewmatrix[:3,:3] row-major (viewmatrix in the render calls' transposed storage, so
+ *   p_cam = p R + T: Mip-Splatting's camera.R / camera.T), 9-11 T = viewmatrix[3,:3], 12 focal_x, 13 focal_y, 14 W, 15 H.
+ *
+ * gsrast_filter3d_compute: per row (x, y, z) of means3D [P][3] and camera, in fp32, every operation rounded, no FMA:
+ *     xc = ((x R00 + y R10) + z R20) + T0,  yc, zc with columns 1, 2;   zz = fmaxf(zc, 0.001f)
+ *     px = (xc / zz) focal_x + W 0.5f,  py = (yc / zz) focal_y + H 0.5f
+ *     seen = zc > near && zz < +inf && -(margin W) <= px <= W + margin W && -(margin H) <= py <= H + margin H
+ *   dist = min of zz over the cameras that see the row;  valid [P] (bytes 0 / 1; NULL = not wanted) = some camera sees it;
+ *   dmax = max of dist over the valid rows;  filter_3D [P] = (valid ? dist : dmax) k,  k = (float)(sqrt(variance) / focal_max) formed in
+ *   fp64;  near, margin, variance are rounded to fp32 once.  A NaN or Inf row is never valid.  No valid row: every filter_3D is +0.0.
+ *   Upstream's compute_3D_filter with near = 0.2, margin = 0.15, variance = 0.2, focal_max = the largest focal_x, except: one multiplication
+ *   by k where it divides and multiplies; the bounds W + margin W where it writes W 1.15; zeros where its max() of nothing raises.
+ *   Two launches (the sweep; the elementwise finish, once the maximum exists) and a clear of the two scratch words, all on `stream`.
+ *   The maximum is an integer max on the bits of positive floats, one writer per element, no floating-point atomics: bit-identical from
+ *   run to run and on every rank.  scratch: >= gsrast_filter3d_scratch_bytes(P, C) bytes (0 = the sizes are refused).
+ *
+ * gsrast_filter3d_apply_forward, on ACTIVATED scales [P][3] and opacities [P]:
+ *     s_f,k = sqrt(s_k s_k + f f);  r_k = s_k / s_f,k (1 where s_f,k == 0);  o_f = o ((r_0 r_1) r_2)
+ *   -- upstream's get_scaling_with_3D_filter and get_opacity_with_3D_filter (o sqrt(prod s^2 / prod (s^2 + f^2))) without the products
+ *   of squares, which underflow in fp32 for thin Gaussians.
+ * gsrast_filter3d_apply_backward recomputes s_f, r from the three inputs (nothing is saved);  q_k = f / s_f,k (0 where s_f,k == 0),
+ *   G = g_o o:   d s_k = g_s,k r_k + (G prod_{j != k} r_j) ((q_k q_k) / s_f,k),   d o = g_o ((r_0 r_1) r_2).
+ *   A NULL upstream gradient counts as zero; a NULL output is not wanted, else OVERWRITTEN; filter_3D gets no gradient.
+ *   One launch each, one lane per row, no LDS, scratch or atomics.
+ *
+ * Refused (GSRAST_E_ARG, gsrast_last_error) before any device call, one text each: P < 0; C < 1; near, variance or focal_max not finite
+ * or <= 0; margin not finite or < 0; a NULL required pointer; a NULL scratch; a backward whose gradient outputs are both NULL.
+ * P = 0 returns 0 without a launch.  The launches have no entry in the profile table. */
+size_t gsrast_filter3d_scratch_bytes(int P, int C);      /* 0: the sizes are refused (gsrast_last_error) */
+int gsrast_filter3d_compute(int P, int C, const float* means3D, const float* table, double near, double margin, double variance,
+                            double focal_max, float* filter_3D, unsigned char* valid /* may be NULL */, void* scratch, void* stream);
+int gsrast_filter3d_apply_forward(int P, const float* scales, const float* opacities, const float* filter_3D, float* scales_f,
+                                  float* opacities_f, void* stream);
+int gsrast_filter3d_apply_backward(int P, const float* scales, const float* opacities, const float* filter_3D,
+                                   const float* d_scales_f /* may be NULL */, const float* d_opacities_f /* may be NULL */,
+                                   float* d_scales /* may be NULL */, float* d_opacities /* may be NULL */, void* stream);
+
 /* ---- "next" row, rank 4 (second item): simple_knn._C.distCUDA2 ----
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (other indices; duplicates count).
  * Replaces the un-vendored dependency imported at scene/saro_gaussian.py:21 and used at :187 (scale initialisation).

@@ -12,6 +12,7 @@
 #include "gsrast_temporal.h"
 #include "gsrast_bilagrid.h"
 #include "gsrast_normal.h"
+#include "gsrast_filter3d.h"
 #include "gsrast_knn.h"
 #include "gsrast_hexplane.h"
 #include <algorithm>
@@ -1064,6 +1065,69 @@ int gsrast_normal_loss_backward(int W, int H, double tanfovx, double tanfovy, co
     if (!dL_dnormal_map && !dL_ddepth) return fail(GSRAST_E_ARG, "normal_loss_backward: dL_dnormal_map and dL_ddepth are both NULL");
     normal_loss_bwd_kernel<<<NORMAL_GRID(W, H), NM_THREADS, 0, s>>>(nm_image(W, H, tanfovx, tanfovy), normal_map, depth, weight, upstream, dL_dnormal_map, dL_ddepth);
     GS_LAUNCHED("normal_loss_bwd");
+    return GSRAST_OK;
+}
+
+// ---- Mip-Splatting's 3-D smoothing filter (gsrast_filter3d.h) ---------------------------------------------------------
+// Not in the profile kernel-name table: tools/filter3d_overhead.py times these calls with device events of its own.
+// scratch of the sweep: two ints (the bits of the largest distance, the number of seen rows), cleared on the stream by every call
+namespace {
+unsigned filter3d_grid(int P) { return (unsigned)(((size_t)P + F3_RUN - 1) / F3_RUN); }
+}  // namespace
+
+size_t gsrast_filter3d_scratch_bytes(int P, int C)
+{
+    if (P < 0) { refuse("filter3d_scratch_bytes", "negative P"); return 0; }
+    if (C < 1) { refuse("filter3d_scratch_bytes", "C must be >= 1"); return 0; }
+    return 256;
+}
+
+int gsrast_filter3d_compute(int P, int C, const float* means3D, const float* table, double near, double margin, double variance, double focal_max,
+                            float* filter_3D, unsigned char* valid, void* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const char* who = "filter3d_compute";
+    if (P < 0) return refuse(who, "negative P");
+    if (C < 1) return refuse(who, "C must be >= 1");
+    if (!std::isfinite(near) || !(near > 0.0)) return refuse(who, "near must be finite and > 0");
+    if (!std::isfinite(margin) || !(margin >= 0.0)) return refuse(who, "margin must be finite and >= 0");
+    if (!std::isfinite(variance) || !(variance > 0.0)) return refuse(who, "variance must be finite and > 0");
+    if (!std::isfinite(focal_max) || !(focal_max > 0.0)) return refuse(who, "focal_max must be finite and > 0");
+    if (P == 0) return GSRAST_OK;
+    if (!means3D || !table || !filter_3D) return refuse(who, "NULL required pointer");
+    if (!scratch) return refuse(who, "NULL scratch");
+    const float k = (float)(std::sqrt((double)(float)variance) / focal_max);      // near, margin, variance rounded to fp32 once; k in fp64, rounded once
+    int* const stats = reinterpret_cast<int*>(scratch);
+    GS_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int), s));
+    filter3d_sweep_kernel<<<std::min(filter3d_grid(P), (unsigned)F3_SWEEP_WGS), F3_RUN, 0, s>>>(P, C, (float)near, (float)margin, means3D, table, filter_3D, stats);
+    GS_LAUNCHED("filter3d_sweep");
+    filter3d_finish_kernel<<<filter3d_grid(P), F3_RUN, 0, s>>>(P, k, stats, filter_3D, valid);      // (a launch of its own: the maximum must exist first)
+    GS_LAUNCHED("filter3d_finish");
+    return GSRAST_OK;
+}
+
+int gsrast_filter3d_apply_forward(int P, const float* scales, const float* opacities, const float* filter_3D, float* scales_f, float* opacities_f,
+                                  void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return refuse("filter3d_apply_forward", "negative P");
+    if (P == 0) return GSRAST_OK;
+    if (!scales || !opacities || !filter_3D || !scales_f || !opacities_f) return refuse("filter3d_apply_forward", "NULL required pointer");
+    filter3d_apply_fwd_kernel<<<filter3d_grid(P), F3_RUN, 0, s>>>(P, scales, opacities, filter_3D, scales_f, opacities_f);
+    GS_LAUNCHED("filter3d_apply_fwd");
+    return GSRAST_OK;
+}
+
+int gsrast_filter3d_apply_backward(int P, const float* scales, const float* opacities, const float* filter_3D, const float* d_scales_f,
+                                   const float* d_opacities_f, float* d_scales, float* d_opacities, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (P < 0) return refuse("filter3d_apply_backward", "negative P");
+    if (!d_scales && !d_opacities) return refuse("filter3d_apply_backward", "d_scales and d_opacities are both NULL");
+    if (P == 0) return GSRAST_OK;
+    if (!scales || !opacities || !filter_3D) return refuse("filter3d_apply_backward", "NULL required pointer");
+    filter3d_apply_bwd_kernel<<<filter3d_grid(P), F3_RUN, 0, s>>>(P, scales, opacities, filter_3D, d_scales_f, d_opacities_f, d_scales, d_opacities);
+    GS_LAUNCHED("filter3d_apply_bwd");
     return GSRAST_OK;
 }
 

@@ -229,6 +229,11 @@ SIGNATURES = {
     "gsrast_normal_loss_scratch_bytes": (_sz, (_ci, _ci)),
     "gsrast_normal_loss_forward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp)),
     "gsrast_normal_loss_backward": (_ci, (_ci, _ci, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    # Mip-Splatting's 3-D smoothing filter: the camera sweep, the fused activation
+    "gsrast_filter3d_scratch_bytes": (_sz, (_ci, _ci)),
+    "gsrast_filter3d_compute": (_ci, (_ci, _ci, _vp, _vp, _cd, _cd, _cd, _cd, _vp, _vp, _vp, _vp)),
+    "gsrast_filter3d_apply_forward": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "gsrast_filter3d_apply_backward": (_ci, (_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
     # the multi-GPU gradient exchange
     "gsrast_sh_grad_combine": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _cf, _vp, _vp)),
     "gsrast_sh_grad_combine_rows": (_ci, (_ci, _ci, _ci, _ci, _vp, _vp, _sz, _ci, _vp, _cf, _vp, _vp, _vp, _vp)),
