@@ -10,16 +10,21 @@ def run_hip(rast, scene, cam, device, dL_dcolor=None, colors_precomp=None, cov3D
             tile_clip=0):
     """tile_clip=0: the reference's literal tile lists (every tile of the 3-sigma square), so keys / point_list /
     ranges / n_contrib can be compared entry by entry.  tile_clip=1 is the product default (lists without the tiles the
-    alpha >= 1/255 ellipse cannot reach): same outputs, shorter lists -- see check_clipped_lists."""
+    alpha >= 1/255 ellipse cannot reach): same outputs, shorter lists -- see check_clipped_lists.
+
+    Two forwards.  The EXPORT forward -- a direct _C.rasterize_gaussians with no_list_cut = 1 and debug_state = 1 -- is the one whose state
+    gsrast_debug_export copies out: every Gaussian listed, every Gaussian's colour evaluated, cov3D kept.  It is a diagnostic plan: under
+    debug_state the forward never takes the list cut's compacting colour kernel (gsrast_policy.h: ForwardPlan::pose_answer) and keeps the
+    predicted cut's mass table in the call's own buffer.  The MODULE call -- the one whose image and gradients the caller compares -- runs
+    with debug_state = 0: the plan a user of the product gets, under whatever list cut the context holds for the pose.  Both must give the
+    same image, radii and depth bit for bit."""
     _C = rast._C
     _C.set_option("exp_mode", exp_mode)
     _C.set_option("tile_clip", tile_clip)
-    _C.set_option("debug_state", 1)         # the forward also keeps cov3D for debug_export (the product default does not store it)
     try:
         return _run_hip(rast, scene, cam, device, dL_dcolor, colors_precomp, cov3D_precomp)
     finally:
         _C.set_option("tile_clip", 1)
-        _C.set_option("debug_state", 0)
 
 
 def _run_hip(rast, scene, cam, device, dL_dcolor, colors_precomp, cov3D_precomp):
@@ -60,14 +65,17 @@ def _run_hip(rast, scene, cam, device, dL_dcolor, colors_precomp, cov3D_precomp)
     # the early Gaussians only and a completed tile's range lies in the point list's second half; the module call below may run under one,
     # and must produce the same image bit for bit)
     _C.set_option("no_list_cut", 1)
+    _C.set_option("debug_state", 1)         # the forward also keeps cov3D for debug_export (the product default does not store it)
     try:
         R, color0, radii0, gb, bb, ib, depth0 = _C.rasterize_gaussians(*args)
+        out = {"R": R}
+        if P > 0:
+            st = _C.debug_export(P, R, rs.image_width, rs.image_height, gb, bb, ib)
+            out.update({k: v.cpu().numpy() for k, v in st.items()})
     finally:
         _C.set_option("no_list_cut", 0)
-    out = {"R": R}
+        _C.set_option("debug_state", 0)     # the module call below runs the product plan
     if P > 0:
-        st = _C.debug_export(P, R, rs.image_width, rs.image_height, gb, bb, ib)
-        out.update({k: v.cpu().numpy() for k, v in st.items()})
         out["keys_sorted"] = out["keys_sorted"].view(np.uint64)
         out["point_list"] = out["point_list"].view(np.uint32)
         out["ranges"] = out["ranges"].view(np.uint32)

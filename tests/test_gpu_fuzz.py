@@ -27,7 +27,11 @@ def _config(seed, large=False):
 @pytest.mark.parametrize("seed", range(100, 112))
 def test_random_configuration_at_bucket_sort_sizes(seed, orc, scenes, rast, gpu, scatter_form):
     """The same sweep at Gaussian counts that take the bucket depth sort (P >= 32768) -- the context carries its capacity hints from
-    one random configuration to the next, so undersized speculative launches and their repeats are part of it."""
+    one random configuration to the next, so undersized speculative launches and their repeats are part of it.
+
+    The compared render (gpu_harness.run_hip's module call) runs the product plan, debug_state = 0: the repeated clip = 1 pass comes back to a
+    pose whose cut depths the pass before left, so it runs `cut_colors` -- the compacting colour kernel on the early Gaussians only, with
+    colors_precomp, cov3D_precomp, SH degrees 0-2 and odd image sizes as the seed draws them."""
     # ... and so are the list cut's depths (include/gsrast.h: options.no_list_cut), forced on here: the seven camera poses come back with
     # another scene each time, so cut lists that hold, cut lists that are too short (the forward falls back inside the call) and stale
     # entries of another image size all occur; every render after a pose's first one is checked exactly like the first

@@ -3,6 +3,7 @@
 * The table is complete: every pick_int<...> / pick_bool( of saro-gs_amd/csrc/gsrast_capi.hip and gsrast_train.hip is found, the values of
   the picks around each dispatch site are the table's, every product of values is a row and every row is such a product.  A new
   instantiation without a row, and a row without an instantiation, turn this red (as tests/test_capi_abi.py pins the signature table).
+* The colour half's if / else dispatch (color_kernels) holds exactly the launch sites and calls of the table's COLOR_LAUNCHES / COLOR_CALLS.
 * The switches select what the row says: gsrast_debug_forward_plan / gsrast_debug_backward_plan under the row's switches
   (tests/test_policy.py drives the same two calls).
 * The feature widths of tests/test_gpu_variants.py visit every chunk as a first pass and as the last pass behind a full 32.
@@ -99,6 +100,52 @@ def test_the_table_has_no_row_without_a_site_and_names_tests_that_exist():
     assert {L for _, _, L in bm.GRIDS} | {16} == {r.args[0] for r in vt.rows_of("bilagrid_bwd_grid")} and "GRIDS = bm.GRIDS + [(64, 64, 16)]" in texts["tests/test_gpu_bilagrid.py"]
     m = re.search(r'parametrize\("W,H,C,mm", \[(.*?)\]\)\n@pytest.mark.parametrize\("scatter", \[0, 1\]\)\ndef test_single_plane_against_oracle', texts["tests/test_hexplane.py"], re.S)
     assert {int(t.split(",")[2]) for t in re.findall(r"\(([^()]*)\)", m.group(1))} == {r.args[0] for r in vt.rows_of("hex_grad_tex_sorted")}
+
+
+def test_the_colour_dispatch_is_the_tables(sources):
+    """color_kernels (gsrast_capi.hip) is a seven-way if / else, no pick: its launch texts, in source order, and the calls of color_kernels are
+    exactly variant_table.COLOR_LAUNCHES / COLOR_CALLS -- a new launch site or call cannot appear without a row -- no colour kernel is
+    launched anywhere else, and every row names a test case that exists."""
+    text = sources[vt.CAPI]
+    launch = re.compile(r"\b(preprocess_color_\w*kernel(?:<[^<>]*>)?)\s*<<<")
+    head = "int color_kernels(" + vt.COLOR_KERNELS_SIGNATURE + ")"
+    assert text.count(head) == 1
+    a = text.index(head)
+    b = text.index("int launch_color(", a)
+    body = text[a:b]
+    assert body.rstrip().endswith("}") and body.count("{") == body.count("}"), "color_kernels no longer ends where this test cuts it"
+    assert tuple(launch.findall(body)) == tuple(r.launch for r in vt.COLOR_LAUNCHES)
+    assert len(launch.findall(text)) == len(vt.COLOR_LAUNCHES), "a colour kernel is launched outside color_kernels"
+    calls = re.findall(r"\bcolor_kernels\(([^()]*)\)", text)
+    assert tuple(calls) == (vt.COLOR_KERNELS_SIGNATURE,) + tuple(r.args for r in vt.COLOR_CALLS)
+    assert text.count("color_kernels") == len(calls), "color_kernels is named somewhere this test does not parse"
+    # no other source file launches a colour kernel or calls color_kernels
+    csrc = os.path.join(ROOT, os.path.dirname(vt.CAPI))
+    for f in sorted(os.listdir(csrc)):
+        if os.path.join(os.path.dirname(vt.CAPI), f) == vt.CAPI:
+            continue
+        with open(os.path.join(csrc, f)) as fh:
+            other = vt.strip_comments(fh.read())
+        assert not launch.search(other) and "color_kernels(" not in other, f
+    # the kernels the launches name are the ones gsrast_preprocess.h defines: none is defined without a launch
+    with open(os.path.join(csrc, "gsrast_preprocess.h")) as fh:
+        defined = set(re.findall(r"^(preprocess_color_\w*kernel)\(", vt.strip_comments(fh.read()), re.M))
+    assert defined == {r.launch.split("<")[0] for r in vt.COLOR_LAUNCHES}
+    # every row names a test function, and a parametrisation id, that the named file holds
+    texts = {}
+    for r in vt.COLOR_LAUNCHES + vt.COLOR_CALLS:
+        path, name = r.test.split("::")
+        if path not in texts:
+            with open(os.path.join(ROOT, path)) as fh:
+                texts[path] = fh.read()
+        m = re.fullmatch(r"(\w+)(?:\[(\w+)\])?", name)
+        assert m and re.search(rf"^def {m.group(1)}\(", texts[path], re.M) and "pytest.mark.gpu" in texts[path], r.test
+        if m.group(2) is not None:      # the id is one of the names the test itself is parametrised with
+            p = re.search(rf'parametrize\("name", (\w+|list\(CASES\))\)\ndef {m.group(1)}\(', texts[path])
+            assert p, r.test
+            ids = re.search(r"^CASES = \{(.*?)^\}", texts[path], re.M | re.S) if p.group(1) == "list(CASES)" else re.search(rf"^{p.group(1)} = \((.*?)\)$", texts[path], re.M)
+            assert ids and f'"{m.group(2)}"' in ids.group(1), r.test
+    assert len({r.launch for r in vt.COLOR_LAUNCHES}) == 7 and len({r.args for r in vt.COLOR_CALLS}) == 3
 
 
 # ---- 2. the switches select what the row says ----------------------------------------------------------------------------------------------

@@ -6,6 +6,10 @@ options and process-wide A/B switches alike) and the Python keywords that select
 tests/test_variants_host.py parses the two translation units and asserts that the value lists found there are exactly this table's, and
 that the switches select what the row says (gsrast_debug_forward_plan / gsrast_debug_backward_plan); tests/test_gpu_variants.py runs the rows.
 
+The forward's colour half dispatches with a plain if / else, which no pick shows: COLOR_LAUNCHES and COLOR_CALLS below list its seven launch
+sites and the three calls of color_kernels, each with the case of tests/test_gpu_cut_colours.py that reaches it; test_variants_host.py
+asserts that the source holds exactly these.
+
 The two `ablate` instantiations of blend_bwd_kernel and the `mutate` kernel are experiments and have no row (OUT_OF_SCOPE names their
 dispatch, and the standalone projection's, whose two instantiations tests/test_gpu_project.py runs)."""
 import contextlib
@@ -121,6 +125,31 @@ def _rows():
 
 
 ROWS = _rows()
+
+# ---- the colour half of the forward: no pick, a seven-way if / else (gsrast_capi.hip: color_kernels) -------------------------------------------------
+# One row per launch text inside color_kernels, in source order: the text, what selects it, and the -m gpu test id that runs it against the oracle.
+# The two compacting launches run under the list cut only (plan.cut_colors: never under debug_state); the other five are what a forward
+# without a cut takes -- visit 0 of every case of tests/test_gpu_cut_colours.py -- and what colours the whole set after a redo.
+ColorLaunch = namedtuple("ColorLaunch", "launch when test")
+ColorCall = namedtuple("ColorCall", "args what test")
+CUT = "tests/test_gpu_cut_colours.py::"
+COLOR_LAUNCHES = (
+    ColorLaunch("preprocess_color_compact_kernel<true>", "list cut, raw leaves", CUT + "test_cut_colours_against_the_oracle[raw_M4_deg1_shs_res]"),
+    ColorLaunch("preprocess_color_compact_kernel<false>", "list cut, shs or colors_precomp", CUT + "test_cut_colours_against_the_oracle[shs_M16_deg3]"),
+    ColorLaunch("preprocess_color_kernel<PP_SH_MAX, true>", "raw leaves, M = 16", "tests/test_gpu_raw.py::test_raw_rasterizer_against_epilogue_then_rasterizer_and_the_oracles"),
+    ColorLaunch("preprocess_color_kernel<0, true>", "raw leaves, M < 16", CUT + "test_cut_colours_against_the_oracle[raw_M4_deg1]"),
+    ColorLaunch("preprocess_color_kernel<PP_SH_MAX, false>", "shs, M = 16, aligned", CUT + "test_cut_colours_against_the_oracle[shs_M16_deg0]"),
+    ColorLaunch("preprocess_color_kernel<0, false>", "shs, M < 16, rows a multiple of four floats, aligned", CUT + "test_cut_colours_against_the_oracle[shs_M4_deg1]"),
+    ColorLaunch("preprocess_color_direct_kernel", "colors_precomp, M > 16, rows no multiple of four floats, an unaligned base",
+                CUT + "test_cut_colours_against_the_oracle[shs_M16_deg3_unaligned]"),
+)
+# the calls of color_kernels(stream, early_only, pred), in source order
+COLOR_CALLS = (
+    ColorCall("side ? side->stream : s, plan.cut_colors, nullptr", "the forward's colour launch: the early Gaussians only under a cut", CUT + "test_cut_colours_against_the_oracle[colors_precomp]"),
+    ColorCall("s, true, pred", "the completion pass: the late candidates' colours, predicated, over skip2", CUT + "test_fallback_colours_the_late_gaussians[shs_M25_deg3]"),
+    ColorCall("s, false, nullptr", "in front of a redo (exact_redo) under cut_colors: every Gaussian, the plain kernels", CUT + "test_redo_colours_every_gaussian[colors_precomp]"),
+)
+COLOR_KERNELS_SIGNATURE = "hipStream_t cs, bool early_only, const uint32_t* pred"
 
 
 def rows_of(site):
