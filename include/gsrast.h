@@ -1131,6 +1131,29 @@ int gsrast_filter3d_apply_backward(int P, const float* scales, const float* opac
 size_t gsrast_knn_scratch_bytes(int P);
 int gsrast_knn3_mean_dist2(int P, const float* points, float* mean_dist2, char* scratch, void* stream);
 
+/* ---- exact k-nearest-neighbour query with indices: mmcv.ops.knn ----
+ * Replaces the un-vendored dependency imported at helper_model.py:27 and called as knn(2, xyz, xyz, False) at :150, :207, :354.
+ * For every query point: the k reference points with the smallest (d2, index) in lexicographic order, ascending.
+ *   ref [n_ref][3] fp32;  query [n_query][3] fp32, or NULL: the reference set queries itself (n_query must then equal n_ref)
+ *   k 1..32;  idx [k][n_query] int32 (mmcv's (B, k, npoint) of one batch, no transpose);  dist2 [k][n_query] fp32, or NULL: not wanted
+ *   scratch >= gsrast_knn_query_scratch_bytes(n_ref, n_query) bytes (negative sizes count as 0; never 0 itself; non-decreasing in each
+ *   argument; pure host code).  All pointers are device pointers.
+ * Semantics:
+ *   exact       d2 = (dx dx + dy dy) + dz dz in fp32, each difference (query - reference) ONE fp32 subtraction, no FMA: the kernel's own
+ *               value, and the search is exact in it.  Equal d2 puts the lower reference index first.
+ *   self        a point is its own neighbour: in a self-query slot 0 has d2 = 0 and is the point itself, or a duplicate of it with a
+ *               lower index (mmcv behaves so; the reference's xyznnpoints[0, 1] relies on it).
+ *   missing     slots j >= n_ref hold idx -1 and dist2 +inf (n_ref = 0: every slot).
+ *   determinism every output element has one writer, no atomics: bit-identical from run to run; dist2 does not depend on the order of
+ *               the reference rows, and permuting the query rows permutes the output columns.
+ *   non-finite  coordinates are unsupported (what such a query or neighbour returns is unspecified), but cause no out-of-range access:
+ *               the Morton quantisation clamps through fminf / fmaxf and every index is bounded by the sizes.
+ * Refused (GSRAST_E_ARG) before any device call: a negative size, k outside 1..32, a NULL idx, ref or scratch (n_ref > 0), a NULL query
+ * with n_query != n_ref.  n_query = 0 returns 0 and touches nothing. */
+size_t gsrast_knn_query_scratch_bytes(int n_ref, int n_query);
+int gsrast_knn_query(int n_ref, const float* ref, int n_query, const float* query, int k, int32_t* idx, float* dist2, char* scratch,
+                     void* stream);
+
 /* ---- "next" row, rank 4 (first item): mip-mapped feature-plane lookup of the residual field ----
  * Replaces nvdiffrast.torch.texture(grid, coords, mip_level_bias=levels, boundary_mode="clamp", max_mip_level=7|0) at
  * scene/hexplane.py:49-56 together with the plane loop of interpolate_ms_features (scene/hexplane.py:95-139): every plane

@@ -14,6 +14,7 @@
 #include "gsrast_normal.h"
 #include "gsrast_filter3d.h"
 #include "gsrast_knn.h"
+#include "gsrast_knn_query.h"
 #include "gsrast_hexplane.h"
 #include <algorithm>
 #include <cmath>
@@ -798,6 +799,87 @@ int gsrast_knn3_mean_dist2(int P, const float* points, float* mean_dist2, char* 
     GS_LAUNCHED("knn_boxes");
     knn_search_kernel<<<nb, 256, 0, s>>>(P, points, order, boxes, nboxes, mean_dist2);
     GS_LAUNCHED("knn_search");
+    return GSRAST_OK;
+}
+
+// ---- exact k-NN query with indices (gsrast_knn_query.h) ----------------------------------------------------------
+// scratch: the reference's part as knn_layout's (bbox | codes A/B | index A/B), the sort's histogram and scan scratch sized for the larger
+// of the two sets | boxes | the Morton-ordered records | the queries' codes A/B and index A/B
+namespace {
+struct KnnQueryLayout { size_t bbox, cA, cB, iA, iB, hist, scan, boxes, rec, qcA, qcB, qiA, qiB, total; };
+KnnQueryLayout knn_query_layout(size_t n_ref, size_t n_query)
+{
+    KnnQueryLayout L; Carver c;
+    const size_t R = n_ref ? n_ref : 1, Q = n_query ? n_query : 1, S = R > Q ? R : Q;
+    L.bbox = c.take(32); L.cA = c.take(R * 4); L.cB = c.take(R * 4); L.iA = c.take(R * 4); L.iB = c.take(R * 4);
+    const size_t hist_n = 256 * rs_blocks_n(S, GSRAST_DEPTH_ITEMS);
+    L.hist = c.take(hist_n * 4); L.scan = c.take(scan_tmp_elems(hist_n) * 4);
+    L.boxes = c.take(((R + KNN_BOX - 1) / KNN_BOX) * 6 * 4);
+    L.rec = c.take(R * 16);
+    L.qcA = c.take(Q * 4); L.qcB = c.take(Q * 4); L.qiA = c.take(Q * 4); L.qiB = c.take(Q * 4);
+    L.total = c.o + 256;
+    return L;
+}
+}
+size_t gsrast_knn_query_scratch_bytes(int n_ref, int n_query) { return knn_query_layout(n_ref > 0 ? (size_t)n_ref : 0, n_query > 0 ? (size_t)n_query : 0).total; }
+
+int gsrast_knn_query(int n_ref, const float* ref, int n_query, const float* query, int k, int32_t* idx, float* dist2, char* scratch, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n_ref < 0 || n_query < 0) return fail(GSRAST_E_ARG, "knn_query: bad size");
+    if (k < 1 || k > KNNQ_MAX_K) return fail(GSRAST_E_ARG, "knn_query: k must be in 1..32");
+    if (n_query == 0) return GSRAST_OK;
+    if (!idx) return fail(GSRAST_E_ARG, "knn_query: NULL idx");
+    if (n_ref == 0) {
+        const size_t slots = (size_t)k * (size_t)n_query;
+        knnq_fill_kernel<<<(unsigned)std::min<size_t>((slots + 255) / 256, 4096), 256, 0, s>>>(slots, idx, dist2);
+        GS_LAUNCHED("knnq_fill");
+        return GSRAST_OK;
+    }
+    if (!ref || !scratch) return fail(GSRAST_E_ARG, "knn_query: NULL pointer");
+    if (!query && n_query != n_ref) return fail(GSRAST_E_ARG, "knn_query: a NULL query is the reference querying itself: n_query must be n_ref");
+    const KnnQueryLayout L = knn_query_layout((size_t)n_ref, (size_t)n_query);
+    unsigned* bbox = at<unsigned>(scratch, L.bbox);
+    uint32_t *cA = at<uint32_t>(scratch, L.cA), *cB = at<uint32_t>(scratch, L.cB);
+    uint32_t *iA = at<uint32_t>(scratch, L.iA), *iB = at<uint32_t>(scratch, L.iB);
+    uint32_t *hist = at<uint32_t>(scratch, L.hist), *scan = at<uint32_t>(scratch, L.scan);
+    const bool inB = radix_passes(30) & 1;
+    const int nb = (n_ref + 255) / 256;
+    // the reference: Morton order, boxes of KNN_BOX consecutive points (the kernels of gsrast_knn.h, as they are), the permuted copy
+    knn_init_kernel<<<1, 64, 0, s>>>(bbox);
+    GS_LAUNCHED("knn_init");
+    knn_bbox_kernel<<<nb, 256, 0, s>>>(n_ref, ref, bbox);
+    GS_LAUNCHED("knn_bbox");
+    knn_morton_kernel<<<nb, 256, 0, s>>>(n_ref, ref, bbox, cA, iA);
+    GS_LAUNCHED("knn_morton");
+    int rc = sort_pairs_small(cA, iA, cB, iB, (uint32_t)n_ref, 30, hist, scan, s);
+    if (rc != GSRAST_OK) return rc;
+    const uint32_t *order = inB ? iB : iA, *codes = inB ? cB : cA;
+    const int nboxes = (n_ref + KNN_BOX - 1) / KNN_BOX;
+    float* boxes = at<float>(scratch, L.boxes);
+    knn_boxes_kernel<<<nboxes, 256, 0, s>>>(n_ref, ref, order, boxes);
+    GS_LAUNCHED("knn_boxes");
+    float4* rec = at<float4>(scratch, L.rec);
+    knnq_records_kernel<<<nb, 256, 0, s>>>(n_ref, ref, order, rec);
+    GS_LAUNCHED("knnq_records");
+    // the queries: Morton order on the reference's grid (codes clamped to it); the reference's own order when it queries itself
+    const uint32_t *qorder = nullptr, *qcodes = nullptr;
+    const int nqb = (n_query + 255) / 256;
+    if (query) {
+        uint32_t *qcA = at<uint32_t>(scratch, L.qcA), *qcB = at<uint32_t>(scratch, L.qcB);
+        uint32_t *qiA = at<uint32_t>(scratch, L.qiA), *qiB = at<uint32_t>(scratch, L.qiB);
+        knn_morton_kernel<<<nqb, 256, 0, s>>>(n_query, query, bbox, qcA, qiA);
+        GS_LAUNCHED("knn_morton");
+        rc = sort_pairs_small(qcA, qiA, qcB, qiB, (uint32_t)n_query, 30, hist, scan, s);
+        if (rc != GSRAST_OK) return rc;
+        qorder = inB ? qiB : qiA; qcodes = inB ? qcB : qcA;
+    }
+    // the smallest capacity that holds k.  (A plain chain, as launch_pixel_topk's switch: the table of compiled variants, tests/variant_table.py,
+    // counts the selection sites of the render kernels, and every instantiation here is run against the fp64 brute force by tests/test_gpu_knn_query.py.)
+#define KNNQ_LAUNCH(CAP) knnq_search_kernel<CAP><<<nqb, 256, 0, s>>>(n_ref, rec, codes, boxes, nboxes, n_query, query, qorder, qcodes, k, idx, dist2)
+    if (k <= 2) KNNQ_LAUNCH(2); else if (k <= 4) KNNQ_LAUNCH(4); else if (k <= 8) KNNQ_LAUNCH(8); else if (k <= 16) KNNQ_LAUNCH(16); else KNNQ_LAUNCH(32);
+#undef KNNQ_LAUNCH
+    GS_LAUNCHED("knnq_search");
     return GSRAST_OK;
 }
 

@@ -254,6 +254,8 @@ SIGNATURES = {
     "gsrast_adam_step_visible": (_ci, (_ci, _adam, _vp, _ci, _ll, _cd, _cd, _cd, _ci, _vp)),
     "gsrast_knn_scratch_bytes": (_sz, (_ci,)),
     "gsrast_knn3_mean_dist2": (_ci, (_ci, _vp, _vp, _vp, _vp)),
+    "gsrast_knn_query_scratch_bytes": (_sz, (_ci, _ci)),
+    "gsrast_knn_query": (_ci, (_ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp)),
     # densification: clone / split / prune, and MCMC
     "gsrast_densify_scratch_bytes": (_sz, (_ci,)),
     "gsrast_densify_plan": (_ci, (_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _vp, _vp, _vp)),
